@@ -15,10 +15,19 @@ and the launcher then starts the ranks ONCE more with `--comm torch` (fresh proc
 `python -m torch.distributed.run ... bench.py --gpus N` (WORLD_SIZE set) it is a rank.  `--dry-launch` prints the
 child command lines and environment instead of starting them.
 
-Rank 0 prints ONE short JSON line (< 2 KB: the contract fields, `roofline`, `cpu_baseline`, `bf16`, `comm` when
-distributed) and writes everything else — per-kernel-family and per-layer tables (one row per SURVEY 8a row and direction),
+Rank 0 prints ONE short JSON line (< 2 KB: the contract fields, `roofline`, `comm` when distributed, and with --full
+`cpu_baseline` and `bf16`) and writes everything else — per-kernel-family and per-layer tables (one row per SURVEY 8a row and direction),
 the CPU baseline table, per-bucket all-reduce times, notes — to the side file named in the line's `detail` field
 (default bench_detail.json next to this file, or under gpurun_out/ when that directory exists).
+
+A plain run (`bench.py --gpus N --steps K --warmup W`) does only what the headline figure needs: set-up, W untimed steps,
+exactly K timed steps, the outputs if --dump-outputs is given, the line.  Everything that takes runs of its own moves behind
+--full: the instrumented pass behind `kernels` / `layers` / --dump-launches, the `bf16` block, the `cpu_baseline` leg and
+the side file (a plain run writes one only when --detail names it).  `roofline` stays in the plain line: its events sit in the
+last 2 timed steps, as they always have, so `value` and `ms_per_step` mean what they did before --full existed.
+  --dump-outputs DIR   after the timed steps, what the last one computed as DIR/<name>.npy (output_arrays: float32, or
+                       float64 where the path computes in float64; fixed seeded samples of large outputs; <= 64 MB in all).
+                       The inputs and initial weights are seeded, so two builds run with the same arguments can be compared.
 
   value / dtype: the fp32 step (BASELINE configs[1]); never the bf16 figure.
   roofline     : the dominant kernel family of the step (default arithmetic: the fp32 Winograd 3x3 kernel
@@ -54,6 +63,7 @@ import subprocess
 import sys
 import tempfile
 import time
+import zlib
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 for p in (ROOT, os.path.join(ROOT, "dl-unet_amd")):
@@ -105,7 +115,17 @@ def parse_args(argv=None):
     ap.add_argument("--share-gpu", action="store_true",
                     help="rehearsal on a box with fewer GPUs than ranks: rank r uses device r %% visible devices, gloo rendezvous, "
                          "torch all-reduce (RCCL refuses two ranks on one device); never a scaling measurement")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the instrumented per-kernel / per-layer pass, the bf16 block, "
+                         "the CPU baseline, the side file (a plain run: set-up, warm-up, the timed steps, the line)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (see output_arrays)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_launches and not args.full:
+        ap.error("--dump-launches comes from the instrumented pass: add --full")
+    return args
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -268,6 +288,60 @@ def split_line(full, detail_path=None):
         for k in ("kernel_time_sum_ms_per_step", "effective_step_tflops", "summary"):
             line.pop(k, None)
     return line, full
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# --dump-outputs
+# ------------------------------------------------------------------------------------------------------------------
+DUMP_BYTES = 64 << 20                # all files of one --dump-outputs together
+DUMP_ELEMS = 1 << 22                 # an output with more elements is written as a fixed, seeded sample of this many
+PARAM_SAMPLE = 1 << 15               # elements sampled from each parameter tensor (the same positions in `params` and `grads`)
+
+
+def sample_index(n, k, name):
+    """Sorted positions of a fixed sample of k of n elements (k < n): the same for every run with the same name, n and k."""
+    import numpy as np
+    rng = np.random.default_rng(zlib.crc32(name.encode()))
+    return np.sort(rng.choice(n, size=k, replace=False))
+
+
+def _host_array(v, name, k):
+    """torch tensor / numpy value -> numpy array: float64 stays float64, everything else becomes float32 (integers only
+    while float32 holds them exactly); more than k elements -> the flat sample_index(numel, k, name) of them."""
+    import numpy as np
+    import torch
+    t = v.detach() if isinstance(v, torch.Tensor) else torch.as_tensor(np.asarray(v))
+    if t.numel() > k:
+        t = t.reshape(-1)[torch.from_numpy(sample_index(t.numel(), k, name)).to(t.device)]
+    if t.dtype != torch.float64:
+        if not t.is_floating_point() and t.numel():
+            assert int(t.abs().max()) < 1 << 24, "%s: integers beyond float32's exact range" % name
+        t = t.float()
+    return t.cpu().numpy()
+
+
+def output_arrays(res, params=None):
+    """What a step returned to its caller ({name: tensor | array}) as {name: numpy array} (_host_array, outputs of more than
+    DUMP_ELEMS elements sampled).  With `params` (the training workloads) also the parameters the step's SGD left and the
+    gradients it used: PARAM_SAMPLE fixed positions of each tensor, concatenated in parameter order as `params` / `grads`."""
+    import numpy as np
+    out = {name: _host_array(v, name, DUMP_ELEMS) for name, v in res.items() if v is not None}
+    if params is not None:
+        ps = list(params)
+        out["params"] = np.concatenate([_host_array(p, "param%d" % i, PARAM_SAMPLE).reshape(-1) for i, p in enumerate(ps)])
+        out["grads"] = np.concatenate([_host_array(p.grad, "param%d" % i, PARAM_SAMPLE).reshape(-1) for i, p in enumerate(ps)])
+    return out
+
+
+def dump_outputs(path, arrays):
+    """arrays ({name: numpy array}) -> path/<name>.npy; refuses more than DUMP_BYTES in all."""
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BYTES:
+        raise RuntimeError("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_BYTES))
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def csrc_sha():
@@ -553,7 +627,7 @@ def run_rank(args):
             loss, masks = hip_optim.bce_argmax_step(logits, labels)      # L1 + L2 in one pass: loss, its gradient, argmax masks
             loss.backward()
             opt.step()
-            return masks, loss
+            return {"logits": logits, "masks": masks, "loss": loss}
         workload = "batch=%d/GPU 572x572x1 fwd+bwd+SGD %s, 64-base-ch U-Net (BASELINE %s)" % (
             B, "fp32" if args.math in (0, 3) else "bf16 compute", "configs[1]" if args.math in (0, 3) else "configs[2] per-GPU work")
         metric, loss_name = "572x572 tiles/sec fwd+bwd", "unweighted BCE-with-logits"
@@ -586,8 +660,8 @@ def run_rank(args):
             preds, loss, labels = trainer._step_loss(net, images, labels, dev, True)      # trainer.py:58-75
             loss.backward()
             opt.step()
-            trainer._first_sample_metrics(preds, labels)                                  # trainer.py:82-89 (host sync, as there)
-            return None, loss
+            metrics = trainer._first_sample_metrics(preds, labels)                        # trainer.py:82-89 (host sync, as there)
+            return {"images": images, "preds": preds, "labels": labels, "loss": loss, "metrics": metrics}
         workload = ("batch=%d 512x512-shaped samples -> 700x700 inputs, training()-shaped step with GPU augmentation "
                     "(rotation + elastic + class_balance), fp32, 64-base-ch U-Net (BASELINE configs[3])" % B)
         metric, loss_name = "700x700 tiles/sec fwd+bwd incl. augmentation", "class-balance weighted BCE-with-logits (trainer.py:72-75)"
@@ -603,7 +677,7 @@ def run_rank(args):
                 xin = data.test_input(imgs)                                               # data.py:184-188 mirror pad + normalise
                 y = net(xin)
                 mask, stats = hip_optim.crop_argmax_metrics(y, labels)                    # tester.py:29-42
-            return mask, stats
+            return {"logits": y, "masks": mask, "stats": stats}
         workload = ("batch=%d 1024x1024 images -> 1212x1212 overlap-tile inputs, forward + crop/argmax/IoU/pixel-error counts, fp32, "
                     "32-base-ch U-Net (BASELINE configs[4])" % B)
         metric, loss_name = "1212x1212 tiles/sec forward (overlap-tile inference)", "none (inference)"
@@ -653,10 +727,13 @@ def run_rank(args):
         return tmax.item(), stats, nsample, res
 
     dom = "wino" if args.math == 3 and args.config != 5 else "igemm"
-    dt, dom_stats, nsample, (masks, loss) = timed_region(args.steps, args.warmup, dom)
+    dt, dom_stats, nsample, res = timed_region(args.steps, args.warmup, dom)
+    if args.dump_outputs and rank == 0:                    # before anything below steps the model again
+        dump_outputs(args.dump_outputs, output_arrays(res, net.parameters() if training_step else None))
 
     psteps = 0
-    if timing:                                             # every rank: the steps contain the collectives
+    instrumented = timing and args.full
+    if instrumented:                                       # every rank: the steps contain the collectives
         psteps = max(1, min(3, args.steps))
         L.unet_profile_reset(); L.unet_profile_select(0xFFFFFFFF); L.unet_profile_enable(1)
         for _ in range(psteps):
@@ -678,7 +755,7 @@ def run_rank(args):
             "vs_baseline": None, "dtype": {0: "f32", 1: "bf16x3", 2: "bf16", 3: "f32"}[args.math],
             "data": "synthetic",
             "config": {"workload": workload, "arithmetic": arith, "global_batch": B * world, "tile": S_in, "parallelism": "dp%d" % world,
-                       "loss": loss_name, "final_loss": float(loss.item()) if training_step else None},
+                       "loss": loss_name, "final_loss": float(res["loss"].item()) if training_step else None},
             "effective_step_tflops": flops_step / (dt / args.steps) / 1e12,
         }
         if use_dist:
@@ -689,7 +766,6 @@ def run_rank(args):
                            "rccl_version": int(L.unet_dp_rccl_version()), "message_mb": 124.1, "buckets": 6,
                            "self_launched": os.environ.get("BENCH_SELF_LAUNCHED") == "1"}
         if timing:
-            fam = read_families()                           # the instrumented pass (psteps steps)
             ms0, n0, fl0, ex0, by0 = dom_stats              # the dominant family, in the timed region
             peak = PEAK_TFLOPS[args.math]
             ach = ex0 / (ms0 * 1e-3) / 1e12 if ms0 > 0 else 0.0
@@ -712,6 +788,8 @@ def run_rank(args):
                                "sampled_steps": nsample,
                                "exec_gflop_per_launch": ex0 / max(n0, 1) / 1e9, "alg_gflop_per_launch": fl0 / max(n0, 1) / 1e9,
                                "share_of_step_time": (ms0 / nsample) / (dt / args.steps * 1e3)}
+        if instrumented:
+            fam = read_families()                           # the instrumented pass (psteps steps)
             out["kernels"] = {k: {"ms_per_step": v[0] / psteps, "launches_per_step": v[1] / psteps,
                                   "exec_tflops": (v[3] / (v[0] * 1e-3) / 1e12 if v[0] > 0 and v[3] > 0 else None),
                                   "effective_tflops": (v[2] / (v[0] * 1e-3) / 1e12 if v[0] > 0 and v[2] > 0 else None),
@@ -748,7 +826,7 @@ def run_rank(args):
                                   "weakest": out["weakest_rows"][:1]}
 
     # ---- the same step with bf16 tensors (BASELINE configs[2]): its own warm-up, >= 10 timed steps, its own family's roofline -------
-    bf16_on = args.config == 2 and args.math == 3 and not args.no_bf16 and args.bf16_steps > 0
+    bf16_on = args.full and args.config == 2 and args.math == 3 and not args.no_bf16 and args.bf16_steps > 0
     if bf16_on:
         _hip.check(L.unet_set_math(2), "unet_set_math")
         nb = max(10, args.bf16_steps)
@@ -766,7 +844,7 @@ def run_rank(args):
                             "share_of_step_time": (st_b[0] / ns_b) / (dtb / nb * 1e3)})
             out["bf16"] = blk
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.config == 2:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.config == 2:
         def gpu_logits_in(mode):
             def fn(params_np, x_np):
                 # the same weights and tile through the HIP path, in the given arithmetic mode
@@ -824,17 +902,18 @@ def run_rank(args):
         dist.destroy_process_group()
     sys.stdout.flush()
     if rank == 0:
-        dpath = args.detail
-        if not dpath:
+        dpath = args.detail                                # a plain run writes a side file only when --detail names one
+        if not dpath and args.full:
             gdir = os.path.join(ROOT, "gpurun_out")
             dpath = os.path.join(gdir if os.path.isdir(gdir) else ROOT, "bench_detail.json")
-        line, detail = split_line(out, os.path.relpath(dpath, ROOT) if dpath.startswith(ROOT) else dpath)
-        try:
-            with open(dpath, "w") as f:
-                json.dump(detail, f, indent=1)
-        except OSError as e:
-            sys.stderr.write("bench.py: cannot write %s (%s); the tables follow on stderr\n" % (dpath, e))
-            line.pop("detail", None)
+        line, detail = split_line(out, dpath and (os.path.relpath(dpath, ROOT) if dpath.startswith(ROOT) else dpath))
+        if dpath:
+            try:
+                with open(dpath, "w") as f:
+                    json.dump(detail, f, indent=1)
+            except OSError as e:
+                sys.stderr.write("bench.py: cannot write %s (%s); the tables follow on stderr\n" % (dpath, e))
+                line.pop("detail", None)
         # a compact per-layer table for whoever reads the log
         for r in out.get("layers", []):
             sys.stderr.write("%-16s %-4s %7.3f ms  mfma %.3f  hbm %.3f  %s\n" % (r["row"], r["survey"] or "", r["ms_per_step"], r["mfma_frac"] or 0.0,

@@ -352,3 +352,46 @@ def test_bench_tables_from_a_synthetic_launch_dump():
     assert bench.layer_table([fast], 1, 3)[0]["bound"] == "hbm+mall" and bench.layer_table([rows[2]], 1, 3)[0]["bound"] == "hbm"
     w = bench.weakest_rows(bench.layer_table([r for r in rows if r["kind"] != "6"], 2, 3), 1)
     assert w[0]["row"] == "pool1.bwd" and abs(w[0]["frac"] - 0.6) < 1e-9
+
+
+def test_bench_plain_run_options():
+    """A plain run is lean: --full (the instrumented pass, bf16 block, CPU baseline, side file) is off by default; --steps
+    sets the timed steps and must be >= 1; --dump-launches comes from the instrumented pass and so needs --full."""
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    a = bench.parse_args(["--full", "--dump-outputs", "out", "--dump-launches", "l.csv"])
+    assert a.full and a.dump_outputs == "out" and a.dump_launches == "l.csv"
+    for bad in (["--steps", "0"], ["--dump-launches", "l.csv"]):
+        with pytest.raises(SystemExit):
+            bench.parse_args(bad)
+
+
+def test_bench_dump_outputs_are_fixed_samples_within_the_limit(tmp_path):
+    """bench.output_arrays / dump_outputs: small outputs whole, large ones a seeded sample that is the same in every run,
+    float64 kept, everything else float32, integers exact; parameters and gradients sampled at the same positions; the
+    64 MB limit is enforced."""
+    import bench
+    g = torch.Generator().manual_seed(0)
+    big = torch.rand(bench.DUMP_ELEMS + 1000, generator=g)
+    res = {"logits": torch.rand(2, 2, 8, 8, generator=g), "masks": torch.randint(0, 2, (2, 8, 8), generator=g),
+           "loss": torch.tensor(0.25), "metrics": np.array([[0.5], [0.125]]), "big": big, "none": None}
+    p = torch.nn.Parameter(torch.rand(bench.PARAM_SAMPLE * 3, generator=g))
+    p.grad = -2 * p.detach()
+    out = bench.output_arrays(res, [p])
+    assert set(out) == {"logits", "masks", "loss", "metrics", "big", "params", "grads"}
+    assert out["logits"].dtype == np.float32 and np.array_equal(out["logits"], res["logits"].numpy())
+    assert out["masks"].dtype == np.float32 and np.array_equal(out["masks"], res["masks"].numpy())
+    assert out["loss"].shape == () and out["loss"] == np.float32(0.25)
+    assert out["metrics"].dtype == np.float64 and np.array_equal(out["metrics"], res["metrics"])
+    idx = bench.sample_index(big.numel(), bench.DUMP_ELEMS, "big")
+    assert np.array_equal(idx, bench.sample_index(big.numel(), bench.DUMP_ELEMS, "big")) and np.all(np.diff(idx) > 0)
+    assert idx.size == bench.DUMP_ELEMS and np.array_equal(out["big"], big.numpy()[idx])
+    assert out["params"].size == bench.PARAM_SAMPLE and np.array_equal(out["grads"], -2 * out["params"])
+    assert np.array_equal(bench.output_arrays(res, [p])["big"], out["big"])
+    bench.dump_outputs(str(tmp_path / "d"), out)
+    for name, a in out.items():
+        assert np.array_equal(np.load(tmp_path / "d" / (name + ".npy")), a)
+    with pytest.raises(RuntimeError):
+        bench.dump_outputs(str(tmp_path / "e"), {"x": np.zeros(bench.DUMP_BYTES // 4 + 1, np.float32)})
+    assert not os.path.exists(tmp_path / "e")

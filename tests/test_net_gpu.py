@@ -820,7 +820,7 @@ def test_bench_self_launch_two_ranks_on_this_gpu(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     detail = os.path.join(tmp_path, "detail.json")
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--share-gpu", "--steps", "2", "--warmup", "1", "--batch", "1",
-                          "--detail", detail], env=env, capture_output=True, text=True, timeout=900)
+                          "--full", "--detail", detail], env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1 and len(lines[0]) < 2048, out.stdout[-2000:]
@@ -829,3 +829,40 @@ def test_bench_self_launch_two_ranks_on_this_gpu(tmp_path):
     assert d["comm"]["self_launched"] is True and d["comm"]["ranks"] == 2 and "gloo" in d["comm"]["gradient_allreduce"]
     assert d["value"] > 0 and "roofline" in d and "cpu_baseline" not in d            # the CPU baseline belongs to the N = 1 line
     assert len(json.load(open(detail))["layers"]) > 50
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_last_step(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR`: exactly K timed steps, the contract fields and nothing that
+    takes runs of its own (no CPU baseline, bf16 block or side file), and DIR/<name>.npy holding what the last timed step
+    computed - logits, the argmax masks of those logits, the loss the line reports, parameters and gradients."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    dump = os.path.join(tmp_path, "out")
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "1",
+                          "--dump-outputs", dump], env=env, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, out.stdout[-2000:]
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline"):
+        assert k in d, k
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["dtype"] == "f32" and d["unit"] == "tiles/s"
+    assert abs(d["value"] * d["ms_per_step"] / 1e3 - 1) < 1e-3                       # 1 tile per step
+    assert "cpu_baseline" not in d and "bf16" not in d and "detail" not in d
+    files = sorted(os.listdir(dump))
+    assert files == ["grads.npy", "logits.npy", "loss.npy", "masks.npy", "params.npy"], files
+    assert sum(os.path.getsize(os.path.join(dump, f)) for f in files) <= 64 << 20
+    a = {f[:-4]: np.load(os.path.join(dump, f)) for f in files}
+    assert a["logits"].shape == (1, 2, 388, 388) and a["logits"].dtype == np.float32 and np.isfinite(a["logits"]).all()
+    assert np.array_equal(a["masks"].reshape(-1), (a["logits"][:, 1] > a["logits"][:, 0]).reshape(-1).astype(np.float32))
+    # the loss is the unweighted BCE-with-logits of these logits against bench.py's seeded labels (drawn after the input)
+    g = torch.Generator().manual_seed(1)
+    torch.rand(1, 1, 572, 572, generator=g)
+    lab = (torch.rand(1, 1, 388, 388, generator=g) >= 0.5).numpy().astype(np.float64)
+    z, t = a["logits"].astype(np.float64), np.concatenate([1 - lab, lab], axis=1)
+    ref = (np.maximum(z, 0) - z * t + np.log1p(np.exp(-np.abs(z)))).mean()
+    assert abs(float(a["loss"]) - ref) <= 1e-5 * abs(ref), (float(a["loss"]), ref)
+    assert a["params"].shape == a["grads"].shape and np.isfinite(a["grads"]).all() and np.abs(a["grads"]).max() > 0
