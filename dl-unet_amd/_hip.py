@@ -65,6 +65,8 @@ _SIGS = {
     "unet_mirror_pad": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
     "unet_eval_masks": (C.c_int, [vp, C.c_long, C.c_long, C.c_long, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp]),
     "unet_class_balance": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
+    "unet_weighted_map_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "unet_weighted_map": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, vp, vp, vp, vp, vp]),
     "unet_gaussian_filter": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_float, vp, vp, vp]),
     "unet_warp_bilinear": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]),
     "unet_rotate_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int]),

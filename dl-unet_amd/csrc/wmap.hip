@@ -1,0 +1,281 @@
+// wmap.hip — the U-Net border weight map (Ronneberger et al. 2015, eq. 2; functions.py:7-78), batched, on the device:
+//   w = w_c + w0 * exp(-(d1 + d2)^2 / (2 sig2)) on background,  w = 1 on cells,
+// d1 / d2 = exact Euclidean distance to the nearest / second-nearest distinct 4-connected foreground component.
+//
+//   1. ccl_local   one workgroup per 32x32 tile: union-find in LDS, every pixel -> its tile-local root (image index)
+//   2. ccl_merge   one thread per tile-border pixel pair: union of the two roots with agent-scope atomics
+//   3. ccl_flatten label = root (the smallest pixel index of the component), component count per image
+//   4. wmap_cols   per pixel, along its column within +-R: nearest foreground (dist_a, label_a), nearest label != label_a (dist_b)
+//   5. wmap_rows   per pixel, over the column results within +-R in x: d1^2, d2^2, then the weight
+//
+// Exactness bound: for s = d1 + d2 > R with R = ceil(sqrt(2 sig2 * 104)), expf(-s^2 / (2 sig2)) underflows (e^-104 < 2^-150),
+// so a component farther than R from a pixel cannot change that pixel's weight; every component within R is found
+// exactly by passes 4-5, whose cost depends on R and not on how many components an image has.
+//
+// Coherence (MI355X: per-XCD L2s are not coherent, a CU's L1 is never refreshed by other CUs' stores): in ccl_merge
+// every read and every update of a parent word is an agent-scope atomic read-modify-write; foreground tests there
+// read the input labels, never the parent words.  Every other hand-off is across a kernel boundary.
+#include "common.hpp"
+#include <cmath>
+#include "../../include/unet_hip.h"
+
+namespace unet {
+
+static constexpr int WM_TILE = 32;          // ccl_local tile edge
+static constexpr int WM_ROWS = 256;         // wmap_rows pixels per workgroup
+static constexpr unsigned WM_NONE = 0xffffu;
+
+__device__ __forceinline__ bool wm_fg(const void *labels, int dtype, size_t e)
+{
+    return dtype == 0 ? ((const long long *)labels)[e] != 0 : ((const float *)labels)[e] != 0.f;
+}
+
+// ---- 1. tile-local union-find --------------------------------------------------------------------------
+__device__ __forceinline__ int lds_find(int *lp, int p)
+{
+    for (;;) {
+        const int q = __hip_atomic_load(&lp[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (q == p) return p;
+        p = q;
+    }
+}
+__device__ __forceinline__ void lds_union(int *lp, int a, int b)
+{
+    for (;;) {
+        a = lds_find(lp, a);
+        b = lds_find(lp, b);
+        if (a == b) return;
+        if (a > b) { const int t = a; a = b; b = t; }
+        int expect = b;                   // link the larger root under the smaller one, only while it is still a root
+        if (__hip_atomic_compare_exchange_strong(&lp[b], &expect, a, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP))
+            return;
+        b = expect;
+    }
+}
+
+__global__ __launch_bounds__(256) void ccl_local_kernel(const void *__restrict__ labels, int dtype, int H, int W,
+                                                        int *__restrict__ parent, unsigned long long *__restrict__ counts)
+{
+    __shared__ int lp[WM_TILE * WM_TILE];
+    const int b = blockIdx.z, x0 = blockIdx.x * WM_TILE, y0 = blockIdx.y * WM_TILE;
+    const size_t img = (size_t)b * H * W;
+    bool fg[4];
+    unsigned long long n1 = 0;
+    for (int k = 0; k < 4; ++k) {
+        const int i = threadIdx.x + 256 * k, x = x0 + (i & 31), y = y0 + (i >> 5);
+        fg[k] = x < W && y < H && wm_fg(labels, dtype, img + (size_t)y * W + x);
+        lp[i] = fg[k] ? i : -1;
+        n1 += fg[k];
+    }
+    __syncthreads();
+    for (int k = 0; k < 4; ++k) {
+        const int i = threadIdx.x + 256 * k;
+        if (!fg[k]) continue;
+        if ((i & 31) && lp[i - 1] >= 0) lds_union(lp, i - 1, i);        // the sign of a word never changes: plain read
+        if (i >= 32 && lp[i - 32] >= 0) lds_union(lp, i - 32, i);
+    }
+    __syncthreads();
+    for (int k = 0; k < 4; ++k) {
+        const int i = threadIdx.x + 256 * k, x = x0 + (i & 31), y = y0 + (i >> 5);
+        if (x >= W || y >= H) continue;
+        int r = -1;
+        if (fg[k]) { const int l = lds_find(lp, i); r = (y0 + (l >> 5)) * W + x0 + (l & 31); }
+        parent[img + (size_t)y * W + x] = r;
+    }
+    for (int d = 32; d >= 1; d >>= 1) n1 += __shfl_xor(n1, d, 64);
+    if ((threadIdx.x & 63) == 0 && n1) atomicAdd(&counts[b], n1);
+}
+
+// ---- 2. merge across tile borders: agent-scope atomics only ----------------------------------------------
+__device__ __forceinline__ int gl_read(int *p) { return __hip_atomic_fetch_or(p, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ int gl_find(int *P, int p)
+{
+    for (;;) {
+        const int q = gl_read(&P[p]);
+        if (q == p) return p;
+        p = q;
+    }
+}
+__device__ __forceinline__ void gl_union(int *P, int a, int b)
+{
+    for (;;) {
+        a = gl_find(P, a);
+        b = gl_find(P, b);
+        if (a == b) return;
+        if (a > b) { const int t = a; a = b; b = t; }
+        int expect = b;
+        if (__hip_atomic_compare_exchange_strong(&P[b], &expect, a, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+            return;
+        b = expect;
+    }
+}
+
+// per image: (tiles_x - 1) vertical borders of H pixel pairs, then (tiles_y - 1) horizontal borders of W pairs
+__global__ __launch_bounds__(256) void ccl_merge_kernel(const void *__restrict__ labels, int dtype, int H, int W, int *parent,
+                                                        int nv, int total)
+{
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= total) return;
+    const size_t img = (size_t)blockIdx.y * H * W;
+    int a, c;
+    if (e < nv) {
+        const int y = e % H, x = (e / H + 1) * WM_TILE;
+        a = y * W + x - 1; c = y * W + x;
+    } else {
+        const int x = (e - nv) % W, y = ((e - nv) / W + 1) * WM_TILE;
+        a = (y - 1) * W + x; c = y * W + x;
+    }
+    if (wm_fg(labels, dtype, img + a) && wm_fg(labels, dtype, img + c)) gl_union(parent + img, a, c);
+}
+
+// ---- 3. flatten: label = root; a root is a component -------------------------------------------------
+__global__ __launch_bounds__(256) void ccl_flatten_kernel(const int *__restrict__ parent, int *__restrict__ label, size_t npx,
+                                                          int *__restrict__ n_objects)
+{
+    const int b = blockIdx.y;
+    const int *P = parent + (size_t)b * npx;
+    int roots = 0;
+    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < npx; e += (size_t)gridDim.x * blockDim.x) {
+        int p = P[e];
+        if (p >= 0) {
+            while (P[p] != p) p = P[p];
+            roots += p == (int)e;
+        }
+        label[(size_t)b * npx + e] = p;
+    }
+    for (int d = 32; d >= 1; d >>= 1) roots += __shfl_xor(roots, d, 64);
+    if ((threadIdx.x & 63) == 0 && roots) atomicAdd(&n_objects[b], roots);
+}
+
+// ---- 4. column pass: nearest foreground (dist_a, label_a) and nearest label != label_a (dist_b) within +-R ------
+__global__ __launch_bounds__(256) void wmap_cols_kernel(const int *__restrict__ label, int H, int W, int R,
+                                                        int *__restrict__ col_label, unsigned *__restrict__ col_dist)
+{
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= W || y >= H) return;
+    const int *L = label + (size_t)blockIdx.z * H * W + x;
+    int la = L[(size_t)y * W];
+    unsigned da = la >= 0 ? 0u : WM_NONE, db = WM_NONE;
+    for (int k = 1; k <= R && db == WM_NONE; ++k) {
+        if (y - k < 0 && y + k >= H) break;
+        for (int s = 0; s < 2; ++s) {
+            const int yy = s ? y + k : y - k;
+            if (yy < 0 || yy >= H) continue;
+            const int v = L[(size_t)yy * W];
+            if (v < 0) continue;
+            if (da == WM_NONE) { la = v; da = k; }
+            else if (v != la && db == WM_NONE) db = k;
+        }
+    }
+    const size_t o = ((size_t)blockIdx.z * H + y) * W + x;
+    col_label[o] = la;
+    col_dist[o] = da | (db << 16);
+}
+
+// ---- 5. row pass + weight -----------------------------------------------------------------------------------
+// Running (b1, L1, b2) over the columns: b1 = least squared distance seen, L1 its label, b2 = least squared distance
+// of a label != L1.  A column is (vA, LA) and vB, the least squared distance of a label != LA; the columns are visited
+// by increasing |dx|, and once dx^2 >= b2 no later column can change either distance.
+__global__ __launch_bounds__(WM_ROWS) void wmap_rows_kernel(const int *__restrict__ col_label, const unsigned *__restrict__ col_dist,
+                                                            int H, int W, int R, int dtype, float w0, float sig2,
+                                                            const unsigned long long *__restrict__ counts,
+                                                            const int *__restrict__ n_objects, float *__restrict__ w)
+{
+    extern __shared__ unsigned wm_lds[];
+    unsigned *sd = wm_lds;
+    int *sl = (int *)(wm_lds + WM_ROWS + 2 * R);
+    const int b = blockIdx.z, y = blockIdx.y, x0 = blockIdx.x * WM_ROWS;
+    const size_t row = ((size_t)b * H + y) * W;
+    for (int i = threadIdx.x; i < WM_ROWS + 2 * R; i += WM_ROWS) {
+        const int xx = x0 - R + i;
+        const bool in = xx >= 0 && xx < W;
+        sd[i] = in ? col_dist[row + xx] : (WM_NONE | (WM_NONE << 16));
+        sl[i] = in ? col_label[row + xx] : -1;
+    }
+    __syncthreads();
+    const int x = x0 + threadIdx.x;
+    if (x >= W) return;
+    const int c = threadIdx.x + R;
+    if ((sd[c] & 0xffffu) == 0) { w[row + x] = 1.f; return; }          // a cell: w_c = counts[1] / counts[1], w_d = 0
+
+    const int nobj = n_objects[b];
+    const unsigned INF = 0xffffffffu;
+    unsigned b1 = INF, b2 = INF;
+    int L1 = -1;
+    for (int dx = 0; dx <= R; ++dx) {
+        const unsigned dx2 = (unsigned)(dx * dx);
+        if (dx2 >= b2 || (nobj == 1 && dx2 >= b1)) break;
+        for (int s = 0; s < (dx ? 2 : 1); ++s) {
+            const int j = s ? c + dx : c - dx;
+            const unsigned d = sd[j], da = d & 0xffffu, db = d >> 16;
+            if (da == WM_NONE) continue;
+            const unsigned va = dx2 + da * da, vb = db == WM_NONE ? INF : dx2 + db * db;
+            const int la = sl[j];
+            if (la == L1) { b1 = min(b1, va); b2 = min(b2, vb); }
+            else if (va < b1) { b2 = min(b1, vb); b1 = va; L1 = la; }
+            else b2 = min(b2, va);
+        }
+    }
+    const float n1 = (float)counts[b], n0 = (float)((size_t)H * W - counts[b]);
+    float wc = n1 / n0;                                      // counts[1] / counts[0] ...
+    if (dtype == 0) wc = truncf(wc);                         // ... stored in torch.empty_like(gt): int64 labels truncate
+    float wd = 0.f;
+    if (b1 != INF && (nobj == 1 || b2 != INF)) {
+        const float s = sqrtf((float)b1) + (nobj == 1 ? 0.f : sqrtf((float)b2));
+        if (s <= (float)R) wd = w0 * expf(-(s * s) / (2.f * sig2));
+    }
+    w[row + x] = wc + wd;
+}
+
+static int wmap_radius(float sig2)
+{
+    return (int)std::ceil(std::sqrt(2.0 * (double)sig2 * 104.0));
+}
+
+} // namespace unet
+
+using namespace unet;
+
+static size_t wm_plane(int B, int H, int W) { return align_up((size_t)B * H * W * sizeof(int), 256); }
+
+size_t unet_weighted_map_scratch_bytes(int B, int H, int W)
+{
+    if (B <= 0 || H <= 0 || W <= 0) return 0;
+    return 3 * wm_plane(B, H, W);
+}
+
+int unet_weighted_map(const void *labels, int labels_dtype, int B, int H, int W, float w0, float sig2, void *weights_f32,
+                      void *counts_u64, void *n_objects_i32, void *scratch, void *stream)
+{
+    ARG_CHECK(labels && weights_f32 && counts_u64 && n_objects_i32 && scratch && B > 0 && H > 0 && W > 0,
+              "unet_weighted_map: bad argument");
+    ARG_CHECK(labels_dtype == 0 || labels_dtype == 1, "unet_weighted_map: labels_dtype must be 0 (int64) or 1 (float32)");
+    ARG_CHECK((size_t)H * W < (1u << 31) && H <= 65535 && B <= 65535, "unet_weighted_map: image too large");
+    ARG_CHECK(std::isfinite(w0) && std::isfinite(sig2) && sig2 > 0.f, "unet_weighted_map: need finite w0 and sig2 > 0");
+    const int R = wmap_radius(sig2);
+    ARG_CHECK(R <= 1024, "unet_weighted_map: sig2 %g gives a reach of %d px (at most 1024)", (double)sig2, R);
+    hipStream_t st = (hipStream_t)stream;
+    const size_t npx = (size_t)H * W;
+    char *s = (char *)scratch;
+    int *parent = (int *)s, *label = (int *)(s + wm_plane(B, H, W));
+    unsigned *col_dist = (unsigned *)(s + 2 * wm_plane(B, H, W));
+    int *col_label = parent;                                  // the parent words are dead after ccl_flatten
+    HIP_TRY(hipMemsetAsync(counts_u64, 0, (size_t)B * sizeof(unsigned long long), st));
+    HIP_TRY(hipMemsetAsync(n_objects_i32, 0, (size_t)B * sizeof(int), st));
+
+    const int tx = cdiv(W, WM_TILE), ty = cdiv(H, WM_TILE);
+    hipLaunchKernelGGL(ccl_local_kernel, dim3(tx, ty, B), dim3(256), 0, st, labels, labels_dtype, H, W, parent,
+                       (unsigned long long *)counts_u64);
+    const int nv = (tx - 1) * H, total = nv + (ty - 1) * W;
+    if (total > 0)
+        hipLaunchKernelGGL(ccl_merge_kernel, dim3(cdiv(total, 256), B), dim3(256), 0, st, labels, labels_dtype, H, W, parent, nv, total);
+    hipLaunchKernelGGL(ccl_flatten_kernel, dim3((unsigned)std::min<size_t>((npx + 255) / 256, 1024), B), dim3(256), 0, st, (const int *)parent, label, npx, (int *)n_objects_i32);
+    hipLaunchKernelGGL(wmap_cols_kernel, dim3(cdiv(W, 64), cdiv(H, 4), B), dim3(256), 0, st, (const int *)label, H, W, R,
+                       col_label, col_dist);
+    const size_t lds = (size_t)(WM_ROWS + 2 * R) * 2 * sizeof(unsigned);
+    hipLaunchKernelGGL(wmap_rows_kernel, dim3(cdiv(W, WM_ROWS), H, B), dim3(WM_ROWS), lds, st, (const int *)col_label,
+                       (const unsigned *)col_dist, H, W, R, labels_dtype, w0, sig2, (const unsigned long long *)counts_u64,
+                       (const int *)n_objects_i32, (float *)weights_f32);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}

@@ -2,16 +2,44 @@
 
 input_size_compute / evaluation_metrics / IoU / Pixel_error / class_balance keep the reference's
 names, arguments and results (functions.py:82-213).  They are host-side bookkeeping on labels and
-388^2 masks (SURVEY §2 rows 5,7,8: out of scope as kernels); weighted_map needs OpenCV, which this
-image does not have, and is dead code at run time in the reference (quirk Q3).
+388^2 masks (SURVEY §2 rows 5,7,8: out of scope as kernels).  weighted_map (functions.py:7-78, the paper's
+border-weighted loss map) runs on the device only (unet_weighted_map); the reference's own OpenCV path has no
+host counterpart here.
 """
 import numpy as np
 import torch
 
 
-def weighted_map(gt_batch):
-    raise NotImplementedError("weighted_map needs OpenCV (cv2.connectedComponents / distanceTransform), absent in this "
-                              "image; the reference never reaches it at run time (trainer.py:68 `is` comparison, SURVEY Q3)")
+def weighted_map(gt_batch, *, w0=20, sig2=25, return_objects=False):
+    """Border weight map of Ronneberger et al. 2015, eq. 2 (functions.py:7-78) for {0,1} labels [B,H,W] on a HIP device:
+    1 on cells; on background w_c + w0 * exp(-(d1 + d2)^2 / (2 sig2)), d1 / d2 the exact distances to the nearest and
+    second-nearest distinct 4-connected cell (d2 = 0 when the image has one).  w_c = count(1) / count(0) takes the
+    label's dtype as in the reference (torch.empty_like(gt)): truncated for integer labels (DESIGN Q9), fp32 for float
+    labels.  Returns float32 [B,H,W] (and the int32 [B] component counts with return_objects=True).  A one-class image
+    raises IndexError as the reference does at counts[1]; host tensors raise NotImplementedError (no CPU path)."""
+    if not gt_batch.is_cuda:
+        raise NotImplementedError("weighted_map runs on the HIP device only (unet_weighted_map): move the labels to the "
+                                  "device first, e.g. weighted_map(gt_batch.cuda()); there is no CPU implementation")
+    import _hip
+    if gt_batch.dim() != 3:
+        raise ValueError("weighted_map takes labels [B,H,W], got %s" % (tuple(gt_batch.shape),))
+    gt = gt_batch.contiguous()
+    if gt.is_floating_point():
+        gt, code = gt.float(), 1
+    else:
+        gt, code = gt.long(), 0
+    B, H, W = gt.shape
+    w = torch.empty(B, H, W, dtype=torch.float32, device=gt.device)
+    counts = torch.empty(B, dtype=torch.int64, device=gt.device)
+    n_objects = torch.empty(B, dtype=torch.int32, device=gt.device)
+    if B * H * W == 0:
+        raise IndexError("index 1 is out of bounds for dimension 0 with size 0")
+    scratch = torch.empty(_hip.lib().unet_weighted_map_scratch_bytes(B, H, W), dtype=torch.uint8, device=gt.device)
+    _hip.run("unet_weighted_map", gt.device, _hip.ptr(gt), code, B, H, W, float(w0), float(sig2), _hip.ptr(w), _hip.ptr(counts),
+             _hip.ptr(n_objects), _hip.ptr(scratch))
+    if bool(((counts == 0) | (counts == H * W)).any()):      # the reference indexes counts[1]: a one-class image raises
+        raise IndexError("index 1 is out of bounds for dimension 0 with size 1")
+    return (w, n_objects) if return_objects else w
 
 
 def class_balance(gt_batch):

@@ -7,6 +7,7 @@
     update (L3)        SGD(lr=1e-4, momentum=0.99)          -> unet_sgd_momentum
     prediction (L2)    preds.argmax(dim=1) + IoU/PE        -> unet_eval_masks (fused crop+argmax+counts)
     weight map (N3)    class_balance(labels)               -> unet_class_balance
+    (loss_weights='border') weighted_map(labels)                -> unet_weighted_map
 
 Reference behaviours kept on purpose: Q3 the dataset-name comparisons are IDENTITY tests
 against string literals in the reference (trainer.py:18-27,68,110): a name arriving from argv never
@@ -23,7 +24,7 @@ from time import time
 import numpy as np
 import torch
 
-from functions import class_balance, metrics_from_counts
+from functions import class_balance, metrics_from_counts, weighted_map
 import optim as hip_optim
 
 
@@ -68,12 +69,15 @@ def _goal_for(DATASET):
     return None, None
 
 
-def _step_loss(unet, images, labels, device, train):
+_LOSS_WEIGHTS = {'class_balance': class_balance, 'border': weighted_map}
+
+
+def _step_loss(unet, images, labels, device, train, weight_fn=class_balance):
     preds = unet(images.to(device))
     labels = labels.to(device)                                  # everything below stays on the device
     pad = int((preds.shape[-1] - labels.shape[-1]) / 2)
     preds = preds[:, :, pad:labels.shape[-1] + pad, pad:labels.shape[-1] + pad]
-    weight_maps = class_balance(labels.squeeze(1))              # [B,H,W] (trainer.py:72), unet_class_balance
+    weight_maps = weight_fn(labels.squeeze(1))                  # [B,H,W] (trainer.py:72 / :70), unet_class_balance / unet_weighted_map
     # the one-hot target [1-y, y] (trainer.py:63-66) is formed inside the kernel from the integer labels
     loss, _ = hip_optim.bce_argmax_step(preds, labels, weight=weight_maps, want_mask=False)
     return preds, loss, labels
@@ -87,10 +91,15 @@ def _first_sample_metrics(preds, labels):
 
 
 def training(unet, train_loader, val_loader, epochs, batch_size, device, fold_dir, DATASET, *, resume_from=None,
-             save_optimizer=False):
-    """Reference signature (trainer.py:15) plus two keyword-only extensions, both off by default so
-    that the files written are exactly the reference's: resume_from = a checkpoint made by checkpoint.py (weights +
-    SGD momentum + scheduler + epoch), save_optimizer = also write models/checkpoint_latest.pth every epoch."""
+             save_optimizer=False, loss_weights='class_balance'):
+    """Reference signature (trainer.py:15) plus keyword-only extensions, all off by default so that the files
+    written are exactly the reference's: resume_from = a checkpoint made by checkpoint.py (weights + SGD momentum +
+    scheduler + epoch), save_optimizer = also write models/checkpoint_latest.pth every epoch (both SURVEY N4);
+    loss_weights = 'border' weights the training and the validation loss with weighted_map (the paper's border
+    map, what the reference's HeLa branch asks for at trainer.py:68-70,110-112) instead of class_balance."""
+    if loss_weights not in _LOSS_WEIGHTS:
+        raise ValueError("loss_weights must be one of %s, got %r" % (sorted(_LOSS_WEIGHTS), loss_weights))
+    weight_fn = _LOSS_WEIGHTS[loss_weights]
     when_to_stop, goal = _goal_for(DATASET)
 
     optimizer = hip_optim.SGD(unet.parameters(), lr=0.0001, momentum=0.99)
@@ -131,7 +140,7 @@ def training(unet, train_loader, val_loader, epochs, batch_size, device, fold_di
 
         for images, labels in train_loader:
             optimizer.zero_grad()
-            preds, loss, labels = _step_loss(unet, images, labels, device, True)
+            preds, loss, labels = _step_loss(unet, images, labels, device, True, weight_fn)
             loss.backward()
             optimizer.step()
             total_loss += loss.detach()
@@ -141,7 +150,7 @@ def training(unet, train_loader, val_loader, epochs, batch_size, device, fold_di
 
         with torch.no_grad():
             for images, labels in val_loader:
-                preds, loss, labels = _step_loss(unet, images, labels, device, False)
+                preds, loss, labels = _step_loss(unet, images, labels, device, False, weight_fn)
                 total_loss_val += loss
                 if val_eval is None:
                     val_eval = _first_sample_metrics(preds, labels)

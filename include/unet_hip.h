@@ -220,6 +220,16 @@ int unet_eval_masks(const void *logits, long batch_stride, long plane_stride, lo
 /* N3, replaces functions.class_balance (functions.py:82-117) for {0,1} labels: w = 1 on cells,
  * count(1)/count(0) on background; counts_u64 [B] receives count(1) (caller checks the degenerate case). */
 int unet_class_balance(const void *labels_i64, int B, int H, int W, void *weights, void *counts_u64, void *stream);
+/* Border weight map, replaces functions.weighted_map (functions.py:7-78: torch.unique counts, cv.connectedComponents(connectivity=4),
+ * one cv.distanceTransform(DIST_L2, 0) per component, sort, w0 * exp(-(d1+d2)^2 / (2 sig2))) for {0,1} labels
+ * [B,H,W], int64 (labels_dtype 0) or float32 (1); H != W allowed.  weights f32 [B,H,W]: 1 on cells; on background
+ * w_c + w_d with w_c = count(1)/count(0) in fp32, truncated for int64 labels (the reference stores it in
+ * torch.empty_like(gt)), d1 / d2 the exact distances to the nearest / second-nearest distinct 4-connected component
+ * (d2 = 0 when the image has one).  counts_u64 [B] receives count(1), n_objects_i32 [B] the component count (the
+ * caller checks the one-class case).  scratch: unet_weighted_map_scratch_bytes(B, H, W); sig2 <= ~5000.        */
+size_t unet_weighted_map_scratch_bytes(int B, int H, int W);
+int unet_weighted_map(const void *labels, int labels_dtype, int B, int H, int W, float w0, float sig2, void *weights_f32,
+                      void *counts_u64, void *n_objects_i32, void *scratch, void *stream);
 /* N1, replaces elastic_transform's two steps (data.py:225-245): scipy.ndimage.gaussian_filter(field,
  * sigma, mode="constant") * scale as two 1-D passes with the caller's normalised taps [2*radius+1], and
  * map_coordinates(img, (row+dy, col+dx), order=1) (bilinear, 0 outside [0,n-1]).                       */
