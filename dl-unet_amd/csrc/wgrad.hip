@@ -866,15 +866,18 @@ static void decompose(const WgradP &p, WgradK &k)
 }
 
 // the pixel-linear up-conv form: the full-window 2x2 stride-2 weight gradient with its bias gradient on X (or none), tensors
-// below 2 GiB (buffer descriptors), exact fp32 or bf16 tensors (the bf16x3 split keeps the row-walking kernel)
+// below 2 GiB (buffer descriptors), exact fp32 or bf16 tensors (the bf16x3 split keeps the row-walking kernel).  With bf16
+// tensors it is the only kernel: like wgrad_bf16_kernel it always stages by buffer descriptor, so neither
+// unet_set_lds_dma(0) nor UNET_WGRAD_UP=0 (an fp32 A/B switch) moves it to the row-walking form, which has no bf16 variant
 static bool up_applicable(const WgradP &p)
 {
-    static const int on = [] { const char *e = getenv("UNET_WGRAD_UP"); return e ? atoi(e) : 1; }();      // 0: the row-walking kernels (A/B)
-    if (!on || p.TY != 2 || p.TX != 2 || p.stride != 2 || p.xpad != 0 || p.oy0 != 0 || p.ox0 != 0) return false;
+    static const int on = [] { const char *e = getenv("UNET_WGRAD_UP"); return e ? atoi(e) : 1; }();      // 0: the fp32 row-walking kernels (A/B)
+    if ((!on && p.math != 2) || p.TY != 2 || p.TX != 2 || p.stride != 2 || p.xpad != 0 || p.oy0 != 0 || p.ox0 != 0) return false;
     if (p.math == 1 || (p.db && !p.db_on_x)) return false;
     if (p.ywin0 != 0 || p.xwin0 != 0 || p.ywin1 != p.YH || p.xwin1 != p.YW || p.XH != 2 * p.YH || p.XW != 2 * p.YW) return false;
     const size_t es = p.math == 2 ? 2 : 4;
-    return (size_t)p.NB * p.XH * p.XW * p.XC * es < 0x7FFFFFFFull && (size_t)p.NB * p.YH * p.YW * p.YC * es < 0x7FFFFFFFull && get_lds_dma_mode() != 0;
+    return (size_t)p.NB * p.XH * p.XW * p.XC * es < 0x7FFFFFFFull && (size_t)p.NB * p.YH * p.YW * p.YC * es < 0x7FFFFFFFull &&
+           (p.math == 2 || get_lds_dma_mode() != 0);
 }
 
 static void up_decompose(const WgradP &p, WgradK &k)
@@ -976,8 +979,8 @@ static int launch_wgrad_t(WgradK &k, hipStream_t st)
     auto kern = buf ? wgrad_f32_kernel<TY, TX, S, NSPLIT, CAN_BUF> : wgrad_f32_kernel<TY, TX, S, NSPLIT, false>;
     if (int rc_ = ensure_dynamic_lds((const void *)kern, G::LDS, buf ? attr_done_b : attr_done)) return rc_;
     char tag[96];
-    snprintf(tag, sizeof(tag), "wgrad<%d;%d;%d;split%d> Ci=%d Cj=%d Y=%dx%d win=%d parts=%d pw=%d rows=%d groups=%d", TY, TX, S, NSPLIT, k.p.Ci, k.p.Cj, k.p.YH, k.p.YW,
-             k.p.ywin1 - k.p.ywin0, k.nparts, k.pw, k.rows_per_chunk, k.ngroups);
+    snprintf(tag, sizeof(tag), "wgrad<%d;%d;%d;split%d> buf=%d Ci=%d Cj=%d Y=%dx%d win=%d parts=%d pw=%d rows=%d groups=%d", TY, TX, S, NSPLIT, (int)buf, k.p.Ci, k.p.Cj,
+             k.p.YH, k.p.YW, k.p.ywin1 - k.p.ywin0, k.nparts, k.pw, k.rows_per_chunk, k.ngroups);
     {
         // executed: every workgroup runs its partitions' rows x pixel pairs (NSPLIT 0) / 16-pixel groups for all taps of a 64x64 tile
         const double rows = (double)k.p.NB * (k.p.ywin1 - k.p.ywin0) * k.nstrips;
@@ -1001,7 +1004,7 @@ static int launch_wgrad_b(WgradK &k, hipStream_t st)
     ARG_CHECK(xb < 0x7FFFFFFFull && yb < 0x7FFFFFFFull, "wgrad (bf16): tensor exceeds 2 GiB");
     k.xbytes = (int)xb; k.ybytes = (int)yb;
     char tag[96];
-    snprintf(tag, sizeof(tag), "wgradb<%d;%d;%d> Ci=%d Cj=%d Y=%dx%d win=%d parts=%d pw=%d rows=%d groups=%d", TY, TX, S, k.p.Ci, k.p.Cj, k.p.YH, k.p.YW,
+    snprintf(tag, sizeof(tag), "wgradb<%d;%d;%d> buf=1 Ci=%d Cj=%d Y=%dx%d win=%d parts=%d pw=%d rows=%d groups=%d", TY, TX, S, k.p.Ci, k.p.Cj, k.p.YH, k.p.YW,
              k.p.ywin1 - k.p.ywin0, k.nparts, k.pw, k.rows_per_chunk, k.ngroups);
     const double rows = (double)k.p.NB * (k.p.ywin1 - k.p.ywin0) * k.nstrips;
     prof_begin(PK_WGRAD, tag, st, wgrad_alg_flops(k.p), 2.0 * rows * k.pw * G::T * k.p.Ci * k.p.Cj, wgrad_alg_bytes(k.p) / 2.0 + 2.0 * G::T * k.p.Ci * k.p.Cj);
@@ -1045,7 +1048,7 @@ int launch_wgrad(WgradP p, hipStream_t st)
         rc = mode == 0 ? launch_wgrad_t<3, 3, 1, 0>(k, st) : mode == 1 ? launch_wgrad_t<3, 3, 1, 3>(k, st) : launch_wgrad_b<3, 3, 1>(k, st);
     else if (p.TY == 2 && p.TX == 2 && p.stride == 2) {
         // (bf16 tensors: only the pixel-linear kernel - it needs what the bf16 row-walking kernel needed too, tensors below 2 GiB)
-        if (mode == 2) { set_error("wgrad (bf16): the up-conv weight gradient needs tensors below 2 GiB, the full window and buffer-descriptor LDS-DMA"); return -4; }
+        if (mode == 2) { set_error("wgrad (bf16): the up-conv weight gradient needs tensors below 2 GiB and the full window"); return -4; }
         rc = mode == 0 ? launch_wgrad_t<2, 2, 2, 0>(k, st) : launch_wgrad_t<2, 2, 2, 3>(k, st);
     }
     else { set_error("wgrad: unsupported taps %dx%d stride %d", p.TY, p.TX, p.stride); return -4; }

@@ -66,7 +66,12 @@ int unet_set_math(int mode);
 int unet_get_math(void);
 /* Operand staging of the MFMA kernels: 1 (default) = LDS-DMA through buffer descriptors whenever every tensor of a launch is
  * below 2 GiB, else global_load_lds; 0 = always global_load_lds (what tensors >= 2 GiB take, e.g. config #5 at batch 16).
- * A tuning / test knob: results are identical.  Also settable with UNET_LDS_DMA.                                       */
+ * A tuning / test knob: results are bit-identical, with one exception - the fp32 up-conv weight and bias gradient (modes 0
+ * and 3): at 1 it is the pixel-linear kernel (wgrad_up<f32>), at 0 the row-walking one (wgrad<2;2;2;split0>), which sums
+ * the pixels in another order (same error bound, different rounding).  The bf16 kernels (mode 2) always stage by buffer
+ * descriptor and ignore the knob; so does the bf16x3 implicit GEMM (mode 1).  Also settable with UNET_LDS_DMA.
+ * (UNET_WGRAD_UP=0, an A/B switch read once per process, moves the fp32 up-conv weight gradient to the row-walking kernel
+ *  in modes 0 and 3; it does not apply to mode 2, whose bf16 tensors have no row-walking kernel.)                 */
 int unet_set_lds_dma(int mode);
 
 /* ---- handle ------------------------------------------------------------------------------

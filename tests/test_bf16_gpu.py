@@ -9,6 +9,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import kernel_paths as kp
+
 pytestmark = pytest.mark.gpu
 
 TOL_F32 = 2e-5
@@ -72,9 +74,11 @@ def test_conv3x3_fwd_bf16(hip, B, H, C, K):
     ref = F.relu(F.conv2d(x, w, b))
     y = torch.empty(B, H - 2, H - 2, K, device="cuda", dtype=torch.bfloat16)
     sc = scratch(hip.lib().unet_conv3x3_scratch_bytes(C, K))
-    hip.check(hip.lib().unet_conv3x3_fwd(hip.ptr(keep(nhwc16(x))), H, H, C, 0, None, 0, B, H, H, hip.ptr(keep(w.float().cuda())),
-                                         hip.ptr(keep(b.float().cuda())), K, 1, hip.ptr(y), hip.ptr(sc), hip.stream()), "conv3x3_fwd")
+    with kp.record() as rec:
+        hip.check(hip.lib().unet_conv3x3_fwd(hip.ptr(keep(nhwc16(x))), H, H, C, 0, None, 0, B, H, H, hip.ptr(keep(w.float().cuda())),
+                                             hip.ptr(keep(b.float().cuda())), K, 1, hip.ptr(y), hip.ptr(sc), hip.stream()), "conv3x3_fwd")
     assert nerr(nchw(y), ref) < TOL_BF16
+    assert rec.main_families() == [kp.bf16_conv_family(H - 2, K, [C], False)], rec
 
 
 @pytest.mark.parametrize("B,Hs,pad,C1,C2,K", [(2, 8, 6, 64, 64, 64), (1, 10, 3, 128, 128, 128), (1, 24, 4, 64, 64, 64), (2, 30, -3, 64, 64, 128),
@@ -87,10 +91,12 @@ def test_conv3x3_fwd_virtual_concat_bf16(hip, B, Hs, pad, C1, C2, K):
     ref = F.relu(F.conv2d(torch.cat((F.pad(a, (pad,) * 4), u), 1), w, b))
     y = torch.empty(B, H - 2, H - 2, K, device="cuda", dtype=torch.bfloat16)
     sc = scratch(hip.lib().unet_conv3x3_scratch_bytes(C1 + C2, K))
-    hip.check(hip.lib().unet_conv3x3_fwd(hip.ptr(keep(nhwc16(a))), Hs, Hs, C1, pad, hip.ptr(keep(nhwc16(u))), C2, B, H, H,
-                                         hip.ptr(keep(w.float().cuda())), hip.ptr(keep(b.float().cuda())), K, 1, hip.ptr(y), hip.ptr(sc),
-                                         hip.stream()), "conv3x3_fwd concat")
+    with kp.record() as rec:
+        hip.check(hip.lib().unet_conv3x3_fwd(hip.ptr(keep(nhwc16(a))), Hs, Hs, C1, pad, hip.ptr(keep(nhwc16(u))), C2, B, H, H,
+                                             hip.ptr(keep(w.float().cuda())), hip.ptr(keep(b.float().cuda())), K, 1, hip.ptr(y), hip.ptr(sc),
+                                             hip.stream()), "conv3x3_fwd concat")
     assert nerr(nchw(y), ref) < TOL_BF16
+    assert rec.main_families() == kp.concat_fwd_families(2, 1, Hs, pad, C1, C2, K), rec      # one launch: no split forward in bf16
 
 
 # (dgrad of a K = 64 layer is a 64-input-channel launch with two pixels of virtual zero padding: convb64 with border tiles)
@@ -116,10 +122,12 @@ def test_conv3x3_bwd_bf16(hip, B, H, C, K, use_mask, use_add):
     dx = torch.empty(B, H, H, C, device="cuda", dtype=torch.bfloat16)
     dw = torch.empty(K, C, 3, 3, device="cuda"); db = torch.empty(K, device="cuda")
     sc = scratch(hip.lib().unet_conv3x3_bwd_scratch_bytes(B, H, H, C, K))
-    hip.check(hip.lib().unet_conv3x3_bwd(hip.ptr(keep(nhwc16(x.detach()))), H, H, C, 0, None, 0, B, H, H, hip.ptr(keep(w.detach().float().cuda())), K,
-                                         hip.ptr(keep(nhwc16(dz))), hip.ptr(dx), hip.ptr(keep(nhwc16(mask))) if use_mask else None,
-                                         hip.ptr(keep(nhwc16(add))) if use_add else None, None, None, hip.ptr(dw), hip.ptr(db),
-                                         hip.ptr(sc), hip.stream()), "conv3x3_bwd")
+    with kp.record() as rec:
+        hip.check(hip.lib().unet_conv3x3_bwd(hip.ptr(keep(nhwc16(x.detach()))), H, H, C, 0, None, 0, B, H, H, hip.ptr(keep(w.detach().float().cuda())), K,
+                                             hip.ptr(keep(nhwc16(dz))), hip.ptr(dx), hip.ptr(keep(nhwc16(mask))) if use_mask else None,
+                                             hip.ptr(keep(nhwc16(add))) if use_add else None, None, None, hip.ptr(dw), hip.ptr(db),
+                                             hip.ptr(sc), hip.stream()), "conv3x3_bwd")
+    assert rec.main_families()[:2] == [kp.bf16_conv_family(H, C, [K], True), "wgradb<3;3;1>"], rec
     assert nerr(nchw(dx), dx_ref) < TOL_BF16
     assert nerr(dw, w.grad) < TOL_F32                    # fp32 result of exact bf16 products: only the summation order differs
     assert nerr(db, dz.sum((0, 2, 3))) < TOL_F32
@@ -137,9 +145,11 @@ def test_conv3x3_bwd_virtual_concat_bf16(hip, B, Hs, pad, C, K):
     dx1 = torch.empty(B, Hs, Hs, C, device="cuda", dtype=torch.bfloat16); dx2 = torch.empty(B, H, H, C, device="cuda", dtype=torch.bfloat16)
     dw = torch.empty(K, 2 * C, 3, 3, device="cuda"); db = torch.empty(K, device="cuda")
     sc = scratch(hip.lib().unet_conv3x3_bwd_scratch_bytes(B, H, H, 2 * C, K))
-    hip.check(hip.lib().unet_conv3x3_bwd(hip.ptr(keep(nhwc16(a.detach()))), Hs, Hs, C, pad, hip.ptr(keep(nhwc16(u.detach()))), C, B, H, H,
-                                         hip.ptr(keep(w.detach().float().cuda())), K, hip.ptr(keep(nhwc16(dz))), hip.ptr(dx1), None, None,
-                                         hip.ptr(dx2), None, hip.ptr(dw), hip.ptr(db), hip.ptr(sc), hip.stream()), "conv3x3_bwd concat")
+    with kp.record() as rec:
+        hip.check(hip.lib().unet_conv3x3_bwd(hip.ptr(keep(nhwc16(a.detach()))), Hs, Hs, C, pad, hip.ptr(keep(nhwc16(u.detach()))), C, B, H, H,
+                                             hip.ptr(keep(w.detach().float().cuda())), K, hip.ptr(keep(nhwc16(dz))), hip.ptr(dx1), None, None,
+                                             hip.ptr(dx2), None, hip.ptr(dw), hip.ptr(db), hip.ptr(sc), hip.stream()), "conv3x3_bwd concat")
+    assert rec.main_families(reduces=False) == kp.concat_bwd_families(2, 1, Hs, pad, C, C, K), rec
     assert nerr(nchw(dx1), a.grad) < TOL_BF16
     assert nerr(nchw(dx2), u.grad) < TOL_BF16
     assert nerr(dw, w.grad) < TOL_F32
@@ -217,8 +227,10 @@ def test_upconv2_fwd_bwd_bf16(hip, B, H, Ci, Co):
                                          hip.ptr(y), hip.ptr(sc), hip.stream()), "upconv2_fwd")
     assert nerr(nchw(y), ref) < TOL_BF16
     dx = torch.empty(B, H, H, Ci, device="cuda", dtype=torch.bfloat16); dw = torch.empty(Ci, Co, 2, 2, device="cuda"); db = torch.empty(Co, device="cuda")
-    hip.check(hip.lib().unet_upconv2_bwd(hip.ptr(xd), B, H, H, Ci, hip.ptr(keep(w.detach().float().cuda())), Co, hip.ptr(keep(nhwc16(dy))),
-                                         hip.ptr(dx), hip.ptr(xd), hip.ptr(dw), hip.ptr(db), hip.ptr(sc), hip.stream()), "upconv2_bwd")
+    with kp.record() as rec:
+        hip.check(hip.lib().unet_upconv2_bwd(hip.ptr(xd), B, H, H, Ci, hip.ptr(keep(w.detach().float().cuda())), Co, hip.ptr(keep(nhwc16(dy))),
+                                             hip.ptr(dx), hip.ptr(xd), hip.ptr(dw), hip.ptr(db), hip.ptr(sc), hip.stream()), "upconv2_bwd")
+    assert "wgrad_up<bf16>" in rec.families, rec                  # the one bf16 up-conv weight gradient, whatever lds_dma says
     assert nerr(nchw(dx), x.grad * (x.detach() > 0)) < TOL_BF16
     assert nerr(dw, w.grad) < TOL_F32
     assert nerr(db, dy.sum((0, 2, 3))) < TOL_F32
@@ -338,3 +350,202 @@ def test_bf16_tensors_at_the_baseline_tile_against_the_reference_golden(hip, gol
     assert e_d <= b_d
     assert worst_flip <= b_d
     assert int(flip.sum()) <= exp_n + 4 * exp_sd
+
+
+# ---- one RNE rounding per bf16 output, fp32 master weights that are not bf16 (tests/kernel_bounds.py) -------------------
+# The max-normalised bound above (4e-3 = 2^-8 of the tensor maximum) would pass a truncating converter or packer and a second
+# rounding of a partial sum.  Here every element is judged: z = the fp64 value after bias / add / mask (ReLU applied in the
+# check), eps = 8 sqrt(K) 2^-24 A; |y - z| <= ulp/2 + eps everywhere, and y == RNE_bf16(z) bit for bit wherever z is farther
+# than eps from a rounding midpoint.  The weights are fp32 and NOT bf16-representable: the reference packs them with
+# w.to(torch.bfloat16), which is round-to-nearest-even.
+import kernel_bounds as kb          # noqa: E402
+from torch.nn.grad import conv2d_input, conv2d_weight      # noqa: E402
+
+RNE_STATS = {}
+
+
+def w32(*shape, seed, scale):
+    w = rnd(*shape, seed=seed, scale=scale).float().double()
+    assert (bf(w) != w).float().mean() > 0.9
+    return w
+
+
+def rne_check(kind, y, z, A, K, relu=False):
+    st = kb.check_rne(y.detach().double().cpu().numpy(), z.detach().double().numpy(), kb.acc_slack(A.detach().double().numpy(), K), relu=relu)
+    n, d = RNE_STATS.get(kind, (0, 0))
+    RNE_STATS[kind] = (n + st["n"], d + st["decidable"])
+    print("RNE %s: %d outputs, %d decidable (%.1f %%), all bit-exact; worst |y-z| / (ulp/2 + eps) = %.3f"
+          % (kind, st["n"], st["decidable"], 100 * st["frac"], st["worst"]))
+    return st
+
+
+@pytest.mark.parametrize("B,H,C,K,fam", [(2, 21, 64, 64, "convb64<8;32>"), (2, 23, 128, 128, "igemmb3<0>"), (1, 21, 128, 128, "igemmb3<0>"),
+                                         (1, 20, 128, 128, "igemmb<128;128;0>"),      # OW = 18: one short of the band kernel's rows
+                                         (1, 14, 128, 64, "igemmb<256;64;0>"), (1, 12, 256, 512, "igemmb<128;128;0>")])
+def test_conv3x3_fwd_bf16_rounds_once(hip, B, H, C, K, fam):
+    keep = Keep()
+    x = bf(rnd(B, C, H, H, seed=1)); w = w32(K, C, 3, 3, seed=2, scale=0.05); b = rnd(K, seed=3).float().double()
+    wq = bf(w)
+    z = F.conv2d(x, wq, b); A = F.conv2d(x.abs(), wq.abs(), b.abs())
+    y = torch.empty(B, H - 2, H - 2, K, device="cuda", dtype=torch.bfloat16)
+    sc = scratch(hip.lib().unet_conv3x3_scratch_bytes(C, K))
+    with kp.record() as rec:
+        hip.check(hip.lib().unet_conv3x3_fwd(hip.ptr(keep(nhwc16(x))), H, H, C, 0, None, 0, B, H, H, hip.ptr(keep(w.float().cuda())),
+                                             hip.ptr(keep(b.float().cuda())), K, 1, hip.ptr(y), hip.ptr(sc), hip.stream()), "conv3x3_fwd")
+    assert nerr(nchw(y), F.relu(z)) < TOL_BF16
+    st = rne_check("fwd", nchw(y), z, A, 9 * C + 1, relu=True)
+    assert st["relu_zeros"] > 0
+    assert [f for f in rec.families if f.startswith(("igemm", "convb64"))] == [fam], rec
+
+
+@pytest.mark.parametrize("B,Hs,pad,C1,C2,K", [(2, 8, 6, 64, 64, 64), (1, 20, 4, 128, 128, 128)])
+def test_conv3x3_fwd_virtual_concat_bf16_rounds_once(hip, B, Hs, pad, C1, C2, K):
+    """A zero-padded skip source: the fp32 modes split this forward into two launches whose partial sums meet in the output
+    tensor; with bf16 tensors that would round twice, so mode 2 keeps one launch (net.hip) - pinned here."""
+    keep = Keep()
+    H = Hs + 2 * pad
+    a = bf(rnd(B, C1, Hs, Hs, seed=1)); u = bf(rnd(B, C2, H, H, seed=2))
+    w = w32(K, C1 + C2, 3, 3, seed=3, scale=0.05); b = rnd(K, seed=4).float().double()
+    xc = torch.cat((F.pad(a, (pad,) * 4), u), 1)
+    z = F.conv2d(xc, bf(w), b); A = F.conv2d(xc.abs(), bf(w).abs(), b.abs())
+    y = torch.empty(B, H - 2, H - 2, K, device="cuda", dtype=torch.bfloat16)
+    sc = scratch(hip.lib().unet_conv3x3_scratch_bytes(C1 + C2, K))
+    with kp.record() as rec:
+        hip.check(hip.lib().unet_conv3x3_fwd(hip.ptr(keep(nhwc16(a))), Hs, Hs, C1, pad, hip.ptr(keep(nhwc16(u))), C2, B, H, H,
+                                             hip.ptr(keep(w.float().cuda())), hip.ptr(keep(b.float().cuda())), K, 1, hip.ptr(y), hip.ptr(sc),
+                                             hip.stream()), "conv3x3_fwd concat")
+    rne_check("fwd", nchw(y), z, A, 9 * (C1 + C2) + 1, relu=True)
+    assert rec.main_families() == kp.concat_fwd_families(2, 1, Hs, pad, C1, C2, K), rec
+
+
+@pytest.mark.parametrize("B,H,C,K,use_mask,use_add,fam", [(2, 21, 64, 64, True, True, "convb64<8;32>"), (2, 13, 128, 256, True, True, "igemmb<128;128;1>"),
+                                                          (2, 23, 128, 128, True, True, "igemmb3<1>"), (1, 14, 64, 128, False, True, "igemmb<256;64;1>")])
+def test_conv3x3_dgrad_bf16_rounds_once(hip, B, H, C, K, use_mask, use_add, fam):
+    keep = Keep()
+    x = bf(rnd(B, C, H, H, seed=1)); w = w32(K, C, 3, 3, seed=2, scale=0.05); dz = bf(rnd(B, K, H - 2, H - 2, seed=3))
+    mask = bf(rnd(B, C, H, H, seed=4).clamp_min(0)) if use_mask else None
+    add = bf(rnd(B, C, H, H, seed=5)) if use_add else None
+    wq = bf(w)
+    z = conv2d_input(x.shape, wq, dz); A = conv2d_input(x.shape, wq.abs(), dz.abs())
+    if add is not None:
+        z = z + add; A = A + add.abs()
+    if mask is not None:
+        z = z * (mask > 0); A = A * (mask > 0)
+    dx = torch.empty(B, H, H, C, device="cuda", dtype=torch.bfloat16)
+    dw = torch.empty(K, C, 3, 3, device="cuda"); db = torch.empty(K, device="cuda")
+    sc = scratch(hip.lib().unet_conv3x3_bwd_scratch_bytes(B, H, H, C, K))
+    with kp.record() as rec:
+        hip.check(hip.lib().unet_conv3x3_bwd(hip.ptr(keep(nhwc16(x))), H, H, C, 0, None, 0, B, H, H, hip.ptr(keep(w.float().cuda())), K,
+                                             hip.ptr(keep(nhwc16(dz))), hip.ptr(dx), hip.ptr(keep(nhwc16(mask))) if use_mask else None,
+                                             hip.ptr(keep(nhwc16(add))) if use_add else None, None, None, hip.ptr(dw), hip.ptr(db),
+                                             hip.ptr(sc), hip.stream()), "conv3x3_bwd")
+    assert nerr(nchw(dx), z) < TOL_BF16
+    rne_check("dgrad", nchw(dx), z, A, 9 * K + 1)
+    assert nerr(dw, conv2d_weight(x, w.shape, dz)) < TOL_F32 and nerr(db, dz.sum((0, 2, 3))) < TOL_F32
+    assert [f for f in rec.families if f.startswith(("igemmb", "convb64"))] == [fam], rec
+    assert "wgradb<3;3;1>" in rec.families
+
+
+@pytest.mark.parametrize("B,H,Ci,Co", [(2, 7, 128, 64), (1, 13, 256, 128), (5, 6, 256, 256)])
+def test_upconv2_bf16_rounds_once(hip, B, H, Ci, Co):
+    keep = Keep()
+    x = bf(rnd(B, Ci, H, H, seed=1).clamp_min(0)); w = w32(Ci, Co, 2, 2, seed=2, scale=0.05); b = rnd(Co, seed=3).float().double()
+    dy = bf(rnd(B, Co, 2 * H, 2 * H, seed=4))
+    wq = bf(w)
+    z = F.conv_transpose2d(x, wq, b, stride=2); A = F.conv_transpose2d(x, wq.abs(), b.abs(), stride=2)
+    xr = x.clone().requires_grad_(True); xa = x.clone().requires_grad_(True)
+    F.conv_transpose2d(xr, wq, stride=2).backward(dy); F.conv_transpose2d(xa, wq.abs(), stride=2).backward(dy.abs())
+    wr = w.clone().requires_grad_(True)
+    F.conv_transpose2d(x, wr, stride=2).backward(dy)
+    sc = scratch(hip.lib().unet_upconv2_scratch_bytes(B, H, H, Ci, Co))
+    y = torch.empty(B, 2 * H, 2 * H, Co, device="cuda", dtype=torch.bfloat16)
+    dx = torch.empty(B, H, H, Ci, device="cuda", dtype=torch.bfloat16); dw = torch.empty(Ci, Co, 2, 2, device="cuda"); db = torch.empty(Co, device="cuda")
+    xd = nhwc16(x)
+    with kp.record() as rec:
+        hip.check(hip.lib().unet_upconv2_fwd(hip.ptr(xd), B, H, H, Ci, hip.ptr(keep(w.float().cuda())), hip.ptr(keep(b.float().cuda())), Co,
+                                             hip.ptr(y), hip.ptr(sc), hip.stream()), "upconv2_fwd")
+        hip.check(hip.lib().unet_upconv2_bwd(hip.ptr(xd), B, H, H, Ci, hip.ptr(keep(w.float().cuda())), Co, hip.ptr(keep(nhwc16(dy))),
+                                             hip.ptr(dx), hip.ptr(xd), hip.ptr(dw), hip.ptr(db), hip.ptr(sc), hip.stream()), "upconv2_bwd")
+    rne_check("upfwd", nchw(y), z, A, Ci + 1)
+    rne_check("updgrad", nchw(dx), xr.grad * (x > 0), xa.grad * (x > 0), 4 * Co)
+    assert nerr(dw, wr.grad) < TOL_F32 and nerr(db, dy.sum((0, 2, 3))) < TOL_F32
+    assert "wgrad_up<bf16>" in rec.families, rec
+
+
+def test_head_dz_and_conv1ch_bf16_round_once(hip):
+    keep = Keep()
+    # head backward: dz = (dlogits . W) * (x > 0), fp32 dlogits and weights (not bf16), one rounding to bf16
+    B, H, Cc = 2, 37, 64
+    x = bf(rnd(B, Cc, H, H, seed=1).clamp_min(0))
+    w = w32(2, Cc, 1, 1, seed=2, scale=0.1); dl = rnd(B, 2, H, H, seed=4).float().double()
+    z = torch.einsum("bohw,oc->bchw", dl, w[:, :, 0, 0]) * (x > 0)
+    A = torch.einsum("bohw,oc->bchw", dl.abs(), w[:, :, 0, 0].abs()) * (x > 0)
+    dz = torch.empty(B, H, H, Cc, device="cuda", dtype=torch.bfloat16); dw = torch.empty(2, Cc, 1, 1, device="cuda"); db = torch.empty(2, device="cuda")
+    sc = scratch(hip.lib().unet_head1x1_bwd_scratch_bytes(B, H, H, Cc))
+    hip.check(hip.lib().unet_head1x1_bwd(hip.ptr(keep(nhwc16(x))), B, H, H, Cc, hip.ptr(keep(w.float().cuda())), hip.ptr(keep(dl.float().cuda())),
+                                         hip.ptr(dz), hip.ptr(dw), hip.ptr(db), hip.ptr(sc), hip.stream()))
+    rne_check("head_dz", nchw(dz), z, A, 2)
+    # conv11c forward: fp32 image and weights, bf16 activations out
+    B, S, K = 2, 60, 64
+    xi = rnd(B, 1, S, S, seed=1).float().double(); wi = rnd(K, 1, 3, 3, seed=2).float().double(); bi = rnd(K, seed=3).float().double()
+    z = F.conv2d(xi, wi, bi); A = F.conv2d(xi.abs(), wi.abs(), bi.abs())
+    yo = torch.empty(B, S - 2, S - 2, K, device="cuda", dtype=torch.bfloat16)
+    hip.check(hip.lib().unet_conv1ch_fwd(hip.ptr(keep(xi.float().cuda())), B, S, hip.ptr(keep(wi.float().cuda())), hip.ptr(keep(bi.float().cuda())), K,
+                                         hip.ptr(yo), hip.stream()))
+    rne_check("conv1ch", nchw(yo), z, A, 10, relu=True)
+
+
+# ---- unet_set_lds_dma(0) in mode 2 --------------------------------------------------------------------------------------
+@pytest.fixture
+def glds(hip):
+    hip.check(hip.lib().unet_set_lds_dma(0), "set_lds_dma")
+    yield 0
+    hip.check(hip.lib().unet_set_lds_dma(1), "set_lds_dma")
+
+
+@pytest.mark.parametrize("B,H,Ci,Co", [(2, 7, 128, 64), (1, 13, 256, 128), (5, 6, 256, 256)])
+def test_upconv2_fwd_bwd_bf16_glds(hip, glds, B, H, Ci, Co):
+    """The bf16 up-conv weight gradient has one kernel (wgrad_up<bf16>, always buffer-descriptor staging, like
+    wgrad_bf16_kernel); unet_set_lds_dma(0) must not take it away (it used to return -4).  The case asserts that it ran."""
+    test_upconv2_fwd_bwd_bf16(hip, B, H, Ci, Co)
+
+
+def test_net_forward_backward_bf16_glds_S188(hip, glds):
+    """Whole-net mode-2 training forward + backward at S = 188 with unet_set_lds_dma(0): runs, and matches the default
+    staging bit for bit (every bf16 kernel ignores the knob)."""
+    import _hip
+    from oracle import prng
+    S, B = 188, 1
+    params = [torch.from_numpy(v).cuda() for v in prng.make_params(0).values()]
+    x = torch.from_numpy(prng.make_input(1, B, S)).cuda()
+    dl = torch.from_numpy(prng.make_cotangent(2, (B, 2, S - 184, S - 184))).float().cuda()
+    h = _hip.Handle(64, 0, 2)
+    outs = []
+    for dma in (0, 1):
+        hip.check(hip.lib().unet_set_lds_dma(dma), "set_lds_dma")
+        ws = torch.empty(h.workspace_bytes(B, S, 1), dtype=torch.uint8, device="cuda")
+        logits = torch.empty(B, 2, S - 184, S - 184, device="cuda")
+        grads = [torch.full_like(p, float("nan")) for p in params]
+        hip.check(hip.lib().unet_forward(h.h, _hip.ptr_table(params), hip.ptr(x), hip.ptr(logits), B, S, hip.ptr(ws), ws.numel(), 1, hip.stream()), "forward")
+        hip.check(hip.lib().unet_backward(h.h, _hip.ptr_table(params), hip.ptr(dl), _hip.ptr_table(grads), hip.ptr(ws), ws.numel(), hip.stream()), "backward")
+        torch.cuda.synchronize()
+        assert all(bool(torch.isfinite(g).all()) for g in grads)
+        outs.append([logits.cpu()] + [g.cpu() for g in grads])
+    hip.check(hip.lib().unet_set_lds_dma(0), "set_lds_dma")
+    for a, b in zip(*outs):
+        assert torch.equal(a, b)
+
+
+def test_fuzz_conv_bf16_tensors():
+    """tools/fuzz_conv.py (30 random shapes through the 3x3 forward and backward, virtual concat with signed pad) in mode 2,
+    in a child process with UNET_MATH=2, as the band A/B test runs its variants."""
+    import subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = ("import sys; sys.path.insert(0, %r); import importlib.util, os\n"
+            "spec = importlib.util.spec_from_file_location('fuzz_conv', os.path.join(%r, 'tools', 'fuzz_conv.py'))\n"
+            "fz = importlib.util.module_from_spec(spec); spec.loader.exec_module(fz)\n"
+            "import torch, _hip; assert _hip.lib().unet_get_math() == 2\n"
+            "w = fz.run(30, 11, verbose=False); print('WORST', w); assert w < fz.TOL\n") % (os.path.join(root, "dl-unet_amd"), root)
+    out = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, UNET_MATH="2"), capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+    assert "WORST" in out.stdout

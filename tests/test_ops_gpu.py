@@ -1,12 +1,15 @@
 """Per-op parity of the HIP kernels (through the C ABI) against fp64 torch CPU references and the
 C oracle.  Floating point: tolerance = normalised max error (|d|_inf / |ref|_inf) <= 2e-5 for fp32
 accumulation over up to 9216 terms (tolerances are normalised by tensor scale)."""
+import collections
 import ctypes as C
 
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
+
+import kernel_paths as kp
 
 pytestmark = pytest.mark.gpu
 
@@ -52,6 +55,9 @@ def rnd(*shape, seed=0, scale=1.0):
     return torch.randn(*shape, generator=g, dtype=torch.float64) * scale
 
 
+ConvMode = collections.namedtuple("ConvMode", "mode dma")
+
+
 @pytest.fixture(params=[(0, 1), (3, 1), (0, 0), (3, 0)], ids=["direct", "winograd", "direct-glds", "winograd-glds"])
 def conv_mode(hip, request):
     """The 3x3 layers have two fp32 evaluations: the direct fmaf chain (math mode 0) and Winograd F(2x2,3x3) (mode 3);
@@ -61,7 +67,7 @@ def conv_mode(hip, request):
     default = hip.lib().unet_get_math()
     hip.check(hip.lib().unet_set_math(mode), "set_math")
     hip.check(hip.lib().unet_set_lds_dma(dma), "set_lds_dma")
-    yield mode
+    yield ConvMode(mode, dma)
     hip.check(hip.lib().unet_set_lds_dma(1), "set_lds_dma")
     hip.check(hip.lib().unet_set_math(default), "set_math")
 
@@ -79,9 +85,11 @@ def test_conv3x3_fwd(hip, conv_mode, B, H, C, K):
     ref = F.relu(F.conv2d(x, w, b))
     y = torch.empty(B, H - 2, H - 2, K, device="cuda")
     sc = scratch(hip.lib().unet_conv3x3_scratch_bytes(C, K))
-    hip.check(hip.lib().unet_conv3x3_fwd(hip.ptr(keep(nhwc(x))), H, H, C, 0, None, 0, B, H, H, hip.ptr(keep(w.float().cuda())),
-                                         hip.ptr(keep(b.float().cuda())), K, 1, hip.ptr(y), hip.ptr(sc), hip.stream()), "conv3x3_fwd")
+    with kp.record() as rec:
+        hip.check(hip.lib().unet_conv3x3_fwd(hip.ptr(keep(nhwc(x))), H, H, C, 0, None, 0, B, H, H, hip.ptr(keep(w.float().cuda())),
+                                             hip.ptr(keep(b.float().cuda())), K, 1, hip.ptr(y), hip.ptr(sc), hip.stream()), "conv3x3_fwd")
     assert nerr(nchw(y), ref) < TOL
+    assert rec.main_families() == [kp.fp32_conv_family(*conv_mode, H - 2, K, [C])], rec       # (mode 3: a listed fallback runs igemm)
 
 
 def test_conv3x3_random_shapes(hip):
@@ -106,10 +114,13 @@ def test_conv3x3_fwd_virtual_concat(hip, conv_mode, B, Hs, pad, C1, C2, K):
     ref = F.relu(F.conv2d(cat, w, b))
     y = torch.empty(B, H - 2, H - 2, K, device="cuda")
     sc = scratch(hip.lib().unet_conv3x3_scratch_bytes(C1 + C2, K))
-    hip.check(hip.lib().unet_conv3x3_fwd(hip.ptr(keep(nhwc(a))), Hs, Hs, C1, pad, hip.ptr(keep(nhwc(u))), C2, B, H, H,
-                                         hip.ptr(keep(w.float().cuda())), hip.ptr(keep(b.float().cuda())), K, 1, hip.ptr(y), hip.ptr(sc),
-                                         hip.stream()), "conv3x3_fwd concat")
+    with kp.record() as rec:
+        hip.check(hip.lib().unet_conv3x3_fwd(hip.ptr(keep(nhwc(a))), Hs, Hs, C1, pad, hip.ptr(keep(nhwc(u))), C2, B, H, H,
+                                             hip.ptr(keep(w.float().cuda())), hip.ptr(keep(b.float().cuda())), K, 1, hip.ptr(y), hip.ptr(sc),
+                                             hip.stream()), "conv3x3_fwd concat")
     assert nerr(nchw(y), ref) < TOL
+    # one two-source launch, or (zero-padded skip, small window) the up-conv source then the skip's window; Winograd where it applies
+    assert rec.main_families() == kp.concat_fwd_families(*conv_mode, Hs, pad, C1, C2, K), rec
 
 
 @pytest.mark.parametrize("B,H,C,K,use_mask,use_add", [(2, 21, 64, 64, True, False), (1, 38, 64, 128, False, True),
@@ -131,10 +142,13 @@ def test_conv3x3_bwd(hip, conv_mode, B, H, C, K, use_mask, use_add):
         dx_ref = dx_ref * (mask > 0)
     dx = torch.empty(B, H, H, C, device="cuda"); dw = torch.empty(K, C, 3, 3, device="cuda"); db = torch.empty(K, device="cuda")
     sc = scratch(hip.lib().unet_conv3x3_bwd_scratch_bytes(B, H, H, C, K))
-    hip.check(hip.lib().unet_conv3x3_bwd(hip.ptr(keep(nhwc(x.detach()))), H, H, C, 0, None, 0, B, H, H, hip.ptr(keep(w.detach().float().cuda())), K,
-                                         hip.ptr(keep(nhwc(dz))), hip.ptr(dx), hip.ptr(keep(nhwc(mask))) if use_mask else None,
-                                         hip.ptr(keep(nhwc(add))) if use_add else None, None, None, hip.ptr(dw), hip.ptr(db),
-                                         hip.ptr(sc), hip.stream()), "conv3x3_bwd")
+    with kp.record() as rec:
+        hip.check(hip.lib().unet_conv3x3_bwd(hip.ptr(keep(nhwc(x.detach()))), H, H, C, 0, None, 0, B, H, H, hip.ptr(keep(w.detach().float().cuda())), K,
+                                             hip.ptr(keep(nhwc(dz))), hip.ptr(dx), hip.ptr(keep(nhwc(mask))) if use_mask else None,
+                                             hip.ptr(keep(nhwc(add))) if use_add else None, None, None, hip.ptr(dw), hip.ptr(db),
+                                             hip.ptr(sc), hip.stream()), "conv3x3_bwd")
+    assert rec.main_families()[0] == kp.fp32_conv_family(*conv_mode, H, C, [K], pad=True), rec
+    assert rec.main_families()[1] == kp.wgrad_family(*conv_mode, C, K), rec
     assert nerr(nchw(dx), dx_ref) < TOL
     assert nerr(dw, w.grad) < TOL
     assert nerr(db, dz.sum((0, 2, 3))) < TOL
@@ -152,9 +166,11 @@ def test_conv3x3_bwd_virtual_concat(hip, conv_mode, B, Hs, pad, C, K):
     dx1 = torch.empty(B, Hs, Hs, C, device="cuda"); dx2 = torch.empty(B, H, H, C, device="cuda")
     dw = torch.empty(K, 2 * C, 3, 3, device="cuda"); db = torch.empty(K, device="cuda")
     sc = scratch(hip.lib().unet_conv3x3_bwd_scratch_bytes(B, H, H, 2 * C, K))
-    hip.check(hip.lib().unet_conv3x3_bwd(hip.ptr(keep(nhwc(a.detach()))), Hs, Hs, C, pad, hip.ptr(keep(nhwc(u.detach()))), C, B, H, H,
-                                         hip.ptr(keep(w.detach().float().cuda())), K, hip.ptr(keep(nhwc(dz))), hip.ptr(dx1), None, None,
-                                         hip.ptr(dx2), None, hip.ptr(dw), hip.ptr(db), hip.ptr(sc), hip.stream()), "conv3x3_bwd concat")
+    with kp.record() as rec:
+        hip.check(hip.lib().unet_conv3x3_bwd(hip.ptr(keep(nhwc(a.detach()))), Hs, Hs, C, pad, hip.ptr(keep(nhwc(u.detach()))), C, B, H, H,
+                                             hip.ptr(keep(w.detach().float().cuda())), K, hip.ptr(keep(nhwc(dz))), hip.ptr(dx1), None, None,
+                                             hip.ptr(dx2), None, hip.ptr(dw), hip.ptr(db), hip.ptr(sc), hip.stream()), "conv3x3_bwd concat")
+    assert rec.main_families(reduces=False) == kp.concat_bwd_families(*conv_mode, Hs, pad, C, C, K), rec
     assert nerr(nchw(dx1), a.grad) < TOL      # pad-backward == crop of the padded gradient
     assert nerr(nchw(dx2), u.grad) < TOL
     assert nerr(dw, w.grad) < TOL
@@ -168,9 +184,12 @@ def test_upconv2_fwd(hip, B, H, Ci, Co):
     ref = F.conv_transpose2d(x, w, b, stride=2)
     y = torch.empty(B, 2 * H, 2 * H, Co, device="cuda")
     sc = scratch(hip.lib().unet_upconv2_scratch_bytes(B, H, H, max(Ci, 64), max(Co, 64)))
-    hip.check(hip.lib().unet_upconv2_fwd(hip.ptr(keep(nhwc(x))), B, H, H, Ci, hip.ptr(keep(w.float().cuda())), hip.ptr(keep(b.float().cuda())), Co,
-                                         hip.ptr(y), hip.ptr(sc), hip.stream()), "upconv2_fwd")
+    with kp.record() as rec:
+        hip.check(hip.lib().unet_upconv2_fwd(hip.ptr(keep(nhwc(x))), B, H, H, Ci, hip.ptr(keep(w.float().cuda())), hip.ptr(keep(b.float().cuda())), Co,
+                                             hip.ptr(y), hip.ptr(sc), hip.stream()), "upconv2_fwd")
     assert nerr(nchw(y), ref) < TOL
+    # a 1x1 GEMM with 4 Co filter rows scattered 2x2 (no Winograd in any fp32 mode, no padded taps)
+    assert rec.main_families() == ["igemm<%s;0>" % ("128;128" if 4 * Co % 128 == 0 else "256;64")], rec
 
 
 @pytest.fixture(params=[1, 0], ids=["pixel-linear", "row-walking"])
@@ -195,8 +214,10 @@ def test_upconv2_bwd(hip, B, H, Ci, Co, up_staging):
     dx = torch.empty(B, H, H, Ci, device="cuda"); dw = torch.empty(Ci, Co, 2, 2, device="cuda"); db = torch.empty(Co, device="cuda")
     sc = scratch(hip.lib().unet_upconv2_scratch_bytes(B, H, H, Ci, Co))
     xd = nhwc(x.detach())
-    hip.check(hip.lib().unet_upconv2_bwd(hip.ptr(xd), B, H, H, Ci, hip.ptr(keep(w.detach().float().cuda())), Co, hip.ptr(keep(nhwc(dy))),
-                                         hip.ptr(dx), hip.ptr(xd), hip.ptr(dw), hip.ptr(db), hip.ptr(sc), hip.stream()), "upconv2_bwd")
+    with kp.record() as rec:
+        hip.check(hip.lib().unet_upconv2_bwd(hip.ptr(xd), B, H, H, Ci, hip.ptr(keep(w.detach().float().cuda())), Co, hip.ptr(keep(nhwc(dy))),
+                                             hip.ptr(dx), hip.ptr(xd), hip.ptr(dw), hip.ptr(db), hip.ptr(sc), hip.stream()), "upconv2_bwd")
+    assert (up_staging and "wgrad_up<f32>" in rec.families) or (not up_staging and rec.reached("wgrad<2;2;2;split0> buf=0")), rec
     assert nerr(nchw(dx), dx_ref) < TOL
     assert nerr(dw, w.grad) < TOL
     assert nerr(db, dy.sum((0, 2, 3))) < TOL
@@ -250,13 +271,17 @@ def test_conv1ch_fwd_bwd_vs_c_oracle(hip, B, S, K):
     x = rnd(B, 1, S, S, seed=1).float(); w = rnd(K, 1, 3, 3, seed=2).float(); b = rnd(K, seed=3).float()
     ref = oracle_c.conv_valid_fwd(x.double().numpy(), w.double().numpy(), b.double().numpy(), True)
     y = torch.empty(B, S - 2, S - 2, K, device="cuda")
-    hip.check(hip.lib().unet_conv1ch_fwd(hip.ptr(keep(x.cuda())), B, S, hip.ptr(keep(w.cuda())), hip.ptr(keep(b.cuda())), K, hip.ptr(y), hip.stream()))
+    with kp.record() as rec:
+        hip.check(hip.lib().unet_conv1ch_fwd(hip.ptr(keep(x.cuda())), B, S, hip.ptr(keep(w.cuda())), hip.ptr(keep(b.cuda())), K, hip.ptr(y), hip.stream()))
     assert nerr(nchw(y), torch.from_numpy(ref)) < TOL
+    assert [f for f, r in zip(rec.families, rec.rows) if r["kind"] == kp.K_CONV11C] == ["conv1ch_fwd"], rec
     dz = rnd(B, K, S - 2, S - 2, seed=4).float()
     _, dw_ref, db_ref = oracle_c.conv_valid_bwd(x.double().numpy(), w.double().numpy(), dz.double().numpy(), need_dx=False)
     dw = torch.empty(K, 1, 3, 3, device="cuda"); db = torch.empty(K, device="cuda")
     sc = scratch(hip.lib().unet_conv1ch_bwd_scratch_bytes(B, S, K))
-    hip.check(hip.lib().unet_conv1ch_bwd(hip.ptr(keep(x.cuda())), B, S, K, hip.ptr(keep(nhwc(dz))), hip.ptr(dw), hip.ptr(db), hip.ptr(sc), hip.stream()))
+    with kp.record() as rec:
+        hip.check(hip.lib().unet_conv1ch_bwd(hip.ptr(keep(x.cuda())), B, S, K, hip.ptr(keep(nhwc(dz))), hip.ptr(dw), hip.ptr(db), hip.ptr(sc), hip.stream()))
+    assert [f for f, r in zip(rec.families, rec.rows) if r["kind"] == kp.K_CONV11C] == ["conv1ch_wgrad"], rec
     assert nerr(dw, torch.from_numpy(dw_ref)) < TOL
     assert nerr(db, torch.from_numpy(db_ref)) < TOL
 
@@ -319,33 +344,34 @@ def test_step_side_kernels(hip, golden_dir):
     l2, m2 = hip_optim.bce_argmax_step(lgr, labels, weight=wm)
     l2.backward()
     assert nerr(lgr.grad, torch.from_numpy(ka["bce_weighted_grad"])) < 1e-5 and np.array_equal(m2.cpu().numpy(), ka["argmax_S220"])
-    # L3 SGD momentum, two steps, against torch.optim.SGD
+    # L3 SGD momentum, two steps, against the pinned C oracle in fp64 (oracle_c.sgd_momentum: buf = first ? g : mu*buf + g;
+    # p -= lr*buf).  The C ABI takes lr and mu as fp32, so the oracle is given those same fp32 values: what remains is the
+    # kernel's fp32 arithmetic, fused or not.  Per step (elementwise; step 1 is exact: buf = g):
+    #   buf: mu*buf and + g round once each, <= 2^-24 (mu|buf| + |mu buf + g|) <= 2^-23 (mu|buf| + |g|), plus mu x the error carried in;
+    #   p:   lr*buf and p - lr*buf round once each, <= 2^-24 lr|buf| + 2^-24 |p|, plus lr x the buffer's error
+    # (tb, tp below; the lr*buf term is counted as 2^-22 lr|buf|, with room to spare).
+    def sgd_vs_oracle(ps, nsteps=2, lr=1e-4, mu=0.99):
+        lr, mu = float(np.float32(lr)), float(np.float32(mu))       # what the kernel computes with
+        p64 = [p.double().cpu().numpy().copy() for p in ps]
+        b64 = [np.zeros_like(q) for q in p64]
+        bufs = [torch.zeros_like(p) for p in ps]
+        numel = (C.c_size_t * len(ps))(*[p.numel() for p in ps])
+        tol_p = [np.zeros_like(q) for q in p64]; tol_b = [np.zeros_like(q) for q in p64]
+        for step in range(nsteps):
+            gs = [torch.randn_like(p) for p in ps]
+            for q, b_, g_, tp, tb in zip(p64, b64, gs, tol_p, tol_b):
+                prev = np.abs(b_).copy()
+                g64 = g_.double().cpu().numpy()
+                oracle_c.sgd_momentum(q, g64, b_, lr, mu, int(step == 0))
+                tb[:] = 0.0 if step == 0 else 2.0 ** -23 * (mu * prev + np.abs(g64)) + mu * tb
+                tp += 2.0 ** -24 * np.abs(q) + 2.0 ** -22 * lr * np.abs(b_) + lr * tb
+            hip.check(L.unet_sgd_momentum(hip.ptr_table(ps), hip.ptr_table(gs), hip.ptr_table(bufs), numel, len(ps), lr, mu, int(step == 0),
+                                          hip.stream()))
+        for p, q, bd, b_, tp, tb in zip(ps, p64, bufs, b64, tol_p, tol_b):
+            assert np.all(np.abs(p.double().cpu().numpy() - q) <= tp)
+            assert np.all(np.abs(bd.double().cpu().numpy() - b_) <= tb)
     torch.manual_seed(0)
-    ps = [torch.randn(n, device="cuda") for n in (5000, 3, 70001)]
-    ref = [torch.nn.Parameter(p.clone()) for p in ps]
-    opt = torch.optim.SGD(ref, lr=1e-4, momentum=0.99)
-    bufs = [torch.zeros_like(p) for p in ps]
-    numel = (C.c_size_t * 3)(*[p.numel() for p in ps])
-    for step in range(2):
-        gs = [torch.randn_like(p) for p in ps]
-        for r, gg in zip(ref, gs):
-            r.grad = gg.clone()
-        opt.step()
-        hip.check(L.unet_sgd_momentum(hip.ptr_table(ps), hip.ptr_table(gs), hip.ptr_table(bufs), numel, 3, 1e-4, 0.99, int(step == 0), hip.stream()))
-    for p, r in zip(ps, ref):
-        assert torch.allclose(p, r.detach(), rtol=0, atol=5e-7)      # <= 1 ulp at |p| ~ 4 (fma vs mul+add)
-    # pointers that are not 16-byte aligned take the 4-byte kernel: same result
+    sgd_vs_oracle([torch.randn(n, device="cuda") for n in (5000, 3, 70001)])
+    # pointers that are not 16-byte aligned take the 4-byte kernel: same bound
     base = [torch.randn(n + 1, device="cuda") for n in (5000, 70001)]
-    ps2 = [b[1:] for b in base]
-    ref2 = [torch.nn.Parameter(p.clone()) for p in ps2]
-    opt2 = torch.optim.SGD(ref2, lr=1e-4, momentum=0.99)
-    bufs2 = [torch.zeros_like(p) for p in ps2]
-    numel2 = (C.c_size_t * 2)(*[p.numel() for p in ps2])
-    for step in range(2):
-        gs = [torch.randn_like(p) for p in ps2]
-        for r, gg in zip(ref2, gs):
-            r.grad = gg.clone()
-        opt2.step()
-        hip.check(L.unet_sgd_momentum(hip.ptr_table(ps2), hip.ptr_table(gs), hip.ptr_table(bufs2), numel2, 2, 1e-4, 0.99, int(step == 0), hip.stream()))
-    for p, r in zip(ps2, ref2):
-        assert torch.allclose(p, r.detach(), rtol=0, atol=5e-7)
+    sgd_vs_oracle([b[1:] for b in base])
