@@ -63,6 +63,10 @@ _SIGS = {
     "unet_sgd_momentum": (C.c_int, [vp, vp, vp, C.POINTER(C.c_size_t), C.c_int, C.c_float, C.c_float, C.c_int, vp]),
     "unet_minmax": (C.c_int, [vp, C.c_int, C.c_size_t, vp, vp]),
     "unet_mirror_pad": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
+    "unet_tile_gather": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_long,
+                                   C.c_int, vp, vp]),
+    "unet_tile_stitch": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int,
+                                   vp, vp, vp]),
     "unet_eval_masks": (C.c_int, [vp, C.c_long, C.c_long, C.c_long, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp]),
     "unet_class_balance": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
     "unet_weighted_map_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),

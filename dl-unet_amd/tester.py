@@ -1,15 +1,23 @@
 """Drop-in for the reference's tester.py: `from tester import testing`, same signature (tester.py:13),
 output tree (images/ labels/ preds/ + test_iou.out, test_pe.out) and metrics; forward and argmax run
 on the HIP path (unet_forward, unet_argmax2).  torchvision is absent here, so the three TIFFs are
-written with PIL using torchvision.utils.save_image's conversion (clamp to [0,1], x255, round, RGB)."""
+written with PIL using torchvision.utils.save_image's conversion (clamp to [0,1], x255, round, RGB).
+
+An extension: segment(unet, images) is the paper's overlap-tile inference (Ronneberger et al. 2015, Fig. 2) for
+images of any size and shape, [H,W] in, [H,W] mask out (unet_tile_gather, unet_forward, unet_tile_stitch); tile_grid
+is its geometry."""
 import os
 from time import time
 
 import numpy as np
 import torch
 
+import _hip
 from functions import evaluation_metrics, metrics_from_counts
 import optim as hip_optim
+
+TILE_MARGIN = 92        # context each side of a tile's output that the valid convolutions eat: (S - So) / 2
+TILE_CAP = 1212         # segment(tile_size=None) never picks a larger tile: the measured winner
 
 
 def maybe_mkdir_p(path):
@@ -57,3 +65,122 @@ def testing(unet, test_loader, batch_size, device, output_dir):
     print('Testing took    :', "{:.6f}".format(time() - t0), 's')
     print(' ')
     print('Testing is finished')
+
+
+# ---- overlap-tile segmentation -------------------------------------------------------------------------------------------
+
+def valid_tile_size(S):
+    """S = 16L+60 with L even >= 8 (the sizes unet_forward accepts): 188, 220, 252, ..."""
+    return S >= 188 and (S - 188) % 32 == 0
+
+
+def _check_tile_size(S):
+    if not valid_tile_size(S):
+        hi = 188 + 32 * max(0, -(-(S - 188) // 32))
+        near = [hi] if S < 188 else [hi - 32, hi]
+        raise ValueError("tile_size %d is not a valid input size (16L+60, L even >= 8); the nearest valid size%s %s"
+                         % (S, "s are" if len(near) > 1 else " is", " and ".join(str(v) for v in near)))
+
+
+def reflect_index(i, n):
+    """numpy.pad(mode='reflect') as an index map: ... 2 1 | 0 1 2 ... n-1 | n-2 n-3 ..., the edge pixel not repeated;
+    period 2(n-1), so a pad wider than the image reflects again.  n >= 2.  (Not data.mirror_transform's asymmetric map.)"""
+    period = 2 * (n - 1)
+    i %= period
+    return i if i < n else period - i
+
+
+def tile_grid(H, W, S):
+    """Overlap-tile geometry of an H x W image for tiles of input size S: returns (ny, nx, oy0, ox0).
+
+    Output tiles are So = S - 184 square; the ny x nx grid of them is centred on the image with its top-left corner at
+    (oy0, ox0) <= 0 in image coordinates.  Tile (b, i, j), linear index t = (b*ny + i)*nx + j, reads image rows
+    [oy0 + i*So - 92, +S) and columns [ox0 + j*So - 92, +S), coordinates outside the image mapped by reflect_index
+    (numpy.pad(mode='reflect'), the mirroring the reference trains with, data.py:111 — not the asymmetric
+    mirror_transform of its test path), and its output covers rows [oy0 + i*So, +So), columns [ox0 + j*So, +So), clipped
+    to the image.  These output rectangles partition the image."""
+    So = S - 2 * TILE_MARGIN
+    if So <= 0 or H < 1 or W < 1:
+        raise ValueError("tile_grid: bad arguments H=%d W=%d S=%d" % (H, W, S))
+    ny, nx = -(-H // So), -(-W // So)
+    return ny, nx, -((ny * So - H) // 2), -((nx * So - W) // 2)
+
+
+def auto_tile_size(H, W, cap=TILE_CAP):
+    """The smallest valid S whose output So = S - 184 covers max(H, W), so the image is one tile, if that S is at most
+    `cap`; otherwise `cap`."""
+    S = 188 + 32 * max(0, -(-(max(H, W) - 4) // 32))
+    return S if S <= cap else cap
+
+
+def segment(unet, images, tile_size=None, max_batch=16, normalise=True, return_probs=False):
+    """Segment images of any size and shape with the overlap-tile strategy; returns the int64 argmax mask of the same
+    shape as `images` (and the float32 foreground probability softmax(logits)[1] with return_probs).
+
+    images: device tensor [H,W] or [B,H,W], float32 (uint8 / uint16 are converted once), H, W >= 2.
+    tile_size: the network's input size S per tile (16L+60, L even >= 8); None = auto_tile_size(H, W).
+    max_batch: tiles per forward (with bf16 tensors, fewer when max_batch tiles would make an activation tensor of 2 GiB
+        or more).  The tiles go through the module's own no-grad forward (its handle, unet_set_math and
+        base_ch apply) in chunks: gather (unet_tile_gather), forward (unet_forward), stitch (unet_tile_stitch), all on the
+        current stream; tile, logit and workspace buffers are allocated once per call.
+    normalise: each image becomes (x - min) / (max - min) first, as the reference's ImageDataset_test does (data.py:188);
+        the min / max are read back once before the first chunk, and a constant image raises ValueError.
+    Geometry and mirroring: tile_grid."""
+    if not images.is_cuda:
+        raise RuntimeError("segment: the HIP path needs the images on a HIP device (got %s); there is no CPU fallback - "
+                           "use unet.to('cuda:0') and images.to('cuda:0')" % images.device)
+    if images.dim() not in (2, 3):
+        raise ValueError("segment: expected images [H,W] or [B,H,W], got %s" % (tuple(images.shape),))
+    if images.dtype not in (torch.float32, torch.uint8, torch.uint16):
+        raise ValueError("segment: expected float32, uint8 or uint16 images, got %s" % images.dtype)
+    single = images.dim() == 2
+    x = (images[None] if single else images).to(torch.float32).contiguous()
+    B, H, W = x.shape
+    if H < 2 or W < 2:
+        raise ValueError("segment: images must be at least 2x2 to be mirrored, got %dx%d" % (H, W))
+    if B < 1:
+        raise ValueError("segment: empty batch")
+    if max_batch < 1:
+        raise ValueError("segment: max_batch must be >= 1")
+    S = auto_tile_size(H, W) if tile_size is None else int(tile_size)
+    _check_tile_size(S)
+    So = S - 2 * TILE_MARGIN
+    ny, nx, oy0, ox0 = tile_grid(H, W, S)
+    T = B * ny * nx
+    nb = min(max_batch, T)
+    dev = x.device
+    h = unet._get_handle(dev.index)
+    L = _hip.lib()
+    if L.unet_activation_bytes(h.h) == 2:
+        # bf16 tensors (unet_set_math(2)): the bf16 kernels address each activation tensor through a 32-bit buffer
+        # descriptor, so a chunk's largest one, conv11c's output [nb, S-2, S-2, base_ch], must stay below 2 GiB
+        nb = max(1, min(nb, (2 ** 31 - 2) // ((S - 2) ** 2 * unet.base_ch * 2)))
+    with torch.cuda.device(dev):
+        ptab = _hip.ptr_table([p.detach() for p in unet._params()])
+        mm = None
+        if normalise:
+            mm = torch.empty(B, 2, dtype=torch.float32, device=dev)
+            _hip.check(L.unet_minmax(_hip.ptr(x), B, H * W, _hip.ptr(mm), _hip.stream(dev)), "unet_minmax")
+            lohi = mm.cpu()
+            flat = (lohi[:, 0] == lohi[:, 1]).nonzero().flatten().tolist()
+            if flat:
+                raise ValueError("segment: image(s) %s are constant; normalise=True would divide by zero" % flat)
+        tiles = torch.empty(nb, 1, S, S, dtype=torch.float32, device=dev)
+        logits = torch.empty(nb, 2, So, So, dtype=torch.float32, device=dev)
+        nbytes = h.workspace_bytes(nb, S, False)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        mask = torch.empty(B, H, W, dtype=torch.int64, device=dev)
+        prob = torch.empty(B, H, W, dtype=torch.float32, device=dev) if return_probs else None
+        st = _hip.stream(dev)
+        for t0 in range(0, T, nb):
+            n = min(nb, T - t0)
+            _hip.check(L.unet_tile_gather(_hip.ptr(x), B, H, W, _hip.ptr(mm), S, oy0, ox0, ny, nx, t0, n, _hip.ptr(tiles), st),
+                       "unet_tile_gather")
+            _hip.check(L.unet_forward(h.h, ptab, _hip.ptr(tiles), _hip.ptr(logits), n, S, _hip.ptr(ws), nbytes, 0, st),
+                       "unet_forward")
+            _hip.check(L.unet_tile_stitch(_hip.ptr(logits), So, oy0, ox0, ny, nx, t0, n, B, H, W, _hip.ptr(mask),
+                                          _hip.ptr(prob), st), "unet_tile_stitch")
+    if single:
+        mask = mask[0]
+        prob = prob[0] if prob is not None else None
+    return (mask, prob) if return_probs else mask

@@ -217,6 +217,21 @@ int unet_sgd_momentum(void *const *params, const void *const *grads, void *const
  * without the edge pixel, bottom/right band with it); minmax (from unet_minmax, [B][2]) may be NULL.   */
 int unet_minmax(const void *x, int B, size_t n_per_image, void *out_minmax, void *stream);
 int unet_mirror_pad(const void *x, int B, int n, int S, const void *minmax, void *out, void *stream);
+/* N2 overlap-tile segmentation of images of any size (tester.segment; the reference crops test images to a square instead,
+ * data.py:174-181): the ny x nx grid of So = S-184 output tiles is centred on the image, origin (oy0, ox0) <= 0
+ * (tester.tile_grid); tile t = (b*ny + i)*nx + j reads rows [oy0 + i*So - 92, +S) and columns [ox0 + j*So - 92, +S) and
+ * covers output rows [oy0 + i*So, +So), columns [ox0 + j*So, +So), clipped to the image.
+ *   unet_tile_gather : img fp32 [B,H,W] (H, W >= 2) -> tiles_out fp32 [nt,1,S,S] = tiles t0 .. t0+nt-1, coordinates outside
+ *                      the image mapped by numpy.pad(mode='reflect') (edge pixel not repeated, period 2(n-1) when the pad is
+ *                      wider than the image; NOT unet_mirror_pad's asymmetric map); minmax ([B][2], from unet_minmax) may
+ *                      be NULL, else each value becomes (x - min) / (max - min) (fp32, true division).
+ *   unet_tile_stitch : logits fp32 [nt,2,So,So] of tiles t0 .. t0+nt-1 -> mask_i64 [B,H,W] = argmax (ties -> class 0, as
+ *                      unet_argmax2) and, if prob_f32 is not NULL, prob_f32 [B,H,W] = 1 / (1 + exp(l0 - l1)), for every
+ *                      pixel of those tiles inside the image; nothing else is written (each pixel has exactly one tile). */
+int unet_tile_gather(const void *img, int B, int H, int W, const void *minmax, int S, int oy0, int ox0, int ny, int nx, long t0, int nt,
+                     void *tiles_out, void *stream);
+int unet_tile_stitch(const void *logits, int So, int oy0, int ox0, int ny, int nx, long t0, int nt, int B, int H, int W, void *mask_i64,
+                     void *prob_f32, void *stream);
 /* N2 back end, replaces pred[:, :, pad:pad+n, pad:pad+n].argmax(dim=1) + IoU / Pixel_error counting
  * (tester.py:29-42, functions.py:174-213): mask int64 [B,n,n]; with labels int64 [B,n,n]:
  * stats u64 [B][3] = {sum(pred&label), sum(pred|label), sum|pred-label|} (exact integer atomics).      */
