@@ -14,6 +14,7 @@ _SO = os.environ.get("UNET_SO") or os.path.join(_HERE, "libunet_hip.so")
 _lib = None
 
 N_PARAMS = 46
+MAX_CLASSES = 16        # UNET_MAX_CLASSES
 
 vp = C.c_void_p
 _SIGS = {
@@ -33,6 +34,8 @@ _SIGS = {
     "unet_dp_broadcast": (C.c_int, [vp, vp, C.c_size_t, C.c_int, vp]),
     "unet_dp_join": (C.c_int, [vp, vp]),
     "unet_create": (C.c_int, [C.POINTER(vp), vp]),
+    "unet_create_classes": (C.c_int, [C.POINTER(vp), vp, C.c_int]),
+    "unet_n_classes": (C.c_int, [vp]),
     "unet_destroy": (C.c_int, [vp]),
     "unet_output_size": (C.c_int, [C.c_int, C.POINTER(C.c_int)]),
     "unet_param_count": (C.c_int, [vp, C.c_int, C.POINTER(C.c_size_t)]),
@@ -60,6 +63,10 @@ _SIGS = {
                                 vp, vp, C.c_float, vp, vp, vp]),
     "unet_onehot2": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp]),
     "unet_argmax2": (C.c_int, [vp, C.c_long, C.c_long, C.c_long, vp, C.c_int, C.c_int, C.c_int, vp]),
+    "unet_softmax_ce_scratch_bytes": (C.c_size_t, [C.c_size_t]),
+    "unet_softmax_ce_step": (C.c_int, [vp, C.c_long, C.c_long, C.c_long, C.c_int, vp, vp, C.c_long, C.c_long, C.c_long, C.c_int, C.c_int,
+                                       C.c_int, vp, vp, C.c_float, vp, vp, vp, vp]),
+    "unet_argmaxk": (C.c_int, [vp, C.c_long, C.c_long, C.c_long, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp]),
     "unet_sgd_momentum": (C.c_int, [vp, vp, vp, C.POINTER(C.c_size_t), C.c_int, C.c_float, C.c_float, C.c_int, vp]),
     "unet_minmax": (C.c_int, [vp, C.c_int, C.c_size_t, vp, vp]),
     "unet_mirror_pad": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
@@ -67,7 +74,10 @@ _SIGS = {
                                    C.c_int, vp, vp]),
     "unet_tile_stitch": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int,
                                    vp, vp, vp]),
+    "unet_tile_stitch_k": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_long, C.c_int, C.c_int, C.c_int,
+                                     C.c_int, vp, vp, vp]),
     "unet_eval_masks": (C.c_int, [vp, C.c_long, C.c_long, C.c_long, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp]),
+    "unet_eval_confusion": (C.c_int, [vp, C.c_long, C.c_long, C.c_long, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, vp]),
     "unet_class_balance": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
     "unet_weighted_map_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "unet_weighted_map": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, vp, vp, vp, vp, vp]),
@@ -89,6 +99,9 @@ _SIGS = {
     "unet_head1x1_fwd": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]),
     "unet_head1x1_bwd_scratch_bytes": (C.c_size_t, [C.c_int] * 4),
     "unet_head1x1_bwd": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp]),
+    "unet_head1xk_fwd": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]),
+    "unet_head1xk_bwd_scratch_bytes": (C.c_size_t, [C.c_int] * 5),
+    "unet_head1xk_bwd": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp]),
     "unet_conv1ch_fwd": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp]),
     "unet_conv1ch_bwd_scratch_bytes": (C.c_size_t, [C.c_int] * 3),
     "unet_conv1ch_bwd": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp]),
@@ -165,14 +178,19 @@ def ptr_table(tensors):
 class Handle:
     """RAII wrapper of unet_handle (one per device / module)."""
 
-    def __init__(self, base_ch=64, device=0, math=-1):
-        """math: arithmetic mode of this handle (include/unet_hip.h unet_set_math codes); -1 follows unet_set_math."""
+    def __init__(self, base_ch=64, device=0, math=-1, n_classes=2):
+        """math: arithmetic mode of this handle (include/unet_hip.h unet_set_math codes); -1 follows unet_set_math.
+        n_classes: output channels of the head, 2 (unet_create, the reference's net) .. MAX_CLASSES (unet_create_classes)."""
         self._h = C.c_void_p()
         cfg = UnetConfig(base_ch, device, math)
-        check(lib().unet_create(C.byref(self._h), C.byref(cfg)), "unet_create")
+        if n_classes == 2:
+            check(lib().unet_create(C.byref(self._h), C.byref(cfg)), "unet_create")
+        else:
+            check(lib().unet_create_classes(C.byref(self._h), C.byref(cfg), int(n_classes)), "unet_create_classes")
         self.base_ch = base_ch
         self.device = device
         self.math = math
+        self.n_classes = n_classes
 
     def __del__(self):
         try:

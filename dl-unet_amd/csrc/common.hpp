@@ -159,6 +159,23 @@ int conv1ch_dgrad(const void *dz, int B, int S, int K, const float *w, float *dx
 int head1x1_fwd(const void *x, int B, int H, int W, int C, const float *w, const float *bias, float *logits, int es, hipStream_t st);
 int head1x1_bwd(const void *x, int B, int H, int W, int C, const float *w, const float *dlogits, float dl_scale, void *dz, float *dw,
                 float *db, float *scratch, int es, hipStream_t st);   // every use of dlogits is dlogits * dl_scale (data parallel: 1/world)
+// K-class head (multiclass.hip): K = 2 runs head1x1_*, 2 < K <= 16 the KP-padded kernels; logits / dlogits [B,K,H,W]
+int headk_fwd(const void *x, int B, int H, int W, int C, int K, const float *w, const float *bias, float *logits, int es, hipStream_t st);
+int headk_bwd(const void *x, int B, int H, int W, int C, int K, const float *w, const float *dlogits, float dl_scale, void *dz, float *dw,
+              float *db, float *scratch, int es, hipStream_t st);
+size_t headk_bwd_scratch_bytes(int B, int H, int W, int C, int K);
+// K classes padded to the kernels' template width: 2, 4, 8 or 16 (multiclass.hip, tile.hip)
+static inline int class_pad(int K) { return K <= 2 ? 2 : K <= 4 ? 4 : K <= 8 ? 8 : 16; }
+// LAUNCH with KP_ = class_pad(K) as a compile-time constant
+#define CLASS_DISPATCH(K, LAUNCH)                                                                                      \
+    do {                                                                                                           \
+        switch (unet::class_pad(K)) {                                                                              \
+        case 2: { constexpr int KP_ = 2; LAUNCH; } break;                                                          \
+        case 4: { constexpr int KP_ = 4; LAUNCH; } break;                                                          \
+        case 8: { constexpr int KP_ = 8; LAUNCH; } break;                                                          \
+        default: { constexpr int KP_ = 16; LAUNCH; } break;                                                        \
+        }                                                                                                          \
+    } while (0)
 int maxpool2_fwd(const void *x, void *y, int B, int H, int W, int C, int es, hipStream_t st);
 int maxpool2_bwd(const void *pre, const void *dy, void *dpre, int B, int H, int W, int C, int es, hipStream_t st);
 

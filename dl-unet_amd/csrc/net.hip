@@ -50,6 +50,7 @@ static const int C2E_L[4] = {C12E, C22E, C32E, C42E};
 
 struct Plan {
     int B = 0, S = 0, base = 0, So = 0, training = 0;
+    int ncls = 2;         // classes of the head (finalconv's output channels)
     int math = 3;         // arithmetic, fixed when the forward is planned: the backward of that forward uses the same
     int ch[5];
     int ein[5], ea1[5], ea2[5], et[4], eu[4], ed1[4], ed2[4], pad[4];
@@ -72,6 +73,7 @@ struct unet_handle {
     int base_ch;
     int device;
     int math;             // arithmetic of this handle's forwards (unet_config::math); -1 = the process default at each forward
+    int n_classes = 2;    // unet_create_classes: output channels of the head, 2..UNET_MAX_CLASSES
     unet_dp *dp = nullptr;
     float grad_scale = 1.f;   // unet_set_grad_scale: the backward reads dlogits * grad_scale (data parallel: 1/world)
     // opt-in (unet_set_overlap / UNET_OVERLAP=1): the weight gradients of a backward stage run on an auxiliary stream next to
@@ -114,7 +116,7 @@ struct MathScope {
 static inline const float *adv(const float *p, size_t elems) { return (const float *)((const char *)p + elems * t_es); }
 static inline float *adv(float *p, size_t elems) { return (float *)((char *)p + elems * t_es); }
 
-static size_t layer_numel(int base, int layer, bool bias)
+static size_t layer_numel(int base, int layer, bool bias, int ncls = 2)
 {
     const int c[5] = {base, base * 2, base * 4, base * 8, base * 16};
     int ci, co, k;
@@ -142,7 +144,7 @@ static size_t layer_numel(int base, int layer, bool bias)
     case UP1: ci = c[1]; co = c[0]; k = 2; up = true; break;
     case C11E: ci = c[1]; co = c[0]; k = 3; break;
     case C12E: ci = c[0]; co = c[0]; k = 3; break;
-    default: ci = c[0]; co = 2; k = 1; break;
+    default: ci = c[0]; co = ncls; k = 1; break;
     }
     (void)up;
     return bias ? (size_t)co : (size_t)ci * co * k * k;
@@ -316,13 +318,13 @@ static WgradP upconv_wgrad_desc(const float *x, int H, int Ci, const float *dy, 
     return p;
 }
 
-static int make_plan(Plan &pl, int base, int B, int S, int training, int math)
+static int make_plan(Plan &pl, int base, int B, int S, int training, int math, int ncls = 2)
 {
     int rc = check_size(S);
     if (rc) return rc;
     if (B <= 0) { set_error("batch must be positive"); return UNET_E_BADARG; }
     pl = Plan();
-    pl.B = B; pl.S = S; pl.base = base; pl.training = training; pl.math = math;
+    pl.B = B; pl.S = S; pl.base = base; pl.training = training; pl.math = math; pl.ncls = ncls;
     MathScope ms(math);                      // the slab sizing below builds weight-gradient descriptors
     for (int l = 0; l < 5; ++l) pl.ch[l] = base << l;
     int cur = S;
@@ -351,11 +353,11 @@ static int make_plan(Plan &pl, int base, int B, int S, int training, int math)
         pl.t[l] = take(sq(pl.et[l], pl.ch[l])); pl.u[l] = take(sq(pl.eu[l], pl.ch[l]));
         pl.d1[l] = take(sq(pl.ed1[l], pl.ch[l])); pl.d2[l] = take(sq(pl.ed2[l], pl.ch[l]));
     }
-    for (int i = 0; i < UNET_N_LAYERS; ++i) pl.wt_fwd[i] = take(layer_numel(base, i, false));
+    for (int i = 0; i < UNET_N_LAYERS; ++i) pl.wt_fwd[i] = take(layer_numel(base, i, false, ncls));
     for (int i = 0; i < UNET_N_LAYERS; ++i) pl.wu_fwd[i] = take_b(math == 3 ? layer_wino_floats(base, i) * 4 : 0);
     if (training) {
         pl.xin = take_b((size_t)B * S * S * 4);
-        for (int i = 0; i < UNET_N_LAYERS; ++i) pl.wt_bwd[i] = take(layer_numel(base, i, false));
+        for (int i = 0; i < UNET_N_LAYERS; ++i) pl.wt_bwd[i] = take(layer_numel(base, i, false, ncls));
         for (int i = 0; i < UNET_N_LAYERS; ++i) pl.wu_bwd[i] = take_b(math == 3 ? layer_wino_floats(base, i) * 4 : 0);
         for (int l = 0; l < 5; ++l) { pl.g_a1[l] = take(sq(pl.ea1[l], pl.ch[l])); pl.g_a2[l] = take(sq(pl.ea2[l], pl.ch[l])); }
         for (int l = 0; l < 4; ++l) {
@@ -386,7 +388,7 @@ static int make_plan(Plan &pl, int base, int B, int S, int training, int math)
         for (int l = 0; l < 5; ++l) { upds(bias_grad_scratch_bytes(sq(pl.ea1[l], 1), pl.ch[l])); upds(bias_grad_scratch_bytes(sq(pl.ea2[l], 1), pl.ch[l])); }
         for (int l = 0; l < 4; ++l) { upds(bias_grad_scratch_bytes(sq(pl.eu[l], 1), pl.ch[l])); upds(bias_grad_scratch_bytes(sq(pl.ed1[l], 1), pl.ch[l])); }
         upds(unet_conv1ch_bwd_scratch_bytes(B, S, base));
-        upds(unet_head1x1_bwd_scratch_bytes(B, pl.So, pl.So, base));
+        upds(headk_bwd_scratch_bytes(B, pl.So, pl.So, base, ncls));
         pl.small_bytes = sm;
         pl.small = take_b(sm + 4);
     }
@@ -427,9 +429,13 @@ int unet_set_lds_dma(int mode)
                   "(one process per GPU: hipSetDevice / torch.cuda.set_device first)", (h)->device, cur_);             \
     } while (0)
 
-int unet_create(unet_handle **out, const unet_config *cfg)
+int unet_create(unet_handle **out, const unet_config *cfg) { return unet_create_classes(out, cfg, 2); }
+
+int unet_create_classes(unet_handle **out, const unet_config *cfg, int n_classes)
 {
     ARG_CHECK(out && cfg, "unet_create: null argument");
+    ARG_CHECK(n_classes >= 2 && n_classes <= UNET_MAX_CLASSES, "unet_create_classes: n_classes %d unsupported (2..%d)", n_classes,
+              UNET_MAX_CLASSES);
     ARG_CHECK(cfg->base_ch == 64 || cfg->base_ch == 32, "unet_create: base_ch %d unsupported (32 or 64)", cfg->base_ch);
     ARG_CHECK(cfg->math >= -1 && cfg->math <= 3, "unet_create: math %d unsupported (-1 = process default, 0..3)", cfg->math);
     // the zero page is made on the handle's device; the caller's current device is left as it was
@@ -443,9 +449,12 @@ int unet_create(unet_handle **out, const unet_config *cfg)
     h->base_ch = cfg->base_ch;
     h->device = cfg->device;
     h->math = cfg->math;
+    h->n_classes = n_classes;
     *out = h;
     return 0;
 }
+
+int unet_n_classes(const unet_handle *h) { return h ? h->n_classes : 0; }
 
 int unet_destroy(unet_handle *h)
 {
@@ -491,7 +500,7 @@ int unet_output_size(int S, int *out_size)
 int unet_param_count(const unet_handle *h, int idx, size_t *numel)
 {
     ARG_CHECK(h && numel && idx >= 0 && idx < UNET_N_PARAMS, "unet_param_count: bad argument");
-    *numel = layer_numel(h->base_ch, idx / 2, idx & 1);
+    *numel = layer_numel(h->base_ch, idx / 2, idx & 1, h->n_classes);
     return 0;
 }
 
@@ -499,7 +508,7 @@ size_t unet_workspace_bytes(const unet_handle *h, int B, int S, int training)
 {
     if (!h) { set_error("null handle"); return 0; }
     Plan pl;
-    if (make_plan(pl, h->base_ch, B, S, training, handle_math(h))) return 0;
+    if (make_plan(pl, h->base_ch, B, S, training, handle_math(h), h->n_classes)) return 0;
     return pl.total;
 }
 
@@ -507,7 +516,7 @@ double unet_flops(const unet_handle *h, int B, int S, int backward)
 {
     if (!h) return 0.0;
     Plan pl;
-    if (make_plan(pl, h->base_ch, B, S, 0, handle_math(h))) return 0.0;
+    if (make_plan(pl, h->base_ch, B, S, 0, handle_math(h), h->n_classes)) return 0.0;
     double f = 0.0, f11c = 0.0;
     auto conv = [&](int eo, int ci, int co, int k) { return 2.0 * B * (double)eo * eo * ci * co * k * k; };
     for (int l = 0; l < 5; ++l) {
@@ -520,7 +529,7 @@ double unet_flops(const unet_handle *h, int B, int S, int backward)
         f += 2.0 * B * (double)(pl.eu[l] / 2) * (pl.eu[l] / 2) * pl.ch[l + 1] * pl.ch[l] * 4;   // up-conv
         f += conv(pl.ed1[l], 2 * pl.ch[l], pl.ch[l], 3) + conv(pl.ed2[l], pl.ch[l], pl.ch[l], 3);
     }
-    f += conv(pl.So, pl.ch[0], 2, 1);
+    f += conv(pl.So, pl.ch[0], pl.ncls, 1);
     return backward ? 3.0 * f - f11c : f;      // bwd = dgrad + wgrad, conv11c needs no dgrad (A23)
 }
 
@@ -533,7 +542,7 @@ int unet_forward(unet_handle *h, const void *const *params, const void *x, void 
     ARG_CHECK(h && params && x && logits && workspace, "unet_forward: null argument");
     CHECK_DEVICE(h, "unet_forward");
     Plan pl;
-    int rc = make_plan(pl, h->base_ch, B, S, training, handle_math(h));
+    int rc = make_plan(pl, h->base_ch, B, S, training, handle_math(h), h->n_classes);
     if (rc) return rc;
     MathScope ms(pl.math);
     ARG_CHECK(workspace_bytes >= pl.total, "unet_forward: workspace too small (%zu < %zu)", workspace_bytes, pl.total);
@@ -614,7 +623,7 @@ int unet_forward(unet_handle *h, const void *const *params, const void *x, void 
     }
     {
         RowScope rs(FINAL, "fwd");
-        if ((rc = head1x1_fwd(WS(pl.d2[0]), B, pl.So, pl.So, ch[0], PARAM(2 * FINAL), PARAM(2 * FINAL + 1), (float *)logits, t_es, st))) return rc;
+        if ((rc = headk_fwd(WS(pl.d2[0]), B, pl.So, pl.So, ch[0], pl.ncls, PARAM(2 * FINAL), PARAM(2 * FINAL + 1), (float *)logits, t_es, st))) return rc;
     }
     if (training) h->remember(workspace, pl);
     return 0;
@@ -634,7 +643,7 @@ int unet_debug_buffer(const unet_handle *h, int B, int S, int training, const ch
 {
     ARG_CHECK(h && name && offset && extent && channels, "unet_debug_buffer: null argument");
     Plan pl;
-    int rc = make_plan(pl, h->base_ch, B, S, training, handle_math(h));
+    int rc = make_plan(pl, h->base_ch, B, S, training, handle_math(h), h->n_classes);
     if (rc) return rc;
     char kind[16];
     int l = 0;
@@ -802,7 +811,7 @@ static int backward_stage_body(unet_handle *h, const Plan &pl, int stage, const 
             ARG_CHECK(dlogits, "unet_backward: null dlogits");
             // finalconv backward, fused with the ReLU backward of conv12e -> dz of conv12e
             RowScope rs(FINAL, "bwd");
-            if ((rc = head1x1_bwd(WS(pl.d2[0]), B, pl.So, pl.So, ch[0], PARAM(2 * FINAL), (const float *)dlogits, h->grad_scale, WS(pl.g_d2[0]),
+            if ((rc = headk_bwd(WS(pl.d2[0]), B, pl.So, pl.So, ch[0], pl.ncls, PARAM(2 * FINAL), (const float *)dlogits, h->grad_scale, WS(pl.g_d2[0]),
                                   GRAD(2 * FINAL), GRAD(2 * FINAL + 1), WS(pl.small), t_es, st))) return rc;
         }
         // conv_l2e: input d1[l] (ReLU output of conv_l1e)

@@ -1,6 +1,7 @@
 // tile.hip — overlap-tile segmentation of images of any size (Ronneberger et al. 2015, Fig. 2), both HBM-bound:
 //   gather : tiles [nt,1,S,S] of a [B,H,W] image batch, numpy 'reflect' outside the image, optional (x-min)/(max-min)
-//   stitch : logits [nt,2,So,So] of those tiles -> argmax mask int64 [B,H,W] (+ foreground probability fp32)
+//   stitch : logits [nt,2,So,So] of those tiles -> argmax mask int64 [B,H,W] (+ foreground probability fp32); stitch_k: [nt,K,So,So]
+//            -> the K-way argmax (+ the softmax of all K classes)
 // Geometry (tester.tile_grid): So = S - 184, margin m = 92; the ny x nx output grid is centred on the image, top-left corner
 // (oy0, ox0) <= 0.  Tile t = (b*ny + i)*nx + j reads rows [oy0 + i*So - m, +S), columns [ox0 + j*So - m, +S) and covers
 // output rows [oy0 + i*So, +So), columns [ox0 + j*So, +So), clipped to the image; the output rectangles partition it.
@@ -103,6 +104,62 @@ __global__ __launch_bounds__(256) void tile_stitch_kernel(const float *__restric
     }
 }
 
+// K classes (2 <= K <= KP): the same lanes as tile_stitch_kernel; argmax with ties -> the lowest class (torch.argmax), and
+// optionally the softmax of all K classes, prob [B,K,H,W], as exp(l_k - max) / sum_j exp(l_j - max)
+template <int KP>
+__global__ __launch_bounds__(256) void tile_stitch_k_kernel(const float *__restrict__ logits, int So, int K, int oy0, int ox0, int ny, int nx,
+                                                            long long t0, int B, int H, int W, long long *__restrict__ mask,
+                                                            float *__restrict__ prob, size_t quads)
+{
+    const int S4 = So >> 2;
+    const size_t plane = (size_t)So * So, iplane = (size_t)H * W;
+    for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < quads; q += (size_t)gridDim.x * blockDim.x) {
+        const int xq = (int)(q % S4);
+        const size_t r = q / S4;
+        const int y = (int)(r % So);
+        const size_t tl = r / So;
+        const long long t = t0 + (long long)tl;
+        const int j = (int)(t % nx);
+        const long long ti = t / nx;
+        const int i = (int)(ti % ny);
+        const size_t b = (size_t)(ti / ny);
+        const int row = oy0 + i * So + y;
+        if ((unsigned)row >= (unsigned)H) continue;
+        const int c0 = ox0 + j * So + 4 * xq;
+        const float *p0 = logits + (size_t)K * tl * plane + (size_t)y * So + 4 * xq;
+        float l[KP][4];
+#pragma unroll
+        for (int k = 0; k < KP; ++k) {
+            if (k < K) {
+                const f32x4 a = *(const f32x4 *)(p0 + k * plane);       // So % 4 == 0 and 16-byte aligned logits (checked)
+#pragma unroll
+                for (int c = 0; c < 4; ++c) l[k][c] = a[c];
+            } else {
+#pragma unroll
+                for (int c = 0; c < 4; ++c) l[k][c] = 0.f;
+            }
+        }
+        const size_t o = (b * H + row) * (size_t)W;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const int col = c0 + c;
+            if ((unsigned)col >= (unsigned)W) continue;
+            float m = l[0][c];
+            int am = 0;
+#pragma unroll
+            for (int k = 1; k < KP; ++k) if (k < K && l[k][c] > m) { m = l[k][c]; am = k; }
+            mask[o + col] = am;
+            if (prob) {
+                float ex[KP], se = 0.f;
+#pragma unroll
+                for (int k = 0; k < KP; ++k) { ex[k] = k < K ? expf(l[k][c] - m) : 0.f; se += ex[k]; }
+#pragma unroll
+                for (int k = 0; k < KP; ++k) if (k < K) prob[(b * K + k) * iplane + (size_t)row * W + col] = ex[k] / se;
+            }
+        }
+    }
+}
+
 static inline int tile_grid1(size_t total, int cap = 16384)
 {
     size_t g = (total + 255) / 256;
@@ -167,6 +224,25 @@ int unet_tile_stitch(const void *logits, int So, int oy0, int ox0, int ny, int n
     else
         hipLaunchKernelGGL(tile_stitch_kernel<false>, dim3(tile_grid1(quads)), dim3(256), 0, st, (const float *)logits, So, oy0, ox0, ny, nx,
                            (long long)t0, H, W, (long long *)mask_i64, (float *)prob_f32, quads);
+    prof_end(st);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int unet_tile_stitch_k(const void *logits, int So, int K, int oy0, int ox0, int ny, int nx, long t0, int nt, int B, int H, int W,
+                       void *mask_i64, void *prob_f32, void *stream)
+{
+    ARG_CHECK(logits && mask_i64, "unet_tile_stitch_k: null argument");
+    ARG_CHECK(K >= 2 && K <= UNET_MAX_CLASSES, "unet_tile_stitch_k: K=%d unsupported (2..%d)", K, UNET_MAX_CLASSES);
+    ARG_CHECK(((uintptr_t)logits & 15) == 0, "unet_tile_stitch_k: logits must be 16-byte aligned");
+    int rc = check_tile_grid("unet_tile_stitch_k", B, H, W, So, oy0, ox0, ny, nx, t0, nt);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t quads = (size_t)nt * So * (So / 4);
+    ProfScope ps("N2.tile_stitch");
+    prof_begin(PK_ELEMWISE, "tile_stitch_k", st, 0.0, 0.0, (4.0 * K + 8.0 + (prob_f32 ? 4.0 * K : 0.0)) * quads * 4);
+    CLASS_DISPATCH(K, hipLaunchKernelGGL(tile_stitch_k_kernel<KP_>, dim3(tile_grid1(quads)), dim3(256), 0, st, (const float *)logits, So,
+                                         K, oy0, ox0, ny, nx, (long long)t0, B, H, W, (long long *)mask_i64, (float *)prob_f32, quads));
     prof_end(st);
     HIP_TRY(hipGetLastError());
     return 0;

@@ -101,6 +101,27 @@ def metrics_from_counts(inter, union, diff, size):
     return out
 
 
+def metrics_from_confusion(conf_b):
+    """[[IoU],[pixel error]] of one image from its K x K confusion counts (optim.crop_argmax_confusion, conf[i, j] = pixels
+    labelled i predicted j), the same (2,1) shape as metrics_from_counts: IoU = mean over the foreground classes 1..K-1 with
+    a nonzero union of inter / union (nan when there is none, like the binary 0/0); PE = mismatched pixels / pixels.
+    At K = 2 both equal metrics_from_counts' values exactly."""
+    conf = np.asarray(conf_b, dtype=np.int64)
+    K = conf.shape[0]
+    out = np.empty([2, 1])
+    ious = []
+    for c in range(1, K):
+        inter = int(conf[c, c])
+        union = int(conf[c, :].sum() + conf[:, c].sum() - conf[c, c])
+        if union:
+            ious.append(inter / union)
+    with np.errstate(invalid='ignore'):
+        out[0] = np.float64(np.nan) if not ious else (ious[0] if len(ious) == 1 else np.mean(ious))
+    size = int(conf.sum())
+    out[1] = (size - int(np.trace(conf))) / size
+    return out
+
+
 def evaluation_metrics(pred, label):
     """[[IoU],[pixel error]] as a (2,1) array (functions.py:150-170)."""
     out = np.empty([2, 1])

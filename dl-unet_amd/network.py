@@ -21,9 +21,9 @@ import dp as dp_mod
 _BASE = 64          # hard-coded in the reference (network.py:23-58)
 
 
-def _layers(base=_BASE):
+def _layers(base=_BASE, n_classes=2):
     """(name, kind, cin, cout, k) in the reference's declaration order; base = first-level width
-    (64 in the reference; 32 is the BASELINE config #5 variant)."""
+    (64 in the reference; 32 is the BASELINE config #5 variant); n_classes = finalconv's output channels."""
     c = [base, 2 * base, 4 * base, 8 * base, 16 * base]
     return [
         ("conv11c", "conv", 1, c[0], 3), ("conv12c", "conv", c[0], c[0], 3),
@@ -35,7 +35,7 @@ def _layers(base=_BASE):
         ("upconv3", "up", c[3], c[2], 2), ("conv31e", "conv", c[3], c[2], 3), ("conv32e", "conv", c[2], c[2], 3),
         ("upconv2", "up", c[2], c[1], 2), ("conv21e", "conv", c[2], c[1], 3), ("conv22e", "conv", c[1], c[1], 3),
         ("upconv1", "up", c[1], c[0], 2), ("conv11e", "conv", c[1], c[0], 3), ("conv12e", "conv", c[0], c[0], 3),
-        ("finalconv", "conv", c[0], 2, 1),
+        ("finalconv", "conv", c[0], n_classes, 1),
     ]
 
 
@@ -57,12 +57,19 @@ def _init_std(name, cin):
 _handles = {}
 
 
-def _handle(device_index, base=_BASE):
-    h = _handles.get((device_index, base))
+def _handle(device_index, base=_BASE, n_classes=2):
+    h = _handles.get((device_index, base, n_classes))
     if h is None:
-        h = _hip.Handle(base, device_index)
-        _handles[(device_index, base)] = h
+        h = _hip.Handle(base, device_index, n_classes=n_classes)
+        _handles[(device_index, base, n_classes)] = h
     return h
+
+
+def check_n_classes(n_classes):
+    """2 <= n_classes <= 16 (UNET_MAX_CLASSES), an int; raises ValueError otherwise (before any device work)."""
+    if isinstance(n_classes, bool) or not isinstance(n_classes, int) or not 2 <= n_classes <= _hip.MAX_CLASSES:
+        raise ValueError("n_classes must be an int in [2, %d], got %r" % (_hip.MAX_CLASSES, n_classes))
+    return n_classes
 
 
 def _stage_layout():
@@ -91,7 +98,7 @@ class _UnetFunction(torch.autograd.Function):
         with torch.cuda.device(x.device):               # the library checks that the handle's device is current
             nbytes = h.workspace_bytes(B, S, True)
             ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-            logits = torch.empty(B, 2, So, So, dtype=torch.float32, device=x.device)
+            logits = torch.empty(B, module.n_classes, So, So, dtype=torch.float32, device=x.device)
             ptab = _hip.ptr_table(params)
             _hip.check(_hip.lib().unet_forward(h.h, ptab, _hip.ptr(x), _hip.ptr(logits), B, S, _hip.ptr(ws), nbytes, 1,
                                                _hip.stream(x.device)), "unet_forward")
@@ -134,13 +141,17 @@ class Unet(nn.Module):
     valid 3x3 convs, skips taken AFTER the pool and zero-padded to the up-conv size,
     1x1 head without activation; fp32; input [B,1,S,S] with S = 16L+60, L even."""
 
-    def __init__(self, base_ch=_BASE):
+    def __init__(self, base_ch=_BASE, n_classes=2):
         """Unet() as in the reference (no arguments).  base_ch is an extension: 32 gives the half-width
         net of BASELINE config #5 (forward and backward; its 32-channel layers take the implicit-GEMM
-        kernels and half-filled weight-gradient tiles instead of the Winograd ones)."""
+        kernels and half-filled weight-gradient tiles instead of the Winograd ones).
+        n_classes is an extension too: a K-class head (2 <= K <= 16; finalconv [K,base_ch,1,1] + [K], logits [B,K,So,So]),
+        trained with optim.softmax_ce_step (the paper's eq. 1).  Only finalconv changes: same 46 state-dict keys, and
+        Unet(n_classes=2) draws exactly the parameters Unet() draws for a seed."""
         super(Unet, self).__init__()
         self.base_ch = base_ch
-        self._layer_table = _layers(base_ch)
+        self.n_classes = check_n_classes(n_classes)
+        self._layer_table = _layers(base_ch, n_classes)
         # nn.Conv2d / nn.ConvTranspose2d serve ONLY as parameter containers with the reference's
         # names, shapes and default-init RNG consumption (their forward is never called).
         for name, kind, cin, cout, k in self._layer_table:
@@ -168,7 +179,7 @@ class Unet(nn.Module):
         dev = params[0].device
         # a handle of this module's own: the communicator, its stream and the 1/world gradient scale live in the handle,
         # and the per-device handle is shared by every other Unet on the device
-        self._own_handle = _hip.Handle(self.base_ch, dev.index)
+        self._own_handle = _hip.Handle(self.base_ch, dev.index, n_classes=self.n_classes)
         self._dp = dp_mod.DataParallel(self._own_handle, dev, process_group, backend)
         self._dp.broadcast_parameters(params)
         return self
@@ -179,7 +190,7 @@ class Unet(nn.Module):
             if h.device != device_index:
                 raise RuntimeError("this Unet was set up for data parallel on device %d; it cannot run on device %d" % (h.device, device_index))
             return h
-        return _handle(device_index, self.base_ch)
+        return _handle(device_index, self.base_ch, self.n_classes)
 
     def _params(self):
         out = []
@@ -219,7 +230,7 @@ class Unet(nn.Module):
         with torch.cuda.device(t.device):
             nbytes = h.workspace_bytes(B, S, False)
             ws = torch.empty(nbytes, dtype=torch.uint8, device=t.device)
-            logits = torch.empty(B, 2, S - 184, S - 184, dtype=torch.float32, device=t.device)
+            logits = torch.empty(B, self.n_classes, S - 184, S - 184, dtype=torch.float32, device=t.device)
             _hip.check(_hip.lib().unet_forward(h.h, _hip.ptr_table([p.detach() for p in params]), _hip.ptr(t), _hip.ptr(logits),
                                                B, S, _hip.ptr(ws), nbytes, 0, _hip.stream(t.device)), "unet_forward")
         return logits

@@ -169,3 +169,117 @@ def crop_argmax_metrics(preds, labels=None):
     _hip.run("unet_eval_masks", preds.device, _hip.ptr(preds), preds.stride(0), preds.stride(1), preds.stride(2), pad, _hip.ptr(labels),
              _hip.ptr(mask), B, n, _hip.ptr(stats))
     return mask, stats
+
+
+# ---- K classes (Unet(n_classes=K)): the paper's loss, eq. 1 ------------------------------------------------------------------
+
+def _pixel_weight_strides(weight, preds):
+    """A per-pixel weight [B,H,W] / [H,W] / [1,H,W] (or anything that broadcasts to [B,H,W]) as three element strides
+    (batch, row, column; 0 on broadcast axes).  Unlike the BCE path's right-alignment against [B,2,H,W] (quirk Q4), the map
+    is aligned with the PIXELS: weight[b, y, x] multiplies pixel (b, y, x) of every class."""
+    B, _, H, W = preds.shape
+    weight = weight.to(preds.device, torch.float32)
+    if weight.dim() == 4 and weight.shape[1] == 1:
+        weight = weight[:, 0]
+    if weight.dim() > 3:
+        raise ValueError("softmax_ce_step: weight must broadcast to [B,H,W] = %s, got %s" % ((B, H, W), tuple(weight.shape)))
+    shape = (1,) * (3 - weight.dim()) + tuple(weight.shape)
+    st = (0,) * (3 - weight.dim()) + tuple(weight.stride())
+    out = []
+    for d, n in enumerate((B, H, W)):
+        if shape[d] == n:
+            out.append(st[d] if n > 1 else 0)
+        elif shape[d] == 1:
+            out.append(0)
+        else:
+            raise ValueError("softmax_ce_step: weight must broadcast to [B,H,W] = %s, got %s" % ((B, H, W), tuple(weight.shape)))
+    return weight, out
+
+
+class _SoftmaxCEFn(torch.autograd.Function):
+    """unet_softmax_ce_step: loss (+ its gradient), the argmax mask and the invalid-label count in one device pass."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, weight, wstrides, grad_scale, want_mask):
+        B, K, H, W = logits.shape
+        need_grad = ctx.needs_input_grad[0]
+        if logits.stride(3) != 1:
+            logits = logits.contiguous()
+        labels = labels.to(logits.device).reshape(B, H, W)
+        if labels.dtype != torch.int64:
+            labels = labels.long()
+        labels = labels.contiguous()
+        loss = torch.empty((), dtype=torch.float32, device=logits.device)
+        invalid = torch.empty((), dtype=torch.int64, device=logits.device)
+        dl = torch.empty(B, K, H, W, dtype=torch.float32, device=logits.device) if need_grad else None
+        mask = torch.empty(B, H, W, dtype=torch.int64, device=logits.device) if want_mask else None
+        sc = torch.empty(_hip.lib().unet_softmax_ce_scratch_bytes(B * H * W), dtype=torch.uint8, device=logits.device)
+        ws = wstrides if weight is not None else (0, 0, 0)
+        _hip.run("unet_softmax_ce_step", logits.device, _hip.ptr(logits), logits.stride(0), logits.stride(1), logits.stride(2), K,
+                 _hip.ptr(labels), _hip.ptr(weight), ws[0], ws[1], ws[2], B, H, W, _hip.ptr(loss), _hip.ptr(dl), float(grad_scale),
+                 _hip.ptr(mask), _hip.ptr(invalid), _hip.ptr(sc))
+        if need_grad:
+            ctx.save_for_backward(dl)
+        ctx.mark_non_differentiable(invalid)
+        if mask is not None:
+            ctx.mark_non_differentiable(mask)
+            return loss, mask, invalid
+        return loss, torch.empty(0, dtype=torch.int64, device=logits.device), invalid
+
+    @staticmethod
+    def backward(ctx, g, _gmask, _ginvalid):
+        (dl,) = ctx.saved_tensors
+        return dl * g, None, None, None, None, None
+
+
+def softmax_ce_step(preds, labels, weight=None, grad_scale=1.0, want_mask=True, validate=True):
+    """The paper's loss (Ronneberger et al. 2015, eq. 1), a pixel-wise soft-max over the K classes with a weighted
+    cross-entropy, and the argmax mask, in one kernel (unet_softmax_ce_step):
+         loss = mean over the B*H*W pixels of w * (logsumexp(preds) - preds[label])      mask = preds.argmax(dim=1)
+    preds [B,K,H,W], K >= 2 (any view with unit last stride, e.g. the trainer's centre crop), labels integer [B,1,H,W] or
+    [B,H,W] in [0, K).  weight: None, or a PER-PIXEL map that broadcasts to [B,H,W] (e.g. [B,H,W], or [H,W] for every
+    sample) - NOT bce_argmax_step's right-alignment against the class axis (quirk Q4).  Labels outside [0, K) are never used
+    as an index and add no loss and no gradient; the kernel counts them, and validate=True reads that count back (8 bytes,
+    one host sync) and raises ValueError when it is not 0.  Returns (loss, mask | None); loss.backward() feeds the gradient
+    the same pass produced (x grad_scale), as bce_argmax_step does."""
+    if preds.dim() != 4 or preds.shape[1] < 2:
+        raise ValueError("softmax_ce_step: expected preds [B,K,H,W] with K >= 2, got %s" % (tuple(preds.shape),))
+    wstrides = None
+    if weight is not None:
+        weight, wstrides = _pixel_weight_strides(weight, preds)
+    loss, mask, invalid = _SoftmaxCEFn.apply(preds, labels, weight, wstrides, grad_scale, want_mask)
+    if validate:
+        n = int(invalid.item())
+        if n:
+            raise ValueError("softmax_ce_step: %d label(s) outside [0, %d)" % (n, preds.shape[1]))
+    return loss, (mask if want_mask else None)
+
+
+def argmaxk(preds):
+    """preds [B,K,H,W] (any view with unit last stride), 2 <= K <= 16 -> int64 [B,H,W]; ties -> the lowest class (torch.argmax)."""
+    B, K, H, W = preds.shape
+    assert preds.stride(3) == 1
+    out = torch.empty(B, H, W, dtype=torch.int64, device=preds.device)
+    _hip.run("unet_argmaxk", preds.device, _hip.ptr(preds), preds.stride(0), preds.stride(1), preds.stride(2), K, _hip.ptr(out), B, H, W)
+    return out
+
+
+def crop_argmax_confusion(preds, labels=None, return_invalid=False):
+    """The K-class counterpart of crop_argmax_metrics (same centre crop): argmax over the K classes and, with int64 labels
+    [B,1,n,n] or [B,n,n], the per-image confusion counts conf[b, i, j] = pixels labelled i predicted j (unet_eval_confusion).
+    Labels outside [0, K) fall in no bin; return_invalid=True also returns their per-image count.
+    Returns (mask int64 [B,n,n], conf int64 [B,K,K] | None) (+ invalid int64 [B] | None)."""
+    B, K, So, _ = preds.shape
+    assert preds.stride(3) == 1
+    if labels is not None:
+        labels = labels.to(preds.device).reshape(B, labels.shape[-2], labels.shape[-1]).contiguous()
+        n = labels.shape[-1]
+    else:
+        n = So
+    pad = int((So - n) / 2)
+    mask = torch.empty(B, n, n, dtype=torch.int64, device=preds.device)
+    conf = torch.empty(B, K, K, dtype=torch.int64, device=preds.device) if labels is not None else None
+    invalid = torch.empty(B, dtype=torch.int64, device=preds.device) if labels is not None else None
+    _hip.run("unet_eval_confusion", preds.device, _hip.ptr(preds), preds.stride(0), preds.stride(1), preds.stride(2), pad, K,
+             _hip.ptr(labels), _hip.ptr(mask), B, n, _hip.ptr(conf), _hip.ptr(invalid))
+    return (mask, conf, invalid) if return_invalid else (mask, conf)

@@ -36,6 +36,10 @@ def save_image(tensor, path):
 
 
 def testing(unet, test_loader, batch_size, device, output_dir):
+    n_classes = getattr(unet, 'n_classes', 2)
+    if n_classes != 2:
+        raise ValueError("testing() writes the reference's binary masks and IoU / PE; this net has %d classes - use segment() and "
+                         "optim.crop_argmax_confusion / functions.metrics_from_confusion" % n_classes)
     t0 = time()
     for sub in ('images', 'preds', 'labels'):
         maybe_mkdir_p(os.path.join(output_dir, sub))
@@ -115,7 +119,9 @@ def auto_tile_size(H, W, cap=TILE_CAP):
 
 def segment(unet, images, tile_size=None, max_batch=16, normalise=True, return_probs=False):
     """Segment images of any size and shape with the overlap-tile strategy; returns the int64 argmax mask of the same
-    shape as `images` (and the float32 foreground probability softmax(logits)[1] with return_probs).
+    shape as `images` (and the float32 foreground probability softmax(logits)[1] with return_probs).  A K-class net
+    (Unet(n_classes=K), K > 2) gives the K-way argmax (ties -> the lowest class) and, with return_probs, the softmax of all
+    K classes, [B,K,H,W] ([K,H,W] for a single image) (unet_tile_stitch_k).
 
     images: device tensor [H,W] or [B,H,W], float32 (uint8 / uint16 are converted once), H, W >= 2.
     tile_size: the network's input size S per tile (16L+60, L even >= 8); None = auto_tile_size(H, W).
@@ -166,11 +172,14 @@ def segment(unet, images, tile_size=None, max_batch=16, normalise=True, return_p
             if flat:
                 raise ValueError("segment: image(s) %s are constant; normalise=True would divide by zero" % flat)
         tiles = torch.empty(nb, 1, S, S, dtype=torch.float32, device=dev)
-        logits = torch.empty(nb, 2, So, So, dtype=torch.float32, device=dev)
+        K = getattr(unet, 'n_classes', 2)
+        logits = torch.empty(nb, K, So, So, dtype=torch.float32, device=dev)
         nbytes = h.workspace_bytes(nb, S, False)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         mask = torch.empty(B, H, W, dtype=torch.int64, device=dev)
-        prob = torch.empty(B, H, W, dtype=torch.float32, device=dev) if return_probs else None
+        prob = None
+        if return_probs:
+            prob = torch.empty((B, H, W) if K == 2 else (B, K, H, W), dtype=torch.float32, device=dev)
         st = _hip.stream(dev)
         for t0 in range(0, T, nb):
             n = min(nb, T - t0)
@@ -178,8 +187,12 @@ def segment(unet, images, tile_size=None, max_batch=16, normalise=True, return_p
                        "unet_tile_gather")
             _hip.check(L.unet_forward(h.h, ptab, _hip.ptr(tiles), _hip.ptr(logits), n, S, _hip.ptr(ws), nbytes, 0, st),
                        "unet_forward")
-            _hip.check(L.unet_tile_stitch(_hip.ptr(logits), So, oy0, ox0, ny, nx, t0, n, B, H, W, _hip.ptr(mask),
-                                          _hip.ptr(prob), st), "unet_tile_stitch")
+            if K == 2:
+                _hip.check(L.unet_tile_stitch(_hip.ptr(logits), So, oy0, ox0, ny, nx, t0, n, B, H, W, _hip.ptr(mask),
+                                              _hip.ptr(prob), st), "unet_tile_stitch")
+            else:
+                _hip.check(L.unet_tile_stitch_k(_hip.ptr(logits), So, K, oy0, ox0, ny, nx, t0, n, B, H, W, _hip.ptr(mask),
+                                                _hip.ptr(prob), st), "unet_tile_stitch_k")
     if single:
         mask = mask[0]
         prob = prob[0] if prob is not None else None

@@ -8,6 +8,7 @@
     prediction (L2)    preds.argmax(dim=1) + IoU/PE        -> unet_eval_masks (fused crop+argmax+counts)
     weight map (N3)    class_balance(labels)               -> unet_class_balance
     (loss_weights='border') weighted_map(labels)                -> unet_weighted_map
+    (loss='softmax_ce')     the paper's eq. 1 for K classes       -> unet_softmax_ce_step, unet_eval_confusion
 
 Reference behaviours kept on purpose: Q3 the dataset-name comparisons are IDENTITY tests
 against string literals in the reference (trainer.py:18-27,68,110): a name arriving from argv never
@@ -24,7 +25,7 @@ from time import time
 import numpy as np
 import torch
 
-from functions import class_balance, metrics_from_counts, weighted_map
+from functions import class_balance, metrics_from_confusion, metrics_from_counts, weighted_map
 import optim as hip_optim
 
 
@@ -69,37 +70,69 @@ def _goal_for(DATASET):
     return None, None
 
 
-_LOSS_WEIGHTS = {'class_balance': class_balance, 'border': weighted_map}
+_LOSS_WEIGHTS = {'class_balance': class_balance, 'border': weighted_map, 'none': None}
+_LOSSES = ('bce', 'softmax_ce')
 
 
-def _step_loss(unet, images, labels, device, train, weight_fn=class_balance):
+def _step_loss(unet, images, labels, device, train, weight_fn=class_balance, loss_kind='bce', validate=False):
     preds = unet(images.to(device))
     labels = labels.to(device)                                  # everything below stays on the device
     pad = int((preds.shape[-1] - labels.shape[-1]) / 2)
     preds = preds[:, :, pad:labels.shape[-1] + pad, pad:labels.shape[-1] + pad]
-    weight_maps = weight_fn(labels.squeeze(1))                  # [B,H,W] (trainer.py:72 / :70), unet_class_balance / unet_weighted_map
-    # the one-hot target [1-y, y] (trainer.py:63-66) is formed inside the kernel from the integer labels
-    loss, _ = hip_optim.bce_argmax_step(preds, labels, weight=weight_maps, want_mask=False)
+    weight_maps = weight_fn(labels.squeeze(1)) if weight_fn is not None else None   # [B,H,W] (trainer.py:72 / :70)
+    if loss_kind == 'softmax_ce':
+        # eq. 1: the weight map multiplies each pixel's cross-entropy (per pixel, not Q4's class-axis alignment)
+        loss, _ = hip_optim.softmax_ce_step(preds, labels, weight=weight_maps, want_mask=False, validate=validate)
+    else:
+        # the one-hot target [1-y, y] (trainer.py:63-66) is formed inside the kernel from the integer labels
+        loss, _ = hip_optim.bce_argmax_step(preds, labels, weight=weight_maps, want_mask=False)
     return preds, loss, labels
 
 
 def _first_sample_metrics(preds, labels):
-    """argmax + IoU / pixel error of the batch in one device pass; only sample 0 is kept (quirk Q5)."""
+    """argmax + IoU / pixel error of the batch in one device pass; only sample 0 is kept (quirk Q5).  Binary heads count
+    with unet_eval_masks; K-class heads with the confusion counts (IoU = mean over the foreground classes)."""
+    if preds.shape[1] != 2:
+        _, conf = hip_optim.crop_argmax_confusion(preds.detach(), labels)
+        return metrics_from_confusion(conf[0].cpu().numpy())
     _, stats = hip_optim.crop_argmax_metrics(preds.detach(), labels)
     inter, union, diff = [int(v) for v in stats[0].tolist()]
     return metrics_from_counts(inter, union, diff, labels.shape[-1] * labels.shape[-2])
 
 
+def check_loss_options(n_classes, loss, loss_weights):
+    """Raises ValueError for a combination training() cannot run, before any device work."""
+    if loss not in _LOSSES:
+        raise ValueError("loss must be one of %s, got %r" % (list(_LOSSES), loss))
+    if loss_weights not in _LOSS_WEIGHTS:
+        raise ValueError("loss_weights must be one of %s, got %r" % (sorted(_LOSS_WEIGHTS), loss_weights))
+    if n_classes != 2:
+        if loss == 'bce':
+            raise ValueError("loss='bce' is the reference's two-class loss; a %d-class net trains with loss='softmax_ce'" % n_classes)
+        if loss_weights != 'none':
+            raise ValueError("loss_weights=%r is defined for {0,1} labels only; a %d-class net takes loss_weights='none'"
+                             % (loss_weights, n_classes))
+
+
 def training(unet, train_loader, val_loader, epochs, batch_size, device, fold_dir, DATASET, *, resume_from=None,
-             save_optimizer=False, loss_weights='class_balance'):
+             save_optimizer=False, loss_weights='class_balance', loss='bce'):
     """Reference signature (trainer.py:15) plus keyword-only extensions, all off by default so that the files
     written are exactly the reference's: resume_from = a checkpoint made by checkpoint.py (weights + SGD momentum +
     scheduler + epoch), save_optimizer = also write models/checkpoint_latest.pth every epoch (both SURVEY N4);
     loss_weights = 'border' weights the training and the validation loss with weighted_map (the paper's border
-    map, what the reference's HeLa branch asks for at trainer.py:68-70,110-112) instead of class_balance."""
-    if loss_weights not in _LOSS_WEIGHTS:
-        raise ValueError("loss_weights must be one of %s, got %r" % (sorted(_LOSS_WEIGHTS), loss_weights))
+    map, what the reference's HeLa branch asks for at trainer.py:68-70,110-112) instead of class_balance.
+    loss = 'softmax_ce' trains with the paper's eq. 1 (optim.softmax_ce_step, a pixel-wise soft-max over the classes with a
+    weighted cross-entropy) instead of the reference's per-channel BCE ('bce', the default).  A net with n_classes = K > 2
+    needs loss='softmax_ce' and loss_weights='none' (uniform; class_balance and 'border' are defined for {0,1} labels), and
+    its IoU / PE series come from the confusion counts (mean IoU over the foreground classes; first sample, Q5).  With K = 2,
+    both losses take all three loss_weights: loss='bce' with loss_weights='none' is the reference's BCE without a weight map
+    (uniform), 'softmax_ce' with 'class_balance' / 'border' weights each pixel's cross-entropy by the map.  Labels are validated (an error if any is outside [0, K)) on the first
+    training step of every epoch only: the check reads a count back to the host, and a sync on every step would add host gap
+    to every step; labels outside [0, K) in the other steps add no loss and no gradient."""
+    n_classes = getattr(unet, 'n_classes', 2)
+    check_loss_options(n_classes, loss, loss_weights)
     weight_fn = _LOSS_WEIGHTS[loss_weights]
+    loss_kind = loss
     when_to_stop, goal = _goal_for(DATASET)
 
     optimizer = hip_optim.SGD(unet.parameters(), lr=0.0001, momentum=0.99)
@@ -138,9 +171,9 @@ def training(unet, train_loader, val_loader, epochs, batch_size, device, fold_di
         train_eval = None
         val_eval = None
 
-        for images, labels in train_loader:
+        for step, (images, labels) in enumerate(train_loader):
             optimizer.zero_grad()
-            preds, loss, labels = _step_loss(unet, images, labels, device, True, weight_fn)
+            preds, loss, labels = _step_loss(unet, images, labels, device, True, weight_fn, loss_kind, step == 0)
             loss.backward()
             optimizer.step()
             total_loss += loss.detach()
@@ -150,7 +183,7 @@ def training(unet, train_loader, val_loader, epochs, batch_size, device, fold_di
 
         with torch.no_grad():
             for images, labels in val_loader:
-                preds, loss, labels = _step_loss(unet, images, labels, device, False, weight_fn)
+                preds, loss, labels = _step_loss(unet, images, labels, device, False, weight_fn, loss_kind)
                 total_loss_val += loss
                 if val_eval is None:
                     val_eval = _first_sample_metrics(preds, labels)

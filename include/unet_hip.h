@@ -30,6 +30,7 @@ extern "C" {
 
 #define UNET_N_PARAMS 46          /* 23 layers x (weight, bias), network.py:23-58 order */
 #define UNET_N_LAYERS 23
+#define UNET_MAX_CLASSES 16        /* unet_create_classes: 2 <= n_classes <= 16 */
 
 enum {
     UNET_E_BADSIZE  = -1,         /* S must be 16L+60 with L even >= 8 (network.py:124-127, Q7) */
@@ -75,8 +76,13 @@ int unet_get_math(void);
 int unet_set_lds_dma(int mode);
 
 /* ---- handle ------------------------------------------------------------------------------
- * replaces: Unet.__init__ bookkeeping that is not parameters (network.py:20-58).            */
+ * replaces: Unet.__init__ bookkeeping that is not parameters (network.py:20-58).
+ * unet_create makes the reference's 2-class net.  unet_create_classes makes a K-class one (Unet(n_classes=K), 2 <= K <= 16):
+ * only the head changes - finalconv is [K,C,1,1] + [K] (parameter indices 44/45), logits and dlogits are [B,K,So,So];
+ * K = 2 is exactly unet_create.  unet_n_classes returns a handle's K.                                  */
 int unet_create(unet_handle **out, const unet_config *cfg);
+int unet_create_classes(unet_handle **out, const unet_config *cfg, int n_classes);
+int unet_n_classes(const unet_handle *h);
 int unet_destroy(unet_handle *h);
 
 /* Size contract of the valid-conv net (functions.py:121-146 input_size_compute):
@@ -91,7 +97,7 @@ size_t unet_workspace_bytes(const unet_handle *h, int B, int S, int training);
 /* ---- whole path ---------------------------------------------------------------------------
  * replaces: Unet.forward (network.py:129-192), called at trainer.py:58,100 and tester.py:27.
  *   params : host array of 46 device pointers, reference state-dict order/layout (fp32)
- *   x      : [B,1,S,S] fp32;  logits : [B,2,S-184,S-184] fp32 NCHW
+ *   x      : [B,1,S,S] fp32;  logits : [B,K,S-184,S-184] fp32 NCHW (K = unet_n_classes, 2 for unet_create)
  *   training=1 keeps the activation stash in `workspace` for unet_backward.               */
 int unet_forward(unet_handle *h, const void *const *params, const void *x, void *logits,
                  int B, int S, void *workspace, size_t workspace_bytes, int training,
@@ -99,7 +105,7 @@ int unet_forward(unet_handle *h, const void *const *params, const void *x, void 
 
 /* replaces: the autograd backward of every op in Unet.forward, triggered by
  * loss.backward() at trainer.py:77.
- *   dlogits : [B,2,So,So] fp32 NCHW (contiguous)
+ *   dlogits : [B,K,So,So] fp32 NCHW (contiguous)
  *   grads   : host array of 46 device pointers, same shapes/layouts as params; OVERWRITTEN
  * Stages let the caller overlap the gradient all-reduce with the rest of the backward:
  * stage s in [0, unet_backward_stages()) must be run in increasing order; after stage s
@@ -199,11 +205,26 @@ int unet_bce_step(const void *logits, long xsB, long xsC, long xsH, const void *
                   float grad_scale, void *mask_i64, void *scratch, void *stream);
 /* builds ll from integer labels on device: ll[:,0]=1-y, ll[:,1]=y (trainer.py:63-66) */
 int unet_onehot2(const void *labels_i64, void *target, int B, int H, int W, void *stream);
+/* L1 + L2 for K classes, the paper's loss (Ronneberger et al. 2015, eq. 1: a pixel-wise soft-max with a weighted cross-entropy):
+ *   logits [B,K,H,W] fp32 through element strides (batch, class plane, row; unit pixel stride), 2 <= K <= 16;
+ *   labels int64 [B,H,W] (dense) in [0, K); weight: NULL or a PER-PIXEL fp32 map through strides (wsB, wsH, wsW), 0 = broadcast.
+ *   loss_out : 1 fp32 = mean over the B*H*W pixels of w * (logsumexp(l) - l_label) (max-subtracted; partials in double, fixed order)
+ *   dlogits  : NULL or dense [B,K,H,W] = w * (softmax(l) - onehot(label)) / (B*H*W) * grad_scale
+ *   mask_i64 : NULL or [B,H,W] argmax, ties -> the lowest class index (torch.argmax)
+ *   invalid_u64 : NULL or 1 u64 = pixels whose label is outside [0, K): they are never used as an index and add no loss and no gradient.
+ * scratch: >= unet_softmax_ce_scratch_bytes(B*H*W). */
+size_t unet_softmax_ce_scratch_bytes(size_t npix);
+int unet_softmax_ce_step(const void *logits, long xsB, long xsC, long xsH, int K, const void *labels_i64, const void *weight,
+                         long wsB, long wsH, long wsW, int B, int H, int W, void *loss_out, void *dlogits, float grad_scale,
+                         void *mask_i64, void *invalid_u64, void *scratch, void *stream);
 
 /* L2 replaces preds.argmax(dim=1) (trainer.py:82, tester.py:30): [B,2,H,W] fp32 with row
  * stride ld (elements) and plane stride ps -> [B,H,W] int64; ties -> class 0.               */
 int unet_argmax2(const void *logits, long batch_stride, long plane_stride, long row_stride,
                  void *out_i64, int B, int H, int W, void *stream);
+/* K-way argmax (2 <= K <= 16) of [B,K,H,W] fp32 with the same strides -> [B,H,W] int64; ties -> the lowest class index. */
+int unet_argmaxk(const void *logits, long batch_stride, long plane_stride, long row_stride, int K, void *out_i64, int B, int H, int W,
+                 void *stream);
 
 /* L3 replaces optim.SGD(lr, momentum).step() (trainer.py:30,78): for each of n tensors
  * buf = first ? g : mu*buf + g ; p -= lr*buf.  Pointer tables are HOST arrays.             */
@@ -232,11 +253,21 @@ int unet_tile_gather(const void *img, int B, int H, int W, const void *minmax, i
                      void *tiles_out, void *stream);
 int unet_tile_stitch(const void *logits, int So, int oy0, int ox0, int ny, int nx, long t0, int nt, int B, int H, int W, void *mask_i64,
                      void *prob_f32, void *stream);
+/*   unet_tile_stitch_k : the same grid contract for K classes (2 <= K <= 16): logits fp32 [nt,K,So,So] (16-byte aligned) ->
+ *                      mask_i64 [B,H,W] = argmax, ties -> the lowest class, and, if prob_f32 is not NULL, prob_f32 [B,K,H,W] =
+ *                      the softmax of the K logits (max-subtracted).                                                       */
+int unet_tile_stitch_k(const void *logits, int So, int K, int oy0, int ox0, int ny, int nx, long t0, int nt, int B, int H, int W,
+                       void *mask_i64, void *prob_f32, void *stream);
 /* N2 back end, replaces pred[:, :, pad:pad+n, pad:pad+n].argmax(dim=1) + IoU / Pixel_error counting
  * (tester.py:29-42, functions.py:174-213): mask int64 [B,n,n]; with labels int64 [B,n,n]:
  * stats u64 [B][3] = {sum(pred&label), sum(pred|label), sum|pred-label|} (exact integer atomics).      */
 int unet_eval_masks(const void *logits, long batch_stride, long plane_stride, long row_stride, int pad,
                     const void *labels_i64, void *mask_i64, int B, int n, void *stats_u64, void *stream);
+/* The K-class counterpart (2 <= K <= 16), same crop rule: mask int64 [B,n,n] = argmax (ties -> the lowest class); with labels
+ * int64 [B,n,n]: conf_u64 [B][K][K], conf[b][i][j] = pixels of image b with label i predicted j, and invalid_u64 [B] = pixels
+ * whose label is outside [0, K) (in no bin).  Exact: per-block LDS histograms, one integer atomic per bin.  */
+int unet_eval_confusion(const void *logits, long batch_stride, long plane_stride, long row_stride, int pad, int K,
+                        const void *labels_i64, void *mask_i64, int B, int n, void *conf_u64, void *invalid_u64, void *stream);
 /* N3, replaces functions.class_balance (functions.py:82-117) for {0,1} labels: w = 1 on cells,
  * count(1)/count(0) on background; counts_u64 [B] receives count(1) (caller checks the degenerate case). */
 int unet_class_balance(const void *labels_i64, int B, int H, int W, void *weights, void *counts_u64, void *stream);
@@ -306,6 +337,12 @@ size_t unet_head1x1_bwd_scratch_bytes(int B, int H, int W, int C);
 int unet_head1x1_bwd(const void *x, int B, int H, int W, int C, const void *w,
                      const void *dlogits, void *dz, void *dw, void *db, void *scratch,
                      void *stream);
+/* finalconv of a K-class net (2 <= K <= 16): logits NCHW [B,K,H,W]; backward dz = (sum_k dl_k w_k) * (x > 0), dw [K,C,1,1] and
+ * db [K] from fixed-order per-block partials.  K = 2 runs the head1x1 kernels above (bit-identical to them).  */
+int unet_head1xk_fwd(const void *x, int B, int H, int W, int C, int K, const void *w, const void *bias, void *logits, void *stream);
+size_t unet_head1xk_bwd_scratch_bytes(int B, int H, int W, int C, int K);
+int unet_head1xk_bwd(const void *x, int B, int H, int W, int C, int K, const void *w, const void *dlogits, void *dz, void *dw, void *db,
+                     void *scratch, void *stream);
 /* conv11c (network.py:23,131): the 1->K stencil layer, direct HBM-bound kernel.
  * x [B,S,S] -> y [B,S-2,S-2,K] (+ReLU); backward gives dw [K,1,3,3], db [K] only.          */
 int unet_conv1ch_fwd(const void *x, int B, int S, const void *w, const void *bias, int K,
