@@ -41,25 +41,53 @@ const float *zero_page()
     return g_zero[dev];
 }
 
-// layer indices in the reference's declaration order (network.py:23-58)
-enum { C11C, C12C, C21C, C22C, C31C, C32C, C41C, C42C, C51C, C52C, UP4, C41E, C42E, UP3, C31E, C32E,
-       UP2, C21E, C22E, UP1, C11E, C12E, FINAL };
-static const int UP_L[4] = {UP1, UP2, UP3, UP4};
-static const int C1E_L[4] = {C11E, C21E, C31E, C41E};
-static const int C2E_L[4] = {C12E, C22E, C32E, C42E};
+// ---- the network, stated once ---------------------------------------------------------------------
+// Everything that depends on the shape of the network (parameter sizes, workspace plan, profile rows, flop counts, forward
+// and backward walks, backward stages) reads this table.
+enum { K_CONV1, K_CONV, K_CAT, K_UP, K_HEAD };          // conv11c (1 input channel) / 3x3 conv / 3x3 conv over the virtual concat / up-conv / head
+enum { T_A1, T_A2, T_T, T_U, T_D1, T_D2, N_TENSORS, T_NONE = N_TENSORS };   // activation tensors of a level (TENSOR_NAME)
+struct Layer {
+    const char *name;     // LAYER_NAME: profile rows are "<name>.<fwd|dgrad|wgrad|bwd>" (bench.py maps them onto SURVEY 8a rows)
+    int kind, level;
+    int ci, co;           // the levels whose width (base_ch << level) the input / output channels are; -1: 1 channel in, n_classes out
+    int stage;            // backward stage (reverse layer order, so gradient buckets complete early for the all-reduce)
+    int in, out;          // tensor read (at level ci; K_CAT: the padded skip t[level] next to u[level]) and written (at level)
+};
+// the reference's declaration order (network.py:23-58) = forward order; the backward walks each stage's layers in reverse
+static const Layer LAYERS[UNET_N_LAYERS] = {
+    {"conv11c", K_CONV1, 0, -1, 0, 5, T_NONE, T_A1}, {"conv12c", K_CONV, 0, 0, 0, 5, T_A1, T_A2},
+    {"conv21c", K_CONV, 1, 0, 1, 5, T_T, T_A1},      {"conv22c", K_CONV, 1, 1, 1, 5, T_A1, T_A2},
+    {"conv31c", K_CONV, 2, 1, 2, 5, T_T, T_A1},      {"conv32c", K_CONV, 2, 2, 2, 5, T_A1, T_A2},
+    {"conv41c", K_CONV, 3, 2, 3, 5, T_T, T_A1},      {"conv42c", K_CONV, 3, 3, 3, 5, T_A1, T_A2},
+    {"conv51c", K_CONV, 4, 3, 4, 4, T_T, T_A1},      {"conv52c", K_CONV, 4, 4, 4, 4, T_A1, T_A2},
+    {"upconv4", K_UP, 3, 4, 3, 3, T_A2, T_U}, {"conv41e", K_CAT, 3, 4, 3, 3, T_T, T_D1}, {"conv42e", K_CONV, 3, 3, 3, 3, T_D1, T_D2},
+    {"upconv3", K_UP, 2, 3, 2, 2, T_D2, T_U}, {"conv31e", K_CAT, 2, 3, 2, 2, T_T, T_D1}, {"conv32e", K_CONV, 2, 2, 2, 2, T_D1, T_D2},
+    {"upconv2", K_UP, 1, 2, 1, 1, T_D2, T_U}, {"conv21e", K_CAT, 1, 2, 1, 1, T_T, T_D1}, {"conv22e", K_CONV, 1, 1, 1, 1, T_D1, T_D2},
+    {"upconv1", K_UP, 0, 1, 0, 0, T_D2, T_U}, {"conv11e", K_CAT, 0, 1, 0, 0, T_T, T_D1}, {"conv12e", K_CONV, 0, 0, 0, 0, T_D1, T_D2},
+    {"finalconv", K_HEAD, 0, 0, -1, 0, T_D2, T_NONE}};
+enum { C11C = 0, FINAL = UNET_N_LAYERS - 1 };
+static const int N_STAGES = 6;
+// unet_debug_buffer's names: "<tensor>_<level>", "g_<tensor>_<level>" for the gradient
+static const struct { const char *name; int levels; } TENSOR_NAME[N_TENSORS] = {{"a1", 5}, {"a2", 5}, {"t", 4}, {"u", 4}, {"d1", 4}, {"d2", 4}};
+
+// one activation tensor, NHWC [B, e, e, c]: workspace offset of the tensor and (training) of its gradient
+struct Act { size_t off = 0, g = 0; int e = 0, c = 0; };
 
 struct Plan {
     int B = 0, S = 0, base = 0, So = 0, training = 0;
     int ncls = 2;         // classes of the head (finalconv's output channels)
     int math = 3;         // arithmetic, fixed when the forward is planned: the backward of that forward uses the same
-    int ch[5];
-    int ein[5], ea1[5], ea2[5], et[4], eu[4], ed1[4], ed2[4], pad[4];
-    size_t a1[5], a2[5], t[4], u[4], d1[4], d2[4];
+    int ch[5], pad[4];    // pad > 0: the skip t[l] is zero-padded to u[l]'s extent, pad < 0: cropped
+    // per level: the two encoder convs' outputs, the pool's, the up-conv's, the two decoder convs'
+    Act a1[5], a2[5], t[4], u[4], d1[4], d2[4];
+    size_t g_ts[4];       // the skip half of conv_l1e's dgrad; added to g_t by the dgrad of the conv that reads t[l]
     size_t wt_fwd[UNET_N_LAYERS], wt_bwd[UNET_N_LAYERS];
     size_t wu_fwd[UNET_N_LAYERS], wu_bwd[UNET_N_LAYERS];     // Winograd-transformed filters (math mode 3), 16/9 of the 3x3 layers
-    size_t g_a1[5], g_a2[5], g_t[4], g_ts[4], g_u[4], g_d1[4], g_d2[4];
     size_t slab = 0, slab_bytes = 0, small = 0, small_bytes = 0, xin = 0;
     size_t total = 0;
+    const Act &act(int tensor, int l) const { const Act *const v[N_TENSORS] = {a1, a2, t, u, d1, d2}; return v[tensor][l]; }
+    const Act &in(const Layer &L) const { return act(L.in, L.kind == K_CAT ? L.level : L.ci); }     // K_CAT: the skip; u[level] is the other
+    const Act &out(const Layer &L) const { return act(L.out, L.level); }
 };
 
 }  // namespace unet
@@ -113,54 +141,30 @@ struct MathScope {
     ~MathScope() { t_math = prev; t_es = prev == 2 ? 2 : 4; }
 };
 // pointer arithmetic on tensors whose element size depends on the mode (the descriptors carry them as float*)
-static inline const float *adv(const float *p, size_t elems) { return (const float *)((const char *)p + elems * t_es); }
 static inline float *adv(float *p, size_t elems) { return (float *)((char *)p + elems * t_es); }
+
+
+static int layer_ci(int base, const Layer &L) { return L.ci < 0 ? 1 : base << L.ci; }
+static int layer_co(int base, const Layer &L, int ncls) { return L.co < 0 ? ncls : base << L.co; }
+static int layer_taps(const Layer &L) { return L.kind == K_UP ? 2 : L.kind == K_HEAD ? 1 : 3; }       // k of its k x k filter
 
 static size_t layer_numel(int base, int layer, bool bias, int ncls = 2)
 {
-    const int c[5] = {base, base * 2, base * 4, base * 8, base * 16};
-    int ci, co, k;
-    bool up = false;
-    switch (layer) {
-    case C11C: ci = 1; co = c[0]; k = 3; break;
-    case C12C: ci = c[0]; co = c[0]; k = 3; break;
-    case C21C: ci = c[0]; co = c[1]; k = 3; break;
-    case C22C: ci = c[1]; co = c[1]; k = 3; break;
-    case C31C: ci = c[1]; co = c[2]; k = 3; break;
-    case C32C: ci = c[2]; co = c[2]; k = 3; break;
-    case C41C: ci = c[2]; co = c[3]; k = 3; break;
-    case C42C: ci = c[3]; co = c[3]; k = 3; break;
-    case C51C: ci = c[3]; co = c[4]; k = 3; break;
-    case C52C: ci = c[4]; co = c[4]; k = 3; break;
-    case UP4: ci = c[4]; co = c[3]; k = 2; up = true; break;
-    case C41E: ci = c[4]; co = c[3]; k = 3; break;
-    case C42E: ci = c[3]; co = c[3]; k = 3; break;
-    case UP3: ci = c[3]; co = c[2]; k = 2; up = true; break;
-    case C31E: ci = c[3]; co = c[2]; k = 3; break;
-    case C32E: ci = c[2]; co = c[2]; k = 3; break;
-    case UP2: ci = c[2]; co = c[1]; k = 2; up = true; break;
-    case C21E: ci = c[2]; co = c[1]; k = 3; break;
-    case C22E: ci = c[1]; co = c[1]; k = 3; break;
-    case UP1: ci = c[1]; co = c[0]; k = 2; up = true; break;
-    case C11E: ci = c[1]; co = c[0]; k = 3; break;
-    case C12E: ci = c[0]; co = c[0]; k = 3; break;
-    default: ci = c[0]; co = ncls; k = 1; break;
-    }
-    (void)up;
-    return bias ? (size_t)co : (size_t)ci * co * k * k;
+    const Layer &L = LAYERS[layer];
+    const int k = layer_taps(L);
+    return bias ? (size_t)layer_co(base, L, ncls) : (size_t)layer_ci(base, L) * layer_co(base, L, ncls) * k * k;
 }
 
 // floats of the Winograd U matrix of a layer (0 for the layers wino.hip does not serve: conv11c, up-convs, head)
 static size_t layer_wino_floats(int base, int layer)
 {
-    if (layer == C11C || layer == UP4 || layer == UP3 || layer == UP2 || layer == UP1 || layer == FINAL) return 0;
+    const Layer &L = LAYERS[layer];
+    if (L.kind != K_CONV && L.kind != K_CAT) return 0;
     // U is kept in whole 64-row blocks (wino_u_floats); forward: rows = output channels, one sub-matrix per source of the
     // virtual concat; dgrad: rows = input channels, one launch (and sub-matrix) per source.  The larger of the two directions.
-    const size_t co = layer_numel(base, layer, true);
-    const size_t ci = layer_numel(base, layer, false) / 9 / co;
-    const bool two = layer == C11E || layer == C21E || layer == C31E || layer == C41E;
-    const size_t fwd = wino_u_floats((int)ci, (int)co);
-    const size_t bwd = two ? 2 * wino_u_floats((int)co, (int)(ci / 2)) : wino_u_floats((int)co, (int)ci);
+    const int ci = layer_ci(base, L), co = layer_co(base, L, 2);
+    const size_t fwd = wino_u_floats(ci, co);
+    const size_t bwd = L.kind == K_CAT ? 2 * wino_u_floats(co, ci / 2) : wino_u_floats(co, ci);
     return fwd > bwd ? fwd : bwd;
 }
 
@@ -178,8 +182,6 @@ struct WLayer {
         return dgrad ? pack_conv_dgrad(w, wt, O, I, t_es, st) : pack_conv_fwd(w, wt, O, C1, C2, t_es, st);
     }
 };
-static WLayer wl_fwd(const float *w, int K, int C1, int C2, float *wt) { return WLayer{w, K, C1 + C2, false, wt, C1, C2}; }
-static WLayer wl_dgrad(const float *w, int K, int C, float *wt) { return WLayer{w, K, C, true, wt, 0, 0}; }
 
 // Route a 3x3 launch: math mode 3 and a shape wino.hip takes -> transform the filters (rows n0.., columns k0.. of the
 // launch's filter matrix within the layer) into `wu`; otherwise make sure the packed igemm weights exist.
@@ -204,13 +206,9 @@ static int check_size(int S)
     return 0;
 }
 
-static const char *const LAYER_NAME[UNET_N_LAYERS] = {
-    "conv11c", "conv12c", "conv21c", "conv22c", "conv31c", "conv32c", "conv41c", "conv42c", "conv51c", "conv52c",
-    "upconv4", "conv41e", "conv42e", "upconv3", "conv31e", "conv32e", "upconv2", "conv21e", "conv22e",
-    "upconv1", "conv11e", "conv12e", "finalconv"};
-// profile row of a launch group: "<layer>.<fwd|dgrad|wgrad>" (bench.py maps them onto SURVEY 8a rows)
+// profile row of a launch group: "<layer>.<fwd|dgrad|wgrad>"
 struct RowScope : ProfScope {
-    static const char *make(char (&buf)[40], int layer, const char *what) { snprintf(buf, sizeof(buf), "%s.%s", LAYER_NAME[layer], what); return buf; }
+    static const char *make(char (&buf)[40], int layer, const char *what) { snprintf(buf, sizeof(buf), "%s.%s", LAYERS[layer].name, what); return buf; }
     char buf[40];
     RowScope(int layer, const char *what) : ProfScope(make(buf, layer, what)) {}
 };
@@ -232,16 +230,20 @@ static IgemmP conv_fwd_desc(const float *x1, int H1, int W1, int C1, int pad1, c
     return p;
 }
 
-// Forward 3x3 conv over the virtual concat.  When the skip source is zero-padded (pad > 0) its taps only
+// Forward 3x3 conv, over one source or over the virtual concat.  One launch: lazy pack or Winograd transform of the filters,
+// and with `pool_dst` the 2x2 max-pool of the output written by the Winograd epilogue where that fuses (*pool_fused).
+// When the skip source is zero-padded (pad > 0) its taps only
 // reach the output window [pad-2, pad+H1): running it as part of one GEMM would spend 30-50 % of that
 // layer's MFMA work on zeros.  So: launch 1 = up-conv source over the full domain (+bias, ReLU outside the
 // window), launch 2 = skip source over the window only, accumulating in place (+ReLU).  Same math, same
 // K order per source; the two partial sums are added in fp32.
 static int conv_fwd_launch(const float *x1, int H1, int C1, int pad1, const float *x2, int C2, int B, int H,
-                           WLayer &L, const float *bias, int K, int relu, float *y, hipStream_t st, float *wu = nullptr)
+                           const float *w_oihw, float *wt, const float *bias, int K, int relu, float *y, hipStream_t st, float *wu = nullptr,
+                           float *pool_dst = nullptr, bool *pool_fused = nullptr)
 {
     const int Ho = H - 2;
-    const float *wt = L.wt;
+    if (!x2) C2 = 0;
+    WLayer L{w_oihw, K, C1 + C2, false, wt, C1, C2};
     int rc;
     int w0 = pad1 - 2; if (w0 < 0) w0 = 0;
     int w1 = pad1 + H1; if (w1 > Ho) w1 = Ho;
@@ -250,8 +252,9 @@ static int conv_fwd_launch(const float *x1, int H1, int C1, int pad1, const floa
     //  the layer's output — and the zero-padded taps cost that mode no memory traffic, only cheap MFMA time)
     const bool split = x2 && pad1 > 0 && t_math != 2 && (double)(w1 - w0) * (w1 - w0) < split_thr * (double)Ho * Ho;
     if (!split) {
-        IgemmP p = conv_fwd_desc(x1, H1, H1, C1, pad1, x2, x2 ? C2 : 0, B, H, H, wt, bias, K, relu, y);
+        IgemmP p = conv_fwd_desc(x1, H1, H1, C1, pad1, x2, C2, B, H, H, wt, bias, K, relu, y);
         if ((rc = with_wino(p, wu, L, 0, 0, st))) return rc;
+        if (pool_dst && p.wino_u && wino_fuses_pool(p)) { p.pool_dst = pool_dst; *pool_fused = true; }
         return launch_igemm(p, st);
     }
     const int ldw = 9 * (C1 + C2);
@@ -267,6 +270,34 @@ static int conv_fwd_launch(const float *x1, int H1, int C1, int pad1, const floa
     b.add = y;
     if ((rc = with_wino(b, wu ? wu + wino_u_floats(C2, K) : nullptr, L, 0, 0, st))) return rc;
     return launch_igemm(b, st);
+}
+
+// 2x2 stride-2 transposed conv as a GEMM over the input pixels: [B*H*W, Ci] x [Ci, 4*Co], scattered to [B, 2H, 2W, Co]
+static IgemmP upconv_fwd_desc(const float *x, int B, int H, int W, int Ci, const float *wt, const float *bias, int Co, float *y)
+{
+    IgemmP u{};
+    u.nsrc = 1; u.src[0] = GSrc{x, H, W, Ci, 0, Ci, 0};
+    u.wt = wt; u.Kd = Ci;
+    u.T = 1; u.TX = 1; u.stride = 1;
+    u.NB = B; u.OH = H; u.OW = W; u.M = B * H * W; u.Nn = 4 * Co;
+    u.dst = y; u.DH = 2 * H; u.DW = 2 * W; u.DC = Co; u.scatter = 1; u.cout = Co;
+    u.bias = bias;
+    u.math = t_math;
+    return u;
+}
+
+// its dgrad: a 2x2 stride-2 conv of dy [B, 2H, 2W, Co], masked by the ReLU output the up-conv read
+static IgemmP upconv_dgrad_desc(const float *dy, int B, int H, int W, int Ci, const float *wt, int Co, float *dx, const float *mask)
+{
+    IgemmP d{};
+    d.nsrc = 1; d.src[0] = GSrc{dy, 2 * H, 2 * W, Co, 0, Co, 0};
+    d.wt = wt; d.Kd = 4 * Co;
+    d.T = 4; d.TX = 2; d.stride = 2;
+    d.NB = B; d.OH = H; d.OW = W; d.M = B * H * W; d.Nn = Ci;
+    d.dst = dx; d.DH = H; d.DW = W; d.DC = Ci;
+    d.mask = mask;
+    d.math = t_math;
+    return d;
 }
 
 // dgrad of a 3x3 valid conv: dx over the window [oy0, oy0+OHW) of the conv's (virtual) input
@@ -318,6 +349,90 @@ static WgradP upconv_wgrad_desc(const float *x, int H, int Ci, const float *dy, 
     return p;
 }
 
+// dgrad launches of a 3x3 conv, one per source that wants its gradient: the first source (C1 channels, extent H1, only its
+// window at pad1 of the virtual input) and, over the virtual concat, the second (C2 channels, the full extent H; else C2 = 0)
+static int conv_dgrad_launch(const float *dz, int Ho, int K, int B, const float *w_oihw, float *wt, float *wu, int H1, int C1, int pad1,
+                             float *dx1, const float *mask1, const float *add1, int H, int C2, float *dx2, const float *mask2, hipStream_t st)
+{
+    WLayer L{w_oihw, K, C1 + C2, true, wt, 0, 0};
+    int rc;
+    if (dx1) {
+        IgemmP d = conv_dgrad_desc(dz, Ho, Ho, K, B, H1, pad1, L.wt, C1, dx1, mask1, add1);
+        if ((rc = with_wino(d, wu, L, 0, 0, st))) return rc;
+        if ((rc = launch_igemm(d, st))) return rc;
+    }
+    if (dx2) {
+        IgemmP d = conv_dgrad_desc(dz, Ho, Ho, K, B, H, 0, adv(L.wt, (size_t)C1 * 9 * K), C2, dx2, mask2, nullptr);
+        if ((rc = with_wino(d, wu + wino_u_floats(K, C1), L, C1, 0, st))) return rc;
+        if ((rc = launch_igemm(d, st))) return rc;
+    }
+    return 0;
+}
+
+// Stream of the weight-gradient launches of a backward stage: the caller's stream, or (overlap on) the handle's auxiliary
+// stream after it has been made to wait for everything enqueued on the caller's stream so far - so a weight gradient must
+// be enqueued BEFORE the dgrad it is to run next to.
+struct WgradStream {
+    unet_handle *h; hipStream_t main; bool overlap; bool used;
+    hipError_t err = hipSuccess;     // sticky: a failed fork / join means the two streams are not ordered - the stage must not report success
+    hipStream_t get()
+    {
+        if (!overlap) return main;
+        // fork failed: the weight gradient stays on the caller's stream (ordered by construction)
+        hipError_t e = hipEventRecord(h->ev_fork, main);
+        if (e == hipSuccess) e = hipStreamWaitEvent(h->aux, h->ev_fork, 0);
+        if (e != hipSuccess) { if (err == hipSuccess) err = e; overlap = false; return main; }
+        used = true;
+        return h->aux;
+    }
+    hipStream_t same() const { return overlap && used ? h->aux : main; }     // right after a get(): the second launch of a pair
+    void join()
+    {
+        if (!used) return;
+        hipError_t e = hipEventRecord(h->ev_join, h->aux);
+        if (e == hipSuccess) e = hipStreamWaitEvent(main, h->ev_join, 0);
+        if (e != hipSuccess) {
+            // last resort: the caller's stream cannot be made to wait, so the host waits for the auxiliary stream
+            (void)hipStreamSynchronize(h->aux);
+            if (err == hipSuccess) err = e;
+        }
+        used = false;
+    }
+};
+
+// What a handle call works on.  All pointers null: the descriptors are built for sizing only (make_plan).
+struct Ctx {
+    unet_handle *h; const Plan &pl; char *base; hipStream_t st;
+    const void *const *params; void *const *grads;
+    WgradStream wst;
+    Ctx(unet_handle *h, const Plan &pl, void *workspace, void *stream, const void *const *params, void *const *grads, bool overlap = false)
+        : h(h), pl(pl), base((char *)workspace), st((hipStream_t)stream), params(params), grads(grads), wst{h, st, overlap, false} {}
+    float *ws(size_t off) const { return base ? (float *)(base + off) : nullptr; }
+    const float *w(int layer) const { return params ? (const float *)params[2 * layer] : nullptr; }
+    const float *b(int layer) const { return params ? (const float *)params[2 * layer + 1] : nullptr; }
+    float *dw(int layer) const { return grads ? (float *)grads[2 * layer] : nullptr; }
+    float *db(int layer) const { return grads ? (float *)grads[2 * layer + 1] : nullptr; }
+};
+
+// Weight-gradient launches of a layer (none for conv11c and the head, whose kernels do their own; two over the virtual
+// concat, the bias gradient riding on the full-window one).  The slab is sized from these same descriptors.
+static int layer_wgrad(const Ctx &cx, int layer, WgradP w[2])
+{
+    const Plan &pl = cx.pl;
+    const Layer &L = LAYERS[layer];
+    if (L.kind == K_CONV1 || L.kind == K_HEAD) return 0;
+    const Act &x = pl.in(L), &y = pl.out(L);
+    const float *dz = cx.ws(y.g);
+    float *dw = cx.dw(layer), *db = cx.db(layer), *slab = cx.ws(pl.slab);
+    if (L.kind == K_UP) w[0] = upconv_wgrad_desc(cx.ws(x.off), x.e, x.c, dz, y.c, pl.B, dw, slab, pl.slab_bytes, db);
+    if (L.kind == K_CONV) w[0] = conv_wgrad_desc(cx.ws(x.off), x.e, x.c, 0, dz, y.e, y.c, pl.B, dw, x.c, 0, slab, pl.slab_bytes, db);
+    if (L.kind != K_CAT) return 1;
+    const Act &u = pl.u[L.level];
+    w[0] = conv_wgrad_desc(cx.ws(x.off), x.e, x.c, pl.pad[L.level], dz, y.e, y.c, pl.B, dw, x.c + u.c, 0, slab, pl.slab_bytes);
+    w[1] = conv_wgrad_desc(cx.ws(u.off), u.e, u.c, 0, dz, y.e, y.c, pl.B, dw, x.c + u.c, x.c, slab, pl.slab_bytes, db);
+    return 2;
+}
+
 static int make_plan(Plan &pl, int base, int B, int S, int training, int math, int ncls = 2)
 {
     int rc = check_size(S);
@@ -327,19 +442,25 @@ static int make_plan(Plan &pl, int base, int B, int S, int training, int math, i
     pl.B = B; pl.S = S; pl.base = base; pl.training = training; pl.math = math; pl.ncls = ncls;
     MathScope ms(math);                      // the slab sizing below builds weight-gradient descriptors
     for (int l = 0; l < 5; ++l) pl.ch[l] = base << l;
-    int cur = S;
+    Act *acts[26];                           // in allocation order
+    int n = 0, cur = S;
     for (int l = 0; l < 5; ++l) {
-        pl.ein[l] = cur; pl.ea1[l] = cur - 2; pl.ea2[l] = cur - 4;
-        if (l < 4) { pl.et[l] = pl.ea2[l] / 2; cur = pl.et[l]; }
+        pl.a1[l].e = cur - 2; pl.a2[l].e = cur - 4;
+        pl.a1[l].c = pl.a2[l].c = pl.ch[l];
+        acts[n++] = &pl.a1[l]; acts[n++] = &pl.a2[l];
+        if (l < 4) cur = pl.a2[l].e / 2;
     }
-    int d = pl.ea2[4];
+    int d = pl.a2[4].e;
     for (int l = 3; l >= 0; --l) {
-        pl.eu[l] = 2 * d; pl.pad[l] = (pl.eu[l] - pl.et[l]) / 2;
+        pl.t[l].e = pl.a2[l].e / 2;
+        pl.u[l].e = 2 * d; pl.pad[l] = (pl.u[l].e - pl.t[l].e) / 2;
         // pad > 0: the skip is zero-padded (every S >= 380); pad < 0: it is cropped (188 <= S < 380).
         // Both are the reference's F.pad(A, (-c,)*4) with c = int((A-B)/2) (network.py:124-126).
-        if ((pl.eu[l] - pl.et[l]) % 2) { set_error("internal: odd skip difference"); return UNET_E_BADSIZE; }
-        pl.ed1[l] = pl.eu[l] - 2; pl.ed2[l] = pl.eu[l] - 4; d = pl.ed2[l];
+        if ((pl.u[l].e - pl.t[l].e) % 2) { set_error("internal: odd skip difference"); return UNET_E_BADSIZE; }
+        pl.d1[l].e = pl.u[l].e - 2; pl.d2[l].e = pl.u[l].e - 4; d = pl.d2[l].e;
+        pl.t[l].c = pl.u[l].c = pl.d1[l].c = pl.d2[l].c = pl.ch[l];
     }
+    for (int l = 0; l < 4; ++l) { acts[n++] = &pl.t[l]; acts[n++] = &pl.u[l]; acts[n++] = &pl.d1[l]; acts[n++] = &pl.d2[l]; }
     pl.So = d;
     if (math == 2 && base % 64 != 0) { set_error("arithmetic mode 2 (bf16 tensors) needs base_ch %% 64 == 0 (got %d)", base); return UNET_E_UNSUPPORTED; }
     // element size of activations, their gradients and the packed filters: bf16 in mode 2, else fp32
@@ -348,45 +469,33 @@ static int make_plan(Plan &pl, int base, int B, int S, int training, int math, i
     auto take_b = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
     auto take = [&](size_t elems) { return take_b(elems * es); };
     auto sq = [&](int e, int c) { return (size_t)B * e * e * c; };
-    for (int l = 0; l < 5; ++l) { pl.a1[l] = take(sq(pl.ea1[l], pl.ch[l])); pl.a2[l] = take(sq(pl.ea2[l], pl.ch[l])); }
-    for (int l = 0; l < 4; ++l) {
-        pl.t[l] = take(sq(pl.et[l], pl.ch[l])); pl.u[l] = take(sq(pl.eu[l], pl.ch[l]));
-        pl.d1[l] = take(sq(pl.ed1[l], pl.ch[l])); pl.d2[l] = take(sq(pl.ed2[l], pl.ch[l]));
-    }
+    for (int i = 0; i < n; ++i) acts[i]->off = take(sq(acts[i]->e, acts[i]->c));
     for (int i = 0; i < UNET_N_LAYERS; ++i) pl.wt_fwd[i] = take(layer_numel(base, i, false, ncls));
     for (int i = 0; i < UNET_N_LAYERS; ++i) pl.wu_fwd[i] = take_b(math == 3 ? layer_wino_floats(base, i) * 4 : 0);
     if (training) {
         pl.xin = take_b((size_t)B * S * S * 4);
         for (int i = 0; i < UNET_N_LAYERS; ++i) pl.wt_bwd[i] = take(layer_numel(base, i, false, ncls));
         for (int i = 0; i < UNET_N_LAYERS; ++i) pl.wu_bwd[i] = take_b(math == 3 ? layer_wino_floats(base, i) * 4 : 0);
-        for (int l = 0; l < 5; ++l) { pl.g_a1[l] = take(sq(pl.ea1[l], pl.ch[l])); pl.g_a2[l] = take(sq(pl.ea2[l], pl.ch[l])); }
-        for (int l = 0; l < 4; ++l) {
-            pl.g_t[l] = take(sq(pl.et[l], pl.ch[l])); pl.g_ts[l] = take(sq(pl.et[l], pl.ch[l]));
-            pl.g_u[l] = take(sq(pl.eu[l], pl.ch[l]));
-            pl.g_d1[l] = take(sq(pl.ed1[l], pl.ch[l])); pl.g_d2[l] = take(sq(pl.ed2[l], pl.ch[l]));
+        for (int i = 0; i < n; ++i) {
+            Act *a = acts[i];
+            a->g = take(sq(a->e, a->c));
+            if (a >= pl.t && a < pl.t + 4) pl.g_ts[a - pl.t] = take(sq(a->e, a->c));
         }
         // split-K slab: the largest need over all weight-gradient launches
         size_t need = 0;
-        auto upd = [&](const WgradP &w) { size_t n = wgrad_slab_need(w); if (n > need) need = n; };
-        {
-            for (int l = 0; l < 5; ++l) {
-                if (l > 0) upd(conv_wgrad_desc(nullptr, pl.ein[l], pl.ch[l - 1], 0, nullptr, pl.ea1[l], pl.ch[l], B, nullptr, pl.ch[l - 1], 0, nullptr, 0));
-                upd(conv_wgrad_desc(nullptr, pl.ea1[l], pl.ch[l], 0, nullptr, pl.ea2[l], pl.ch[l], B, nullptr, pl.ch[l], 0, nullptr, 0));
-            }
-            for (int l = 0; l < 4; ++l) {
-                upd(conv_wgrad_desc(nullptr, pl.et[l], pl.ch[l], pl.pad[l], nullptr, pl.ed1[l], pl.ch[l], B, nullptr, 2 * pl.ch[l], 0, nullptr, 0));
-                upd(conv_wgrad_desc(nullptr, pl.eu[l], pl.ch[l], 0, nullptr, pl.ed1[l], pl.ch[l], B, nullptr, 2 * pl.ch[l], 0, nullptr, 0));
-                upd(conv_wgrad_desc(nullptr, pl.ed1[l], pl.ch[l], 0, nullptr, pl.ed2[l], pl.ch[l], B, nullptr, pl.ch[l], 0, nullptr, 0));
-                upd(upconv_wgrad_desc(nullptr, pl.eu[l] / 2, pl.ch[l + 1], nullptr, pl.ch[l], B, nullptr, nullptr, 0));
-            }
+        const Ctx sizing(nullptr, pl, nullptr, nullptr, nullptr, nullptr);
+        for (int i = 0; i < UNET_N_LAYERS; ++i) {
+            WgradP w[2];
+            const int nw = layer_wgrad(sizing, i, w);
+            for (int j = 0; j < nw; ++j) { const size_t s = wgrad_slab_need(w[j]); if (s > need) need = s; }
         }
         pl.slab_bytes = need;
         pl.slab = take_b(need);
         // small scratch: bias-grad partials, conv11c / head partials
         size_t sm = 0;
-        auto upds = [&](size_t n) { if (n > sm) sm = n; };
-        for (int l = 0; l < 5; ++l) { upds(bias_grad_scratch_bytes(sq(pl.ea1[l], 1), pl.ch[l])); upds(bias_grad_scratch_bytes(sq(pl.ea2[l], 1), pl.ch[l])); }
-        for (int l = 0; l < 4; ++l) { upds(bias_grad_scratch_bytes(sq(pl.eu[l], 1), pl.ch[l])); upds(bias_grad_scratch_bytes(sq(pl.ed1[l], 1), pl.ch[l])); }
+        auto upds = [&](size_t s) { if (s > sm) sm = s; };
+        for (int l = 0; l < 5; ++l) { upds(bias_grad_scratch_bytes(sq(pl.a1[l].e, 1), pl.ch[l])); upds(bias_grad_scratch_bytes(sq(pl.a2[l].e, 1), pl.ch[l])); }
+        for (int l = 0; l < 4; ++l) { upds(bias_grad_scratch_bytes(sq(pl.u[l].e, 1), pl.ch[l])); upds(bias_grad_scratch_bytes(sq(pl.d1[l].e, 1), pl.ch[l])); }
         upds(unet_conv1ch_bwd_scratch_bytes(B, S, base));
         upds(headk_bwd_scratch_bytes(B, pl.So, pl.So, base, ncls));
         pl.small_bytes = sm;
@@ -517,24 +626,49 @@ double unet_flops(const unet_handle *h, int B, int S, int backward)
     if (!h) return 0.0;
     Plan pl;
     if (make_plan(pl, h->base_ch, B, S, 0, handle_math(h), h->n_classes)) return 0.0;
-    double f = 0.0, f11c = 0.0;
-    auto conv = [&](int eo, int ci, int co, int k) { return 2.0 * B * (double)eo * eo * ci * co * k * k; };
-    for (int l = 0; l < 5; ++l) {
-        const int ci = l ? pl.ch[l - 1] : 1;
-        const double a = conv(pl.ea1[l], ci, pl.ch[l], 3);
-        if (l == 0) f11c = a;
-        f += a + conv(pl.ea2[l], pl.ch[l], pl.ch[l], 3);
+    double f = 0.0, f11c = 0.0, first = 0.0;
+    for (int i = 0; i < UNET_N_LAYERS; ++i) {
+        const Layer &L = LAYERS[i];
+        const int k = layer_taps(L);
+        // pixels the filter is applied at: the output's, for the up-conv (and the head) the input's
+        const int eo = L.kind == K_UP || L.kind == K_HEAD ? pl.in(L).e : pl.out(L).e;
+        const double a = 2.0 * B * (double)eo * eo * layer_ci(pl.base, L) * layer_co(pl.base, L, pl.ncls) * k * k;
+        if (L.kind == K_CONV1) f11c = a;
+        // (order of summation: the two convs of a level are added to each other first)
+        if (L.out == T_A1 || L.out == T_D1) first = a;
+        else if (L.out == T_A2 || L.out == T_D2) f += first + a;
+        else f += a;
     }
-    for (int l = 0; l < 4; ++l) {
-        f += 2.0 * B * (double)(pl.eu[l] / 2) * (pl.eu[l] / 2) * pl.ch[l + 1] * pl.ch[l] * 4;   // up-conv
-        f += conv(pl.ed1[l], 2 * pl.ch[l], pl.ch[l], 3) + conv(pl.ed2[l], pl.ch[l], pl.ch[l], 3);
-    }
-    f += conv(pl.So, pl.ch[0], pl.ncls, 1);
     return backward ? 3.0 * f - f11c : f;      // bwd = dgrad + wgrad, conv11c needs no dgrad (A23)
 }
 
-#define WS(off) ((float *)((char *)workspace + (off)))
-#define PARAM(i) ((const float *)params[(i)])
+static int pool_launch(const Ctx &cx, int l, bool bwd)
+{
+    char nm[40]; snprintf(nm, sizeof(nm), "pool%d.%s", l + 1, bwd ? "bwd" : "fwd");
+    ProfScope ps(nm);
+    const Act &a2 = cx.pl.a2[l], &t = cx.pl.t[l];
+    return bwd ? maxpool2_bwd(cx.ws(a2.off), cx.ws(t.g), cx.ws(a2.g), cx.pl.B, a2.e, a2.e, a2.c, t_es, cx.st)
+               : maxpool2_fwd(cx.ws(a2.off), cx.ws(t.off), cx.pl.B, a2.e, a2.e, a2.c, t_es, cx.st);
+}
+
+// Forward of a 3x3 layer of the table: K_CONV, or K_CAT over the virtual concat of the padded skip t[l] and u[l].  The
+// second conv of an encoder level is followed by the pool, fused into its launch where the Winograd epilogue can.
+static int conv_forward(const Ctx &cx, int layer)
+{
+    const Plan &pl = cx.pl;
+    const Layer &L = LAYERS[layer];
+    const bool cat = L.kind == K_CAT, pools = L.out == T_A2 && L.level < 4;
+    const Act &x1 = pl.in(L), &y = pl.out(L), *x2 = cat ? &pl.u[L.level] : nullptr;
+    bool pool_fused = false;
+    {
+        RowScope rs(layer, "fwd");
+        int rc = conv_fwd_launch(cx.ws(x1.off), x1.e, x1.c, cat ? pl.pad[L.level] : 0, cat ? cx.ws(x2->off) : nullptr, cat ? x2->c : 0, pl.B, y.e + 2,
+                                 cx.w(layer), cx.ws(pl.wt_fwd[layer]), cx.b(layer), y.c, 1, cx.ws(y.off), cx.st, cx.ws(pl.wu_fwd[layer]),
+                                 pools ? cx.ws(pl.t[L.level].off) : nullptr, &pool_fused);
+        if (rc) return rc;
+    }
+    return pools && !pool_fused ? pool_launch(cx, L.level, false) : 0;
+}
 
 int unet_forward(unet_handle *h, const void *const *params, const void *x, void *logits, int B, int S,
                  void *workspace, size_t workspace_bytes, int training, void *stream)
@@ -547,83 +681,46 @@ int unet_forward(unet_handle *h, const void *const *params, const void *x, void 
     MathScope ms(pl.math);
     ARG_CHECK(workspace_bytes >= pl.total, "unet_forward: workspace too small (%zu < %zu)", workspace_bytes, pl.total);
     ARG_CHECK(((uintptr_t)workspace & 255) == 0, "unet_forward: workspace must be 256-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    const int *ch = pl.ch;
+    const Ctx cx(h, pl, workspace, stream, params, nullptr);
+    hipStream_t st = cx.st;
 
-    // repack the parameters (reference layout, owned by the caller and updated by its optimizer)
+    // repack the parameters (reference layout, owned by the caller and updated by its optimizer): the up-convs', level 0 first
     // (the 3x3 layers' weights are packed lazily, only if a launch of the layer takes the implicit-GEMM path: with_wino)
-    for (int l = 0; l < 4; ++l) {
-        RowScope rs(UP_L[l], "fwd");
-        if ((rc = pack_upconv_fwd(PARAM(2 * UP_L[l]), WS(pl.wt_fwd[UP_L[l]]), ch[l + 1], ch[l], t_es, st))) return rc;
+    for (int i = UNET_N_LAYERS - 1; i >= 0; --i) {
+        if (LAYERS[i].kind != K_UP) continue;
+        RowScope rs(i, "fwd");
+        if ((rc = pack_upconv_fwd(cx.w(i), cx.ws(pl.wt_fwd[i]), pl.ch[LAYERS[i].ci], pl.ch[LAYERS[i].co], t_es, st))) return rc;
     }
 
-    // encoder (network.py:131-156); the input is kept for conv11c's weight gradient
-    {
-        RowScope rs(C11C, "fwd");
-        if (training) HIP_TRY(hipMemcpyAsync(WS(pl.xin), x, (size_t)B * S * S * sizeof(float), hipMemcpyDeviceToDevice, st));
-        if ((rc = conv1ch_fwd((const float *)x, B, S, PARAM(0), PARAM(1), ch[0], WS(pl.a1[0]), t_es, st))) return rc;
-    }
-    for (int l = 0; l < 5; ++l) {
-        if (l > 0) {
-            RowScope rs(2 * l, "fwd");
-            IgemmP p = conv_fwd_desc(WS(pl.t[l - 1]), pl.ein[l], pl.ein[l], ch[l - 1], 0, nullptr, 0, B, pl.ein[l], pl.ein[l],
-                                     WS(pl.wt_fwd[2 * l]), PARAM(2 * (2 * l) + 1), ch[l], 1, WS(pl.a1[l]));
-            WLayer L = wl_fwd(PARAM(2 * (2 * l)), ch[l], ch[l - 1], 0, WS(pl.wt_fwd[2 * l]));
-            if ((rc = with_wino(p, WS(pl.wu_fwd[2 * l]), L, 0, 0, st))) return rc;
+    // the layers in order: encoder (network.py:131-156), decoder (network.py:159-188: up-conv, virtual zero-pad-concat, two
+    // convs), head
+    for (int i = 0; i < UNET_N_LAYERS; ++i) {
+        const Layer &L = LAYERS[i];
+        switch (L.kind) {
+        case K_CONV1: {                      // the input is kept for conv11c's weight gradient
+            RowScope rs(i, "fwd");
+            if (training) HIP_TRY(hipMemcpyAsync(cx.ws(pl.xin), x, (size_t)B * S * S * sizeof(float), hipMemcpyDeviceToDevice, st));
+            if ((rc = conv1ch_fwd((const float *)x, B, S, cx.w(i), cx.b(i), pl.ch[0], cx.ws(pl.a1[0].off), t_es, st))) return rc;
+            break;
+        }
+        case K_CONV:
+        case K_CAT:
+            if ((rc = conv_forward(cx, i))) return rc;
+            break;
+        case K_UP: {
+            RowScope rs(i, "fwd");
+            const Act &in = pl.in(L), &u = pl.u[L.level];
+            IgemmP p = upconv_fwd_desc(cx.ws(in.off), B, in.e, in.e, in.c, cx.ws(pl.wt_fwd[i]), cx.b(i), u.c, cx.ws(u.off));
             if ((rc = launch_igemm(p, st))) return rc;
+            break;
         }
-        bool pool_fused = false;
-        {
-            RowScope rs(2 * l + 1, "fwd");
-            IgemmP p = conv_fwd_desc(WS(pl.a1[l]), pl.ea1[l], pl.ea1[l], ch[l], 0, nullptr, 0, B, pl.ea1[l], pl.ea1[l],
-                                     WS(pl.wt_fwd[2 * l + 1]), PARAM(2 * (2 * l + 1) + 1), ch[l], 1, WS(pl.a2[l]));
-            WLayer L2 = wl_fwd(PARAM(2 * (2 * l + 1)), ch[l], ch[l], 0, WS(pl.wt_fwd[2 * l + 1]));
-            if ((rc = with_wino(p, WS(pl.wu_fwd[2 * l + 1]), L2, 0, 0, st))) return rc;
-            pool_fused = l < 4 && p.wino_u && wino_fuses_pool(p);       // the Winograd epilogue writes t[l] too
-            if (pool_fused) p.pool_dst = WS(pl.t[l]);
-            if ((rc = launch_igemm(p, st))) return rc;
+        case K_HEAD: {
+            RowScope rs(i, "fwd");
+            const Act &in = pl.in(L);
+            if ((rc = headk_fwd(cx.ws(in.off), B, in.e, in.e, in.c, pl.ncls, cx.w(i), cx.b(i), (float *)logits, t_es, st))) return rc;
+            break;
         }
-        if (l < 4 && !pool_fused) {
-            char nm[40]; snprintf(nm, sizeof(nm), "pool%d.fwd", l + 1);
-            ProfScope ps(nm);
-            if ((rc = maxpool2_fwd(WS(pl.a2[l]), WS(pl.t[l]), B, pl.ea2[l], pl.ea2[l], ch[l], t_es, st))) return rc;
         }
-    }
-    // decoder (network.py:159-188): up-conv, virtual zero-pad-concat, two convs
-    const float *dsrc = WS(pl.a2[4]);
-    for (int l = 3; l >= 0; --l) {
-        const int hin = pl.eu[l] / 2;
-        {
-            RowScope rs(UP_L[l], "fwd");
-            IgemmP u{};
-            u.nsrc = 1; u.src[0] = GSrc{dsrc, hin, hin, ch[l + 1], 0, ch[l + 1], 0};
-            u.wt = WS(pl.wt_fwd[UP_L[l]]); u.Kd = ch[l + 1];
-            u.T = 1; u.TX = 1; u.stride = 1;
-            u.NB = B; u.OH = hin; u.OW = hin; u.M = B * hin * hin; u.Nn = 4 * ch[l];
-            u.dst = WS(pl.u[l]); u.DH = pl.eu[l]; u.DW = pl.eu[l]; u.DC = ch[l]; u.scatter = 1; u.cout = ch[l];
-            u.bias = PARAM(2 * UP_L[l] + 1);
-            u.math = pl.math;
-            if ((rc = launch_igemm(u, st))) return rc;
-        }
-        {
-            RowScope rs(C1E_L[l], "fwd");
-            WLayer L1 = wl_fwd(PARAM(2 * C1E_L[l]), ch[l], ch[l], ch[l], WS(pl.wt_fwd[C1E_L[l]]));
-            if ((rc = conv_fwd_launch(WS(pl.t[l]), pl.et[l], ch[l], pl.pad[l], WS(pl.u[l]), ch[l], B, pl.eu[l],
-                                      L1, PARAM(2 * C1E_L[l] + 1), ch[l], 1, WS(pl.d1[l]), st, WS(pl.wu_fwd[C1E_L[l]])))) return rc;
-        }
-        {
-            RowScope rs(C2E_L[l], "fwd");
-            IgemmP c2 = conv_fwd_desc(WS(pl.d1[l]), pl.ed1[l], pl.ed1[l], ch[l], 0, nullptr, 0, B, pl.ed1[l], pl.ed1[l],
-                                      WS(pl.wt_fwd[C2E_L[l]]), PARAM(2 * C2E_L[l] + 1), ch[l], 1, WS(pl.d2[l]));
-            WLayer L2e = wl_fwd(PARAM(2 * C2E_L[l]), ch[l], ch[l], 0, WS(pl.wt_fwd[C2E_L[l]]));
-            if ((rc = with_wino(c2, WS(pl.wu_fwd[C2E_L[l]]), L2e, 0, 0, st))) return rc;
-            if ((rc = launch_igemm(c2, st))) return rc;
-        }
-        dsrc = WS(pl.d2[l]);
-    }
-    {
-        RowScope rs(FINAL, "fwd");
-        if ((rc = headk_fwd(WS(pl.d2[0]), B, pl.So, pl.So, ch[0], pl.ncls, PARAM(2 * FINAL), PARAM(2 * FINAL + 1), (float *)logits, t_es, st))) return rc;
     }
     if (training) h->remember(workspace, pl);
     return 0;
@@ -646,122 +743,118 @@ int unet_debug_buffer(const unet_handle *h, int B, int S, int training, const ch
     int rc = make_plan(pl, h->base_ch, B, S, training, handle_math(h), h->n_classes);
     if (rc) return rc;
     char kind[16];
-    int l = 0;
     const char *us = strrchr(name, '_');
     if (!strcmp(name, "xin")) { ARG_CHECK(training, "xin exists only with training=1"); *offset = pl.xin; *extent = S; *channels = 1; return 0; }
     ARG_CHECK(us && (size_t)(us - name) < sizeof(kind), "unet_debug_buffer: bad name %s", name);
     memcpy(kind, name, us - name); kind[us - name] = 0;
-    l = atoi(us + 1);
+    const int l = atoi(us + 1);
     ARG_CHECK(l >= 0 && l < 5, "unet_debug_buffer: bad level in %s", name);
     const bool g = !strncmp(kind, "g_", 2);
     ARG_CHECK(!g || training, "gradient buffers exist only with training=1");
     const char *k = g ? kind + 2 : kind;
-    *channels = pl.ch[l];
-    if (!strcmp(k, "a1")) { *offset = g ? pl.g_a1[l] : pl.a1[l]; *extent = pl.ea1[l]; return 0; }
-    if (!strcmp(k, "a2")) { *offset = g ? pl.g_a2[l] : pl.a2[l]; *extent = pl.ea2[l]; return 0; }
-    ARG_CHECK(l < 4, "unet_debug_buffer: bad level in %s", name);
-    if (!strcmp(k, "t")) { *offset = g ? pl.g_t[l] : pl.t[l]; *extent = pl.et[l]; return 0; }
-    if (!strcmp(k, "ts") && g) { *offset = pl.g_ts[l]; *extent = pl.et[l]; return 0; }
-    if (!strcmp(k, "u")) { *offset = g ? pl.g_u[l] : pl.u[l]; *extent = pl.eu[l]; return 0; }
-    if (!strcmp(k, "d1")) { *offset = g ? pl.g_d1[l] : pl.d1[l]; *extent = pl.ed1[l]; return 0; }
-    if (!strcmp(k, "d2")) { *offset = g ? pl.g_d2[l] : pl.d2[l]; *extent = pl.ed2[l]; return 0; }
-    set_error("unet_debug_buffer: unknown buffer %s", name);
-    return UNET_E_BADARG;
+    const bool ts = g && !strcmp(k, "ts");                  // the one buffer that is no tensor's gradient: t's extent
+    int id = ts ? T_T : 0;
+    while (!ts && id < N_TENSORS && strcmp(k, TENSOR_NAME[id].name)) ++id;
+    ARG_CHECK(l < (id < N_TENSORS ? TENSOR_NAME[id].levels : 4), "unet_debug_buffer: bad level in %s", name);
+    if (id == N_TENSORS) { set_error("unet_debug_buffer: unknown buffer %s", name); return UNET_E_BADARG; }
+    const Act &a = pl.act(id, l);
+    *offset = ts ? pl.g_ts[l] : g ? a.g : a.off; *extent = a.e; *channels = a.c;
+    return 0;
 }
 
 // ---- backward ------------------------------------------------------------------------------------
-// Stage order = reverse layer order, so gradient buckets complete early for the all-reduce:
-//   0: finalconv, conv12e, conv11e, upconv1      1: conv22e, conv21e, upconv2
-//   2: conv32e, conv31e, upconv3                 3: conv42e, conv41e, upconv4
-//   4: conv52c, conv51c                          5: conv42c ... conv11c
-static const int N_STAGES = 6;
+// (stages: the table's column; a stage's layers run last first)
 int unet_backward_stages(void) { return N_STAGES; }
 
 int unet_backward_stage_params(int stage, int *idx, int cap)
 {
-    int layers[12], n = 0;
-    if (stage >= 0 && stage < 4) {
-        const int l = stage;
-        if (l == 0) layers[n++] = FINAL;
-        layers[n++] = C2E_L[l]; layers[n++] = C1E_L[l]; layers[n++] = UP_L[l];
-    } else if (stage == 4) {
-        layers[n++] = C52C; layers[n++] = C51C;
-    } else if (stage == 5) {
-        for (int l = C42C; l >= C11C; --l) layers[n++] = l;
-    }
     int k = 0;
-    for (int i = 0; i < n; ++i)
-        for (int b = 0; b < 2; ++b)
-            if (k < cap && idx) idx[k++] = 2 * layers[i] + b; else if (!idx || k >= cap) ++k;
-    return 2 * n;
+    for (int i = UNET_N_LAYERS - 1; i >= 0; --i)
+        for (int b = 0; b < 2 && LAYERS[i].stage == stage; ++b, ++k)
+            if (idx && k < cap) idx[k] = 2 * i + b;
+    return k;
 }
 
-#define GRAD(i) ((float *)grads[(i)])
-
-// Stream of the weight-gradient launches of the backward stage this thread is in: the caller's stream, or (overlap on) the
-// handle's auxiliary stream after it has been made to wait for everything enqueued on the caller's stream so far - so a
-// weight gradient must be enqueued BEFORE the dgrad it is to run next to.
-struct WgradStream {
-    unet_handle *h; hipStream_t main; bool overlap; bool used;
-    hipError_t err = hipSuccess;     // sticky: a failed fork / join means the two streams are not ordered - the stage must not report success
-    hipStream_t get()
-    {
-        if (!overlap) return main;
-        // fork failed: the weight gradient stays on the caller's stream (ordered by construction)
-        hipError_t e = hipEventRecord(h->ev_fork, main);
-        if (e == hipSuccess) e = hipStreamWaitEvent(h->aux, h->ev_fork, 0);
-        if (e != hipSuccess) { if (err == hipSuccess) err = e; overlap = false; return main; }
-        used = true;
-        return h->aux;
-    }
-    void join()
-    {
-        if (!used) return;
-        hipError_t e = hipEventRecord(h->ev_join, h->aux);
-        if (e == hipSuccess) e = hipStreamWaitEvent(main, h->ev_join, 0);
-        if (e != hipSuccess) {
-            // last resort: the caller's stream cannot be made to wait, so the host waits for the auxiliary stream
-            (void)hipStreamSynchronize(h->aux);
-            if (err == hipSuccess) err = e;
-        }
-        used = false;
-    }
-};
-static thread_local WgradStream *t_wst = nullptr;
-static inline hipStream_t wgrad_stream(hipStream_t st) { return t_wst ? t_wst->get() : st; }
-static inline hipStream_t wst_same(hipStream_t st) { return (t_wst && t_wst->overlap && t_wst->used) ? t_wst->h->aux : st; }   // right after a wgrad_stream() call
-
-static int conv_backward(const Plan &pl, void *workspace, hipStream_t st, const void *const *params, void *const *grads,
-                         int layer, const float *X, int XH, int C, const float *dz, int Ho, int K,
-                         float *dx, const float *mask, const float *add)
+// weight gradient (+ bias gradient) of a layer, next to the dgrad chain when the stage overlaps
+static int wgrad_backward(Ctx &cx, int layer)
 {
-    // single-source 3x3 conv: wgrad + bias grad, dgrad (optional)
-    const int B = pl.B;
-    int rc;
-    {
-        RowScope rs(layer, "wgrad");
-        WgradP w = conv_wgrad_desc(X, XH, C, 0, dz, Ho, K, B, GRAD(2 * layer), C, 0, WS(pl.slab), pl.slab_bytes, GRAD(2 * layer + 1));
-        if ((rc = launch_wgrad(w, wgrad_stream(st)))) return rc;
-    }
-    if (dx) {
-        RowScope rs(layer, "dgrad");
-        WLayer L = wl_dgrad(PARAM(2 * layer), K, C, WS(pl.wt_bwd[layer]));
-        IgemmP d = conv_dgrad_desc(dz, Ho, Ho, K, B, XH, 0, WS(pl.wt_bwd[layer]), C, dx, mask, add);
-        if ((rc = with_wino(d, WS(pl.wu_bwd[layer]), L, 0, 0, st))) return rc;
-        if ((rc = launch_igemm(d, st))) return rc;
+    RowScope rs(layer, "wgrad");
+    WgradP w[2];
+    const int n = layer_wgrad(cx, layer, w);
+    for (int j = 0; j < n; ++j) {
+        int rc = launch_wgrad(w[j], j ? cx.wst.same() : cx.wst.get());
+        if (rc) return rc;
     }
     return 0;
 }
 
-static int pool_backward(const Plan &pl, void *workspace, int l, void *stream)
+// Single-source 3x3 conv: wgrad + bias grad, dgrad.  Its input is a ReLU output, which masks the dgrad - or the pool's t[l]:
+// then the skip's gradient g_ts[l] is added instead and the pool's backward follows.
+static int conv_backward(Ctx &cx, int layer)
 {
-    char nm[40]; snprintf(nm, sizeof(nm), "pool%d.bwd", l + 1);
-    ProfScope ps(nm);
-    return maxpool2_bwd(WS(pl.a2[l]), WS(pl.g_t[l]), WS(pl.g_a2[l]), pl.B, pl.ea2[l], pl.ea2[l], pl.ch[l], t_es, (hipStream_t)stream);
+    const Plan &pl = cx.pl;
+    const Layer &L = LAYERS[layer];
+    const Act &x = pl.in(L), &y = pl.out(L);
+    const bool pooled = L.in == T_T;
+    int rc;
+    if ((rc = wgrad_backward(cx, layer))) return rc;
+    {
+        RowScope rs(layer, "dgrad");
+        if ((rc = conv_dgrad_launch(cx.ws(y.g), y.e, y.c, pl.B, cx.w(layer), cx.ws(pl.wt_bwd[layer]), cx.ws(pl.wu_bwd[layer]), x.e, x.c, 0, cx.ws(x.g),
+                                    pooled ? nullptr : cx.ws(x.off), pooled ? cx.ws(pl.g_ts[L.ci]) : nullptr, 0, 0, nullptr, nullptr, cx.st))) return rc;
+    }
+    return pooled ? pool_launch(cx, L.ci, true) : 0;
 }
 
-static int backward_stage_body(unet_handle *h, const Plan &pl, int stage, const void *const *params, const void *dlogits, void *const *grads,
-                               void *workspace, void *stream);
+// the layers of a stage, last first
+static int backward_stage_body(Ctx &cx, int stage, const void *dlogits)
+{
+    const Plan &pl = cx.pl;
+    hipStream_t st = cx.st;
+    const int B = pl.B;
+    int rc;
+    for (int i = UNET_N_LAYERS - 1; i >= 0; --i) {
+        const Layer &L = LAYERS[i];
+        if (L.stage != stage) continue;
+        switch (L.kind) {
+        case K_HEAD: {                       // fused with the ReLU backward of conv12e -> dz of conv12e
+            ARG_CHECK(dlogits, "unet_backward: null dlogits");
+            RowScope rs(i, "bwd");
+            const Act &x = pl.in(L);
+            if ((rc = headk_bwd(cx.ws(x.off), B, x.e, x.e, x.c, pl.ncls, cx.w(i), (const float *)dlogits, cx.h->grad_scale, cx.ws(x.g),
+                                cx.dw(i), cx.db(i), cx.ws(pl.small), t_es, st))) return rc;
+            break;
+        }
+        case K_CONV:
+            if ((rc = conv_backward(cx, i))) return rc;
+            break;
+        case K_CAT: {                        // virtual concat input: dgrad per source half (skip half only over the crop window)
+            const int l = L.level;
+            const Act &t = pl.t[l], &u = pl.u[l], &y = pl.d1[l];
+            if ((rc = wgrad_backward(cx, i))) return rc;
+            RowScope rs(i, "dgrad");
+            if ((rc = conv_dgrad_launch(cx.ws(y.g), y.e, y.c, B, cx.w(i), cx.ws(pl.wt_bwd[i]), cx.ws(pl.wu_bwd[i]), t.e, t.c, pl.pad[l], cx.ws(pl.g_ts[l]), nullptr, nullptr,
+                                        u.e, u.c, cx.ws(u.g), nullptr, st))) return rc;
+            break;
+        }
+        case K_UP: {                         // its input is a ReLU output (d2[l+1] or a2[4]), which masks its dgrad
+            const Act &x = pl.in(L), &u = pl.u[L.level];
+            if ((rc = wgrad_backward(cx, i))) return rc;
+            RowScope rs(i, "dgrad");
+            if ((rc = pack_upconv_dgrad(cx.w(i), cx.ws(pl.wt_bwd[i]), x.c, u.c, t_es, st))) return rc;
+            IgemmP d = upconv_dgrad_desc(cx.ws(u.g), B, x.e, x.e, x.c, cx.ws(pl.wt_bwd[i]), u.c, cx.ws(x.g), cx.ws(x.off));
+            if ((rc = launch_igemm(d, st))) return rc;
+            break;
+        }
+        case K_CONV1: {                      // weight/bias gradient only (A1 needs no dgrad)
+            RowScope rs(i, "wgrad");
+            if ((rc = conv1ch_bwd(cx.ws(pl.xin), B, pl.S, pl.ch[0], cx.ws(pl.a1[0].g), cx.dw(i), cx.db(i), cx.ws(pl.small), t_es, st))) return rc;
+            break;
+        }
+        }
+    }
+    return 0;
+}
 
 int unet_backward_stage(unet_handle *h, int stage, const void *const *params, const void *dlogits, void *const *grads,
                         void *workspace, size_t workspace_bytes, void *stream)
@@ -785,111 +878,14 @@ int unet_backward_stage(unet_handle *h, int stage, const void *const *params, co
         HIP_TRY(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
         HIP_TRY(hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
     }
-    WgradStream wst{h, (hipStream_t)stream, overlap, false};
-    t_wst = &wst;
-    int rc = backward_stage_body(h, pl, stage, params, dlogits, grads, workspace, stream);
-    wst.join();                              // every path re-joins the streams before the caller sees the stage as enqueued
-    t_wst = nullptr;
-    if (rc == 0 && wst.err != hipSuccess) {
-        set_error("unet_backward: ordering the weight-gradient stream against the caller's failed: %s", hipGetErrorString(wst.err));
-        rc = (int)wst.err;
+    Ctx cx(h, pl, workspace, stream, params, grads, overlap);
+    int rc = backward_stage_body(cx, stage, dlogits);
+    cx.wst.join();                           // every path re-joins the streams before the caller sees the stage as enqueued
+    if (rc == 0 && cx.wst.err != hipSuccess) {
+        set_error("unet_backward: ordering the weight-gradient stream against the caller's failed: %s", hipGetErrorString(cx.wst.err));
+        rc = (int)cx.wst.err;
     }
     return rc;
-}
-
-static int backward_stage_body(unet_handle *h, const Plan &pl, int stage, const void *const *params, const void *dlogits, void *const *grads,
-                               void *workspace, void *stream)
-{
-    hipStream_t st = (hipStream_t)stream;
-    const int B = pl.B;
-    const int *ch = pl.ch;
-    int rc;
-
-    if (stage < 4) {
-        const int l = stage;
-        if (l == 0) {
-            ARG_CHECK(dlogits, "unet_backward: null dlogits");
-            // finalconv backward, fused with the ReLU backward of conv12e -> dz of conv12e
-            RowScope rs(FINAL, "bwd");
-            if ((rc = headk_bwd(WS(pl.d2[0]), B, pl.So, pl.So, ch[0], pl.ncls, PARAM(2 * FINAL), (const float *)dlogits, h->grad_scale, WS(pl.g_d2[0]),
-                                  GRAD(2 * FINAL), GRAD(2 * FINAL + 1), WS(pl.small), t_es, st))) return rc;
-        }
-        // conv_l2e: input d1[l] (ReLU output of conv_l1e)
-        if ((rc = conv_backward(pl, workspace, st, params, grads, C2E_L[l], WS(pl.d1[l]), pl.ed1[l], ch[l], WS(pl.g_d2[l]), pl.ed2[l], ch[l],
-                                WS(pl.g_d1[l]), WS(pl.d1[l]), nullptr))) return rc;
-        // conv_l1e: virtual concat input.  dgrad per source half (skip half only over the crop window)
-        const int lay = C1E_L[l];
-        {
-            RowScope rs(lay, "wgrad");
-            WgradP ws_ = conv_wgrad_desc(WS(pl.t[l]), pl.et[l], ch[l], pl.pad[l], WS(pl.g_d1[l]), pl.ed1[l], ch[l], B,
-                                         GRAD(2 * lay), 2 * ch[l], 0, WS(pl.slab), pl.slab_bytes);
-            if ((rc = launch_wgrad(ws_, wgrad_stream(st)))) return rc;
-            WgradP wu = conv_wgrad_desc(WS(pl.u[l]), pl.eu[l], ch[l], 0, WS(pl.g_d1[l]), pl.ed1[l], ch[l], B,
-                                        GRAD(2 * lay), 2 * ch[l], ch[l], WS(pl.slab), pl.slab_bytes, GRAD(2 * lay + 1));
-            if ((rc = launch_wgrad(wu, wst_same(st)))) return rc;
-        }
-        WLayer Ld = wl_dgrad(PARAM(2 * lay), ch[l], 2 * ch[l], WS(pl.wt_bwd[lay]));
-        {
-            RowScope rs(lay, "dgrad");
-            IgemmP ds = conv_dgrad_desc(WS(pl.g_d1[l]), pl.ed1[l], pl.ed1[l], ch[l], B, pl.et[l], pl.pad[l],
-                                        WS(pl.wt_bwd[lay]), ch[l], WS(pl.g_ts[l]), nullptr, nullptr);
-            if ((rc = with_wino(ds, WS(pl.wu_bwd[lay]), Ld, 0, 0, st))) return rc;
-            if ((rc = launch_igemm(ds, st))) return rc;
-            IgemmP du = conv_dgrad_desc(WS(pl.g_d1[l]), pl.ed1[l], pl.ed1[l], ch[l], B, pl.eu[l], 0,
-                                        adv(WS(pl.wt_bwd[lay]), (size_t)ch[l] * 9 * ch[l]), ch[l], WS(pl.g_u[l]), nullptr, nullptr);
-            if ((rc = with_wino(du, WS(pl.wu_bwd[lay]) + wino_u_floats(ch[l], ch[l]), Ld, ch[l], 0, st))) return rc;
-            if ((rc = launch_igemm(du, st))) return rc;
-        }
-        // upconv_l: input is d2[l+1] (or a2[4]); its dgrad is masked by that ReLU output
-        {
-            const int ul = UP_L[l];
-            const int hin = pl.eu[l] / 2;
-            const float *uin = l == 3 ? WS(pl.a2[4]) : WS(pl.d2[l + 1]);
-            float *dzin = l == 3 ? WS(pl.g_a2[4]) : WS(pl.g_d2[l + 1]);
-            {
-                RowScope rs(ul, "wgrad");
-                WgradP w = upconv_wgrad_desc(uin, hin, ch[l + 1], WS(pl.g_u[l]), ch[l], B, GRAD(2 * ul), WS(pl.slab), pl.slab_bytes, GRAD(2 * ul + 1));
-                if ((rc = launch_wgrad(w, wgrad_stream(st)))) return rc;
-            }
-            {
-                RowScope rs(ul, "dgrad");
-                if ((rc = pack_upconv_dgrad(PARAM(2 * ul), WS(pl.wt_bwd[ul]), ch[l + 1], ch[l], t_es, st))) return rc;
-                IgemmP d{};
-                d.nsrc = 1; d.src[0] = GSrc{WS(pl.g_u[l]), pl.eu[l], pl.eu[l], ch[l], 0, ch[l], 0};
-                d.wt = WS(pl.wt_bwd[ul]); d.Kd = 4 * ch[l];
-                d.T = 4; d.TX = 2; d.stride = 2;
-                d.NB = B; d.OH = hin; d.OW = hin; d.M = B * hin * hin; d.Nn = ch[l + 1];
-                d.dst = dzin; d.DH = hin; d.DW = hin; d.DC = ch[l + 1];
-                d.mask = uin;
-                d.math = pl.math;
-                if ((rc = launch_igemm(d, st))) return rc;
-            }
-        }
-        return 0;
-    }
-
-    if (stage == 4) {
-        if ((rc = conv_backward(pl, workspace, st, params, grads, C52C, WS(pl.a1[4]), pl.ea1[4], ch[4], WS(pl.g_a2[4]), pl.ea2[4], ch[4],
-                                WS(pl.g_a1[4]), WS(pl.a1[4]), nullptr))) return rc;
-        if ((rc = conv_backward(pl, workspace, st, params, grads, C51C, WS(pl.t[3]), pl.ein[4], ch[3], WS(pl.g_a1[4]), pl.ea1[4], ch[4],
-                                WS(pl.g_t[3]), nullptr, WS(pl.g_ts[3])))) return rc;
-        return pool_backward(pl, workspace, 3, stream);
-    }
-
-    // stage 5: encoder levels 3..0
-    for (int l = 3; l >= 0; --l) {
-        if ((rc = conv_backward(pl, workspace, st, params, grads, 2 * l + 1, WS(pl.a1[l]), pl.ea1[l], ch[l], WS(pl.g_a2[l]), pl.ea2[l], ch[l],
-                                WS(pl.g_a1[l]), WS(pl.a1[l]), nullptr))) return rc;
-        if (l == 0) {
-            // conv11c: weight/bias gradient only (A1 needs no dgrad)
-            RowScope rs(C11C, "wgrad");
-            return conv1ch_bwd(WS(pl.xin), B, pl.S, ch[0], WS(pl.g_a1[0]), GRAD(0), GRAD(1), WS(pl.small), t_es, st);
-        }
-        if ((rc = conv_backward(pl, workspace, st, params, grads, 2 * l, WS(pl.t[l - 1]), pl.ein[l], ch[l - 1], WS(pl.g_a1[l]), pl.ea1[l], ch[l],
-                                WS(pl.g_t[l - 1]), nullptr, WS(pl.g_ts[l - 1])))) return rc;
-        if ((rc = pool_backward(pl, workspace, l - 1, stream))) return rc;
-    }
-    return 0;
 }
 
 int unet_backward_input(unet_handle *h, const void *const *params, void *dx, void *workspace, size_t workspace_bytes, void *stream)
@@ -903,9 +899,10 @@ int unet_backward_input(unet_handle *h, const void *const *params, void *dx, voi
     }
     ARG_CHECK(workspace_bytes >= pl.total, "unet_backward_input: workspace too small");
     MathScope ms(pl.math);
+    const Ctx cx(h, pl, workspace, stream, params, nullptr);
     RowScope rs(C11C, "dgrad");
     // g_a1[0] = d loss / d conv11c's output, masked by its ReLU: final once the last backward stage has been enqueued
-    return conv1ch_dgrad(WS(pl.g_a1[0]), pl.B, pl.S, pl.ch[0], PARAM(0), (float *)dx, t_es, (hipStream_t)stream);
+    return conv1ch_dgrad(cx.ws(pl.a1[0].g), pl.B, pl.S, pl.ch[0], cx.w(C11C), (float *)dx, t_es, cx.st);
 }
 
 int unet_backward(unet_handle *h, const void *const *params, const void *dlogits, void *const *grads,
@@ -965,9 +962,8 @@ int unet_conv3x3_fwd(const void *x1, int H1, int W1, int C1, int pad1, const voi
     ARG_CHECK(x2 || (H1 + 2 * pad1 == H && W1 + 2 * pad1 == W), "conv3x3_fwd: single source must match the input extent");
     hipStream_t st = (hipStream_t)stream;
     ARG_CHECK(H == W && H1 == W1, "conv3x3_fwd: square tiles only");
-    WLayer L = wl_fwd((const float *)w_oihw, K, C1, x2 ? C2 : 0, (float *)scratch);
     float *wu = (float *)((char *)scratch + align_up((size_t)K * (C1 + (x2 ? C2 : 0)) * 9 * sizeof(float), 256));
-    return conv_fwd_launch((const float *)x1, H1, C1, pad1, (const float *)x2, x2 ? C2 : 0, B, H, L,
+    return conv_fwd_launch((const float *)x1, H1, C1, pad1, (const float *)x2, C2, B, H, (const float *)w_oihw, (float *)scratch,
                            (const float *)bias, K, relu, (float *)y, st, wu);
 }
 
@@ -995,19 +991,8 @@ int unet_conv3x3_bwd(const void *x1, int H1, int W1, int C1, int pad1, const voi
     float *small = (float *)((char *)scratch + wt_bytes + slab_bytes);
     float *wu = (float *)((char *)scratch + wt_bytes + slab_bytes + align_up(bias_grad_scratch_bytes((size_t)B * Ho * Ho, K), 256));
     int rc;
-    if (dx1 || dx2) {
-        WLayer L = wl_dgrad((const float *)w_oihw, K, C, wt);
-        if (dx1) {
-            IgemmP d = conv_dgrad_desc((const float *)dz, Ho, Ho, K, B, H1, pad1, wt, C1, (float *)dx1, (const float *)mask1, (const float *)add1);
-            if ((rc = with_wino(d, wu, L, 0, 0, st))) return rc;
-            if ((rc = launch_igemm(d, st))) return rc;
-        }
-        if (dx2 && x2) {
-            IgemmP d = conv_dgrad_desc((const float *)dz, Ho, Ho, K, B, H, 0, adv(wt, (size_t)C1 * 9 * K), C2, (float *)dx2, (const float *)mask2, nullptr);
-            if ((rc = with_wino(d, wu + wino_u_floats(K, C1), L, C1, 0, st))) return rc;
-            if ((rc = launch_igemm(d, st))) return rc;
-        }
-    }
+    if ((rc = conv_dgrad_launch((const float *)dz, Ho, K, B, (const float *)w_oihw, wt, wu, H1, C1, pad1, (float *)dx1, (const float *)mask1,
+                                (const float *)add1, H, C - C1, x2 ? (float *)dx2 : nullptr, (const float *)mask2, st))) return rc;
     bool db_done = false;
     if (dw) {
         // the bias gradient rides on whichever weight-gradient launch covers the full dz window
@@ -1042,15 +1027,7 @@ int unet_upconv2_fwd(const void *x, int B, int H, int W, int Ci, const void *w_i
     hipStream_t st = (hipStream_t)stream;
     int rc = pack_upconv_fwd((const float *)w_iohw, scratch, Ci, Co, t_es, st);
     if (rc) return rc;
-    IgemmP u{};
-    u.nsrc = 1; u.src[0] = GSrc{(const float *)x, H, W, Ci, 0, Ci, 0};
-    u.wt = (const float *)scratch; u.Kd = Ci;
-    u.T = 1; u.TX = 1; u.stride = 1;
-    u.NB = B; u.OH = H; u.OW = W; u.M = B * H * W; u.Nn = 4 * Co;
-    u.dst = (float *)y; u.DH = 2 * H; u.DW = 2 * W; u.DC = Co; u.scatter = 1; u.cout = Co;
-    u.bias = (const float *)bias;
-    u.math = t_math;
-    return launch_igemm(u, st);
+    return launch_igemm(upconv_fwd_desc((const float *)x, B, H, W, Ci, (const float *)scratch, (const float *)bias, Co, (float *)y), st);
 }
 
 int unet_upconv2_bwd(const void *x, int B, int H, int W, int Ci, const void *w_iohw, int Co, const void *dy,
@@ -1069,15 +1046,7 @@ int unet_upconv2_bwd(const void *x, int B, int H, int W, int Ci, const void *w_i
     int rc;
     if (dx) {
         if ((rc = pack_upconv_dgrad((const float *)w_iohw, wt, Ci, Co, t_es, st))) return rc;
-        IgemmP d{};
-        d.nsrc = 1; d.src[0] = GSrc{(const float *)dy, 2 * H, 2 * W, Co, 0, Co, 0};
-        d.wt = wt; d.Kd = 4 * Co;
-        d.T = 4; d.TX = 2; d.stride = 2;
-        d.NB = B; d.OH = H; d.OW = W; d.M = B * H * W; d.Nn = Ci;
-        d.dst = (float *)dx; d.DH = H; d.DW = W; d.DC = Ci;
-        d.mask = (const float *)mask;
-        d.math = t_math;
-        if ((rc = launch_igemm(d, st))) return rc;
+        if ((rc = launch_igemm(upconv_dgrad_desc((const float *)dy, B, H, W, Ci, wt, Co, (float *)dx, (const float *)mask), st))) return rc;
     }
     if (dw) {
         WgradP w = upconv_wgrad_desc((const float *)x, H, Ci, (const float *)dy, Co, B, (float *)dw, slab, slab_bytes, (float *)db);

@@ -14,8 +14,10 @@
  *     OIHW, transposed-conv weights IOHW, int64 labels/masks.  Internally activations are
  *     NHWC fp32 (per-op entry points take NHWC).
  *   - The caller owns every buffer, including the workspace (size: unet_workspace_bytes).
- *   - All work is enqueued on the caller's stream; a handle is re-entrant per stream: nothing a call needs lives in
- *     process-wide state (the arithmetic mode is fixed per forward and kept with its plan for the backward).
+ *   - All work is enqueued on the caller's stream; a handle is re-entrant per stream: what a forward plans (workspace
+ *     layout, arithmetic mode) is kept with its plan for the backward.  Process-wide are only the switches: unet_set_math
+ *     (the default of handles created with math = -1, and of the per-op entry points), unet_set_overlap, unet_set_lds_dma
+ *     and unet_profile_*; set them while no call is in flight.
  *   - One process per GPU: a handle's calls must be made while its device is the current HIP device (checked).
  */
 #ifndef UNET_HIP_H
