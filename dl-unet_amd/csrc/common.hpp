@@ -38,20 +38,36 @@ struct ProfScope {          // RAII: names the row for the launches of a block
     ~ProfScope() { prof_scope(nullptr); }
 };
 
-// raise a kernel's dynamic-LDS limit once per (kernel, device)
-static inline int ensure_dynamic_lds(const void *kern, int bytes, bool (&done)[64])
+// one launch of an MFMA kernel: raise the kernel's dynamic-LDS limit once per (kernel, device), then the launch inside its
+// profile record (kind, tag and the three roofline figures as prof_begin takes them)
+template <auto Kern, class Arg>
+static inline int launch_profiled(int grid, int threads, int lds, hipStream_t st, int kind, const char *tag, double alg_flops,
+                                  double exec_flops, double alg_bytes, const Arg &arg)
 {
+    static bool attr_done[64] = {false};
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) { set_error("bad device"); return -2; }
-    if (!done[dev]) {
-        HIP_TRY(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-        done[dev] = true;
+    if (!attr_done[dev]) {
+        HIP_TRY(hipFuncSetAttribute((const void *)Kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        attr_done[dev] = true;
     }
+    prof_begin(kind, tag, st, alg_flops, exec_flops, alg_bytes);
+    hipLaunchKernelGGL(Kern, dim3(grid), dim3(threads), lds, st, arg);
+    prof_end(st);
+    HIP_TRY(hipGetLastError());
     return 0;
 }
+int device_cu_count();        // compute units of the current device (256 if the query fails)
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// The one size rule: element counts stay below 2^31 - 1 (31-bit element offsets), and a tensor is staged through a buffer
+// descriptor (32-bit num_records, the out-of-range marker of kernel_parts.hpp) only if its bytes do; else no descriptor
+constexpr size_t LIMIT_31BIT = 0x7FFFFFFFull;
+static inline size_t tensor_elems(int NB, int H, int W, int C) { return (size_t)NB * H * W * C; }
+static inline size_t tensor_bytes(int NB, int H, int W, int C, size_t es) { return tensor_elems(NB, H, W, C) * es; }
+static inline bool fits_buffer(size_t bytes) { return bytes < LIMIT_31BIT; }
 
 // ---------------------------------------------------------------------------------------------
 // Implicit-GEMM descriptor (igemm.hip):  D[m][n] = epi( sum_{src,tap,c} A[m][src,tap,c] * Wt[n][kd] )
@@ -108,6 +124,18 @@ struct IgemmP {
     FastDiv d_ohw, d_ow;   // set by launch_igemm: division by OH*OW and by OW (pixel index -> image, row, column)
 };
 int launch_igemm(IgemmP p, hipStream_t st);
+// buffer-descriptor sizes (bytes) of the sources, es bytes per element, into out[0..1] (0 for an absent source); returns the
+// first source too large for a descriptor, or -1
+static inline int igemm_source_bytes(const IgemmP &p, size_t es, int out[2])
+{
+    int big = -1;
+    for (int i = 0; i < 2; ++i) {
+        const size_t b = i < p.nsrc ? tensor_bytes(p.NB, p.src[i].H, p.src[i].W, p.src[i].C, es) : 0;
+        if (!fits_buffer(b) && big < 0) big = i;
+        out[i] = (int)b;
+    }
+    return big;
+}
 // Winograd F(2x2,3x3) path (wino.hip): filter transform into U (wino_u_floats(channels, Nn) floats) and applicability
 bool wino_applicable(const IgemmP &p);
 bool wino_fuses_pool(const IgemmP &p);

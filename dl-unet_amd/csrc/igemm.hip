@@ -37,15 +37,13 @@ static int g_lds_dma = [] { const char *e = getenv("UNET_LDS_DMA"); return e ? a
 int get_lds_dma_mode() { return g_lds_dma; }
 void set_lds_dma_mode(int m) { g_lds_dma = m; }
 
-#define GLDS16(gptr, lptr)                                                                    \
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(gptr),  \
-                                     (__attribute__((address_space(3))) void *)(lptr), 16, 0, 0)
-
-// 16-byte LDS-DMA through a buffer descriptor (a __device__ helper: calling the builtin directly from the kernel template
-// made the host pass drop the kernel's stub without a diagnostic)
-__device__ __forceinline__ void buf_lds16(__amdgpu_buffer_rsrc_t r, unsigned char *lds, int voff)
+int device_cu_count()
 {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void *)lds, 16, voff, 0, 0, 0);
+    static int ncu[64] = {0};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
+    if (!ncu[dev] && (hipDeviceGetAttribute(&ncu[dev], hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu[dev] <= 0)) ncu[dev] = 256;
+    return ncu[dev];
 }
 
 template <int BM, int BN, bool PAD, bool BUF>
@@ -62,18 +60,13 @@ __global__ __launch_bounds__(256, 2) void igemm_f32_kernel(const IgemmP p)
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / WN, wn = wave % WN;
-    // kernel arguments of the K loop and the epilogue, copied up front and pinned in SGPRs (igemm_epilogue.hpp)
+    // kernel arguments of the K loop and the epilogue, copied up front and pinned in SGPRs (kernel_parts.hpp)
     const IgEp ep = igb_epilogue_args(p);
     int a_TX = p.TX, a_T = p.T, a_nsrc = p.nsrc, a_oy0 = p.oy0, a_ox0 = p.ox0, a_stride = p.stride, a_ldw = p.ldw;
     IGB_PIN(a_TX); IGB_PIN(a_T); IGB_PIN(a_nsrc); IGB_PIN(a_oy0); IGB_PIN(a_ox0); IGB_PIN(a_stride); IGB_PIN(a_ldw);
 
-    // XCD-aware tile order: blocks b and b+8 share an XCD (and its L2), so give every XCD a
-    // contiguous run of logical tiles; N-tiles of one M-tile are neighbours and reuse the A rows.
-    int logical;
-    {
-        const int nblk = gridDim.x, q = nblk >> 3, r = nblk & 7, xcd = blockIdx.x & 7;
-        logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (blockIdx.x >> 3);
-    }
+    // N-tiles of one M-tile are neighbours in slot order (on one XCD) and reuse the A rows
+    const int logical = xcd_slot();
     const int mt = logical / p.ntiles, nt = logical - mt * p.ntiles;
     const int m0 = mt * BM, n0 = nt * BN;
 
@@ -97,21 +90,19 @@ __global__ __launch_bounds__(256, 2) void igemm_f32_kernel(const IgemmP p)
 
     // BUF: LDS-DMA through buffer descriptors (buffer_load_dwordx4 ... offen lds): 32-bit byte offsets, the weight column in
     // the scalar offset, taps in the zero padding as offsets beyond num_records (the range check returns zeros).
-    __amdgpu_buffer_rsrc_t rs_a = __builtin_amdgcn_make_buffer_rsrc((void *)p.src[0].p, 0, BUF ? p.buf_bytes[0] : 0, 0x00020000);
-    __amdgpu_buffer_rsrc_t rs_b = __builtin_amdgcn_make_buffer_rsrc((void *)p.wt, 0, BUF ? p.buf_bytes[2] : 0, 0x00020000);
+    __amdgpu_buffer_rsrc_t rs_a = make_rsrc(p.src[0].p, BUF ? p.buf_bytes[0] : 0);
+    __amdgpu_buffer_rsrc_t rs_b = make_rsrc(p.wt, BUF ? p.buf_bytes[2] : 0);
     auto setup_source = [&](int si) {
         const GSrc &g = p.src[si];
         sp = g.p; sH = g.H; sW = g.W; sC = g.C; snch = g.nch;
-        if (BUF) rs_a = __builtin_amdgcn_make_buffer_rsrc((void *)g.p, 0, p.buf_bytes[si], 0x00020000);
+        if (BUF) rs_a = make_rsrc(g.p, p.buf_bytes[si]);
         const int ohw = ep.OH * ep.OW;
 #pragma unroll
         for (int i = 0; i < RA; ++i) {
             int m = m0 + srow + 32 * i;
             m = m < ep.M ? m : ep.M - 1;
-            const int img = fdiv(m, ep.d_ohw);
-            const int rem = m - img * ohw;
-            const int oy = fdiv(rem, ep.d_ow);
-            const int ox = rem - oy * ep.OW;
+            int img, oy, ox;
+            pixel_of(ep, ohw, m, img, oy, ox);
             const int iy = (oy + a_oy0) * a_stride - g.pad;
             const int ix = (ox + a_ox0) * a_stride - g.pad;
             a_iy[i] = iy; a_ix[i] = ix;
@@ -129,13 +120,13 @@ __global__ __launch_bounds__(256, 2) void igemm_f32_kernel(const IgemmP p)
                 int vo = (a_off[i] + toff + kc) * 4;
                 if (PAD) {
                     const bool inb = (unsigned)(a_iy[i] + ty) < (unsigned)sH && (unsigned)(a_ix[i] + tx) < (unsigned)sW;
-                    vo = inb ? vo : (int)0x80000000;
+                    vo = inb ? vo : LDS_DMA_OOB;
                 }
-                buf_lds16(rs_a, abase + i * (32 * 128), vo);
+                lds_dma16(rs_a, abase + i * (32 * 128), vo, 0);
             }
 #pragma unroll
             for (int j = 0; j < RB; ++j)
-                buf_lds16(rs_b, bbase + j * (32 * 128), (b_off[j] + kglob) * 4);
+                lds_dma16(rs_b, bbase + j * (32 * 128), (b_off[j] + kglob) * 4, 0);
             return;
         }
 #pragma unroll
@@ -255,19 +246,13 @@ template <int BM, int BN, bool PAD, bool BUF>
 static int launch_cfg(const IgemmP &p, hipStream_t st)
 {
     constexpr int LDS = 2 * (BM + BN) * 128;
-    static bool attr_done[64] = {false};
-    auto kern = igemm_f32_kernel<BM, BN, PAD, BUF>;
-    if (int rc_ = ensure_dynamic_lds((const void *)kern, LDS, attr_done)) return rc_;
     IgemmP q = p;
     q.mtiles = cdiv(p.M, BM);
     q.ntiles = cdiv(p.Nn, BN);
     char tag[96];
     snprintf(tag, sizeof(tag), "igemm<%d;%d;%d> M=%d N=%d Kd=%d T=%d s=%d nsrc=%d", BM, BN, (int)PAD, p.M, p.Nn, p.Kd, p.T, p.stride, p.nsrc);
-    prof_begin(PK_IGEMM, tag, st, igemm_alg_flops(p), 2.0 * q.mtiles * BM * (double)q.ntiles * BN * p.Kd, igemm_alg_bytes(p));
-    hipLaunchKernelGGL(kern, dim3(q.mtiles * q.ntiles), dim3(256), LDS, st, q);
-    prof_end(st);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return launch_profiled<igemm_f32_kernel<BM, BN, PAD, BUF>>(q.mtiles * q.ntiles, 256, LDS, st, PK_IGEMM, tag, igemm_alg_flops(p),
+                                                               2.0 * q.mtiles * BM * (double)q.ntiles * BN * p.Kd, igemm_alg_bytes(p), q);
 }
 
 int launch_igemm(IgemmP p, hipStream_t st)
@@ -295,7 +280,7 @@ int launch_igemm(IgemmP p, hipStream_t st)
     ARG_CHECK(p.DC % 4 == 0 && p.dn0 % 4 == 0 && p.Nn % 4 == 0 && (!p.scatter || p.cout % 4 == 0), "igemm: 16-byte stores need channel counts that are multiples of 4");
     ARG_CHECK((size_t)p.NB * p.DH * p.DW * p.DC < 0xFFFFFFFFull, "igemm: destination exceeds 32-bit element offsets");
     for (int i = 0; i < p.nsrc; ++i)
-        ARG_CHECK((size_t)p.NB * p.src[i].H * p.src[i].W * p.src[i].C < 0x7FFFFFFFull, "igemm: source exceeds 31-bit element offsets");
+        ARG_CHECK(tensor_elems(p.NB, p.src[i].H, p.src[i].W, p.src[i].C) < LIMIT_31BIT, "igemm: source exceeds 31-bit element offsets");
     ARG_CHECK(!p.pool_dst || (p.math == 3 && p.wino_u), "igemm: the fused max-pool exists only in the Winograd epilogue");
     p.zeros = zero_page();
     if (!p.zeros) return -2;
@@ -303,25 +288,16 @@ int launch_igemm(IgemmP p, hipStream_t st)
     p.d_ow = make_fastdiv((unsigned)p.OW);
     ARG_CHECK(p.math >= 0 && p.math <= 3, "igemm: bad arithmetic mode %d", p.math);
     if (p.math == 3 && p.wino_u && wino_applicable(p)) {
-        ARG_CHECK((size_t)p.NB * p.DH * p.DW * p.DC < 0x7FFFFFFFull, "igemm: destination exceeds 31-bit element offsets");
+        ARG_CHECK(tensor_elems(p.NB, p.DH, p.DW, p.DC) < LIMIT_31BIT, "igemm: destination exceeds 31-bit element offsets");
         return launch_wino(p, p.wino_u, st);
     }
     if (p.math == 1) return launch_igemmx(p, pad, st);
     if (p.math == 2) return launch_igemmb(p, pad, st);          // bf16 tensors (igemmb.hip)
-    ARG_CHECK((size_t)p.NB * p.DH * p.DW * p.DC < 0x7FFFFFFFull, "igemm: destination exceeds 31-bit element offsets");
+    ARG_CHECK(tensor_elems(p.NB, p.DH, p.DW, p.DC) < LIMIT_31BIT, "igemm: destination exceeds 31-bit element offsets");
     // buffer-descriptor LDS-DMA needs sources and weights below 2 GiB
-    bool buf = g_lds_dma != 0;
-    for (int i = 0; i < 3; ++i) p.buf_bytes[i] = 0;
-    for (int i = 0; i < p.nsrc; ++i) {
-        const size_t b = (size_t)p.NB * p.src[i].H * p.src[i].W * p.src[i].C * sizeof(float);
-        if (b >= 0x7FFFFFFFull) buf = false;
-        p.buf_bytes[i] = (int)b;
-    }
-    {
-        const size_t b = (size_t)p.Nn * p.ldw * sizeof(float);
-        if (b >= 0x7FFFFFFFull) buf = false;
-        p.buf_bytes[2] = (int)b;
-    }
+    const size_t wbytes = (size_t)p.Nn * p.ldw * sizeof(float);
+    const bool buf = igemm_source_bytes(p, sizeof(float), p.buf_bytes) < 0 && fits_buffer(wbytes) && g_lds_dma != 0;
+    p.buf_bytes[2] = (int)wbytes;
     if (buf) {
         if (p.Nn % 128 == 0) return pad ? launch_cfg<128, 128, true, true>(p, st) : launch_cfg<128, 128, false, true>(p, st);
         return pad ? launch_cfg<256, 64, true, true>(p, st) : launch_cfg<256, 64, false, true>(p, st);

@@ -1,35 +1,9 @@
-// igemm_epilogue.hpp — epilogue shared by the implicit-GEMM kernels (igemm.hip, igemmx.hip).
+// igemm_epilogue.hpp — the fp32 LDS-transpose epilogue of the implicit GEMMs with fp32 tensors (igemm.hip, igemmx.hip); the
+// pinned arguments it takes (IgEp) and the destination rows are in kernel_parts.hpp.
 #pragma once
-#include "common.hpp"
+#include "kernel_parts.hpp"
 
 namespace unet {
-
-__device__ __forceinline__ int fdiv(int n, const FastDiv &f) { return (int)(((unsigned long long)(unsigned)n * f.mul) >> f.shift); }
-
-// The epilogue's (and the K loop's) kernel arguments are copied into locals up front and pinned in SGPRs (IGB_PIN): fetched where
-// they are used, every one of them is a scalar-load round trip behind the branch that needs it — dozens in a row per workgroup,
-// some of them once per K step (found with in-kernel stamps on the fp32 Winograd kernel).
-#define IGB_PIN(x) asm volatile("" : "+s"(x))
-struct IgEp {
-    int rw0, rw1, scatter, DC, OH, OW, DH, DW, dwy0, dwx0, M, cout, Nn, dn0, relu;
-    FastDiv d_ohw, d_ow;
-    const float *bias, *mask, *add;
-    float *dst;
-};
-__device__ __forceinline__ IgEp igb_epilogue_args(const IgemmP &p)
-{
-    IgEp e;
-    e.rw0 = p.rw0; e.rw1 = p.rw1; e.scatter = p.scatter; e.DC = p.DC; e.OH = p.OH; e.OW = p.OW; e.DH = p.DH; e.DW = p.DW;
-    e.dwy0 = p.dwy0; e.dwx0 = p.dwx0; e.M = p.M; e.cout = p.cout; e.Nn = p.Nn; e.dn0 = p.dn0; e.relu = p.relu;
-    e.d_ohw = p.d_ohw; e.d_ow = p.d_ow;
-    e.bias = p.bias; e.mask = p.mask; e.add = p.add; e.dst = p.dst;
-    IGB_PIN(e.rw0); IGB_PIN(e.rw1); IGB_PIN(e.scatter); IGB_PIN(e.DC); IGB_PIN(e.OH); IGB_PIN(e.OW); IGB_PIN(e.DH); IGB_PIN(e.DW);
-    IGB_PIN(e.dwy0); IGB_PIN(e.dwx0); IGB_PIN(e.M); IGB_PIN(e.cout); IGB_PIN(e.Nn); IGB_PIN(e.dn0); IGB_PIN(e.relu);
-    IGB_PIN(e.d_ohw.mul); IGB_PIN(e.d_ohw.shift); IGB_PIN(e.d_ow.mul); IGB_PIN(e.d_ow.shift);
-    // (the pointers are not pinned: behind the asm they would be generic pointers, i.e. FLAT instructions)
-    return e;
-}
-
 
 // ---- epilogue: bias / add / ReLU / mask / store with 16-byte accesses.
 // The MFMA accumulator layout gives a lane one column and 16 rows, i.e. dword stores (64 per lane; measured
@@ -46,25 +20,8 @@ __device__ __forceinline__ void igemm_rowoff_entry(const P &p, int m0, int i, un
 {
     unsigned *rowoff = (unsigned *)lds;
     unsigned char *inwin = lds + BM * 4 + 4 * EPI_WAVE_BYTES;     // per-row flag: pixel inside the deferred-ReLU window
-    const bool relu_win = p.rw1 > p.rw0;
-    int m = m0 + i;
-    m = m < p.M ? m : p.M - 1;
-    unsigned off;
-    unsigned char flag = 0;
-    if (!p.scatter && !relu_win) {
-        off = (unsigned)m * (unsigned)p.DC;
-    } else {
-        const int ohw = p.OH * p.OW;
-        const int img = fdiv(m, p.d_ohw);
-        const int rem = m - img * ohw;
-        const int oy = fdiv(rem, p.d_ow);
-        const int ox = rem - oy * p.OW;
-        if (p.scatter == 1) off = (unsigned)((img * p.DH + 2 * oy) * p.DW + 2 * ox) * (unsigned)p.DC;
-        else if (p.scatter == 2) off = (unsigned)((img * p.DH + oy + p.dwy0) * p.DW + ox + p.dwx0) * (unsigned)p.DC;
-        else off = (unsigned)m * (unsigned)p.DC;
-        flag = relu_win && oy >= p.rw0 && oy < p.rw1 && ox >= p.rw0 && ox < p.rw1;
-    }
-    rowoff[i] = off;
+    unsigned char flag;
+    rowoff[i] = dst_row(p, m0, i, flag);
     inwin[i] = flag;
 }
 

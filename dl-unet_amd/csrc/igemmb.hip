@@ -29,19 +29,13 @@
 // forwards +3...+10 %, some dgrads +6...+9 %).  With two workgroups per CU what the epilogue costs is its place at the end of a
 // workgroup's life, not its LDS instruction count.
 #include "common.hpp"
-#include "igemm_epilogue.hpp"
+#include "kernel_parts.hpp"
 #include <cstdio>
 #include <cstdlib>
 
 namespace unet {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned short u16;
-
-__device__ __forceinline__ void bbuf_lds16(__amdgpu_buffer_rsrc_t r, unsigned char *lds, int voff, int soff)
-{
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void *)lds, 16, voff, soff, 0, 0);
-}
 
 __device__ __forceinline__ float bf2f(u16 v) { return __builtin_bit_cast(float, (unsigned)v << 16); }
 __device__ __forceinline__ u16 f2bf(float f) { return __builtin_bit_cast(u16, (__bf16)f); }
@@ -54,9 +48,9 @@ constexpr int EPB_PITCH = 68;
 constexpr int EPB_WAVE_BYTES = 32 * EPB_PITCH * 4;          // 8704
 
 // row tables of a linear-M tile: element offset of each tile row's pixel in dst | flags (bit 0: inside the deferred-ReLU
-// window, bit 1: row outside the output domain)
-template <int BM, class P>
-__device__ __forceinline__ void igemmb_rows_linear(const P &p, int m0, int tid, unsigned *rowoff, unsigned char *rflag)
+// window, bit 1: row outside the output domain).  The offsets are dst_row's (kernel_parts.hpp), restated here: see there
+template <int BM>
+__device__ __forceinline__ void igemmb_rows_linear(const IgEp &p, int m0, int tid, unsigned *rowoff, unsigned char *rflag)
 {
     if (tid < BM) {
         const bool relu_win = p.rw1 > p.rw0;
@@ -85,15 +79,13 @@ __device__ __forceinline__ void igemmb_rows_linear(const P &p, int m0, int tid, 
 
 // TN = 32-column tiles per wave; the wave's tile rows start at `wrow0` of the workgroup tile, its columns at n0w.
 // The row tables must be complete (barrier) before the call; `patch` is the wave's private LDS area (EPB_WAVE_BYTES).
-// PF = row passes whose +add / mask operands are prefetched together (all of a slab's by default; the register-resident-filter
-// kernel below has fewer registers to spare)
 // The accumulators reach the store loop through a writer: write(tm, patch) puts slab tm (32 rows x 32 TN columns, bias added)
 // of the wave's block into the patch.  Acc16: 16x16x32 MFMAs (column = lane & 15, row = 4 (lane >> 4) + r), two 16-row tiles per slab.
-template <int TN, class P>
+template <int TN>
 struct Acc16 {
     f32x4 (&acc)[4][2 * TN];
     float bv[2 * TN];
-    __device__ __forceinline__ Acc16(const P &p, f32x4 (&a)[4][2 * TN], int n0w, int lane) : acc(a)
+    __device__ __forceinline__ Acc16(const IgEp &p, f32x4 (&a)[4][2 * TN], int n0w, int lane) : acc(a)
     {
         const int l15 = lane & 15;
 #pragma unroll
@@ -119,8 +111,8 @@ struct Acc16 {
     }
 };
 
-template <int TN, int PF = 0, class P = IgemmP, class ACC = Acc16<TN, P>>
-__device__ __forceinline__ void igemmb_store(const P &p, const ACC &accw, int wrow0, int n0w, int lane, float *patch,
+template <int TN>
+__device__ __forceinline__ void igemmb_store(const IgEp &p, const Acc16<TN> &accw, int wrow0, int n0w, int lane, float *patch,
                                              const unsigned *rowoff, const unsigned char *rflag)
 {
     constexpr int NL = 4 * TN;                 // lanes per row on the read-back side (8 channels each)
@@ -143,16 +135,13 @@ __device__ __forceinline__ void igemmb_store(const P &p, const ACC &accw, int wr
     for (int tm = 0; tm < 2; ++tm) {
         // the slab's +add / ReLU' mask operands first, all of them: their latency runs under the LDS transpose (issued one per
         // row pass inside the store loop they serialise against the stores - the compiler cannot prove dst != add/mask)
-        constexpr int NPA = 32 / RPP;                         // row passes of the slab
-        constexpr int NP = PF > 0 && PF < NPA ? PF : NPA;     // ... handled per chunk
+        constexpr int NP = 32 / RPP;                          // row passes of the slab
         size_t o[NP];
         unsigned char fl[NP];
         uint4 ta[NP], tk[NP];
 #pragma unroll
-      for (int k0 = 0; k0 < NPA; k0 += NP) {
-#pragma unroll
         for (int k = 0; k < NP; ++k) {
-            const int trow = wrow0 + tm * 32 + rrow + RPP * (k0 + k);
+            const int trow = wrow0 + tm * 32 + rrow + RPP * k;
             o[k] = (size_t)rowoff[trow] + (size_t)coloff;
             fl[k] = rflag[trow];
         }
@@ -164,10 +153,10 @@ __device__ __forceinline__ void igemmb_store(const P &p, const ACC &accw, int wr
 #pragma unroll
             for (int k = 0; k < NP; ++k) tk[k] = *(const uint4 *)(maskp + o[k]);
         }
-        if (k0 == 0) accw.write(tm, patch, lane);
+        accw.write(tm, patch, lane);
 #pragma unroll
         for (int k = 0; k < NP; ++k) {
-            const int prow = rrow + RPP * (k0 + k);
+            const int prow = rrow + RPP * k;
             const f32x4 lo = *(const f32x4 *)(patch + prow * EPB_PITCH + 8 * cg);
             const f32x4 hi = *(const f32x4 *)(patch + prow * EPB_PITCH + 8 * cg + 4);
             float v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
@@ -199,12 +188,11 @@ __device__ __forceinline__ void igemmb_store(const P &p, const ACC &accw, int wr
                 *(uint4 *)(dstp + o[k]) = w;
             }
         }
-      }
     }
 }
 
-template <int BM, int BN, class P, class A>
-__device__ __forceinline__ void igemmb_epilogue(const P &p, A &acc, int m0, int n0, int tid, unsigned char *lds)
+template <int BM, int BN>
+__device__ __forceinline__ void igemmb_epilogue(const IgEp &p, f32x4 (&acc)[4][4], int m0, int n0, int tid, unsigned char *lds)
 {
     constexpr int WN = BN / 64;
     unsigned *rowoff = (unsigned *)lds;
@@ -214,8 +202,8 @@ __device__ __forceinline__ void igemmb_epilogue(const P &p, A &acc, int m0, int 
     __syncthreads();
     const int lane = tid & 63, wave = tid >> 6;
     const int wm = wave / WN, wn = wave % WN;
-    const Acc16<2, P> w(p, acc, n0 + wn * 64, lane);
-    igemmb_store<2, 0, P, Acc16<2, P>>(p, w, wm * 64, n0 + wn * 64, lane, patch0 + wave * (EPB_WAVE_BYTES / 4), rowoff, rflag);
+    const Acc16<2> w(p, acc, n0 + wn * 64, lane);
+    igemmb_store<2>(p, w, wm * 64, n0 + wn * 64, lane, patch0 + wave * (EPB_WAVE_BYTES / 4), rowoff, rflag);
 }
 
 // ---- plain kernel: every tap re-stages its A rows (up-conv GEMMs, and any 3x3 shape the halo kernel does not take) -------
@@ -241,11 +229,7 @@ __global__ __launch_bounds__(256, 2) void igemmb_kernel(const IgemmP p)
     int a_TX = p.TX, a_T = p.T, a_nsrc = p.nsrc, a_oy0 = p.oy0, a_ox0 = p.ox0, a_stride = p.stride;
     IGB_PIN(a_TX); IGB_PIN(a_T); IGB_PIN(a_nsrc); IGB_PIN(a_oy0); IGB_PIN(a_ox0); IGB_PIN(a_stride);
 
-    int logical;
-    {
-        const int nblk = gridDim.x, q = nblk >> 3, r = nblk & 7, xcd = blockIdx.x & 7;
-        logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (blockIdx.x >> 3);
-    }
+    const int logical = xcd_slot();
     const int mt = logical / p.ntiles, nt = logical - mt * p.ntiles;
     const int m0 = mt * BM, n0 = nt * BN;
 
@@ -265,21 +249,19 @@ __global__ __launch_bounds__(256, 2) void igemmb_kernel(const IgemmP p)
 
     int s = 0, ty = 0, tx = 0, kc = 0, kglob = 0, kbase = 0;
     int sH = 0, sW = 0, sC = 0, snch = 0, toff = 0;
-    __amdgpu_buffer_rsrc_t rs_a = __builtin_amdgcn_make_buffer_rsrc((void *)p.src[0].p, 0, p.buf_bytes[0], 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_b = __builtin_amdgcn_make_buffer_rsrc((void *)p.wt, 0, p.buf_bytes[2], 0x00020000);
+    __amdgpu_buffer_rsrc_t rs_a = make_rsrc(p.src[0].p, p.buf_bytes[0]);
+    const __amdgpu_buffer_rsrc_t rs_b = make_rsrc(p.wt, p.buf_bytes[2]);
     auto setup_source = [&](int si) {
         const GSrc &g = p.src[si];
         sH = g.H; sW = g.W; sC = g.C; snch = g.nch;
-        rs_a = __builtin_amdgcn_make_buffer_rsrc((void *)g.p, 0, p.buf_bytes[si], 0x00020000);
+        rs_a = make_rsrc(g.p, p.buf_bytes[si]);
         const int ohw = ep.OH * ep.OW;
 #pragma unroll
         for (int i = 0; i < RA; ++i) {
             int m = m0 + srow + 32 * i;
             m = m < ep.M ? m : ep.M - 1;
-            const int img = fdiv(m, ep.d_ohw);
-            const int rem = m - img * ohw;
-            const int oy = fdiv(rem, ep.d_ow);
-            const int ox = rem - oy * ep.OW;
+            int img, oy, ox;
+            pixel_of(ep, ohw, m, img, oy, ox);
             const int iy = (oy + a_oy0) * a_stride - g.pad;
             const int ix = (ox + a_ox0) * a_stride - g.pad;
             a_iy[i] = iy; a_ix[i] = ix;
@@ -298,12 +280,12 @@ __global__ __launch_bounds__(256, 2) void igemmb_kernel(const IgemmP p)
             int vo = a_off[i] + so;
             if (PAD) {
                 const bool inb = (unsigned)(a_iy[i] + ty) < (unsigned)sH && (unsigned)(a_ix[i] + tx) < (unsigned)sW;
-                vo = inb ? vo : (int)0x80000000;
+                vo = inb ? vo : LDS_DMA_OOB;
             }
-            bbuf_lds16(rs_a, abase + i * (32 * 128), vo, 0);
+            lds_dma16(rs_a, abase + i * (32 * 128), vo, 0);
         }
 #pragma unroll
-        for (int j = 0; j < RB; ++j) bbuf_lds16(rs_b, bbase + j * (32 * 128), b_off[j], kglob * 2);
+        for (int j = 0; j < RB; ++j) lds_dma16(rs_b, bbase + j * (32 * 128), b_off[j], kglob * 2);
     };
     // K order of the loop: channel chunk outermost per source, taps innermost - consecutive steps re-read (almost) the same
     // pixels' same 128-byte pieces, shifted by one pixel or one row, while they are still in L2 (measured +0.5-3 % per layer
@@ -401,7 +383,6 @@ __global__ __launch_bounds__(256, 2) void igemmb3_kernel(const Igb3P k)
 {
     constexpr int BM = 128, BN = 128, WN = 2;
     constexpr int A_SLOT = IGB3_BAND * 128, B_BYTES = BN * 128, OFF_B = 2 * A_SLOT;
-    constexpr int OOB = (int)0x80000000;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const IgemmP &p = k.p;
 
@@ -413,11 +394,7 @@ __global__ __launch_bounds__(256, 2) void igemmb3_kernel(const Igb3P k)
     int a_nsrc = p.nsrc, a_oy0 = p.oy0, a_ox0 = p.ox0, a_Wv = k.Wv, a_nbands = k.nbands;
     IGB_PIN(a_nsrc); IGB_PIN(a_oy0); IGB_PIN(a_ox0); IGB_PIN(a_Wv); IGB_PIN(a_nbands);
 
-    int logical;
-    {
-        const int nblk = gridDim.x, q = nblk >> 3, r = nblk & 7, xcd = blockIdx.x & 7;
-        logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (blockIdx.x >> 3);
-    }
+    const int logical = xcd_slot();
     const int mt = logical / p.ntiles, nt = logical - mt * p.ntiles;
     const int m0 = mt * BM, n0 = nt * BN;
     const int grow0 = fdiv(m0, ep.d_ow);
@@ -435,7 +412,7 @@ __global__ __launch_bounds__(256, 2) void igemmb3_kernel(const Igb3P k)
             b_off[j] = (n * p.ldw + coff) * 2;
         }
     }
-    const __amdgpu_buffer_rsrc_t rs_b = __builtin_amdgcn_make_buffer_rsrc((void *)p.wt, 0, p.buf_bytes[2], 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_b = make_rsrc(p.wt, p.buf_bytes[2]);
 
     // band staging: the 18 instructions of a band (G: band rows 8 G .. 8 G + 7) go out in two halves, during the first and the
     // second K step of the band before; entry e = 3 h + kk of a thread is G = 9 h + wave + 4 kk (kk = 2: wave 0 only)
@@ -444,11 +421,11 @@ __global__ __launch_bounds__(256, 2) void igemmb3_kernel(const Igb3P k)
     // the band being fetched ("next"): source, channel chunk, filter row
     int s = 0, kc = 0, ty = 0, kbase = 0;
     int sH = 0, sW = 0, sC = 0, snch = 0;
-    __amdgpu_buffer_rsrc_t rs_a = __builtin_amdgcn_make_buffer_rsrc((void *)p.src[0].p, 0, p.buf_bytes[0], 0x00020000);
+    __amdgpu_buffer_rsrc_t rs_a = make_rsrc(p.src[0].p, p.buf_bytes[0]);
     auto setup_source = [&](int si) {
         const GSrc &g = p.src[si];
         sH = g.H; sW = g.W; sC = g.C; snch = g.nch;
-        rs_a = __builtin_amdgcn_make_buffer_rsrc((void *)g.p, 0, p.buf_bytes[si], 0x00020000);
+        rs_a = make_rsrc(g.p, p.buf_bytes[si]);
         const int nrows = p.NB * ep.OH;
 #pragma unroll
         for (int e = 0; e < 6; ++e) {
@@ -463,7 +440,7 @@ __global__ __launch_bounds__(256, 2) void igemmb3_kernel(const Igb3P k)
             const int iy = oy + a_oy0 - g.pad;
             const int ix = oxv + a_ox0 - g.pad;
             a_iy[e] = iy; a_ix[e] = ix;
-            a_off[e] = grow < nrows ? (((img * g.H + iy) * g.W + ix) * g.C + g.c0 + acoff) * 2 : OOB;
+            a_off[e] = grow < nrows ? (((img * g.H + iy) * g.W + ix) * g.C + g.c0 + acoff) * 2 : LDS_DMA_OOB;
             if (PAD && grow >= nrows) a_ix[e] = -1;
         }
     };
@@ -478,16 +455,16 @@ __global__ __launch_bounds__(256, 2) void igemmb3_kernel(const Igb3P k)
                 int vo = a_off[e] + so;
                 if (PAD) {
                     const bool inb = (unsigned)(a_iy[e] + ty) < (unsigned)sH && (unsigned)a_ix[e] < (unsigned)sW;
-                    vo = inb ? vo : OOB;
+                    vo = inb ? vo : LDS_DMA_OOB;
                 }
-                bbuf_lds16(rs_a, base + kk * 4096, vo, 0);
+                lds_dma16(rs_a, base + kk * 4096, vo, 0);
             }
         }
     };
     auto stage_b = [&](int kglob, int buf) {
         unsigned char *bbase = smem + OFF_B + buf * B_BYTES + wave * (8 * 128);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) bbuf_lds16(rs_b, bbase + j * (32 * 128), b_off[j], kglob * 2);
+        for (int j = 0; j < 4; ++j) lds_dma16(rs_b, bbase + j * (32 * 128), b_off[j], kglob * 2);
     };
     auto advance = [&]() {
         ++ty;
@@ -630,13 +607,9 @@ __global__ __launch_bounds__(256, 2) void igemmb3_kernel(const Igb3P k)
 // One barrier per tile.  The MFMA loop itself (36 steps of 4 ds_read_b128 + 4 MFMAs, fragments requested two steps ahead)
 // runs at 33 cycles per MFMA (tools/mfma_bf16_lds.hip: 34.8 for this mix on its own).
 // =========================================================================================================================
-#ifndef CB64_DEPTH
-#define CB64_DEPTH 3
-#endif
 struct CB64P {
     IgemmP p;
     int tx_n, ty_n, tiles;       // tiles per row / per column / in total (all images)
-    int dbg;                     // UNET_CB64_DBG & 8: in-kernel cycle stamps per phase (workgroup 0, wave 0)
     FastDiv d_tpi, d_tx;
 };
 
@@ -667,15 +640,11 @@ struct CB64Geom {
     static_assert(LDS <= 160 * 1024, "one workgroup per CU");
 };
 
-__device__ unsigned long long g_cb64_stamps[8];      // UNET_CB64_DBG & 8: cycles per phase (timing experiments)
-
 template <int TH, int TW, bool HAS_ADD, bool HAS_MASK>
 __global__ __launch_bounds__(256, 1) void convb64_kernel(const CB64P k)
 {
     using G = CB64Geom<TH, TW>;
     static_assert(TH == 8 && TW == 32, "a wave owns two tile rows of 32 pixels: each is one MFMA column block");
-    unsigned long long stamp[6] = {0, 0, 0, 0, 0, 0}, tprev = __builtin_readcyclecounter();
-    auto mark = [&](int i) { const unsigned long long now = __builtin_readcyclecounter(); stamp[i] += now - tprev; tprev = now; };
     const IgemmP &p = k.p;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
@@ -685,9 +654,8 @@ __global__ __launch_bounds__(256, 1) void convb64_kernel(const CB64P k)
     const int nb = blockIdx.x % nblk, wg = blockIdx.x / nblk, nwg = gridDim.x / nblk;
     const int n0 = nb * 64;
     const GSrc &g0 = p.src[0];
-    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc((void *)p.wt, 0, p.buf_bytes[2], 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc((void *)g0.p, 0, p.buf_bytes[0], 0x00020000);
-    constexpr int OOB = (int)0x80000000;
+    const __amdgpu_buffer_rsrc_t rs_w = make_rsrc(p.wt, p.buf_bytes[2]);
+    const __amdgpu_buffer_rsrc_t rs_x = make_rsrc(g0.p, p.buf_bytes[0]);
     const int l31 = lane & 31, lh = lane >> 5;
     const int tpi = k.tx_n * k.ty_n;
 
@@ -727,7 +695,7 @@ __global__ __launch_bounds__(256, 1) void convb64_kernel(const CB64P k)
                 const int iy = q.iy0 + (hpos[ii] >> 8), ix = q.ix0 + (hpos[ii] & 255);
                 ok = ok && (unsigned)iy < (unsigned)g0.H && (unsigned)ix < (unsigned)g0.W;
             }
-            hreg[ii] = __builtin_amdgcn_raw_buffer_load_b128(rs_x, ok ? q.base + hrel[ii] : OOB, 0, 0);     // zeros outside the tensor
+            hreg[ii] = __builtin_amdgcn_raw_buffer_load_b128(rs_x, ok ? q.base + hrel[ii] : LDS_DMA_OOB, 0, 0);     // zeros outside the tensor
         }
     };
     auto halo_store = [&](unsigned char *hl) {
@@ -747,7 +715,7 @@ __global__ __launch_bounds__(256, 1) void convb64_kernel(const CB64P k)
             const int R = 8 * i + sub;
             const int tap = R >> 6, n = R & 63;
             const int c = slot ^ ((n >> 1) & 7);
-            bbuf_lds16(rs_w, wl + i * 1024, ((n0 + n) * p.ldw + tap * 64 + c * 8) * 2, 0);
+            lds_dma16(rs_w, wl + i * 1024, ((n0 + n) * p.ldw + tap * 64 + c * 8) * 2, 0);
         }
     }
     int bw[2];                           // filter fragment base of n-block nbk (without tap / k step): row n = 32 nbk + l31
@@ -812,11 +780,10 @@ __global__ __launch_bounds__(256, 1) void convb64_kernel(const CB64P k)
             for (int j = 0; j < 2; ++j)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[i][j][r] = bv[i][r >> 2][r & 3];
-        if (k.dbg & 8) mark(0);            // set-up of the tile
 
         // ---- 36 steps (9 taps x 4 k steps of 16 channels), fully unrolled.  One wave per SIMD: nobody else hides the LDS
         // latency, so the fragments of step s + DEPTH - 1 are requested before the 4 MFMAs of step s issue
-        constexpr int DEPTH = CB64_DEPTH;
+        constexpr int DEPTH = 3;
         bf16x8 fa[DEPTH][2], fb[DEPTH][2];
         auto read_frags = [&](int st, int slot) {
             const int tap = st >> 2, x = (st & 3) << 5;
@@ -842,11 +809,9 @@ __global__ __launch_bounds__(256, 1) void convb64_kernel(const CB64P k)
                     acc[nbk][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[st % DEPTH][nbk], fa[st % DEPTH][j], acc[nbk][j], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
         }
-        if (k.dbg & 8) mark(1);            // MFMA loop
 
         // ---- the next tile's halo: registers -> the other buffer (every wave finished reading it before the last barrier)
         halo_store(smem + (cur ^ 1) * G::HALO_BYTES);
-        if (k.dbg & 8) mark(2);            // wait for the loads + LDS writes
 
         // ---- epilogue in registers: +add, ReLU, ReLU' mask, one rounding to bf16.  A lane holds 4-channel groups 8 g + 4 lh
         // of its pixel; v_permlane32_swap exchanges groups with the lane of the other half so that each ends up with two runs
@@ -897,14 +862,8 @@ __global__ __launch_bounds__(256, 1) void convb64_kernel(const CB64P k)
                     }
                 }
             }
-        if (k.dbg & 8) mark(3);            // epilogue
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");        // this wave's halo writes are in LDS
         __builtin_amdgcn_s_barrier();                              // (no vmcnt wait: the stores stay in flight)
-        if (k.dbg & 8) mark(4);            // barrier
-    }
-    if ((k.dbg & 8) && blockIdx.x == 0 && tid == 0) {
-        for (int i = 0; i < 5; ++i) atomicAdd(&g_cb64_stamps[i], stamp[i]);
-        atomicAdd(&g_cb64_stamps[7], 1ull);
     }
 }
 
@@ -918,37 +877,19 @@ template <int TH, int TW, bool HAS_ADD, bool HAS_MASK>
 static int launch_convb64_t(const IgemmP &p, hipStream_t st)
 {
     using G = CB64Geom<TH, TW>;
-    static bool attr_done[64] = {false};
-    auto kern = convb64_kernel<TH, TW, HAS_ADD, HAS_MASK>;
-    if (int rc_ = ensure_dynamic_lds((const void *)kern, G::LDS, attr_done)) return rc_;
     CB64P k;
     k.p = p;
     k.tx_n = cdiv(p.OW, TW); k.ty_n = cdiv(p.OH, TH);
     k.tiles = p.NB * k.tx_n * k.ty_n;
     k.d_tpi = make_fastdiv((unsigned)(k.tx_n * k.ty_n));
     k.d_tx = make_fastdiv((unsigned)k.tx_n);
-    static const int dbg = [] { const char *e = getenv("UNET_CB64_DBG"); return e ? atoi(e) : 0; }();
-    k.dbg = dbg;
     const int nblk = p.Nn / 64;
-    int cus = 256;
-    {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) cus = n;
-    }
+    const int cus = device_cu_count();
     int per = k.tiles < cus ? k.tiles : cus;          // persistent workgroups per n-block: one per CU
     char tag[96];
     snprintf(tag, sizeof(tag), "convb64<%d;%d> M=%d N=%d tiles=%d wgs=%d pad=%d", TH, TW, p.M, p.Nn, k.tiles, per * nblk, p.src[0].pad);
-    prof_begin(PK_IGEMM, tag, st, igemm_alg_flops(p), 2.0 * (double)k.tiles * (TH * TW) * p.Nn * 576.0, igemm_alg_bytes(p) / 2.0);
-    hipLaunchKernelGGL(kern, dim3(per * nblk), dim3(256), G::LDS, st, k);
-    prof_end(st);
-    HIP_TRY(hipGetLastError());
-    if (dbg & 8) {
-        unsigned long long h[8];
-        HIP_TRY(hipStreamSynchronize(st));
-        HIP_TRY(hipMemcpyFromSymbol(h, HIP_SYMBOL(g_cb64_stamps), sizeof(h)));
-        fprintf(stderr, "cb64 stamps %s: setup %llu mfma %llu halo-write %llu epilogue %llu barrier %llu (cycles, cumulative over %llu launches)\n", tag, h[0], h[1], h[2], h[3], h[4], h[7]);
-    }
-    return 0;
+    return launch_profiled<convb64_kernel<TH, TW, HAS_ADD, HAS_MASK>>(per * nblk, 256, G::LDS, st, PK_IGEMM, tag, igemm_alg_flops(p),
+                                                                      2.0 * (double)k.tiles * (TH * TW) * p.Nn * 576.0, igemm_alg_bytes(p) / 2.0, k);
 }
 
 template <int TH, int TW>
@@ -966,19 +907,13 @@ static int launch_cfgb(const IgemmP &p, hipStream_t st)
     constexpr int STAGES = 2 * (BM + BN) * 128;
     constexpr int EPI = BM * 4 + ((BM + 15) & ~15) + 4 * EPB_WAVE_BYTES;
     constexpr int LDS = STAGES > EPI ? STAGES : EPI;
-    static bool attr_done[64] = {false};
-    auto kern = igemmb_kernel<BM, BN, PAD>;
-    if (int rc_ = ensure_dynamic_lds((const void *)kern, LDS, attr_done)) return rc_;
     IgemmP q = p;
     q.mtiles = cdiv(p.M, BM);
     q.ntiles = cdiv(p.Nn, BN);
     char tag[96];
     snprintf(tag, sizeof(tag), "igemmb<%d;%d;%d> M=%d N=%d Kd=%d T=%d s=%d nsrc=%d", BM, BN, (int)PAD, p.M, p.Nn, p.Kd, p.T, p.stride, p.nsrc);
-    prof_begin(PK_IGEMM, tag, st, igemm_alg_flops(p), 2.0 * q.mtiles * BM * (double)q.ntiles * BN * p.Kd, igemm_alg_bytes(p) / 2.0);   // every tensor is 2 B/element
-    hipLaunchKernelGGL(kern, dim3(q.mtiles * q.ntiles), dim3(256), LDS, st, q);
-    prof_end(st);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return launch_profiled<igemmb_kernel<BM, BN, PAD>>(q.mtiles * q.ntiles, 256, LDS, st, PK_IGEMM, tag, igemm_alg_flops(p),
+                                                       2.0 * q.mtiles * BM * (double)q.ntiles * BN * p.Kd, igemm_alg_bytes(p) / 2.0, q);   // every tensor is 2 B/element
 }
 
 static bool igemmb3_applicable(const IgemmP &p)
@@ -987,7 +922,7 @@ static bool igemmb3_applicable(const IgemmP &p)
     for (int i = 0; i < p.nsrc; ++i)
         if (p.src[i].nch % 64) return false;
     // virtual pixel indices (two extra columns per output row) and the band rows past the last tile stay below 2^31
-    return (size_t)p.NB * p.OH * (p.OW + 2) + 1024 < 0x7FFFFFFFull;
+    return tensor_elems(p.NB, p.OH, p.OW + 2, 1) + 1024 < LIMIT_31BIT;
 }
 
 template <bool PAD>
@@ -997,9 +932,6 @@ static int launch_igemmb3(const IgemmP &p, hipStream_t st)
     constexpr int STAGES = 2 * IGB3_BAND * 128 + 2 * BN * 128;
     constexpr int EPI = BM * 4 + ((BM + 15) & ~15) + 4 * EPB_WAVE_BYTES;
     constexpr int LDS = STAGES > EPI ? STAGES : EPI;
-    static bool attr_done[64] = {false};
-    auto kern = igemmb3_kernel<PAD>;
-    if (int rc_ = ensure_dynamic_lds((const void *)kern, LDS, attr_done)) return rc_;
     Igb3P k;
     k.p = p;
     k.p.mtiles = cdiv(p.M, BM);
@@ -1010,11 +942,8 @@ static int launch_igemmb3(const IgemmP &p, hipStream_t st)
     k.d_oh = make_fastdiv((unsigned)p.OH);
     char tag[96];
     snprintf(tag, sizeof(tag), "igemmb3<%d> M=%d N=%d Kd=%d OW=%d nsrc=%d", (int)PAD, p.M, p.Nn, p.Kd, p.OW, p.nsrc);
-    prof_begin(PK_IGEMM, tag, st, igemm_alg_flops(p), 2.0 * k.p.mtiles * BM * (double)k.p.ntiles * BN * p.Kd, igemm_alg_bytes(p) / 2.0);
-    hipLaunchKernelGGL(kern, dim3(k.p.mtiles * k.p.ntiles), dim3(256), LDS, st, k);
-    prof_end(st);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return launch_profiled<igemmb3_kernel<PAD>>(k.p.mtiles * k.p.ntiles, 256, LDS, st, PK_IGEMM, tag, igemm_alg_flops(p),
+                                                2.0 * k.p.mtiles * BM * (double)k.p.ntiles * BN * p.Kd, igemm_alg_bytes(p) / 2.0, k);
 }
 
 // p has passed launch_igemm's generic checks; tensors are bf16
@@ -1025,18 +954,11 @@ int launch_igemmb(IgemmP p, bool pad, hipStream_t st)
         ARG_CHECK(p.src[i].C % 8 == 0 && p.src[i].c0 % 8 == 0, "igemmb: channel pitch/offset must be multiples of 8");
     }
     ARG_CHECK(p.ldw % 8 == 0 && p.DC % 8 == 0 && p.dn0 % 8 == 0 && p.Nn % 8 == 0 && (!p.scatter || p.cout % 8 == 0), "igemmb: 16-byte accesses need channel counts that are multiples of 8");
-    ARG_CHECK((size_t)p.NB * p.DH * p.DW * p.DC < 0x7FFFFFFFull, "igemmb: destination exceeds 31-bit element offsets");
-    for (int i = 0; i < 3; ++i) p.buf_bytes[i] = 0;
-    for (int i = 0; i < p.nsrc; ++i) {
-        const size_t b = (size_t)p.NB * p.src[i].H * p.src[i].W * p.src[i].C * 2;
-        ARG_CHECK(b < 0x7FFFFFFFull, "igemmb: source tensor exceeds 2 GiB");
-        p.buf_bytes[i] = (int)b;
-    }
-    {
-        const size_t b = (size_t)p.Nn * p.ldw * 2;
-        ARG_CHECK(b < 0x7FFFFFFFull, "igemmb: filter matrix exceeds 2 GiB");
-        p.buf_bytes[2] = (int)b;
-    }
+    ARG_CHECK(tensor_elems(p.NB, p.DH, p.DW, p.DC) < LIMIT_31BIT, "igemmb: destination exceeds 31-bit element offsets");
+    ARG_CHECK(igemm_source_bytes(p, 2, p.buf_bytes) < 0, "igemmb: source tensor exceeds 2 GiB");
+    const size_t wbytes = (size_t)p.Nn * p.ldw * 2;
+    ARG_CHECK(fits_buffer(wbytes), "igemmb: filter matrix exceeds 2 GiB");
+    p.buf_bytes[2] = (int)wbytes;
     static const int use_cb64 = [] { const char *e = getenv("UNET_CONVB64"); return e ? atoi(e) : 1; }();
     if (use_cb64 && convb64_applicable(p)) {
         return launch_convb64<8, 32>(p, st);

@@ -13,7 +13,7 @@
 // global_load_lds (the 3x3 taps then re-read the same LDS rows: X is fetched once, not 9x), and every
 // wave accumulates T 32x32 MFMA tiles (v_mfma_f32_32x32x2_f32, K = a pair of pixels).  Partial tiles
 // go to a slab and a second kernel reduces them in a fixed order (deterministic, no atomics).
-#include "common.hpp"
+#include "kernel_parts.hpp"
 #include <array>
 #include <cstdio>
 #include <cstdlib>
@@ -27,15 +27,7 @@ bool wgradw_applicable(const WgradP &p);
 size_t wgradw_slab_need(const WgradP &p);
 int launch_wgradw(const WgradP &p, hipStream_t st);
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-#define GLDS16(gptr, lptr)                                                                    \
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(gptr),  \
-                                     (__attribute__((address_space(3))) void *)(lptr), 16, 0, 0)
-
 constexpr int PWMAX = 32;     // pixels per strip (MFMA K = pixel pairs)
-
-__device__ __forceinline__ int fdiv_u(int n, const FastDiv &f) { return (int)(((unsigned long long)(unsigned)n * f.mul) >> f.shift); }
 
 struct WgradK {               // kernel-side copy with the derived decomposition
     WgradP p;
@@ -63,13 +55,6 @@ struct WgradGeom {
     static_assert(TY + S <= RING, "ring too small");
 };
 
-// (a plain function: with a run-time scalar offset the builtin, used directly inside a kernel's nested lambdas, makes the host
-//  pass drop the kernel's stub without a diagnostic)
-__device__ __forceinline__ void wg_dma16(__amdgpu_buffer_rsrc_t r, unsigned char *lds, int voff, int soff)
-{
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void *)lds, 16, voff, soff, 0, 0);
-}
-
 // NSPLIT 0: exact fp32 MFMA; 3: bf16x3 split of fp32 operands (see igemmx.hip).  BUF: the steady-state row step stages through
 // buffer descriptors with its items worked out once per partition (tensors below 2 GiB); else global_load_lds per item.
 template <int TY, int TX, int S, int NSPLIT, bool BUF>
@@ -89,11 +74,7 @@ __global__ __launch_bounds__(256, ((TY * TX == 9 && NSPLIT == 0) ? 3 : 2)) void 
     // block -> (partition group grp, channel tile); tiles of one group are neighbours on one XCD.  A workgroup
     // accumulates ALL partitions P = grp, grp+ngroups, ... of its tile in registers and writes one slab, so the
     // slab traffic is set by the number of resident workgroups, not by how finely the pixels are partitioned.
-    int logical;
-    {
-        const int nblk = gridDim.x, q = nblk >> 3, r = nblk & 7, xcd = blockIdx.x & 7;
-        logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (blockIdx.x >> 3);
-    }
+    const int logical = xcd_slot();
     const int ntile = k.ntile_i * k.ntile_j;
     const int grp = logical / ntile;
     const int tile = logical - grp * ntile;
@@ -116,9 +97,8 @@ __global__ __launch_bounds__(256, ((TY * TX == 9 && NSPLIT == 0) ? 3 : 2)) void 
     const int l31 = lane & 31, lh = lane >> 5;
     const int a_lane = (wi * 32 + l31) * 4;      // byte offset of this lane's X channel within a pixel
     const int b_lane = (wj * 32 + l31) * 4;
-    const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc((void *)p.X, 0, BUF ? k.xbytes : 0, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_y = __builtin_amdgcn_make_buffer_rsrc((void *)p.Y, 0, BUF ? k.ybytes : 0, 0x00020000);
-    static constexpr int OOB = (int)0x80000000;
+    const __amdgpu_buffer_rsrc_t rs_x = make_rsrc(p.X, BUF ? k.xbytes : 0);
+    const __amdgpu_buffer_rsrc_t rs_y = make_rsrc(p.Y, BUF ? k.ybytes : 0);
 
     for (int P = grp; P < k.nparts; P += k.ngroups) {
     const int strip = P % k.nstrips;
@@ -170,19 +150,19 @@ __global__ __launch_bounds__(256, ((TY * TX == 9 && NSPLIT == 0) ? 3 : 2)) void 
 #pragma unroll
         for (int i = 0; i < G::NI; ++i) {
             const int e = wave + 4 * i;
-            iv[i] = OOB; il[i] = 0; irr[i] = -1;
+            iv[i] = LDS_DMA_OOB; il[i] = 0; irr[i] = -1;
             if (e < S * G::XGROUPS) {
                 const int rr = (S == 2 && e >= G::XGROUPS) ? 1 : 0;
                 const int g = e - rr * G::XGROUPS;
                 const int xc = xcol0 + 4 * g + lq;
                 const bool ok = (unsigned)xc < (unsigned)p.XW && it * 64 + 4 * l15 < k.ci_real;
-                iv[i] = ok ? (xc * p.XC + p.xc0 + it * 64 + 4 * l15) * 4 : OOB;
+                iv[i] = ok ? (xc * p.XC + p.xc0 + it * 64 + 4 * l15) * 4 : LDS_DMA_OOB;
                 il[i] = g * 1024; irr[i] = rr;
             } else if (e < S * G::XGROUPS + G::YGROUPS) {
                 const int g = e - S * G::XGROUPS;
                 const int px = 4 * g + lq;
                 const bool ok = px < pwv && jt * 64 + 4 * l15 < k.cj_real;
-                iv[i] = ok ? ((x0 + px) * p.YC + p.yc0 + jt * 64 + 4 * l15) * 4 : OOB;
+                iv[i] = ok ? ((x0 + px) * p.YC + p.yc0 + jt * 64 + 4 * l15) * 4 : LDS_DMA_OOB;
                 il[i] = g * 1024;
             }
         }
@@ -196,9 +176,9 @@ __global__ __launch_bounds__(256, ((TY * TX == 9 && NSPLIT == 0) ? 3 : 2)) void 
                 if (irr[i] >= 0) {
                     const int xr = xr_base + irr[i];
                     const bool rok = (unsigned)xr < (unsigned)p.XH;
-                    wg_dma16(rs_x, xs + (xr & (G::RING - 1)) * G::XSLOT + il[i], rok ? iv[i] : OOB, rok ? ((img * p.XH + xr) * p.XW) * p.XC * 4 : 0);
+                    lds_dma16(rs_x, xs + (xr & (G::RING - 1)) * G::XSLOT + il[i], rok ? iv[i] : LDS_DMA_OOB, rok ? ((img * p.XH + xr) * p.XW) * p.XC * 4 : 0);
                 } else {
-                    wg_dma16(rs_y, ys + buf * G::YBUF + il[i], iv[i], ysoff);
+                    lds_dma16(rs_y, ys + buf * G::YBUF + il[i], iv[i], ysoff);
                 }
             }
         }
@@ -344,13 +324,6 @@ __device__ __forceinline__ float frag_sum(const bf16x8 &v)
     return s;
 }
 
-// (a plain function: with a run-time scalar offset the builtin, used directly inside the kernel's nested lambdas, makes the host
-//  pass drop the kernel's stub without a diagnostic)
-__device__ __forceinline__ void wgb_dma16(__amdgpu_buffer_rsrc_t r, unsigned char *lds, int voff, int soff)
-{
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void *)lds, 16, voff, soff, 0, 0);
-}
-
 template <int TY, int TX, int S>
 __global__ __launch_bounds__(256, 2) void wgrad_bf16_kernel(const WgradK k)
 {
@@ -365,11 +338,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_bf16_kernel(const WgradK k)
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wi = wave >> 1, wj = wave & 1;
 
-    int logical;
-    {
-        const int nblk = gridDim.x, q = nblk >> 3, r = nblk & 7, xcd = blockIdx.x & 7;
-        logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (blockIdx.x >> 3);
-    }
+    const int logical = xcd_slot();
     const int ntile = k.ntile_i * k.ntile_j;
     const int grp = logical / ntile;
     const int tile = logical - grp * ntile;
@@ -398,9 +367,8 @@ __global__ __launch_bounds__(256, 2) void wgrad_bf16_kernel(const WgradK k)
         xoff[tx] = (8 * f_h + f_q + tx) * 128 + ((cA ^ ((((f_q + tx) >> 1) & 1) << 2)) * 16) + (f_pp & 1) * 8;
     }
 
-    const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc((void *)p.X, 0, k.xbytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_y = __builtin_amdgcn_make_buffer_rsrc((void *)p.Y, 0, k.ybytes, 0x00020000);
-    static constexpr int OOB = (int)0x80000000;
+    const __amdgpu_buffer_rsrc_t rs_x = make_rsrc(p.X, k.xbytes);
+    const __amdgpu_buffer_rsrc_t rs_y = make_rsrc(p.Y, k.ybytes);
 
     // One copy of the whole partition loop per bias role (wave-uniform): the k loop's body must be straight-line code — a
     // branch per tap made the compiler wait for every fragment right before its MFMA (LDS latency exposed 36 times per row) —
@@ -424,14 +392,13 @@ __global__ __launch_bounds__(256, 2) void wgrad_bf16_kernel(const WgradK k)
         const int xc = xcol0 + pos;
         const bool ok = (unsigned)xr < (unsigned)p.XH && (unsigned)xc < (unsigned)p.XW;
         const int off = (((img * p.XH + xr) * p.XW + xc) * p.XC + p.xc0 + it * 64 + d_c * 8) * 2;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_x, (__attribute__((address_space(3))) void *)(xs + slot * G::XSLOT + g * 1024), 16,
-                                                 ok ? off : OOB, 0, 0, 0);
+        lds_dma16(rs_x, xs + slot * G::XSLOT + g * 1024, ok ? off : LDS_DMA_OOB, 0);
     };
     auto stage_y = [&](int y, int buf, int g) {
         const int px = 8 * g + d_px;
         const bool ok = px < pwv;
         const int off = (((img * p.YH + y) * p.YW + x0 + px) * p.YC + p.yc0 + jt * 64 + d_c * 8) * 2;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_y, (__attribute__((address_space(3))) void *)(ys + buf * G::YBUF + g * 1024), 16, ok ? off : OOB, 0, 0, 0);
+        lds_dma16(rs_y, ys + buf * G::YBUF + g * 1024, ok ? off : LDS_DMA_OOB, 0);
     };
     // items of one step: S new X rows (XG groups each) then the Y row; round-robin over waves.  Groups past the strip's
     // last needed pixel are skipped (their LDS content is never read: k-steps stop at nks).
@@ -465,19 +432,19 @@ __global__ __launch_bounds__(256, 2) void wgrad_bf16_kernel(const WgradK k)
 #pragma unroll
     for (int i = 0; i < G::NI; ++i) {
         const int e = wave + 4 * i;
-        iv[i] = OOB; il[i] = 0; irr[i] = -1;
+        iv[i] = LDS_DMA_OOB; il[i] = 0; irr[i] = -1;
         if (e < S * xg_used) {
             const int rr = 0;
             const int g = e;
             const int pos = 8 * g + d_px;
             const int xc = xcol0 + pos;
             const bool ok = (unsigned)xc < (unsigned)p.XW;
-            iv[i] = ok ? (xc * p.XC + p.xc0 + it * 64 + d_c * 8) * 2 : OOB;
+            iv[i] = ok ? (xc * p.XC + p.xc0 + it * 64 + d_c * 8) * 2 : LDS_DMA_OOB;
             il[i] = g * 1024; irr[i] = rr;
         } else if (e < n_items) {
             const int g = e - S * xg_used;
             const int px = 8 * g + d_px;
-            iv[i] = px < pwv ? ((x0 + px) * p.YC + p.yc0 + jt * 64 + d_c * 8) * 2 : OOB;
+            iv[i] = px < pwv ? ((x0 + px) * p.YC + p.yc0 + jt * 64 + d_c * 8) * 2 : LDS_DMA_OOB;
             il[i] = g * 1024;
         }
     }
@@ -492,9 +459,9 @@ __global__ __launch_bounds__(256, 2) void wgrad_bf16_kernel(const WgradK k)
                     const int xr = xr_base + irr[i];
                     const bool rok = (unsigned)xr < (unsigned)p.XH;
                     unsigned char *dst = xs + ((j * S + (TY - S) + irr[i]) % G::RING) * G::XSLOT + il[i];
-                    wgb_dma16(rs_x, dst, rok ? iv[i] : OOB, rok ? ((img * p.XH + xr) * p.XW) * p.XC * 2 : 0);
+                    lds_dma16(rs_x, dst, rok ? iv[i] : LDS_DMA_OOB, rok ? ((img * p.XH + xr) * p.XW) * p.XC * 2 : 0);
                 } else {
-                    wgb_dma16(rs_y, yb_ + il[i], iv[i], ysoff);
+                    lds_dma16(rs_y, yb_ + il[i], iv[i], ysoff);
                 }
             }
         }
@@ -595,11 +562,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_up_kernel(const WgradK k)
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wi = wave >> 1, wj = wave & 1;
 
-    int logical;
-    {
-        const int nblk = gridDim.x, q = nblk >> 3, r = nblk & 7, xcd = blockIdx.x & 7;
-        logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (blockIdx.x >> 3);
-    }
+    const int logical = xcd_slot();
     const int ntile = k.ntile_i * k.ntile_j;
     const int grp = logical / ntile;
     const int tile = logical - grp * ntile;
@@ -619,9 +582,8 @@ __global__ __launch_bounds__(256, 2) void wgrad_up_kernel(const WgradK k)
     const int d_ch = BF ? (((lane & 7) ^ (((lane >> 4) & 1) << 2)) * 8) : 4 * (lane & 15);        // source channel (bf16: swizzled chunk)
     const bool x_ch_ok = it * 64 + d_ch < k.ci_real, y_ch_ok = jt * 64 + d_ch < k.cj_real;
     const int x_lane = (p.xc0 + it * 64 + d_ch) * ES, y_lane = (p.yc0 + jt * 64 + d_ch) * ES;
-    const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc((void *)p.X, 0, k.xbytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_y = __builtin_amdgcn_make_buffer_rsrc((void *)p.Y, 0, k.ybytes, 0x00020000);
-    static constexpr int OOB = (int)0x80000000;
+    const __amdgpu_buffer_rsrc_t rs_x = make_rsrc(p.X, k.xbytes);
+    const __amdgpu_buffer_rsrc_t rs_y = make_rsrc(p.Y, k.ybytes);
     const int YW = p.YW;
     // tap (ty, tx) of dOut pixel (2y + ty, 2x + tx): a uniform byte offset from tap (0, 0)
     int tap_off[T];
@@ -636,13 +598,13 @@ __global__ __launch_bounds__(256, 2) void wgrad_up_kernel(const WgradK k)
             const int g = wave + 4 * gg;
             const int pix = c * G::PIX + g * G::PPI + d_px;
             const bool ok = pix < k.up_npix;
-            const int r = fdiv_u(pix, k.d_yw);                 // (image, y) row index of the layer input
+            const int r = fdiv(pix, k.d_yw);                 // (image, y) row index of the layer input
             const int x = pix - r * YW;
-            const int xo = ok && x_ch_ok ? ((4 * r * YW + 2 * x) * p.XC) * ES + x_lane : OOB;      // dOut pixel (2y, 2x)
-            const int yo = ok && y_ch_ok ? pix * p.YC * ES + y_lane : OOB;
+            const int xo = ok && x_ch_ok ? ((4 * r * YW + 2 * x) * p.XC) * ES + x_lane : LDS_DMA_OOB;      // dOut pixel (2y, 2x)
+            const int yo = ok && y_ch_ok ? pix * p.YC * ES + y_lane : LDS_DMA_OOB;
 #pragma unroll
-            for (int t = 0; t < T; ++t) wg_dma16(rs_x, sb + t * G::IMG + g * 1024, xo, tap_off[t]);
-            wg_dma16(rs_y, sb + 4 * G::IMG + g * 1024, yo, 0);
+            for (int t = 0; t < T; ++t) lds_dma16(rs_x, sb + t * G::IMG + g * 1024, xo, tap_off[t]);
+            lds_dma16(rs_y, sb + 4 * G::IMG + g * 1024, yo, 0);
         }
     };
 
@@ -876,7 +838,7 @@ static bool up_applicable(const WgradP &p)
     if (p.math == 1 || (p.db && !p.db_on_x)) return false;
     if (p.ywin0 != 0 || p.xwin0 != 0 || p.ywin1 != p.YH || p.xwin1 != p.YW || p.XH != 2 * p.YH || p.XW != 2 * p.YW) return false;
     const size_t es = p.math == 2 ? 2 : 4;
-    return (size_t)p.NB * p.XH * p.XW * p.XC * es < 0x7FFFFFFFull && (size_t)p.NB * p.YH * p.YW * p.YC * es < 0x7FFFFFFFull &&
+    return fits_buffer(tensor_bytes(p.NB, p.XH, p.XW, p.XC, es)) && fits_buffer(tensor_bytes(p.NB, p.YH, p.YW, p.YC, es)) &&
            (p.math == 2 || get_lds_dma_mode() != 0);
 }
 
@@ -900,19 +862,13 @@ template <bool BF>
 static int launch_wgrad_up(WgradK &k, hipStream_t st)
 {
     using G = UpGeom<BF>;
-    static bool attr_done[64] = {false};
-    auto kern = wgrad_up_kernel<BF>;
-    if (int rc_ = ensure_dynamic_lds((const void *)kern, G::LDS, attr_done)) return rc_;
-    k.xbytes = (int)((size_t)k.p.NB * k.p.XH * k.p.XW * k.p.XC * G::ES);
-    k.ybytes = (int)((size_t)k.p.NB * k.p.YH * k.p.YW * k.p.YC * G::ES);
+    k.xbytes = (int)tensor_bytes(k.p.NB, k.p.XH, k.p.XW, k.p.XC, G::ES);
+    k.ybytes = (int)tensor_bytes(k.p.NB, k.p.YH, k.p.YW, k.p.YC, G::ES);
     char tag[96];
     snprintf(tag, sizeof(tag), "wgrad_up<%s> Ci=%d Cj=%d Y=%dx%d chunks=%d per=%d groups=%d", BF ? "bf16" : "f32", k.p.Ci, k.p.Cj, k.p.YH, k.p.YW, k.up_nchunks, k.up_per, k.ngroups);
-    prof_begin(PK_WGRAD, tag, st, wgrad_alg_flops(k.p), 2.0 * (double)k.up_nchunks * G::PIX * 4.0 * k.p.Ci * k.p.Cj,
-               BF ? wgrad_alg_bytes(k.p) / 2.0 + 2.0 * 4.0 * k.p.Ci * k.p.Cj : wgrad_alg_bytes(k.p));
-    hipLaunchKernelGGL(kern, dim3(k.ngroups * k.ntile_i * k.ntile_j), dim3(256), G::LDS, st, k);
-    prof_end(st);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return launch_profiled<wgrad_up_kernel<BF>>(k.ngroups * k.ntile_i * k.ntile_j, 256, G::LDS, st, PK_WGRAD, tag, wgrad_alg_flops(k.p),
+                                                2.0 * (double)k.up_nchunks * G::PIX * 4.0 * k.p.Ci * k.p.Cj,
+                                                BF ? wgrad_alg_bytes(k.p) / 2.0 + 2.0 * 4.0 * k.p.Ci * k.p.Cj : wgrad_alg_bytes(k.p), k);
 }
 
 // whole 64-channel tiles: the kernels' unit; tensors with 32 channels (base-32 net) occupy half a tile
@@ -968,50 +924,37 @@ template <int TY, int TX, int S, int NSPLIT>
 static int launch_wgrad_t(WgradK &k, hipStream_t st)
 {
     using G = WgradGeom<TY, TX, S>;
-    static bool attr_done[64] = {false}, attr_done_b[64] = {false};
     // buffer-descriptor staging needs both tensors below 2 GiB (32-bit offsets, the out-of-range marker); larger ones and
     // unet_set_lds_dma(0) take the global_load_lds instantiation
-    const size_t xb = (size_t)k.p.NB * k.p.XH * k.p.XW * k.p.XC * 4, yb = (size_t)k.p.NB * k.p.YH * k.p.YW * k.p.YC * 4;
+    const size_t xb = tensor_bytes(k.p.NB, k.p.XH, k.p.XW, k.p.XC, 4), yb = tensor_bytes(k.p.NB, k.p.YH, k.p.YW, k.p.YC, 4);
     // (not for the exact-fp32 3x3 instantiation: at its three waves per SIMD the item registers would spill)
     constexpr bool CAN_BUF = !(TY * TX == 9 && NSPLIT == 0);
-    const bool buf = CAN_BUF && get_lds_dma_mode() != 0 && xb < 0x7FFFFFFFull && yb < 0x7FFFFFFFull;
+    const bool buf = CAN_BUF && get_lds_dma_mode() != 0 && fits_buffer(xb) && fits_buffer(yb);
     k.xbytes = buf ? (int)xb : 0; k.ybytes = buf ? (int)yb : 0;
-    auto kern = buf ? wgrad_f32_kernel<TY, TX, S, NSPLIT, CAN_BUF> : wgrad_f32_kernel<TY, TX, S, NSPLIT, false>;
-    if (int rc_ = ensure_dynamic_lds((const void *)kern, G::LDS, buf ? attr_done_b : attr_done)) return rc_;
+    const auto launch = buf ? launch_profiled<wgrad_f32_kernel<TY, TX, S, NSPLIT, CAN_BUF>, WgradK> : launch_profiled<wgrad_f32_kernel<TY, TX, S, NSPLIT, false>, WgradK>;
     char tag[96];
     snprintf(tag, sizeof(tag), "wgrad<%d;%d;%d;split%d> buf=%d Ci=%d Cj=%d Y=%dx%d win=%d parts=%d pw=%d rows=%d groups=%d", TY, TX, S, NSPLIT, (int)buf, k.p.Ci, k.p.Cj,
              k.p.YH, k.p.YW, k.p.ywin1 - k.p.ywin0, k.nparts, k.pw, k.rows_per_chunk, k.ngroups);
-    {
-        // executed: every workgroup runs its partitions' rows x pixel pairs (NSPLIT 0) / 16-pixel groups for all taps of a 64x64 tile
-        const double rows = (double)k.p.NB * (k.p.ywin1 - k.p.ywin0) * k.nstrips;
-        const double kpix = NSPLIT == 0 ? 2.0 * ((k.pw + 1) / 2) : 16.0 * ((k.pw + 15) / 16);
-        prof_begin(PK_WGRAD, tag, st, wgrad_alg_flops(k.p), 2.0 * rows * kpix * G::T * k.p.Ci * k.p.Cj * (NSPLIT == 3 ? 3 : 1), wgrad_alg_bytes(k.p));
-    }
-    hipLaunchKernelGGL(kern, dim3(k.ngroups * k.ntile_i * k.ntile_j), dim3(256), G::LDS, st, k);
-    prof_end(st);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    // executed: every workgroup runs its partitions' rows x pixel pairs (NSPLIT 0) / 16-pixel groups for all taps of a 64x64 tile
+    const double rows = (double)k.p.NB * (k.p.ywin1 - k.p.ywin0) * k.nstrips;
+    const double kpix = NSPLIT == 0 ? 2.0 * ((k.pw + 1) / 2) : 16.0 * ((k.pw + 15) / 16);
+    return launch(k.ngroups * k.ntile_i * k.ntile_j, 256, G::LDS, st, PK_WGRAD, tag, wgrad_alg_flops(k.p),
+                  2.0 * rows * kpix * G::T * k.p.Ci * k.p.Cj * (NSPLIT == 3 ? 3 : 1), wgrad_alg_bytes(k.p), k);
 }
 
 template <int TY, int TX, int S>
 static int launch_wgrad_b(WgradK &k, hipStream_t st)
 {
     using G = WgradBGeom<TY, TX, S>;
-    static bool attr_done[64] = {false};
-    auto kern = wgrad_bf16_kernel<TY, TX, S>;
-    if (int rc_ = ensure_dynamic_lds((const void *)kern, G::LDS, attr_done)) return rc_;
-    const size_t xb = (size_t)k.p.NB * k.p.XH * k.p.XW * k.p.XC * 2, yb = (size_t)k.p.NB * k.p.YH * k.p.YW * k.p.YC * 2;
-    ARG_CHECK(xb < 0x7FFFFFFFull && yb < 0x7FFFFFFFull, "wgrad (bf16): tensor exceeds 2 GiB");
+    const size_t xb = tensor_bytes(k.p.NB, k.p.XH, k.p.XW, k.p.XC, 2), yb = tensor_bytes(k.p.NB, k.p.YH, k.p.YW, k.p.YC, 2);
+    ARG_CHECK(fits_buffer(xb) && fits_buffer(yb), "wgrad (bf16): tensor exceeds 2 GiB");
     k.xbytes = (int)xb; k.ybytes = (int)yb;
     char tag[96];
     snprintf(tag, sizeof(tag), "wgradb<%d;%d;%d> buf=1 Ci=%d Cj=%d Y=%dx%d win=%d parts=%d pw=%d rows=%d groups=%d", TY, TX, S, k.p.Ci, k.p.Cj, k.p.YH, k.p.YW,
              k.p.ywin1 - k.p.ywin0, k.nparts, k.pw, k.rows_per_chunk, k.ngroups);
     const double rows = (double)k.p.NB * (k.p.ywin1 - k.p.ywin0) * k.nstrips;
-    prof_begin(PK_WGRAD, tag, st, wgrad_alg_flops(k.p), 2.0 * rows * k.pw * G::T * k.p.Ci * k.p.Cj, wgrad_alg_bytes(k.p) / 2.0 + 2.0 * G::T * k.p.Ci * k.p.Cj);
-    hipLaunchKernelGGL(kern, dim3(k.ngroups * k.ntile_i * k.ntile_j), dim3(256), G::LDS, st, k);
-    prof_end(st);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return launch_profiled<wgrad_bf16_kernel<TY, TX, S>>(k.ngroups * k.ntile_i * k.ntile_j, 256, G::LDS, st, PK_WGRAD, tag, wgrad_alg_flops(k.p),
+                                                         2.0 * rows * k.pw * G::T * k.p.Ci * k.p.Cj, wgrad_alg_bytes(k.p) / 2.0 + 2.0 * G::T * k.p.Ci * k.p.Cj, k);
 }
 
 int launch_wgrad(WgradP p, hipStream_t st)
@@ -1024,7 +967,7 @@ int launch_wgrad(WgradP p, hipStream_t st)
     ARG_CHECK(p.XC % 4 == 0 && p.YC % 4 == 0 && p.xc0 % 4 == 0 && p.yc0 % 4 == 0, "wgrad: channel pitch/offset must be multiples of 4");
     if (p.math == 2) ARG_CHECK(p.XC % 8 == 0 && p.YC % 8 == 0 && p.xc0 % 8 == 0 && p.yc0 % 8 == 0, "wgrad (bf16): channel pitch/offset must be multiples of 8");
     ARG_CHECK(p.ywin0 >= 0 && p.ywin1 <= p.YH && p.xwin0 >= 0 && p.xwin1 <= p.YW && p.ywin0 < p.ywin1 && p.xwin0 < p.xwin1, "wgrad: bad window");
-    ARG_CHECK((size_t)p.NB * p.XH * p.XW * p.XC < 0x7FFFFFFFull * 2 && (size_t)p.NB * p.YH * p.YW * p.YC < 0x7FFFFFFFull * 2, "wgrad: tensor too large");
+    ARG_CHECK(tensor_elems(p.NB, p.XH, p.XW, p.XC) < LIMIT_31BIT * 2 && tensor_elems(p.NB, p.YH, p.YW, p.YC) < LIMIT_31BIT * 2, "wgrad: tensor too large");
     p.zeros = zero_page();
     if (!p.zeros) return -2;
     ARG_CHECK(p.math >= 0 && p.math <= 3, "wgrad: bad arithmetic mode %d", p.math);

@@ -21,17 +21,11 @@
 // Each workgroup applies the signs and G^T . G to its partial dU itself; the partial 3x3 slabs are reduced in a fixed order by
 // wgradw_reduce_kernel, which writes the gradient in the caller's layout; the fused bias gradient is the sum of the dz values a wave reads anyway.
 #include "common.hpp"
-#include "igemm_epilogue.hpp"
+#include "kernel_parts.hpp"
 #include <cstdio>
 #include <cstdlib>
 
 namespace unet {
-
-#define GLDS16(gptr, lptr)                                                                    \
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(gptr),  \
-                                     (__attribute__((address_space(3))) void *)(lptr), 16, 0, 0)
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 struct WgradWK {
     WgradP p;
@@ -71,12 +65,8 @@ __global__ __launch_bounds__(512, 1) void wgradw_f32_kernel(const WgradWK k)
     const int wi = wave >> 1, wj = wave & 1;
     const int l15 = lane & 15, kg = lane >> 4;
 
-    // XCD-aware order: consecutive logical workgroups = the channel tiles of one K range (they read the same pixels)
-    int logical;
-    {
-        const int nblk = gridDim.x, q = nblk >> 3, r = nblk & 7, xcd = blockIdx.x & 7;
-        logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (blockIdx.x >> 3);
-    }
+    // consecutive logical workgroups = the channel tiles of one K range (they read the same pixels)
+    const int logical = xcd_slot();
     const int ntile = k.ntile_i * k.ntile_j;
     const int part = logical / ntile, tile = logical - part * ntile;
     const int it = tile / k.ntile_j, jt = tile - it * k.ntile_j;
@@ -93,9 +83,8 @@ __global__ __launch_bounds__(512, 1) void wgradw_f32_kernel(const WgradWK k)
 
     // BUF: LDS-DMA through buffer descriptors (buffer_load_dwordx4 ... offen lds): 32-bit byte offsets, the row offset as
     // scalar offset, pixels outside the tensors as offsets beyond num_records (the range check returns zeros).
-    const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc((void *)p.X, 0, BUF ? k.xbytes : 0, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_y = __builtin_amdgcn_make_buffer_rsrc((void *)p.Y, 0, BUF ? k.ybytes : 0, 0x00020000);
-    constexpr int OOB = (int)0x80000000;
+    const __amdgpu_buffer_rsrc_t rs_x = make_rsrc(p.X, BUF ? k.xbytes : 0);
+    const __amdgpu_buffer_rsrc_t rs_y = make_rsrc(p.Y, BUF ? k.ybytes : 0);
     auto stage = [&](int buf, int step) {
         unsigned char *sb = smem + buf * WW_STAGE;
         // the lane-derived roles are recomputed per call (a handful of VALU) instead of living in VGPRs across the loop:
@@ -125,7 +114,7 @@ __global__ __launch_bounds__(512, 1) void wgradw_f32_kernel(const WgradWK k)
                 const bool ok = xok && (unsigned)(iy0 + qy) < (unsigned)p.XH;
                 unsigned char *dst = sb + ((qy * 2 + d_par) * 4 + d_cb) * 1024;
                 if (BUF) {
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_x, (__attribute__((address_space(3))) void *)dst, 16, ok ? (base + qy * p.XW * p.XC) * 4 : OOB, 0, 0, 0);      // (base alone can be negative under zero padding)
+                    lds_dma16(rs_x, dst, ok ? (base + qy * p.XW * p.XC) * 4 : LDS_DMA_OOB, 0);      // (base alone can be negative under zero padding)
                 } else {
                     const float *g = ok ? p.X + (base + qy * p.XW * p.XC) : p.zeros;
                     GLDS16(g, dst);
@@ -142,7 +131,7 @@ __global__ __launch_bounds__(512, 1) void wgradw_f32_kernel(const WgradWK k)
                 const bool ok = xok && yy0 + py < p.YH;
                 unsigned char *dst = sb + WW_PATCH + WW_EXTRA + ((py * 2 + d_par) * 4 + d_cb) * 1024;
                 if (BUF) {
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_y, (__attribute__((address_space(3))) void *)dst, 16, ok ? (base + py * p.YW * p.YC) * 4 : OOB, 0, 0, 0);
+                    lds_dma16(rs_y, dst, ok ? (base + py * p.YW * p.YC) * 4 : LDS_DMA_OOB, 0);
                 } else {
                     const float *g = ok ? p.Y + (base + py * p.YW * p.YC) : p.zeros;
                     GLDS16(g, dst);
@@ -166,7 +155,7 @@ __global__ __launch_bounds__(512, 1) void wgradw_f32_kernel(const WgradWK k)
             const bool ok = eok && (unsigned)iy < (unsigned)p.XH && (unsigned)ix < (unsigned)p.XW;
             const int eoff = ((eimg * p.XH + iy) * p.XW + ix) * p.XC + e_xch;
             if (BUF) {
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_x, (__attribute__((address_space(3))) void *)(sb + WW_PATCH + wave * 1024), 16, ok ? eoff * 4 : OOB, 0, 0, 0);
+                lds_dma16(rs_x, sb + WW_PATCH + wave * 1024, ok ? eoff * 4 : LDS_DMA_OOB, 0);
             } else {
                 const float *g = ok ? p.X + eoff : p.zeros;
                 GLDS16(g, sb + WW_PATCH + wave * 1024);
@@ -464,15 +453,6 @@ bool wgradw_applicable(const WgradP &p)
     return true;
 }
 
-static int ww_cus()
-{
-    static int ncu[64] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-    if (!ncu[dev] && hipDeviceGetAttribute(&ncu[dev], hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) ncu[dev] = 256;
-    return ncu[dev];
-}
-
 static void ww_decompose(const WgradP &p, WgradWK &k, int cus)
 {
     k.p = p;
@@ -504,28 +484,23 @@ size_t wgradw_slab_need(const WgradP &p)
 
 int launch_wgradw(const WgradP &p, hipStream_t st)
 {
-    const size_t xb = (size_t)p.NB * p.XH * p.XW * p.XC * sizeof(float), yb = (size_t)p.NB * p.YH * p.YW * p.YC * sizeof(float);
-    const bool buf = get_lds_dma_mode() != 0 && xb < 0x7FFFFFFFull && yb < 0x7FFFFFFFull;
-    auto kern = buf ? wgradw_f32_kernel<true> : wgradw_f32_kernel<false>;
-    static bool attr_done[2][64] = {{false}};
-    if (int rc_ = ensure_dynamic_lds((const void *)kern, WW_LDS, attr_done[buf ? 1 : 0])) return rc_;
+    const size_t xb = tensor_bytes(p.NB, p.XH, p.XW, p.XC, sizeof(float)), yb = tensor_bytes(p.NB, p.YH, p.YW, p.YC, sizeof(float));
+    const bool buf = get_lds_dma_mode() != 0 && fits_buffer(xb) && fits_buffer(yb);
+    const auto launch = buf ? launch_profiled<wgradw_f32_kernel<true>, WgradWK> : launch_profiled<wgradw_f32_kernel<false>, WgradWK>;
     WgradWK k;
-    int cus = ww_cus();
+    int cus = device_cu_count();
     if (cus > 256) cus = 256;
     ww_decompose(p, k, cus);
     k.xbytes = buf ? (int)xb : 0; k.ybytes = buf ? (int)yb : 0;
     const int ntile = k.ntile_i * k.ntile_j;
     const size_t need = (size_t)ntile * k.nsplit * k.pstride * sizeof(float);
     ARG_CHECK(need <= p.slab_bytes, "wgradw: slab scratch too small (%zu < %zu)", p.slab_bytes, need);
-    ARG_CHECK((size_t)p.NB * p.XH * p.XW * p.XC < 0x7FFFFFFFull && (size_t)p.NB * p.YH * p.YW * p.YC < 0x7FFFFFFFull,
+    ARG_CHECK(tensor_elems(p.NB, p.XH, p.XW, p.XC) < LIMIT_31BIT && tensor_elems(p.NB, p.YH, p.YW, p.YC) < LIMIT_31BIT,
               "wgradw: tensor exceeds 31-bit element offsets");
     if (p.db) ARG_CHECK(p.ywin0 == 0 && p.xwin0 == 0 && p.ywin1 == p.YH && p.xwin1 == p.YW, "wgradw: fused bias gradient needs the full Y window");
     char tag[96];
     snprintf(tag, sizeof(tag), "wgradw<%d> Ci=%d Cj=%d Y=%dx%d tiles=%dx%d steps=%d split=%d", (int)buf, p.Ci, p.Cj, p.YH, p.YW, k.TYn, k.TXn, k.nsteps, k.nsplit);
-    prof_begin(PK_WGRAD, tag, st, wgrad_alg_flops(p), 2.0 * k.nsteps * 16.0 * 16.0 * p.Ci * p.Cj, wgrad_alg_bytes(p));
-    hipLaunchKernelGGL(kern, dim3(ntile * k.nsplit), dim3(512), WW_LDS, st, k);
-    prof_end(st);
-    HIP_TRY(hipGetLastError());
+    if (int rc_ = launch(ntile * k.nsplit, 512, WW_LDS, st, PK_WGRAD, tag, wgrad_alg_flops(p), 2.0 * k.nsteps * 16.0 * 16.0 * p.Ci * p.Cj, wgrad_alg_bytes(p), k)) return rc_;
     prof_begin(PK_REDUCE, "wgradw_reduce", st, 0.0, 0.0, (double)ntile * k.nsplit * k.pstride * 4.0 + 9.0 * p.Ci * p.Cj * 4.0);
     if (ntile <= 4 && k.nsplit >= 32)
         hipLaunchKernelGGL(wgradw_reduce_kernel<16>, dim3(ntile * 64), dim3(1024), 0, st, p.slab, k.nsplit, k.pstride, k.ntile_j,

@@ -30,17 +30,11 @@
 // what a step has to hide: 34 KiB per 64 MFMAs per wave.  DESIGN.md section 4 has the history (a 512-thread, 64-channel
 // wide, one-per-CU variant with 3-deep rings was measured slower or equal on every launch of the net and removed).
 #include "common.hpp"
-#include "igemm_epilogue.hpp"
+#include "kernel_parts.hpp"
 #include <cstdio>
 #include <cstdlib>
 
 namespace unet {
-
-#define GLDS16(gptr, lptr)                                                                    \
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(gptr),  \
-                                     (__attribute__((address_space(3))) void *)(lptr), 16, 0, 0)
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 struct WinoP {
     IgemmP p;
@@ -168,11 +162,7 @@ __global__ __launch_bounds__(256, 2) void wino32_f32_kernel(const WinoP k)
     // instruction): they run at raised priority, the K loop at the default (-0.3 % per step)
     __builtin_amdgcn_s_setprio(3);
 
-    int slot;
-    {
-        const int G = gridDim.x, q = G >> 3, r = G & 7, xcd = blockIdx.x & 7;
-        slot = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (blockIdx.x >> 3);
-    }
+    const int slot = xcd_slot();
     // consecutive slots (= workgroups resident together on an XCD, sharing its L2): gn n-tiles of one m-tile, then the next
     // m-tile; after all m-tiles the next group of n-tiles.  gn = 1 is n-major (the U block shared, every patch image distinct)
     int nt, mt;
@@ -189,8 +179,8 @@ __global__ __launch_bounds__(256, 2) void wino32_f32_kernel(const WinoP k)
     // BUF: LDS-DMA through buffer descriptors (buffer_load_dwordx4 ... offen lds): the per-lane byte offset is fixed for the
     // whole tile, the channel step goes into the scalar offset, and pixels outside the tensor are offsets beyond
     // num_records (the range check returns zeros) - no per-step address VALU at all.  Needs tensors < 2 GiB.
-    __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc((void *)p.src[0].p, 0, BUF ? k.xbytes[0] : 0, 0x00020000);
-    __amdgpu_buffer_rsrc_t rs_u = __builtin_amdgcn_make_buffer_rsrc((void *)k.U, 0, BUF ? k.ubytes : 0, 0x00020000);
+    __amdgpu_buffer_rsrc_t rs_x = make_rsrc(p.src[0].p, BUF ? k.xbytes[0] : 0);
+    __amdgpu_buffer_rsrc_t rs_u = make_rsrc(k.U, BUF ? k.ubytes : 0);
     const int u_voff = ((4 * wave) * 256 + lane * 4) * 4;
     const int u_soff0 = ((nt >> 1) * ns * 8192 + (nt & 1) * 4096) * 4;
     int uissued = 0;
@@ -201,7 +191,7 @@ __global__ __launch_bounds__(256, 2) void wino32_f32_kernel(const WinoP k)
             const int us = u_soff0 + uissued * 32768;
 #pragma unroll
             for (int i = 0; i < 4; ++i)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_u, (__attribute__((address_space(3))) void *)(ub + i * 1024), 16, u_voff, us + i * 1024, 0, 0);
+                lds_dma16(rs_u, ub + i * 1024, u_voff, us + i * 1024);
         } else {
             const float *us = ublk + (size_t)uissued * 8192;
 #pragma unroll
@@ -274,7 +264,7 @@ __global__ __launch_bounds__(256, 2) void wino32_f32_kernel(const WinoP k)
     int snch = p.src[0].nch, kc = 0, pissued = 0;
     if (BUF) {
 #pragma unroll
-        for (int ii = 0; ii < NPI; ++ii) poff[ii] = poff[ii] >= 0 ? poff[ii] * 4 : (int)0x80000000;
+        for (int ii = 0; ii < NPI; ++ii) poff[ii] = poff[ii] >= 0 ? poff[ii] * 4 : LDS_DMA_OOB;
     }
     const int tl = wave * 16 + l15;
     const int offA = tl * 32 + (((kg >> 1) ^ ((tl >> 3) & 1)) * 16) + (kg & 1) * 8;
@@ -297,9 +287,9 @@ __global__ __launch_bounds__(256, 2) void wino32_f32_kernel(const WinoP k)
         if (BUF) {
 #pragma unroll
             for (int ii = 0; ii < 4; ++ii)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_x, (__attribute__((address_space(3))) void *)(sb + ii * 4096), 16, poff[ii], kc * 4, 0, 0);
+                lds_dma16(rs_x, sb + ii * 4096, poff[ii], kc * 4);
             if (wave < 2)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_x, (__attribute__((address_space(3))) void *)(sb + 16384), 16, poff[4], kc * 4, 0, 0);
+                lds_dma16(rs_x, sb + 16384, poff[4], kc * 4);
         } else {
 #pragma unroll
             for (int ii = 0; ii < 4; ++ii) {
@@ -316,9 +306,9 @@ __global__ __launch_bounds__(256, 2) void wino32_f32_kernel(const WinoP k)
         if (kc == snch && pissued < ns) {
             kc = 0;
             sp = p.src[1].p; snch = p.src[1].nch;
-            if (BUF) rs_x = __builtin_amdgcn_make_buffer_rsrc((void *)p.src[1].p, 0, k.xbytes[1], 0x00020000);
+            if (BUF) rs_x = make_rsrc(p.src[1].p, k.xbytes[1]);
 #pragma unroll
-            for (int ii = 0; ii < NPI; ++ii) { const int o = poff1[ii * 256]; poff[ii] = BUF ? (o >= 0 ? o * 4 : (int)0x80000000) : o; }
+            for (int ii = 0; ii < NPI; ++ii) { const int o = poff1[ii * 256]; poff[ii] = BUF ? (o >= 0 ? o * 4 : LDS_DMA_OOB) : o; }
         }
     };
     auto issue_stage = [&]() { issue_patch(); issue_u(); };
@@ -575,20 +565,9 @@ int launch_wino(const IgemmP &p, const float *U, hipStream_t st)
     q.p.ntiles = p.Nn / 32;
     // buffer-descriptor LDS-DMA needs every tensor below 2 GiB (32-bit num_records and the out-of-range marker);
     // larger tensors (config #5 at batch 16) and unet_set_lds_dma(0) take the global_load_lds instantiation
-    bool buf = get_lds_dma_mode() != 0;
-    {
-        const size_t ub = wino_u_floats(kc, p.Nn) * sizeof(float);
-        if (ub >= 0x7FFFFFFFull) buf = false;
-        q.ubytes = (int)ub;
-        for (int i = 0; i < 2; ++i) {
-            q.xbytes[i] = 0;
-            if (i < p.nsrc) {
-                const size_t xb = (size_t)p.NB * p.src[i].H * p.src[i].W * p.src[i].C * sizeof(float);
-                if (xb >= 0x7FFFFFFFull) buf = false;
-                q.xbytes[i] = (int)xb;
-            }
-        }
-    }
+    const size_t ub = wino_u_floats(kc, p.Nn) * sizeof(float);
+    const bool buf = igemm_source_bytes(p, sizeof(float), q.xbytes) < 0 && fits_buffer(ub) && get_lds_dma_mode() != 0;
+    q.ubytes = (int)ub;
     // tile order: consecutive slots walk gn n-tiles of one m-tile, then the same n-tiles of the next m-tile (all m-tiles), then
     // the next group of n-tiles.  The 64 workgroups resident together on an XCD (32 CUs x 2) are then a 16 (m) x 4 (n) block of
     // the tile grid at about the same K step, and its L2 serves each patch stage to 4 and each U stage to 16 of them.  Round 3
@@ -600,16 +579,10 @@ int launch_wino(const IgemmP &p, const float *U, hipStream_t st)
     static const int gn_env = [] { const char *e = getenv("UNET_WINO_GN"); return e ? atoi(e) : 4; }();
     q.gn = 1; q.gn_shift = 0;
     while (q.gn * 2 <= gn_env && q.p.ntiles % (q.gn * 2) == 0) { q.gn *= 2; ++q.gn_shift; }
-    static bool attr32[64] = {false}, attr32b[64] = {false};
-    auto k32 = buf ? wino32_f32_kernel<true> : wino32_f32_kernel<false>;
-    if (int rc_ = ensure_dynamic_lds((const void *)k32, W32_TOTAL, buf ? attr32b : attr32)) return rc_;
     char tag32[96];
     snprintf(tag32, sizeof(tag32), "wino32<%d> M=%d N=%d Kd=%d nsrc=%d tiles=%d", (int)buf, p.M, p.Nn, p.Kd, p.nsrc, q.MT);
-    prof_begin(PK_WINO, tag32, st, igemm_alg_flops(p), igemm_alg_flops(p) * (16.0 / 36.0), igemm_alg_bytes(p));
-    hipLaunchKernelGGL(k32, dim3(q.p.mtiles * q.p.ntiles), dim3(256), W32_TOTAL, st, q);
-    prof_end(st);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    const auto launch = buf ? launch_profiled<wino32_f32_kernel<true>, WinoP> : launch_profiled<wino32_f32_kernel<false>, WinoP>;
+    return launch(q.p.mtiles * q.p.ntiles, 256, W32_TOTAL, st, PK_WINO, tag32, igemm_alg_flops(p), igemm_alg_flops(p) * (16.0 / 36.0), igemm_alg_bytes(p), q);
 }
 
 }  // namespace unet
