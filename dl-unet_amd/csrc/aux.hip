@@ -4,12 +4,11 @@
 //   N3 class-balance maps     : per-image class counts -> weight map            (functions.py:82-117)
 //   N1 elastic deformation    : separable Gaussian of a uniform field, bilinear warp (data.py:225-245)
 #include "common.hpp"
+#include "elem.hpp"
 #include <cmath>
 #include "../../include/unet_hip.h"
 
 namespace unet {
-
-typedef float float4_ __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ float wave_min(float v) { for (int d = 32; d >= 1; d >>= 1) v = fminf(v, __shfl_xor(v, d, 64)); return v; }
 __device__ __forceinline__ float wave_max(float v) { for (int d = 32; d >= 1; d >>= 1) v = fmaxf(v, __shfl_xor(v, d, 64)); return v; }
@@ -250,12 +249,6 @@ __global__ __launch_bounds__(256) void rotate_sample_kernel(const float *__restr
     }
 }
 
-static inline int grid1(size_t total, int cap = 16384)
-{
-    size_t g = (total + 255) / 256;
-    return (int)(g < 1 ? 1 : (g > (size_t)cap ? cap : g));
-}
-
 }  // namespace unet
 
 using namespace unet;
@@ -275,7 +268,7 @@ int unet_mirror_pad(const void *x, int B, int n, int S, const void *minmax, void
     ARG_CHECK(x && out && B > 0, "unet_mirror_pad: null argument");
     ARG_CHECK(S >= n && (S - n) % 2 == 0 && (S - n) / 2 <= n - 1, "unet_mirror_pad: cannot mirror %d into %d (pad must be even-split and < n)", n, S);
     const size_t total = (size_t)B * S * S;
-    hipLaunchKernelGGL(mirror_pad_kernel, dim3(grid1(total)), dim3(256), 0, (hipStream_t)stream, (const float *)x, (float *)out, n, S, (S - n) / 2,
+    hipLaunchKernelGGL(mirror_pad_kernel, dim3(grid_for(total, 256, 16384)), dim3(256), 0, (hipStream_t)stream, (const float *)x, (float *)out, n, S, (S - n) / 2,
                        (const float *)minmax, total);
     HIP_TRY(hipGetLastError());
     return 0;
@@ -288,7 +281,7 @@ int unet_eval_masks(const void *logits, long batch_stride, long plane_stride, lo
     ARG_CHECK(!labels_i64 || stats_u64, "unet_eval_masks: stats buffer needed with labels");
     hipStream_t st = (hipStream_t)stream;
     if (labels_i64) HIP_TRY(hipMemsetAsync(stats_u64, 0, (size_t)B * 3 * sizeof(unsigned long long), st));
-    int gx = grid1((size_t)n * n, 256);
+    int gx = grid_for((size_t)n * n, 256, 256);
     hipLaunchKernelGGL(eval_masks_kernel, dim3(gx, B), dim3(256), 0, st, (const float *)logits, batch_stride, plane_stride, row_stride, pad,
                        (const long long *)labels_i64, (long long *)mask_i64, n, (unsigned long long *)stats_u64);
     HIP_TRY(hipGetLastError());
@@ -301,8 +294,8 @@ int unet_class_balance(const void *labels_i64, int B, int H, int W, void *weight
     hipStream_t st = (hipStream_t)stream;
     const size_t npx = (size_t)H * W;
     HIP_TRY(hipMemsetAsync(counts_u64, 0, (size_t)B * sizeof(unsigned long long), st));
-    hipLaunchKernelGGL(count_ones_kernel, dim3(grid1(npx, 256), B), dim3(256), 0, st, (const long long *)labels_i64, npx, (unsigned long long *)counts_u64);
-    hipLaunchKernelGGL(class_balance_kernel, dim3(grid1(npx * B)), dim3(256), 0, st, (const long long *)labels_i64, npx,
+    hipLaunchKernelGGL(count_ones_kernel, dim3(grid_for(npx, 256, 256), B), dim3(256), 0, st, (const long long *)labels_i64, npx, (unsigned long long *)counts_u64);
+    hipLaunchKernelGGL(class_balance_kernel, dim3(grid_for(npx * B, 256, 16384)), dim3(256), 0, st, (const long long *)labels_i64, npx,
                        (const unsigned long long *)counts_u64, (float *)weights, npx * B);
     HIP_TRY(hipGetLastError());
     return 0;
@@ -313,8 +306,8 @@ int unet_gaussian_filter(const void *field, int B, int H, int W, const void *wei
     ARG_CHECK(field && weights && tmp && out && radius >= 0, "unet_gaussian_filter: bad argument");
     hipStream_t st = (hipStream_t)stream;
     const size_t total = (size_t)B * H * W;
-    hipLaunchKernelGGL(gauss1d_kernel, dim3(grid1(total)), dim3(256), 0, st, (const float *)field, (float *)tmp, H, W, 0, (const float *)weights, radius, 1.f, total);
-    hipLaunchKernelGGL(gauss1d_kernel, dim3(grid1(total)), dim3(256), 0, st, (const float *)tmp, (float *)out, H, W, 1, (const float *)weights, radius, scale, total);
+    hipLaunchKernelGGL(gauss1d_kernel, dim3(grid_for(total, 256, 16384)), dim3(256), 0, st, (const float *)field, (float *)tmp, H, W, 0, (const float *)weights, radius, 1.f, total);
+    hipLaunchKernelGGL(gauss1d_kernel, dim3(grid_for(total, 256, 16384)), dim3(256), 0, st, (const float *)tmp, (float *)out, H, W, 1, (const float *)weights, radius, scale, total);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -323,7 +316,7 @@ int unet_warp_bilinear(const void *img, const void *dy, const void *dx, int B, i
 {
     ARG_CHECK(img && dy && dx && out, "unet_warp_bilinear: null argument");
     const size_t total = (size_t)B * H * W;
-    hipLaunchKernelGGL(warp_bilinear_kernel, dim3(grid1(total)), dim3(256), 0, (hipStream_t)stream, (const float *)img, (const float *)dy, (const float *)dx,
+    hipLaunchKernelGGL(warp_bilinear_kernel, dim3(grid_for(total, 256, 16384)), dim3(256), 0, (hipStream_t)stream, (const float *)img, (const float *)dy, (const float *)dx,
                        (float *)out, H, W, total);
     HIP_TRY(hipGetLastError());
     return 0;
@@ -367,17 +360,14 @@ int unet_reflect_rotate_crop(const void *img, int B, int n, int pad, int S, cons
     }
     hipStream_t st = (hipStream_t)stream;
     float *reg = (float *)scratch, *tmp = reg + (size_t)B * W * W;
-    const size_t rt = (size_t)B * W * W;
+    const size_t rt = (size_t)B * W * W, ot = (size_t)B * S * S;
     ProfScope ps("N1.rotate");
-    prof_begin(PK_ELEMWISE, "reflect_rotate_crop", st, 0.0, 0.0, 4.0 * (5.0 * rt + (double)B * S * S));
-    hipLaunchKernelGGL(reflect_region_kernel, dim3(grid1(rt)), dim3(256), 0, st, (const float *)img, reg, n, pad, W, c0, c0, rt);
-    hipLaunchKernelGGL(spline_fir_kernel, dim3(grid1(rt)), dim3(256), 0, st, (const float *)reg, tmp, W, 1, taps, rt);
-    hipLaunchKernelGGL(spline_fir_kernel, dim3(grid1(rt)), dim3(256), 0, st, (const float *)tmp, reg, W, 0, taps, rt);
-    const size_t ot = (size_t)B * S * S;
-    hipLaunchKernelGGL(rotate_sample_kernel, dim3(grid1(ot)), dim3(256), 0, st, (const float *)reg, (float *)out, S, W, c0, c0, g, (float)levels, ot);
-    prof_end(st);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return profiled(PK_ELEMWISE, "reflect_rotate_crop", st, 0.0, 0.0, 4.0 * (5.0 * rt + (double)B * S * S), [&] {
+        hipLaunchKernelGGL(reflect_region_kernel, dim3(grid_for(rt, 256, 16384)), dim3(256), 0, st, (const float *)img, reg, n, pad, W, c0, c0, rt);
+        hipLaunchKernelGGL(spline_fir_kernel, dim3(grid_for(rt, 256, 16384)), dim3(256), 0, st, (const float *)reg, tmp, W, 1, taps, rt);
+        hipLaunchKernelGGL(spline_fir_kernel, dim3(grid_for(rt, 256, 16384)), dim3(256), 0, st, (const float *)tmp, reg, W, 0, taps, rt);
+        hipLaunchKernelGGL(rotate_sample_kernel, dim3(grid_for(ot, 256, 16384)), dim3(256), 0, st, (const float *)reg, (float *)out, S, W, c0, c0, g, (float)levels, ot);
+    });
 }
 
 }  // extern "C"

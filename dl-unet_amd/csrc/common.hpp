@@ -38,8 +38,18 @@ struct ProfScope {          // RAII: names the row for the launches of a block
     ~ProfScope() { prof_scope(nullptr); }
 };
 
-// one launch of an MFMA kernel: raise the kernel's dynamic-LDS limit once per (kernel, device), then the launch inside its
-// profile record (kind, tag and the three roofline figures as prof_begin takes them)
+// the launch bracket: one profile record (kind, tag and the three roofline figures as prof_begin takes them) around the one
+// or more launches that `launches` issues on st, then the launch error
+template <class F>
+static inline int profiled(int kind, const char *tag, hipStream_t st, double alg_flops, double exec_flops, double alg_bytes, F launches)
+{
+    prof_begin(kind, tag, st, alg_flops, exec_flops, alg_bytes);
+    launches();
+    prof_end(st);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+// one launch of an MFMA kernel: raise the kernel's dynamic-LDS limit once per (kernel, device), then the launch in its bracket
 template <auto Kern, class Arg>
 static inline int launch_profiled(int grid, int threads, int lds, hipStream_t st, int kind, const char *tag, double alg_flops,
                                   double exec_flops, double alg_bytes, const Arg &arg)
@@ -51,13 +61,10 @@ static inline int launch_profiled(int grid, int threads, int lds, hipStream_t st
         HIP_TRY(hipFuncSetAttribute((const void *)Kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
         attr_done[dev] = true;
     }
-    prof_begin(kind, tag, st, alg_flops, exec_flops, alg_bytes);
-    hipLaunchKernelGGL(Kern, dim3(grid), dim3(threads), lds, st, arg);
-    prof_end(st);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return profiled(kind, tag, st, alg_flops, exec_flops, alg_bytes,
+                    [&] { hipLaunchKernelGGL(Kern, dim3(grid), dim3(threads), lds, st, arg); });
 }
-int device_cu_count();        // compute units of the current device (256 if the query fails)
+int device_cu_count();       // compute units of the current device (256 if the query fails)
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -143,6 +150,8 @@ size_t wino_u_floats(int Kc, int Nn);
 int wino_transform_ref(const float *w_oihw, int I, int dgrad, int n0, int Nn, int k0, int Kc, float *U, hipStream_t st);
 int get_math_mode();          // process default (UNET_MATH / unet_set_math); plans and per-op calls copy it into their descriptors
 void set_math_mode(int m);
+// element size of the activation tensors the per-op entry points take: bf16 in arithmetic mode 2, else fp32
+static inline int op_es() { return get_math_mode() == 2 ? 2 : 4; }
 int get_lds_dma_mode();       // 1 (default): buffer-descriptor LDS-DMA when every tensor of a launch is below 2 GiB; 0: always global_load_lds
 void set_lds_dma_mode(int m);
 double igemm_alg_flops(const IgemmP &p);

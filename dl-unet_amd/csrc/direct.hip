@@ -1,7 +1,9 @@
 // direct.hip — the HBM-bound kernels of the path (no dense contraction worth a matrix core):
 //   conv11c (1 -> K stencil) fwd / weight-grad, 1x1 head fwd / bwd, 2x2 max-pool fwd / bwd,
-//   weight packers, bias gradients, and the step-side kernels (BCE-with-logits, one-hot,
-//   argmax, SGD-momentum).  All are written for 16 B per lane coalesced NHWC traffic.
+//   conv11c input gradient, weight packers, bias gradients, and the step-side kernels
+//   (BCE-with-logits alone and fused with the argmax mask, one-hot, argmax, SGD-momentum).
+// All are written for 16 B (fp32) / 8 B (bf16) per lane coalesced NHWC traffic, templated on the storage type.  Element
+// access, the block sum, grid_for and the dispatch on (element size, width) are elem.hpp's; the launch bracket is common.hpp's.
 #include "common.hpp"
 #include "elem.hpp"
 #include "../../include/unet_hip.h"
@@ -37,9 +39,9 @@ __global__ __launch_bounds__(256) void conv1ch_fwd_kernel(const float *__restric
     const int n4 = (3 * S) >> 2;              // S % 4 == 0 (S = 16L + 60)
     for (int row = blockIdx.x; row < nrows; row += gridDim.x) {
         const int img = row / So, oy = row - img * So;
-        const float4_ *xp = (const float4_ *)(x + ((size_t)img * S + oy) * S);
+        const f32x4 *xp = (const f32x4 *)(x + ((size_t)img * S + oy) * S);
         __syncthreads();                      // the previous row's readers are done with xs
-        for (int i = threadIdx.x; i < n4; i += 256) ((float4_ *)xs)[i] = xp[i];
+        for (int i = threadIdx.x; i < n4; i += 256) ((f32x4 *)xs)[i] = xp[i];
         __syncthreads();
         T *yrow = y + (size_t)row * So * K + cg * 4;
         for (int ox = pl; ox < So; ox += PPP) {
@@ -48,7 +50,7 @@ __global__ __launch_bounds__(256) void conv1ch_fwd_kernel(const float *__restric
             for (int r = 0; r < 3; ++r)
 #pragma unroll
                 for (int q = 0; q < 3; ++q) xv[r * 3 + q] = xs[r * S + ox + q];
-            float4_ o;
+            f32x4 o;
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
                 float a = bv[c];
@@ -84,14 +86,14 @@ __global__ __launch_bounds__(256) void conv1ch_wgrad_kernel(const float *__restr
     int row1 = row0 + rows_per_block; row1 = row1 < nrows ? row1 : nrows;
     for (int row = row0; row < row1; ++row) {
         const int img = row / So, oy = row - img * So;
-        const float4_ *xp = (const float4_ *)(x + ((size_t)img * S + oy) * S);
+        const f32x4 *xp = (const f32x4 *)(x + ((size_t)img * S + oy) * S);
         __syncthreads();
-        for (int i = threadIdx.x; i < n4; i += 256) ((float4_ *)xs)[i] = xp[i];
+        for (int i = threadIdx.x; i < n4; i += 256) ((f32x4 *)xs)[i] = xp[i];
         __syncthreads();
         const T *zrow = dz + (size_t)row * So * K + cg * 4;
 #pragma unroll 2
         for (int ox = pl; ox < So; ox += PPP) {
-            const float4_ g = load4(zrow + (size_t)ox * K);
+            const f32x4 g = load4(zrow + (size_t)ox * K);
 #pragma unroll
             for (int r = 0; r < 3; ++r)
 #pragma unroll
@@ -159,7 +161,7 @@ __global__ __launch_bounds__(256) void head1x1_fwd_kernel(const T *__restrict__ 
     constexpr int PPB = PPP * PASSES;               // pixels per block
     __shared__ float outs[2][PPB];
     const int cg = threadIdx.x % CG, pl = threadIdx.x / CG;
-    float4_ w0 = *(const float4_ *)(w + cg * 4), w1 = *(const float4_ *)(w + C + cg * 4);
+    f32x4 w0 = *(const f32x4 *)(w + cg * 4), w1 = *(const f32x4 *)(w + C + cg * 4);
     const float b0 = bias[0], b1 = bias[1];
     const size_t npix = (size_t)B * HW;
     const size_t base = (size_t)blockIdx.x * PPB;
@@ -169,7 +171,7 @@ __global__ __launch_bounds__(256) void head1x1_fwd_kernel(const T *__restrict__ 
         const size_t pix = base + lp;
         float s0 = 0.f, s1 = 0.f;
         if (pix < npix) {
-            const float4_ v = load4(x + pix * C + cg * 4);
+            const f32x4 v = load4(x + pix * C + cg * 4);
             s0 = v[0] * w0[0] + v[1] * w0[1] + v[2] * w0[2] + v[3] * w0[3];
             s1 = v[0] * w1[0] + v[1] * w1[1] + v[2] * w1[2] + v[3] * w1[3];
         }
@@ -197,9 +199,9 @@ __global__ __launch_bounds__(256) void head1x1_bwd_kernel(const T *__restrict__ 
 {
     constexpr int CG = C / 4, PPP = 256 / CG;
     const int cg = threadIdx.x % CG, pl = threadIdx.x / CG;
-    const float4_ w0 = *(const float4_ *)(w + cg * 4), w1 = *(const float4_ *)(w + C + cg * 4);
+    const f32x4 w0 = *(const f32x4 *)(w + cg * 4), w1 = *(const f32x4 *)(w + C + cg * 4);
     const size_t npix = (size_t)B * HW;
-    float4_ a0 = {0, 0, 0, 0}, a1 = {0, 0, 0, 0};
+    f32x4 a0 = {0, 0, 0, 0}, a1 = {0, 0, 0, 0};
     float sb0 = 0.f, sb1 = 0.f;
     // two pixels per trip: both loads are in flight before either is used (the loop is a dependent chain otherwise)
     const size_t step = (size_t)gridDim.x * PPP;
@@ -209,12 +211,12 @@ __global__ __launch_bounds__(256) void head1x1_bwd_kernel(const T *__restrict__ 
         const size_t pb = okb ? pixb : pix;
         const size_t img = pix / HW, rem = pix - img * HW;
         const size_t imgb = pb / HW, remb = pb - imgb * HW;
-        const float4_ v = load4(x + pix * C + cg * 4);
-        const float4_ vb = load4(x + pb * C + cg * 4);
+        const f32x4 v = load4(x + pix * C + cg * 4);
+        const f32x4 vb = load4(x + pb * C + cg * 4);
         const float d0 = dlogits[(img * 2) * HW + rem] * dls, d1 = dlogits[(img * 2 + 1) * HW + rem] * dls;
         float d0b = dlogits[(imgb * 2) * HW + remb] * dls, d1b = dlogits[(imgb * 2 + 1) * HW + remb] * dls;
         if (!okb) { d0b = 0.f; d1b = 0.f; }
-        float4_ g, gb;
+        f32x4 g, gb;
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             g[c] = v[c] > 0.f ? d0 * w0[c] + d1 * w1[c] : 0.f;
@@ -233,8 +235,8 @@ __global__ __launch_bounds__(256) void head1x1_bwd_kernel(const T *__restrict__ 
     }
     // row pitch 2C+4 floats: 16-byte aligned rows, one ds_write_b128 per class instead of four conflicting dword writes
     __shared__ __attribute__((aligned(16))) float red[PPP][2 * C + 4];
-    *(float4_ *)&red[pl][cg * 4] = a0;
-    *(float4_ *)&red[pl][C + cg * 4] = a1;
+    *(f32x4 *)&red[pl][cg * 4] = a0;
+    *(f32x4 *)&red[pl][C + cg * 4] = a1;
     if (cg == 0) { red[pl][2 * C] = sb0; red[pl][2 * C + 1] = sb1; }
     __syncthreads();
     for (int e = threadIdx.x; e < 2 * C + 2; e += 256) {
@@ -272,8 +274,8 @@ __global__ __launch_bounds__(256) void maxpool2_fwd_kernel(const T *__restrict__
         const int oy = (int)(pp % Ho);
         const int img = (int)(pp / Ho);
         const T *src = x + ((((size_t)img * H + 2 * oy) * W + 2 * ox) * C4 + c4) * 4;
-        const float4_ v00 = load4(src), v01 = load4(src + 4 * C4), v10 = load4(src + (size_t)W * C4 * 4), v11 = load4(src + ((size_t)W * C4 + C4) * 4);
-        float4_ m;
+        const f32x4 v00 = load4(src), v01 = load4(src + 4 * C4), v10 = load4(src + (size_t)W * C4 * 4), v11 = load4(src + ((size_t)W * C4 + C4) * 4);
+        f32x4 m;
 #pragma unroll
         for (int c = 0; c < 4; ++c) m[c] = fmaxf(fmaxf(v00[c], v01[c]), fmaxf(v10[c], v11[c]));
         store4(y + e * 4, m);             // a maximum of stored values: exact in either storage type
@@ -295,10 +297,10 @@ __global__ __launch_bounds__(256) void maxpool2_bwd_kernel(const T *__restrict__
         const int img = (int)(pp / Ho);
         const size_t o00 = ((((size_t)img * H + 2 * oy) * W + 2 * ox) * C4 + c4) * 4;
         const size_t o01 = o00 + 4 * (size_t)C4, o10 = o00 + (size_t)W * C4 * 4, o11 = o10 + 4 * (size_t)C4;
-        const float4_ v00 = load4(pre + o00), v01 = load4(pre + o01);
-        const float4_ v10 = load4(pre + o10), v11 = load4(pre + o11);
-        const float4_ g = load4(dy + e * 4);
-        float4_ g00, g01, g10, g11;
+        const f32x4 v00 = load4(pre + o00), v01 = load4(pre + o01);
+        const f32x4 v10 = load4(pre + o10), v11 = load4(pre + o11);
+        const f32x4 g = load4(dy + e * 4);
+        f32x4 g00, g01, g10, g11;
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             float m = v00[c]; int mi = 0;
@@ -371,33 +373,28 @@ __global__ void pack_upconv_dgrad_kernel(const float *__restrict__ w, T *__restr
 
 // es = element size of the packed matrix: 4 (fp32) or 2 (bf16, arithmetic mode 2)
 #define PACK_LAUNCH(kern, total, ...)                                                                           \
-    do {                                                                                                         \
-        prof_begin(PK_ELEMWISE, #kern, st, 0.0, 0.0, (4.0 + es) * (double)(total));                               \
-        if (es == 2) hipLaunchKernelGGL(kern<bf16_t>, dim3(grid_for(total)), dim3(256), 0, st, w, (bf16_t *)wt, __VA_ARGS__); \
-        else hipLaunchKernelGGL(kern<float>, dim3(grid_for(total)), dim3(256), 0, st, w, (float *)wt, __VA_ARGS__);          \
-        prof_end(st);                                                                                            \
-        HIP_TRY(hipGetLastError());                                                                              \
-    } while (0)
+    profiled(PK_ELEMWISE, #kern, st, 0.0, 0.0, (4.0 + es) * (double)(total), [&] {                                \
+        dispatch_es(es, [&](auto t) {                                                                            \
+            using T = decltype(t);                                                                               \
+            hipLaunchKernelGGL(kern<T>, dim3(grid_for(total)), dim3(256), 0, st, w, (T *)wt, __VA_ARGS__);        \
+        });                                                                                                      \
+    })
 
 int pack_conv_fwd(const float *w, void *wt, int K, int C1, int C2, int es, hipStream_t st)
 {
-    PACK_LAUNCH(pack_conv_fwd_kernel, (size_t)K * (C1 + C2) * 9, K, C1, C2);
-    return 0;
+    return PACK_LAUNCH(pack_conv_fwd_kernel, (size_t)K * (C1 + C2) * 9, K, C1, C2);
 }
 int pack_conv_dgrad(const float *w, void *wt, int K, int C, int es, hipStream_t st)
 {
-    PACK_LAUNCH(pack_conv_dgrad_kernel, (size_t)K * C * 9, K, C);
-    return 0;
+    return PACK_LAUNCH(pack_conv_dgrad_kernel, (size_t)K * C * 9, K, C);
 }
 int pack_upconv_fwd(const float *w, void *wt, int Ci, int Co, int es, hipStream_t st)
 {
-    PACK_LAUNCH(pack_upconv_fwd_kernel, (size_t)Ci * Co * 4, Ci, Co);
-    return 0;
+    return PACK_LAUNCH(pack_upconv_fwd_kernel, (size_t)Ci * Co * 4, Ci, Co);
 }
 int pack_upconv_dgrad(const float *w, void *wt, int Ci, int Co, int es, hipStream_t st)
 {
-    PACK_LAUNCH(pack_upconv_dgrad_kernel, (size_t)Ci * Co * 4, Ci, Co);
-    return 0;
+    return PACK_LAUNCH(pack_upconv_dgrad_kernel, (size_t)Ci * Co * 4, Ci, Co);
 }
 
 // ============================================================================================
@@ -415,19 +412,19 @@ __global__ __launch_bounds__(256) void bias_grad_kernel(const T *__restrict__ dz
     const int cg = threadIdx.x % CG, sl = threadIdx.x / CG;
     const size_t r0 = (size_t)blockIdx.x * BG_ROWS;
     size_t r1 = r0 + BG_ROWS; r1 = r1 < M ? r1 : M;
-    float4_ a = {0, 0, 0, 0};
+    f32x4 a = {0, 0, 0, 0};
     if (sl < slots)
         for (size_t r = r0 + sl; r < r1; r += slots) {
-            const float4_ v = load4(dz + r * K + cg * 4);
+            const f32x4 v = load4(dz + r * K + cg * 4);
             a[0] += v[0]; a[1] += v[1]; a[2] += v[2]; a[3] += v[3];
         }
-    __shared__ float4_ red[256];
+    __shared__ f32x4 red[256];
     red[threadIdx.x] = a;
     __syncthreads();
     if (threadIdx.x < CG) {
-        float4_ s = {0, 0, 0, 0};
-        for (int q = 0; q < slots; ++q) { const float4_ v = red[q * CG + threadIdx.x]; s[0] += v[0]; s[1] += v[1]; s[2] += v[2]; s[3] += v[3]; }
-        *(float4_ *)(partial + (size_t)blockIdx.x * K + threadIdx.x * 4) = s;
+        f32x4 s = {0, 0, 0, 0};
+        for (int q = 0; q < slots; ++q) { const f32x4 v = red[q * CG + threadIdx.x]; s[0] += v[0]; s[1] += v[1]; s[2] += v[2]; s[3] += v[3]; }
+        *(f32x4 *)(partial + (size_t)blockIdx.x * K + threadIdx.x * 4) = s;
     }
 }
 __global__ void bias_grad_reduce_kernel(const float *__restrict__ partial, int nb, int K, float *__restrict__ db)
@@ -448,13 +445,13 @@ int bias_grad(const void *dz, size_t M, int K, float *db, float *scratch, int es
 {
     ARG_CHECK(K % 4 == 0 && K / 4 <= 256, "bias_grad: K=%d unsupported", K);
     const int nb = (int)((M + BG_ROWS - 1) / BG_ROWS);
-    prof_begin(PK_ELEMWISE, "bias_grad", st, (double)M * K, 0.0, (double)es * M * K);
-    if (es == 2) hipLaunchKernelGGL(bias_grad_kernel<bf16_t>, dim3(nb), dim3(256), 0, st, (const bf16_t *)dz, M, K, scratch);
-    else hipLaunchKernelGGL(bias_grad_kernel<float>, dim3(nb), dim3(256), 0, st, (const float *)dz, M, K, scratch);
-    hipLaunchKernelGGL(bias_grad_reduce_kernel, dim3(cdiv(K, 256)), dim3(256), 0, st, scratch, nb, K, db);
-    prof_end(st);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return profiled(PK_ELEMWISE, "bias_grad", st, (double)M * K, 0.0, (double)es * M * K, [&] {
+        dispatch_es(es, [&](auto t) {
+            using T = decltype(t);
+            hipLaunchKernelGGL(bias_grad_kernel<T>, dim3(nb), dim3(256), 0, st, (const T *)dz, M, K, scratch);
+        });
+        hipLaunchKernelGGL(bias_grad_reduce_kernel, dim3(cdiv(K, 256)), dim3(256), 0, st, scratch, nb, K, db);
+    });
 }
 
 // ============================================================================================
@@ -491,27 +488,15 @@ __global__ __launch_bounds__(256) void bce_logits_kernel(const float *__restrict
             dx[e] = wv * (sg - zv) * inv_n * gscale;
         }
     }
-    __shared__ double red[256];
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
+    acc = block_sum256(acc);
+    if (threadIdx.x == 0) partial[blockIdx.x] = acc;
 }
 __global__ __launch_bounds__(256) void bce_final_kernel(const double *__restrict__ partial, int nb, size_t n, float *loss)
 {
-    __shared__ double red[256];
     double a = 0.0;
     for (int i = threadIdx.x; i < nb; i += 256) a += partial[i];
-    red[threadIdx.x] = a;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *loss = (float)(red[0] / (double)n);
+    a = block_sum256(a);
+    if (threadIdx.x == 0) *loss = (float)(a / (double)n);
 }
 
 // L1 + L2 in one pass over the logits (trainer.py:60-82): the one-hot target [1-y, y] is never materialised, the loss
@@ -552,14 +537,8 @@ __global__ __launch_bounds__(256) void bce_step_kernel(const float *__restrict__
         }
         if (mask) mask[e] = x1 > x0 ? 1 : 0;              // first maximum wins on ties -> class 0
     }
-    __shared__ double red[256];
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int s2 = 128; s2 > 0; s2 >>= 1) {
-        if (threadIdx.x < s2) red[threadIdx.x] += red[threadIdx.x + s2];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
+    acc = block_sum256(acc);
+    if (threadIdx.x == 0) partial[blockIdx.x] = acc;
 }
 
 __global__ void onehot2_kernel(const long long *__restrict__ labels, float *__restrict__ t, int B, size_t HW)
@@ -606,14 +585,14 @@ __global__ __launch_bounds__(256) void sgd_momentum_kernel(const SgdTable tb, fl
         float *pp = tb.p[t] + off; const float *gp = tb.g[t] + off; float *bp = tb.b[t] + off;
         const unsigned long long left = n - off;
         if (VEC && left >= SGD_CHUNK) {
-            float4_ g[4], b[4], q[4];
+            f32x4 g[4], b[4], q[4];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) g[i] = ((const float4_ *)gp)[i * 256 + threadIdx.x];
+            for (int i = 0; i < 4; ++i) g[i] = ((const f32x4 *)gp)[i * 256 + threadIdx.x];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) q[i] = ((const float4_ *)pp)[i * 256 + threadIdx.x];
+            for (int i = 0; i < 4; ++i) q[i] = ((const f32x4 *)pp)[i * 256 + threadIdx.x];
             if (!first) {
 #pragma unroll
-                for (int i = 0; i < 4; ++i) b[i] = ((const float4_ *)bp)[i * 256 + threadIdx.x];
+                for (int i = 0; i < 4; ++i) b[i] = ((const f32x4 *)bp)[i * 256 + threadIdx.x];
             }
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
@@ -623,8 +602,8 @@ __global__ __launch_bounds__(256) void sgd_momentum_kernel(const SgdTable tb, fl
                     b[i][c] = bn;
                     q[i][c] = __fsub_rn(q[i][c], __fmul_rn(lr, bn));
                 }
-                ((float4_ *)bp)[i * 256 + threadIdx.x] = b[i];
-                ((float4_ *)pp)[i * 256 + threadIdx.x] = q[i];
+                ((f32x4 *)bp)[i * 256 + threadIdx.x] = b[i];
+                ((f32x4 *)pp)[i * 256 + threadIdx.x] = q[i];
             }
         } else {
             const int m = left < SGD_CHUNK ? (int)left : SGD_CHUNK;
@@ -646,20 +625,14 @@ int conv1ch_fwd(const float *x, int B, int S, const float *w, const float *bias,
     const int So = S - 2, nrows = B * So;
     const int grid = nrows < 2048 ? nrows : 2048;
     const size_t lds = (size_t)3 * S * sizeof(float);
-    prof_begin(PK_STENCIL, "conv1ch_fwd", st, 18.0 * nrows * So * K, 0.0, 4.0 * B * S * S + (double)es * nrows * So * K);
-    if (es == 2) {
-        if (K == 64) hipLaunchKernelGGL((conv1ch_fwd_kernel<64, bf16_t>), dim3(grid), dim3(256), lds, st, x, w, bias, (bf16_t *)y, S, nrows);
-        else hipLaunchKernelGGL((conv1ch_fwd_kernel<32, bf16_t>), dim3(grid), dim3(256), lds, st, x, w, bias, (bf16_t *)y, S, nrows);
-    } else {
-        if (K == 64) hipLaunchKernelGGL((conv1ch_fwd_kernel<64, float>), dim3(grid), dim3(256), lds, st, x, w, bias, (float *)y, S, nrows);
-        else hipLaunchKernelGGL((conv1ch_fwd_kernel<32, float>), dim3(grid), dim3(256), lds, st, x, w, bias, (float *)y, S, nrows);
-    }
-    prof_end(st);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return profiled(PK_STENCIL, "conv1ch_fwd", st, 18.0 * nrows * So * K, 0.0, 4.0 * B * S * S + (double)es * nrows * So * K, [&] {
+        dispatch_es_width(es, K, [&](auto t, auto k) {
+            using T = decltype(t);
+            hipLaunchKernelGGL((conv1ch_fwd_kernel<k(), T>), dim3(grid), dim3(256), lds, st, x, w, bias, (T *)y, S, nrows);
+        });
+    });
 }
 
-// rows per workgroup and workgroup count of the weight-gradient pass (<= 1024 partial vectors)
 // conv11c input gradient (only a caller that asks for d loss / d image needs it; the reference's training never does):
 //   dx[b][y][x] = sum_{k,ty,tx} dz[b][y - ty][x - tx][k] w[k][ty][tx]      (full correlation with the flipped filter)
 // One thread per input pixel, the 9 x K filter taps in LDS, dz read with 16-byte (fp32) / 8-byte (bf16) accesses; neighbouring
@@ -689,7 +662,7 @@ __global__ __launch_bounds__(256) void conv1ch_dgrad_kernel(const T *__restrict_
                 const float *wt = ws[ty * 3 + tx];
 #pragma unroll
                 for (int k = 0; k < K; k += 4) {
-                    const float4_ v = load4(src + k);
+                    const f32x4 v = load4(src + k);
                     acc += v[0] * wt[k] + v[1] * wt[k + 1] + v[2] * wt[k + 2] + v[3] * wt[k + 3];
                 }
             }
@@ -702,20 +675,17 @@ int conv1ch_dgrad(const void *dz, int B, int S, int K, const float *w, float *dx
 {
     ARG_CHECK(K == 64 || K == 32, "conv1ch: K=%d unsupported (32 or 64)", K);
     const size_t total = (size_t)B * S * S;
-    const int nb = (int)((total + 255) / 256 < 65536 ? (total + 255) / 256 : 65536);
-    prof_begin(PK_STENCIL, "conv1ch_dgrad", st, 18.0 * (double)B * (S - 2) * (S - 2) * K, 0.0, 4.0 * (double)total + (double)es * B * (S - 2) * (S - 2) * K);
-    if (es == 2) {
-        if (K == 64) hipLaunchKernelGGL((conv1ch_dgrad_kernel<64, bf16_t>), dim3(nb), dim3(256), 0, st, (const bf16_t *)dz, w, dx, B, S);
-        else hipLaunchKernelGGL((conv1ch_dgrad_kernel<32, bf16_t>), dim3(nb), dim3(256), 0, st, (const bf16_t *)dz, w, dx, B, S);
-    } else {
-        if (K == 64) hipLaunchKernelGGL((conv1ch_dgrad_kernel<64, float>), dim3(nb), dim3(256), 0, st, (const float *)dz, w, dx, B, S);
-        else hipLaunchKernelGGL((conv1ch_dgrad_kernel<32, float>), dim3(nb), dim3(256), 0, st, (const float *)dz, w, dx, B, S);
-    }
-    prof_end(st);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    const int nb = grid_for(total, 256, 65536);
+    return profiled(PK_STENCIL, "conv1ch_dgrad", st, 18.0 * (double)B * (S - 2) * (S - 2) * K, 0.0,
+                    4.0 * (double)total + (double)es * B * (S - 2) * (S - 2) * K, [&] {
+        dispatch_es_width(es, K, [&](auto t, auto k) {
+            using T = decltype(t);
+            hipLaunchKernelGGL((conv1ch_dgrad_kernel<k(), T>), dim3(nb), dim3(256), 0, st, (const T *)dz, w, dx, B, S);
+        });
+    });
 }
 
+// rows per workgroup and workgroup count of the weight-gradient pass (<= 1024 partial vectors)
 static void conv1ch_bwd_split(int B, int S, int &rpb, int &nb)
 {
     const int nrows = B * (S - 2);
@@ -731,18 +701,13 @@ int conv1ch_bwd(const float *x, int B, int S, int K, const void *dz, float *dw, 
     const int So = S - 2, nrows = B * So;
     size_t lds = (size_t)3 * S * sizeof(float);
     if (lds < (size_t)40 * K * sizeof(float)) lds = (size_t)40 * K * sizeof(float);
-    prof_begin(PK_STENCIL, "conv1ch_wgrad", st, 20.0 * nrows * So * K, 0.0, 4.0 * B * S * S + (double)es * nrows * So * K);
-    if (es == 2) {
-        if (K == 64) hipLaunchKernelGGL((conv1ch_wgrad_kernel<64, bf16_t>), dim3(nb), dim3(256), lds, st, x, (const bf16_t *)dz, scratch, S, nrows, rpb);
-        else hipLaunchKernelGGL((conv1ch_wgrad_kernel<32, bf16_t>), dim3(nb), dim3(256), lds, st, x, (const bf16_t *)dz, scratch, S, nrows, rpb);
-    } else {
-        if (K == 64) hipLaunchKernelGGL((conv1ch_wgrad_kernel<64, float>), dim3(nb), dim3(256), lds, st, x, (const float *)dz, scratch, S, nrows, rpb);
-        else hipLaunchKernelGGL((conv1ch_wgrad_kernel<32, float>), dim3(nb), dim3(256), lds, st, x, (const float *)dz, scratch, S, nrows, rpb);
-    }
-    hipLaunchKernelGGL(conv1ch_wgrad_reduce_kernel, dim3(cdiv(10 * K, 4)), dim3(256), 0, st, (const float *)scratch, nb, K, dw, db);
-    prof_end(st);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return profiled(PK_STENCIL, "conv1ch_wgrad", st, 20.0 * nrows * So * K, 0.0, 4.0 * B * S * S + (double)es * nrows * So * K, [&] {
+        dispatch_es_width(es, K, [&](auto t, auto k) {
+            using T = decltype(t);
+            hipLaunchKernelGGL((conv1ch_wgrad_kernel<k(), T>), dim3(nb), dim3(256), lds, st, x, (const T *)dz, scratch, S, nrows, rpb);
+        });
+        hipLaunchKernelGGL(conv1ch_wgrad_reduce_kernel, dim3(cdiv(10 * K, 4)), dim3(256), 0, st, (const float *)scratch, nb, K, dw, db);
+    });
 }
 
 int head1x1_fwd(const void *x, int B, int H, int W, int C, const float *w, const float *bias, float *logits, int es, hipStream_t st)
@@ -751,17 +716,12 @@ int head1x1_fwd(const void *x, int B, int H, int W, int C, const float *w, const
     const size_t npix = (size_t)B * H * W;
     const int ppb = (256 / (C / 4)) * 16;
     const int grid = (int)((npix + ppb - 1) / ppb);
-    prof_begin(PK_ELEMWISE, "head1x1_fwd", st, 4.0 * npix * C, 0.0, (double)npix * (es * C + 8));
-    if (es == 2) {
-        if (C == 64) hipLaunchKernelGGL((head1x1_fwd_kernel<64, bf16_t>), dim3(grid), dim3(256), 0, st, (const bf16_t *)x, w, bias, logits, B, H * W);
-        else hipLaunchKernelGGL((head1x1_fwd_kernel<32, bf16_t>), dim3(grid), dim3(256), 0, st, (const bf16_t *)x, w, bias, logits, B, H * W);
-    } else {
-        if (C == 64) hipLaunchKernelGGL((head1x1_fwd_kernel<64, float>), dim3(grid), dim3(256), 0, st, (const float *)x, w, bias, logits, B, H * W);
-        else hipLaunchKernelGGL((head1x1_fwd_kernel<32, float>), dim3(grid), dim3(256), 0, st, (const float *)x, w, bias, logits, B, H * W);
-    }
-    prof_end(st);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return profiled(PK_ELEMWISE, "head1x1_fwd", st, 4.0 * npix * C, 0.0, (double)npix * (es * C + 8), [&] {
+        dispatch_es_width(es, C, [&](auto t, auto c) {
+            using T = decltype(t);
+            hipLaunchKernelGGL((head1x1_fwd_kernel<c(), T>), dim3(grid), dim3(256), 0, st, (const T *)x, w, bias, logits, B, H * W);
+        });
+    });
 }
 
 static int head_bwd_blocks(int B, int H, int W) { return grid_for((size_t)B * H * W, 16 * 32, 2048); }
@@ -771,41 +731,36 @@ int head1x1_bwd(const void *x, int B, int H, int W, int C, const float *w, const
     ARG_CHECK(C == 64 || C == 32, "head1x1: C=%d unsupported (32 or 64)", C);
     const int nb = head_bwd_blocks(B, H, W);
     const double npix = (double)B * H * W;
-    prof_begin(PK_ELEMWISE, "head1x1_bwd", st, 8.0 * npix * C, 0.0, npix * (2.0 * es * C + 8));
-    if (es == 2) {
-        if (C == 64) hipLaunchKernelGGL((head1x1_bwd_kernel<64, bf16_t>), dim3(nb), dim3(256), 0, st, (const bf16_t *)x, w, dlogits, dl_scale, (bf16_t *)dz, scratch, B, H * W);
-        else hipLaunchKernelGGL((head1x1_bwd_kernel<32, bf16_t>), dim3(nb), dim3(256), 0, st, (const bf16_t *)x, w, dlogits, dl_scale, (bf16_t *)dz, scratch, B, H * W);
-    } else {
-        if (C == 64) hipLaunchKernelGGL((head1x1_bwd_kernel<64, float>), dim3(nb), dim3(256), 0, st, (const float *)x, w, dlogits, dl_scale, (float *)dz, scratch, B, H * W);
-        else hipLaunchKernelGGL((head1x1_bwd_kernel<32, float>), dim3(nb), dim3(256), 0, st, (const float *)x, w, dlogits, dl_scale, (float *)dz, scratch, B, H * W);
-    }
-    hipLaunchKernelGGL(head1x1_bwd_reduce_kernel, dim3(cdiv(2 * C + 2, 4)), dim3(256), 0, st, (const float *)scratch, nb, C, dw, db);
-    prof_end(st);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return profiled(PK_ELEMWISE, "head1x1_bwd", st, 8.0 * npix * C, 0.0, npix * (2.0 * es * C + 8), [&] {
+        dispatch_es_width(es, C, [&](auto t, auto c) {
+            using T = decltype(t);
+            hipLaunchKernelGGL((head1x1_bwd_kernel<c(), T>), dim3(nb), dim3(256), 0, st, (const T *)x, w, dlogits, dl_scale, (T *)dz, scratch, B, H * W);
+        });
+        hipLaunchKernelGGL(head1x1_bwd_reduce_kernel, dim3(cdiv(2 * C + 2, 4)), dim3(256), 0, st, (const float *)scratch, nb, C, dw, db);
+    });
 }
 
 int maxpool2_fwd(const void *x, void *y, int B, int H, int W, int C, int es, hipStream_t st)
 {
     ARG_CHECK(H % 2 == 0 && W % 2 == 0 && C % 4 == 0, "maxpool2: H,W must be even and C a multiple of 4");
     const size_t total = (size_t)B * (H / 2) * (W / 2) * (C / 4);
-    prof_begin(PK_ELEMWISE, "maxpool2_fwd", st, 0.0, 0.0, 4.0 * es * (double)total * 5.0);
-    if (es == 2) hipLaunchKernelGGL(maxpool2_fwd_kernel<bf16_t>, dim3(grid_for(total, 256, 65536)), dim3(256), 0, st, (const bf16_t *)x, (bf16_t *)y, B, H, W, C / 4);
-    else hipLaunchKernelGGL(maxpool2_fwd_kernel<float>, dim3(grid_for(total, 256, 65536)), dim3(256), 0, st, (const float *)x, (float *)y, B, H, W, C / 4);
-    prof_end(st);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return profiled(PK_ELEMWISE, "maxpool2_fwd", st, 0.0, 0.0, 4.0 * es * (double)total * 5.0, [&] {
+        dispatch_es(es, [&](auto t) {
+            using T = decltype(t);
+            hipLaunchKernelGGL(maxpool2_fwd_kernel<T>, dim3(grid_for(total, 256, 65536)), dim3(256), 0, st, (const T *)x, (T *)y, B, H, W, C / 4);
+        });
+    });
 }
 int maxpool2_bwd(const void *pre, const void *dy, void *dpre, int B, int H, int W, int C, int es, hipStream_t st)
 {
     ARG_CHECK(H % 2 == 0 && W % 2 == 0 && C % 4 == 0, "maxpool2: H,W must be even and C a multiple of 4");
     const size_t total = (size_t)B * (H / 2) * (W / 2) * (C / 4);
-    prof_begin(PK_ELEMWISE, "maxpool2_bwd", st, 0.0, 0.0, 4.0 * es * (double)total * 9.0);
-    if (es == 2) hipLaunchKernelGGL(maxpool2_bwd_kernel<bf16_t>, dim3(grid_for(total, 256, 65536)), dim3(256), 0, st, (const bf16_t *)pre, (const bf16_t *)dy, (bf16_t *)dpre, B, H, W, C / 4);
-    else hipLaunchKernelGGL(maxpool2_bwd_kernel<float>, dim3(grid_for(total, 256, 65536)), dim3(256), 0, st, (const float *)pre, (const float *)dy, (float *)dpre, B, H, W, C / 4);
-    prof_end(st);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return profiled(PK_ELEMWISE, "maxpool2_bwd", st, 0.0, 0.0, 4.0 * es * (double)total * 9.0, [&] {
+        dispatch_es(es, [&](auto t) {
+            using T = decltype(t);
+            hipLaunchKernelGGL(maxpool2_bwd_kernel<T>, dim3(grid_for(total, 256, 65536)), dim3(256), 0, st, (const T *)pre, (const T *)dy, (T *)dpre, B, H, W, C / 4);
+        });
+    });
 }
 
 }  // namespace unet
@@ -813,9 +768,6 @@ int maxpool2_bwd(const void *pre, const void *dy, void *dpre, int B, int H, int 
 using namespace unet;
 
 extern "C" {
-
-// element size of the activation tensors the per-op entry points take: bf16 in arithmetic mode 2, else fp32
-static int op_es() { return get_math_mode() == 2 ? 2 : 4; }
 
 int unet_conv1ch_fwd(const void *x, int B, int S, const void *w, const void *bias, int K, void *y, void *stream)
 {
@@ -854,13 +806,11 @@ int unet_bce_logits(const void *logits, const void *target, const void *weight, 
     const int nb = (int)((n + BCE_PER_BLOCK - 1) / BCE_PER_BLOCK);
     hipStream_t st = (hipStream_t)stream;
     ProfScope ps("L1.bce");
-    prof_begin(PK_ELEMWISE, "bce_logits", st, 0.0, 0.0, 4.0 * (double)n * (2 + (weight ? 1 : 0) + (dlogits ? 1 : 0)));
-    hipLaunchKernelGGL(bce_logits_kernel, dim3(nb), dim3(256), 0, st, (const float *)logits, (const float *)target, (const float *)weight,
-                       wsB, wsC, wsH, wsW, H, W, n, (float *)dlogits, grad_scale, (double *)scratch);
-    hipLaunchKernelGGL(bce_final_kernel, dim3(1), dim3(256), 0, st, (const double *)scratch, nb, n, (float *)loss_out);
-    prof_end(st);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return profiled(PK_ELEMWISE, "bce_logits", st, 0.0, 0.0, 4.0 * (double)n * (2 + (weight ? 1 : 0) + (dlogits ? 1 : 0)), [&] {
+        hipLaunchKernelGGL(bce_logits_kernel, dim3(nb), dim3(256), 0, st, (const float *)logits, (const float *)target, (const float *)weight,
+                           wsB, wsC, wsH, wsW, H, W, n, (float *)dlogits, grad_scale, (double *)scratch);
+        hipLaunchKernelGGL(bce_final_kernel, dim3(1), dim3(256), 0, st, (const double *)scratch, nb, n, (float *)loss_out);
+    });
 }
 size_t unet_bce_step_scratch_bytes(size_t npix) { return ((npix + BCE_PX_PER_BLOCK - 1) / BCE_PX_PER_BLOCK) * sizeof(double); }
 int unet_bce_step(const void *logits, long xsB, long xsC, long xsH, const void *labels_i64, const void *weight, long wsB, long wsC,
@@ -873,34 +823,29 @@ int unet_bce_step(const void *logits, long xsB, long xsC, long xsH, const void *
     hipStream_t st = (hipStream_t)stream;
     ProfScope ps("L1.bce+L2.argmax");
     // logits 8 B + label 8 B in, dlogits 8 B + mask 8 B out per pixel
-    prof_begin(PK_ELEMWISE, "bce_step", st, 24.0 * npix, 0.0, (double)npix * (16.0 + (dlogits ? 8.0 : 0.0) + (mask_i64 ? 8.0 : 0.0) + (weight ? 8.0 : 0.0)));
-    hipLaunchKernelGGL(bce_step_kernel, dim3(nb), dim3(256), 0, st, (const float *)logits, xsB, xsC, xsH, (const long long *)labels_i64,
-                       (const float *)weight, wsB, wsC, wsH, wsW, H, W, npix, (float *)dlogits, grad_scale, (long long *)mask_i64, (double *)scratch);
-    hipLaunchKernelGGL(bce_final_kernel, dim3(1), dim3(256), 0, st, (const double *)scratch, nb, 2 * npix, (float *)loss_out);
-    prof_end(st);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return profiled(PK_ELEMWISE, "bce_step", st, 24.0 * npix, 0.0,
+                    (double)npix * (16.0 + (dlogits ? 8.0 : 0.0) + (mask_i64 ? 8.0 : 0.0) + (weight ? 8.0 : 0.0)), [&] {
+        hipLaunchKernelGGL(bce_step_kernel, dim3(nb), dim3(256), 0, st, (const float *)logits, xsB, xsC, xsH, (const long long *)labels_i64,
+                           (const float *)weight, wsB, wsC, wsH, wsW, H, W, npix, (float *)dlogits, grad_scale, (long long *)mask_i64, (double *)scratch);
+        hipLaunchKernelGGL(bce_final_kernel, dim3(1), dim3(256), 0, st, (const double *)scratch, nb, 2 * npix, (float *)loss_out);
+    });
 }
 
 int unet_onehot2(const void *labels_i64, void *target, int B, int H, int W, void *stream)
 {
     hipStream_t st = (hipStream_t)stream;
     ProfScope ps("L1.onehot");
-    prof_begin(PK_ELEMWISE, "onehot2", st, 0.0, 0.0, 16.0 * (double)B * H * W);
-    hipLaunchKernelGGL(onehot2_kernel, dim3(grid_for((size_t)B * H * W)), dim3(256), 0, st, (const long long *)labels_i64, (float *)target, B, (size_t)H * W);
-    prof_end(st);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return profiled(PK_ELEMWISE, "onehot2", st, 0.0, 0.0, 16.0 * (double)B * H * W, [&] {
+        hipLaunchKernelGGL(onehot2_kernel, dim3(grid_for((size_t)B * H * W)), dim3(256), 0, st, (const long long *)labels_i64, (float *)target, B, (size_t)H * W);
+    });
 }
 int unet_argmax2(const void *logits, long batch_stride, long plane_stride, long row_stride, void *out_i64, int B, int H, int W, void *stream)
 {
     hipStream_t st = (hipStream_t)stream;
     ProfScope ps("L2.argmax");
-    prof_begin(PK_ELEMWISE, "argmax2", st, 0.0, 0.0, 16.0 * (double)B * H * W);
-    hipLaunchKernelGGL(argmax2_kernel, dim3(grid_for((size_t)B * H * W)), dim3(256), 0, st, (const float *)logits, batch_stride, plane_stride, row_stride, (long long *)out_i64, B, H, W);
-    prof_end(st);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return profiled(PK_ELEMWISE, "argmax2", st, 0.0, 0.0, 16.0 * (double)B * H * W, [&] {
+        hipLaunchKernelGGL(argmax2_kernel, dim3(grid_for((size_t)B * H * W)), dim3(256), 0, st, (const float *)logits, batch_stride, plane_stride, row_stride, (long long *)out_i64, B, H, W);
+    });
 }
 int unet_sgd_momentum(void *const *params, const void *const *grads, void *const *bufs, const size_t *numel, int n,
                       float lr, float mu, int first_step, void *stream)
@@ -922,14 +867,12 @@ int unet_sgd_momentum(void *const *params, const void *const *grads, void *const
     tb.cstart[n] = chunks;
     if (chunks == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
-    const int grid = chunks < 16384u ? (int)chunks : 16384;
+    const int grid = grid_for(chunks, 1, 16384);
     ProfScope ps("L3.sgd");
-    prof_begin(PK_ELEMWISE, "sgd_momentum", st, 4.0 * (double)total, 0.0, 4.0 * (double)total * (first_step ? 4 : 5));
-    if (vec) hipLaunchKernelGGL(sgd_momentum_kernel<true>, dim3(grid), dim3(256), 0, st, tb, lr, mu, first_step);
-    else hipLaunchKernelGGL(sgd_momentum_kernel<false>, dim3(grid), dim3(256), 0, st, tb, lr, mu, first_step);
-    prof_end(st);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return profiled(PK_ELEMWISE, "sgd_momentum", st, 4.0 * (double)total, 0.0, 4.0 * (double)total * (first_step ? 4 : 5), [&] {
+        if (vec) hipLaunchKernelGGL(sgd_momentum_kernel<true>, dim3(grid), dim3(256), 0, st, tb, lr, mu, first_step);
+        else hipLaunchKernelGGL(sgd_momentum_kernel<false>, dim3(grid), dim3(256), 0, st, tb, lr, mu, first_step);
+    });
 }
 
 }  // extern "C"

@@ -1,26 +1,28 @@
-// elem.hpp — element access shared by the HBM-bound kernels (direct.hip, multiclass.hip): 4 consecutive channels of an
-// activation tensor stored as fp32 (16 B) or bf16 (8 B, arithmetic mode 2), read / written as 4 floats, and the grid size of
-// a grid-stride launch.
+// elem.hpp — what the HBM-bound kernels (direct.hip, multiclass.hip, tile.hip, aux.hip) share:
+//   device : 4 consecutive channels of an activation tensor stored as fp32 (16 B) or bf16 (8 B, arithmetic mode 2), read /
+//            written as 4 floats; the sum of one value per thread over a 256-thread block
+//   host   : the grid size of a grid-stride launch, and the dispatch of a launch on element size, channel width and padded
+//            class count (the launch bracket, profiled(), is common.hpp's)
 #pragma once
 #include "common.hpp"
+#include <type_traits>
 
 namespace unet {
 
-typedef float float4_ __attribute__((ext_vector_type(4)));
 typedef unsigned short bf16_t;          // storage type of arithmetic mode 2: bf16 bit patterns
 
 // 4 consecutive channels of a tensor stored as T (float: 16 B, bf16: 8 B), as floats
-__device__ __forceinline__ float4_ load4(const float *p) { return *(const float4_ *)p; }
-__device__ __forceinline__ float4_ load4(const bf16_t *p)
+__device__ __forceinline__ f32x4 load4(const float *p) { return *(const f32x4 *)p; }
+__device__ __forceinline__ f32x4 load4(const bf16_t *p)
 {
     const uint2 w = *(const uint2 *)p;
-    return float4_{__builtin_bit_cast(float, w.x << 16), __builtin_bit_cast(float, w.x & 0xffff0000u),
-                   __builtin_bit_cast(float, w.y << 16), __builtin_bit_cast(float, w.y & 0xffff0000u)};
+    return f32x4{__builtin_bit_cast(float, w.x << 16), __builtin_bit_cast(float, w.x & 0xffff0000u),
+                 __builtin_bit_cast(float, w.y << 16), __builtin_bit_cast(float, w.y & 0xffff0000u)};
 }
 __device__ __forceinline__ void put1(float *p, float v) { *p = v; }
 __device__ __forceinline__ void put1(bf16_t *p, float v) { *p = __builtin_bit_cast(bf16_t, (__bf16)v); }
-__device__ __forceinline__ void store4(float *p, float4_ v) { *(float4_ *)p = v; }
-__device__ __forceinline__ void store4(bf16_t *p, float4_ v)
+__device__ __forceinline__ void store4(float *p, f32x4 v) { *(f32x4 *)p = v; }
+__device__ __forceinline__ void store4(bf16_t *p, f32x4 v)
 {
     uint2 w;
     w.x = (unsigned)__builtin_bit_cast(bf16_t, (__bf16)v[0]) | ((unsigned)__builtin_bit_cast(bf16_t, (__bf16)v[1]) << 16);
@@ -28,10 +30,49 @@ __device__ __forceinline__ void store4(bf16_t *p, float4_ v)
     *(uint2 *)p = w;
 }
 
+// Sum of one value per thread over a 256-thread block: LDS tree in the fixed order 128, 64, ... 1 (deterministic); the total is
+// valid in thread 0
+template <typename V>
+__device__ __forceinline__ V block_sum256(V v)
+{
+    __shared__ V red[256];
+    red[threadIdx.x] = v;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+        __syncthreads();
+    }
+    return red[0];
+}
 static inline int grid_for(size_t total, int per_block = 256, int cap = 8192)
 {
     size_t g = (total + per_block - 1) / per_block;
     return (int)(g < 1 ? 1 : (g > (size_t)cap ? cap : g));
+}
+
+// Launch dispatch: f is a generic lambda that receives the storage type as a value of it (es 2: bf16_t, else float), then the
+// channel width (32 or 64; the callers have checked it) and for the K-class head KP = class_pad(K) (4, 8 or 16: K = 2 runs the
+// head1x1 kernels) as std::integral_constant, so a launch function names its kernel and its arguments once
+template <class F>
+static inline void dispatch_es(int es, F f)
+{
+    if (es == 2) f(bf16_t{}); else f(float{});
+}
+template <class F>
+static inline void dispatch_es_width(int es, int width, F f)
+{
+    dispatch_es(es, [&](auto t) {
+        if (width == 64) f(t, std::integral_constant<int, 64>{}); else f(t, std::integral_constant<int, 32>{});
+    });
+}
+template <class F>
+static inline void dispatch_es_width_kp(int es, int width, int kp, F f)
+{
+    dispatch_es_width(es, width, [&](auto t, auto c) {
+        if (kp == 4) f(t, c, std::integral_constant<int, 4>{});
+        else if (kp == 8) f(t, c, std::integral_constant<int, 8>{});
+        else f(t, c, std::integral_constant<int, 16>{});
+    });
 }
 
 }  // namespace unet

@@ -50,9 +50,9 @@ __global__ __launch_bounds__(256) void headk_fwd_kernel(const T *__restrict__ x,
     constexpr int R = CG > KP ? CG / KP : 1;         // lanes that end with the same classes (the first of them writes)
     __shared__ float outs[KP][PPB];
     const int cg = threadIdx.x % CG, pl = threadIdx.x / CG;
-    float4_ wr[KP];
+    f32x4 wr[KP];
 #pragma unroll
-    for (int k = 0; k < KP; ++k) wr[k] = k < K ? *(const float4_ *)(w + k * C + cg * 4) : float4_{0.f, 0.f, 0.f, 0.f};
+    for (int k = 0; k < KP; ++k) wr[k] = k < K ? *(const f32x4 *)(w + k * C + cg * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
     int cb = 0;
     {
         int n = KP;
@@ -69,7 +69,7 @@ __global__ __launch_bounds__(256) void headk_fwd_kernel(const T *__restrict__ x,
         const int lp = ps * PPP + pl;
         const size_t pix = base + lp;
         float s[KP];
-        float4_ v = {0.f, 0.f, 0.f, 0.f};
+        f32x4 v = {0.f, 0.f, 0.f, 0.f};
         if (pix < npix) v = load4(x + pix * C + cg * 4);
 #pragma unroll
         for (int k = 0; k < KP; ++k) s[k] = v[0] * wr[k][0] + v[1] * wr[k][1] + v[2] * wr[k][2] + v[3] * wr[k][3];
@@ -103,12 +103,12 @@ __global__ __launch_bounds__(256) void headk_bwd_kernel(const T *__restrict__ x,
     constexpr int CG = C / 4, PPP = 256 / CG, PASSES = HK_PPB / PPP;
     __shared__ __attribute__((aligned(16))) float dsh[KP][HK_PPB];
     const int cg = threadIdx.x % CG, pl = threadIdx.x / CG;
-    float4_ wr[KP], a[KP];
+    f32x4 wr[KP], a[KP];
     float sb[KP];
 #pragma unroll
     for (int k = 0; k < KP; ++k) {
-        wr[k] = k < K ? *(const float4_ *)(w + k * C + cg * 4) : float4_{0.f, 0.f, 0.f, 0.f};
-        a[k] = float4_{0.f, 0.f, 0.f, 0.f};
+        wr[k] = k < K ? *(const f32x4 *)(w + k * C + cg * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
+        a[k] = f32x4{0.f, 0.f, 0.f, 0.f};
         sb[k] = 0.f;
     }
     const size_t npix = (size_t)B * HW;
@@ -130,11 +130,11 @@ __global__ __launch_bounds__(256) void headk_bwd_kernel(const T *__restrict__ x,
             const int lp = ps * PPP + pl;
             const size_t pix = base + lp;
             if (pix >= npix) break;
-            const float4_ v = load4(x + pix * C + cg * 4);
+            const f32x4 v = load4(x + pix * C + cg * 4);
             float d[KP];
 #pragma unroll
             for (int k = 0; k < KP; ++k) d[k] = dsh[k][lp];
-            float4_ g;
+            f32x4 g;
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
                 float s = d[0] * wr[0][c];
@@ -168,7 +168,7 @@ __global__ __launch_bounds__(256) void headk_bwd_kernel(const T *__restrict__ x,
     const int wave = threadIdx.x >> 6;
     if ((threadIdx.x & 63) < CG) {
 #pragma unroll
-        for (int k = 0; k < KP; ++k) *(float4_ *)&red[wave][k * C + cg * 4] = a[k];
+        for (int k = 0; k < KP; ++k) *(f32x4 *)&red[wave][k * C + cg * 4] = a[k];
         if (cg == 0) {
 #pragma unroll
             for (int k = 0; k < KP; ++k) red[wave][KP * C + k] = sb[k];
@@ -336,22 +336,6 @@ __global__ __launch_bounds__(256) void eval_confusion_kernel(const float *__rest
     if (threadIdx.x == 0 && hist[KP * KP]) atomicAdd(&invalid[b], (unsigned long long)hist[KP * KP]);
 }
 
-// the head kernels at KP >= 4 (K = 2 is direct.hip's head1x1)
-#define HEAD_DISPATCH(K, C, es, KERN, ...)                                                                                    \
-    do {                                                                                                                     \
-        const int kp_ = class_pad(K);                                                                                           \
-        if (es == 2) {                                                                                                       \
-            if (C == 64) { if (kp_ == 4) LAUNCH_HK(KERN, 64, 4, bf16_t, __VA_ARGS__); else if (kp_ == 8) LAUNCH_HK(KERN, 64, 8, bf16_t, __VA_ARGS__); else LAUNCH_HK(KERN, 64, 16, bf16_t, __VA_ARGS__); } \
-            else         { if (kp_ == 4) LAUNCH_HK(KERN, 32, 4, bf16_t, __VA_ARGS__); else if (kp_ == 8) LAUNCH_HK(KERN, 32, 8, bf16_t, __VA_ARGS__); else LAUNCH_HK(KERN, 32, 16, bf16_t, __VA_ARGS__); } \
-        } else {                                                                                                             \
-            if (C == 64) { if (kp_ == 4) LAUNCH_HK(KERN, 64, 4, float, __VA_ARGS__); else if (kp_ == 8) LAUNCH_HK(KERN, 64, 8, float, __VA_ARGS__); else LAUNCH_HK(KERN, 64, 16, float, __VA_ARGS__); } \
-            else         { if (kp_ == 4) LAUNCH_HK(KERN, 32, 4, float, __VA_ARGS__); else if (kp_ == 8) LAUNCH_HK(KERN, 32, 8, float, __VA_ARGS__); else LAUNCH_HK(KERN, 32, 16, float, __VA_ARGS__); } \
-        }                                                                                                                    \
-    } while (0)
-
-// one launch of KERN<C_, KP_, TT>; the launch arguments may name the activation type as T_
-#define LAUNCH_HK(KERN, C_, KP_, TT, ...) do { typedef TT T_; hipLaunchKernelGGL((KERN<C_, KP_, T_>), __VA_ARGS__); } while (0)
-
 }  // namespace mc
 
 // one block per HK_PPB-pixel chunk up to 4096 blocks (a 572^2 batch of 8 is 2353 chunks: no block takes two)
@@ -372,11 +356,12 @@ int headk_fwd(const void *x, int B, int H, int W, int C, int K, const float *w, 
     const size_t npix = (size_t)B * H * W;
     const int ppb = (256 / (C / 4)) * 16;
     const int grid = (int)((npix + ppb - 1) / ppb);
-    prof_begin(PK_ELEMWISE, "head1xk_fwd", st, 2.0 * npix * C * K, 0.0, (double)npix * (es * C + 4 * K));
-    HEAD_DISPATCH(K, C, es, headk_fwd_kernel, dim3(grid), dim3(256), 0, st, (const T_ *)x, w, bias, logits, K, B, H * W);
-    prof_end(st);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return profiled(PK_ELEMWISE, "head1xk_fwd", st, 2.0 * npix * C * K, 0.0, (double)npix * (es * C + 4 * K), [&] {
+        dispatch_es_width_kp(es, C, class_pad(K), [&](auto t, auto c, auto kp) {
+            using T = decltype(t);
+            hipLaunchKernelGGL((headk_fwd_kernel<c(), kp(), T>), dim3(grid), dim3(256), 0, st, (const T *)x, w, bias, logits, K, B, H * W);
+        });
+    });
 }
 
 int headk_bwd(const void *x, int B, int H, int W, int C, int K, const float *w, const float *dlogits, float dl_scale, void *dz, float *dw,
@@ -388,15 +373,14 @@ int headk_bwd(const void *x, int B, int H, int W, int C, int K, const float *w, 
     using namespace mc;
     const int nb = headk_bwd_blocks(B, H, W);
     const double npix = (double)B * H * W;
-    prof_begin(PK_ELEMWISE, "head1xk_bwd", st, 4.0 * npix * C * K, 0.0, npix * (2.0 * es * C + 4 * K));
-    HEAD_DISPATCH(K, C, es, headk_bwd_kernel, dim3(nb), dim3(256), 0, st, (const T_ *)x, w, dlogits, dl_scale, (T_ *)dz, scratch, K, B, H * W);
-    hipLaunchKernelGGL(headk_bwd_reduce_kernel, dim3(cdiv(K * C + K, 4)), dim3(256), 0, st, (const float *)scratch, nb, K, C, dw, db);
-    prof_end(st);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return profiled(PK_ELEMWISE, "head1xk_bwd", st, 4.0 * npix * C * K, 0.0, npix * (2.0 * es * C + 4 * K), [&] {
+        dispatch_es_width_kp(es, C, class_pad(K), [&](auto t, auto c, auto kp) {
+            using T = decltype(t);
+            hipLaunchKernelGGL((headk_bwd_kernel<c(), kp(), T>), dim3(nb), dim3(256), 0, st, (const T *)x, w, dlogits, dl_scale, (T *)dz, scratch, K, B, H * W);
+        });
+        hipLaunchKernelGGL(headk_bwd_reduce_kernel, dim3(cdiv(K * C + K, 4)), dim3(256), 0, st, (const float *)scratch, nb, K, C, dw, db);
+    });
 }
-#undef HEAD_DISPATCH
-#undef LAUNCH_HK
 
 }  // namespace unet
 
@@ -405,13 +389,10 @@ using namespace unet::mc;
 
 extern "C" {
 
-// element size of the activation tensors the per-op entry points take: bf16 in arithmetic mode 2, else fp32
-static int op_es_k() { return get_math_mode() == 2 ? 2 : 4; }
-
 int unet_head1xk_fwd(const void *x, int B, int H, int W, int C, int K, const void *w, const void *bias, void *logits, void *stream)
 {
     ARG_CHECK(x && w && bias && logits && B > 0 && H > 0 && W > 0, "unet_head1xk_fwd: bad argument");
-    return headk_fwd(x, B, H, W, C, K, (const float *)w, (const float *)bias, (float *)logits, op_es_k(), (hipStream_t)stream);
+    return headk_fwd(x, B, H, W, C, K, (const float *)w, (const float *)bias, (float *)logits, op_es(), (hipStream_t)stream);
 }
 size_t unet_head1xk_bwd_scratch_bytes(int B, int H, int W, int C, int K) { return headk_bwd_scratch_bytes(B, H, W, C, K); }
 int unet_head1xk_bwd(const void *x, int B, int H, int W, int C, int K, const void *w, const void *dlogits, void *dz, void *dw, void *db,
@@ -419,7 +400,7 @@ int unet_head1xk_bwd(const void *x, int B, int H, int W, int C, int K, const voi
 {
     ARG_CHECK(x && w && dlogits && dz && scratch && B > 0 && H > 0 && W > 0, "unet_head1xk_bwd: bad argument");
     return headk_bwd(x, B, H, W, C, K, (const float *)w, (const float *)dlogits, 1.0f, dz, (float *)dw, (float *)db, (float *)scratch,
-                     op_es_k(), (hipStream_t)stream);
+                     op_es(), (hipStream_t)stream);
 }
 
 size_t unet_softmax_ce_scratch_bytes(size_t npix) { return ((npix + CE_PX_PER_BLOCK - 1) / CE_PX_PER_BLOCK) * 2 * sizeof(double); }
@@ -437,16 +418,14 @@ int unet_softmax_ce_step(const void *logits, long xsB, long xsC, long xsH, int K
     unsigned long long *bad = (unsigned long long *)(part + nb);
     ProfScope ps("L1.softmax_ce+L2.argmax");
     // K logits + label (+ weight) in, K dlogits + mask out per pixel
-    prof_begin(PK_ELEMWISE, "softmax_ce_step", st, 8.0 * K * npix, 0.0,
-               (double)npix * (4.0 * K + 8.0 + (dlogits ? 4.0 * K : 0.0) + (mask_i64 ? 8.0 : 0.0) + (weight ? 4.0 : 0.0)));
-    CLASS_DISPATCH(K, hipLaunchKernelGGL(softmax_ce_kernel<KP_>, dim3(nb), dim3(256), 0, st, (const float *)logits, xsB, xsC, xsH,
-                                      (const long long *)labels_i64, (const float *)weight, wsB, wsH, wsW, K, H, W, npix, (float *)dlogits,
-                                      grad_scale, (long long *)mask_i64, part, bad));
-    hipLaunchKernelGGL(softmax_ce_final_kernel, dim3(1), dim3(256), 0, st, (const double *)part, (const unsigned long long *)bad, nb, npix,
-                       (float *)loss_out, (unsigned long long *)invalid_u64);
-    prof_end(st);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return profiled(PK_ELEMWISE, "softmax_ce_step", st, 8.0 * K * npix, 0.0,
+                    (double)npix * (4.0 * K + 8.0 + (dlogits ? 4.0 * K : 0.0) + (mask_i64 ? 8.0 : 0.0) + (weight ? 4.0 : 0.0)), [&] {
+        CLASS_DISPATCH(K, hipLaunchKernelGGL(softmax_ce_kernel<KP_>, dim3(nb), dim3(256), 0, st, (const float *)logits, xsB, xsC, xsH,
+                                          (const long long *)labels_i64, (const float *)weight, wsB, wsH, wsW, K, H, W, npix,
+                                          (float *)dlogits, grad_scale, (long long *)mask_i64, part, bad));
+        hipLaunchKernelGGL(softmax_ce_final_kernel, dim3(1), dim3(256), 0, st, (const double *)part, (const unsigned long long *)bad, nb, npix,
+                           (float *)loss_out, (unsigned long long *)invalid_u64);
+    });
 }
 
 int unet_argmaxk(const void *logits, long batch_stride, long plane_stride, long row_stride, int K, void *out_i64, int B, int H, int W,
@@ -457,12 +436,10 @@ int unet_argmaxk(const void *logits, long batch_stride, long plane_stride, long 
     hipStream_t st = (hipStream_t)stream;
     const size_t total = (size_t)B * H * W;
     ProfScope ps("L2.argmax");
-    prof_begin(PK_ELEMWISE, "argmaxk", st, 0.0, 0.0, (4.0 * K + 8.0) * (double)total);
-    CLASS_DISPATCH(K, hipLaunchKernelGGL(argmaxk_kernel<KP_>, dim3(grid_for(total)), dim3(256), 0, st, (const float *)logits, batch_stride,
-                                      plane_stride, row_stride, K, (long long *)out_i64, H, W, total));
-    prof_end(st);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return profiled(PK_ELEMWISE, "argmaxk", st, 0.0, 0.0, (4.0 * K + 8.0) * (double)total, [&] {
+        CLASS_DISPATCH(K, hipLaunchKernelGGL(argmaxk_kernel<KP_>, dim3(grid_for(total)), dim3(256), 0, st, (const float *)logits, batch_stride,
+                                          plane_stride, row_stride, K, (long long *)out_i64, H, W, total));
+    });
 }
 
 int unet_eval_confusion(const void *logits, long batch_stride, long plane_stride, long row_stride, int pad, int K, const void *labels_i64,

@@ -6,6 +6,7 @@
 // (oy0, ox0) <= 0.  Tile t = (b*ny + i)*nx + j reads rows [oy0 + i*So - m, +S), columns [ox0 + j*So - m, +S) and covers
 // output rows [oy0 + i*So, +So), columns [ox0 + j*So, +So), clipped to the image; the output rectangles partition it.
 #include "common.hpp"
+#include "elem.hpp"
 #include "../../include/unet_hip.h"
 
 namespace unet {
@@ -160,12 +161,6 @@ __global__ __launch_bounds__(256) void tile_stitch_k_kernel(const float *__restr
     }
 }
 
-static inline int tile_grid1(size_t total, int cap = 16384)
-{
-    size_t g = (total + 255) / 256;
-    return (int)(g < 1 ? 1 : (g > (size_t)cap ? cap : g));
-}
-
 // checks shared by both entry points: the grid covers the image and is centred as tester.tile_grid makes it
 static int check_tile_grid(const char *who, int B, int H, int W, int So, int oy0, int ox0, int ny, int nx, long long t0, int nt)
 {
@@ -196,16 +191,15 @@ int unet_tile_gather(const void *img, int B, int H, int W, const void *minmax, i
     hipStream_t st = (hipStream_t)stream;
     const size_t quads = (size_t)nt * S * (S / 4);
     ProfScope ps("N2.tile_gather");
-    prof_begin(PK_ELEMWISE, "tile_gather", st, 0.0, 0.0, 8.0 * quads * 4);
-    if (((uintptr_t)tiles_out & 15) == 0)
-        hipLaunchKernelGGL(tile_gather_kernel<true>, dim3(tile_grid1(quads)), dim3(256), 0, st, (const float *)img, H, W, (const float *)minmax,
-                           S, oy0, ox0, ny, nx, (long long)t0, (float *)tiles_out, quads);
-    else
-        hipLaunchKernelGGL(tile_gather_kernel<false>, dim3(tile_grid1(quads)), dim3(256), 0, st, (const float *)img, H, W, (const float *)minmax,
-                           S, oy0, ox0, ny, nx, (long long)t0, (float *)tiles_out, quads);
-    prof_end(st);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    const int grid = grid_for(quads, 256, 16384);
+    return profiled(PK_ELEMWISE, "tile_gather", st, 0.0, 0.0, 8.0 * quads * 4, [&] {
+        if (((uintptr_t)tiles_out & 15) == 0)
+            hipLaunchKernelGGL(tile_gather_kernel<true>, dim3(grid), dim3(256), 0, st, (const float *)img, H, W, (const float *)minmax,
+                               S, oy0, ox0, ny, nx, (long long)t0, (float *)tiles_out, quads);
+        else
+            hipLaunchKernelGGL(tile_gather_kernel<false>, dim3(grid), dim3(256), 0, st, (const float *)img, H, W, (const float *)minmax,
+                               S, oy0, ox0, ny, nx, (long long)t0, (float *)tiles_out, quads);
+    });
 }
 
 int unet_tile_stitch(const void *logits, int So, int oy0, int ox0, int ny, int nx, long t0, int nt, int B, int H, int W, void *mask_i64,
@@ -217,16 +211,15 @@ int unet_tile_stitch(const void *logits, int So, int oy0, int ox0, int ny, int n
     hipStream_t st = (hipStream_t)stream;
     const size_t quads = (size_t)nt * So * (So / 4);
     ProfScope ps("N2.tile_stitch");
-    prof_begin(PK_ELEMWISE, "tile_stitch", st, 0.0, 0.0, (8.0 + 8.0 + (prob_f32 ? 4.0 : 0.0)) * quads * 4);
-    if (((uintptr_t)logits & 15) == 0)
-        hipLaunchKernelGGL(tile_stitch_kernel<true>, dim3(tile_grid1(quads)), dim3(256), 0, st, (const float *)logits, So, oy0, ox0, ny, nx,
-                           (long long)t0, H, W, (long long *)mask_i64, (float *)prob_f32, quads);
-    else
-        hipLaunchKernelGGL(tile_stitch_kernel<false>, dim3(tile_grid1(quads)), dim3(256), 0, st, (const float *)logits, So, oy0, ox0, ny, nx,
-                           (long long)t0, H, W, (long long *)mask_i64, (float *)prob_f32, quads);
-    prof_end(st);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    const int grid = grid_for(quads, 256, 16384);
+    return profiled(PK_ELEMWISE, "tile_stitch", st, 0.0, 0.0, (8.0 + 8.0 + (prob_f32 ? 4.0 : 0.0)) * quads * 4, [&] {
+        if (((uintptr_t)logits & 15) == 0)
+            hipLaunchKernelGGL(tile_stitch_kernel<true>, dim3(grid), dim3(256), 0, st, (const float *)logits, So, oy0, ox0, ny, nx,
+                               (long long)t0, H, W, (long long *)mask_i64, (float *)prob_f32, quads);
+        else
+            hipLaunchKernelGGL(tile_stitch_kernel<false>, dim3(grid), dim3(256), 0, st, (const float *)logits, So, oy0, ox0, ny, nx,
+                               (long long)t0, H, W, (long long *)mask_i64, (float *)prob_f32, quads);
+    });
 }
 
 int unet_tile_stitch_k(const void *logits, int So, int K, int oy0, int ox0, int ny, int nx, long t0, int nt, int B, int H, int W,
@@ -240,12 +233,10 @@ int unet_tile_stitch_k(const void *logits, int So, int K, int oy0, int ox0, int 
     hipStream_t st = (hipStream_t)stream;
     const size_t quads = (size_t)nt * So * (So / 4);
     ProfScope ps("N2.tile_stitch");
-    prof_begin(PK_ELEMWISE, "tile_stitch_k", st, 0.0, 0.0, (4.0 * K + 8.0 + (prob_f32 ? 4.0 * K : 0.0)) * quads * 4);
-    CLASS_DISPATCH(K, hipLaunchKernelGGL(tile_stitch_k_kernel<KP_>, dim3(tile_grid1(quads)), dim3(256), 0, st, (const float *)logits, So,
-                                         K, oy0, ox0, ny, nx, (long long)t0, B, H, W, (long long *)mask_i64, (float *)prob_f32, quads));
-    prof_end(st);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return profiled(PK_ELEMWISE, "tile_stitch_k", st, 0.0, 0.0, (4.0 * K + 8.0 + (prob_f32 ? 4.0 * K : 0.0)) * quads * 4, [&] {
+        CLASS_DISPATCH(K, hipLaunchKernelGGL(tile_stitch_k_kernel<KP_>, dim3(grid_for(quads, 256, 16384)), dim3(256), 0, st, (const float *)logits,
+                                             So, K, oy0, ox0, ny, nx, (long long)t0, B, H, W, (long long *)mask_i64, (float *)prob_f32, quads));
+    });
 }
 
 }  // extern "C"

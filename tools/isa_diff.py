@@ -2,7 +2,7 @@
 """Compare the gfx950 device code of two source trees, kernel by kernel (the check of a kernel refactor that must not
 change code: run it on a CPU-only machine, hipcc cross-compiles).
 
-    tools/isa_diff.py PARENT/dl-unet_amd/csrc NEW/dl-unet_amd/csrc [FILE.hip ...]     (default: the six MFMA files)
+    tools/isa_diff.py PARENT/dl-unet_amd/csrc NEW/dl-unet_amd/csrc [FILE.hip ...]     (default: every *.hip of PARENT)
 
 Each file of both trees is compiled with  hipcc -O3 -std=c++17 --offload-arch=gfx950 --cuda-device-only -S;  comments,
 .file / .ident / .loc / .cfi lines and the __hip_cuid_* symbol are dropped, a kernel's own symbol and the function
@@ -21,7 +21,7 @@ import sys
 import tempfile
 from concurrent.futures import ThreadPoolExecutor
 
-FILES = ["igemm.hip", "igemmx.hip", "igemmb.hip", "wino.hip", "wgrad.hip", "wgradw.hip"]
+FILES = ["igemm.hip", "igemmx.hip", "igemmb.hip", "wino.hip", "wgrad.hip", "wgradw.hip"]     # if PARENT lists no *.hip
 META_KEYS = (".agpr_count", ".vgpr_count", ".sgpr_count", ".vgpr_spill_count", ".sgpr_spill_count", ".group_segment_fixed_size",
              ".private_segment_fixed_size", ".kernarg_segment_size", ".max_flat_workgroup_size", ".uses_dynamic_stack")
 DROP = re.compile(r"^\s*(;|\.file\b|\.ident\b|\.loc\b|\.cfi_|\.p2align\b|\.section\b|\.text\b|\.protected\b|\.globl\b|\.weak\b|\.size\b|\.set\b)")
@@ -78,11 +78,12 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("parent")
     ap.add_argument("new")
-    ap.add_argument("files", nargs="*", default=FILES)
+    ap.add_argument("files", nargs="*")
     ap.add_argument("-v", action="store_true", help="print the differing lines")
     ap.add_argument("--allow", default=None, metavar="REGEX", help="demangled kernel names that may differ")
     ap.add_argument("--hipcc", default=os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"))
     a = ap.parse_args()
+    a.files = a.files or sorted(f for f in os.listdir(a.parent) if f.endswith(".hip")) or FILES
     demangle = lambda s: subprocess.run(["c++filt", s], capture_output=True, text=True).stdout.strip() or s
     bad = 0
     with tempfile.TemporaryDirectory() as tmp, ThreadPoolExecutor(max_workers=min(12, os.cpu_count() or 1)) as ex:
