@@ -127,14 +127,17 @@ def test_base32_net_trains(dev):
     L = _hip.lib()
     h = network._handle(0, base)
     plist = [p.detach() for p in net._params()]
+    import guarded as gd
+    mem = gd.Arena(dev)                                     # poisoned, guarded, exact buffers (tests/guarded.py)
     nbytes = h.workspace_bytes(B, S, True)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    logits = torch.empty(B, 2, S - 184, S - 184, device=dev)
+    ws = mem.scratch(nbytes, "workspace")
+    logits = mem.out((B, 2, S - 184, S - 184), torch.float32, "logits")
     ptab = _hip.ptr_table(plist)
     _hip.check(L.unet_forward(h.h, ptab, _hip.ptr(torch.from_numpy(x).to(dev)), _hip.ptr(logits), B, S, _hip.ptr(ws), nbytes, 1, _hip.stream()), "fwd")
-    grads = [torch.empty_like(p) for p in plist]
+    grads = [mem.out(p.shape, torch.float32, "grad %d" % i) for i, p in enumerate(plist)]
     _hip.check(L.unet_backward(h.h, ptab, _hip.ptr(torch.from_numpy(dl).to(dev)), _hip.ptr_table(grads), _hip.ptr(ws), nbytes, _hip.stream()), "bwd")
     torch.cuda.synchronize()
+    mem.verify(logits, *grads)
     masks, sels = parity.branch_of(h, ws, B, S)
     p64 = {k: v.astype(np.float64) for k, v in params.items()}
     ref_logits, ref_grads = oracle_c.unet_fwd_bwd(p64, x.astype(np.float64), base=base, dlogits=dl.astype(np.float64), relu_masks=masks, pool_sel=sels)

@@ -9,6 +9,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import guarded as gd
 import kernel_paths as kp
 
 pytestmark = pytest.mark.gpu
@@ -46,14 +47,7 @@ def nchw(t):
     return t.permute(0, 3, 1, 2).double().cpu()
 
 
-class Keep(list):
-    def __call__(self, t):
-        self.append(t)
-        return t
-
-
-def scratch(nbytes):
-    return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device="cuda")
+# (every buffer handed to the library comes from a guarded.Arena: tests/guarded.py)
 
 
 def rnd(*shape, seed=0, scale=1.0):
@@ -69,14 +63,15 @@ def rnd(*shape, seed=0, scale=1.0):
                                      # tile and an image boundary, an odd number of bands, a ragged last tile over three images, wide rows
                                      (2, 21, 128, 128), (1, 23, 192, 128), (3, 40, 128, 256), (1, 150, 256, 128), (2, 20, 128, 128)])
 def test_conv3x3_fwd_bf16(hip, B, H, C, K):
-    keep = Keep()
+    mem = gd.Arena()
     x = bf(rnd(B, C, H, H, seed=1)); w = bf(rnd(K, C, 3, 3, seed=2, scale=0.05)); b = rnd(K, seed=3).float().double()
     ref = F.relu(F.conv2d(x, w, b))
-    y = torch.empty(B, H - 2, H - 2, K, device="cuda", dtype=torch.bfloat16)
-    sc = scratch(hip.lib().unet_conv3x3_scratch_bytes(C, K))
+    y = mem.out((B, H - 2, H - 2, K), torch.bfloat16, "y")
+    sc = mem.scratch(hip.lib().unet_conv3x3_scratch_bytes(C, K))
     with kp.record() as rec:
-        hip.check(hip.lib().unet_conv3x3_fwd(hip.ptr(keep(nhwc16(x))), H, H, C, 0, None, 0, B, H, H, hip.ptr(keep(w.float().cuda())),
-                                             hip.ptr(keep(b.float().cuda())), K, 1, hip.ptr(y), hip.ptr(sc), hip.stream()), "conv3x3_fwd")
+        hip.check(hip.lib().unet_conv3x3_fwd(hip.ptr(mem.inp(nhwc16(x))), H, H, C, 0, None, 0, B, H, H, hip.ptr(mem.inp(w.float().cuda())),
+                                             hip.ptr(mem.inp(b.float().cuda())), K, 1, hip.ptr(y), mem.ptr(sc), hip.stream()), "conv3x3_fwd")
+    mem.verify(y)
     assert nerr(nchw(y), ref) < TOL_BF16
     assert rec.main_families() == [kp.bf16_conv_family(H - 2, K, [C], False)], rec
 
@@ -84,17 +79,18 @@ def test_conv3x3_fwd_bf16(hip, B, H, C, K):
 @pytest.mark.parametrize("B,Hs,pad,C1,C2,K", [(2, 8, 6, 64, 64, 64), (1, 10, 3, 128, 128, 128), (1, 24, 4, 64, 64, 64), (2, 30, -3, 64, 64, 128),
                                               (2, 20, 4, 128, 128, 128), (1, 40, -5, 128, 64, 256)])
 def test_conv3x3_fwd_virtual_concat_bf16(hip, B, Hs, pad, C1, C2, K):
-    keep = Keep()
+    mem = gd.Arena()
     H = Hs + 2 * pad
     a = bf(rnd(B, C1, Hs, Hs, seed=1)); u = bf(rnd(B, C2, H, H, seed=2))
     w = bf(rnd(K, C1 + C2, 3, 3, seed=3, scale=0.05)); b = rnd(K, seed=4).float().double()
     ref = F.relu(F.conv2d(torch.cat((F.pad(a, (pad,) * 4), u), 1), w, b))
-    y = torch.empty(B, H - 2, H - 2, K, device="cuda", dtype=torch.bfloat16)
-    sc = scratch(hip.lib().unet_conv3x3_scratch_bytes(C1 + C2, K))
+    y = mem.out((B, H - 2, H - 2, K), torch.bfloat16, "y")
+    sc = mem.scratch(hip.lib().unet_conv3x3_scratch_bytes(C1 + C2, K))
     with kp.record() as rec:
-        hip.check(hip.lib().unet_conv3x3_fwd(hip.ptr(keep(nhwc16(a))), Hs, Hs, C1, pad, hip.ptr(keep(nhwc16(u))), C2, B, H, H,
-                                             hip.ptr(keep(w.float().cuda())), hip.ptr(keep(b.float().cuda())), K, 1, hip.ptr(y), hip.ptr(sc),
+        hip.check(hip.lib().unet_conv3x3_fwd(hip.ptr(mem.inp(nhwc16(a))), Hs, Hs, C1, pad, hip.ptr(mem.inp(nhwc16(u))), C2, B, H, H,
+                                             hip.ptr(mem.inp(w.float().cuda())), hip.ptr(mem.inp(b.float().cuda())), K, 1, hip.ptr(y), mem.ptr(sc),
                                              hip.stream()), "conv3x3_fwd concat")
+    mem.verify(y)
     assert nerr(nchw(y), ref) < TOL_BF16
     assert rec.main_families() == kp.concat_fwd_families(2, 1, Hs, pad, C1, C2, K), rec      # one launch: no split forward in bf16
 
@@ -107,7 +103,7 @@ def test_conv3x3_fwd_virtual_concat_bf16(hip, B, Hs, pad, C1, C2, K):
                                                       (2, 23, 128, 128, True, True), (1, 30, 256, 192, False, False), (3, 27, 128, 128, True, False),
                                                       (2, 19, 128, 128, False, True)])
 def test_conv3x3_bwd_bf16(hip, B, H, C, K, use_mask, use_add):
-    keep = Keep()
+    mem = gd.Arena()
     x = bf(rnd(B, C, H, H, seed=1)).requires_grad_(True)
     w = bf(rnd(K, C, 3, 3, seed=2, scale=0.05)).requires_grad_(True)
     dz = bf(rnd(B, K, H - 2, H - 2, seed=3))
@@ -119,14 +115,15 @@ def test_conv3x3_bwd_bf16(hip, B, H, C, K, use_mask, use_add):
         dx_ref = dx_ref + add
     if mask is not None:
         dx_ref = dx_ref * (mask > 0)
-    dx = torch.empty(B, H, H, C, device="cuda", dtype=torch.bfloat16)
-    dw = torch.empty(K, C, 3, 3, device="cuda"); db = torch.empty(K, device="cuda")
-    sc = scratch(hip.lib().unet_conv3x3_bwd_scratch_bytes(B, H, H, C, K))
+    dx = mem.out((B, H, H, C), torch.bfloat16, "dx")
+    dw = mem.out((K, C, 3, 3), torch.float32, "dw"); db = mem.out((K,), torch.float32, "db")
+    sc = mem.scratch(hip.lib().unet_conv3x3_bwd_scratch_bytes(B, H, H, C, K))
     with kp.record() as rec:
-        hip.check(hip.lib().unet_conv3x3_bwd(hip.ptr(keep(nhwc16(x.detach()))), H, H, C, 0, None, 0, B, H, H, hip.ptr(keep(w.detach().float().cuda())), K,
-                                             hip.ptr(keep(nhwc16(dz))), hip.ptr(dx), hip.ptr(keep(nhwc16(mask))) if use_mask else None,
-                                             hip.ptr(keep(nhwc16(add))) if use_add else None, None, None, hip.ptr(dw), hip.ptr(db),
-                                             hip.ptr(sc), hip.stream()), "conv3x3_bwd")
+        hip.check(hip.lib().unet_conv3x3_bwd(hip.ptr(mem.inp(nhwc16(x.detach()))), H, H, C, 0, None, 0, B, H, H, hip.ptr(mem.inp(w.detach().float().cuda())), K,
+                                             hip.ptr(mem.inp(nhwc16(dz))), hip.ptr(dx), hip.ptr(mem.inp(nhwc16(mask))) if use_mask else None,
+                                             hip.ptr(mem.inp(nhwc16(add))) if use_add else None, None, None, hip.ptr(dw), hip.ptr(db),
+                                             mem.ptr(sc), hip.stream()), "conv3x3_bwd")
+    mem.verify(dx, dw, db)
     assert rec.main_families()[:2] == [kp.bf16_conv_family(H, C, [K], True), "wgradb<3;3;1>"], rec
     assert nerr(nchw(dx), dx_ref) < TOL_BF16
     assert nerr(dw, w.grad) < TOL_F32                    # fp32 result of exact bf16 products: only the summation order differs
@@ -136,19 +133,20 @@ def test_conv3x3_bwd_bf16(hip, B, H, C, K, use_mask, use_add):
 @pytest.mark.parametrize("B,Hs,pad,C,K", [(2, 8, 6, 64, 64), (1, 12, 3, 128, 128), (1, 24, 4, 64, 64), (2, 30, -3, 64, 128),
                                           (1, 20, 4, 128, 128), (2, 34, -4, 128, 128)])
 def test_conv3x3_bwd_virtual_concat_bf16(hip, B, Hs, pad, C, K):
-    keep = Keep()
+    mem = gd.Arena()
     H = Hs + 2 * pad
     a = bf(rnd(B, C, Hs, Hs, seed=1)).requires_grad_(True); u = bf(rnd(B, C, H, H, seed=2)).requires_grad_(True)
     w = bf(rnd(K, 2 * C, 3, 3, seed=3, scale=0.05)).requires_grad_(True)
     dz = bf(rnd(B, K, H - 2, H - 2, seed=4))
     F.conv2d(torch.cat((F.pad(a, (pad,) * 4), u), 1), w).backward(dz)
-    dx1 = torch.empty(B, Hs, Hs, C, device="cuda", dtype=torch.bfloat16); dx2 = torch.empty(B, H, H, C, device="cuda", dtype=torch.bfloat16)
-    dw = torch.empty(K, 2 * C, 3, 3, device="cuda"); db = torch.empty(K, device="cuda")
-    sc = scratch(hip.lib().unet_conv3x3_bwd_scratch_bytes(B, H, H, 2 * C, K))
+    dx1 = mem.out((B, Hs, Hs, C), torch.bfloat16, "dx1"); dx2 = mem.out((B, H, H, C), torch.bfloat16, "dx2")
+    dw = mem.out((K, 2 * C, 3, 3), torch.float32, "dw"); db = mem.out((K,), torch.float32, "db")
+    sc = mem.scratch(hip.lib().unet_conv3x3_bwd_scratch_bytes(B, H, H, 2 * C, K))
     with kp.record() as rec:
-        hip.check(hip.lib().unet_conv3x3_bwd(hip.ptr(keep(nhwc16(a.detach()))), Hs, Hs, C, pad, hip.ptr(keep(nhwc16(u.detach()))), C, B, H, H,
-                                             hip.ptr(keep(w.detach().float().cuda())), K, hip.ptr(keep(nhwc16(dz))), hip.ptr(dx1), None, None,
-                                             hip.ptr(dx2), None, hip.ptr(dw), hip.ptr(db), hip.ptr(sc), hip.stream()), "conv3x3_bwd concat")
+        hip.check(hip.lib().unet_conv3x3_bwd(hip.ptr(mem.inp(nhwc16(a.detach()))), Hs, Hs, C, pad, hip.ptr(mem.inp(nhwc16(u.detach()))), C, B, H, H,
+                                             hip.ptr(mem.inp(w.detach().float().cuda())), K, hip.ptr(mem.inp(nhwc16(dz))), hip.ptr(dx1), None, None,
+                                             hip.ptr(dx2), None, hip.ptr(dw), hip.ptr(db), mem.ptr(sc), hip.stream()), "conv3x3_bwd concat")
+    mem.verify(dx1, dx2, dw, db)
     assert rec.main_families(reduces=False) == kp.concat_bwd_families(2, 1, Hs, pad, C, C, K), rec
     assert nerr(nchw(dx1), a.grad) < TOL_BF16
     assert nerr(nchw(dx2), u.grad) < TOL_BF16
@@ -159,8 +157,10 @@ def test_conv3x3_bwd_virtual_concat_bf16(hip, B, Hs, pad, C, K):
 _BAND_AB = r"""
 import hashlib, os, sys
 sys.path.insert(0, os.path.join(sys.argv[1], "dl-unet_amd"))
+sys.path.insert(0, os.path.join(sys.argv[1], "tests"))
 import torch
 import _hip
+import guarded
 L = _hip.lib()
 _hip.check(L.unet_set_math(2), "set_math")
 torch.cuda.set_device(0)
@@ -168,30 +168,32 @@ g = torch.Generator().manual_seed(7)
 def rnd(*s, scale=1.0):
     return (torch.randn(*s, generator=g) * scale)
 h = hashlib.sha256()
-keep = []
 def dev16(t):
-    t = t.to(torch.bfloat16).cuda(); keep.append(t); return t
+    return mem.inp(t.to(torch.bfloat16))
 def dev32(t):
-    t = t.float().cuda(); keep.append(t); return t
+    return mem.inp(t.float())
 # (B, H, C1, C2, pad of source 1, K): single source, two sources with positive / negative pad (crop), ragged tiles, narrowest rows
 for B, H, C1, C2, pad, K in [(2, 21, 128, 0, 0, 128), (3, 40, 256, 0, 0, 256), (1, 150, 128, 0, 0, 128), (2, 28, 128, 128, 4, 128),
                              (1, 30, 128, 64, -5, 256), (8, 30, 1024, 0, 0, 1024)]:
     Hs = H - 2 * pad
     C = C1 + C2
+    mem = guarded.Arena()
     a = dev16(rnd(B, Hs if C2 else H, Hs if C2 else H, C1)); u = dev16(rnd(B, H, H, C2)) if C2 else None
     w = dev32(rnd(K, C, 3, 3, scale=0.05).to(torch.bfloat16)); b = dev32(rnd(K))
-    y = torch.empty(B, H - 2, H - 2, K, device="cuda", dtype=torch.bfloat16)
-    sc = torch.empty(max(int(L.unet_conv3x3_scratch_bytes(C, K)), 256), dtype=torch.uint8, device="cuda")
+    y = mem.out((B, H - 2, H - 2, K), torch.bfloat16, "y")
+    sc = mem.scratch(L.unet_conv3x3_scratch_bytes(C, K))
     _hip.check(L.unet_conv3x3_fwd(_hip.ptr(a), Hs if C2 else H, Hs if C2 else H, C1, pad, _hip.ptr(u) if C2 else None, C2, B, H, H, _hip.ptr(w), _hip.ptr(b), K, 1,
-                                  _hip.ptr(y), _hip.ptr(sc), _hip.stream()), "fwd")
+                                  _hip.ptr(y), mem.ptr(sc), _hip.stream()), "fwd")
+    mem.verify(y)
     h.update(y.view(torch.int16).cpu().numpy().tobytes())
     if not C2:
         dz = dev16(rnd(B, H - 2, H - 2, K)); mask = dev16(rnd(B, H, H, C).clamp_min(0)); add = dev16(rnd(B, H, H, C))
-        dx = torch.empty(B, H, H, C, device="cuda", dtype=torch.bfloat16)
-        dw = torch.empty(K, C, 3, 3, device="cuda"); db = torch.empty(K, device="cuda")
-        sc2 = torch.empty(max(int(L.unet_conv3x3_bwd_scratch_bytes(B, H, H, C, K)), 256), dtype=torch.uint8, device="cuda")
+        dx = mem.out((B, H, H, C), torch.bfloat16, "dx")
+        dw = mem.out((K, C, 3, 3), torch.float32, "dw"); db = mem.out((K,), torch.float32, "db")
+        sc2 = mem.scratch(L.unet_conv3x3_bwd_scratch_bytes(B, H, H, C, K))
         _hip.check(L.unet_conv3x3_bwd(_hip.ptr(a), H, H, C, 0, None, 0, B, H, H, _hip.ptr(w), K, _hip.ptr(dz), _hip.ptr(dx), _hip.ptr(mask), _hip.ptr(add),
-                                      None, None, _hip.ptr(dw), _hip.ptr(db), _hip.ptr(sc2), _hip.stream()), "bwd")
+                                      None, None, _hip.ptr(dw), _hip.ptr(db), mem.ptr(sc2), _hip.stream()), "bwd")
+        mem.verify(dx, dw, db)
         h.update(dx.view(torch.int16).cpu().numpy().tobytes())
 print("DIGEST", h.hexdigest())
 """
@@ -214,22 +216,24 @@ def test_band_kernel_is_bit_identical_to_the_plain_implicit_gemm(hip):
 
 @pytest.mark.parametrize("B,H,Ci,Co", [(2, 7, 128, 64), (1, 13, 256, 128), (1, 4, 1024, 512), (1, 40, 128, 64), (1, 5, 64, 64), (5, 6, 256, 256)])
 def test_upconv2_fwd_bwd_bf16(hip, B, H, Ci, Co):
-    keep = Keep()
+    mem = gd.Arena()
     x = bf(rnd(B, Ci, H, H, seed=1).clamp_min(0)).requires_grad_(True)
     w = bf(rnd(Ci, Co, 2, 2, seed=2, scale=0.05)).requires_grad_(True); b = rnd(Co, seed=3).float().double()
     dy = bf(rnd(B, Co, 2 * H, 2 * H, seed=4))
     ref = F.conv_transpose2d(x, w, b, stride=2)
     ref.backward(dy)
-    sc = scratch(hip.lib().unet_upconv2_scratch_bytes(B, H, H, Ci, Co))
-    y = torch.empty(B, 2 * H, 2 * H, Co, device="cuda", dtype=torch.bfloat16)
-    xd = nhwc16(x.detach())
-    hip.check(hip.lib().unet_upconv2_fwd(hip.ptr(xd), B, H, H, Ci, hip.ptr(keep(w.detach().float().cuda())), hip.ptr(keep(b.float().cuda())), Co,
-                                         hip.ptr(y), hip.ptr(sc), hip.stream()), "upconv2_fwd")
+    sc = mem.scratch(hip.lib().unet_upconv2_scratch_bytes(B, H, H, Ci, Co))
+    y = mem.out((B, 2 * H, 2 * H, Co), torch.bfloat16, "y")
+    xd = mem.inp(nhwc16(x.detach()))
+    hip.check(hip.lib().unet_upconv2_fwd(hip.ptr(xd), B, H, H, Ci, hip.ptr(mem.inp(w.detach().float().cuda())), hip.ptr(mem.inp(b.float().cuda())), Co,
+                                         hip.ptr(y), mem.ptr(sc), hip.stream()), "upconv2_fwd")
+    mem.verify(y)
     assert nerr(nchw(y), ref) < TOL_BF16
-    dx = torch.empty(B, H, H, Ci, device="cuda", dtype=torch.bfloat16); dw = torch.empty(Ci, Co, 2, 2, device="cuda"); db = torch.empty(Co, device="cuda")
+    dx = mem.out((B, H, H, Ci), torch.bfloat16, "dx"); dw = mem.out((Ci, Co, 2, 2), torch.float32, "dw"); db = mem.out((Co,), torch.float32, "db")
     with kp.record() as rec:
-        hip.check(hip.lib().unet_upconv2_bwd(hip.ptr(xd), B, H, H, Ci, hip.ptr(keep(w.detach().float().cuda())), Co, hip.ptr(keep(nhwc16(dy))),
-                                             hip.ptr(dx), hip.ptr(xd), hip.ptr(dw), hip.ptr(db), hip.ptr(sc), hip.stream()), "upconv2_bwd")
+        hip.check(hip.lib().unet_upconv2_bwd(hip.ptr(xd), B, H, H, Ci, hip.ptr(mem.inp(w.detach().float().cuda())), Co, hip.ptr(mem.inp(nhwc16(dy))),
+                                             hip.ptr(dx), hip.ptr(xd), hip.ptr(dw), hip.ptr(db), mem.ptr(sc), hip.stream()), "upconv2_bwd")
+    mem.verify(dx, dw, db)
     assert "wgrad_up<bf16>" in rec.families, rec                  # the one bf16 up-conv weight gradient, whatever lds_dma says
     assert nerr(nchw(dx), x.grad * (x.detach() > 0)) < TOL_BF16
     assert nerr(dw, w.grad) < TOL_F32
@@ -237,7 +241,7 @@ def test_upconv2_fwd_bwd_bf16(hip, B, H, Ci, Co):
 
 
 def test_pool_head_conv1ch_bf16(hip):
-    keep = Keep()
+    mem = gd.Arena()
     # pool: a selection, exact in bf16 (ties -> first maximum)
     B, H, Cc = 2, 12, 64
     pre = bf(rnd(B, Cc, H, H, seed=1).clamp_min(0))
@@ -247,10 +251,11 @@ def test_pool_head_conv1ch_bf16(hip):
     y_ref = F.max_pool2d(F.relu(p), 2, 2)
     dy = bf(rnd(B, Cc, H // 2, H // 2, seed=2))
     y_ref.backward(dy)
-    y = torch.empty(B, H // 2, H // 2, Cc, device="cuda", dtype=torch.bfloat16); dpre = torch.empty(B, H, H, Cc, device="cuda", dtype=torch.bfloat16)
-    xd = nhwc16(pre)
+    y = mem.out((B, H // 2, H // 2, Cc), torch.bfloat16, "y"); dpre = mem.out((B, H, H, Cc), torch.bfloat16, "dpre")
+    xd = mem.inp(nhwc16(pre))
     hip.check(hip.lib().unet_maxpool2_fwd(hip.ptr(xd), hip.ptr(y), B, H, H, Cc, hip.stream()))
-    hip.check(hip.lib().unet_maxpool2_bwd(hip.ptr(xd), hip.ptr(keep(nhwc16(dy))), hip.ptr(dpre), B, H, H, Cc, hip.stream()))
+    hip.check(hip.lib().unet_maxpool2_bwd(hip.ptr(xd), hip.ptr(mem.inp(nhwc16(dy))), hip.ptr(dpre), B, H, H, Cc, hip.stream()))
+    mem.verify(y, dpre)
     assert torch.equal(nchw(y), y_ref.detach()) and torch.equal(nchw(dpre), p.grad)
     # head: bf16 activations in, fp32 logits out; backward writes bf16 dz and fp32 dw / db
     B, H, Cc = 2, 37, 64
@@ -259,30 +264,34 @@ def test_pool_head_conv1ch_bf16(hip):
     ref = F.conv2d(x, w, b)
     dl = rnd(B, 2, H, H, seed=4).float().double()
     ref.backward(dl)
-    logits = torch.empty(B, 2, H, H, device="cuda")
-    xd = nhwc16(x.detach())
-    hip.check(hip.lib().unet_head1x1_fwd(hip.ptr(xd), B, H, H, Cc, hip.ptr(keep(w.detach().float().cuda())), hip.ptr(keep(b.float().cuda())),
+    logits = mem.out((B, 2, H, H), torch.float32, "logits")
+    xd = mem.inp(nhwc16(x.detach()))
+    hip.check(hip.lib().unet_head1x1_fwd(hip.ptr(xd), B, H, H, Cc, hip.ptr(mem.inp(w.detach().float().cuda())), hip.ptr(mem.inp(b.float().cuda())),
                                          hip.ptr(logits), hip.stream()))
+    mem.verify(logits)
     assert nerr(logits, ref) < TOL_F32
-    dz = torch.empty(B, H, H, Cc, device="cuda", dtype=torch.bfloat16); dw = torch.empty(2, Cc, 1, 1, device="cuda"); db = torch.empty(2, device="cuda")
-    sc = scratch(hip.lib().unet_head1x1_bwd_scratch_bytes(B, H, H, Cc))
-    hip.check(hip.lib().unet_head1x1_bwd(hip.ptr(xd), B, H, H, Cc, hip.ptr(keep(w.detach().float().cuda())), hip.ptr(keep(dl.float().cuda())),
-                                         hip.ptr(dz), hip.ptr(dw), hip.ptr(db), hip.ptr(sc), hip.stream()))
+    dz = mem.out((B, H, H, Cc), torch.bfloat16, "dz"); dw = mem.out((2, Cc, 1, 1), torch.float32, "dw"); db = mem.out((2,), torch.float32, "db")
+    sc = mem.scratch(hip.lib().unet_head1x1_bwd_scratch_bytes(B, H, H, Cc))
+    hip.check(hip.lib().unet_head1x1_bwd(hip.ptr(xd), B, H, H, Cc, hip.ptr(mem.inp(w.detach().float().cuda())), hip.ptr(mem.inp(dl.float().cuda())),
+                                         hip.ptr(dz), hip.ptr(dw), hip.ptr(db), mem.ptr(sc), hip.stream()))
+    mem.verify(dz, dw, db)
     assert nerr(nchw(dz), x.grad * (x.detach() > 0)) < TOL_BF16
     assert nerr(dw, w.grad) < TOL_F32 and nerr(db, dl.sum((0, 2, 3))) < TOL_F32
     # conv11c: fp32 image in, bf16 activations out; weight gradient from bf16 dz
     B, S, K = 2, 60, 64
     xi = rnd(B, 1, S, S, seed=1).float().double(); wi = rnd(K, 1, 3, 3, seed=2).float().double().requires_grad_(True); bi = rnd(K, seed=3).float().double()
     z = F.conv2d(xi, wi, bi)
-    yo = torch.empty(B, S - 2, S - 2, K, device="cuda", dtype=torch.bfloat16)
-    hip.check(hip.lib().unet_conv1ch_fwd(hip.ptr(keep(xi.float().cuda())), B, S, hip.ptr(keep(wi.detach().float().cuda())), hip.ptr(keep(bi.float().cuda())), K,
+    yo = mem.out((B, S - 2, S - 2, K), torch.bfloat16, "yo")
+    hip.check(hip.lib().unet_conv1ch_fwd(hip.ptr(mem.inp(xi.float().cuda())), B, S, hip.ptr(mem.inp(wi.detach().float().cuda())), hip.ptr(mem.inp(bi.float().cuda())), K,
                                          hip.ptr(yo), hip.stream()))
+    mem.verify(yo)
     assert nerr(nchw(yo), F.relu(z.detach())) < TOL_BF16
     dzi = bf(rnd(B, K, S - 2, S - 2, seed=4))
     z.backward(dzi)
-    dwi = torch.empty(K, 1, 3, 3, device="cuda"); dbi = torch.empty(K, device="cuda")
-    sc = scratch(hip.lib().unet_conv1ch_bwd_scratch_bytes(B, S, K))
-    hip.check(hip.lib().unet_conv1ch_bwd(hip.ptr(keep(xi.float().cuda())), B, S, K, hip.ptr(keep(nhwc16(dzi))), hip.ptr(dwi), hip.ptr(dbi), hip.ptr(sc), hip.stream()))
+    dwi = mem.out((K, 1, 3, 3), torch.float32, "dwi"); dbi = mem.out((K,), torch.float32, "dbi")
+    sc = mem.scratch(hip.lib().unet_conv1ch_bwd_scratch_bytes(B, S, K))
+    hip.check(hip.lib().unet_conv1ch_bwd(hip.ptr(mem.inp(xi.float().cuda())), B, S, K, hip.ptr(mem.inp(nhwc16(dzi))), hip.ptr(dwi), hip.ptr(dbi), mem.ptr(sc), hip.stream()))
+    mem.verify(dwi, dbi)
     assert nerr(dwi, wi.grad) < TOL_F32 and nerr(dbi, dzi.sum((0, 2, 3))) < TOL_F32
 
 
@@ -292,19 +301,21 @@ def test_bf16_weight_gradient_refuses_tensors_of_2GiB_loudly(hip):
     128 bf16 is exactly 2 GiB; nothing is launched, the gradient buffers keep their sentinel."""
     B, H, C, K = 8, 1024, 128, 64
     L = hip.lib()
+    mem = gd.Arena()
     x = torch.zeros(B, H, H, C, device="cuda", dtype=torch.bfloat16)
     assert x.numel() * 2 == 2 ** 31
     dz = torch.zeros(B, H - 2, H - 2, K, device="cuda", dtype=torch.bfloat16)
     w = torch.zeros(K, C, 3, 3, device="cuda")
     dw = torch.full((K, C, 3, 3), 7.0, device="cuda"); db = torch.full((K,), 7.0, device="cuda")
-    sc = scratch(L.unet_conv3x3_bwd_scratch_bytes(B, H, H, C, K))
+    sc = mem.scratch(L.unet_conv3x3_bwd_scratch_bytes(B, H, H, C, K))
     rc = L.unet_conv3x3_bwd(hip.ptr(x), H, H, C, 0, None, 0, B, H, H, hip.ptr(w), K, hip.ptr(dz), None, None, None, None, None,
-                            hip.ptr(dw), hip.ptr(db), hip.ptr(sc), hip.stream())
+                            hip.ptr(dw), hip.ptr(db), mem.ptr(sc), hip.stream())
     torch.cuda.synchronize()
     assert rc != 0
     assert b"2 GiB" in L.unet_last_error()
     with pytest.raises(RuntimeError, match="2 GiB"):
         hip.check(rc, "conv3x3_bwd")
+    mem.check()
     assert bool((dw == 7.0).all()) and bool((db == 7.0).all())
 
 
@@ -383,15 +394,16 @@ def rne_check(kind, y, z, A, K, relu=False):
                                          (1, 20, 128, 128, "igemmb<128;128;0>"),      # OW = 18: one short of the band kernel's rows
                                          (1, 14, 128, 64, "igemmb<256;64;0>"), (1, 12, 256, 512, "igemmb<128;128;0>")])
 def test_conv3x3_fwd_bf16_rounds_once(hip, B, H, C, K, fam):
-    keep = Keep()
+    mem = gd.Arena()
     x = bf(rnd(B, C, H, H, seed=1)); w = w32(K, C, 3, 3, seed=2, scale=0.05); b = rnd(K, seed=3).float().double()
     wq = bf(w)
     z = F.conv2d(x, wq, b); A = F.conv2d(x.abs(), wq.abs(), b.abs())
-    y = torch.empty(B, H - 2, H - 2, K, device="cuda", dtype=torch.bfloat16)
-    sc = scratch(hip.lib().unet_conv3x3_scratch_bytes(C, K))
+    y = mem.out((B, H - 2, H - 2, K), torch.bfloat16, "y")
+    sc = mem.scratch(hip.lib().unet_conv3x3_scratch_bytes(C, K))
     with kp.record() as rec:
-        hip.check(hip.lib().unet_conv3x3_fwd(hip.ptr(keep(nhwc16(x))), H, H, C, 0, None, 0, B, H, H, hip.ptr(keep(w.float().cuda())),
-                                             hip.ptr(keep(b.float().cuda())), K, 1, hip.ptr(y), hip.ptr(sc), hip.stream()), "conv3x3_fwd")
+        hip.check(hip.lib().unet_conv3x3_fwd(hip.ptr(mem.inp(nhwc16(x))), H, H, C, 0, None, 0, B, H, H, hip.ptr(mem.inp(w.float().cuda())),
+                                             hip.ptr(mem.inp(b.float().cuda())), K, 1, hip.ptr(y), mem.ptr(sc), hip.stream()), "conv3x3_fwd")
+    mem.verify(y)
     assert nerr(nchw(y), F.relu(z)) < TOL_BF16
     st = rne_check("fwd", nchw(y), z, A, 9 * C + 1, relu=True)
     assert st["relu_zeros"] > 0
@@ -402,18 +414,19 @@ def test_conv3x3_fwd_bf16_rounds_once(hip, B, H, C, K, fam):
 def test_conv3x3_fwd_virtual_concat_bf16_rounds_once(hip, B, Hs, pad, C1, C2, K):
     """A zero-padded skip source: the fp32 modes split this forward into two launches whose partial sums meet in the output
     tensor; with bf16 tensors that would round twice, so mode 2 keeps one launch (net.hip) - pinned here."""
-    keep = Keep()
+    mem = gd.Arena()
     H = Hs + 2 * pad
     a = bf(rnd(B, C1, Hs, Hs, seed=1)); u = bf(rnd(B, C2, H, H, seed=2))
     w = w32(K, C1 + C2, 3, 3, seed=3, scale=0.05); b = rnd(K, seed=4).float().double()
     xc = torch.cat((F.pad(a, (pad,) * 4), u), 1)
     z = F.conv2d(xc, bf(w), b); A = F.conv2d(xc.abs(), bf(w).abs(), b.abs())
-    y = torch.empty(B, H - 2, H - 2, K, device="cuda", dtype=torch.bfloat16)
-    sc = scratch(hip.lib().unet_conv3x3_scratch_bytes(C1 + C2, K))
+    y = mem.out((B, H - 2, H - 2, K), torch.bfloat16, "y")
+    sc = mem.scratch(hip.lib().unet_conv3x3_scratch_bytes(C1 + C2, K))
     with kp.record() as rec:
-        hip.check(hip.lib().unet_conv3x3_fwd(hip.ptr(keep(nhwc16(a))), Hs, Hs, C1, pad, hip.ptr(keep(nhwc16(u))), C2, B, H, H,
-                                             hip.ptr(keep(w.float().cuda())), hip.ptr(keep(b.float().cuda())), K, 1, hip.ptr(y), hip.ptr(sc),
+        hip.check(hip.lib().unet_conv3x3_fwd(hip.ptr(mem.inp(nhwc16(a))), Hs, Hs, C1, pad, hip.ptr(mem.inp(nhwc16(u))), C2, B, H, H,
+                                             hip.ptr(mem.inp(w.float().cuda())), hip.ptr(mem.inp(b.float().cuda())), K, 1, hip.ptr(y), mem.ptr(sc),
                                              hip.stream()), "conv3x3_fwd concat")
+    mem.verify(y)
     rne_check("fwd", nchw(y), z, A, 9 * (C1 + C2) + 1, relu=True)
     assert rec.main_families() == kp.concat_fwd_families(2, 1, Hs, pad, C1, C2, K), rec
 
@@ -421,7 +434,7 @@ def test_conv3x3_fwd_virtual_concat_bf16_rounds_once(hip, B, Hs, pad, C1, C2, K)
 @pytest.mark.parametrize("B,H,C,K,use_mask,use_add,fam", [(2, 21, 64, 64, True, True, "convb64<8;32>"), (2, 13, 128, 256, True, True, "igemmb<128;128;1>"),
                                                           (2, 23, 128, 128, True, True, "igemmb3<1>"), (1, 14, 64, 128, False, True, "igemmb<256;64;1>")])
 def test_conv3x3_dgrad_bf16_rounds_once(hip, B, H, C, K, use_mask, use_add, fam):
-    keep = Keep()
+    mem = gd.Arena()
     x = bf(rnd(B, C, H, H, seed=1)); w = w32(K, C, 3, 3, seed=2, scale=0.05); dz = bf(rnd(B, K, H - 2, H - 2, seed=3))
     mask = bf(rnd(B, C, H, H, seed=4).clamp_min(0)) if use_mask else None
     add = bf(rnd(B, C, H, H, seed=5)) if use_add else None
@@ -431,14 +444,15 @@ def test_conv3x3_dgrad_bf16_rounds_once(hip, B, H, C, K, use_mask, use_add, fam)
         z = z + add; A = A + add.abs()
     if mask is not None:
         z = z * (mask > 0); A = A * (mask > 0)
-    dx = torch.empty(B, H, H, C, device="cuda", dtype=torch.bfloat16)
-    dw = torch.empty(K, C, 3, 3, device="cuda"); db = torch.empty(K, device="cuda")
-    sc = scratch(hip.lib().unet_conv3x3_bwd_scratch_bytes(B, H, H, C, K))
+    dx = mem.out((B, H, H, C), torch.bfloat16, "dx")
+    dw = mem.out((K, C, 3, 3), torch.float32, "dw"); db = mem.out((K,), torch.float32, "db")
+    sc = mem.scratch(hip.lib().unet_conv3x3_bwd_scratch_bytes(B, H, H, C, K))
     with kp.record() as rec:
-        hip.check(hip.lib().unet_conv3x3_bwd(hip.ptr(keep(nhwc16(x))), H, H, C, 0, None, 0, B, H, H, hip.ptr(keep(w.float().cuda())), K,
-                                             hip.ptr(keep(nhwc16(dz))), hip.ptr(dx), hip.ptr(keep(nhwc16(mask))) if use_mask else None,
-                                             hip.ptr(keep(nhwc16(add))) if use_add else None, None, None, hip.ptr(dw), hip.ptr(db),
-                                             hip.ptr(sc), hip.stream()), "conv3x3_bwd")
+        hip.check(hip.lib().unet_conv3x3_bwd(hip.ptr(mem.inp(nhwc16(x))), H, H, C, 0, None, 0, B, H, H, hip.ptr(mem.inp(w.float().cuda())), K,
+                                             hip.ptr(mem.inp(nhwc16(dz))), hip.ptr(dx), hip.ptr(mem.inp(nhwc16(mask))) if use_mask else None,
+                                             hip.ptr(mem.inp(nhwc16(add))) if use_add else None, None, None, hip.ptr(dw), hip.ptr(db),
+                                             mem.ptr(sc), hip.stream()), "conv3x3_bwd")
+    mem.verify(dx, dw, db)
     assert nerr(nchw(dx), z) < TOL_BF16
     rne_check("dgrad", nchw(dx), z, A, 9 * K + 1)
     assert nerr(dw, conv2d_weight(x, w.shape, dz)) < TOL_F32 and nerr(db, dz.sum((0, 2, 3))) < TOL_F32
@@ -448,7 +462,7 @@ def test_conv3x3_dgrad_bf16_rounds_once(hip, B, H, C, K, use_mask, use_add, fam)
 
 @pytest.mark.parametrize("B,H,Ci,Co", [(2, 7, 128, 64), (1, 13, 256, 128), (5, 6, 256, 256)])
 def test_upconv2_bf16_rounds_once(hip, B, H, Ci, Co):
-    keep = Keep()
+    mem = gd.Arena()
     x = bf(rnd(B, Ci, H, H, seed=1).clamp_min(0)); w = w32(Ci, Co, 2, 2, seed=2, scale=0.05); b = rnd(Co, seed=3).float().double()
     dy = bf(rnd(B, Co, 2 * H, 2 * H, seed=4))
     wq = bf(w)
@@ -457,15 +471,16 @@ def test_upconv2_bf16_rounds_once(hip, B, H, Ci, Co):
     F.conv_transpose2d(xr, wq, stride=2).backward(dy); F.conv_transpose2d(xa, wq.abs(), stride=2).backward(dy.abs())
     wr = w.clone().requires_grad_(True)
     F.conv_transpose2d(x, wr, stride=2).backward(dy)
-    sc = scratch(hip.lib().unet_upconv2_scratch_bytes(B, H, H, Ci, Co))
-    y = torch.empty(B, 2 * H, 2 * H, Co, device="cuda", dtype=torch.bfloat16)
-    dx = torch.empty(B, H, H, Ci, device="cuda", dtype=torch.bfloat16); dw = torch.empty(Ci, Co, 2, 2, device="cuda"); db = torch.empty(Co, device="cuda")
-    xd = nhwc16(x)
+    sc = mem.scratch(hip.lib().unet_upconv2_scratch_bytes(B, H, H, Ci, Co))
+    y = mem.out((B, 2 * H, 2 * H, Co), torch.bfloat16, "y")
+    dx = mem.out((B, H, H, Ci), torch.bfloat16, "dx"); dw = mem.out((Ci, Co, 2, 2), torch.float32, "dw"); db = mem.out((Co,), torch.float32, "db")
+    xd = mem.inp(nhwc16(x))
     with kp.record() as rec:
-        hip.check(hip.lib().unet_upconv2_fwd(hip.ptr(xd), B, H, H, Ci, hip.ptr(keep(w.float().cuda())), hip.ptr(keep(b.float().cuda())), Co,
-                                             hip.ptr(y), hip.ptr(sc), hip.stream()), "upconv2_fwd")
-        hip.check(hip.lib().unet_upconv2_bwd(hip.ptr(xd), B, H, H, Ci, hip.ptr(keep(w.float().cuda())), Co, hip.ptr(keep(nhwc16(dy))),
-                                             hip.ptr(dx), hip.ptr(xd), hip.ptr(dw), hip.ptr(db), hip.ptr(sc), hip.stream()), "upconv2_bwd")
+        hip.check(hip.lib().unet_upconv2_fwd(hip.ptr(xd), B, H, H, Ci, hip.ptr(mem.inp(w.float().cuda())), hip.ptr(mem.inp(b.float().cuda())), Co,
+                                             hip.ptr(y), mem.ptr(sc), hip.stream()), "upconv2_fwd")
+        hip.check(hip.lib().unet_upconv2_bwd(hip.ptr(xd), B, H, H, Ci, hip.ptr(mem.inp(w.float().cuda())), Co, hip.ptr(mem.inp(nhwc16(dy))),
+                                             hip.ptr(dx), hip.ptr(xd), hip.ptr(dw), hip.ptr(db), mem.ptr(sc), hip.stream()), "upconv2_bwd")
+    mem.verify(y, dx, dw, db)
     rne_check("upfwd", nchw(y), z, A, Ci + 1)
     rne_check("updgrad", nchw(dx), xr.grad * (x > 0), xa.grad * (x > 0), 4 * Co)
     assert nerr(dw, wr.grad) < TOL_F32 and nerr(db, dy.sum((0, 2, 3))) < TOL_F32
@@ -473,25 +488,27 @@ def test_upconv2_bf16_rounds_once(hip, B, H, Ci, Co):
 
 
 def test_head_dz_and_conv1ch_bf16_round_once(hip):
-    keep = Keep()
+    mem = gd.Arena()
     # head backward: dz = (dlogits . W) * (x > 0), fp32 dlogits and weights (not bf16), one rounding to bf16
     B, H, Cc = 2, 37, 64
     x = bf(rnd(B, Cc, H, H, seed=1).clamp_min(0))
     w = w32(2, Cc, 1, 1, seed=2, scale=0.1); dl = rnd(B, 2, H, H, seed=4).float().double()
     z = torch.einsum("bohw,oc->bchw", dl, w[:, :, 0, 0]) * (x > 0)
     A = torch.einsum("bohw,oc->bchw", dl.abs(), w[:, :, 0, 0].abs()) * (x > 0)
-    dz = torch.empty(B, H, H, Cc, device="cuda", dtype=torch.bfloat16); dw = torch.empty(2, Cc, 1, 1, device="cuda"); db = torch.empty(2, device="cuda")
-    sc = scratch(hip.lib().unet_head1x1_bwd_scratch_bytes(B, H, H, Cc))
-    hip.check(hip.lib().unet_head1x1_bwd(hip.ptr(keep(nhwc16(x))), B, H, H, Cc, hip.ptr(keep(w.float().cuda())), hip.ptr(keep(dl.float().cuda())),
-                                         hip.ptr(dz), hip.ptr(dw), hip.ptr(db), hip.ptr(sc), hip.stream()))
+    dz = mem.out((B, H, H, Cc), torch.bfloat16, "dz"); dw = mem.out((2, Cc, 1, 1), torch.float32, "dw"); db = mem.out((2,), torch.float32, "db")
+    sc = mem.scratch(hip.lib().unet_head1x1_bwd_scratch_bytes(B, H, H, Cc))
+    hip.check(hip.lib().unet_head1x1_bwd(hip.ptr(mem.inp(nhwc16(x))), B, H, H, Cc, hip.ptr(mem.inp(w.float().cuda())), hip.ptr(mem.inp(dl.float().cuda())),
+                                         hip.ptr(dz), hip.ptr(dw), hip.ptr(db), mem.ptr(sc), hip.stream()))
+    mem.verify(dz, dw, db)
     rne_check("head_dz", nchw(dz), z, A, 2)
     # conv11c forward: fp32 image and weights, bf16 activations out
     B, S, K = 2, 60, 64
     xi = rnd(B, 1, S, S, seed=1).float().double(); wi = rnd(K, 1, 3, 3, seed=2).float().double(); bi = rnd(K, seed=3).float().double()
     z = F.conv2d(xi, wi, bi); A = F.conv2d(xi.abs(), wi.abs(), bi.abs())
-    yo = torch.empty(B, S - 2, S - 2, K, device="cuda", dtype=torch.bfloat16)
-    hip.check(hip.lib().unet_conv1ch_fwd(hip.ptr(keep(xi.float().cuda())), B, S, hip.ptr(keep(wi.float().cuda())), hip.ptr(keep(bi.float().cuda())), K,
+    yo = mem.out((B, S - 2, S - 2, K), torch.bfloat16, "yo")
+    hip.check(hip.lib().unet_conv1ch_fwd(hip.ptr(mem.inp(xi.float().cuda())), B, S, hip.ptr(mem.inp(wi.float().cuda())), hip.ptr(mem.inp(bi.float().cuda())), K,
                                          hip.ptr(yo), hip.stream()))
+    mem.verify(yo)
     rne_check("conv1ch", nchw(yo), z, A, 10, relu=True)
 
 
@@ -523,12 +540,14 @@ def test_net_forward_backward_bf16_glds_S188(hip, glds):
     outs = []
     for dma in (0, 1):
         hip.check(hip.lib().unet_set_lds_dma(dma), "set_lds_dma")
-        ws = torch.empty(h.workspace_bytes(B, S, 1), dtype=torch.uint8, device="cuda")
-        logits = torch.empty(B, 2, S - 184, S - 184, device="cuda")
-        grads = [torch.full_like(p, float("nan")) for p in params]
+        mem = gd.Arena()
+        ws = mem.scratch(h.workspace_bytes(B, S, 1), "workspace")
+        logits = mem.out((B, 2, S - 184, S - 184), torch.float32, "logits")
+        grads = [mem.out(p.shape, torch.float32, "grad %d" % i) for i, p in enumerate(params)]
         hip.check(hip.lib().unet_forward(h.h, _hip.ptr_table(params), hip.ptr(x), hip.ptr(logits), B, S, hip.ptr(ws), ws.numel(), 1, hip.stream()), "forward")
         hip.check(hip.lib().unet_backward(h.h, _hip.ptr_table(params), hip.ptr(dl), _hip.ptr_table(grads), hip.ptr(ws), ws.numel(), hip.stream()), "backward")
         torch.cuda.synchronize()
+        mem.verify(logits, *grads)
         assert all(bool(torch.isfinite(g).all()) for g in grads)
         outs.append([logits.cpu()] + [g.cpu() for g in grads])
     hip.check(hip.lib().unet_set_lds_dma(0), "set_lds_dma")
@@ -545,7 +564,8 @@ def test_fuzz_conv_bf16_tensors():
             "spec = importlib.util.spec_from_file_location('fuzz_conv', os.path.join(%r, 'tools', 'fuzz_conv.py'))\n"
             "fz = importlib.util.module_from_spec(spec); spec.loader.exec_module(fz)\n"
             "import torch, _hip; assert _hip.lib().unet_get_math() == 2\n"
-            "w = fz.run(30, 11, verbose=False); print('WORST', w); assert w < fz.TOL\n") % (os.path.join(root, "dl-unet_amd"), root)
+            "sys.path.insert(0, os.path.join(%r, 'tests')); import guarded\n"
+            "w = fz.run(30, 11, verbose=False, arena=guarded.Arena); print('WORST', w); assert w < fz.TOL\n") % (os.path.join(root, "dl-unet_amd"), root, root)
     out = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, UNET_MATH="2"), capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     assert "WORST" in out.stdout

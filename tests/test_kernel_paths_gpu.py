@@ -7,6 +7,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import guarded as gd
 import kernel_paths as kp
 
 pytestmark = pytest.mark.gpu
@@ -38,16 +39,16 @@ def nerr(a, ref):
 
 def run_op(hip, mode, dma, op, args):
     """Runs one per-op case in `mode` with staging `dma`; returns (record, outputs {name: device tensor}, references
-    {name: (fp64 reference, is_activation)})."""
+    {name: (fp64 reference, is_activation)}).  Every requested output is checked to be fully written and every guard intact."""
     L = hip.lib()
     hip.check(L.unet_set_math(mode), "set_math"); hip.check(L.unet_set_lds_dma(dma), "set_lds_dma")
     adt = torch.bfloat16 if mode == 2 else torch.float32
     q = (lambda t: t.to(torch.bfloat16).double()) if mode == 2 else (lambda t: t)       # what the kernels see of a tensor
     dev = lambda t: t.permute(0, 2, 3, 1).contiguous().to(adt).cuda()
     host = lambda t: t.permute(0, 3, 1, 2).double().cpu()
-    keep = []
-    k = lambda t: (keep.append(t), t)[1]
-    sc = lambda n: k(torch.empty(max(int(n), 256), dtype=torch.uint8, device="cuda"))
+    mem = gd.Arena()                                                # every buffer the library sees: poisoned, guarded, exact (tests/guarded.py)
+    k = mem.inp
+    sc = lambda n: mem.ptr(mem.scratch(n))
     out, ref = {}, {}
     try:
         with kp.record(L) as rec:
@@ -63,20 +64,20 @@ def run_op(hip, mode, dma, op, args):
                 ad, ud = k(dev(a.detach())), (k(dev(u.detach())) if C2 else None)
                 wd = k(w.detach().float().cuda())
                 if op == "fwd":
-                    y = torch.empty(B, H - 2, H - 2, K, device="cuda", dtype=adt)
+                    y = mem.out((B, H - 2, H - 2, K), adt, "y")
                     hip.check(L.unet_conv3x3_fwd(hip.ptr(ad), Hs, Hs, C1, pad, hip.ptr(ud) if C2 else None, C2, B, H, H, hip.ptr(wd),
-                                                 hip.ptr(k(b.float().cuda())), K, 1, hip.ptr(y), hip.ptr(sc(L.unet_conv3x3_scratch_bytes(C1 + C2, K))),
+                                                 hip.ptr(k(b.float().cuda())), K, 1, hip.ptr(y), sc(L.unet_conv3x3_scratch_bytes(C1 + C2, K)),
                                                  hip.stream()), "conv3x3_fwd")
                     out["y"] = y; ref["y"] = (F.relu(z.detach()), True)
                 else:
                     dz = q(rnd(B, K, H - 2, H - 2, seed=5))
                     z.backward(dz)
-                    dx1 = torch.empty(B, Hs, Hs, C1, device="cuda", dtype=adt)
-                    dx2 = torch.empty(B, H, H, C2, device="cuda", dtype=adt) if C2 else None
-                    dw = torch.empty(K, C1 + C2, 3, 3, device="cuda"); db = torch.empty(K, device="cuda")
+                    dx1 = mem.out((B, Hs, Hs, C1), adt, "dx1")
+                    dx2 = mem.out((B, H, H, C2), adt, "dx2") if C2 else None
+                    dw = mem.out((K, C1 + C2, 3, 3), torch.float32, "dw"); db = mem.out((K,), torch.float32, "db")
                     hip.check(L.unet_conv3x3_bwd(hip.ptr(ad), Hs, Hs, C1, pad, hip.ptr(ud) if C2 else None, C2, B, H, H, hip.ptr(wd), K,
                                                  hip.ptr(k(dev(dz))), hip.ptr(dx1), None, None, hip.ptr(dx2) if C2 else None, None,
-                                                 hip.ptr(dw), hip.ptr(db), hip.ptr(sc(L.unet_conv3x3_bwd_scratch_bytes(B, H, H, C1 + C2, K))),
+                                                 hip.ptr(dw), hip.ptr(db), sc(L.unet_conv3x3_bwd_scratch_bytes(B, H, H, C1 + C2, K)),
                                                  hip.stream()), "conv3x3_bwd")
                     out.update(dx1=dx1, dw=dw, db=db); ref.update(dx1=(a.grad, True), dw=(wq.grad, False), db=(dz.sum((0, 2, 3)), False))
                     if C2:
@@ -91,15 +92,16 @@ def run_op(hip, mode, dma, op, args):
                 z.backward(dy)
                 s = sc(L.unet_upconv2_scratch_bytes(B, H, H, max(Ci, 64), max(Co, 64)))
                 xd, wd = k(dev(x.detach())), k(w.detach().float().cuda())
-                y = torch.empty(B, 2 * H, 2 * H, Co, device="cuda", dtype=adt)
-                dx = torch.empty(B, H, H, Ci, device="cuda", dtype=adt); dw = torch.empty(Ci, Co, 2, 2, device="cuda"); db = torch.empty(Co, device="cuda")
-                hip.check(L.unet_upconv2_fwd(hip.ptr(xd), B, H, H, Ci, hip.ptr(wd), hip.ptr(k(b.float().cuda())), Co, hip.ptr(y), hip.ptr(s), hip.stream()), "upconv2_fwd")
+                y = mem.out((B, 2 * H, 2 * H, Co), adt, "y")
+                dx = mem.out((B, H, H, Ci), adt, "dx"); dw = mem.out((Ci, Co, 2, 2), torch.float32, "dw"); db = mem.out((Co,), torch.float32, "db")
+                hip.check(L.unet_upconv2_fwd(hip.ptr(xd), B, H, H, Ci, hip.ptr(wd), hip.ptr(k(b.float().cuda())), Co, hip.ptr(y), s, hip.stream()), "upconv2_fwd")
                 hip.check(L.unet_upconv2_bwd(hip.ptr(xd), B, H, H, Ci, hip.ptr(wd), Co, hip.ptr(k(dev(dy))), hip.ptr(dx), hip.ptr(xd), hip.ptr(dw), hip.ptr(db),
-                                             hip.ptr(s), hip.stream()), "upconv2_bwd")
+                                             s, hip.stream()), "upconv2_bwd")
                 out.update(y=y, dx=dx, dw=dw, db=db)
                 ref.update(y=(z.detach(), True), dx=(x.grad * (x.detach() > 0), True), dw=(wq.grad, False), db=(dy.sum((0, 2, 3)), False))
     finally:
         hip.check(L.unet_set_lds_dma(1), "set_lds_dma")
+    mem.verify(*out.values())
     out = {n: (host(t) if t.dim() == 4 and n.startswith(("y", "dx")) else t.cpu()) for n, t in out.items()}
     return rec, out, ref
 

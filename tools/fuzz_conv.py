@@ -1,5 +1,8 @@
 """Random-shape parity of the 3x3 conv forward / backward entry points (both sources, signed pad, masks) against fp64
-torch on the CPU.  Run on the GPU box: python tools/fuzz_conv.py [n] [seed]."""
+torch on the CPU.  Run on the GPU box: python tools/fuzz_conv.py [n] [seed].
+run(..., arena=) takes an allocator factory, called once per shape: an object with out(shape, dtype, label), scratch(nbytes),
+inp(tensor), ptr(tensor) and verify(*outputs) - tests/guarded.py's Arena (poisoned, guarded buffers of the exact size) is
+what the suite passes; the default is plain torch.empty."""
 import sys, os, random
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "dl-unet_amd"))
 import torch, torch.nn.functional as F
@@ -15,7 +18,17 @@ nhwc = lambda t: t.permute(0, 2, 3, 1).contiguous().to(torch.bfloat16 if BF16 el
 nchw = lambda t: t.permute(0, 3, 1, 2).double().cpu()
 
 
-def run(n, seed, verbose=True):
+class Plain:
+    """The default allocator: torch.empty of the requested size, nothing checked."""
+    def __init__(self): self.keep = []
+    def out(self, shape, dtype=torch.float32, label=None): return torch.empty(shape, device="cuda", dtype=dtype)
+    def scratch(self, nbytes, label=None): return torch.empty(int(nbytes), dtype=torch.uint8, device="cuda")
+    def inp(self, t, label=None): self.keep.append(t); return t
+    def ptr(self, t): return _hip.ptr(t)
+    def verify(self, *outputs): pass
+
+
+def run(n, seed, verbose=True, arena=None):
   L = _hip.lib()
   rng = random.Random(seed)
   worst = 0.0
@@ -38,20 +51,22 @@ def run(n, seed, verbose=True):
       dz = r(B, K, H - 2, H - 2)
       xin = torch.cat((F.pad(a, (pad,) * 4), u), 1) if concat else a
       z = F.conv2d(xin, w, b); z.backward(dz)
-      keep = []
-      def k(t): keep.append(t); return t
+      mem = (arena or Plain)()
+      k = mem.inp
       adt = torch.bfloat16 if BF16 else torch.float32
-      y = torch.empty(B, H - 2, H - 2, K, device="cuda", dtype=adt)
-      sc = torch.empty(L.unet_conv3x3_scratch_bytes(Ct, K), dtype=torch.uint8, device="cuda")
+      y = mem.out((B, H - 2, H - 2, K), adt, "y")
+      sc = mem.scratch(L.unet_conv3x3_scratch_bytes(Ct, K))
       _hip.check(L.unet_conv3x3_fwd(_hip.ptr(k(nhwc(a.detach()))), Hs, Hs, C, pad, _hip.ptr(k(nhwc(u.detach()))) if concat else None, C if concat else 0,
-                                    B, H, H, _hip.ptr(k(w.detach().float().cuda())), _hip.ptr(k(b.float().cuda())), K, 1, _hip.ptr(y), _hip.ptr(sc), _hip.stream()))
+                                    B, H, H, _hip.ptr(k(w.detach().float().cuda())), _hip.ptr(k(b.float().cuda())), K, 1, _hip.ptr(y), mem.ptr(sc), _hip.stream()))
+      mem.verify(y)
       e_f = nerr(nchw(y), F.relu(z.detach()))
-      dx1 = torch.empty(B, Hs, Hs, C, device="cuda", dtype=adt); dx2 = torch.empty(B, H, H, C, device="cuda", dtype=adt) if concat else None
-      dw = torch.empty(K, Ct, 3, 3, device="cuda"); db = torch.empty(K, device="cuda")
-      sc2 = torch.empty(L.unet_conv3x3_bwd_scratch_bytes(B, H, H, Ct, K), dtype=torch.uint8, device="cuda")
+      dx1 = mem.out((B, Hs, Hs, C), adt, "dx1"); dx2 = mem.out((B, H, H, C), adt, "dx2") if concat else None
+      dw = mem.out((K, Ct, 3, 3), torch.float32, "dw"); db = mem.out((K,), torch.float32, "db")
+      sc2 = mem.scratch(L.unet_conv3x3_bwd_scratch_bytes(B, H, H, Ct, K))
       _hip.check(L.unet_conv3x3_bwd(_hip.ptr(k(nhwc(a.detach()))), Hs, Hs, C, pad, _hip.ptr(k(nhwc(u.detach()))) if concat else None, C if concat else 0,
                                     B, H, H, _hip.ptr(k(w.detach().float().cuda())), K, _hip.ptr(k(nhwc(dz))), _hip.ptr(dx1), None, None,
-                                    _hip.ptr(dx2) if concat else None, None, _hip.ptr(dw), _hip.ptr(db), _hip.ptr(sc2), _hip.stream()))
+                                    _hip.ptr(dx2) if concat else None, None, _hip.ptr(dw), _hip.ptr(db), mem.ptr(sc2), _hip.stream()))
+      mem.verify(dx1, dx2, dw, db)
       errs = [e_f, nerr(nchw(dx1), a.grad), nerr(dw, w.grad), nerr(db, dz.sum((0, 2, 3)))]
       tols = [TOL_ACT, TOL_ACT, TOL, TOL]
       if concat: errs.append(nerr(nchw(dx2), u.grad)); tols.append(TOL_ACT)
