@@ -81,6 +81,10 @@ _SIGS = {
     "unet_class_balance": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
     "unet_weighted_map_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "unet_weighted_map": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, vp, vp, vp, vp, vp]),
+    "unet_label_components_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "unet_label_components": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]),
+    "unet_instance_overlap_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_size_t]),
+    "unet_instance_overlap": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, vp, vp, vp, vp, vp, vp, vp]),
     "unet_gaussian_filter": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_float, vp, vp, vp]),
     "unet_warp_bilinear": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]),
     "unet_rotate_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int]),

@@ -213,6 +213,11 @@ static inline int class_pad(int K) { return K <= 2 ? 2 : K <= 4 ? 4 : K <= 8 ? 8
         default: { constexpr int KP_ = 16; LAUNCH; } break;                                                        \
         }                                                                                                          \
     } while (0)
+// exact 4-connected labelling (wmap.hip, passes ccl_local / ccl_merge / ccl_flatten; shared by unet_weighted_map and
+// unet_label_components): label [B,H,W] = the smallest pixel index of the pixel's component in its image, -1 where mask == 0
+// (dtype 0: int64, 1: float32); counts[b] = foreground pixels, n_objects[b] = components; parent is an int plane of scratch
+int ccl_labels(const void *mask, int dtype, int B, int H, int W, int *parent, int *label, unsigned long long *counts, int *n_objects,
+               hipStream_t st);
 int maxpool2_fwd(const void *x, void *y, int B, int H, int W, int C, int es, hipStream_t st);
 int maxpool2_bwd(const void *pre, const void *dy, void *dpre, int B, int H, int W, int C, int es, hipStream_t st);
 

@@ -1,0 +1,274 @@
+// instances.hip — cell instances from a foreground mask, and the per-cell overlaps the Cell Tracking Challenge SEG measure
+// needs (Ronneberger et al. 2015, Table 2), batched, on the device.
+//
+// unet_label_components: ccl_labels (wmap.hip passes 1-3: label = root = the smallest pixel index of the component), then
+//   4. inst_count  one workgroup per 1024 consecutive pixels: how many of them are roots (label[e] == e)
+//   5. inst_scan   one workgroup per image: exclusive scan of those counts
+//   6. inst_rank   the same 1024 pixels again: a root writes 1 + (roots before it in raster order) into the id plane at its index
+//   7. inst_write  labels = id[root], 0 on background
+// A component's root is its first pixel in raster order, so the ranks of the roots are the raster numbering of
+// scipy.ndimage.label / cv.connectedComponents(connectivity=4).  Passes 4-7 touch every pixel a fixed number of times: their
+// cost does not depend on how many components there are.
+//
+// unet_instance_overlap: two id maps -> per-id areas, and for every ground-truth id the one predicted id that covers more than
+// half of it, with the size of that overlap:
+//   1. overlap_fill   a wave reads 64 consecutive pixels, merges the runs of equal (gt, pred) pairs among them with one ballot,
+//                     and the first lane of a run adds the run's length to both area histograms and, for gt, pred >= 1, to the
+//                     pair's counter in an open-addressing table (64-bit key (b, gt, pred), claimed by compare-and-swap)
+//   2. overlap_match  one thread per table slot: 2 * count > area_gt[g] -> match[g] = p, inter[g] = count (at most one p per g)
+// Every count is an integer sum: the outputs do not depend on the order of the atomics.  Which slot a key lands in does, and
+// nothing reads that.
+//
+// Coherence (wmap.hip's rule): inside overlap_fill a table key is only ever touched by an agent-scope compare-and-swap, a
+// counter, a histogram bin or a status word only by an agent-scope add; overlap_match, and every pass of the labelling, reads
+// what an earlier kernel wrote.  No word is handed from one workgroup to another inside a kernel by plain loads and stores.
+#include "common.hpp"
+#include <algorithm>
+#include "../../include/unet_hip.h"
+
+namespace unet {
+
+static constexpr int IN_CHUNK = 1024;                        // pixels per workgroup of inst_count / inst_rank: 256 threads x 4
+static constexpr unsigned long long OV_EMPTY = ~0ull;        // never a key: b <= 65534
+static constexpr int OV_ID_BITS = 24;
+static constexpr int OV_ID_MAX = (1 << OV_ID_BITS) - 1;
+
+// exclusive prefix of v over the 256 threads of the workgroup, and their sum
+__device__ __forceinline__ int block_scan256(int v, int &total)
+{
+    __shared__ int wave_sum[4];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    int inc = v;
+    for (int d = 1; d < 64; d <<= 1) {
+        const int t = __shfl_up(inc, d, 64);
+        if (lane >= d) inc += t;
+    }
+    __syncthreads();                                        // the previous call's reads of wave_sum are done
+    if (lane == 63) wave_sum[w] = inc;
+    __syncthreads();
+    int before = 0;
+    total = 0;
+    for (int i = 0; i < 4; ++i) {
+        if (i < w) before += wave_sum[i];
+        total += wave_sum[i];
+    }
+    return before + inc - v;
+}
+
+// roots among this thread's 4 consecutive pixels, as a bit mask
+__device__ __forceinline__ int inst_roots(const int *__restrict__ L, size_t npx, size_t e0)
+{
+    int m = 0;
+    for (int k = 0; k < 4; ++k)
+        if (e0 + k < npx && L[e0 + k] == (int)(e0 + k)) m |= 1 << k;
+    return m;
+}
+
+__global__ __launch_bounds__(256) void inst_count_kernel(const int *__restrict__ label, size_t npx, int *__restrict__ chunk_roots)
+{
+    const size_t e0 = (size_t)blockIdx.x * IN_CHUNK + threadIdx.x * 4;
+    int total;
+    block_scan256(__popc(inst_roots(label + (size_t)blockIdx.y * npx, npx, e0)), total);
+    if (threadIdx.x == 0) chunk_roots[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = total;
+}
+
+// in place: chunk_roots[b][c] becomes the number of roots in the chunks before c
+__global__ __launch_bounds__(256) void inst_scan_kernel(int *__restrict__ chunk_roots, int nchunk)
+{
+    int *c = chunk_roots + (size_t)blockIdx.x * nchunk;
+    int carry = 0;
+    for (int base = 0; base < nchunk; base += 256) {
+        const int i = base + threadIdx.x;
+        const int v = i < nchunk ? c[i] : 0;
+        int total;
+        const int before = block_scan256(v, total);
+        if (i < nchunk) c[i] = carry + before;
+        carry += total;
+    }
+}
+
+__global__ __launch_bounds__(256) void inst_rank_kernel(const int *__restrict__ label, size_t npx, const int *__restrict__ chunk_before,
+                                                        int *__restrict__ id)
+{
+    const size_t img = (size_t)blockIdx.y * npx, e0 = (size_t)blockIdx.x * IN_CHUNK + threadIdx.x * 4;
+    const int m = inst_roots(label + img, npx, e0);
+    int total;
+    int rank = chunk_before[(size_t)blockIdx.y * gridDim.x + blockIdx.x] + block_scan256(__popc(m), total);
+    for (int k = 0; k < 4; ++k)
+        if (m >> k & 1) id[img + e0 + k] = ++rank;
+}
+
+// label holds the root (or -1) on entry and the component's number (or 0) on return; each thread rewrites only what it read
+__global__ __launch_bounds__(256) void inst_write_kernel(int *__restrict__ label, size_t npx, const int *__restrict__ id)
+{
+    const size_t img = (size_t)blockIdx.y * npx;
+    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < npx; e += (size_t)gridDim.x * blockDim.x) {
+        const int r = label[img + e];
+        label[img + e] = r >= 0 ? id[img + r] : 0;
+    }
+}
+
+// ---- overlaps ---------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ unsigned long long ov_hash(unsigned long long x)
+{
+    x ^= x >> 33; x *= 0xff51afd7ed558ccdull;
+    x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ull;
+    return x ^ (x >> 33);
+}
+__device__ __forceinline__ unsigned long long wave_sum64(unsigned long long v)
+{
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+    return v;
+}
+
+// adds n to the counter of `key`; false when the key is absent and no slot is free
+__device__ __forceinline__ bool ov_insert(unsigned long long *keys, unsigned *cnt, size_t slots, unsigned long long key, unsigned n)
+{
+    size_t h = ov_hash(key) & (slots - 1);
+    for (size_t probe = 0; probe < slots; ++probe) {
+        unsigned long long seen = OV_EMPTY;
+        if (__hip_atomic_compare_exchange_strong(&keys[h], &seen, key, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ||
+            seen == key) {
+            __hip_atomic_fetch_add(&cnt[h], n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            return true;
+        }
+        h = (h + 1) & (slots - 1);
+    }
+    return false;
+}
+
+__global__ __launch_bounds__(256) void overlap_fill_kernel(const int *__restrict__ gt, const int *__restrict__ pred, size_t npx,
+                                                           int ng_max, int np_max, unsigned long long *keys, unsigned *cnt,
+                                                           size_t slots, unsigned *area_gt, unsigned *area_pred,
+                                                           unsigned long long *status)
+{
+    const int b = blockIdx.y, lane = threadIdx.x & 63;
+    const int *G = gt + (size_t)b * npx, *P = pred + (size_t)b * npx;
+    unsigned *ag = area_gt + (size_t)b * (ng_max + 1), *ap = area_pred + (size_t)b * (np_max + 1);
+    unsigned long long bad = 0, dropped = 0, g0 = 0, p0 = 0;      // this lane's share of status[b][0..1] and of the two bins 0
+    bool full = false;                                            // the table only fills up: after one failed probe, stop probing
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t base = (size_t)blockIdx.x * blockDim.x + (threadIdx.x & ~63); base < npx; base += stride) {   // wave-uniform
+        const size_t e = base + lane;
+        const bool in = e < npx;
+        int g = in ? G[e] : -1, p = in ? P[e] : -1;
+        const bool ok = in && (unsigned)g <= (unsigned)ng_max && (unsigned)p <= (unsigned)np_max;
+        if (!ok) g = p = in ? -1 : -2;                            // out-of-range pixels form runs of their own; so does the tail past the image
+        const int gl = __shfl_up(g, 1, 64), pl = __shfl_up(p, 1, 64);
+        const bool head = lane == 0 || g != gl || p != pl;
+        const unsigned long long heads = __ballot(head);
+        const unsigned long long above = lane == 63 ? 0ull : heads >> (lane + 1);
+        const unsigned n = above ? (unsigned)__ffsll(above) : (unsigned)(64 - lane);   // run length: up to the next head
+        if (head && in) {
+            if (!ok) bad += n;
+            else {
+                if (g) __hip_atomic_fetch_add(&ag[g], n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); else g0 += n;
+                if (p) __hip_atomic_fetch_add(&ap[p], n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); else p0 += n;
+                if (g && p) {
+                    const unsigned long long key = (unsigned long long)b << (2 * OV_ID_BITS) | (unsigned long long)g << OV_ID_BITS | (unsigned)p;
+                    if (full || !ov_insert(keys, cnt, slots, key, n)) { dropped += n; full = true; }
+                }
+            }
+        }
+        full = __any(full);
+    }
+    bad = wave_sum64(bad); dropped = wave_sum64(dropped); g0 = wave_sum64(g0); p0 = wave_sum64(p0);
+    if (lane == 0) {
+        if (bad) __hip_atomic_fetch_add(&status[2 * b], bad, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (dropped) __hip_atomic_fetch_add(&status[2 * b + 1], dropped, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (g0) __hip_atomic_fetch_add(&ag[0], (unsigned)g0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (p0) __hip_atomic_fetch_add(&ap[0], (unsigned)p0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+__global__ __launch_bounds__(256) void overlap_match_kernel(const unsigned long long *__restrict__ keys, const unsigned *__restrict__ cnt,
+                                                            size_t slots, int ng_max, const unsigned *__restrict__ area_gt,
+                                                            int *__restrict__ match, unsigned *__restrict__ inter)
+{
+    for (size_t s = (size_t)blockIdx.x * blockDim.x + threadIdx.x; s < slots; s += (size_t)gridDim.x * blockDim.x) {
+        const unsigned long long key = keys[s];
+        if (key == OV_EMPTY) continue;
+        const size_t b = key >> (2 * OV_ID_BITS);
+        const int g = (int)(key >> OV_ID_BITS) & OV_ID_MAX, p = (int)key & OV_ID_MAX;
+        const size_t o = b * (ng_max + 1) + g;
+        const unsigned c = cnt[s];
+        if (2ull * c > area_gt[o]) { match[o] = p; inter[o] = c; }      // strict: no two p can both hold more than half of g
+    }
+}
+
+} // namespace unet
+
+using namespace unet;
+
+static size_t in_plane(int B, int H, int W) { return align_up((size_t)B * H * W * sizeof(int), 256); }
+static size_t in_chunks(int H, int W) { return ((size_t)H * W + IN_CHUNK - 1) / IN_CHUNK; }
+static size_t in_chunk_bytes(int B, int H, int W) { return align_up((size_t)B * in_chunks(H, W) * sizeof(int), 256); }
+
+size_t unet_label_components_scratch_bytes(int B, int H, int W)
+{
+    if (B <= 0 || H <= 0 || W <= 0) return 0;
+    return in_plane(B, H, W) + in_chunk_bytes(B, H, W) + align_up((size_t)B * sizeof(unsigned long long), 256);
+}
+
+int unet_label_components(const void *mask, int dtype, int B, int H, int W, void *labels_i32, void *n_objects_i32, void *scratch,
+                          void *stream)
+{
+    ARG_CHECK(mask && labels_i32 && n_objects_i32 && scratch && B > 0 && H > 0 && W > 0, "unet_label_components: bad argument");
+    ARG_CHECK(dtype == 0 || dtype == 1, "unet_label_components: dtype must be 0 (int64) or 1 (float32)");
+    ARG_CHECK((size_t)H * W < (1u << 31) && H <= 65535 && B <= 65535, "unet_label_components: image too large");
+    hipStream_t st = (hipStream_t)stream;
+    const size_t npx = (size_t)H * W;
+    const unsigned nchunk = (unsigned)in_chunks(H, W);
+    char *s = (char *)scratch;
+    int *plane = (int *)s;                                        // the parent words, then (they are dead after ccl_flatten) the ids
+    int *chunk_roots = (int *)(s + in_plane(B, H, W));
+    unsigned long long *counts = (unsigned long long *)(s + in_plane(B, H, W) + in_chunk_bytes(B, H, W));
+    int *label = (int *)labels_i32;
+    if (int rc = ccl_labels(mask, dtype, B, H, W, plane, label, counts, (int *)n_objects_i32, st)) return rc;
+    hipLaunchKernelGGL(inst_count_kernel, dim3(nchunk, B), dim3(256), 0, st, (const int *)label, npx, chunk_roots);
+    hipLaunchKernelGGL(inst_scan_kernel, dim3(B), dim3(256), 0, st, chunk_roots, (int)nchunk);
+    hipLaunchKernelGGL(inst_rank_kernel, dim3(nchunk, B), dim3(256), 0, st, (const int *)label, npx, (const int *)chunk_roots, plane);
+    hipLaunchKernelGGL(inst_write_kernel, dim3((unsigned)std::min<size_t>((npx + 255) / 256, 2048), B), dim3(256), 0, st, label, npx,
+                       (const int *)plane);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+static size_t ov_key_bytes(size_t slots) { return align_up(slots * sizeof(unsigned long long), 256); }
+
+size_t unet_instance_overlap_scratch_bytes(int B, int ng_max, int np_max, size_t table_slots)
+{
+    if (B <= 0 || ng_max < 0 || np_max < 0 || table_slots == 0) return 0;
+    return ov_key_bytes(table_slots) + align_up(table_slots * sizeof(unsigned), 256);
+}
+
+int unet_instance_overlap(const void *gt_i32, const void *pred_i32, int B, int H, int W, int ng_max, int np_max, size_t table_slots,
+                          void *area_gt_u32, void *area_pred_u32, void *match_i32, void *inter_u32, void *status_u64, void *scratch,
+                          void *stream)
+{
+    ARG_CHECK(gt_i32 && pred_i32 && area_gt_u32 && area_pred_u32 && match_i32 && inter_u32 && status_u64 && scratch && B > 0 &&
+              H > 0 && W > 0, "unet_instance_overlap: bad argument");
+    ARG_CHECK((size_t)H * W < (1u << 31) && B <= 65535, "unet_instance_overlap: image too large");
+    ARG_CHECK(ng_max >= 0 && np_max >= 0 && ng_max <= OV_ID_MAX && np_max <= OV_ID_MAX,
+              "unet_instance_overlap: ng_max and np_max must be in [0, %d]", OV_ID_MAX);
+    ARG_CHECK(table_slots > 0 && (table_slots & (table_slots - 1)) == 0, "unet_instance_overlap: table_slots must be a power of two");
+    hipStream_t st = (hipStream_t)stream;
+    const size_t npx = (size_t)H * W, ng1 = (size_t)ng_max + 1, np1 = (size_t)np_max + 1;
+    unsigned long long *keys = (unsigned long long *)scratch;
+    unsigned *cnt = (unsigned *)((char *)scratch + ov_key_bytes(table_slots));
+    HIP_TRY(hipMemsetAsync(keys, 0xFF, table_slots * sizeof(unsigned long long), st));          // OV_EMPTY
+    HIP_TRY(hipMemsetAsync(cnt, 0, table_slots * sizeof(unsigned), st));
+    HIP_TRY(hipMemsetAsync(area_gt_u32, 0, B * ng1 * sizeof(unsigned), st));
+    HIP_TRY(hipMemsetAsync(area_pred_u32, 0, B * np1 * sizeof(unsigned), st));
+    HIP_TRY(hipMemsetAsync(match_i32, 0, B * ng1 * sizeof(int), st));
+    HIP_TRY(hipMemsetAsync(inter_u32, 0, B * ng1 * sizeof(unsigned), st));
+    HIP_TRY(hipMemsetAsync(status_u64, 0, (size_t)B * 2 * sizeof(unsigned long long), st));
+    hipLaunchKernelGGL(overlap_fill_kernel, dim3((unsigned)std::min<size_t>((npx + 255) / 256, 2048), B), dim3(256), 0, st,
+                       (const int *)gt_i32, (const int *)pred_i32, npx, ng_max, np_max, keys, cnt, table_slots, (unsigned *)area_gt_u32,
+                       (unsigned *)area_pred_u32, (unsigned long long *)status_u64);
+    hipLaunchKernelGGL(overlap_match_kernel, dim3((unsigned)std::min<size_t>((table_slots + 255) / 256, 2048)), dim3(256), 0, st,
+                       (const unsigned long long *)keys, (const unsigned *)cnt, table_slots, ng_max, (const unsigned *)area_gt_u32,
+                       (int *)match_i32, (unsigned *)inter_u32);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}

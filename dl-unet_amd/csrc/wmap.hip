@@ -8,6 +8,8 @@
 //   4. wmap_cols   per pixel, along its column within +-R: nearest foreground (dist_a, label_a), nearest label != label_a (dist_b)
 //   5. wmap_rows   per pixel, over the column results within +-R in x: d1^2, d2^2, then the weight
 //
+// Passes 1-3 are ccl_labels (common.hpp), which instances.hip calls too.
+//
 // Exactness bound: for s = d1 + d2 > R with R = ceil(sqrt(2 sig2 * 104)), expf(-s^2 / (2 sig2)) underflows (e^-104 < 2^-150),
 // so a component farther than R from a pixel cannot change that pixel's weight; every component within R is found
 // exactly by passes 4-5, whose cost depends on R and not on how many components an image has.
@@ -227,6 +229,24 @@ __global__ __launch_bounds__(WM_ROWS) void wmap_rows_kernel(const int *__restric
     w[row + x] = wc + wd;
 }
 
+// passes 1-3 on st (shared with instances.hip): parent and label are int planes [B,H,W]; label = the root, the smallest pixel
+// index of the pixel's component within its image, -1 on background; counts[b] = foreground pixels, n_objects[b] = components
+// (both zeroed here).  The parent words are dead afterwards.  The caller has checked H * W < 2^31, H <= 65535, B <= 65535.
+int ccl_labels(const void *mask, int dtype, int B, int H, int W, int *parent, int *label, unsigned long long *counts, int *n_objects,
+               hipStream_t st)
+{
+    const size_t npx = (size_t)H * W;
+    HIP_TRY(hipMemsetAsync(counts, 0, (size_t)B * sizeof(unsigned long long), st));
+    HIP_TRY(hipMemsetAsync(n_objects, 0, (size_t)B * sizeof(int), st));
+    const int tx = cdiv(W, WM_TILE), ty = cdiv(H, WM_TILE);
+    hipLaunchKernelGGL(ccl_local_kernel, dim3(tx, ty, B), dim3(256), 0, st, mask, dtype, H, W, parent, counts);
+    const int nv = (tx - 1) * H, total = nv + (ty - 1) * W;
+    if (total > 0)
+        hipLaunchKernelGGL(ccl_merge_kernel, dim3(cdiv(total, 256), B), dim3(256), 0, st, mask, dtype, H, W, parent, nv, total);
+    hipLaunchKernelGGL(ccl_flatten_kernel, dim3((unsigned)std::min<size_t>((npx + 255) / 256, 1024), B), dim3(256), 0, st, (const int *)parent, label, npx, n_objects);
+    return 0;
+}
+
 static int wmap_radius(float sig2)
 {
     return (int)std::ceil(std::sqrt(2.0 * (double)sig2 * 104.0));
@@ -255,21 +275,11 @@ int unet_weighted_map(const void *labels, int labels_dtype, int B, int H, int W,
     const int R = wmap_radius(sig2);
     ARG_CHECK(R <= 1024, "unet_weighted_map: sig2 %g gives a reach of %d px (at most 1024)", (double)sig2, R);
     hipStream_t st = (hipStream_t)stream;
-    const size_t npx = (size_t)H * W;
     char *s = (char *)scratch;
     int *parent = (int *)s, *label = (int *)(s + wm_plane(B, H, W));
     unsigned *col_dist = (unsigned *)(s + 2 * wm_plane(B, H, W));
     int *col_label = parent;                                  // the parent words are dead after ccl_flatten
-    HIP_TRY(hipMemsetAsync(counts_u64, 0, (size_t)B * sizeof(unsigned long long), st));
-    HIP_TRY(hipMemsetAsync(n_objects_i32, 0, (size_t)B * sizeof(int), st));
-
-    const int tx = cdiv(W, WM_TILE), ty = cdiv(H, WM_TILE);
-    hipLaunchKernelGGL(ccl_local_kernel, dim3(tx, ty, B), dim3(256), 0, st, labels, labels_dtype, H, W, parent,
-                       (unsigned long long *)counts_u64);
-    const int nv = (tx - 1) * H, total = nv + (ty - 1) * W;
-    if (total > 0)
-        hipLaunchKernelGGL(ccl_merge_kernel, dim3(cdiv(total, 256), B), dim3(256), 0, st, labels, labels_dtype, H, W, parent, nv, total);
-    hipLaunchKernelGGL(ccl_flatten_kernel, dim3((unsigned)std::min<size_t>((npx + 255) / 256, 1024), B), dim3(256), 0, st, (const int *)parent, label, npx, (int *)n_objects_i32);
+    if (int rc = ccl_labels(labels, labels_dtype, B, H, W, parent, label, (unsigned long long *)counts_u64, (int *)n_objects_i32, st)) return rc;
     hipLaunchKernelGGL(wmap_cols_kernel, dim3(cdiv(W, 64), cdiv(H, 4), B), dim3(256), 0, st, (const int *)label, H, W, R,
                        col_label, col_dist);
     const size_t lds = (size_t)(WM_ROWS + 2 * R) * 2 * sizeof(unsigned);

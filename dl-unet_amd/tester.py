@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 import _hip
-from functions import evaluation_metrics, metrics_from_counts
+from functions import evaluation_metrics, label_cells, metrics_from_counts
 import optim as hip_optim
 
 TILE_MARGIN = 92        # context each side of a tile's output that the valid convolutions eat: (S - So) / 2
@@ -117,11 +117,14 @@ def auto_tile_size(H, W, cap=TILE_CAP):
     return S if S <= cap else cap
 
 
-def segment(unet, images, tile_size=None, max_batch=16, normalise=True, return_probs=False):
+def segment(unet, images, tile_size=None, max_batch=16, normalise=True, return_probs=False, return_instances=False):
     """Segment images of any size and shape with the overlap-tile strategy; returns the int64 argmax mask of the same
     shape as `images` (and the float32 foreground probability softmax(logits)[1] with return_probs).  A K-class net
     (Unet(n_classes=K), K > 2) gives the K-way argmax (ties -> the lowest class) and, with return_probs, the softmax of all
-    K classes, [B,K,H,W] ([K,H,W] for a single image) (unet_tile_stitch_k).
+    K classes, [B,K,H,W] ([K,H,W] for a single image) (unet_tile_stitch_k).  With return_instances the returned tuple gains,
+    as its last element, the int32 instance map of the mask, shaped like the mask: 0 where mask == 0, else the number 1..n of
+    the pixel's 4-connected component of mask != 0 in raster order (functions.label_cells, unet_label_components), computed
+    on the device right after the last stitch, on the same stream.
 
     images: device tensor [H,W] or [B,H,W], float32 (uint8 / uint16 are converted once), H, W >= 2.
     tile_size: the network's input size S per tile (16L+60, L even >= 8); None = auto_tile_size(H, W).
@@ -193,7 +196,10 @@ def segment(unet, images, tile_size=None, max_batch=16, normalise=True, return_p
             else:
                 _hip.check(L.unet_tile_stitch_k(_hip.ptr(logits), So, K, oy0, ox0, ny, nx, t0, n, B, H, W, _hip.ptr(mask),
                                                 _hip.ptr(prob), st), "unet_tile_stitch_k")
+        inst = label_cells(mask)[0] if return_instances else None
     if single:
         mask = mask[0]
         prob = prob[0] if prob is not None else None
-    return (mask, prob) if return_probs else mask
+        inst = inst[0] if inst is not None else None
+    out = (mask,) + ((prob,) if return_probs else ()) + ((inst,) if return_instances else ())
+    return out if len(out) > 1 else mask

@@ -283,6 +283,32 @@ int unet_class_balance(const void *labels_i64, int B, int H, int W, void *weight
 size_t unet_weighted_map_scratch_bytes(int B, int H, int W);
 int unet_weighted_map(const void *labels, int labels_dtype, int B, int H, int W, float w0, float sig2, void *weights_f32,
                       void *counts_u64, void *n_objects_i32, void *scratch, void *stream);
+/* Cell instances of a foreground mask, replaces cv.connectedComponents as the reference calls it to number objects
+ * (functions.py:47 with connectivity=4, the rule used here; data.py:375 when it writes the man_seg instance images; touching
+ * cells are carved apart beforehand by preprocess_gt, data.py:195-219): mask [B,H,W], int64 (dtype 0) or float32 (1),
+ * foreground = value != 0; H != W allowed, down to 1 x 1.  labels_i32 [B,H,W]: 0 on background, else the number 1..n of the
+ * pixel's 4-connected component, the components numbered in raster order of their first pixel (scipy.ndimage.label's and
+ * OpenCV's numbering); n_objects_i32 [B] = n.  Exact, and the cost does not depend on n.
+ * scratch: unet_label_components_scratch_bytes(B, H, W), initialised by the call.                                        */
+size_t unet_label_components_scratch_bytes(int B, int H, int W);
+int unet_label_components(const void *mask, int dtype, int B, int H, int W, void *labels_i32, void *n_objects_i32, void *scratch,
+                          void *stream);
+/* The integers of the Cell Tracking Challenge SEG measure, the score behind the goals of trainer.py:20-26 (Ronneberger et al.
+ * 2015, Table 2): gt_i32, pred_i32 id maps int32 [B,H,W], 0 = background, gt ids anywhere in [0, ng_max] (not necessarily
+ * consecutive, an object not necessarily connected), pred ids in [0, np_max]; ng_max, np_max < 2^24.
+ *   area_gt_u32 [B][ng_max+1], area_pred_u32 [B][np_max+1] : pixels per id (index 0 = background)
+ *   match_i32 [B][ng_max+1] : for g >= 1 the p >= 1 with 2 |g n p| > area_gt[g] (strict, so at most one), else 0;  [b][0] = 0
+ *   inter_u32 [B][ng_max+1] : that |g n p|, else 0
+ *   status_u64 [B][2]       : {pixels whose gt or pred id is outside its range (negative included): used as no index and
+ *                              counted nowhere else;  pixels dropped because the pair table was full: if non-zero, match and
+ *                              inter of that image are invalid and the caller repeats the call with a larger table}
+ * table_slots: a power of two, the slots of the open-addressing table of distinct (b, g, p) pairs with g, p >= 1, shared by
+ * the batch; a table with more slots than B*H*W cannot fill up.  Exact integer atomics: results are the same in every run.
+ * scratch: unet_instance_overlap_scratch_bytes(B, ng_max, np_max, table_slots), initialised by the call.                 */
+size_t unet_instance_overlap_scratch_bytes(int B, int ng_max, int np_max, size_t table_slots);
+int unet_instance_overlap(const void *gt_i32, const void *pred_i32, int B, int H, int W, int ng_max, int np_max, size_t table_slots,
+                          void *area_gt_u32, void *area_pred_u32, void *match_i32, void *inter_u32, void *status_u64, void *scratch,
+                          void *stream);
 /* N1, replaces elastic_transform's two steps (data.py:225-245): scipy.ndimage.gaussian_filter(field,
  * sigma, mode="constant") * scale as two 1-D passes with the caller's normalised taps [2*radius+1], and
  * map_coordinates(img, (row+dy, col+dx), order=1) (bilinear, 0 outside [0,n-1]).                       */
