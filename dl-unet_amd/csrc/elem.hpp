@@ -1,6 +1,7 @@
 // elem.hpp — what the HBM-bound kernels (direct.hip, multiclass.hip, tile.hip, aux.hip) share:
 //   device : 4 consecutive channels of an activation tensor stored as fp32 (16 B) or bf16 (8 B, arithmetic mode 2), read /
-//            written as 4 floats; the sum of one value per thread over a 256-thread block
+//            written as 4 floats; the sum of one value per thread over a 256-thread block, and (instances.hip, prepare.hip) the
+//            exclusive prefix of one int per thread over it
 //   host   : the grid size of a grid-stride launch, and the dispatch of a launch on element size, channel width and padded
 //            class count (the launch bracket, profiled(), is common.hpp's)
 #pragma once
@@ -44,6 +45,28 @@ __device__ __forceinline__ V block_sum256(V v)
     }
     return red[0];
 }
+// exclusive prefix of v over the 256 threads of the workgroup, and their sum
+__device__ __forceinline__ int block_scan256(int v, int &total)
+{
+    __shared__ int wave_sum[4];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    int inc = v;
+    for (int d = 1; d < 64; d <<= 1) {
+        const int t = __shfl_up(inc, d, 64);
+        if (lane >= d) inc += t;
+    }
+    __syncthreads();                                        // the previous call's reads of wave_sum are done
+    if (lane == 63) wave_sum[w] = inc;
+    __syncthreads();
+    int before = 0;
+    total = 0;
+    for (int i = 0; i < 4; ++i) {
+        if (i < w) before += wave_sum[i];
+        total += wave_sum[i];
+    }
+    return before + inc - v;
+}
+
 static inline int grid_for(size_t total, int per_block = 256, int cap = 8192)
 {
     size_t g = (total + per_block - 1) / per_block;

@@ -22,7 +22,7 @@
 // Coherence (wmap.hip's rule): inside overlap_fill a table key is only ever touched by an agent-scope compare-and-swap, a
 // counter, a histogram bin or a status word only by an agent-scope add; overlap_match, and every pass of the labelling, reads
 // what an earlier kernel wrote.  No word is handed from one workgroup to another inside a kernel by plain loads and stores.
-#include "common.hpp"
+#include "elem.hpp"
 #include <algorithm>
 #include "../../include/unet_hip.h"
 
@@ -32,28 +32,6 @@ static constexpr int IN_CHUNK = 1024;                        // pixels per workg
 static constexpr unsigned long long OV_EMPTY = ~0ull;        // never a key: b <= 65534
 static constexpr int OV_ID_BITS = 24;
 static constexpr int OV_ID_MAX = (1 << OV_ID_BITS) - 1;
-
-// exclusive prefix of v over the 256 threads of the workgroup, and their sum
-__device__ __forceinline__ int block_scan256(int v, int &total)
-{
-    __shared__ int wave_sum[4];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int inc = v;
-    for (int d = 1; d < 64; d <<= 1) {
-        const int t = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += t;
-    }
-    __syncthreads();                                        // the previous call's reads of wave_sum are done
-    if (lane == 63) wave_sum[w] = inc;
-    __syncthreads();
-    int before = 0;
-    total = 0;
-    for (int i = 0; i < 4; ++i) {
-        if (i < w) before += wave_sum[i];
-        total += wave_sum[i];
-    }
-    return before + inc - v;
-}
 
 // roots among this thread's 4 consecutive pixels, as a bit mask
 __device__ __forceinline__ int inst_roots(const int *__restrict__ L, size_t npx, size_t e0)

@@ -7,8 +7,14 @@
   elastic_transform(images, a, s)    data.py:225-245   Simard-2003 elastic deformation (N1)
   reflect_rotate_crop(images, deg)   data.py:106-125   reflect pad + cubic-spline rotation + centre crop, fused (N1)
   augment(image, target, ...)        data.py:97-135    ImageDataset.__getitem__ after the file reads, on the device
+  preprocess_gt(img)                 data.py:195-221   borders carved between touching cells of an instance image
+  binary_target(img)                 data.py:63-64     preprocess_gt + cv.threshold(gt, 0, 255): the {0,255} training target
+  crop_distribution(target, crop)    data.py:67-82     the crop origins and their weights (foreground share close to one half)
+  draw_crop(rng, pairs, p, ...)      data.py:98-103    one origin from that distribution + jitter, in the reference's RNG order
+  CropDataset(images, instances, ..) data.py:23-137    ImageDataset on arrays that are already read: an iterable of batches
 
-Datasets, file readers, downloaders and the OpenCV label preprocessing are out of scope.
+File and TIFF reading, the ST/GT folder handling of ImageDataset.__init__ and the downloaders are out of scope (SURVEY §2
+rows 9, 13).
 """
 import ctypes as _C
 
@@ -161,3 +167,175 @@ def augment(image, target, crop_xy, crop, rot_deg, alpha, sigma, random_state=No
     if batched:
         return inp[:, None], gt[:, None]
     return inp[0][None], gt[0][None]
+
+
+# ---- from instance images to targets and weighted crops (prepare.hip) -----------------------------------------------------
+
+def _device_only(t, name, entry):
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise NotImplementedError("%s runs on the HIP device only (%s): move the tensor to the device first, e.g. %s(x.cuda()); "
+                                  "there is no CPU implementation" % (name, entry, name))
+
+
+def _planes(t, name):
+    """[H,W] or [B,H,W] -> contiguous [B,H,W]"""
+    if t.dim() not in (2, 3):
+        raise ValueError("%s takes [H,W] or [B,H,W], got %s" % (name, tuple(t.shape)))
+    if t.numel() == 0:
+        raise ValueError("%s: empty input %s" % (name, tuple(t.shape)))
+    return (t[None] if t.dim() == 2 else t).contiguous()
+
+
+def _int_code(x, uint8_ok):
+    """The tensor in one of the widths the library reads, and its dtype code: float -> float32 (1), int64 and the unsigned
+    types int32 cannot hold -> int64 (0), uint8 stays where the entry point takes it (3), every other integer type (uint16
+    from a numpy-born image included) and bool -> int32 (2)."""
+    if x.is_floating_point():
+        return x.float(), 1
+    if x.dtype == torch.uint8 and uint8_ok:
+        return x, 3
+    if x.dtype in (torch.int64, torch.uint32, torch.uint64):
+        return x.to(torch.int64), 0
+    return x.to(torch.int32), 2
+
+
+def _reach(kernel, iterations):
+    kernel, iterations = int(kernel), int(iterations)
+    if kernel < 1 or kernel % 2 == 0 or iterations < 0:
+        raise ValueError("preprocess_gt: kernel must be odd and positive, iterations non-negative")
+    reach = iterations * (kernel - 1) // 2
+    if reach > 8:
+        raise ValueError("preprocess_gt: iterations * (kernel - 1) / 2 = %d, the device op reaches 8 pixels at the most" % reach)
+    return reach
+
+
+def _carve(img, name, kernel, iterations, want):
+    """unet_carve_borders on img; want = which of (gt, edges, bin) to form.  One read-back: the status words."""
+    _device_only(img, name, "unet_carve_borders")
+    reach = _reach(kernel, iterations)
+    x, code = _int_code(_planes(img, name), False)
+    B, H, W = x.shape
+    dev = x.device
+    outs = [torch.empty(B, H, W, dtype=dt, device=dev) if w else None
+            for w, dt in zip(want, (torch.float32, torch.float32, torch.uint8))]
+    status = torch.empty(B, dtype=torch.int64, device=dev)
+    _hip.run("unet_carve_borders", dev, _hip.ptr(x), code, B, H, W, reach, _hip.ptr(outs[0]), _hip.ptr(outs[1]), _hip.ptr(outs[2]),
+             _hip.ptr(status))
+    bad = int(status.sum())
+    if bad:
+        raise ValueError("%s: %d pixels hold ids outside [0, 2^24)" % (name, bad))
+    return [o if o is None or img.dim() == 3 else o[0] for o in outs]
+
+
+def preprocess_gt(img, kernel=5, iterations=2):
+    """The reference's preprocess_gt (data.py:195-221) on a HIP device: img is an instance image [H,W] or a stack [B,H,W], 0 =
+    background and any ids in [1, 2^24) on the cells, of any integer dtype or float (a uint16 image born in numpy goes through
+    int32).  Every cell is dilated `iterations` times with a kernel x kernel rectangle, and the ring it gained counts 255 in
+    mask_global; gt = img - mask_global clipped at 0, so touching cells are carved apart.  Returns (gt, mask_global) of the
+    input's shape.  Same name and meaning as the reference; only the float width differs: float32 here, float64 there, and every
+    value is an integer below 2^24, which both hold exactly.  The cost does not depend on the number of cells.
+    Ids outside [0, 2^24) raise ValueError (one read-back); host tensors raise NotImplementedError (no CPU path)."""
+    gt, edges, _ = _carve(img, "preprocess_gt", kernel, iterations, (True, True, False))
+    return gt, edges
+
+
+def binary_target(img, kernel=5, iterations=2):
+    """The training target the reference's datasets keep (data.py:63-64, :162-163): preprocess_gt, then
+    cv.threshold(gt, 0, 255, THRESH_BINARY).  uint8 {0,255} of img's shape, formed in the same kernel."""
+    return _carve(img, "binary_target", kernel, iterations, (False, False, True))[2]
+
+
+def crop_probabilities(counts, crop):
+    """Host half of crop_distribution: counts [..., ny, nx] = foreground pixels per window -> float64 [..., ny * nx], the
+    reference's weights (data.py:73-82): x = np.mean(window) / 255 with its two roundings, 0 outside [0.1, 0.9], else
+    10 * norm.pdf(x, 0.5, 0.05) written out; each image's row is divided by its sum, or uniform when the sum is 0."""
+    c = np.asarray(counts).astype(np.float64)
+    c = c.reshape(c.shape[:-2] + (-1,))
+    x = ((255.0 * c) / (crop * crop)) / 255
+    z = (x - 0.5) / 0.05
+    prob = np.where((x < 0.1) | (x > 0.9), 0.0, 10 * (np.exp(-z ** 2 / 2.0) / np.sqrt(2 * np.pi) / 0.05))
+    out = np.empty_like(prob)
+    for idx in np.ndindex(prob.shape[:-1]):
+        row = prob[idx]
+        total = np.sum(row)
+        out[idx] = np.ones(len(row)) / len(row) if total == 0 else row / total
+    return out
+
+
+def crop_distribution(target, crop, skip=10):
+    """The reference's weighted crop distribution (data.py:67-82) of a target [H,W] or [B,H,W] on a HIP device (foreground =
+    value != 0, e.g. binary_target's output): returns (pairs, p), pairs the list of window origins (ii, jj) over
+    range(0, H - crop, skip) x range(0, W - crop, skip), p float64 numpy [B, len(pairs)] ([1, ...] for a single image), each
+    row the distribution of one image.  The window counts are exact integers from the device (unet_crop_counts), read back
+    once; the weights are formed from them on the host in float64 (crop_probabilities).  An image no larger than the crop has
+    no window: ValueError.  Host tensors raise NotImplementedError (no CPU path)."""
+    _device_only(target, "crop_distribution", "unet_crop_counts")
+    x, code = _int_code(_planes(target, "crop_distribution"), True)
+    B, H, W = x.shape
+    crop, skip = int(crop), int(skip)
+    if crop < 1 or skip < 1 or H <= crop or W <= crop:
+        raise ValueError("crop_distribution: no window of %d in a %d x %d image with skip %d" % (crop, H, W, skip))
+    pairs = [(ii, jj) for ii in range(0, H - crop, skip) for jj in range(0, W - crop, skip)]
+    ny, nx = len(range(0, H - crop, skip)), len(range(0, W - crop, skip))
+    counts = torch.empty(B, ny, nx, dtype=torch.int32, device=x.device)      # the library's u32 words: at most crop^2 < 2^31
+    scratch = torch.empty(_hip.lib().unet_crop_counts_scratch_bytes(B, H, W, crop, skip), dtype=torch.uint8, device=x.device)
+    _hip.run("unet_crop_counts", x.device, _hip.ptr(x), code, B, H, W, crop, skip, _hip.ptr(counts), _hip.ptr(scratch))
+    return pairs, crop_probabilities(counts.cpu().numpy(), crop)
+
+
+def draw_crop(rng, pairs, p_row, shape, crop, skip=10):
+    """One crop origin (x, y) as ImageDataset.__getitem__ draws it (data.py:98-103), host only: rng is a
+    numpy.random.RandomState (the reference uses the global one) and is consumed in the reference's order: choice over the
+    pairs with weights p_row, randint for the row jitter, randint for the column jitter; both are then clamped to
+    [0, dim - crop].  The reference draws the angle next: rng.choice(np.arange(0, 360, 30)) (data.py:115)."""
+    crop_id = rng.choice(range(len(pairs)), 1, p=p_row)[0]
+    x, y = pairs[crop_id]
+    x += rng.randint(-skip / 2, (skip / 2) + 1)
+    y += rng.randint(-skip / 2, (skip / 2) + 1)
+    x = min(max(0, x), shape[0] - crop)
+    y = min(max(0, y), shape[1] - crop)
+    return int(x), int(y)
+
+
+class CropDataset:
+    """The reference's ImageDataset (data.py:23-137) on arrays that are already read: images [N,H,W] grey levels and instances
+    [N,H,W] man_seg instance images (numpy arrays or tensors).  At construction binary_target and crop_distribution run once
+    for all N on the device; a [N,H,W] stack has one shape, so `pairs` is built from that shape and applies to every image, as
+    the reference builds it from its first image (data.py:67-68).  Iterating yields len(self) batches of batch_size consecutive
+    samples (the last may be shorter): per sample the crop origin (draw_crop) and then the angle are drawn from rng in the
+    reference's order, and the batch goes through one data.augment call, so each item is (inp [B,1,S,S] float32,
+    gt [B,1,crop,crop] int64) on the device - usable as train_loader / val_loader of trainer.training as it is.  The elastic
+    fields come from random_state (a numpy RandomState, drawn as the reference's elastic_transform draws them), or from the
+    device generator when it is None."""
+
+    def __init__(self, images, instances, alpha, sigma, crop, batch_size, rng, levels=255, *, random_state=None, skip=10, device=None):
+        if device is None:
+            device = images.device if torch.is_tensor(images) and images.is_cuda else torch.device("cuda", torch.cuda.current_device())
+        self.device = torch.device(device)
+        as_tensor = lambda a: (a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))).to(self.device)
+        self.image = as_tensor(images).float()
+        inst = as_tensor(instances)
+        if self.image.dim() != 3 or inst.shape != self.image.shape:
+            raise ValueError("CropDataset takes images and instances of one shape [N,H,W], got %s and %s"
+                             % (tuple(self.image.shape), tuple(inst.shape)))
+        self.alpha, self.sigma, self.crop, self.skip, self.levels = alpha, sigma, int(crop), int(skip), levels
+        self.batch_size = int(batch_size)
+        self.rng, self.random_state = rng, random_state
+        self.target = binary_target(inst)
+        self.pairs, self.target_weighted_crop_distribution = crop_distribution(self.target, self.crop, self.skip)
+
+    def __len__(self):
+        return -(-self.image.shape[0] // self.batch_size)
+
+    def draw(self, idx):
+        """(crop origin, angle) of sample idx, consuming rng as the reference's __getitem__ does"""
+        xy = draw_crop(self.rng, self.pairs, self.target_weighted_crop_distribution[idx], self.image.shape[1:], self.crop, self.skip)
+        return xy, self.rng.choice(np.arange(0, 360, 30))
+
+    def __iter__(self):
+        N = self.image.shape[0]
+        for lo in range(0, N, self.batch_size):
+            idx = list(range(lo, min(N, lo + self.batch_size)))
+            draws = [self.draw(i) for i in idx]
+            yield augment(self.image[idx], self.target[idx], [d[0] for d in draws], self.crop, [d[1] for d in draws], self.alpha,
+                          self.sigma, random_state=self.random_state, levels=self.levels)

@@ -309,6 +309,31 @@ size_t unet_instance_overlap_scratch_bytes(int B, int ng_max, int np_max, size_t
 int unet_instance_overlap(const void *gt_i32, const void *pred_i32, int B, int H, int W, int ng_max, int np_max, size_t table_slots,
                           void *area_gt_u32, void *area_pred_u32, void *match_i32, void *inter_u32, void *status_u64, void *scratch,
                           void *stream);
+/* Carved training targets from an instance image, replaces preprocess_gt (data.py:195-221: per cell, cv.dilate with a 5 x 5
+ * rectangle, iterations=2, and 255 added on the ring the cell gained) and the cv.threshold(gt, 0, 255, THRESH_BINARY) after it
+ * (data.py:64, :163).  ids [B,H,W], dtype 0 = int64, 1 = float32 holding integral values, 2 = int32 (what
+ * unet_label_components writes); 0 = background, objects any ids in [1, 2^24), not necessarily consecutive or connected; H != W
+ * allowed, down to 1 x 1.  reach = iterations * (kernel - 1) / 2 (4 for the reference), 0 <= reach <= 8: the iterated
+ * rectangles are one (2 reach + 1)^2 rectangle clipped to the image.  With n(p) = the number of distinct ids other than 0 and
+ * id(p) in that window around p:
+ *   edges_f32 [B,H,W] = 255 n           (mask_global)
+ *   gt_f32    [B,H,W] = max(0, id - 255 n)
+ *   bin_u8    [B,H,W] = 255 where gt > 0, else 0
+ * each may be NULL, not all three.  Every value is an integer below 2^24, exact in fp32.  status_u64 [B] = pixels whose id is
+ * outside [0, 2^24) (negative and NaN included): such a pixel is background everywhere and indexes nothing.  Exact; the cost
+ * depends on reach and on the image size, never on the number of cells.  No scratch.                                        */
+int unet_carve_borders(const void *ids, int dtype, int B, int H, int W, int reach, void *gt_f32, void *edges_f32, void *bin_u8,
+                       void *status_u64, void *stream);
+/* The integers behind the weighted crop distribution, replaces the np.mean(gt_bin[ii:ii+crop, jj:jj+crop]) of every window of
+ * ImageDataset.__init__ (data.py:67-82).  mask [B,H,W], dtype 0 = int64, 1 = float32, 2 = int32, 3 = uint8; foreground =
+ * value != 0.  counts_u32 [B][ny][nx], ny = ceil((H - crop) / skip), nx = ceil((W - crop) / skip) (= len(range(0, H - crop,
+ * skip)), ...): counts[b][i][j] = foreground pixels of rows [skip i, skip i + crop) x columns [skip j, skip j + crop).  Exact,
+ * from per-row prefix sums: no pixel is read once per window.  H <= crop, W <= crop, crop < 1 or skip < 1 leave the reference
+ * no window to draw from: UNET_E_BADARG (and 0 scratch bytes).  H * W < 2^31.
+ * scratch: unet_crop_counts_scratch_bytes(B, H, W, crop, skip), initialised by the call.                                   */
+size_t unet_crop_counts_scratch_bytes(int B, int H, int W, int crop, int skip);
+int unet_crop_counts(const void *mask, int dtype, int B, int H, int W, int crop, int skip, void *counts_u32, void *scratch,
+                     void *stream);
 /* N1, replaces elastic_transform's two steps (data.py:225-245): scipy.ndimage.gaussian_filter(field,
  * sigma, mode="constant") * scale as two 1-D passes with the caller's normalised taps [2*radius+1], and
  * map_coordinates(img, (row+dy, col+dx), order=1) (bilinear, 0 outside [0,n-1]).                       */
