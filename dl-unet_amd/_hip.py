@@ -85,7 +85,11 @@ _SIGS = {
     "unet_label_components": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]),
     "unet_instance_overlap_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_size_t]),
     "unet_instance_overlap": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, vp, vp, vp, vp, vp, vp, vp]),
-    "unet_carve_borders": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp]),
+    "unet_partition_pairs_scratch_bytes": (C.c_size_t, [C.c_int, C.c_size_t]),
+    "unet_partition_pairs": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, vp, vp, vp, vp, vp, vp]),
+    "unet_grow_labels_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "unet_grow_labels": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_longlong, vp, vp, vp]),
+    "unet_carve_borders":(C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp]),
     "unet_crop_counts_scratch_bytes": (C.c_size_t, [C.c_int] * 5),
     "unet_crop_counts": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
     "unet_gaussian_filter": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_float, vp, vp, vp]),

@@ -19,8 +19,15 @@
 // Every count is an integer sum: the outputs do not depend on the order of the atomics.  Which slot a key lands in does, and
 // nothing reads that.
 //
+// unet_partition_pairs: the contingency table of two id maps restricted to ground-truth foreground, which the Rand and information
+// scores of the ISBI 2012 challenge (Ronneberger et al. 2015, Table 1) are sums over:
+//   1. overlap_fill<FG>  the same wave loop and table, for every pixel with gt >= 1 and any pred >= 0; no histograms
+//   2. pairs_compact     a wave reads 64 slots, one agent-scope add on n_pairs gives it a block of the dense (key, count) list
+// The list's order depends on the order of those adds; its content does not.
+//
 // Coherence (wmap.hip's rule): inside overlap_fill a table key is only ever touched by an agent-scope compare-and-swap, a
-// counter, a histogram bin or a status word only by an agent-scope add; overlap_match, and every pass of the labelling, reads
+// counter, a histogram bin or a status word only by an agent-scope add, and n_pairs in pairs_compact likewise; overlap_match,
+// pairs_compact, and every pass of the labelling, reads
 // what an earlier kernel wrote.  No word is handed from one workgroup to another inside a kernel by plain loads and stores.
 #include "elem.hpp"
 #include <algorithm>
@@ -115,6 +122,9 @@ __device__ __forceinline__ bool ov_insert(unsigned long long *keys, unsigned *cn
     return false;
 }
 
+// FG = false: unet_instance_overlap (both area histograms, pairs with g, p >= 1).  FG = true: unet_partition_pairs (no histogram,
+// pairs with g >= 1 and any p >= 0: the table restricted to ground-truth foreground, "predicted background" being the column 0)
+template <bool FG>
 __global__ __launch_bounds__(256) void overlap_fill_kernel(const int *__restrict__ gt, const int *__restrict__ pred, size_t npx,
                                                            int ng_max, int np_max, unsigned long long *keys, unsigned *cnt,
                                                            size_t slots, unsigned *area_gt, unsigned *area_pred,
@@ -122,7 +132,7 @@ __global__ __launch_bounds__(256) void overlap_fill_kernel(const int *__restrict
 {
     const int b = blockIdx.y, lane = threadIdx.x & 63;
     const int *G = gt + (size_t)b * npx, *P = pred + (size_t)b * npx;
-    unsigned *ag = area_gt + (size_t)b * (ng_max + 1), *ap = area_pred + (size_t)b * (np_max + 1);
+    unsigned *ag = FG ? nullptr : area_gt + (size_t)b * (ng_max + 1), *ap = FG ? nullptr : area_pred + (size_t)b * (np_max + 1);
     unsigned long long bad = 0, dropped = 0, g0 = 0, p0 = 0;      // this lane's share of status[b][0..1] and of the two bins 0
     bool full = false;                                            // the table only fills up: after one failed probe, stop probing
     const size_t stride = (size_t)gridDim.x * blockDim.x;
@@ -140,9 +150,11 @@ __global__ __launch_bounds__(256) void overlap_fill_kernel(const int *__restrict
         if (head && in) {
             if (!ok) bad += n;
             else {
-                if (g) __hip_atomic_fetch_add(&ag[g], n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); else g0 += n;
-                if (p) __hip_atomic_fetch_add(&ap[p], n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); else p0 += n;
-                if (g && p) {
+                if constexpr (!FG) {
+                    if (g) __hip_atomic_fetch_add(&ag[g], n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); else g0 += n;
+                    if (p) __hip_atomic_fetch_add(&ap[p], n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); else p0 += n;
+                }
+                if (g && (FG || p)) {
                     const unsigned long long key = (unsigned long long)b << (2 * OV_ID_BITS) | (unsigned long long)g << OV_ID_BITS | (unsigned)p;
                     if (full || !ov_insert(keys, cnt, slots, key, n)) { dropped += n; full = true; }
                 }
@@ -154,8 +166,10 @@ __global__ __launch_bounds__(256) void overlap_fill_kernel(const int *__restrict
     if (lane == 0) {
         if (bad) __hip_atomic_fetch_add(&status[2 * b], bad, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (dropped) __hip_atomic_fetch_add(&status[2 * b + 1], dropped, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (g0) __hip_atomic_fetch_add(&ag[0], (unsigned)g0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (p0) __hip_atomic_fetch_add(&ap[0], (unsigned)p0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if constexpr (!FG) {
+            if (g0) __hip_atomic_fetch_add(&ag[0], (unsigned)g0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (p0) __hip_atomic_fetch_add(&ap[0], (unsigned)p0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
     }
 }
 
@@ -171,6 +185,32 @@ __global__ __launch_bounds__(256) void overlap_match_kernel(const unsigned long 
         const size_t o = b * (ng_max + 1) + g;
         const unsigned c = cnt[s];
         if (2ull * c > area_gt[o]) { match[o] = p; inter[o] = c; }      // strict: no two p can both hold more than half of g
+    }
+}
+
+// the occupied slots, densely: a wave reads 64 consecutive slots and its first occupied lane takes the wave's block of output
+// indices with one agent-scope add on n_pairs; which block a wave gets depends on the order of those adds, so the list's order is
+// unspecified (the caller sorts it).  At most `slots` slots are occupied: every index is inside the [slots] outputs.
+__global__ __launch_bounds__(256) void pairs_compact_kernel(const unsigned long long *__restrict__ keys, const unsigned *__restrict__ cnt,
+                                                            size_t slots, unsigned long long *__restrict__ pair_keys,
+                                                            unsigned *__restrict__ pair_counts, unsigned long long *n_pairs)
+{
+    const int lane = threadIdx.x & 63;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t base = (size_t)blockIdx.x * blockDim.x + (threadIdx.x & ~63); base < slots; base += stride) {   // wave-uniform
+        const size_t s = base + lane;
+        const unsigned long long key = s < slots ? keys[s] : OV_EMPTY;
+        const unsigned long long occupied = __ballot(key != OV_EMPTY);
+        if (!occupied) continue;
+        const int leader = __ffsll(occupied) - 1;
+        unsigned long long first = 0;
+        if (lane == leader) first = __hip_atomic_fetch_add(n_pairs, (unsigned long long)__popcll(occupied), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        first = __shfl(first, leader, 64);
+        if (key != OV_EMPTY) {
+            const size_t o = first + __popcll(occupied & ((1ull << lane) - 1));
+            pair_keys[o] = key;
+            pair_counts[o] = cnt[s];
+        }
     }
 }
 
@@ -241,12 +281,45 @@ int unet_instance_overlap(const void *gt_i32, const void *pred_i32, int B, int H
     HIP_TRY(hipMemsetAsync(match_i32, 0, B * ng1 * sizeof(int), st));
     HIP_TRY(hipMemsetAsync(inter_u32, 0, B * ng1 * sizeof(unsigned), st));
     HIP_TRY(hipMemsetAsync(status_u64, 0, (size_t)B * 2 * sizeof(unsigned long long), st));
-    hipLaunchKernelGGL(overlap_fill_kernel, dim3((unsigned)std::min<size_t>((npx + 255) / 256, 2048), B), dim3(256), 0, st,
+    hipLaunchKernelGGL(overlap_fill_kernel<false>, dim3((unsigned)std::min<size_t>((npx + 255) / 256, 2048), B), dim3(256), 0, st,
                        (const int *)gt_i32, (const int *)pred_i32, npx, ng_max, np_max, keys, cnt, table_slots, (unsigned *)area_gt_u32,
                        (unsigned *)area_pred_u32, (unsigned long long *)status_u64);
     hipLaunchKernelGGL(overlap_match_kernel, dim3((unsigned)std::min<size_t>((table_slots + 255) / 256, 2048)), dim3(256), 0, st,
                        (const unsigned long long *)keys, (const unsigned *)cnt, table_slots, ng_max, (const unsigned *)area_gt_u32,
                        (int *)match_i32, (unsigned *)inter_u32);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+size_t unet_partition_pairs_scratch_bytes(int B, size_t table_slots)
+{
+    if (B <= 0 || table_slots == 0) return 0;
+    return ov_key_bytes(table_slots) + align_up(table_slots * sizeof(unsigned), 256);
+}
+
+int unet_partition_pairs(const void *gt_i32, const void *pred_i32, int B, int H, int W, int ng_max, int np_max, size_t table_slots,
+                         void *pair_keys_u64, void *pair_counts_u32, void *n_pairs_u64, void *status_u64, void *scratch, void *stream)
+{
+    ARG_CHECK(gt_i32 && pred_i32 && pair_keys_u64 && pair_counts_u32 && n_pairs_u64 && status_u64 && scratch && B > 0 && H > 0 && W > 0,
+              "unet_partition_pairs: bad argument");
+    ARG_CHECK((size_t)H * W < (1u << 31) && B <= 65535, "unet_partition_pairs: image too large");
+    ARG_CHECK(ng_max >= 0 && np_max >= 0 && ng_max <= OV_ID_MAX && np_max <= OV_ID_MAX,
+              "unet_partition_pairs: ng_max and np_max must be in [0, %d]", OV_ID_MAX);
+    ARG_CHECK(table_slots > 0 && (table_slots & (table_slots - 1)) == 0, "unet_partition_pairs: table_slots must be a power of two");
+    hipStream_t st = (hipStream_t)stream;
+    const size_t npx = (size_t)H * W;
+    unsigned long long *keys = (unsigned long long *)scratch;
+    unsigned *cnt = (unsigned *)((char *)scratch + ov_key_bytes(table_slots));
+    HIP_TRY(hipMemsetAsync(keys, 0xFF, table_slots * sizeof(unsigned long long), st));          // OV_EMPTY
+    HIP_TRY(hipMemsetAsync(cnt, 0, table_slots * sizeof(unsigned), st));
+    HIP_TRY(hipMemsetAsync(n_pairs_u64, 0, sizeof(unsigned long long), st));
+    HIP_TRY(hipMemsetAsync(status_u64, 0, (size_t)B * 2 * sizeof(unsigned long long), st));
+    hipLaunchKernelGGL(overlap_fill_kernel<true>, dim3((unsigned)std::min<size_t>((npx + 255) / 256, 2048), B), dim3(256), 0, st,
+                       (const int *)gt_i32, (const int *)pred_i32, npx, ng_max, np_max, keys, cnt, table_slots, (unsigned *)nullptr,
+                       (unsigned *)nullptr, (unsigned long long *)status_u64);
+    hipLaunchKernelGGL(pairs_compact_kernel, dim3((unsigned)std::min<size_t>((table_slots + 255) / 256, 2048)), dim3(256), 0, st,
+                       (const unsigned long long *)keys, (const unsigned *)cnt, table_slots, (unsigned long long *)pair_keys_u64,
+                       (unsigned *)pair_counts_u32, (unsigned long long *)n_pairs_u64);
     HIP_TRY(hipGetLastError());
     return 0;
 }

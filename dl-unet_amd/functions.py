@@ -6,9 +6,13 @@ names, arguments and results (functions.py:82-213).  They are host-side bookkeep
 border-weighted loss map) runs on the device only (unet_weighted_map); the reference's own OpenCV path has no
 host counterpart here.  label_cells and seg_measure are extensions, device only as well: the cell instances of a mask
 (unet_label_components) and the Cell Tracking Challenge SEG measure of two instance maps (unet_instance_overlap), the score
-the goals of trainer.py:20-26 are stated in.
+the goals of trainer.py:20-26 are stated in.  grow_cells, pair_table and rand_scores extend them to the other table those goals
+quote (Ronneberger et al. 2015, Table 1, ISBI 2012): nearest-cell growth of an instance map (unet_grow_labels), the contingency
+table of two instance maps on ground-truth foreground (unet_partition_pairs), and the Rand and information scores formed from it.
 """
 import collections
+import fractions
+import math
 
 import numpy as np
 import torch
@@ -145,6 +149,190 @@ def seg_measure(pred_labels, gt_labels, *, _table_slots=None):
             break
         slots *= 2                      # ends: a table with more slots than pixels cannot fill up
     return seg_from_counts(area_gt.cpu().numpy(), area_pred.cpu().numpy(), match.cpu().numpy(), inter.cpu().numpy())
+
+
+def _id_maps(name, entry, *maps):
+    """The checks seg_measure makes of its id maps, for the ops that take one or two: equal shape, rank, dtype, size (ValueError,
+    on any device), then the device (NotImplementedError); returns them as contiguous [B,H,W]."""
+    if any(t.shape != maps[0].shape for t in maps) or maps[0].dim() not in (2, 3):
+        raise ValueError("%s takes id maps of equal shape [H,W] or [B,H,W], got %s" % (name, ", ".join(str(tuple(t.shape)) for t in maps)))
+    for t in maps:
+        if t.dtype not in (torch.int32, torch.int64):
+            raise ValueError("%s takes int32 or int64 id maps, got %s" % (name, t.dtype))
+    if maps[0].numel() == 0:
+        raise ValueError("%s: empty id maps %s" % (name, tuple(maps[0].shape)))
+    if not all(t.is_cuda for t in maps):
+        raise NotImplementedError("%s runs on the HIP device only (%s): move the label maps to the device first, e.g. with "
+                                  ".cuda(); there is no CPU implementation" % (name, entry))
+    return [(t[None] if t.dim() == 2 else t).contiguous() for t in maps]
+
+
+def _id_range(name, *maps):
+    """(max id of each map), read back in one copy; negative ids and ids >= 2^24 raise ValueError."""
+    lo = maps[0].min()
+    for t in maps[1:]:
+        lo = torch.minimum(lo, t.min())
+    vals = [int(v) for v in torch.stack([lo.long()] + [t.max().long() for t in maps]).tolist()]
+    if vals[0] < 0:
+        raise ValueError("%s: negative ids (the smallest is %d)" % (name, vals[0]))
+    if max(vals[1:]) >= 1 << 24:
+        raise ValueError("%s: ids must be below 2^24, got up to %d" % (name, max(vals[1:])))
+    return vals[1:]
+
+
+def grow_cells(labels, max_distance=None):
+    """Nearest-cell growth of an instance map (border thinning; skimage.segmentation.expand_labels with an exact metric and a
+    stated tie rule): int32 / int64 ids [H,W] or [B,H,W] on a HIP device, 0 = background, ids in [1, 2^24), not necessarily
+    consecutive or connected.  Returns an int32 map of the same shape: a pixel with id != 0 keeps it; a background pixel takes
+    the id of the labelled pixel at the smallest exact squared Euclidean distance d^2, the smallest id among those at that d^2.
+    max_distance (a float >= 0): only labelled pixels with d^2 <= floor(max_distance^2) count, and a pixel with none in reach
+    stays 0; 0 is the identity.  None: unlimited; an image without labels stays all 0.  data.preprocess_gt carves borders of
+    4 px reach between touching cells, so label_cells(mask) loses every cell's rim against the man_seg ids: grow_cells(., 4)
+    hands it back before seg_measure.  Exact, on the device (unet_grow_labels), at a cost independent of the number of cells.
+    Negative ids and ids >= 2^24 raise ValueError; host tensors raise NotImplementedError (no CPU path)."""
+    (lab,) = _id_maps("grow_cells", "unet_grow_labels", labels)
+    import _hip
+    if max_distance is None or max_distance == math.inf:
+        max_dist2 = -1
+    else:
+        if not max_distance >= 0:
+            raise ValueError("grow_cells: max_distance must be None or a number >= 0, got %r" % (max_distance,))
+        max_dist2 = min(int(math.floor(float(max_distance) ** 2)), 1 << 40)
+    _id_range("grow_cells", lab)
+    lab = lab.int()
+    B, H, W = lab.shape
+    out = torch.empty_like(lab)
+    scratch = torch.empty(_hip.lib().unet_grow_labels_scratch_bytes(B, H, W), dtype=torch.uint8, device=lab.device)
+    _hip.run("unet_grow_labels", lab.device, _hip.ptr(lab), B, H, W, max_dist2, _hip.ptr(out), _hip.ptr(scratch))
+    return out[0] if labels.dim() == 2 else out
+
+
+def pair_table(pred_labels, gt_labels, *, _table_slots=None):
+    """The contingency table of predicted against ground-truth instance maps (as seg_measure takes them) restricted to
+    ground-truth foreground: int64 numpy arrays (b, g, p, n), one entry per distinct (image, gt id >= 1, pred id >= 0) with
+    n > 0 pixels, sorted by (b, g, p).  p = 0 is "predicted background"; pixels with gt = 0 are in no entry.  The counting is
+    exact and on the device (unet_partition_pairs); the protocol is seg_measure's: the two id maxima are read back once, and
+    the table is doubled and the call repeated while it reports an overflow.  Negative ids (the kernel counts them in its
+    status words) and ids >= 2^24 raise ValueError;
+    host tensors raise NotImplementedError (no CPU path)."""
+    pred, gt = _id_maps("pair_table", "unet_partition_pairs", pred_labels, gt_labels)
+    import _hip
+    B, H, W = gt.shape
+    dev = gt.device
+    ng_max, np_max = (max(0, int(v)) for v in torch.stack([gt.max().long(), pred.max().long()]).tolist())
+    if max(ng_max, np_max) >= 1 << 24:
+        raise ValueError("pair_table: ids must be below 2^24, got up to %d" % max(ng_max, np_max))
+    gt, pred = gt.int(), pred.int()
+    n_pairs = torch.empty(1, dtype=torch.int64, device=dev)
+    status = torch.empty(B, 2, dtype=torch.int64, device=dev)
+    slots = 1 << (4 * (ng_max + np_max) + 1024 - 1).bit_length() if _table_slots is None else int(_table_slots)
+    while True:
+        keys = torch.empty(slots, dtype=torch.int64, device=dev)
+        counts = torch.empty(slots, dtype=torch.int32, device=dev)
+        scratch = torch.empty(_hip.lib().unet_partition_pairs_scratch_bytes(B, slots), dtype=torch.uint8, device=dev)
+        _hip.run("unet_partition_pairs", dev, _hip.ptr(gt), _hip.ptr(pred), B, H, W, ng_max, np_max, slots, _hip.ptr(keys),
+                 _hip.ptr(counts), _hip.ptr(n_pairs), _hip.ptr(status), _hip.ptr(scratch))
+        st = status.cpu()
+        if int(st[:, 0].sum()):
+            raise ValueError("pair_table: %d pixels hold negative ids (outside [0, %d] / [0, %d])" % (int(st[:, 0].sum()), ng_max, np_max))
+        if not int(st[:, 1].sum()):
+            break
+        slots *= 2                      # ends: a table with more slots than pixels cannot fill up
+    n = int(n_pairs.item())
+    k, c = keys[:n].cpu().numpy().view(np.uint64), counts[:n].cpu().numpy().astype(np.int64)
+    order = np.argsort(k)                                   # distinct unsigned keys b << 48 | g << 24 | p: the order of (b, g, p)
+    k, c = k[order], c[order]
+    return tuple((k >> np.uint64(s) & np.uint64(m)).astype(np.int64) for s, m in ((48, 0xFFFF), (24, 0xFFFFFF), (0, 0xFFFFFF))) + (c,)
+
+
+RandScores = collections.namedtuple("RandScores", "rand_split rand_merge v_rand rand_error info_split info_merge v_info voi_split "
+                                                  "voi_merge rand_error_mean v_info_mean N S_pair S_pred S_gt c")
+
+
+def _quot(num, den):
+    """num / den of two exact rationals as the nearest float64; nan for 0 / 0 (and for any x / 0: no score here has one)."""
+    return float(fractions.Fraction(num) / den) if den else math.nan
+
+
+def _ratio(num, den):
+    return num / den if den else math.nan
+
+
+def rand_from_pairs(b, g, p, n, B, alpha=0.5):
+    """RandScores from a pair table (b, g, p, n) of B images, as pair_table returns it (any order; host arrays, no GPU).  Per
+    image, with n_gp the counts, a_g = sum_p n_gp (p = 0 included), b_p = sum_g n_gp for p >= 1, c = sum_g n_g0, N = sum a_g;
+    the c predicted-background pixels inside ground-truth foreground are singleton segments:
+        S_pair = sum_{p>=1} n_gp^2 + c      S_pred = sum_{p>=1} b_p^2 + c      S_gt = sum a_g^2
+        rand_split = S_pair / S_gt    rand_merge = S_pair / S_pred    v_rand = S_pair / (alpha S_pred + (1 - alpha) S_gt)
+        rand_error = 1 - v_rand       (alpha = 1/2: the adapted Rand error of the ISBI 2012 / SNEMI3D evaluation)
+    each one quotient of exact integers (alpha enters as the rational its float is), rounded once: equal integers give equal
+    floats everywhere.  With natural logarithms and every sum formed by math.fsum (no dependence on order),
+        N H_pred = N ln N - sum_{p>=1} b ln b     N H_gt = N ln N - sum a ln a     N H_joint = N ln N - sum_{p>=1} n ln n
+        I = H_pred + H_gt - H_joint    info_split = I / H_pred    info_merge = I / H_gt
+        v_info = I / ((1 - alpha) H_pred + alpha H_gt)    voi_split = H_joint - H_gt = H(pred | gt)    voi_merge = H_joint - H_pred
+    (singletons add 0 to every sum of x ln x).  0 / 0 is nan: an image with N = 0 has nan for every score, a prediction that is
+    one segment has H_pred = 0 and info_split = nan.  rand_error_mean and v_info_mean are the means over the images where the
+    score is not nan (nan if there is none); N, S_pair, S_pred, S_gt, c are int64 [B], to pool over a data set."""
+    b, g, p, n = (np.asarray(a).astype(np.int64).ravel() for a in (b, g, p, n))
+    alpha_q = fractions.Fraction(float(alpha))
+    names = RandScores._fields[:9]
+    out = {k: np.full(B, np.nan) for k in names}
+    ints = {k: np.zeros(B, np.int64) for k in ("N", "S_pair", "S_pred", "S_gt", "c")}
+    xlnx = lambda v: [x * math.log(x) for x in v]
+    for i in range(B):
+        sel = b == i
+        gi, pi, ni = g[sel], p[sel], n[sel]
+        fg = pi >= 1
+        a = [int(v) for v in _group_sums(gi, ni)]
+        bp = [int(v) for v in _group_sums(pi[fg], ni[fg])]
+        nn = [int(v) for v in ni[fg]]
+        c = int(ni[~fg].sum())
+        N = sum(a)
+        S_pair, S_pred, S_gt = sum(v * v for v in nn) + c, sum(v * v for v in bp) + c, sum(v * v for v in a)
+        for k, v in zip(("N", "S_pair", "S_pred", "S_gt", "c"), (N, S_pair, S_pred, S_gt, c)):
+            ints[k][i] = v
+        if N == 0:
+            continue
+        den = alpha_q * S_pred + (1 - alpha_q) * S_gt
+        out["rand_split"][i], out["rand_merge"][i] = _quot(S_pair, S_gt), _quot(S_pair, S_pred)
+        out["v_rand"][i] = _quot(S_pair, den)
+        out["rand_error"][i] = _quot(den - S_pair, den)
+        T = N * math.log(N)
+        X_pair, X_pred, X_gt = xlnx(nn), xlnx(bp), xlnx(a)
+        neg = lambda v: [-x for x in v]
+        H_pred, H_gt = math.fsum([T] + neg(X_pred)) / N, math.fsum([T] + neg(X_gt)) / N
+        I = math.fsum([T] + neg(X_pred) + neg(X_gt) + X_pair) / N
+        out["info_split"][i], out["info_merge"][i] = _ratio(I, H_pred), _ratio(I, H_gt)
+        out["v_info"][i] = _ratio(I, (1 - alpha) * H_pred + alpha * H_gt)
+        out["voi_split"][i] = math.fsum(X_gt + neg(X_pair)) / N
+        out["voi_merge"][i] = math.fsum(X_pred + neg(X_pair)) / N
+    mean = lambda v: np.float64(v[~np.isnan(v)].mean()) if (~np.isnan(v)).any() else np.float64(np.nan)
+    return RandScores(rand_error_mean=mean(out["rand_error"]), v_info_mean=mean(out["v_info"]), **out, **ints)
+
+
+def _group_sums(ids, weights):
+    """Sums of the int64 weights per distinct id (exact: integer adds)."""
+    if len(ids) == 0:
+        return np.zeros(0, np.int64)
+    u, inv = np.unique(ids, return_inverse=True)
+    s = np.zeros(len(u), np.int64)
+    np.add.at(s, inv, weights)
+    return s
+
+
+def rand_scores(pred_labels, gt_labels, *, grow=None, alpha=0.5):
+    """The foreground-restricted Rand and information scores of predicted against ground-truth instance maps (as seg_measure
+    takes them): the ranking scores of the ISBI 2012 challenge, Ronneberger et al. 2015, Table 1.  grow = True or a number:
+    pred_labels first goes through grow_cells(pred_labels, None if grow is True else grow), the challenge's border thinning (a
+    prediction is scored after its border pixels have gone to the neighbouring segments).  Returns the RandScores of
+    rand_from_pairs (see there for every definition) on pair_table(pred, gt).
+    This is not the warping error; it is not bit-equal to the Fiji script of the challenge, whose thinning leaves borders one
+    pixel wide where grow=True leaves none; and label_cells stays 4-connected.  Errors as pair_table and grow_cells."""
+    pred, gt = _id_maps("rand_scores", "unet_partition_pairs", pred_labels, gt_labels)
+    if grow is not None and grow is not False:
+        pred = grow_cells(pred, None if grow is True else grow)
+    b, g, p, n = pair_table(pred, gt)
+    return rand_from_pairs(b, g, p, n, gt.shape[0], alpha)
 
 
 def class_balance(gt_batch):

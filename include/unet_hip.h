@@ -309,6 +309,32 @@ size_t unet_instance_overlap_scratch_bytes(int B, int ng_max, int np_max, size_t
 int unet_instance_overlap(const void *gt_i32, const void *pred_i32, int B, int H, int W, int ng_max, int np_max, size_t table_slots,
                           void *area_gt_u32, void *area_pred_u32, void *match_i32, void *inter_u32, void *status_u64, void *scratch,
                           void *stream);
+/* The contingency table of two instance maps restricted to ground-truth foreground: the integers behind the Rand and
+ * information scores of the ISBI 2012 challenge (Ronneberger et al. 2015, Table 1; functions.rand_scores).  gt_i32, pred_i32,
+ * ng_max, np_max, table_slots and status_u64 as in unet_instance_overlap, with two differences: only pixels with gt >= 1 are
+ * counted, and for those pred = 0 ("predicted background") is a column like any other.  A pixel with gt = 0 adds nothing,
+ * whatever its pred id, unless an id is out of range: status[b][0] counts such pixels of any gt value.
+ *   pair_keys_u64 [table_slots]   : the distinct (b, g, p), g >= 1, p >= 0, packed b << 48 | g << 24 | p, in unspecified order
+ *   pair_counts_u32 [table_slots] : the pixels of each
+ *   n_pairs_u64 [1]               : how many entries of the two lists are written; the rest is left untouched
+ * If status[b][1] != 0 for some b the list misses pixels and the caller repeats the call with a larger table.  Exact integer
+ * atomics: after sorting, the list is the same in every run.
+ * scratch: unet_partition_pairs_scratch_bytes(B, table_slots), initialised by the call.                                    */
+size_t unet_partition_pairs_scratch_bytes(int B, size_t table_slots);
+int unet_partition_pairs(const void *gt_i32, const void *pred_i32, int B, int H, int W, int ng_max, int np_max, size_t table_slots,
+                         void *pair_keys_u64, void *pair_counts_u32, void *n_pairs_u64, void *status_u64, void *scratch,
+                         void *stream);
+/* Nearest-cell growth of an instance map (border thinning; skimage.segmentation.expand_labels with an exact metric and a
+ * stated tie rule; functions.grow_cells).  labels_i32, out_i32 int32 [B,H,W], 0 = background, ids in [1, 2^24), not
+ * necessarily consecutive or connected; H != W allowed, down to 1 x 1.  A pixel with id != 0 keeps it.  A background pixel takes
+ * the id of the labelled pixel at the smallest exact squared Euclidean distance d^2 (an integer), the smallest id among those at
+ * that d^2.  max_dist2 >= 0: only labelled pixels with d^2 <= max_dist2 count and a pixel with none in reach stays 0 (0 is the
+ * identity); max_dist2 < 0: unlimited, and an image without labels stays 0.  A value outside [0, 2^24) is copied to the output
+ * and is no cell to grow from (it indexes nothing).  Exact; H * W * min(W, 2 floor(sqrt(max_dist2)) + 257) key evaluations,
+ * whatever the number of cells.  Limits as unet_label_components (H * W < 2^31, H <= 65535, B <= 65535) and W <= 65535.
+ * scratch: unet_grow_labels_scratch_bytes(B, H, W) (8 bytes per pixel), initialised by the call.                           */
+size_t unet_grow_labels_scratch_bytes(int B, int H, int W);
+int unet_grow_labels(const void *labels_i32, int B, int H, int W, long long max_dist2, void *out_i32, void *scratch, void *stream);
 /* Carved training targets from an instance image, replaces preprocess_gt (data.py:195-221: per cell, cv.dilate with a 5 x 5
  * rectangle, iterations=2, and 255 added on the ring the cell gained) and the cv.threshold(gt, 0, 255, THRESH_BINARY) after it
  * (data.py:64, :163).  ids [B,H,W], dtype 0 = int64, 1 = float32 holding integral values, 2 = int32 (what
