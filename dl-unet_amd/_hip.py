@@ -76,6 +76,10 @@ _SIGS = {
                                    vp, vp, vp]),
     "unet_tile_stitch_k": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_long, C.c_int, C.c_int, C.c_int,
                                      C.c_int, vp, vp, vp]),
+    "unet_tile_gather_view": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                        C.c_long, C.c_int, vp, vp]),
+    "unet_tile_stitch_view": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_long, C.c_int, C.c_int,
+                                        C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
     "unet_eval_masks": (C.c_int, [vp, C.c_long, C.c_long, C.c_long, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp]),
     "unet_eval_confusion": (C.c_int, [vp, C.c_long, C.c_long, C.c_long, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, vp]),
     "unet_class_balance": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]),

@@ -5,7 +5,8 @@ written with PIL using torchvision.utils.save_image's conversion (clamp to [0,1]
 
 An extension: segment(unet, images) is the paper's overlap-tile inference (Ronneberger et al. 2015, Fig. 2) for
 images of any size and shape, [H,W] in, [H,W] mask out (unet_tile_gather, unet_forward, unet_tile_stitch); tile_grid
-is its geometry."""
+is its geometry.  segment(..., views=...) averages the class probabilities over dihedral views of each image (apply_view,
+undo_view, view_shape, parse_views; unet_tile_gather_view, unet_tile_stitch_view)."""
 import os
 from time import time
 
@@ -117,7 +118,86 @@ def auto_tile_size(H, W, cap=TILE_CAP):
     return S if S <= cap else cap
 
 
-def segment(unet, images, tile_size=None, max_batch=16, normalise=True, return_probs=False, return_instances=False):
+# ---- dihedral views ---------------------------------------------------------------------------------------------------------
+
+VIEW_SETS = {'rot4': (0, 3, 6, 5), 'flips': (0, 2, 4, 6), 'd4': (0, 1, 2, 3, 4, 5, 6, 7)}
+
+
+def _view_code(v):
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) <= 7:
+        raise ValueError("view code %r is not an int in 0..7" % (v,))
+    return int(v)
+
+
+def view_shape(H, W, v):
+    """(Hv, Wv) of view v of an H x W image: (W, H) for the transposed codes (v odd)."""
+    return (W, H) if _view_code(v) & 1 else (H, W)
+
+
+def apply_view(x, v):
+    """View v (0..7) of x [..., H, W], a torch tensor (any device) or a numpy array; the result is a view, not a copy.
+    With t = v & 1, fy = (v >> 1) & 1, fx = (v >> 2) & 1:  V = x.T if t else x;  if fy: V = V[::-1];  if fx: V = V[:, ::-1]
+    (on the last two axes).  np.rot90(x, k), k = 0..3, are the codes 0, 3, 6, 5."""
+    v = _view_code(v)
+    tensor = torch.is_tensor(x)
+    if v & 1:
+        x = x.transpose(-1, -2) if tensor else np.swapaxes(x, -1, -2)
+    axes = [a for a, on in ((-2, v & 2), (-1, v & 4)) if on]
+    if axes:
+        x = torch.flip(x, axes) if tensor else np.flip(x, axes)
+    return x
+
+
+def undo_view(x, v):
+    """The inverse of apply_view(., v): undo_view(apply_view(x, v), v) == x."""
+    v = _view_code(v)
+    tensor = torch.is_tensor(x)
+    axes = [a for a, on in ((-2, v & 2), (-1, v & 4)) if on]
+    if axes:
+        x = torch.flip(x, axes) if tensor else np.flip(x, axes)
+    if v & 1:
+        x = x.transpose(-1, -2) if tensor else np.swapaxes(x, -1, -2)
+    return x
+
+
+def parse_views(views):
+    """A tuple of distinct view codes from 'rot4' (0, 3, 6, 5: the four rotations), 'flips' (0, 2, 4, 6), 'd4' (all 8) or any
+    non-empty sequence of distinct ints in 0..7, whose order is kept."""
+    if isinstance(views, str):
+        if views not in VIEW_SETS:
+            raise ValueError("views %r is not one of %s or a sequence of view codes 0..7" % (views, ", ".join(map(repr, VIEW_SETS))))
+        return VIEW_SETS[views]
+    try:
+        vs = tuple(views)
+    except TypeError:
+        raise ValueError("views %r is not one of %s or a sequence of view codes 0..7" % (views, ", ".join(map(repr, VIEW_SETS))))
+    if not vs:
+        raise ValueError("views %r is empty" % (views,))
+    vs = tuple(_view_code(v) for v in vs)
+    if len(set(vs)) != len(vs):
+        raise ValueError("views %r repeats the code %d" % (views, next(v for k, v in enumerate(vs) if v in vs[:k])))
+    return vs
+
+
+VIEW_FIRST, VIEW_LAST = 1, 2        # unet_tile_stitch_view's phase bits: store (not add) the probability; finalise after it
+
+
+def _view_chunks(n_views, Tv, nb):
+    """The tile list of n_views views of Tv tiles each, cut into chunks of at most nb: yields (t0, n, segments), a segment
+    being (index of the view in the list, first tile within that view, number of tiles, offset in the chunk)."""
+    T = n_views * Tv
+    for t0 in range(0, T, nb):
+        n = min(nb, T - t0)
+        segs, off = [], 0
+        while off < n:
+            k, a = divmod(t0 + off, Tv)
+            m = min(Tv - a, n - off)
+            segs.append((k, a, m, off))
+            off += m
+        yield t0, n, segs
+
+
+def segment(unet, images, tile_size=None, max_batch=16, normalise=True, return_probs=False, return_instances=False, views=None):
     """Segment images of any size and shape with the overlap-tile strategy; returns the int64 argmax mask of the same
     shape as `images` (and the float32 foreground probability softmax(logits)[1] with return_probs).  A K-class net
     (Unet(n_classes=K), K > 2) gives the K-way argmax (ties -> the lowest class) and, with return_probs, the softmax of all
@@ -134,6 +214,14 @@ def segment(unet, images, tile_size=None, max_batch=16, normalise=True, return_p
         current stream; tile, logit and workspace buffers are allocated once per call.
     normalise: each image becomes (x - min) / (max - min) first, as the reference's ImageDataset_test does (data.py:188);
         the min / max are read back once before the first chunk, and a constant image raises ValueError.
+    views: None, or what parse_views accepts ('rot4', 'flips', 'd4', a sequence of view codes): the class probabilities are
+        averaged over these dihedral views of each image (apply_view) and the mask is taken from the average: prob > 0.5, or
+        for K > 2 the argmax of the summed probabilities, ties -> the lowest class.  No view is materialised: the tiles of all
+        views form one list, in the order of the codes, which is cut into the same chunks of max_batch, so one forward may hold
+        tiles of several views (unet_tile_gather_view per view in the chunk, one unet_forward, unet_tile_stitch_view per view).
+        The sum runs in the order of the codes and is deterministic.  views=(0,) gives the probabilities of views=None bit for
+        bit; its mask is prob > 0.5 and not l1 > l0, which differ only where prob == 0.5 exactly (logit differences below
+        about 6e-8, where 1 + exp(l0 - l1) rounds to 2).
     Geometry and mirroring: tile_grid."""
     if not images.is_cuda:
         raise RuntimeError("segment: the HIP path needs the images on a HIP device (got %s); there is no CPU fallback - "
@@ -151,11 +239,12 @@ def segment(unet, images, tile_size=None, max_batch=16, normalise=True, return_p
         raise ValueError("segment: empty batch")
     if max_batch < 1:
         raise ValueError("segment: max_batch must be >= 1")
+    vs = None if views is None else parse_views(views)
     S = auto_tile_size(H, W) if tile_size is None else int(tile_size)
     _check_tile_size(S)
     So = S - 2 * TILE_MARGIN
     ny, nx, oy0, ox0 = tile_grid(H, W, S)
-    T = B * ny * nx
+    T = B * ny * nx * (1 if vs is None else len(vs))        # a transposed view has as many tiles: its grid is (nx, ny)
     nb = min(max_batch, T)
     dev = x.device
     h = unet._get_handle(dev.index)
@@ -181,10 +270,23 @@ def segment(unet, images, tile_size=None, max_batch=16, normalise=True, return_p
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         mask = torch.empty(B, H, W, dtype=torch.int64, device=dev)
         prob = None
-        if return_probs:
+        if return_probs or vs is not None:
             prob = torch.empty((B, H, W) if K == 2 else (B, K, H, W), dtype=torch.float32, device=dev)
         st = _hip.stream(dev)
-        for t0 in range(0, T, nb):
+        for t0, n, segs in (_view_chunks(len(vs), B * ny * nx, nb) if vs is not None else ()):
+            grids = {k: tile_grid(*view_shape(H, W, vs[k]), S) for k, _, _, _ in segs}
+            for k, a, m, off in segs:
+                gy, gx, y0, x0 = grids[k]
+                _hip.check(L.unet_tile_gather_view(_hip.ptr(x), B, H, W, _hip.ptr(mm), S, vs[k], y0, x0, gy, gx, a, m,
+                                                   _hip.ptr(tiles[off:]), st), "unet_tile_gather_view")
+            _hip.check(L.unet_forward(h.h, ptab, _hip.ptr(tiles), _hip.ptr(logits), n, S, _hip.ptr(ws), nbytes, 0, st),
+                       "unet_forward")
+            for k, a, m, off in segs:
+                gy, gx, y0, x0 = grids[k]
+                phase = (VIEW_FIRST if k == 0 else 0) | (VIEW_LAST if k == len(vs) - 1 else 0)
+                _hip.check(L.unet_tile_stitch_view(_hip.ptr(logits[off:]), So, K, vs[k], y0, x0, gy, gx, a, m, B, H, W, phase,
+                                                   len(vs), _hip.ptr(prob), _hip.ptr(mask), st), "unet_tile_stitch_view")
+        for t0 in range(0, T, nb) if vs is None else ():
             n = min(nb, T - t0)
             _hip.check(L.unet_tile_gather(_hip.ptr(x), B, H, W, _hip.ptr(mm), S, oy0, ox0, ny, nx, t0, n, _hip.ptr(tiles), st),
                        "unet_tile_gather")
@@ -199,7 +301,7 @@ def segment(unet, images, tile_size=None, max_batch=16, normalise=True, return_p
         inst = label_cells(mask)[0] if return_instances else None
     if single:
         mask = mask[0]
-        prob = prob[0] if prob is not None else None
+        prob = prob[0] if return_probs else None
         inst = inst[0] if inst is not None else None
     out = (mask,) + ((prob,) if return_probs else ()) + ((inst,) if return_instances else ())
     return out if len(out) > 1 else mask

@@ -260,6 +260,23 @@ int unet_tile_stitch(const void *logits, int So, int oy0, int ox0, int ny, int n
  *                      the softmax of the K logits (max-subtracted).                                                       */
 int unet_tile_stitch_k(const void *logits, int So, int K, int oy0, int ox0, int ny, int nx, long t0, int nt, int B, int H, int W,
                        void *mask_i64, void *prob_f32, void *stream);
+/* The same two for one of the 8 dihedral views of the image (tester.apply_view / segment(views=...)), without materialising it.
+ * View code v = 0..7: t = v & 1 (transpose), fy = (v >> 1) & 1, fx = (v >> 2) & 1; the view has shape (Hv, Wv) = t ? (W, H) : (H, W)
+ * and its pixel (y, x) is image pixel t ? (x', y') : (y', x'), y' = fy ? Hv-1-y : y, x' = fx ? Wv-1-x : x.  H, W are always the
+ * image's; (ny, nx, oy0, ox0) is tester.tile_grid(Hv, Wv, S) and t = (b*ny + i)*nx + j indexes the tiles of this one view.
+ *   unet_tile_gather_view : tiles_out = what unet_tile_gather gives on the materialised contiguous view, bit for bit.
+ *   unet_tile_stitch_view : logits fp32 [nt,K,So,So] (2 <= K <= 16; 16-byte aligned for K > 2) -> each tile pixel's class
+ *                      probabilities by the expressions of unet_tile_stitch (K = 2: class 1 only, prob_f32 [B,H,W]) and
+ *                      unet_tile_stitch_k (K > 2: prob_f32 [B,K,H,W]), landed at the image pixel the view pixel came from.
+ *                      phase bit 0 (FIRST): prob = p, else prob += p.  phase bit 1 (LAST): then, for this launch's pixels,
+ *                      prob = sum / (float)n_views and mask_i64 [B,H,W] = prob > 0.5f (K = 2) or the argmax of the sums, ties ->
+ *                      the lowest class (K > 2).  mask_i64 may be NULL unless LAST is set.  A view's tiles partition the image
+ *                      and a launch touches each of its pixels once, without atomics: the order of the sum is the stream
+ *                      order of the launches.                                                                               */
+int unet_tile_gather_view(const void *img, int B, int H, int W, const void *minmax, int S, int view, int oy0, int ox0, int ny, int nx,
+                          long t0, int nt, void *tiles_out, void *stream);
+int unet_tile_stitch_view(const void *logits, int So, int K, int view, int oy0, int ox0, int ny, int nx, long t0, int nt, int B, int H,
+                          int W, int phase, int n_views, void *prob_f32, void *mask_i64, void *stream);
 /* N2 back end, replaces pred[:, :, pad:pad+n, pad:pad+n].argmax(dim=1) + IoU / Pixel_error counting
  * (tester.py:29-42, functions.py:174-213): mask int64 [B,n,n]; with labels int64 [B,n,n]:
  * stats u64 [B][3] = {sum(pred&label), sum(pred|label), sum|pred-label|} (exact integer atomics).      */

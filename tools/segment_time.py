@@ -7,6 +7,13 @@ call, after warm-up, median of --reps), and the device time of the same call's g
 chunks, without the forwards) as a share of it.  The 64-base-channel net, random weights.
 
     timeout -k 10 900 python tools/segment_time.py [--reps 3] [--json out.json]
+
+--views times segment(views='d4') instead: one call that averages the 8 dihedral views, against the composite one would
+write by hand without it (8 segment(return_probs=True) calls on apply_view(x, v).contiguous(), undo_view, a torch mean and a
+threshold), at 1 x 520x696, 30 x 512^2 (the ISBI stack) and 1 x 4096^2, fp32 and bf16, automatic tile size, max_batch 16;
+the same events, warm-up and median.
+
+    timeout -k 10 900 python tools/segment_time.py --views [--reps 3] [--json out.json]
 """
 import argparse
 import json
@@ -61,6 +68,37 @@ def gather_stitch_fn(x, S, mb):
     return fn, T
 
 
+def composite_d4(net, x):
+    """What segment(views='d4') replaces: a segment per materialised view, brought back and averaged with torch ops."""
+    acc = None
+    for v in tester.parse_views('d4'):
+        _, p = tester.segment(net, tester.apply_view(x, v).contiguous(), return_probs=True)
+        p = tester.undo_view(p, v)
+        acc = p if acc is None else acc + p
+    prob = acc / 8
+    return prob > 0.5, prob
+
+
+def time_views(a, net, L):
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device=dev).manual_seed(0)
+    images = {"1x520x696": torch.rand(1, 520, 696, generator=g, device=dev) * 255,
+              "30x512x512": torch.rand(30, 512, 512, generator=g, device=dev) * 255,
+              "1x4096x4096": torch.rand(1, 4096, 4096, generator=g, device=dev) * 255}
+    rows = []
+    for math in (int(m) for m in a.maths.split(",")):
+        _hip.check(L.unet_set_math(math), "unet_set_math")
+        for name, x in images.items():
+            one = median_ms(lambda: tester.segment(net, x, return_probs=True, views='d4'), a.reps, warm=1)
+            torch.cuda.empty_cache()
+            comp = median_ms(lambda: composite_d4(net, x), a.reps, warm=1)
+            torch.cuda.empty_cache()
+            rows.append({"math": math, "image": name, "views_ms": one, "composite_ms": comp, "ratio": comp / one})
+            print("math %d  %-12s  segment(views='d4') %9.2f ms   composite of 8 calls %9.2f ms   composite / one call %.3f" %
+                  (math, name, one, comp, comp / one), flush=True)
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=3)
@@ -68,6 +106,7 @@ def main():
     ap.add_argument("--batches", default="4,16")
     ap.add_argument("--maths", default="3,2")
     ap.add_argument("--json", default=None)
+    ap.add_argument("--views", action="store_true", help="time segment(views='d4') against the composite of 8 calls")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     torch.cuda.set_device(dev)
@@ -78,6 +117,15 @@ def main():
     images = {"4096x4096": torch.rand(1, 4096, 4096, generator=g, device=dev) * 255,
               "520x696": torch.rand(1, 520, 696, generator=g, device=dev) * 255}
     rows = []
+    if a.views:
+        try:
+            rows = time_views(a, net, L)
+        finally:
+            L.unet_set_math(default_math)
+        if a.json:
+            with open(a.json, "w") as f:
+                json.dump(rows, f, indent=1)
+        return
     try:
         for math in (int(m) for m in a.maths.split(",")):
             _hip.check(L.unet_set_math(math), "unet_set_math")
