@@ -41,6 +41,8 @@ _SIGS = {
     "unet_param_count": (C.c_int, [vp, C.c_int, C.POINTER(C.c_size_t)]),
     "unet_workspace_bytes": (C.c_size_t, [vp, C.c_int, C.c_int, C.c_int]),
     "unet_forward": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, vp, C.c_size_t, C.c_int, vp]),
+    "unet_forward_dropout": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, vp, C.c_size_t, C.c_float, C.c_ulonglong, C.c_ulonglong, vp]),
+    "unet_dropout_mask": (C.c_int, [C.c_ulonglong, C.c_ulonglong, C.c_int, C.c_size_t, C.c_size_t, C.c_float, vp, vp]),
     "unet_backward": (C.c_int, [vp, vp, vp, vp, vp, C.c_size_t, vp]),
     "unet_backward_stages": (C.c_int, []),
     "unet_backward_stage": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, C.c_size_t, vp]),
@@ -108,6 +110,8 @@ _SIGS = {
                                    vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "unet_maxpool2_fwd": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "unet_maxpool2_bwd": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "unet_dropout_pool_fwd": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_ulonglong, C.c_ulonglong, C.c_int, vp]),
+    "unet_dropout_bwd": (C.c_int, [vp, C.c_size_t, C.c_float, vp]),
     "unet_upconv2_scratch_bytes": (C.c_size_t, [C.c_int] * 5),
     "unet_upconv2_fwd": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp]),
     "unet_upconv2_bwd": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp]),

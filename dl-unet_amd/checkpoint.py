@@ -9,6 +9,8 @@ run is not the run that was interrupted — momentum 0.99 remembers ~100 steps.
   save_checkpoint(path, unet, optimizer, scheduler=None, **extra)   one file: model + optimizer (+ scheduler) state
   load_checkpoint(path, unet, optimizer=None, scheduler=None)       restores them; returns the `extra` dict
   find_resume_checkpoint(models_dir)                                'latest' if present, else 'best' (what -sf meant to do)
+Added with Unet(dropout=p > 0) only: the drop-out state {p, seed, step}, so that the resumed run draws the masks the
+interrupted one would have.
 Only tensors, numbers and strings are stored: files load with torch.load(weights_only=True).
 """
 import os
@@ -18,6 +20,9 @@ import torch
 
 def save_checkpoint(path, unet, optimizer, scheduler=None, **extra):
     ckpt = {"format": "dl-unet_amd/1", "model": unet.state_dict(), "optimizer": optimizer.state_dict(), "extra": dict(extra)}
+    if getattr(unet, "dropout", 0.0) > 0:
+        # Unet(dropout=p): which masks the next forward draws (p, seed, step); files of a net without drop-out are unchanged
+        ckpt["dropout"] = unet.dropout_state()
     if scheduler is not None:
         ckpt["scheduler"] = {k: v for k, v in scheduler.state_dict().items() if isinstance(v, (int, float, str, bool, list, type(None)))}
     tmp = path + ".tmp"
@@ -33,6 +38,8 @@ def load_checkpoint(path, unet, optimizer=None, scheduler=None, map_location=Non
         unet.load_state_dict(ckpt)
         return {}
     unet.load_state_dict(ckpt["model"])
+    if "dropout" in ckpt and hasattr(unet, "load_dropout_state"):
+        unet.load_dropout_state(ckpt["dropout"])
     if optimizer is not None and "optimizer" in ckpt:
         optimizer.load_state_dict(ckpt["optimizer"])          # momentum buffers land on the parameters' device
     if scheduler is not None and "scheduler" in ckpt:

@@ -220,5 +220,9 @@ int ccl_labels(const void *mask, int dtype, int B, int H, int W, int *parent, in
                hipStream_t st);
 int maxpool2_fwd(const void *x, void *y, int B, int H, int W, int C, int es, hipStream_t st);
 int maxpool2_bwd(const void *pre, const void *dy, void *dpre, int B, int H, int W, int C, int es, hipStream_t st);
+// drop-out (dropout.hip): x [B,H,W,C] dropped in place (+ its 2x2 max-pool into `pooled`, or null); g[0, n) *= 1 / (1 - p)
+int dropout_pool_fwd(void *x, void *pooled, int B, int H, int W, int C, float p, unsigned long long seed, unsigned long long step,
+                     int site, int es, hipStream_t st);
+int dropout_bwd(void *g, size_t n, float p, int es, hipStream_t st);
 
 }  // namespace unet

@@ -52,14 +52,15 @@ struct Layer {
     int ci, co;           // the levels whose width (base_ch << level) the input / output channels are; -1: 1 channel in, n_classes out
     int stage;            // backward stage (reverse layer order, so gradient buckets complete early for the all-reduce)
     int in, out;          // tensor read (at level ci; K_CAT: the padded skip t[level] next to u[level]) and written (at level)
+    int drop = -1;        // drop-out site of the layer's output (Ronneberger et al. 2015, section 3.1; dropout.hip), -1: none
 };
 // the reference's declaration order (network.py:23-58) = forward order; the backward walks each stage's layers in reverse
 static const Layer LAYERS[UNET_N_LAYERS] = {
     {"conv11c", K_CONV1, 0, -1, 0, 5, T_NONE, T_A1}, {"conv12c", K_CONV, 0, 0, 0, 5, T_A1, T_A2},
     {"conv21c", K_CONV, 1, 0, 1, 5, T_T, T_A1},      {"conv22c", K_CONV, 1, 1, 1, 5, T_A1, T_A2},
     {"conv31c", K_CONV, 2, 1, 2, 5, T_T, T_A1},      {"conv32c", K_CONV, 2, 2, 2, 5, T_A1, T_A2},
-    {"conv41c", K_CONV, 3, 2, 3, 5, T_T, T_A1},      {"conv42c", K_CONV, 3, 3, 3, 5, T_A1, T_A2},
-    {"conv51c", K_CONV, 4, 3, 4, 4, T_T, T_A1},      {"conv52c", K_CONV, 4, 4, 4, 4, T_A1, T_A2},
+    {"conv41c", K_CONV, 3, 2, 3, 5, T_T, T_A1},      {"conv42c", K_CONV, 3, 3, 3, 5, T_A1, T_A2, 0},
+    {"conv51c", K_CONV, 4, 3, 4, 4, T_T, T_A1},      {"conv52c", K_CONV, 4, 4, 4, 4, T_A1, T_A2, 1},
     {"upconv4", K_UP, 3, 4, 3, 3, T_A2, T_U}, {"conv41e", K_CAT, 3, 4, 3, 3, T_T, T_D1}, {"conv42e", K_CONV, 3, 3, 3, 3, T_D1, T_D2},
     {"upconv3", K_UP, 2, 3, 2, 2, T_D2, T_U}, {"conv31e", K_CAT, 2, 3, 2, 2, T_T, T_D1}, {"conv32e", K_CONV, 2, 2, 2, 2, T_D1, T_D2},
     {"upconv2", K_UP, 1, 2, 1, 1, T_D2, T_U}, {"conv21e", K_CAT, 1, 2, 1, 1, T_T, T_D1}, {"conv22e", K_CONV, 1, 1, 1, 1, T_D1, T_D2},
@@ -77,6 +78,9 @@ struct Plan {
     int B = 0, S = 0, base = 0, So = 0, training = 0;
     int ncls = 2;         // classes of the head (finalconv's output channels)
     int math = 3;         // arithmetic, fixed when the forward is planned: the backward of that forward uses the same
+    float drop_p = 0.f;   // unet_forward_dropout: drop probability of this forward (0: none); the backward scales by 1 / (1 - p)
+    unsigned long long drop_seed = 0, drop_step = 0;
+    bool drops(const Layer &L) const { return L.drop >= 0 && drop_p > 0.f; }
     int ch[5], pad[4];    // pad > 0: the skip t[l] is zero-padded to u[l]'s extent, pad < 0: cropped
     // per level: the two encoder convs' outputs, the pool's, the up-conv's, the two decoder convs'
     Act a1[5], a2[5], t[4], u[4], d1[4], d2[4];
@@ -651,33 +655,52 @@ static int pool_launch(const Ctx &cx, int l, bool bwd)
                : maxpool2_fwd(cx.ws(a2.off), cx.ws(t.off), cx.pl.B, a2.e, a2.e, a2.c, t_es, cx.st);
 }
 
+// Drop-out of a layer's output where the table has a site (and the forward was planned with p > 0).  Forward: in place, and
+// where the output is pooled the pooled tensor t[l] of the dropped values.  Backward: the output's gradient times 1 / (1 - p);
+// every consumer has already masked it with (dropped tensor > 0), and a dropped element is exactly 0 there.
+static int drop_launch(const Ctx &cx, int layer, bool bwd)
+{
+    const Plan &pl = cx.pl;
+    const Layer &L = LAYERS[layer];
+    char nm[40]; snprintf(nm, sizeof(nm), "drop%d.%s", L.level + 1, bwd ? "bwd" : "fwd");
+    ProfScope ps(nm);
+    const Act &y = pl.out(L);
+    if (bwd) return dropout_bwd(cx.ws(y.g), tensor_elems(pl.B, y.e, y.e, y.c), pl.drop_p, t_es, cx.st);
+    return dropout_pool_fwd(cx.ws(y.off), L.level < 4 ? cx.ws(pl.t[L.level].off) : nullptr, pl.B, y.e, y.e, y.c, pl.drop_p, pl.drop_seed,
+                            pl.drop_step, L.drop, t_es, cx.st);
+}
+
 // Forward of a 3x3 layer of the table: K_CONV, or K_CAT over the virtual concat of the padded skip t[l] and u[l].  The
 // second conv of an encoder level is followed by the pool, fused into its launch where the Winograd epilogue can.
 static int conv_forward(const Ctx &cx, int layer)
 {
     const Plan &pl = cx.pl;
     const Layer &L = LAYERS[layer];
-    const bool cat = L.kind == K_CAT, pools = L.out == T_A2 && L.level < 4;
+    const bool cat = L.kind == K_CAT, pools = L.out == T_A2 && L.level < 4, drops = pl.drops(L);
     const Act &x1 = pl.in(L), &y = pl.out(L), *x2 = cat ? &pl.u[L.level] : nullptr;
     bool pool_fused = false;
     {
         RowScope rs(layer, "fwd");
         int rc = conv_fwd_launch(cx.ws(x1.off), x1.e, x1.c, cat ? pl.pad[L.level] : 0, cat ? cx.ws(x2->off) : nullptr, cat ? x2->c : 0, pl.B, y.e + 2,
                                  cx.w(layer), cx.ws(pl.wt_fwd[layer]), cx.b(layer), y.c, 1, cx.ws(y.off), cx.st, cx.ws(pl.wu_fwd[layer]),
-                                 pools ? cx.ws(pl.t[L.level].off) : nullptr, &pool_fused);
+                                 pools && !drops ? cx.ws(pl.t[L.level].off) : nullptr, &pool_fused);
         if (rc) return rc;
     }
+    if (drops) return drop_launch(cx, layer, false);     // the pool must see the dropped values: its kernel pools too
     return pools && !pool_fused ? pool_launch(cx, L.level, false) : 0;
 }
 
-int unet_forward(unet_handle *h, const void *const *params, const void *x, void *logits, int B, int S,
-                 void *workspace, size_t workspace_bytes, int training, void *stream)
+// unet_forward and unet_forward_dropout (p > 0: the two drop-out sites of the table are active; p == 0 is unet_forward)
+static int forward_body(unet_handle *h, const void *const *params, const void *x, void *logits, int B, int S, void *workspace,
+                        size_t workspace_bytes, int training, float drop_p, unsigned long long drop_seed, unsigned long long drop_step,
+                        void *stream)
 {
     ARG_CHECK(h && params && x && logits && workspace, "unet_forward: null argument");
     CHECK_DEVICE(h, "unet_forward");
     Plan pl;
     int rc = make_plan(pl, h->base_ch, B, S, training, handle_math(h), h->n_classes);
     if (rc) return rc;
+    pl.drop_p = drop_p; pl.drop_seed = drop_seed; pl.drop_step = drop_step;
     MathScope ms(pl.math);
     ARG_CHECK(workspace_bytes >= pl.total, "unet_forward: workspace too small (%zu < %zu)", workspace_bytes, pl.total);
     ARG_CHECK(((uintptr_t)workspace & 255) == 0, "unet_forward: workspace must be 256-byte aligned");
@@ -724,6 +747,19 @@ int unet_forward(unet_handle *h, const void *const *params, const void *x, void 
     }
     if (training) h->remember(workspace, pl);
     return 0;
+}
+
+int unet_forward(unet_handle *h, const void *const *params, const void *x, void *logits, int B, int S,
+                 void *workspace, size_t workspace_bytes, int training, void *stream)
+{
+    return forward_body(h, params, x, logits, B, S, workspace, workspace_bytes, training, 0.f, 0, 0, stream);
+}
+
+int unet_forward_dropout(unet_handle *h, const void *const *params, const void *x, void *logits, int B, int S,
+                         void *workspace, size_t workspace_bytes, float p, unsigned long long seed, unsigned long long step, void *stream)
+{
+    ARG_CHECK(p >= 0.f && p < 1.f, "unet_forward_dropout: p must be in [0, 1), got %g", (double)p);
+    return forward_body(h, params, x, logits, B, S, workspace, workspace_bytes, 1, p, seed, step, stream);
 }
 
 int unet_activation_bytes(const unet_handle *h)
@@ -797,6 +833,9 @@ static int conv_backward(Ctx &cx, int layer)
     const Act &x = pl.in(L), &y = pl.out(L);
     const bool pooled = L.in == T_T;
     int rc;
+    // drop-out site: the output's gradient is scaled on the caller's stream before the weight gradient forks from it, so
+    // that both it and the dgrad read the scaled tensor
+    if (pl.drops(L) && (rc = drop_launch(cx, layer, true))) return rc;
     if ((rc = wgrad_backward(cx, layer))) return rc;
     {
         RowScope rs(layer, "dgrad");

@@ -10,6 +10,8 @@ device memory and streams; for data parallel the gradient all-reduce is the libr
 There is no CPU fallback: calling the module with a host tensor raises.
 """
 import ctypes as C
+import math
+import numbers
 
 import torch
 import torch.nn as nn
@@ -72,6 +74,22 @@ def check_n_classes(n_classes):
     return n_classes
 
 
+def check_dropout(p):
+    """A real number in [0, 1); raises ValueError otherwise (before any device work).  Returns it as a float."""
+    if isinstance(p, bool) or not isinstance(p, numbers.Real) or math.isnan(p) or not 0.0 <= p < 1.0:
+        raise ValueError("dropout must be a real number in [0, 1), got %r" % (p,))
+    return float(p)
+
+
+_MASK64 = (1 << 64) - 1
+
+
+def dropout_seed_for_rank(seed, rank):
+    """Drop-out seed of data-parallel rank `rank`: (seed + 0x9E3779B97F4A7C15 * rank) mod 2^64, so that the ranks (which
+    count the same steps) do not draw the same masks.  Rank 0 keeps `seed`."""
+    return (int(seed) + 0x9E3779B97F4A7C15 * int(rank)) & _MASK64
+
+
 def _stage_layout():
     """Gradient flat-buffer order = completion order of the backward stages (reverse layer order),
     so every stage's parameters form one contiguous bucket for the all-reduce."""
@@ -100,8 +118,16 @@ class _UnetFunction(torch.autograd.Function):
             ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
             logits = torch.empty(B, module.n_classes, So, So, dtype=torch.float32, device=x.device)
             ptab = _hip.ptr_table(params)
-            _hip.check(_hip.lib().unet_forward(h.h, ptab, _hip.ptr(x), _hip.ptr(logits), B, S, _hip.ptr(ws), nbytes, 1,
-                                               _hip.stream(x.device)), "unet_forward")
+            if module.training and module.dropout > 0:
+                # drop-out at the end of the contracting path: this forward's masks are those of (seed, step)
+                step = module.dropout_step
+                module.dropout_step = step + 1
+                _hip.check(_hip.lib().unet_forward_dropout(h.h, ptab, _hip.ptr(x), _hip.ptr(logits), B, S, _hip.ptr(ws), nbytes,
+                                                           module.dropout, module._rank_dropout_seed(), step & _MASK64,
+                                                           _hip.stream(x.device)), "unet_forward_dropout")
+            else:
+                _hip.check(_hip.lib().unet_forward(h.h, ptab, _hip.ptr(x), _hip.ptr(logits), B, S, _hip.ptr(ws), nbytes, 1,
+                                                   _hip.stream(x.device)), "unet_forward")
         ctx.save_for_backward(*params)
         ctx.ws, ctx.nbytes, ctx.dev, ctx.module, ctx.x_shape = ws, nbytes, dev, module, tuple(x.shape)
         return logits
@@ -141,16 +167,29 @@ class Unet(nn.Module):
     valid 3x3 convs, skips taken AFTER the pool and zero-padded to the up-conv size,
     1x1 head without activation; fp32; input [B,1,S,S] with S = 16L+60, L even."""
 
-    def __init__(self, base_ch=_BASE, n_classes=2):
+    def __init__(self, base_ch=_BASE, n_classes=2, dropout=0.0, dropout_seed=0):
         """Unet() as in the reference (no arguments).  base_ch is an extension: 32 gives the half-width
         net of BASELINE config #5 (forward and backward; its 32-channel layers take the implicit-GEMM
         kernels and half-filled weight-gradient tiles instead of the Winograd ones).
         n_classes is an extension too: a K-class head (2 <= K <= 16; finalconv [K,base_ch,1,1] + [K], logits [B,K,So,So]),
         trained with optim.softmax_ce_step (the paper's eq. 1).  Only finalconv changes: same 46 state-dict keys, and
-        Unet(n_classes=2) draws exactly the parameters Unet() draws for a seed."""
+        Unet(n_classes=2) draws exactly the parameters Unet() draws for a seed.
+        dropout is the paper's own (section 3.1: "Drop-out layers at the end of the contracting path perform further implicit
+        data augmentation"), which the reference left out: probability p in [0, 1) of dropping an element of conv42c's output
+        (before the pool: conv51c and the skip both see the dropped tensor) and of conv52c's output (before upconv4); kept
+        elements are scaled by 1 / (1 - p).  Active on training-mode forwards that record a backward; never under .eval() or
+        torch.no_grad().  The masks are a pure function of (dropout_seed, dropout_step, site, element): each such forward uses
+        dropout_step and increments it; dropout_state() / load_dropout_state() carry it across a resume.  No parameters, no
+        buffers, no RNG draw: the 46 state-dict keys and the parameters drawn for a torch seed are those of Unet().  The default
+        0.0 is the reference's net."""
         super(Unet, self).__init__()
         self.base_ch = base_ch
         self.n_classes = check_n_classes(n_classes)
+        self.dropout = check_dropout(dropout)
+        if isinstance(dropout_seed, bool) or not isinstance(dropout_seed, numbers.Integral) or not 0 <= dropout_seed <= _MASK64:
+            raise ValueError("dropout_seed must be an int in [0, 2^64), got %r" % (dropout_seed,))
+        self.dropout_seed = int(dropout_seed)
+        self.dropout_step = 0
         self._layer_table = _layers(base_ch, n_classes)
         # nn.Conv2d / nn.ConvTranspose2d serve ONLY as parameter containers with the reference's
         # names, shapes and default-init RNG consumption (their forward is never called).
@@ -183,6 +222,20 @@ class Unet(nn.Module):
         self._dp = dp_mod.DataParallel(self._own_handle, dev, process_group, backend)
         self._dp.broadcast_parameters(params)
         return self
+
+    # -- drop-out state: plain Python numbers, not buffers (the state dict stays the reference's 46 keys) -------------
+    def dropout_state(self):
+        return {"p": self.dropout, "seed": self.dropout_seed, "step": self.dropout_step}
+
+    def load_dropout_state(self, d):
+        p, seed, step = check_dropout(d["p"]), int(d["seed"]), int(d["step"])
+        if not 0 <= seed <= _MASK64 or step < 0:
+            raise ValueError("load_dropout_state: seed must be in [0, 2^64) and step >= 0, got %r" % (d,))
+        self.dropout, self.dropout_seed, self.dropout_step = p, seed, step
+        return self
+
+    def _rank_dropout_seed(self):
+        return dropout_seed_for_rank(self.dropout_seed, self._dp.rank if self._dp is not None else 0)
 
     def _get_handle(self, device_index):
         h = self._own_handle

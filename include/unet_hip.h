@@ -105,6 +105,24 @@ int unet_forward(unet_handle *h, const void *const *params, const void *x, void 
                  int B, int S, void *workspace, size_t workspace_bytes, int training,
                  void *stream);
 
+/* Training forward with drop-out at the end of the contracting path (Ronneberger et al. 2015, section 3.1: "Drop-out layers at
+ * the end of the contracting path perform further implicit data augmentation"; the reference has none: network.py:150-156).
+ * Two sites, as in the authors' network definition: site 0 = conv42c's output (after its ReLU, before the pool, so conv51c
+ * and the skip both see the dropped tensor), site 1 = conv52c's output (before upconv4).  Inverted, in place:
+ *   y = keep ? x * s : 0,  s = 1.0f / (1.0f - p) in fp32, one fp32 multiply per element (bf16 tensors: rounded to nearest even)
+ *   keep = word (idx & 3) of Philox4x32-10(counter, key) >= (uint32) min(floor(p * 2^32), 2^32 - 1)
+ *   idx = linear index into the NHWC tensor;  key = (seed lo, seed hi);
+ *   counter = (g lo, g hi, step lo, (step hi & 0x7fffffff) | site << 31),  g = idx >> 2
+ * Always a training forward (activations kept, the plan remembered with p: the backward of this workspace scales the two
+ * sites' gradients by s; the drop itself is in the consumers' ReLU masks).  Stateless: the caller owns seed and step.
+ * 0 <= p < 1; p == 0 is exactly the plain forward with training=1.  Same workspace as unet_workspace_bytes(h, B, S, 1). */
+int unet_forward_dropout(unet_handle *h, const void *const *params, const void *x, void *logits,
+                         int B, int S, void *workspace, size_t workspace_bytes, float p,
+                         unsigned long long seed, unsigned long long step, void *stream);
+/* The keep flags (1 / 0 bytes) of elements [first, first + n) of a site's tensor, as the forward above draws them. */
+int unet_dropout_mask(unsigned long long seed, unsigned long long step, int site, size_t first, size_t n, float p,
+                      void *keep_u8, void *stream);
+
 /* replaces: the autograd backward of every op in Unet.forward, triggered by
  * loss.backward() at trainer.py:77.
  *   dlogits : [B,K,So,So] fp32 NCHW (contiguous)
@@ -418,6 +436,12 @@ int unet_conv3x3_bwd(const void *x1, int H1, int W1, int C1, int pad1, const voi
 int unet_maxpool2_fwd(const void *x, void *y, int B, int H, int W, int C, void *stream);
 int unet_maxpool2_bwd(const void *pre, const void *dy, void *dpre, int B, int H, int W, int C,
                       void *stream);
+/* Drop-out (Ronneberger et al. 2015, section 3.1; flags and arithmetic as stated at unet_forward_dropout) of x [B,H,W,C] in
+ * place and, unless pooled is NULL, F.max_pool2d(2,2) of the dropped tensor into pooled [B,H/2,W/2,C]; its backward:
+ * g[0,n) *= 1 / (1 - p) in place.  H, W even, C % 4 == 0, 0 <= p < 1, site 0 or 1.                                    */
+int unet_dropout_pool_fwd(void *x_inout, void *pooled_or_null, int B, int H, int W, int C, float p,
+                          unsigned long long seed, unsigned long long step, int site, void *stream);
+int unet_dropout_bwd(void *g_inout, size_t n, float p, void *stream);
 /* nn.ConvTranspose2d(k2,s2), network.py:159-183: x [B,H,W,Ci] -> y [B,2H,2W,Co]; w IOHW. */
 size_t unet_upconv2_scratch_bytes(int B, int H, int W, int Ci, int Co);
 int unet_upconv2_fwd(const void *x, int B, int H, int W, int Ci, const void *w_iohw,
