@@ -5,6 +5,8 @@
   mirror_transform_tensor(image)     data.py:281-312
   test_input(images)                 data.py:184-188   mirror + (x-min)/ptp for a batch (ImageDataset_test)
   elastic_transform(images, a, s)    data.py:225-245   Simard-2003 elastic deformation (N1)
+  grid_displacements(rs, B, G, s)    -                 the paper's random displacement vectors on a coarse G x G grid
+  elastic_grid(images, disp, a)      -                 the paper's elastic deformation: that grid, bicubic, bilinear warp
   reflect_rotate_crop(images, deg)   data.py:106-125   reflect pad + cubic-spline rotation + centre crop, fused (N1)
   augment(image, target, ...)        data.py:97-135    ImageDataset.__getitem__ after the file reads, on the device
   preprocess_gt(img)                 data.py:195-221   borders carved between touching cells of an instance image
@@ -104,6 +106,65 @@ def elastic_transform(images, alpha, sigma, random_state=None, fields=None):
     return outs
 
 
+def grid_displacements(random_state, B, grid=3, sigma=10.0):
+    """The random input of the paper's elastic deformation (Ronneberger et al. 3.1: "random displacement vectors on a coarse 3
+    by 3 grid ... sampled from a Gaussian distribution with 10 pixels standard deviation"): float64 [B,2,grid,grid] in pixels,
+    equal to random_state.normal(0, sigma, (B, 2, grid, grid)).  The draw order is the contract: sample after sample, for one
+    sample the grid x grid row displacements (plane 0, row-major) before its column displacements (plane 1) - 2 grid^2 normal
+    draws per sample and nothing else, so a caller can replay or interleave them."""
+    G = int(grid)
+    if G < 2:
+        raise ValueError("grid_displacements: a grid of %d nodes per side, need at least 2" % G)
+    if random_state is None:
+        raise ValueError("grid_displacements draws from a numpy RandomState; got None")
+    return random_state.normal(0, sigma, (int(B), 2, G, G))
+
+
+MAX_ELASTIC_GRID = 16      # UNET_ELASTIC_MAX_GRID
+
+
+def _grid_tensor(disp, B, dev, name):
+    """disp [2,G,G] (every sample) or [B,2,G,G], numpy or tensor of any float type -> contiguous fp64 [B,2,G,G] on dev"""
+    d = disp.detach() if torch.is_tensor(disp) else torch.from_numpy(np.ascontiguousarray(disp, dtype=np.float64))
+    if d.dim() == 3:
+        d = d[None].expand(B, *d.shape)
+    if d.dim() != 4 or d.shape[0] != B or d.shape[1] != 2 or d.shape[2] != d.shape[3]:
+        raise ValueError("%s: disp must be [2,G,G] or [%d,2,G,G], got %s" % (name, B, tuple(disp.shape)))
+    if not 2 <= d.shape[2] <= MAX_ELASTIC_GRID:
+        raise ValueError("%s: a grid of %d nodes per side, need 2 .. %d" % (name, d.shape[2], MAX_ELASTIC_GRID))
+    return d.to(dev, torch.float64).contiguous()
+
+
+def elastic_grid(images, disp, a=-0.5):
+    """The paper's elastic deformation (Ronneberger et al. 3.1).  images: tuple of device tensors of equal shape
+    [H,W] or [B,H,W]; every image of a sample is warped with the SAME displacements (image and mask).  disp: [B,2,G,G], or
+    [2,G,G] for every sample alike - displacement vectors in pixels on a coarse corner-aligned G x G grid (plane 0 moves rows,
+    plane 1 columns, elastic_transform's dx and dy; grid_displacements draws them), numpy or a tensor of any float type, used
+    as fp64.  They are brought to every pixel by Keys' cubic convolution with parameter a (-0.5: Keys' third-order kernel,
+    "bicubic" as MATLAB has it; -0.75: what torch's bicubic interpolate computes) and the images sampled bilinearly at the
+    displaced coordinates, 0 outside the image, in one kernel in fp64 - no field exists in memory.  Returns the list of warped
+    float32 tensors.  ValueError on host tensors, on shapes that do not agree and on G < 2; there is no CPU implementation."""
+    if len(images) == 0:
+        raise ValueError("elastic_grid: no image")
+    for im in images:
+        if not torch.is_tensor(im) or not im.is_cuda:
+            raise ValueError("elastic_grid runs on the HIP device only (unet_elastic_grid): move the images to the device first")
+        if im.dim() not in (2, 3) or im.shape != images[0].shape:
+            raise ValueError("elastic_grid takes images of one shape [H,W] or [B,H,W], got %s" % ([tuple(i.shape) for i in images],))
+    B, H, W = _as_batch(images[0]).shape
+    if H < 2 or W < 2:
+        raise ValueError("elastic_grid: a sample of %d x %d, need at least 2 x 2" % (H, W))
+    dev = images[0].device
+    d = _grid_tensor(disp, B, dev, "elastic_grid")
+    outs = []
+    for im in images:
+        x = _as_batch(im).contiguous().float()
+        o = torch.empty_like(x)
+        _hip.run("unet_elastic_grid", dev, _hip.ptr(x), 1, B, H, W, _hip.ptr(d), d.shape[2], float(a), _hip.ptr(o))
+        outs.append(o.reshape(im.shape))
+    return outs
+
+
 def reflect_rotate_crop(images, angles_deg, input_size=None, levels=255):
     """images: device tensor [n,n] or [B,n,n] (the random crop of the sample, e.g. 388^2); angles_deg: one angle or B angles
     (the reference draws one of 0,30,...,330 per sample, data.py:113).  Returns [S,S] / [B,S,S] with S = input_size: the centre
@@ -134,14 +195,42 @@ def reflect_rotate_crop(images, angles_deg, input_size=None, levels=255):
     return out[0] if single else out
 
 
-def augment(image, target, crop_xy, crop, rot_deg, alpha, sigma, random_state=None, fields=None, levels=255):
+def _grid_stage(both, crop, disp, a, levels):
+    """augment's elastic='grid' stage: both [2B,S,S] = the rotated images, then the rotated masks -> (inp [B,S,S] in [0,1],
+    gt [B,crop,crop] int64).  One small upload (the nodes) and the library's two calls; no ATen arithmetic."""
+    B, S = both.shape[0] // 2, both.shape[-1]
+    dev = both.device
+    pad = int((S - crop) / 2)
+    d = _grid_tensor(disp, B, dev, "augment")
+    inp = torch.empty(B, S, S, dtype=torch.float32, device=dev)
+    gt = torch.empty(B, crop, crop, dtype=torch.int64, device=dev)
+    mm = torch.empty(B, 2, dtype=torch.float32, device=dev)
+    _hip.run("unet_elastic_grid_sample", dev, _hip.ptr(both[:B]), _hip.ptr(both[B:]), B, S, _hip.ptr(d), d.shape[2], float(a),
+             int(levels), pad, int(crop), _hip.ptr(inp), _hip.ptr(gt), _hip.ptr(mm))
+    _hip.run("unet_normalise01", dev, _hip.ptr(inp), B, S * S, _hip.ptr(mm))
+    return inp, gt
+
+
+def augment(image, target, crop_xy, crop, rot_deg, alpha, sigma, random_state=None, fields=None, levels=255, elastic='field', grid=3,
+            disp=None, a=-0.5):
     """What ImageDataset.__getitem__ does to one sample after reading it (data.py:97-135), on the device.  The random draws
     stay with the caller (crop origin from the weighted distribution + jitter, rot_deg from np.arange(0,360,30), the elastic
     fields), so the host RNG sequence can follow the reference's:  crop -> reflect pad + rotate + centre crop -> the same
     elastic deformation for image and mask -> mask cropped to the label extent and thresholded at 127 -> image to [0,1].
     image / target: device tensors [H,W] (grey levels / {0,255}); returns (inp [1,S,S] float32, gt [1,crop,crop] int64).
     A whole batch in one call (the DataLoader's collate, vectorised): image / target [B,H,W], crop_xy a list of B origins,
-    rot_deg B angles; returns (inp [B,1,S,S], gt [B,1,crop,crop]) - every kernel then runs once for the batch."""
+    rot_deg B angles; returns (inp [B,1,S,S], gt [B,1,crop,crop]) - every kernel then runs once for the batch.
+    elastic='field' (default) is the reference's deformation, elastic_transform.  elastic='grid' is the paper's (elastic_grid):
+    sigma is then the standard deviation in pixels of the displacements of the grid x grid nodes, and alpha and fields are
+    ignored.  The node displacements are disp ([B,2,G,G], or [2,G,G] for one sample) or, when disp is None,
+    grid_displacements(random_state, B, grid, sigma): random_state must then be given, the device generator is not used.
+    After the rotation the grid path is two kernels: unet_elastic_grid_sample (warp of image and mask, rounding, crop and
+    threshold of the mask, per-sample min / max) and unet_normalise01."""
+    if elastic not in ('field', 'grid'):
+        raise ValueError("augment: elastic is 'field' or 'grid', got %r" % (elastic,))
+    if elastic == 'grid' and disp is None and random_state is None:
+        raise ValueError("augment(elastic='grid') draws the node displacements from random_state (a numpy RandomState): "
+                         "pass one, or pass disp")
     batched = image.dim() == 3
     imgs = image if batched else image[None]
     tgts = target if batched else target[None]
@@ -154,6 +243,11 @@ def augment(image, target, crop_xy, crop, rot_deg, alpha, sigma, random_state=No
     tgt = torch.stack([tgts[b, x0:x0 + crop, y0:y0 + crop] for b, (x0, y0) in enumerate(origins)]).float()
     _, S, _ = input_size_compute(img)
     both = reflect_rotate_crop(torch.cat((img, tgt)), angles + angles, S, levels=levels)            # [2B,S,S]: images, then masks
+    if elastic == 'grid':
+        inp, gt = _grid_stage(both, crop, grid_displacements(random_state, B, grid, sigma) if disp is None else disp, a, levels)
+        if batched:
+            return inp[:, None], gt[:, None]
+        return inp[0][None], gt[0][None]
     inp, gt = elastic_transform((both[:B], both[B:]), alpha, sigma, random_state=random_state, fields=fields)
     if levels:
         # the reference warps the uint8 / uint16 arrays it loaded: scipy's map_coordinates writes its result in the input's
@@ -306,9 +400,18 @@ class CropDataset:
     reference's order, and the batch goes through one data.augment call, so each item is (inp [B,1,S,S] float32,
     gt [B,1,crop,crop] int64) on the device - usable as train_loader / val_loader of trainer.training as it is.  The elastic
     fields come from random_state (a numpy RandomState, drawn as the reference's elastic_transform draws them), or from the
-    device generator when it is None."""
+    device generator when it is None.  elastic='grid' deforms with the paper's grid x grid displacement grid instead
+    (augment(elastic='grid'): sigma is the nodes' standard deviation in pixels, alpha is ignored, random_state is required)."""
 
-    def __init__(self, images, instances, alpha, sigma, crop, batch_size, rng, levels=255, *, random_state=None, skip=10, device=None):
+    def __init__(self, images, instances, alpha, sigma, crop, batch_size, rng, levels=255, *, random_state=None, skip=10, device=None,
+                 elastic='field', grid=3):
+        if elastic not in ('field', 'grid'):
+            raise ValueError("CropDataset: elastic is 'field' or 'grid', got %r" % (elastic,))
+        if elastic == 'grid' and random_state is None:
+            raise ValueError("CropDataset(elastic='grid') draws the node displacements from random_state (a numpy RandomState)")
+        if elastic == 'grid' and int(grid) < 2:
+            raise ValueError("CropDataset: a grid of %d nodes per side, need at least 2" % int(grid))
+        self.elastic, self.grid = elastic, int(grid)
         if device is None:
             device = images.device if torch.is_tensor(images) and images.is_cuda else torch.device("cuda", torch.cuda.current_device())
         self.device = torch.device(device)
@@ -338,4 +441,4 @@ class CropDataset:
             idx = list(range(lo, min(N, lo + self.batch_size)))
             draws = [self.draw(i) for i in idx]
             yield augment(self.image[idx], self.target[idx], [d[0] for d in draws], self.crop, [d[1] for d in draws], self.alpha,
-                          self.sigma, random_state=self.random_state, levels=self.levels)
+                          self.sigma, random_state=self.random_state, levels=self.levels, elastic=self.elastic, grid=self.grid)

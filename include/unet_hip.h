@@ -410,6 +410,28 @@ int unet_warp_bilinear(const void *img, const void *dy, const void *dx, int B, i
 size_t unet_rotate_scratch_bytes(int B, int S);
 int unet_reflect_rotate_crop(const void *img, int B, int n, int pad, int S, const float *angles_deg_host, int levels,
                              void *out, void *scratch, void *stream);
+/* The paper's elastic deformation (Ronneberger et al. §3.1): per sample a coarse displacement grid g [2,G,G]
+ * fp64 in pixels (plane 0 displaces rows, plane 1 columns; 2 <= G <= UNET_ELASTIC_MAX_GRID), corner-aligned on the H x W
+ * sample (row y sits at grid position y (G-1)/(H-1)), interpolated to every pixel with Keys' cubic convolution of parameter a
+ * (-0.5: Keys' third-order kernel; -0.75: torch's bicubic), node indices clamped to [0, G-1]; the planes are then sampled at
+ * (y + d_row, x + d_col) as unet_warp_bilinear samples (bilinear inside [0,H-1] x [0,W-1], 0 outside).  Displacement,
+ * coordinate and bilinear combination are fp64 on the device, narrowed to fp32 at the store; no field is ever stored.
+ * grid_f64: DEVICE fp64 [B,2,G,G].  H, W >= 2.
+ *   unet_elastic_grid        : planes fp32 [P,B,H,W] -> out fp32 [P,B,H,W], every plane of sample b warped with grid b; one
+ *                              launch, no rounding.
+ *   unet_elastic_grid_sample : the training sample.  img, mask fp32 [B,S,S]; out_img fp32 [B,S,S] = the warped image,
+ *                              rounded for levels = 255 / 65535 as the reference's integer images round (floor(v + 0.5)
+ *                              clamped to [0, levels]; levels = 0 keeps the float value); minmax fp32 [B][2] = each
+ *                              sample's min and max of out_img; out_gt_i64 [B,crop,crop] = (the mask warped with the same
+ *                              grid and rounded the same way) > 127, formed for the window [pad, pad+crop)^2 only
+ *                              (pad >= 0, crop >= 1, pad + crop <= S).
+ *   unet_normalise01         : x fp32 [B][n] in place: (x - lo) / (hi - lo) with lo, hi = minmax[b] (fp32, true division;
+ *                              hi == lo gives 0/0 = NaN, as the expression does).                                          */
+#define UNET_ELASTIC_MAX_GRID 16
+int unet_elastic_grid(const void *planes, int P, int B, int H, int W, const void *grid_f64, int G, double a, void *out, void *stream);
+int unet_elastic_grid_sample(const void *img, const void *mask, int B, int S, const void *grid_f64, int G, double a, int levels,
+                             int pad, int crop, void *out_img, void *out_gt_i64, void *minmax, void *stream);
+int unet_normalise01(void *x, int B, size_t n, const void *minmax, void *stream);
 
 /* ---- per-op entry points (NHWC fp32), used by the unit tests ---------------------------------
  * Each replaces the ATen op dispatched at the cited line.  w_* are in reference layout.    */
