@@ -188,6 +188,11 @@ def run(name, device, *args):
         check(getattr(lib(), name)(*args, stream(device)), name)
 
 
+def scratch(name, device, *dims):
+    """The uint8 scratch tensor an entry point asks for: lib().<name>_scratch_bytes(*dims) bytes on `device`."""
+    return torch.empty(getattr(lib(), name + "_scratch_bytes")(*dims), dtype=torch.uint8, device=device)
+
+
 def ptr_table(tensors):
     arr = (C.c_void_p * len(tensors))()
     for i, t in enumerate(tensors):

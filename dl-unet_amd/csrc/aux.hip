@@ -10,23 +10,14 @@
 
 namespace unet {
 
-__device__ __forceinline__ float wave_min(float v) { for (int d = 32; d >= 1; d >>= 1) v = fminf(v, __shfl_xor(v, d, 64)); return v; }
-__device__ __forceinline__ float wave_max(float v) { for (int d = 32; d >= 1; d >>= 1) v = fmaxf(v, __shfl_xor(v, d, 64)); return v; }
-
 // ---- per-image min / max: one workgroup per image (images are <= a few MB) ------------------------
 __global__ __launch_bounds__(1024) void minmax_kernel(const float *__restrict__ x, size_t n, float *__restrict__ out)
 {
     const float *p = x + (size_t)blockIdx.x * n;
     float lo = INFINITY, hi = -INFINITY;
     for (size_t i = threadIdx.x; i < n; i += blockDim.x) { const float v = p[i]; lo = fminf(lo, v); hi = fmaxf(hi, v); }
-    lo = wave_min(lo); hi = wave_max(hi);
-    __shared__ float slo[16], shi[16];
-    if ((threadIdx.x & 63) == 0) { slo[threadIdx.x >> 6] = lo; shi[threadIdx.x >> 6] = hi; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < (int)(blockDim.x >> 6); ++w) { lo = fminf(lo, slo[w]); hi = fmaxf(hi, shi[w]); }
-        out[2 * blockIdx.x] = lo; out[2 * blockIdx.x + 1] = hi;
-    }
+    const MinMax m = block_minmax<16>(lo, hi);
+    if (threadIdx.x == 0) { out[2 * blockIdx.x] = m.lo; out[2 * blockIdx.x + 1] = m.hi; }
 }
 
 // ---- mirror_transform (+ optional (x-min)/ptp): out[b,Y,X] = in[b, r(Y), r(X)] --------------------
@@ -72,9 +63,7 @@ __global__ __launch_bounds__(256) void eval_masks_kernel(const float *__restrict
         }
     }
     if (!labels) return;
-    for (int d = 32; d >= 1; d >>= 1) {
-        inter += __shfl_xor(inter, d, 64); uni += __shfl_xor(uni, d, 64); diff += __shfl_xor(diff, d, 64);
-    }
+    inter = wave_sum(inter); uni = wave_sum(uni); diff = wave_sum(diff);
     if ((threadIdx.x & 63) == 0) {       // integer atomics: order-independent, exact
         atomicAdd(&stats[3 * b], inter); atomicAdd(&stats[3 * b + 1], uni); atomicAdd(&stats[3 * b + 2], diff);
     }
@@ -87,7 +76,7 @@ __global__ __launch_bounds__(256) void count_ones_kernel(const long long *__rest
     unsigned long long c = 0;
     for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < npx; e += (size_t)gridDim.x * blockDim.x)
         c += labels[(size_t)b * npx + e] != 0;
-    for (int d = 32; d >= 1; d >>= 1) c += __shfl_xor(c, d, 64);
+    c = wave_sum(c);
     if ((threadIdx.x & 63) == 0) atomicAdd(&counts[b], c);
 }
 __global__ __launch_bounds__(256) void class_balance_kernel(const long long *__restrict__ labels, size_t npx,

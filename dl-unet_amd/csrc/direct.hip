@@ -138,8 +138,7 @@ __global__ __launch_bounds__(256) void conv1ch_wgrad_reduce_kernel(const float *
     if (e >= 10 * K) return;
     float s = 0.f;
     for (int b = lane; b < nb; b += 64) s += partial[(size_t)b * 10 * K + e];
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d, 64);
+    s = wave_sum(s);
     if (lane == 0) {
         const int t = e / K, kk = e - t * K;
         if (t < 9) { if (dw) dw[kk * 9 + t] = s; } else if (db) db[kk] = s;
@@ -253,8 +252,7 @@ __global__ __launch_bounds__(256) void head1x1_bwd_reduce_kernel(const float *__
     if (e >= 2 * C + 2) return;
     float s = 0.f;
     for (int b = lane; b < nb; b += 64) s += partial[(size_t)b * (2 * C + 2) + e];
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d, 64);
+    s = wave_sum(s);
     if (lane == 0) { if (e < 2 * C) { if (dw) dw[e] = s; } else if (db) db[e - 2 * C] = s; }
 }
 

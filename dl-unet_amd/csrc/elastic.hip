@@ -139,8 +139,6 @@ __global__ __launch_bounds__(256) void elastic_grid_kernel(const float *__restri
     }
 }
 
-__device__ __forceinline__ float wave_min_f32(float v) { for (int d = 32; d >= 1; d >>= 1) v = fminf(v, __shfl_xor(v, d, 64)); return v; }
-__device__ __forceinline__ float wave_max_f32(float v) { for (int d = 32; d >= 1; d >>= 1) v = fmaxf(v, __shfl_xor(v, d, 64)); return v; }
 // float min / max as integer atomics: non-negative floats order like their bits as signed integers, negative ones the other way
 // round as unsigned integers (which also places them above every non-negative one).  -0 is stored as +0; a NaN is left out.
 __device__ __forceinline__ void atomic_min_f32(float *addr, float v)
@@ -169,7 +167,6 @@ __global__ __launch_bounds__(256) void elastic_sample_kernel(const float *__rest
                                                              float *__restrict__ out_img, long long *__restrict__ out_gt, float *__restrict__ minmax)
 {
     __shared__ EgShared s;
-    __shared__ float slo[4], shi[4];
     const int b = blockIdx.z, x0 = blockIdx.x * EG_TX, y0 = blockIdx.y * EG_TY;
     eg_prologue(s, grid, b, G, a, S, S, y0, x0);
     const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
@@ -197,13 +194,10 @@ __global__ __launch_bounds__(256) void elastic_sample_kernel(const float *__rest
             }
         }
     }
-    lo = wave_min_f32(lo); hi = wave_max_f32(hi);
-    if ((threadIdx.x & 63) == 0) { slo[threadIdx.x >> 6] = lo; shi[threadIdx.x >> 6] = hi; }
-    __syncthreads();
+    const MinMax m = block_minmax<4>(lo, hi);
     if (threadIdx.x == 0) {
-        for (int w = 1; w < 4; ++w) { lo = fminf(lo, slo[w]); hi = fmaxf(hi, shi[w]); }
-        atomic_min_f32(minmax + 2 * b, lo);
-        atomic_max_f32(minmax + 2 * b + 1, hi);
+        atomic_min_f32(minmax + 2 * b, m.lo);
+        atomic_max_f32(minmax + 2 * b + 1, m.hi);
     }
 }
 

@@ -1,9 +1,11 @@
-// elem.hpp — what the HBM-bound kernels (direct.hip, multiclass.hip, tile.hip, aux.hip) share:
+// elem.hpp — what the HBM-bound kernels (direct.hip, multiclass.hip, tile.hip, aux.hip) and the data-path files (wmap.hip,
+// instances.hip, prepare.hip, grow.hip, elastic.hip) share:
 //   device : 4 consecutive channels of an activation tensor stored as fp32 (16 B) or bf16 (8 B, arithmetic mode 2), read /
-//            written as 4 floats; the sum of one value per thread over a 256-thread block, and (instances.hip, prepare.hip) the
+//            written as 4 floats; the sum / min / max of one value per lane over a wave; the min and max of one value per thread
+//            over a block; the sum of one value per thread over a 256-thread block, and (instances.hip, prepare.hip) the
 //            exclusive prefix of one int per thread over it
-//   host   : the grid size of a grid-stride launch, and the dispatch of a launch on element size, channel width and padded
-//            class count (the launch bracket, profiled(), is common.hpp's)
+//   host   : the grid size of a grid-stride launch, the bytes of a [B,H,W] scratch plane, and the dispatch of a launch on
+//            element size, channel width and padded class count (the launch bracket, profiled(), is common.hpp's)
 #pragma once
 #include "common.hpp"
 #include <type_traits>
@@ -31,6 +33,27 @@ __device__ __forceinline__ void store4(bf16_t *p, f32x4 v)
     *(uint2 *)p = w;
 }
 
+// 64-lane butterflies: the result is valid in every lane
+template <typename V>
+__device__ __forceinline__ V wave_sum(V v) { for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64); return v; }
+__device__ __forceinline__ float wave_min(float v) { for (int d = 32; d >= 1; d >>= 1) v = fminf(v, __shfl_xor(v, d, 64)); return v; }
+__device__ __forceinline__ float wave_max(float v) { for (int d = 32; d >= 1; d >>= 1) v = fmaxf(v, __shfl_xor(v, d, 64)); return v; }
+
+// min and max of one (lo, hi) pair per thread over a block of NW waves: one wave result per wave through LDS, thread 0 combines
+// them: only its return value is the block's
+struct MinMax { float lo, hi; };
+template <int NW>
+__device__ __forceinline__ MinMax block_minmax(float lo, float hi)
+{
+    __shared__ float slo[NW], shi[NW];
+    lo = wave_min(lo); hi = wave_max(hi);
+    if ((threadIdx.x & 63) == 0) { slo[threadIdx.x >> 6] = lo; shi[threadIdx.x >> 6] = hi; }
+    __syncthreads();
+    if (threadIdx.x == 0)
+        for (int w = 1; w < NW; ++w) { lo = fminf(lo, slo[w]); hi = fmaxf(hi, shi[w]); }
+    return {lo, hi};
+}
+
 // Sum of one value per thread over a 256-thread block: LDS tree in the fixed order 128, 64, ... 1 (deterministic); the total is
 // valid in thread 0
 template <typename V>
@@ -48,21 +71,21 @@ __device__ __forceinline__ V block_sum256(V v)
 // exclusive prefix of v over the 256 threads of the workgroup, and their sum
 __device__ __forceinline__ int block_scan256(int v, int &total)
 {
-    __shared__ int wave_sum[4];
+    __shared__ int wave_tot[4];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     int inc = v;
     for (int d = 1; d < 64; d <<= 1) {
         const int t = __shfl_up(inc, d, 64);
         if (lane >= d) inc += t;
     }
-    __syncthreads();                                        // the previous call's reads of wave_sum are done
-    if (lane == 63) wave_sum[w] = inc;
+    __syncthreads();                                        // the previous call's reads of wave_tot are done
+    if (lane == 63) wave_tot[w] = inc;
     __syncthreads();
     int before = 0;
     total = 0;
     for (int i = 0; i < 4; ++i) {
-        if (i < w) before += wave_sum[i];
-        total += wave_sum[i];
+        if (i < w) before += wave_tot[i];
+        total += wave_tot[i];
     }
     return before + inc - v;
 }
@@ -73,9 +96,18 @@ static inline int grid_for(size_t total, int per_block = 256, int cap = 8192)
     return (int)(g < 1 ? 1 : (g > (size_t)cap ? cap : g));
 }
 
+// bytes of a [B,H,W] plane of elem_size-byte words inside a scratch buffer, 256-aligned
+static inline size_t plane_bytes(int B, int H, int W, size_t elem_size) { return align_up((size_t)B * H * W * elem_size, 256); }
+
 // Launch dispatch: f is a generic lambda that receives the storage type as a value of it (es 2: bf16_t, else float), then the
 // channel width (32 or 64; the callers have checked it) and for the K-class head KP = class_pad(K) (4, 8 or 16: K = 2 runs the
-// head1x1 kernels) as std::integral_constant, so a launch function names its kernel and its arguments once
+// head1x1 kernels) as std::integral_constant, so a launch function names its kernel and its arguments once; dispatch_bool does
+// the same for one flag (tile.hip: 16-byte aligned or not), as std::bool_constant
+template <class F>
+static inline void dispatch_bool(bool v, F f)
+{
+    if (v) f(std::true_type{}); else f(std::false_type{});
+}
 template <class F>
 static inline void dispatch_es(int es, F f)
 {

@@ -24,7 +24,7 @@
 //
 // Coherence (wmap.hip's rule): grow_rows reads what grow_cols, an earlier kernel, wrote; in grow_cols a thread re-reads only the
 // words of its own column, which it wrote itself.  No word is handed from one workgroup to another inside a kernel.
-#include "common.hpp"
+#include "elem.hpp"
 #include <algorithm>
 #include <cmath>
 #include "../../include/unet_hip.h"
@@ -103,7 +103,7 @@ using namespace unet;
 size_t unet_grow_labels_scratch_bytes(int B, int H, int W)
 {
     if (B <= 0 || H <= 0 || W <= 0) return 0;
-    return align_up((size_t)B * H * W * sizeof(unsigned long long), 256);
+    return plane_bytes(B, H, W, sizeof(unsigned long long));
 }
 
 int unet_grow_labels(const void *labels_i32, int B, int H, int W, long long max_dist2, void *out_i32, void *scratch, void *stream)

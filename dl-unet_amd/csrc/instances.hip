@@ -30,7 +30,6 @@
 // pairs_compact, and every pass of the labelling, reads
 // what an earlier kernel wrote.  No word is handed from one workgroup to another inside a kernel by plain loads and stores.
 #include "elem.hpp"
-#include <algorithm>
 #include "../../include/unet_hip.h"
 
 namespace unet {
@@ -100,11 +99,6 @@ __device__ __forceinline__ unsigned long long ov_hash(unsigned long long x)
     x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ull;
     return x ^ (x >> 33);
 }
-__device__ __forceinline__ unsigned long long wave_sum64(unsigned long long v)
-{
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
 
 // adds n to the counter of `key`; false when the key is absent and no slot is free
 __device__ __forceinline__ bool ov_insert(unsigned long long *keys, unsigned *cnt, size_t slots, unsigned long long key, unsigned n)
@@ -162,7 +156,7 @@ __global__ __launch_bounds__(256) void overlap_fill_kernel(const int *__restrict
         }
         full = __any(full);
     }
-    bad = wave_sum64(bad); dropped = wave_sum64(dropped); g0 = wave_sum64(g0); p0 = wave_sum64(p0);
+    bad = wave_sum(bad); dropped = wave_sum(dropped); g0 = wave_sum(g0); p0 = wave_sum(p0);
     if (lane == 0) {
         if (bad) __hip_atomic_fetch_add(&status[2 * b], bad, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (dropped) __hip_atomic_fetch_add(&status[2 * b + 1], dropped, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -218,7 +212,7 @@ __global__ __launch_bounds__(256) void pairs_compact_kernel(const unsigned long 
 
 using namespace unet;
 
-static size_t in_plane(int B, int H, int W) { return align_up((size_t)B * H * W * sizeof(int), 256); }
+static size_t in_plane(int B, int H, int W) { return plane_bytes(B, H, W, sizeof(int)); }
 static size_t in_chunks(int H, int W) { return ((size_t)H * W + IN_CHUNK - 1) / IN_CHUNK; }
 static size_t in_chunk_bytes(int B, int H, int W) { return align_up((size_t)B * in_chunks(H, W) * sizeof(int), 256); }
 
@@ -246,46 +240,64 @@ int unet_label_components(const void *mask, int dtype, int B, int H, int W, void
     hipLaunchKernelGGL(inst_count_kernel, dim3(nchunk, B), dim3(256), 0, st, (const int *)label, npx, chunk_roots);
     hipLaunchKernelGGL(inst_scan_kernel, dim3(B), dim3(256), 0, st, chunk_roots, (int)nchunk);
     hipLaunchKernelGGL(inst_rank_kernel, dim3(nchunk, B), dim3(256), 0, st, (const int *)label, npx, (const int *)chunk_roots, plane);
-    hipLaunchKernelGGL(inst_write_kernel, dim3((unsigned)std::min<size_t>((npx + 255) / 256, 2048), B), dim3(256), 0, st, label, npx,
+    hipLaunchKernelGGL(inst_write_kernel, dim3(grid_for(npx, 256, 2048), B), dim3(256), 0, st, label, npx,
                        (const int *)plane);
     HIP_TRY(hipGetLastError());
     return 0;
 }
 
+struct OvTable { unsigned long long *keys; unsigned *cnt; };
 static size_t ov_key_bytes(size_t slots) { return align_up(slots * sizeof(unsigned long long), 256); }
+static size_t ov_scratch_bytes(size_t slots) { return ov_key_bytes(slots) + align_up(slots * sizeof(unsigned), 256); }
+
+// what unet_instance_overlap (FG = false) and unet_partition_pairs (FG = true) share: the checks, the table carved from the
+// scratch, the clears of everything overlap_fill adds to (FG: no histograms, area_gt and area_pred are null) and its launch
+template <bool FG>
+static int ov_fill(const char *who, const void *gt_i32, const void *pred_i32, int B, int H, int W, int ng_max, int np_max,
+                   size_t table_slots, void *area_gt_u32, void *area_pred_u32, void *status_u64, void *scratch, hipStream_t st, OvTable &t)
+{
+    ARG_CHECK(gt_i32 && pred_i32 && status_u64 && scratch && B > 0 && H > 0 && W > 0, "%s: bad argument", who);
+    ARG_CHECK((size_t)H * W < (1u << 31) && B <= 65535, "%s: image too large", who);
+    ARG_CHECK(ng_max >= 0 && np_max >= 0 && ng_max <= OV_ID_MAX && np_max <= OV_ID_MAX, "%s: ng_max and np_max must be in [0, %d]", who,
+              OV_ID_MAX);
+    ARG_CHECK(table_slots > 0 && (table_slots & (table_slots - 1)) == 0, "%s: table_slots must be a power of two", who);
+    const size_t npx = (size_t)H * W;
+    t.keys = (unsigned long long *)scratch;
+    t.cnt = (unsigned *)((char *)scratch + ov_key_bytes(table_slots));
+    HIP_TRY(hipMemsetAsync(t.keys, 0xFF, table_slots * sizeof(unsigned long long), st));        // OV_EMPTY
+    HIP_TRY(hipMemsetAsync(t.cnt, 0, table_slots * sizeof(unsigned), st));
+    if (!FG) {
+        HIP_TRY(hipMemsetAsync(area_gt_u32, 0, B * ((size_t)ng_max + 1) * sizeof(unsigned), st));
+        HIP_TRY(hipMemsetAsync(area_pred_u32, 0, B * ((size_t)np_max + 1) * sizeof(unsigned), st));
+    }
+    HIP_TRY(hipMemsetAsync(status_u64, 0, (size_t)B * 2 * sizeof(unsigned long long), st));
+    hipLaunchKernelGGL(overlap_fill_kernel<FG>, dim3(grid_for(npx, 256, 2048), B), dim3(256), 0, st, (const int *)gt_i32,
+                       (const int *)pred_i32, npx, ng_max, np_max, t.keys, t.cnt, table_slots, (unsigned *)area_gt_u32,
+                       (unsigned *)area_pred_u32, (unsigned long long *)status_u64);
+    return 0;
+}
 
 size_t unet_instance_overlap_scratch_bytes(int B, int ng_max, int np_max, size_t table_slots)
 {
     if (B <= 0 || ng_max < 0 || np_max < 0 || table_slots == 0) return 0;
-    return ov_key_bytes(table_slots) + align_up(table_slots * sizeof(unsigned), 256);
+    return ov_scratch_bytes(table_slots);
 }
 
 int unet_instance_overlap(const void *gt_i32, const void *pred_i32, int B, int H, int W, int ng_max, int np_max, size_t table_slots,
                           void *area_gt_u32, void *area_pred_u32, void *match_i32, void *inter_u32, void *status_u64, void *scratch,
                           void *stream)
 {
-    ARG_CHECK(gt_i32 && pred_i32 && area_gt_u32 && area_pred_u32 && match_i32 && inter_u32 && status_u64 && scratch && B > 0 &&
-              H > 0 && W > 0, "unet_instance_overlap: bad argument");
-    ARG_CHECK((size_t)H * W < (1u << 31) && B <= 65535, "unet_instance_overlap: image too large");
-    ARG_CHECK(ng_max >= 0 && np_max >= 0 && ng_max <= OV_ID_MAX && np_max <= OV_ID_MAX,
-              "unet_instance_overlap: ng_max and np_max must be in [0, %d]", OV_ID_MAX);
-    ARG_CHECK(table_slots > 0 && (table_slots & (table_slots - 1)) == 0, "unet_instance_overlap: table_slots must be a power of two");
+    ARG_CHECK(area_gt_u32 && area_pred_u32 && match_i32 && inter_u32, "unet_instance_overlap: bad argument");
     hipStream_t st = (hipStream_t)stream;
-    const size_t npx = (size_t)H * W, ng1 = (size_t)ng_max + 1, np1 = (size_t)np_max + 1;
-    unsigned long long *keys = (unsigned long long *)scratch;
-    unsigned *cnt = (unsigned *)((char *)scratch + ov_key_bytes(table_slots));
-    HIP_TRY(hipMemsetAsync(keys, 0xFF, table_slots * sizeof(unsigned long long), st));          // OV_EMPTY
-    HIP_TRY(hipMemsetAsync(cnt, 0, table_slots * sizeof(unsigned), st));
-    HIP_TRY(hipMemsetAsync(area_gt_u32, 0, B * ng1 * sizeof(unsigned), st));
-    HIP_TRY(hipMemsetAsync(area_pred_u32, 0, B * np1 * sizeof(unsigned), st));
+    OvTable t;
+    if (int rc = ov_fill<false>("unet_instance_overlap", gt_i32, pred_i32, B, H, W, ng_max, np_max, table_slots, area_gt_u32,
+                                area_pred_u32, status_u64, scratch, st, t))
+        return rc;
+    const size_t ng1 = (size_t)ng_max + 1;
     HIP_TRY(hipMemsetAsync(match_i32, 0, B * ng1 * sizeof(int), st));
     HIP_TRY(hipMemsetAsync(inter_u32, 0, B * ng1 * sizeof(unsigned), st));
-    HIP_TRY(hipMemsetAsync(status_u64, 0, (size_t)B * 2 * sizeof(unsigned long long), st));
-    hipLaunchKernelGGL(overlap_fill_kernel<false>, dim3((unsigned)std::min<size_t>((npx + 255) / 256, 2048), B), dim3(256), 0, st,
-                       (const int *)gt_i32, (const int *)pred_i32, npx, ng_max, np_max, keys, cnt, table_slots, (unsigned *)area_gt_u32,
-                       (unsigned *)area_pred_u32, (unsigned long long *)status_u64);
-    hipLaunchKernelGGL(overlap_match_kernel, dim3((unsigned)std::min<size_t>((table_slots + 255) / 256, 2048)), dim3(256), 0, st,
-                       (const unsigned long long *)keys, (const unsigned *)cnt, table_slots, ng_max, (const unsigned *)area_gt_u32,
+    hipLaunchKernelGGL(overlap_match_kernel, dim3(grid_for(table_slots, 256, 2048)), dim3(256), 0, st,
+                       (const unsigned long long *)t.keys, (const unsigned *)t.cnt, table_slots, ng_max, (const unsigned *)area_gt_u32,
                        (int *)match_i32, (unsigned *)inter_u32);
     HIP_TRY(hipGetLastError());
     return 0;
@@ -294,31 +306,21 @@ int unet_instance_overlap(const void *gt_i32, const void *pred_i32, int B, int H
 size_t unet_partition_pairs_scratch_bytes(int B, size_t table_slots)
 {
     if (B <= 0 || table_slots == 0) return 0;
-    return ov_key_bytes(table_slots) + align_up(table_slots * sizeof(unsigned), 256);
+    return ov_scratch_bytes(table_slots);
 }
 
 int unet_partition_pairs(const void *gt_i32, const void *pred_i32, int B, int H, int W, int ng_max, int np_max, size_t table_slots,
                          void *pair_keys_u64, void *pair_counts_u32, void *n_pairs_u64, void *status_u64, void *scratch, void *stream)
 {
-    ARG_CHECK(gt_i32 && pred_i32 && pair_keys_u64 && pair_counts_u32 && n_pairs_u64 && status_u64 && scratch && B > 0 && H > 0 && W > 0,
-              "unet_partition_pairs: bad argument");
-    ARG_CHECK((size_t)H * W < (1u << 31) && B <= 65535, "unet_partition_pairs: image too large");
-    ARG_CHECK(ng_max >= 0 && np_max >= 0 && ng_max <= OV_ID_MAX && np_max <= OV_ID_MAX,
-              "unet_partition_pairs: ng_max and np_max must be in [0, %d]", OV_ID_MAX);
-    ARG_CHECK(table_slots > 0 && (table_slots & (table_slots - 1)) == 0, "unet_partition_pairs: table_slots must be a power of two");
+    ARG_CHECK(pair_keys_u64 && pair_counts_u32 && n_pairs_u64, "unet_partition_pairs: bad argument");
     hipStream_t st = (hipStream_t)stream;
-    const size_t npx = (size_t)H * W;
-    unsigned long long *keys = (unsigned long long *)scratch;
-    unsigned *cnt = (unsigned *)((char *)scratch + ov_key_bytes(table_slots));
-    HIP_TRY(hipMemsetAsync(keys, 0xFF, table_slots * sizeof(unsigned long long), st));          // OV_EMPTY
-    HIP_TRY(hipMemsetAsync(cnt, 0, table_slots * sizeof(unsigned), st));
+    OvTable t;
+    if (int rc = ov_fill<true>("unet_partition_pairs", gt_i32, pred_i32, B, H, W, ng_max, np_max, table_slots, nullptr, nullptr,
+                               status_u64, scratch, st, t))
+        return rc;
     HIP_TRY(hipMemsetAsync(n_pairs_u64, 0, sizeof(unsigned long long), st));
-    HIP_TRY(hipMemsetAsync(status_u64, 0, (size_t)B * 2 * sizeof(unsigned long long), st));
-    hipLaunchKernelGGL(overlap_fill_kernel<true>, dim3((unsigned)std::min<size_t>((npx + 255) / 256, 2048), B), dim3(256), 0, st,
-                       (const int *)gt_i32, (const int *)pred_i32, npx, ng_max, np_max, keys, cnt, table_slots, (unsigned *)nullptr,
-                       (unsigned *)nullptr, (unsigned long long *)status_u64);
-    hipLaunchKernelGGL(pairs_compact_kernel, dim3((unsigned)std::min<size_t>((table_slots + 255) / 256, 2048)), dim3(256), 0, st,
-                       (const unsigned long long *)keys, (const unsigned *)cnt, table_slots, (unsigned long long *)pair_keys_u64,
+    hipLaunchKernelGGL(pairs_compact_kernel, dim3(grid_for(table_slots, 256, 2048)), dim3(256), 0, st,
+                       (const unsigned long long *)t.keys, (const unsigned *)t.cnt, table_slots, (unsigned long long *)pair_keys_u64,
                        (unsigned *)pair_counts_u32, (unsigned long long *)n_pairs_u64);
     HIP_TRY(hipGetLastError());
     return 0;

@@ -190,8 +190,7 @@ __global__ __launch_bounds__(256) void headk_bwd_reduce_kernel(const float *__re
     if (e >= n) return;
     float s = 0.f;
     for (int b = lane; b < nb; b += 64) s += partial[(size_t)b * n + e];
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d, 64);
+    s = wave_sum(s);
     if (lane == 0) { if (e < K * C) { if (dw) dw[e] = s; } else if (db) db[e - K * C] = s; }
 }
 

@@ -140,7 +140,7 @@ __global__ __launch_bounds__(256) void carve_kernel(const void *__restrict__ ids
         if (edges) edges[o] = (float)e;
         if (bin) bin[o] = g > 0 ? 255 : 0;
     }
-    for (int d = 32; d >= 1; d >>= 1) bad += __shfl_xor(bad, d, 64);
+    bad = wave_sum(bad);
     if ((threadIdx.x & 63) == 0 && bad)
         __hip_atomic_fetch_add(&status[b], (unsigned long long)bad, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }

@@ -17,7 +17,7 @@
 // Coherence (MI355X: per-XCD L2s are not coherent, a CU's L1 is never refreshed by other CUs' stores): in ccl_merge
 // every read and every update of a parent word is an agent-scope atomic read-modify-write; foreground tests there
 // read the input labels, never the parent words.  Every other hand-off is across a kernel boundary.
-#include "common.hpp"
+#include "elem.hpp"
 #include <cmath>
 #include "../../include/unet_hip.h"
 
@@ -84,7 +84,7 @@ __global__ __launch_bounds__(256) void ccl_local_kernel(const void *__restrict__
         if (fg[k]) { const int l = lds_find(lp, i); r = (y0 + (l >> 5)) * W + x0 + (l & 31); }
         parent[img + (size_t)y * W + x] = r;
     }
-    for (int d = 32; d >= 1; d >>= 1) n1 += __shfl_xor(n1, d, 64);
+    n1 = wave_sum(n1);
     if ((threadIdx.x & 63) == 0 && n1) atomicAdd(&counts[b], n1);
 }
 
@@ -145,7 +145,7 @@ __global__ __launch_bounds__(256) void ccl_flatten_kernel(const int *__restrict_
         }
         label[(size_t)b * npx + e] = p;
     }
-    for (int d = 32; d >= 1; d >>= 1) roots += __shfl_xor(roots, d, 64);
+    roots = wave_sum(roots);
     if ((threadIdx.x & 63) == 0 && roots) atomicAdd(&n_objects[b], roots);
 }
 
@@ -243,7 +243,8 @@ int ccl_labels(const void *mask, int dtype, int B, int H, int W, int *parent, in
     const int nv = (tx - 1) * H, total = nv + (ty - 1) * W;
     if (total > 0)
         hipLaunchKernelGGL(ccl_merge_kernel, dim3(cdiv(total, 256), B), dim3(256), 0, st, mask, dtype, H, W, parent, nv, total);
-    hipLaunchKernelGGL(ccl_flatten_kernel, dim3((unsigned)std::min<size_t>((npx + 255) / 256, 1024), B), dim3(256), 0, st, (const int *)parent, label, npx, n_objects);
+    hipLaunchKernelGGL(ccl_flatten_kernel, dim3(grid_for(npx, 256, 1024), B), dim3(256), 0, st, (const int *)parent, label, npx,
+                       n_objects);
     return 0;
 }
 
@@ -256,12 +257,10 @@ static int wmap_radius(float sig2)
 
 using namespace unet;
 
-static size_t wm_plane(int B, int H, int W) { return align_up((size_t)B * H * W * sizeof(int), 256); }
-
 size_t unet_weighted_map_scratch_bytes(int B, int H, int W)
 {
     if (B <= 0 || H <= 0 || W <= 0) return 0;
-    return 3 * wm_plane(B, H, W);
+    return 3 * plane_bytes(B, H, W, sizeof(int));
 }
 
 int unet_weighted_map(const void *labels, int labels_dtype, int B, int H, int W, float w0, float sig2, void *weights_f32,
@@ -276,8 +275,9 @@ int unet_weighted_map(const void *labels, int labels_dtype, int B, int H, int W,
     ARG_CHECK(R <= 1024, "unet_weighted_map: sig2 %g gives a reach of %d px (at most 1024)", (double)sig2, R);
     hipStream_t st = (hipStream_t)stream;
     char *s = (char *)scratch;
-    int *parent = (int *)s, *label = (int *)(s + wm_plane(B, H, W));
-    unsigned *col_dist = (unsigned *)(s + 2 * wm_plane(B, H, W));
+    const size_t plane = plane_bytes(B, H, W, sizeof(int));
+    int *parent = (int *)s, *label = (int *)(s + plane);
+    unsigned *col_dist = (unsigned *)(s + 2 * plane);
     int *col_label = parent;                                  // the parent words are dead after ccl_flatten
     if (int rc = ccl_labels(labels, labels_dtype, B, H, W, parent, label, (unsigned long long *)counts_u64, (int *)n_objects_i32, st)) return rc;
     hipLaunchKernelGGL(wmap_cols_kernel, dim3(cdiv(W, 64), cdiv(H, 4), B), dim3(256), 0, st, (const int *)label, H, W, R,

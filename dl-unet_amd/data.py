@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 import _hip
-from functions import input_size_compute
+from functions import _device_only, _int_code, _planes, input_size_compute
 
 
 def _as_batch(image):
@@ -187,7 +187,7 @@ def reflect_rotate_crop(images, angles_deg, input_size=None, levels=255):
         xb = x[lo:lo + 64]
         b = xb.shape[0]
         out = torch.empty(b, S, S, dtype=torch.float32, device=x.device)
-        sc = torch.empty(_hip.lib().unet_rotate_scratch_bytes(b, S), dtype=torch.uint8, device=x.device)
+        sc = _hip.scratch("unet_rotate", x.device, b, S)
         arr = (_C.c_float * b)(*[float(a) for a in ang[lo:lo + b]])
         _hip.run("unet_reflect_rotate_crop", x.device, _hip.ptr(xb), b, n, S, S, arr, int(levels), _hip.ptr(out), _hip.ptr(sc))
         outs.append(out)
@@ -265,34 +265,6 @@ def augment(image, target, crop_xy, crop, rot_deg, alpha, sigma, random_state=No
 
 # ---- from instance images to targets and weighted crops (prepare.hip) -----------------------------------------------------
 
-def _device_only(t, name, entry):
-    if not torch.is_tensor(t) or not t.is_cuda:
-        raise NotImplementedError("%s runs on the HIP device only (%s): move the tensor to the device first, e.g. %s(x.cuda()); "
-                                  "there is no CPU implementation" % (name, entry, name))
-
-
-def _planes(t, name):
-    """[H,W] or [B,H,W] -> contiguous [B,H,W]"""
-    if t.dim() not in (2, 3):
-        raise ValueError("%s takes [H,W] or [B,H,W], got %s" % (name, tuple(t.shape)))
-    if t.numel() == 0:
-        raise ValueError("%s: empty input %s" % (name, tuple(t.shape)))
-    return (t[None] if t.dim() == 2 else t).contiguous()
-
-
-def _int_code(x, uint8_ok):
-    """The tensor in one of the widths the library reads, and its dtype code: float -> float32 (1), int64 and the unsigned
-    types int32 cannot hold -> int64 (0), uint8 stays where the entry point takes it (3), every other integer type (uint16
-    from a numpy-born image included) and bool -> int32 (2)."""
-    if x.is_floating_point():
-        return x.float(), 1
-    if x.dtype == torch.uint8 and uint8_ok:
-        return x, 3
-    if x.dtype in (torch.int64, torch.uint32, torch.uint64):
-        return x.to(torch.int64), 0
-    return x.to(torch.int32), 2
-
-
 def _reach(kernel, iterations):
     kernel, iterations = int(kernel), int(iterations)
     if kernel < 1 or kernel % 2 == 0 or iterations < 0:
@@ -305,9 +277,9 @@ def _reach(kernel, iterations):
 
 def _carve(img, name, kernel, iterations, want):
     """unet_carve_borders on img; want = which of (gt, edges, bin) to form.  One read-back: the status words."""
-    _device_only(img, name, "unet_carve_borders")
+    _device_only(name, "unet_carve_borders", img)
     reach = _reach(kernel, iterations)
-    x, code = _int_code(_planes(img, name), False)
+    x, code = _int_code(_planes(name, img))
     B, H, W = x.shape
     dev = x.device
     outs = [torch.empty(B, H, W, dtype=dt, device=dev) if w else None
@@ -363,8 +335,8 @@ def crop_distribution(target, crop, skip=10):
     row the distribution of one image.  The window counts are exact integers from the device (unet_crop_counts), read back
     once; the weights are formed from them on the host in float64 (crop_probabilities).  An image no larger than the crop has
     no window: ValueError.  Host tensors raise NotImplementedError (no CPU path)."""
-    _device_only(target, "crop_distribution", "unet_crop_counts")
-    x, code = _int_code(_planes(target, "crop_distribution"), True)
+    _device_only("crop_distribution", "unet_crop_counts", target)
+    x, code = _int_code(_planes("crop_distribution", target), uint8_ok=True)
     B, H, W = x.shape
     crop, skip = int(crop), int(skip)
     if crop < 1 or skip < 1 or H <= crop or W <= crop:
@@ -372,7 +344,7 @@ def crop_distribution(target, crop, skip=10):
     pairs = [(ii, jj) for ii in range(0, H - crop, skip) for jj in range(0, W - crop, skip)]
     ny, nx = len(range(0, H - crop, skip)), len(range(0, W - crop, skip))
     counts = torch.empty(B, ny, nx, dtype=torch.int32, device=x.device)      # the library's u32 words: at most crop^2 < 2^31
-    scratch = torch.empty(_hip.lib().unet_crop_counts_scratch_bytes(B, H, W, crop, skip), dtype=torch.uint8, device=x.device)
+    scratch = _hip.scratch("unet_crop_counts", x.device, B, H, W, crop, skip)
     _hip.run("unet_crop_counts", x.device, _hip.ptr(x), code, B, H, W, crop, skip, _hip.ptr(counts), _hip.ptr(scratch))
     return pairs, crop_probabilities(counts.cpu().numpy(), crop)
 

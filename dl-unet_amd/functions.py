@@ -18,6 +18,85 @@ import numpy as np
 import torch
 
 
+# ---- what the device-only ops share: the checks of their inputs and the table protocol ------------------------------------
+
+def _device_only(name, entry, *tensors):
+    if not all(torch.is_tensor(t) and t.is_cuda for t in tensors):
+        raise NotImplementedError("%s runs on the HIP device only (%s): move the input to the device first, e.g. with .cuda(); "
+                                  "there is no CPU implementation" % (name, entry))
+
+
+def _planes(name, t):
+    """[H,W] or [B,H,W] -> contiguous [B,H,W]"""
+    if t.dim() not in (2, 3):
+        raise ValueError("%s takes [H,W] or [B,H,W], got %s" % (name, tuple(t.shape)))
+    if t.numel() == 0:
+        raise ValueError("%s: empty input %s" % (name, tuple(t.shape)))
+    return (t[None] if t.dim() == 2 else t).contiguous()
+
+
+def _int_code(x, uint8_ok=False, int32_ok=True):
+    """The tensor in one of the widths the library reads, and its dtype code: float -> float32 (1), int64 and the unsigned
+    types int32 cannot hold -> int64 (0), uint8 stays where the entry point takes it (3), every other integer type (uint16
+    from a numpy-born image included) and bool -> int32 (2), or int64 (0) where the entry point reads only that and float32."""
+    if x.is_floating_point():
+        return x.float(), 1
+    if x.dtype == torch.uint8 and uint8_ok:
+        return x, 3
+    if not int32_ok or x.dtype in (torch.int64, torch.uint32, torch.uint64):
+        return x.to(torch.int64), 0
+    return x.to(torch.int32), 2
+
+
+def _id_maps(name, entry, *maps):
+    """The checks of the ops that take one or two id maps: equal shape, rank, dtype, size (ValueError, on any device), then the
+    device (NotImplementedError); returns them as contiguous [B,H,W]."""
+    if any(t.shape != maps[0].shape for t in maps) or maps[0].dim() not in (2, 3):
+        raise ValueError("%s takes id maps of equal shape [H,W] or [B,H,W], got %s" % (name, ", ".join(str(tuple(t.shape)) for t in maps)))
+    for t in maps:
+        if t.dtype not in (torch.int32, torch.int64):
+            raise ValueError("%s takes int32 or int64 id maps, got %s" % (name, t.dtype))
+    planes = [_planes(name, t) for t in maps]
+    _device_only(name, entry, *maps)
+    return planes
+
+
+def _id_range(name, *maps):
+    """(max id of each map), read back in one copy; negative ids and ids >= 2^24 raise ValueError."""
+    lo = maps[0].min()
+    for t in maps[1:]:
+        lo = torch.minimum(lo, t.min())
+    vals = [int(v) for v in torch.stack([lo.long()] + [t.max().long() for t in maps]).tolist()]
+    if vals[0] < 0:
+        raise ValueError("%s: negative ids (the smallest is %d)" % (name, vals[0]))
+    if max(vals[1:]) >= 1 << 24:
+        raise ValueError("%s: ids must be below 2^24, got up to %d" % (name, max(vals[1:])))
+    return vals[1:]
+
+
+def _pair_counts(entry, gt, pred, ng_max, np_max, slots, scratch_dims, outputs, bad):
+    """The table protocol of unet_instance_overlap and unet_partition_pairs on int32 maps [B,H,W]: allocate the scratch
+    (scratch_dims(slots)) and the entry's outputs (outputs(slots)), call it, read the status words back once; status[:, 0], the
+    pixels whose ids the entry refuses, raises ValueError(bad % (count, ng_max, np_max)); status[:, 1], the pixels a full table
+    dropped, doubles the table and repeats, which ends: a table with more slots than pixels cannot fill up.  Returns the outputs."""
+    import _hip
+    B, H, W = gt.shape
+    dev = gt.device
+    status = torch.empty(B, 2, dtype=torch.int64, device=dev)
+    slots = 1 << (4 * (ng_max + np_max) + 1024 - 1).bit_length() if slots is None else int(slots)
+    while True:
+        outs = outputs(slots)
+        scratch = _hip.scratch(entry, dev, *scratch_dims(slots))
+        _hip.run(entry, dev, _hip.ptr(gt), _hip.ptr(pred), B, H, W, ng_max, np_max, slots, *[_hip.ptr(o) for o in outs],
+                 _hip.ptr(status), _hip.ptr(scratch))
+        refused, dropped = (int(v) for v in status.cpu().sum(dim=0))
+        if refused:
+            raise ValueError(bad % (refused, ng_max, np_max))
+        if not dropped:
+            return outs
+        slots *= 2
+
+
 def weighted_map(gt_batch, *, w0=20, sig2=25, return_objects=False):
     """Border weight map of Ronneberger et al. 2015, eq. 2 (functions.py:7-78) for {0,1} labels [B,H,W] on a HIP device:
     1 on cells; on background w_c + w0 * exp(-(d1 + d2)^2 / (2 sig2)), d1 / d2 the exact distances to the nearest and
@@ -25,24 +104,18 @@ def weighted_map(gt_batch, *, w0=20, sig2=25, return_objects=False):
     label's dtype as in the reference (torch.empty_like(gt)): truncated for integer labels (DESIGN Q9), fp32 for float
     labels.  Returns float32 [B,H,W] (and the int32 [B] component counts with return_objects=True).  A one-class image
     raises IndexError as the reference does at counts[1]; host tensors raise NotImplementedError (no CPU path)."""
-    if not gt_batch.is_cuda:
-        raise NotImplementedError("weighted_map runs on the HIP device only (unet_weighted_map): move the labels to the "
-                                  "device first, e.g. weighted_map(gt_batch.cuda()); there is no CPU implementation")
+    _device_only("weighted_map", "unet_weighted_map", gt_batch)
     import _hip
     if gt_batch.dim() != 3:
         raise ValueError("weighted_map takes labels [B,H,W], got %s" % (tuple(gt_batch.shape),))
-    gt = gt_batch.contiguous()
-    if gt.is_floating_point():
-        gt, code = gt.float(), 1
-    else:
-        gt, code = gt.long(), 0
+    gt, code = _int_code(gt_batch.contiguous(), int32_ok=False)
     B, H, W = gt.shape
     w = torch.empty(B, H, W, dtype=torch.float32, device=gt.device)
     counts = torch.empty(B, dtype=torch.int64, device=gt.device)
     n_objects = torch.empty(B, dtype=torch.int32, device=gt.device)
     if B * H * W == 0:
         raise IndexError("index 1 is out of bounds for dimension 0 with size 0")
-    scratch = torch.empty(_hip.lib().unet_weighted_map_scratch_bytes(B, H, W), dtype=torch.uint8, device=gt.device)
+    scratch = _hip.scratch("unet_weighted_map", gt.device, B, H, W)
     _hip.run("unet_weighted_map", gt.device, _hip.ptr(gt), code, B, H, W, float(w0), float(sig2), _hip.ptr(w), _hip.ptr(counts),
              _hip.ptr(n_objects), _hip.ptr(scratch))
     if bool(((counts == 0) | (counts == H * W)).any()):      # the reference indexes counts[1]: a one-class image raises
@@ -56,23 +129,13 @@ def label_cells(mask):
     and 1..n on the 4-connected components, numbered in raster order of their first pixel like scipy.ndimage.label and
     cv.connectedComponents(connectivity=4) (functions.py:47); n_objects int32 [B] ([1] for a single image) = n.
     Host tensors raise NotImplementedError (no CPU path)."""
-    if not mask.is_cuda:
-        raise NotImplementedError("label_cells runs on the HIP device only (unet_label_components): move the mask to the "
-                                  "device first, e.g. label_cells(mask.cuda()); there is no CPU implementation")
+    _device_only("label_cells", "unet_label_components", mask)
     import _hip
-    if mask.dim() not in (2, 3):
-        raise ValueError("label_cells takes a mask [H,W] or [B,H,W], got %s" % (tuple(mask.shape),))
-    m = (mask[None] if mask.dim() == 2 else mask).contiguous()
-    if m.is_floating_point():
-        m, code = m.float(), 1
-    else:
-        m, code = m.long(), 0
+    m, code = _int_code(_planes("label_cells", mask), int32_ok=False)
     B, H, W = m.shape
-    if B * H * W == 0:
-        raise ValueError("label_cells: empty mask %s" % (tuple(mask.shape),))
     labels = torch.empty(B, H, W, dtype=torch.int32, device=m.device)
     n_objects = torch.empty(B, dtype=torch.int32, device=m.device)
-    scratch = torch.empty(_hip.lib().unet_label_components_scratch_bytes(B, H, W), dtype=torch.uint8, device=m.device)
+    scratch = _hip.scratch("unet_label_components", m.device, B, H, W)
     _hip.run("unet_label_components", m.device, _hip.ptr(m), code, B, H, W, _hip.ptr(labels), _hip.ptr(n_objects), _hip.ptr(scratch))
     return (labels[0] if mask.dim() == 2 else labels), n_objects
 
@@ -111,73 +174,16 @@ def seg_measure(pred_labels, gt_labels, *, _table_slots=None):
     order.  The counting is exact and on the device (unet_instance_overlap); the two id maxima are read back once to size the
     tables, and the pair table is doubled and the call repeated while it reports an overflow.  Negative ids raise ValueError;
     host tensors raise NotImplementedError (no CPU path)."""
-    if not (pred_labels.is_cuda and gt_labels.is_cuda):
-        raise NotImplementedError("seg_measure runs on the HIP device only (unet_instance_overlap): move the label maps to the "
-                                  "device first, e.g. seg_measure(pred.cuda(), gt.cuda()); there is no CPU implementation")
-    import _hip
-    if pred_labels.shape != gt_labels.shape or pred_labels.dim() not in (2, 3):
-        raise ValueError("seg_measure takes two id maps of equal shape [H,W] or [B,H,W], got %s and %s"
-                         % (tuple(pred_labels.shape), tuple(gt_labels.shape)))
-    for t in (pred_labels, gt_labels):
-        if t.dtype not in (torch.int32, torch.int64):
-            raise ValueError("seg_measure takes int32 or int64 id maps, got %s" % t.dtype)
-    if pred_labels.numel() == 0:
-        raise ValueError("seg_measure: empty id maps %s" % (tuple(pred_labels.shape),))
-    pred, gt = ((t[None] if t.dim() == 2 else t).contiguous() for t in (pred_labels, gt_labels))
-    B, H, W = gt.shape
-    dev = gt.device
-    lo, ng_max, np_max = (int(v) for v in torch.stack([torch.minimum(gt.min(), pred.min()).long(), gt.max().long(), pred.max().long()]).tolist())
-    if lo < 0:
-        raise ValueError("seg_measure: negative ids (the smallest is %d)" % lo)
-    if max(ng_max, np_max) >= 1 << 24:
-        raise ValueError("seg_measure: ids must be below 2^24, got up to %d" % max(ng_max, np_max))
-    gt, pred = gt.int(), pred.int()
+    pred, gt = _id_maps("seg_measure", "unet_instance_overlap", pred_labels, gt_labels)
+    ng_max, np_max = _id_range("seg_measure", gt, pred)
+    B, dev = gt.shape[0], gt.device
     area_gt = torch.empty(B, ng_max + 1, dtype=torch.int32, device=dev)         # the library's u32 / u64 words: counts of at
     area_pred = torch.empty(B, np_max + 1, dtype=torch.int32, device=dev)       # most H * W < 2^31, so the signed views agree
     match = torch.empty(B, ng_max + 1, dtype=torch.int32, device=dev)
     inter = torch.empty(B, ng_max + 1, dtype=torch.int32, device=dev)
-    status = torch.empty(B, 2, dtype=torch.int64, device=dev)
-    slots = 1 << (4 * (ng_max + np_max) + 1024 - 1).bit_length() if _table_slots is None else int(_table_slots)
-    while True:
-        scratch = torch.empty(_hip.lib().unet_instance_overlap_scratch_bytes(B, ng_max, np_max, slots), dtype=torch.uint8, device=dev)
-        _hip.run("unet_instance_overlap", dev, _hip.ptr(gt), _hip.ptr(pred), B, H, W, ng_max, np_max, slots, _hip.ptr(area_gt),
-                 _hip.ptr(area_pred), _hip.ptr(match), _hip.ptr(inter), _hip.ptr(status), _hip.ptr(scratch))
-        st = status.cpu()
-        if int(st[:, 0].sum()):
-            raise ValueError("seg_measure: %d pixels hold ids outside [0, %d] / [0, %d]" % (int(st[:, 0].sum()), ng_max, np_max))
-        if not int(st[:, 1].sum()):
-            break
-        slots *= 2                      # ends: a table with more slots than pixels cannot fill up
+    _pair_counts("unet_instance_overlap", gt.int(), pred.int(), ng_max, np_max, _table_slots, lambda slots: (B, ng_max, np_max, slots),
+                 lambda slots: (area_gt, area_pred, match, inter), "seg_measure: %d pixels hold ids outside [0, %d] / [0, %d]")
     return seg_from_counts(area_gt.cpu().numpy(), area_pred.cpu().numpy(), match.cpu().numpy(), inter.cpu().numpy())
-
-
-def _id_maps(name, entry, *maps):
-    """The checks seg_measure makes of its id maps, for the ops that take one or two: equal shape, rank, dtype, size (ValueError,
-    on any device), then the device (NotImplementedError); returns them as contiguous [B,H,W]."""
-    if any(t.shape != maps[0].shape for t in maps) or maps[0].dim() not in (2, 3):
-        raise ValueError("%s takes id maps of equal shape [H,W] or [B,H,W], got %s" % (name, ", ".join(str(tuple(t.shape)) for t in maps)))
-    for t in maps:
-        if t.dtype not in (torch.int32, torch.int64):
-            raise ValueError("%s takes int32 or int64 id maps, got %s" % (name, t.dtype))
-    if maps[0].numel() == 0:
-        raise ValueError("%s: empty id maps %s" % (name, tuple(maps[0].shape)))
-    if not all(t.is_cuda for t in maps):
-        raise NotImplementedError("%s runs on the HIP device only (%s): move the label maps to the device first, e.g. with "
-                                  ".cuda(); there is no CPU implementation" % (name, entry))
-    return [(t[None] if t.dim() == 2 else t).contiguous() for t in maps]
-
-
-def _id_range(name, *maps):
-    """(max id of each map), read back in one copy; negative ids and ids >= 2^24 raise ValueError."""
-    lo = maps[0].min()
-    for t in maps[1:]:
-        lo = torch.minimum(lo, t.min())
-    vals = [int(v) for v in torch.stack([lo.long()] + [t.max().long() for t in maps]).tolist()]
-    if vals[0] < 0:
-        raise ValueError("%s: negative ids (the smallest is %d)" % (name, vals[0]))
-    if max(vals[1:]) >= 1 << 24:
-        raise ValueError("%s: ids must be below 2^24, got up to %d" % (name, max(vals[1:])))
-    return vals[1:]
 
 
 def grow_cells(labels, max_distance=None):
@@ -202,7 +208,7 @@ def grow_cells(labels, max_distance=None):
     lab = lab.int()
     B, H, W = lab.shape
     out = torch.empty_like(lab)
-    scratch = torch.empty(_hip.lib().unet_grow_labels_scratch_bytes(B, H, W), dtype=torch.uint8, device=lab.device)
+    scratch = _hip.scratch("unet_grow_labels", lab.device, B, H, W)
     _hip.run("unet_grow_labels", lab.device, _hip.ptr(lab), B, H, W, max_dist2, _hip.ptr(out), _hip.ptr(scratch))
     return out[0] if labels.dim() == 2 else out
 
@@ -216,28 +222,15 @@ def pair_table(pred_labels, gt_labels, *, _table_slots=None):
     status words) and ids >= 2^24 raise ValueError;
     host tensors raise NotImplementedError (no CPU path)."""
     pred, gt = _id_maps("pair_table", "unet_partition_pairs", pred_labels, gt_labels)
-    import _hip
-    B, H, W = gt.shape
-    dev = gt.device
+    B, dev = gt.shape[0], gt.device
     ng_max, np_max = (max(0, int(v)) for v in torch.stack([gt.max().long(), pred.max().long()]).tolist())
     if max(ng_max, np_max) >= 1 << 24:
         raise ValueError("pair_table: ids must be below 2^24, got up to %d" % max(ng_max, np_max))
-    gt, pred = gt.int(), pred.int()
     n_pairs = torch.empty(1, dtype=torch.int64, device=dev)
-    status = torch.empty(B, 2, dtype=torch.int64, device=dev)
-    slots = 1 << (4 * (ng_max + np_max) + 1024 - 1).bit_length() if _table_slots is None else int(_table_slots)
-    while True:
-        keys = torch.empty(slots, dtype=torch.int64, device=dev)
-        counts = torch.empty(slots, dtype=torch.int32, device=dev)
-        scratch = torch.empty(_hip.lib().unet_partition_pairs_scratch_bytes(B, slots), dtype=torch.uint8, device=dev)
-        _hip.run("unet_partition_pairs", dev, _hip.ptr(gt), _hip.ptr(pred), B, H, W, ng_max, np_max, slots, _hip.ptr(keys),
-                 _hip.ptr(counts), _hip.ptr(n_pairs), _hip.ptr(status), _hip.ptr(scratch))
-        st = status.cpu()
-        if int(st[:, 0].sum()):
-            raise ValueError("pair_table: %d pixels hold negative ids (outside [0, %d] / [0, %d])" % (int(st[:, 0].sum()), ng_max, np_max))
-        if not int(st[:, 1].sum()):
-            break
-        slots *= 2                      # ends: a table with more slots than pixels cannot fill up
+    keys, counts, _ = _pair_counts(
+        "unet_partition_pairs", gt.int(), pred.int(), ng_max, np_max, _table_slots, lambda slots: (B, slots),
+        lambda slots: (torch.empty(slots, dtype=torch.int64, device=dev), torch.empty(slots, dtype=torch.int32, device=dev), n_pairs),
+        "pair_table: %d pixels hold negative ids (outside [0, %d] / [0, %d])")
     n = int(n_pairs.item())
     k, c = keys[:n].cpu().numpy().view(np.uint64), counts[:n].cpu().numpy().astype(np.int64)
     order = np.argsort(k)                                   # distinct unsigned keys b << 48 | g << 24 | p: the order of (b, g, p)

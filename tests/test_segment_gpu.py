@@ -193,6 +193,48 @@ def test_stitch_mask_probability_and_bounds(dev, B, H, W, S):
     assert np.array_equal(m[G:G + n].reshape(B, H, W), want_m) and (m[:G] == -7).all() and (m[G + n:] == -7).all()
 
 
+@pytest.mark.parametrize("K", [2, 3])
+def test_stitch_and_stitch_k_against_numpy_on_a_clipped_grid(dev, K):
+    """unet_tile_stitch (K = 2) and unet_tile_stitch_k (K = 2 and 3) on a 2 x 9 x 14 batch, whose 3 x 4 grid of 4-pixel tiles
+    overhangs the image on both axes, against numpy on guarded buffers.  Logits with exact ties, some of them at the maximum:
+    the masks are bit-equal to l1 > l0 and to the first maximum (ties -> the lowest class).  Probabilities against fp64:
+    1 / (1 + e^(l0 - l1)) within 4e-7 (d = l0 - l1 is rounded once, which moves p by at most p (1 - p) |d| 2^-24 <=
+    0.23 * 2^-24; expf's 2 ulp move it by at most 4 p (1 - p) 2^-24 <= 2^-24; the sum and the division add 2^-24 each: below
+    3.3 * 2^-24 = 2e-7), the softmax within multiclass_ref.softmax_bound."""
+    import _hip
+    import guarded
+    import multiclass_ref
+    import tester
+    B, H, W, S = 2, 9, 14, 188
+    So = S - 184
+    ny, nx, oy0, ox0 = tester.tile_grid(H, W, S)
+    assert (ny, nx) == (3, 4) and oy0 < 0 and ox0 < 0
+    T = B * ny * nx
+    rs = np.random.RandomState(31 + K)
+    lg = (rs.randn(T, K, So, So) * 4).astype(np.float32)
+    tie = rs.rand(T, So, So) < 0.2
+    lg[:, 1][tie] = lg[:, 0][tie]
+    top = rs.rand(T, So, So) < 0.1
+    lg[:, 0][top] = lg[:, 1][top] = np.abs(lg).max(axis=1)[top] + 1
+    ar = guarded.Arena(dev)
+    lgd = ar.inp(torch.from_numpy(lg))
+    want_m, want_p = multiclass_ref.stitch_k(lg, B, H, W, S)
+    assert (want_m == 0).any() and (want_m == K - 1).any()
+    mask, prob = ar.out((B, H, W), torch.int64), ar.out((B, K, H, W))
+    _hip.run("unet_tile_stitch_k", dev, ar.ptr(lgd), So, K, oy0, ox0, ny, nx, 0, T, B, H, W, ar.ptr(mask), ar.ptr(prob))
+    ar.verify(mask, prob)
+    assert np.array_equal(mask.cpu().numpy(), want_m)
+    assert np.abs(prob.cpu().numpy() - want_p).max() <= multiclass_ref.softmax_bound(lg, K)
+    if K == 2:
+        want_m2, want_p2 = ref.stitch(lg, B, H, W, S)
+        assert np.array_equal(want_m2, want_m)
+        mask2, prob2 = ar.out((B, H, W), torch.int64), ar.out((B, H, W))
+        _hip.run("unet_tile_stitch", dev, ar.ptr(lgd), So, oy0, ox0, ny, nx, 0, T, B, H, W, ar.ptr(mask2), ar.ptr(prob2))
+        ar.verify(mask2, prob2)
+        assert np.array_equal(mask2.cpu().numpy(), want_m2)
+        assert np.abs(prob2.cpu().numpy() - want_p2).max() <= 4e-7
+
+
 # ---- end to end ----------------------------------------------------------------------------------------------------------
 
 def pipeline(net, img, S, max_batch, norm=True):

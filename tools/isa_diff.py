@@ -10,7 +10,8 @@ numbers in local labels are normalised, and per kernel the instruction stream, t
 resource lines (VGPRs, SGPRs, LDS, scratch, kernarg size) are compared.  Kernels are paired by mangled name; kernels left
 over on both sides (a template parameter was removed: the symbol changes) are paired when their normalised code is equal.
 Exit status 0 iff every kernel of the parent has an identical partner or matches --allow REGEX (kernels that are meant to
-change: their resource lines are printed); -v prints a unified diff of those that differ.
+change, their resource lines are printed, or to go: an instantiation nothing launches); -v prints a unified diff of those
+that differ.
 """
 import argparse
 import difflib
@@ -113,8 +114,9 @@ def main():
                 if a.v:
                     print("\n".join(d))
             for n in left_a[len(left_b):]:
-                bad += 1
-                print("%s: only in parent: %s" % (f, demangle(n)))
+                allowed = bool(a.allow and re.search(a.allow, demangle(n)))
+                bad += 0 if allowed else 1
+                print("%s: only in parent%s: %s" % (f, " (allowed)" if allowed else "", demangle(n)))
             for n in left_b[len(left_a):]:
                 print("%s: only in new: %s" % (f, demangle(n)))
             print("%s: %d of %d kernels identical" % (f, same, len(ka)))
