@@ -11,6 +11,7 @@ import torch.nn.functional as F
 
 import guarded as gd
 import kernel_paths as kp
+import step_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -359,32 +360,10 @@ def test_step_side_kernels(hip, golden_dir):
     l2, m2 = hip_optim.bce_argmax_step(lgr, labels, weight=wm)
     l2.backward()
     assert nerr(lgr.grad, torch.from_numpy(ka["bce_weighted_grad"])) < 1e-5 and np.array_equal(m2.cpu().numpy(), ka["argmax_S220"])
-    # L3 SGD momentum, two steps, against the pinned C oracle in fp64 (oracle_c.sgd_momentum: buf = first ? g : mu*buf + g;
-    # p -= lr*buf).  The C ABI takes lr and mu as fp32, so the oracle is given those same fp32 values: what remains is the
-    # kernel's fp32 arithmetic, fused or not.  Per step (elementwise; step 1 is exact: buf = g):
-    #   buf: mu*buf and + g round once each, <= 2^-24 (mu|buf| + |mu buf + g|) <= 2^-23 (mu|buf| + |g|), plus mu x the error carried in;
-    #   p:   lr*buf and p - lr*buf round once each, <= 2^-24 lr|buf| + 2^-24 |p|, plus lr x the buffer's error
-    # (tb, tp below; the lr*buf term is counted as 2^-22 lr|buf|, with room to spare).
+    # L3 SGD momentum, two steps, against the pinned C oracle in fp64, elementwise: the helper and the derivation of its bound
+    # live in tests/step_ref.py, shared with tests/test_step_ops_gpu.py
     def sgd_vs_oracle(ps, nsteps=2, lr=1e-4, mu=0.99):
-        lr, mu = float(np.float32(lr)), float(np.float32(mu))       # what the kernel computes with
-        p64 = [p.double().cpu().numpy().copy() for p in ps]
-        b64 = [np.zeros_like(q) for q in p64]
-        bufs = [torch.zeros_like(p) for p in ps]
-        numel = (C.c_size_t * len(ps))(*[p.numel() for p in ps])
-        tol_p = [np.zeros_like(q) for q in p64]; tol_b = [np.zeros_like(q) for q in p64]
-        for step in range(nsteps):
-            gs = [torch.randn_like(p) for p in ps]
-            for q, b_, g_, tp, tb in zip(p64, b64, gs, tol_p, tol_b):
-                prev = np.abs(b_).copy()
-                g64 = g_.double().cpu().numpy()
-                oracle_c.sgd_momentum(q, g64, b_, lr, mu, int(step == 0))
-                tb[:] = 0.0 if step == 0 else 2.0 ** -23 * (mu * prev + np.abs(g64)) + mu * tb
-                tp += 2.0 ** -24 * np.abs(q) + 2.0 ** -22 * lr * np.abs(b_) + lr * tb
-            hip.check(L.unet_sgd_momentum(hip.ptr_table(ps), hip.ptr_table(gs), hip.ptr_table(bufs), numel, len(ps), lr, mu, int(step == 0),
-                                          hip.stream()))
-        for p, q, bd, b_, tp, tb in zip(ps, p64, bufs, b64, tol_p, tol_b):
-            assert np.all(np.abs(p.double().cpu().numpy() - q) <= tp)
-            assert np.all(np.abs(bd.double().cpu().numpy() - b_) <= tb)
+        step_ref.sgd_vs_oracle(hip, ps, nsteps=nsteps, lr=lr, mu=mu)
     torch.manual_seed(0)
     sgd_vs_oracle([torch.randn(n, device="cuda") for n in (5000, 3, 70001)])
     # pointers that are not 16-byte aligned take the 4-byte kernel: same bound
