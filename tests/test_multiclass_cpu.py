@@ -154,3 +154,90 @@ def test_numpy_stitch_k_matches_torch():
         if K == 2:
             m2, p2 = segment_ref.stitch(lg, 1, 60, 70, S)
             assert np.array_equal(mask, m2) and np.abs(prob[:, 1] - p2).max() <= 1e-15
+
+
+# ---- the inputs of tests/test_multiclass_ops_gpu.py are well-posed ----------------------------------------------------------
+
+@pytest.mark.parametrize("K", [5, 9, 16])
+def test_numpy_softmax_ce_matches_torch_fp64_on_extreme_logits(K):
+    """multiclass_ref.softmax_ce on the 'extreme' family (logits up to +-1e4, invalid labels planted) against
+    F.cross_entropy(reduction='none') in fp64 with the weight applied by hand and the gradient from autograd."""
+    B, H, W = 3, 1, 683
+    l, lab, w = ref.ce_cases(B, K, H, W, "extreme")
+    lab, nbad = ref.plant_invalid(lab, K)
+    assert np.abs(l).max() == 1e4
+    loss, d, mask, bad = ref.softmax_ce(l, lab, w, grad_scale=0.25)
+    ok = (lab >= 0) & (lab < K)
+    lt = torch.tensor(l.astype(np.float64), requires_grad=True)
+    ce = F.cross_entropy(lt, torch.tensor(np.where(ok, lab, 0)), reduction="none")
+    tl = (ce * torch.tensor(w.astype(np.float64)) * torch.tensor(ok)).sum() / (B * H * W)
+    (tl * 0.25).backward()
+    assert bad == nbad == 5
+    assert abs(loss - tl.item()) <= 1e-13 * abs(tl.item())
+    assert np.abs(d - lt.grad.numpy()).max() <= 1e-15
+    assert np.array_equal(mask, torch.argmax(torch.tensor(l), dim=1).numpy())
+    assert (d.transpose(0, 2, 3, 1)[~ok] == 0).all()
+
+
+def test_ce_shape_and_class_lists():
+    assert [b * h * w for b, h, w in ref.CE_SHAPES] == [1, 2047, 2048, 2049, 2100, 255, 525312]
+    assert 300 * 1 * 7 == 2100 and 1 * 7 < 256                        # a thread's next pixel lies 256 / 7 = 36 images on
+    assert -(-525312 // 2048) == 257                                   # partials: one more than the finisher's 256 threads
+    small = [c for c in ref.CE_CASES if c[0] != ref.CE_LARGE_SHAPE]
+    assert [c for c in ref.CE_CASES if c[0] == ref.CE_LARGE_SHAPE] == [(ref.CE_LARGE_SHAPE, 3)]
+    assert len(set(small)) == len(small)
+    for K in ref.ALL_K:
+        assert sum(1 for s, k in small if k == K) >= 3, K
+    for s in ref.CE_SMALL_SHAPES:
+        assert sum(1 for t, k in small if t == s) >= 3, s
+    assert set(k for _, k in small) == set(ref.ALL_K) == {2, 3, 4, 5, 8, 9, 16}
+
+
+@pytest.mark.parametrize("family", ref.CE_FAMILIES)
+@pytest.mark.parametrize("shape,K", ref.CE_CASES)
+def test_ce_cases_are_well_posed(shape, K, family):
+    """Ties where the shape has room, saturated pixels where claimed, invalid labels as planted, a loss of ordinary size,
+    a positive finite bound; the reference's dlogits are exactly 0 at saturated pixels to within 1e-45 x w / n."""
+    B, H, W = shape
+    npix = B * H * W
+    x, lab, w = ref.ce_cases(B, K, H, W, family)
+    assert x.dtype == np.float32 and x.shape == (B, K, H, W) and lab.dtype == np.int64 and w.dtype == np.float32
+    assert np.isfinite(x).all() and lab.min() >= 0 and lab.max() < K and w.min() >= 0.1 and w.max() <= 4.0
+    f = x.transpose(1, 0, 2, 3).reshape(K, -1)
+    t_all, t_last, t_one = ref.tie_pixels(npix)
+    if npix >= 3:
+        assert len({t_all, t_last, t_one}) == 3
+        assert (f[:, t_all] == f[0, t_all]).all()
+        assert f[K - 1, t_last] == f[:, t_last].max() and f[1, t_one] == f[:, t_one].max()
+        if K > 2:                                                      # a lower class shares the maximum: the first one wins
+            assert f[:, t_last].argmax() < K - 1 or (f[:K - 1, t_last] < f[K - 1, t_last]).all()
+    else:
+        assert (t_all, t_last, t_one) == (None, None, None)
+    if family == "extreme":
+        assert npix < 255 or all((x == v).any() for v in ref.SPECIAL if v != 0) and (np.signbit(x) & (x == 0)).any()
+    bad, nbad = ref.plant_invalid(lab, K)
+    assert nbad == (5 if npix >= 16 else 0)
+    wrong = (bad < 0) | (bad >= K)
+    assert wrong.sum() == nbad and (nbad == 0 or sorted(bad[wrong].tolist()) == sorted([-1, K, 1000, -7, 2 ** 40]))
+    assert not (set(np.flatnonzero(wrong.reshape(-1)).tolist()) & {t_all, t_last, t_one})
+    sat = ref.saturated_pixels(x, bad)
+    if family == "extreme" and npix >= 2047:
+        assert sat.sum() >= 5
+    assert not (sat & wrong).any()
+    for gs, wt in ((1.0, None), (0.25, w)):
+        loss, d, _, n = ref.softmax_ce(x, bad, wt, gs)
+        assert n == nbad and np.isfinite(loss) and loss > 1e-2
+        bound = ref.softmax_ce_grad_bound(x, wt, K, gs)
+        assert bound.shape == (B, 1, H, W) and np.isfinite(bound).all() and (bound > 0).all()
+        assert (bound >= (0.1 if wt is not None else 1.0) / npix * gs * (K + 12) * ref.EPS32).all()
+        assert np.abs(d.transpose(0, 2, 3, 1)[sat]).max(initial=0.0) <= 2.0 ** -126
+
+
+def test_head_bounds_helper_shapes():
+    x, w, b, dl = torch.randn(2, 3, 5, 32), torch.randn(5, 32, 1, 1), torch.randn(5), torch.randn(2, 5, 3, 5)
+    r = ref.head_reference_and_bounds(x, w, b, dl, 1, True)
+    assert r["y"].shape == r["yb"].shape == (30, 5) and r["dz"].shape == r["dzb"].shape == (30, 32)
+    assert r["dw"].shape == r["dwb"].shape == (5, 32) and r["db"].shape == r["dbb"].shape == (5,)
+    assert all(v.dtype == torch.float64 for v in r.values()) and all((r[k] > 0).all() for k in ("yb", "dzb", "dwb", "dbb"))
+    y = torch.einsum("bhwc,kc->bhwk", x.double(), w.double().reshape(5, 32)) + b.double()
+    assert torch.allclose(r["y"], y.reshape(30, 5), rtol=1e-13, atol=1e-13)

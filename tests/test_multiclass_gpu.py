@@ -3,7 +3,6 @@ cross-entropy step (the paper's eq. 1), the K-way argmax and confusion counts, o
 loss='softmax_ce'.  References: fp64 numpy / torch (tests/multiclass_ref.py), oracle.torch_ref in fp64, and the binary path."""
 import copy
 import ctypes as C
-import math
 
 import numpy as np
 import pytest
@@ -66,14 +65,8 @@ HEAD_CASES = ([(shape, K, C_, dt) for shape in ((1, 37, 29), (8, 388, 388)) for 
 
 @pytest.mark.parametrize("shape,K,C_,dtype", HEAD_CASES)
 def test_head1xk_per_op(dev, math_mode, dtype, C_, K, shape):
-    """unet_head1xk_fwd / _bwd against fp64.  Bounds (per element, EPS = 2^-24):
-      forward  y = sum_c x_c w_c + b: 4-term dot products per lane, then a log2(C/4)-deep pairwise tree, then + b:
-               |y - y64| <= (log2(C) + 3) EPS (sum_c |x_c w_c| + |b|);
-      dz       = (sum_k dl_k w_k) [x > 0], an fma chain of K terms: <= (K + 1) EPS sum_k |dl_k w_k|, plus, for bf16 dz, the
-               final rounding to 8 significant bits, half an ulp: <= 2^-8 |dz|;
-      dw, db   per lane a serial fma chain over its pixels (head1x1: n / (blocks x pixels per pass); K > 2: 512-pixel chunks per
-               block x passes per chunk), then a shuffle tree over the wave (<= 3), the 4 waves (3), and the cross-block
-               reduce (nb / 64 + 6): <= (chain + nb/64 + 12) EPS sum_m |dl_k x_c|.
+    """unet_head1xk_fwd / _bwd against fp64, per element within the forward, dz and dw / db chain-length bounds stated in
+    multiclass_ref.head_reference_and_bounds (shared with tests/test_multiclass_ops_gpu.py).
     bf16 activations (mode 2) are exact bf16 inputs here, so the same bounds hold for the fp32 outputs.
     At K = 2 the entry points are the head1x1 kernels: bit-identical to unet_head1x1_*."""
     import _hip
@@ -109,27 +102,14 @@ def test_head1xk_per_op(dev, math_mode, dtype, C_, K, shape):
                  _hip.ptr(db1), _hip.ptr(sc))
         torch.cuda.synchronize()
         assert torch.equal(y, y1) and torch.equal(dz, dz1) and torch.equal(dw, dw1) and torch.equal(db, db1)
-    x64 = x.double().reshape(n, C_)
-    w64 = w.double().reshape(K, C_)
-    dl64 = dl.double().permute(0, 2, 3, 1).reshape(n, K)
-    y64 = x64 @ w64.T + b.double()
-    yb = (math.log2(C_) + 3) * EPS * ((x64.abs() @ w64.abs().T) + b.double().abs())
-    yk = y.permute(0, 2, 3, 1).reshape(n, K).double().cpu()
-    assert ((yk - y64).abs() <= yb).all()
-    dz64 = (dl64 @ w64) * (x64 > 0)
-    dzb = (K + 1) * EPS * (dl64.abs() @ w64.abs())
-    if dtype == "bf16":
-        dzb = dzb + 2.0 ** -8 * dz64.abs()
-    dzk = dz.float().reshape(n, C_).double().cpu()
-    assert ((dzk - dz64).abs() <= dzb).all()
     nb = sb // ((K * C_ + K) * 4)
-    ppp = 256 // (C_ // 4)                                   # pixels per pass of a block
-    chain = max(-(-n // (nb * ppp)), -(-(-(-n // 512)) // nb) * (512 // ppp)) + nb / 64 + 12
-    dw64 = dl64.T @ x64
-    dwb = chain * EPS * (dl64.abs().T @ x64.abs())
-    assert ((dw.reshape(K, C_).double().cpu() - dw64).abs() <= dwb).all()
-    db64 = dl64.sum(0)
-    assert ((db.double().cpu() - db64).abs() <= chain * EPS * dl64.abs().sum(0)).all()
+    r = ref.head_reference_and_bounds(x, w, b, dl, nb, dtype == "bf16")
+    yk = y.permute(0, 2, 3, 1).reshape(n, K).double().cpu()
+    assert ((yk - r["y"]).abs() <= r["yb"]).all()
+    dzk = dz.float().reshape(n, C_).double().cpu()
+    assert ((dzk - r["dz"]).abs() <= r["dzb"]).all()
+    assert ((dw.reshape(K, C_).double().cpu() - r["dw"]).abs() <= r["dwb"]).all()
+    assert ((db.double().cpu() - r["db"]).abs() <= r["dbb"]).all()
 
 
 def test_head1xk_rejects_bad_arguments(dev):

@@ -9,7 +9,7 @@ import torch
 from scipy import ndimage
 
 import weighted_map_ref as ref
-from weighted_map_ref import golden_cases
+from weighted_map_ref import check_against_restatement, golden_cases
 
 pytestmark = pytest.mark.gpu
 
@@ -21,24 +21,6 @@ def dev():
     assert torch.cuda.is_available()
     torch.cuda.set_device(0)
     return torch.device("cuda:0")
-
-
-def check_against_restatement(lab, w, n_objects):
-    """lab numpy [B,H,W]; w, n_objects: the device op's results.  Counts exact, cells exactly 1, background with no
-    component within reach exactly w_c, elsewhere |dw| <= 1e-5 max(1, |w_ref|)."""
-    w_ref, n_ref = ref.weighted_map_batch(lab)
-    assert np.array_equal(n_objects, n_ref)
-    for b in range(lab.shape[0]):
-        fg = lab[b] != 0
-        assert np.all(w[b][fg] == 1.0)
-        d1, _, _ = ref.distances(lab[b])
-        far = ~fg & (d1 > ref.REACH)
-        if far.any():
-            n1 = np.float32(fg.sum()); wc = n1 / np.float32(fg.size - fg.sum())
-            if not np.issubdtype(lab.dtype, np.floating):
-                wc = np.float32(np.trunc(wc))
-            assert np.all(w[b][far] == wc)
-    assert np.all(np.abs(w - w_ref) <= 1e-5 * np.maximum(1.0, np.abs(w_ref)))
 
 
 def test_weighted_map_matches_reference_golden(dev, golden_dir):
