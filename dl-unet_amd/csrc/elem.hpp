@@ -3,7 +3,7 @@
 //   device : 4 consecutive channels of an activation tensor stored as fp32 (16 B) or bf16 (8 B, arithmetic mode 2), read /
 //            written as 4 floats; the sum / min / max of one value per lane over a wave; the min and max of one value per thread
 //            over a block; the sum of one value per thread over a 256-thread block, and (instances.hip, prepare.hip) the
-//            exclusive prefix of one int per thread over it
+//            exclusive prefix of one int per thread over it; whether an element of a mask of any of the four dtypes is set
 //   host   : the grid size of a grid-stride launch, the bytes of a [B,H,W] scratch plane, and the dispatch of a launch on
 //            element size, channel width and padded class count (the launch bracket, profiled(), is common.hpp's)
 #pragma once
@@ -88,6 +88,15 @@ __device__ __forceinline__ int block_scan256(int v, int &total)
         total += wave_tot[i];
     }
     return before + inc - v;
+}
+
+// is element e of a mask non-zero (prepare.hip, warp.hip; dtype 0: int64, 1: float32, 2: int32, 3: uint8)
+__device__ __forceinline__ int mask_on(const void *mask, int dtype, size_t e)
+{
+    if (dtype == 0) return ((const long long *)mask)[e] != 0;
+    if (dtype == 1) return ((const float *)mask)[e] != 0.0f;
+    if (dtype == 2) return ((const int *)mask)[e] != 0;
+    return ((const unsigned char *)mask)[e] != 0;
 }
 
 static inline int grid_for(size_t total, int per_block = 256, int cap = 8192)

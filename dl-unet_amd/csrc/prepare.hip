@@ -51,15 +51,6 @@ __device__ __forceinline__ int carve_id(const void *ids, int dtype, size_t e)
     return v >= 0 && v < CV_ID_LIMIT ? v : -1;
 }
 
-// is element e non-zero (dtype 0: int64, 1: float32, 2: int32, 3: uint8)
-__device__ __forceinline__ int mask_on(const void *mask, int dtype, size_t e)
-{
-    if (dtype == 0) return ((const long long *)mask)[e] != 0;
-    if (dtype == 1) return ((const float *)mask)[e] != 0.0f;
-    if (dtype == 2) return ((const int *)mask)[e] != 0;
-    return ((const unsigned char *)mask)[e] != 0;
-}
-
 __global__ __launch_bounds__(256) void carve_kernel(const void *__restrict__ ids, int dtype, int H, int W, int r,
                                                     float *__restrict__ gt, float *__restrict__ edges,
                                                     unsigned char *__restrict__ bin, unsigned long long *__restrict__ status)

@@ -9,6 +9,8 @@ host counterpart here.  label_cells and seg_measure are extensions, device only 
 the goals of trainer.py:20-26 are stated in.  grow_cells, pair_table and rand_scores extend them to the other table those goals
 quote (Ronneberger et al. 2015, Table 1, ISBI 2012): nearest-cell growth of an instance map (unet_grow_labels), the contingency
 table of two instance maps on ground-truth foreground (unet_partition_pairs), and the Rand and information scores formed from it.
+warp_labels and warping_error add that table's third column: the topology-preserving warp of a ground-truth mask towards a
+prediction (unet_warp_init / unet_warp_sweeps / unet_warp_finish) and the disagreement it leaves.
 """
 import collections
 import fractions
@@ -319,13 +321,94 @@ def rand_scores(pred_labels, gt_labels, *, grow=None, alpha=0.5):
     pred_labels first goes through grow_cells(pred_labels, None if grow is True else grow), the challenge's border thinning (a
     prediction is scored after its border pixels have gone to the neighbouring segments).  Returns the RandScores of
     rand_from_pairs (see there for every definition) on pair_table(pred, gt).
-    This is not the warping error; it is not bit-equal to the Fiji script of the challenge, whose thinning leaves borders one
+    This is not the warping error (that is warping_error); it is not bit-equal to the Fiji script of the challenge, whose thinning leaves borders one
     pixel wide where grow=True leaves none; and label_cells stays 4-connected.  Errors as pair_table and grow_cells."""
     pred, gt = _id_maps("rand_scores", "unet_partition_pairs", pred_labels, gt_labels)
     if grow is not None and grow is not False:
         pred = grow_cells(pred, None if grow is True else grow)
     b, g, p, n = pair_table(pred, gt)
     return rand_from_pairs(b, g, p, n, gt.shape[0], alpha)
+
+
+WarpCounts = collections.namedtuple("WarpCounts", "mismatch mismatch_before flips sweeps mismatch_map")
+WarpScores = collections.namedtuple("WarpScores", "warping_error mismatch mismatch_before flips sweeps error_regions warping_error_mean")
+
+
+def warp_labels(gt_mask, pred_mask, *, reach=None, mask=None, connectivity=4, _passes=16, _launches=8):
+    """The topology-preserving warp of a ground-truth mask towards a predicted one (Jain et al. 2010): masks of equal shape
+    [H,W] or [B,H,W] on a HIP device, foreground = value != 0, of any dtype _int_code takes.  L starts as gt_mask; a pixel with
+    L != pred that may flip and is simple in L (flipping it changes neither the 4-connected foreground components nor the
+    8-connected background components of L) takes the prediction's value.  Pass s = 0..3 flips every such pixel with
+    (y & 1) * 2 + (x & 1) == s at once, a sweep is the four passes in that order, and sweeps repeat until one flips nothing.
+    The first and last row and column never flip.  reach (a number >= 0): only pixels whose exact squared distance to the nearest
+    pixel of the other class of gt_mask is <= floor(reach^2) may flip (none in a one-class image); mask: only pixels where it is
+    != 0 may (ANDed with the reach).  connectivity=8: foreground 8-connected, background 4-connected, by definition the same
+    warp of the two complements.  Returns (warped, WarpCounts): warped int32 {0,1} of the input's shape, and mismatch,
+    mismatch_before, flips (int64 numpy [B]: |warped != pred|, |gt != pred|, pixels flipped), sweeps (the sweeps of the image
+    that needed most, the final empty one counted) and mismatch_map (float32 on the device, 1 where warped != pred).
+    Exact, on the device (unet_warp_init / unet_warp_sweeps / unet_warp_finish): _launches launches of _passes passes are
+    enqueued, their flip counts read back in one copy, and the loop ends at the first launch that flipped nothing; neither
+    changes any result.  Unequal shapes, a bad connectivity and reach < 0 raise ValueError; host tensors raise
+    NotImplementedError (no CPU path)."""
+    tensors = [gt_mask, pred_mask] + ([] if mask is None else [mask])
+    if any(not torch.is_tensor(t) for t in tensors):
+        raise NotImplementedError("warp_labels takes tensors on the HIP device (unet_warp_init); there is no CPU implementation")
+    if any(t.shape != gt_mask.shape for t in tensors):
+        raise ValueError("warp_labels takes masks of equal shape, got %s" % ", ".join(str(tuple(t.shape)) for t in tensors))
+    if connectivity not in (4, 8):
+        raise ValueError("warp_labels: connectivity must be 4 or 8, got %r" % (connectivity,))
+    if reach is None or reach == math.inf:
+        max_dist2 = -1
+    else:
+        if not reach >= 0:
+            raise ValueError("warp_labels: reach must be None or a number >= 0, got %r" % (reach,))
+        max_dist2 = min(int(math.floor(float(reach) ** 2)), 1 << 40)
+    planes = [_planes("warp_labels", t) for t in tensors]
+    _device_only("warp_labels", "unet_warp_init", *tensors)
+    import _hip
+    coded = [_int_code(t, uint8_ok=True) for t in planes]
+    (gt, gt_code), (pred, pred_code) = coded[:2]
+    user, user_code = coded[2] if mask is not None else (None, 0)
+    B, H, W = gt.shape
+    dev = gt.device
+    state = torch.empty(B, H, W, dtype=torch.uint8, device=dev)
+    counts = torch.empty(2, B, dtype=torch.int32, device=dev)          # the library's u32 words: at most H * W < 2^31
+    scratch = _hip.scratch("unet_warp", dev, B, H, W)
+    _hip.run("unet_warp_init", dev, _hip.ptr(gt), gt_code, _hip.ptr(pred), pred_code, _hip.ptr(user), user_code, B, H, W, max_dist2,
+             connectivity, _hip.ptr(state), _hip.ptr(counts[0]), _hip.ptr(scratch))
+    per_sweep = []                                                      # flips of every sweep so far, [B] each
+    while True:
+        slots = torch.empty(_launches, 4, B, dtype=torch.int32, device=dev)
+        _hip.run("unet_warp_sweeps", dev, _hip.ptr(state), B, H, W, _passes, _launches, _hip.ptr(slots), 0, _hip.ptr(scratch))
+        slots = slots.cpu().numpy().astype(np.int64)
+        per_sweep.extend(slots[:, :_passes // 4].reshape(-1, B))
+        if not slots.any(axis=(1, 2)).all():                            # a launch that flipped nothing: so did all after it
+            break
+    per_sweep = np.stack(per_sweep)
+    warped = torch.empty(B, H, W, dtype=torch.int32, device=dev)
+    mismatch_map = torch.empty(B, H, W, dtype=torch.float32, device=dev)
+    _hip.run("unet_warp_finish", dev, _hip.ptr(state), B, H, W, connectivity, _hip.ptr(warped), _hip.ptr(mismatch_map), _hip.ptr(counts[1]))
+    before, after = counts.cpu().numpy().astype(np.int64)
+    single = gt_mask.dim() == 2
+    return (warped[0] if single else warped), WarpCounts(
+        mismatch=after, mismatch_before=before, flips=per_sweep.sum(axis=0), sweeps=int(np.argmin(per_sweep.any(axis=1))) + 1,
+        mismatch_map=mismatch_map[0] if single else mismatch_map)
+
+
+def warping_error(pred_mask, gt_mask, *, reach=None, mask=None, connectivity=4):
+    """The warping error of predicted against ground-truth masks (the ranking score of the ISBI 2012 challenge, Ronneberger et
+    al. 2015, Table 1): the disagreement that is left after warp_labels(gt_mask, pred_mask, ...) has moved the ground truth
+    towards the prediction as far as its topology allows.  Returns WarpScores: warping_error float64 [B] = mismatch / (H W);
+    mismatch, mismatch_before, flips int64 [B] and sweeps as WarpCounts has them; error_regions int64 [B] = the 4-connected
+    components of {warped != pred} (label_cells); warping_error_mean float64.  Arguments and errors as warp_labels.
+    Not bit-equal to the Fiji plug-in of the challenge, which flips in another order, restricts the flips by another mask and
+    thresholds a probability map at many levels; error_regions is not its split / merge / hole classification."""
+    warped, c = warp_labels(gt_mask, pred_mask, reach=reach, mask=mask, connectivity=connectivity)
+    H, W = warped.shape[-2:]
+    err = c.mismatch / np.float64(H * W)
+    regions = label_cells(c.mismatch_map)[1].cpu().numpy().astype(np.int64)
+    return WarpScores(warping_error=err, mismatch=c.mismatch, mismatch_before=c.mismatch_before, flips=c.flips, sweeps=c.sweeps,
+                      error_regions=regions, warping_error_mean=np.float64(err.mean()))
 
 
 def class_balance(gt_batch):

@@ -370,6 +370,38 @@ int unet_partition_pairs(const void *gt_i32, const void *pred_i32, int B, int H,
  * scratch: unet_grow_labels_scratch_bytes(B, H, W) (8 bytes per pixel), initialised by the call.                           */
 size_t unet_grow_labels_scratch_bytes(int B, int H, int W);
 int unet_grow_labels(const void *labels_i32, int B, int H, int W, long long max_dist2, void *out_i32, void *scratch, void *stream);
+/* The topology-preserving warp behind the warping error of the ISBI 2012 challenge (Jain et al. 2010; Ronneberger et al. 2015,
+ * Table 1; functions.warp_labels, functions.warping_error; the definition in full: DESIGN.md section 4m).  L starts as the ground
+ * truth gt, T is the prediction pred; foreground = value != 0, 4-connected, the background 8-connected.  A pixel is a candidate
+ * when it is not in the first or last row or column, may flip, and has L != T; it is simple when, among its 8 neighbours in L,
+ * the foreground forms exactly one 4-connected component that holds a 4-neighbour of the pixel and the background exactly one
+ * 8-connected component.  Pass s = 0..3 flips, at once, every simple candidate with (y & 1) * 2 + (x & 1) == s; a sweep is the
+ * passes 0, 1, 2, 3; sweeps repeat until one flips nothing.  connectivity 8 (foreground 8-, background 4-connected) is the same
+ * warp of the complements of gt and pred.  Three calls, all on one stream, none of which synchronises:
+ *   unet_warp_init    gt, pred, mask [B,H,W] of dtype 0 = int64, 1 = float32, 2 = int32, 3 = uint8 (mask may be NULL: every
+ *                     pixel).  max_dist2 >= 0: only pixels whose exact squared distance to the nearest pixel of the other class
+ *                     of gt is <= max_dist2 may flip (none in a one-class image; two calls of unet_grow_labels); < 0: no
+ *                     such limit.  state_u8 [B,H,W] receives one byte per pixel: bit 0 = L, bit 1 = T (both complemented for
+ *                     connectivity 8), bit 2 = may flip (mask AND reach AND not on the image border).  mismatch_before_u32 [B] =
+ *                     |gt != pred|.
+ *   unet_warp_sweeps  enqueues n_launches launches of passes_per_launch = 4, 8 or 16 passes each (1, 2 or 4 whole sweeps, by
+ *                     temporal blocking: the result is that of the passes one by one) on state_u8, in place as the caller sees
+ *                     it.  flips_out_u32 [slots][4][B]: launch l of the call first clears, then fills slot first_slot + l:
+ *                     [q][b] = the pixels of image b flipped by the q-th sweep of that launch (q < passes_per_launch / 4, the
+ *                     rest 0); other slots are untouched.  A launch that flips nothing leaves the state as it is, and so does
+ *                     every launch after it: the caller reads the slots back and stops at the first that is all 0.
+ *   unet_warp_finish  warped_i32 [B,H,W] = L in {0,1} (complemented back for connectivity 8), mismatch_map_f32 [B,H,W] = 1.0
+ *                     where L != T else 0.0 (a mask unet_label_components takes), mismatch_u32 [B] = |L != T|.
+ * Exact integers throughout.  Limits as unet_grow_labels (H * W < 2^31, H, W, B <= 65535), H != W allowed, down to 1 x 1.
+ * scratch: unet_warp_scratch_bytes(B, H, W), the same buffer for unet_warp_init and every unet_warp_sweeps of one warp (it holds
+ * the second state plane; 21 bytes per pixel).                                                                              */
+size_t unet_warp_scratch_bytes(int B, int H, int W);
+int unet_warp_init(const void *gt, int gt_dtype, const void *pred, int pred_dtype, const void *mask, int mask_dtype, int B, int H, int W,
+                   long long max_dist2, int connectivity, void *state_u8, void *mismatch_before_u32, void *scratch, void *stream);
+int unet_warp_sweeps(void *state_u8, int B, int H, int W, int passes_per_launch, int n_launches, void *flips_out_u32, int first_slot,
+                     void *scratch, void *stream);
+int unet_warp_finish(const void *state_u8, int B, int H, int W, int connectivity, void *warped_i32, void *mismatch_map_f32,
+                     void *mismatch_u32, void *stream);
 /* Carved training targets from an instance image, replaces preprocess_gt (data.py:195-221: per cell, cv.dilate with a 5 x 5
  * rectangle, iterations=2, and 255 added on the ring the cell gained) and the cv.threshold(gt, 0, 255, THRESH_BINARY) after it
  * (data.py:64, :163).  ids [B,H,W], dtype 0 = int64, 1 = float32 holding integral values, 2 = int32 (what
