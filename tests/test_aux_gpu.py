@@ -6,16 +6,9 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_support import dev
+
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def dev():
-    import _hip
-    _hip.lib()
-    assert torch.cuda.is_available()
-    torch.cuda.set_device(0)
-    return torch.device("cuda:0")
 
 
 def test_mirror_transform_bit_exact(dev, golden_dir):

@@ -12,36 +12,10 @@ import torch
 
 import aux_ops_ref as ref
 import guarded as gd
+from gpu_support import hip, put, rejected, still_poison
 from oracle import aux_ref
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def hip():
-    import _hip
-    _hip.lib()
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    torch.cuda.set_device(0)
-    return _hip
-
-
-def put(mem, a, label=None):
-    """numpy array -> guarded device copy"""
-    return mem.inp(torch.from_numpy(np.ascontiguousarray(a)), label)
-
-
-def still_poison(t):
-    return bool((t.view(torch.uint8) == gd.POISON).all())
-
-
-def rejected(hip, rc, mem, *outs):
-    """The call returned an error and wrote nothing: every output is still all poison, every guard intact."""
-    assert rc != 0 and hip.lib().unet_last_error()
-    torch.cuda.synchronize()
-    for o in outs:
-        assert still_poison(o)
-    mem.verify()
 
 
 # ---- 1. unet_minmax ---------------------------------------------------------------------------------------------------------

@@ -11,6 +11,7 @@ import torch.nn.functional as F
 
 import guarded as gd
 import kernel_paths as kp
+from gpu_support import hip_fixture, library_state, nchw, nerr, rnd
 
 pytestmark = pytest.mark.gpu
 
@@ -18,21 +19,7 @@ TOL_F32 = 2e-5
 TOL_BF16 = 4e-3
 
 
-@pytest.fixture(scope="module")
-def hip():
-    import _hip
-    _hip.lib()
-    assert torch.cuda.is_available()
-    torch.cuda.set_device(0)
-    default = _hip.lib().unet_get_math()
-    _hip.check(_hip.lib().unet_set_math(2), "set_math")
-    yield _hip
-    _hip.check(_hip.lib().unet_set_math(default), "set_math")
-
-
-def nerr(a, ref):
-    a = a.detach().double().cpu(); ref = ref.detach().double().cpu()
-    return ((a - ref).abs().max() / ref.abs().max().clamp_min(1e-300)).item()
+hip = hip_fixture(math=2)
 
 
 def bf(t):          # round to bf16, keep as fp64 for the reference
@@ -43,16 +30,7 @@ def nhwc16(t):      # NCHW fp64 (bf16-representable) -> NHWC bf16 on the device
     return t.permute(0, 2, 3, 1).contiguous().to(torch.bfloat16).cuda()
 
 
-def nchw(t):
-    return t.permute(0, 3, 1, 2).double().cpu()
-
-
 # (every buffer handed to the library comes from a guarded.Arena: tests/guarded.py)
-
-
-def rnd(*shape, seed=0, scale=1.0):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randn(*shape, generator=g, dtype=torch.float64) * scale
 
 
 # (the 64-input-channel shapes take the persistent convb64 kernel: 8 x 32 pixel tiles - extents below / at / just above tile
@@ -515,9 +493,8 @@ def test_head_dz_and_conv1ch_bf16_round_once(hip):
 # ---- unet_set_lds_dma(0) in mode 2 --------------------------------------------------------------------------------------
 @pytest.fixture
 def glds(hip):
-    hip.check(hip.lib().unet_set_lds_dma(0), "set_lds_dma")
-    yield 0
-    hip.check(hip.lib().unet_set_lds_dma(1), "set_lds_dma")
+    with library_state(lds_dma=0) as set_knobs:
+        yield set_knobs
 
 
 @pytest.mark.parametrize("B,H,Ci,Co", [(2, 7, 128, 64), (1, 13, 256, 128), (5, 6, 256, 256)])
@@ -539,7 +516,7 @@ def test_net_forward_backward_bf16_glds_S188(hip, glds):
     h = _hip.Handle(64, 0, 2)
     outs = []
     for dma in (0, 1):
-        hip.check(hip.lib().unet_set_lds_dma(dma), "set_lds_dma")
+        glds(lds_dma=dma)
         mem = gd.Arena()
         ws = mem.scratch(h.workspace_bytes(B, S, 1), "workspace")
         logits = mem.out((B, 2, S - 184, S - 184), torch.float32, "logits")
@@ -550,7 +527,7 @@ def test_net_forward_backward_bf16_glds_S188(hip, glds):
         mem.verify(logits, *grads)
         assert all(bool(torch.isfinite(g).all()) for g in grads)
         outs.append([logits.cpu()] + [g.cpu() for g in grads])
-    hip.check(hip.lib().unet_set_lds_dma(0), "set_lds_dma")
+    glds(lds_dma=0)
     for a, b in zip(*outs):
         assert torch.equal(a, b)
 

@@ -18,48 +18,25 @@ from torch.nn.grad import conv2d_input, conv2d_weight
 import kernel_bounds as kb
 import guarded as gd
 import kernel_paths as kp
+from gpu_support import dma, hip_fixture, nchw, nhwc, rnd
 
 pytestmark = pytest.mark.gpu
 
 WORST = {}          # worst |y - z| / A per output kind, printed at the end of the module (-s)
 
 
-@pytest.fixture(scope="module")
-def hip():
-    import _hip
-    _hip.lib()
-    assert torch.cuda.is_available()
-    torch.cuda.set_device(0)
-    default = _hip.lib().unet_get_math()
-    _hip.check(_hip.lib().unet_set_math(1), "set_math")
-    yield _hip
-    _hip.check(_hip.lib().unet_set_lds_dma(1), "set_lds_dma")
-    _hip.check(_hip.lib().unet_set_math(default), "set_math")
+hip = hip_fixture(math=1)
+
+
+@pytest.fixture(scope="module", autouse=True)
+def report_worst():
+    yield
     for k, v in sorted(WORST.items()):
         print("bf16x3 %-6s worst |y-z|/A %.3e (bound %.3e at its K)" % (k, v[0], v[1]))
 
 
-@pytest.fixture(params=[1, 0], ids=["dma", "glds"])
-def dma(hip, request):
-    hip.check(hip.lib().unet_set_lds_dma(request.param), "set_lds_dma")
-    yield request.param
-    hip.check(hip.lib().unet_set_lds_dma(1), "set_lds_dma")
-
-
-# (every buffer handed to the library comes from a guarded.Arena: tests/guarded.py)
-
-
-def rnd(*shape, seed=0, scale=1.0):
-    g = torch.Generator().manual_seed(seed)
-    return (torch.randn(*shape, generator=g, dtype=torch.float64) * scale).float().double()     # fp32 values, not bf16
-
-
-def nhwc(t):
-    return t.permute(0, 2, 3, 1).contiguous().float().cuda()
-
-
-def nchw(t):
-    return t.permute(0, 3, 1, 2).double().cpu()
+# (every buffer handed to the library comes from a guarded.Arena: tests/guarded.py; operands are drawn with rnd(fp32=True):
+#  fp32 values, not bf16)
 
 
 def judge(kind, y, z, A, K):
@@ -89,8 +66,8 @@ def fwd_family(K, pad):
 def test_conv3x3_fwd_bf16x3(hip, dma, B, Hs, pad, C1, C2, K):
     mem = gd.Arena()
     H = Hs + 2 * pad
-    a = rnd(B, C1, Hs, Hs, seed=1); u = rnd(B, C2, H, H, seed=2) if C2 else None
-    w = rnd(K, C1 + C2, 3, 3, seed=3, scale=0.05); b = rnd(K, seed=4)
+    a = rnd(B, C1, Hs, Hs, seed=1, fp32=True); u = rnd(B, C2, H, H, seed=2, fp32=True) if C2 else None
+    w = rnd(K, C1 + C2, 3, 3, seed=3, scale=0.05, fp32=True); b = rnd(K, seed=4, fp32=True)
     not_bf16(a, w)
     x = torch.cat((F.pad(a, (pad,) * 4), u), 1) if C2 else a
     z = F.relu(F.conv2d(x, w, b))
@@ -112,9 +89,9 @@ def test_conv3x3_fwd_bf16x3(hip, dma, B, Hs, pad, C1, C2, K):
                                                       (2, 22, 32, 32, True, True), (1, 16, 96, 96, False, False)])
 def test_conv3x3_bwd_bf16x3(hip, dma, B, H, C, K, use_mask, use_add):
     mem = gd.Arena()
-    x = rnd(B, C, H, H, seed=1); w = rnd(K, C, 3, 3, seed=2, scale=0.05); dz = rnd(B, K, H - 2, H - 2, seed=3)
-    mask = rnd(B, C, H, H, seed=4).clamp_min(0) if use_mask else None
-    add = rnd(B, C, H, H, seed=5) if use_add else None
+    x = rnd(B, C, H, H, seed=1, fp32=True); w = rnd(K, C, 3, 3, seed=2, scale=0.05, fp32=True); dz = rnd(B, K, H - 2, H - 2, seed=3, fp32=True)
+    mask = rnd(B, C, H, H, seed=4, fp32=True).clamp_min(0) if use_mask else None
+    add = rnd(B, C, H, H, seed=5, fp32=True) if use_add else None
     not_bf16(x, w, dz)
     dx_z = conv2d_input(x.shape, w, dz); dx_A = conv2d_input(x.shape, w.abs(), dz.abs())
     if add is not None:
@@ -142,8 +119,8 @@ def test_conv3x3_bwd_bf16x3(hip, dma, B, H, C, K, use_mask, use_add):
 def test_conv3x3_bwd_virtual_concat_bf16x3(hip, dma, B, Hs, pad, C, K):
     mem = gd.Arena()
     H = Hs + 2 * pad
-    a = rnd(B, C, Hs, Hs, seed=1).requires_grad_(True); u = rnd(B, C, H, H, seed=2).requires_grad_(True)
-    w = rnd(K, 2 * C, 3, 3, seed=3, scale=0.05).requires_grad_(True); dz = rnd(B, K, H - 2, H - 2, seed=4)
+    a = rnd(B, C, Hs, Hs, seed=1, fp32=True).requires_grad_(True); u = rnd(B, C, H, H, seed=2, fp32=True).requires_grad_(True)
+    w = rnd(K, 2 * C, 3, 3, seed=3, scale=0.05, fp32=True).requires_grad_(True); dz = rnd(B, K, H - 2, H - 2, seed=4, fp32=True)
     F.conv2d(torch.cat((F.pad(a, (pad,) * 4), u), 1), w).backward(dz)
     aa = a.detach().abs().requires_grad_(True); ua = u.detach().abs().requires_grad_(True); wa = w.detach().abs().requires_grad_(True)
     F.conv2d(torch.cat((F.pad(aa, (pad,) * 4), ua), 1), wa).backward(dz.abs())
@@ -166,8 +143,8 @@ def test_conv3x3_bwd_virtual_concat_bf16x3(hip, dma, B, Hs, pad, C, K):
 @pytest.mark.parametrize("B,H,Ci,Co", [(2, 7, 128, 64), (1, 13, 256, 128), (3, 11, 64, 32), (2, 9, 96, 96)])
 def test_upconv2_fwd_bwd_bf16x3(hip, dma, B, H, Ci, Co):
     mem = gd.Arena()
-    x = rnd(B, Ci, H, H, seed=1).clamp_min(0); w = rnd(Ci, Co, 2, 2, seed=2, scale=0.05); b = rnd(Co, seed=3)
-    dy = rnd(B, Co, 2 * H, 2 * H, seed=4)
+    x = rnd(B, Ci, H, H, seed=1, fp32=True).clamp_min(0); w = rnd(Ci, Co, 2, 2, seed=2, scale=0.05, fp32=True); b = rnd(Co, seed=3, fp32=True)
+    dy = rnd(B, Co, 2 * H, 2 * H, seed=4, fp32=True)
     not_bf16(w, dy)
     z = F.conv_transpose2d(x, w, b, stride=2); A = F.conv_transpose2d(x.abs(), w.abs(), b.abs(), stride=2)
     xr = x.clone().requires_grad_(True); wr = w.clone().requires_grad_(True)
@@ -201,7 +178,7 @@ def test_split_probe_pins_the_split(hip):
     B, H, C, K = 2, 18, 64, 64
     probe = lambda *s, seed: torch.from_numpy(kb.split_probe(s, seed))
     hi_lo = lambda t: torch.from_numpy(sum(kb.split3(t.numpy())))        # hi + lo: what the split keeps of a bf16-exact partner
-    pos16 = lambda *s, seed, scale: (rnd(*s, seed=seed, scale=scale).abs() + scale / 8).to(torch.bfloat16).double()
+    pos16 = lambda *s, seed, scale: (rnd(*s, seed=seed, scale=scale, fp32=True).abs() + scale / 8).to(torch.bfloat16).double()
     x = probe(B, C, H, H, seed=1); w = pos16(K, C, 3, 3, seed=2, scale=0.05)
     dz = probe(B, K, H - 2, H - 2, seed=3)
     y = mem.out((B, H - 2, H - 2, K), torch.float32, "y"); zb = mem.inp(torch.zeros(K))

@@ -20,6 +20,7 @@ import torch.nn.functional as F
 
 import guarded as gd
 import philox_ref
+from gpu_support import hip, library_state
 
 pytestmark = pytest.mark.gpu
 
@@ -30,23 +31,12 @@ SEED, STEP = 0x123456789ABCDEF, 5
 S, B = 188, 2
 
 
-@pytest.fixture(scope="module")
-def hip():
-    import _hip
-    _hip.lib()
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    torch.cuda.set_device(0)
-    return _hip
-
-
 @pytest.fixture(params=[4, 2], ids=["fp32", "bf16"])
 def es(hip, request):
     """Element size of the per-op entries' tensors: they follow unet_set_math (2 = bf16 tensors)."""
-    L = hip.lib()
-    default = L.unet_get_math()
-    hip.check(L.unet_set_math(2 if request.param == 2 else default if default != 2 else 3), "set_math")
-    yield request.param
-    hip.check(L.unet_set_math(default), "set_math")
+    default = hip.lib().unet_get_math()
+    with library_state(math=2 if request.param == 2 else default if default != 2 else 3):
+        yield request.param
 
 
 def gpu_flags(hip, seed, step, site, first, n, p):

@@ -11,6 +11,7 @@ import torch
 
 import elastic_grid_ref as ref
 import guarded
+from gpu_support import dev
 
 pytestmark = pytest.mark.gpu
 
@@ -21,15 +22,6 @@ LEVELS = (255, 65535, 0)
 # |device - fp64 restatement| for float outputs of values up to 255: what is left is the narrowing to fp32 at the store (half
 # an ulp at 255 = 7.6e-6) and fp64 roundings (1e-13); 255 * 1e-6 = 2.55e-4 is the issue's outer bound, 2e-5 the one asserted
 FLOAT_BOUND = 2e-5
-
-
-@pytest.fixture(scope="module")
-def dev():
-    import _hip
-    _hip.lib()
-    assert torch.cuda.is_available()
-    torch.cuda.set_device(0)
-    return torch.device("cuda:0")
 
 
 def blobs(rs, B, H, W):

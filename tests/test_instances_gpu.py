@@ -9,21 +9,13 @@ import torch
 import guarded
 import instances_ref as ref
 import multiclass_ref
+from gpu_support import dev
 
 pytestmark = pytest.mark.gpu
 
 SIZES = [(1, 1), (1, 2), (2, 1), (1, 40), (17, 5), (33, 31), (64, 64), (37, 300), (300, 37), (129, 97), (516, 516), (520, 696)]
 KINDS = ["discs", "speckle0.3", "speckle0.5", "speckle0.6", "speckle0.8", "zeros", "ones", "serpentine", "comb"]
 CASES = ((1, 9, 128, 128), (2, 37, 256, 256), (3, 99, 388, 388))          # seed, cells, H, W of instances_ref.cells_case
-
-
-@pytest.fixture(scope="module")
-def dev():
-    import _hip
-    _hip.lib()
-    assert torch.cuda.is_available()
-    torch.cuda.set_device(0)
-    return torch.device("cuda:0")
 
 
 def raw_label(dev, mask):

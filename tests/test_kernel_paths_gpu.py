@@ -9,39 +9,17 @@ import torch.nn.functional as F
 
 import guarded as gd
 import kernel_paths as kp
+from gpu_support import hip, library_state, nerr, rnd
 
 pytestmark = pytest.mark.gpu
 
 MAIN_KINDS = {kp.K_IGEMM, kp.K_WGRAD, kp.K_REDUCE, kp.K_WINO}
 
 
-@pytest.fixture(scope="module")
-def hip():
-    import _hip
-    _hip.lib()
-    assert torch.cuda.is_available()
-    torch.cuda.set_device(0)
-    default = _hip.lib().unet_get_math()
-    yield _hip
-    _hip.check(_hip.lib().unet_set_lds_dma(1), "set_lds_dma")
-    _hip.check(_hip.lib().unet_set_math(default), "set_math")
-
-
-def rnd(*shape, seed=0, scale=1.0):
-    g = torch.Generator().manual_seed(seed)
-    return (torch.randn(*shape, generator=g, dtype=torch.float64) * scale).float().double()
-
-
-def nerr(a, ref):
-    a = a.detach().double().cpu(); ref = ref.detach().double().cpu()
-    return ((a - ref).abs().max() / ref.abs().max().clamp_min(1e-300)).item()
-
-
 def run_op(hip, mode, dma, op, args):
     """Runs one per-op case in `mode` with staging `dma`; returns (record, outputs {name: device tensor}, references
     {name: (fp64 reference, is_activation)}).  Every requested output is checked to be fully written and every guard intact."""
     L = hip.lib()
-    hip.check(L.unet_set_math(mode), "set_math"); hip.check(L.unet_set_lds_dma(dma), "set_lds_dma")
     adt = torch.bfloat16 if mode == 2 else torch.float32
     q = (lambda t: t.to(torch.bfloat16).double()) if mode == 2 else (lambda t: t)       # what the kernels see of a tensor
     dev = lambda t: t.permute(0, 2, 3, 1).contiguous().to(adt).cuda()
@@ -50,14 +28,14 @@ def run_op(hip, mode, dma, op, args):
     k = mem.inp
     sc = lambda n: mem.ptr(mem.scratch(n))
     out, ref = {}, {}
-    try:
+    with library_state(math=mode, lds_dma=dma):
         with kp.record(L) as rec:
             if op in ("fwd", "bwd"):
                 B, Hs, pad, C1, C2, K = args
                 H = Hs + 2 * pad
-                a = q(rnd(B, C1, Hs, Hs, seed=1)).requires_grad_(True)
-                u = q(rnd(B, C2, H, H, seed=2)).requires_grad_(True) if C2 else None
-                w = rnd(K, C1 + C2, 3, 3, seed=3, scale=0.05); b = rnd(K, seed=4)
+                a = q(rnd(B, C1, Hs, Hs, seed=1, fp32=True)).requires_grad_(True)
+                u = q(rnd(B, C2, H, H, seed=2, fp32=True)).requires_grad_(True) if C2 else None
+                w = rnd(K, C1 + C2, 3, 3, seed=3, scale=0.05, fp32=True); b = rnd(K, seed=4, fp32=True)
                 wq = q(w).requires_grad_(True)                      # (the gradient must not flow through the bf16 cast)
                 x = torch.cat((F.pad(a, (pad,) * 4), u), 1) if C2 else a
                 z = F.conv2d(x, wq, b)
@@ -70,7 +48,7 @@ def run_op(hip, mode, dma, op, args):
                                                  hip.stream()), "conv3x3_fwd")
                     out["y"] = y; ref["y"] = (F.relu(z.detach()), True)
                 else:
-                    dz = q(rnd(B, K, H - 2, H - 2, seed=5))
+                    dz = q(rnd(B, K, H - 2, H - 2, seed=5, fp32=True))
                     z.backward(dz)
                     dx1 = mem.out((B, Hs, Hs, C1), adt, "dx1")
                     dx2 = mem.out((B, H, H, C2), adt, "dx2") if C2 else None
@@ -84,10 +62,10 @@ def run_op(hip, mode, dma, op, args):
                         out["dx2"] = dx2; ref["dx2"] = (u.grad, True)
             else:                                                   # "up": up-conv forward + backward
                 B, H, Ci, Co = args
-                x = q(rnd(B, Ci, H, H, seed=1).clamp_min(0)).requires_grad_(True)
-                w = rnd(Ci, Co, 2, 2, seed=2, scale=0.05); b = rnd(Co, seed=3)
+                x = q(rnd(B, Ci, H, H, seed=1, fp32=True).clamp_min(0)).requires_grad_(True)
+                w = rnd(Ci, Co, 2, 2, seed=2, scale=0.05, fp32=True); b = rnd(Co, seed=3, fp32=True)
                 wq = q(w).requires_grad_(True)
-                dy = q(rnd(B, Co, 2 * H, 2 * H, seed=4))
+                dy = q(rnd(B, Co, 2 * H, 2 * H, seed=4, fp32=True))
                 z = F.conv_transpose2d(x, wq, b, stride=2)
                 z.backward(dy)
                 s = sc(L.unet_upconv2_scratch_bytes(B, H, H, max(Ci, 64), max(Co, 64)))
@@ -99,8 +77,6 @@ def run_op(hip, mode, dma, op, args):
                                              s, hip.stream()), "upconv2_bwd")
                 out.update(y=y, dx=dx, dw=dw, db=db)
                 ref.update(y=(z.detach(), True), dx=(x.grad * (x.detach() > 0), True), dw=(wq.grad, False), db=(dy.sum((0, 2, 3)), False))
-    finally:
-        hip.check(L.unet_set_lds_dma(1), "set_lds_dma")
     mem.verify(*out.values())
     out = {n: (host(t) if t.dim() == 4 and n.startswith(("y", "dx")) else t.cpu()) for n, t in out.items()}
     return rec, out, ref

@@ -11,6 +11,7 @@ import torch.nn.functional as F
 
 import multiclass_ref as ref
 import segment_ref
+from gpu_support import dev, math_mode, nerr
 
 pytestmark = pytest.mark.gpu
 
@@ -19,35 +20,11 @@ FWD_TOL = 2e-5              # normalised forward error against fp64 (tests/test_
 GRAD_TOL = 3e-4
 
 
-@pytest.fixture(scope="module")
-def dev():
-    import _hip
-    _hip.lib()
-    assert torch.cuda.is_available()
-    torch.cuda.set_device(0)
-    return torch.device("cuda:0")
-
-
-@pytest.fixture
-def math_mode():
-    import _hip
-    L = _hip.lib()
-    default = L.unet_get_math()
-    yield lambda m: _hip.check(L.unet_set_math(m), "unet_set_math")
-    _hip.check(L.unet_set_math(default), "unet_set_math")
-
-
 def knet(K, dev, base=64, seed=0):
     import network
     m = network.Unet(base_ch=base, n_classes=K)
     m.load_state_dict({k: torch.from_numpy(v) for k, v in ref.head_params(K, base=base, seed=seed).items()})
     return m.to(dev)
-
-
-def nerr(a, b):
-    a = np.asarray(a, np.float64)
-    b = np.asarray(b, np.float64)
-    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-300))
 
 
 # ---- head per op -----------------------------------------------------------------------------------------------------------

@@ -14,44 +14,9 @@ import torch
 
 import guarded as gd
 import multiclass_ref as ref
+from gpu_support import hip, math_mode, put, still_poison, strided
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def hip():
-    import _hip
-    _hip.lib()
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    torch.cuda.set_device(0)
-    return _hip
-
-
-@pytest.fixture
-def math_mode():
-    import _hip
-    L = _hip.lib()
-    default = L.unet_get_math()
-    yield lambda m: _hip.check(L.unet_set_math(m), "unet_set_math")
-    _hip.check(L.unet_set_math(default), "unet_set_math")
-
-
-def put(mem, a, label=None):
-    return mem.inp(torch.from_numpy(np.ascontiguousarray(a)), label)
-
-
-def still_poison(t):
-    return bool((t.view(torch.uint8) == gd.POISON).all())
-
-
-def strided(mem, x, top=2, left=3, bottom=2, right=3):
-    """x [B,K,H,W] as a crop view inside a NaN tensor: (pointer of the view, its batch, class-plane and row strides)."""
-    B, K, H, W = x.shape
-    Hb, Wb = H + top + bottom, W + left + right
-    big = np.full((B, K, Hb, Wb), np.nan, np.float32)
-    big[:, :, top:top + H, left:left + W] = x
-    d = put(mem, big, "logits inside NaN")
-    return C.c_void_p(mem.address(d) + (top * Wb + left) * 4), (K * Hb * Wb, Hb * Wb, Wb)
 
 
 # ---- unet_softmax_ce_step ---------------------------------------------------------------------------------------------------

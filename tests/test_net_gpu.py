@@ -23,6 +23,8 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_support import dev, library_state, math_mode, nerr, net
+
 pytestmark = pytest.mark.gpu
 
 FWD_TOL = 2e-5
@@ -30,23 +32,6 @@ GRAD_TOL = 3e-4          # same-branch
 TRAINER_SAME_BRANCH_TOL = 1e-5   # relative: 4 SGD steps, HIP (fp32) against the fp64 oracle following the same ReLU/pool branch
 TRAINER_LOSS_FLOOR = 2e-5    # relative: one forward rounding (FWD_TOL) on top of twice the reference's own fp32 distance
 TRAINER_PIXEL_FLOOR = 1.0    # pixels of the mask on top of twice the reference's own fp32 distance (IoU / pixel-error series)
-
-
-@pytest.fixture(scope="module")
-def net():
-    import network
-    from oracle import prng
-    assert torch.cuda.is_available()
-    torch.cuda.set_device(0)
-    m = network.Unet()
-    sd = {k: torch.from_numpy(v) for k, v in prng.make_params(0).items()}
-    m.load_state_dict(sd)
-    return m.to("cuda:0")
-
-
-def nerr(a, ref):
-    a = np.asarray(a, dtype=np.float64); ref = np.asarray(ref, dtype=np.float64)
-    return np.abs(a - ref).max() / max(np.abs(ref).max(), 1e-300)
 
 
 def run(net, S, B, with_grad, seed_x=1):
@@ -397,15 +382,6 @@ def test_config4_shaped_training_loop_with_gpu_augmentation(tmp_path, golden_dir
     assert np.isfinite(np.loadtxt(os.path.join(tmp_path, "progress", "loss.out")))
 
 
-@pytest.fixture
-def math_mode():
-    import _hip
-    L = _hip.lib()
-    default = L.unet_get_math()
-    yield lambda m: _hip.check(L.unet_set_math(m), "unet_set_math")
-    _hip.check(L.unet_set_math(default), "unet_set_math")
-
-
 def test_bf16x3_mode_keeps_fp32_class_accuracy(math_mode, golden_dir):
     """unet_set_math(1): fp32 operands split into two bf16 terms, three bf16 MFMAs per product, fp32 accumulation.
     Measured: logits 3e-5, same-branch gradients 6e-5 of tensor scale (fp32 MFMA: 4e-6 / 7e-6) — bounds below are
@@ -488,10 +464,8 @@ def test_bf16_tensors_overlap_default_is_bit_identical_to_one_stream(math_mode):
     """With bf16 tensors the weight gradients run on the handle's auxiliary stream by default (unet_set_overlap(-1): per
     arithmetic mode).  Same kernels on the same data: logits and all 46 gradients must be bit-identical to the one-stream
     order, run after run."""
-    import _hip
     import network
     from oracle import prng
-    L = _hip.lib()
     math_mode(2)
     m = network.Unet()
     m.load_state_dict({k: torch.from_numpy(v) for k, v in prng.make_params(0).items()})
@@ -506,15 +480,12 @@ def test_bf16_tensors_overlap_default_is_bit_identical_to_one_stream(math_mode):
         torch.cuda.synchronize()
         return y.detach().clone(), [p.grad.clone() for p in m.parameters()]
 
-    try:
-        _hip.check(L.unet_set_overlap(0), "unet_set_overlap")
+    with library_state(overlap=0) as set_knobs:
         y0, g0 = once()
-        _hip.check(L.unet_set_overlap(-1), "unet_set_overlap")
+        set_knobs(overlap=-1)
         for _ in range(3):
             y1, g1 = once()
             assert torch.equal(y0, y1) and all(torch.equal(a, b) for a, b in zip(g0, g1))
-    finally:
-        _hip.check(L.unet_set_overlap(-1), "unet_set_overlap")
 
 
 @pytest.mark.parametrize("B,S", [(1, 188), (3, 252), (2, 700), (5, 380), (1, 1212), (16, 572)])
@@ -540,9 +511,7 @@ def test_overlap_knob_gives_bit_identical_gradients(net):
     """unet_set_overlap(1): weight gradients on the handle's auxiliary stream next to the dgrad chain, re-joined at every stage
     end.  Same kernels on the same data, only their interleaving differs: logits and all 46 gradients must be bit-identical
     (any missing stream dependency shows up as a difference here or as a failure of the fp64 comparison at S=380)."""
-    import _hip
     from oracle import parity, prng
-    L = _hip.lib()
     x = torch.from_numpy(prng.make_input(1, 2, 252)).cuda()
     dl = torch.from_numpy(prng.make_cotangent(2, (2, 2, 68, 68))).cuda()
 
@@ -553,17 +522,14 @@ def test_overlap_knob_gives_bit_identical_gradients(net):
         torch.cuda.synchronize()
         return y.detach().clone(), [p.grad.clone() for p in net.parameters()]
 
-    _hip.check(L.unet_set_overlap(0), "unet_set_overlap")
-    y0, g0 = once()
-    _hip.check(L.unet_set_overlap(1), "unet_set_overlap")
-    try:
+    with library_state(overlap=0) as set_knobs:             # (on exit overlap is -1, the default: per arithmetic mode)
+        y0, g0 = once()
+        set_knobs(overlap=1)
         for _ in range(3):                                   # repeated: a race would not lose every time
             y1, g1 = once()
             assert torch.equal(y0, y1) and all(torch.equal(a, b) for a, b in zip(g0, g1))
         r = parity.check_same_branch(380, 1)
         assert r["fwd"] < FWD_TOL and max(r["grads"].values()) < GRAD_TOL
-    finally:
-        _hip.check(L.unet_set_overlap(-1), "unet_set_overlap")       # the default: per arithmetic mode
 
 
 def test_rccl_communicator_behind_the_c_abi_single_rank(net):

@@ -12,41 +12,15 @@ import torch.nn.functional as F
 import guarded as gd
 import kernel_paths as kp
 import step_ref
+from gpu_support import hip, library_state, nchw, nerr, nhwc, rnd
 
 pytestmark = pytest.mark.gpu
 
 TOL = 2e-5
 
 
-@pytest.fixture(scope="module")
-def hip():
-    import _hip
-    _hip.lib()
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    torch.cuda.set_device(0)
-    return _hip
-
-
-def nerr(a, ref):
-    a = a.detach().double().cpu(); ref = ref.detach().double().cpu()
-    return ((a - ref).abs().max() / ref.abs().max().clamp_min(1e-300)).item()
-
-
-def nhwc(t):   # NCHW cpu -> NHWC cuda fp32
-    return t.permute(0, 2, 3, 1).contiguous().float().cuda()
-
-
-def nchw(t):   # NHWC cuda -> NCHW cpu fp64
-    return t.permute(0, 3, 1, 2).double().cpu()
-
-
 # Every buffer handed to the library comes from a guarded.Arena (tests/guarded.py): outputs and scratch are poisoned and of the
 # exact size, inputs are copies with poison around them; mem.verify(outputs...) = every element written, every guard intact.
-
-
-def rnd(*shape, seed=0, scale=1.0):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randn(*shape, generator=g, dtype=torch.float64) * scale
 
 
 ConvMode = collections.namedtuple("ConvMode", "mode dma")
@@ -58,12 +32,8 @@ def conv_mode(hip, request):
     each stages its operands either by buffer-descriptor LDS-DMA (default) or by global_load_lds — the instantiation
     tensors >= 2 GiB take (BASELINE config #5 at batch 16), forced here with unet_set_lds_dma(0)."""
     mode, dma = request.param
-    default = hip.lib().unet_get_math()
-    hip.check(hip.lib().unet_set_math(mode), "set_math")
-    hip.check(hip.lib().unet_set_lds_dma(dma), "set_lds_dma")
-    yield ConvMode(mode, dma)
-    hip.check(hip.lib().unet_set_lds_dma(1), "set_lds_dma")
-    hip.check(hip.lib().unet_set_math(default), "set_math")
+    with library_state(math=mode, lds_dma=dma):
+        yield ConvMode(mode, dma)
 
 
 @pytest.mark.parametrize("B,H,C,K", [(2, 21, 64, 64), (1, 37, 64, 128), (3, 14, 128, 128), (1, 12, 256, 512), (2, 9, 128, 64), (1, 30, 32, 32),
@@ -195,9 +165,8 @@ def test_upconv2_fwd(hip, B, H, Ci, Co):
 def up_staging(hip, request):
     """The up-conv weight gradient runs as the pixel-linear kernel (buffer-descriptor LDS-DMA); with unet_set_lds_dma(0) - what
     tensors >= 2 GiB take by themselves - it falls back to the row-walking kernel."""
-    hip.check(hip.lib().unet_set_lds_dma(request.param), "set_lds_dma")
-    yield request.param
-    hip.check(hip.lib().unet_set_lds_dma(1), "set_lds_dma")
+    with library_state(lds_dma=request.param):
+        yield request.param
 
 
 # (the weight gradient is the pixel-linear kernel: fewer pixels than one 32-pixel chunk, a ragged last chunk, chunks that cross

@@ -6,12 +6,8 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_support import nerr
 from oracle import oracle_c, prng, torch_ref
-
-
-def nerr(a, ref):
-    ref = np.asarray(ref, dtype=np.float64)
-    return np.abs(np.asarray(a, dtype=np.float64) - ref).max() / max(np.abs(ref).max(), 1e-300)
 
 
 def _checks(grads, g, tag, tol):

@@ -11,6 +11,7 @@ import torch
 
 import guarded
 import prepare_ref as ref
+from gpu_support import dev
 
 pytestmark = pytest.mark.gpu
 
@@ -19,15 +20,6 @@ REACHES = (0, 1, 4, 8)
 NP_OF_CODE = {0: np.int64, 1: np.float32, 2: np.int32, 3: np.uint8}
 WANTS = ((True, True, True), (True, False, False), (False, True, False), (False, False, True))     # gt, edges, bin
 P_BOUND = 1e-12
-
-
-@pytest.fixture(scope="module")
-def dev():
-    import _hip
-    _hip.lib()
-    assert torch.cuda.is_available()
-    torch.cuda.set_device(0)
-    return torch.device("cuda:0")
 
 
 @pytest.fixture(scope="module")

@@ -11,19 +11,11 @@ import torch
 import guarded
 import instances_ref
 import rand_ref as ref
+from gpu_support import dev
 
 pytestmark = pytest.mark.gpu
 
 SIZES = [(1, 1), (1, 2), (2, 1), (1, 40), (17, 5), (33, 31), (64, 64), (63, 65), (37, 300), (300, 37), (129, 97), (257, 255)]
-
-
-@pytest.fixture(scope="module")
-def dev():
-    import _hip
-    _hip.lib()
-    assert torch.cuda.is_available()
-    torch.cuda.set_device(0)
-    return torch.device("cuda:0")
 
 
 def raw_grow(dev, ids, max_dist2):

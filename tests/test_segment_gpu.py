@@ -6,49 +6,9 @@ import pytest
 import torch
 
 import segment_ref as ref
+from gpu_support import dev, image, math_mode, net
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def dev():
-    import _hip
-    _hip.lib()
-    assert torch.cuda.is_available()
-    torch.cuda.set_device(0)
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def net(dev):
-    import network
-    from oracle import prng
-    m = network.Unet()
-    m.load_state_dict({k: torch.from_numpy(v) for k, v in prng.make_params(0).items()})
-    return m.to(dev)
-
-
-@pytest.fixture
-def math_mode():
-    import _hip
-    L = _hip.lib()
-    default = L.unet_get_math()
-    yield lambda m: _hip.check(L.unet_set_math(m), "unet_set_math")
-    _hip.check(L.unet_set_math(default), "unet_set_math")
-
-
-def image(seed, B, H, W):
-    """Smooth blobs plus noise, float32 in roughly [0, 255] (a microscope-like dynamic range; not normalised)."""
-    rs = np.random.RandomState(seed)
-    yy, xx = np.mgrid[0:H, 0:W]
-    img = np.empty((B, H, W), np.float32)
-    for b in range(B):
-        f = 40 * rs.rand(H, W)
-        for _ in range(12):
-            cy, cx, r = rs.uniform(0, H), rs.uniform(0, W), rs.uniform(2, max(3.0, min(H, W) / 5))
-            f += 200 * np.exp(-((yy - cy) ** 2 + (xx - cx) ** 2) / (2 * r * r))
-        img[b] = f
-    return img
 
 
 def gather(x, S, t0, nt, minmax=None):
@@ -76,7 +36,7 @@ def minmax(x):
 def test_gather_is_numpy_reflect_pad(dev, B, H, W, S):
     """Bit-identical to np.pad(reflect) + slicing, raw and normalised ((x - min) / (max - min), fp32 true division), for
     the whole tile range and for sub-ranges that start mid-image."""
-    img = image(B * 1000 + H + W, B, H, W)
+    img = image(B * 1000 + H + W, B, H, W, blobs=12)
     x = torch.from_numpy(img).to(dev)
     T = len(ref.tile_windows(H, W, S)[0]) * B
     want, want_n = ref.tiles(img, S), ref.tiles(img, S, norm=True)
@@ -123,7 +83,7 @@ def test_unaligned_buffers_take_the_scalar_path(dev):
     So = S - 184
     ny, nx, oy0, ox0 = tester.tile_grid(H, W, S)
     T = B * ny * nx
-    img = image(3, B, H, W)
+    img = image(3, B, H, W, blobs=12)
     x = torch.from_numpy(img).to(dev)
     buf = torch.full((T * S * S + 1,), float("nan"), device=dev)
     _hip.run("unet_tile_gather", dev, _hip.ptr(x), B, H, W, None, S, oy0, ox0, ny, nx, 0, T, _hip.ptr(buf[1:]))
@@ -255,7 +215,7 @@ def test_segment_matches_numpy_pipeline(dev, net, math_mode, mode, B, H, W, S, m
     cap - for 1500^2)."""
     import tester
     math_mode(mode)
-    img = image(H + W + mode, B, H, W)
+    img = image(H + W + mode, B, H, W, blobs=12)
     S_used = S or tester.auto_tile_size(H, W)
     if S is None:
         assert (H, W, S_used, tester.tile_grid(H, W, S_used)[:2]) in ((300, 300, 508, (1, 1)), (520, 696, 892, (1, 1)),
@@ -276,7 +236,7 @@ def test_segment_half_width_net_and_unnormalised(dev):
     m32 = network.Unet(base_ch=32)
     m32.load_state_dict({k: torch.from_numpy(v) for k, v in prng.make_params(3, base=32).items()})
     m32 = m32.to(dev)
-    img = image(5, 1, 400, 250) / 255
+    img = image(5, 1, 400, 250, blobs=12) / 255
     (want_m, _), _ = pipeline(m32, img, 572, 16, norm=False)
     got = tester.segment(m32, torch.from_numpy(img).to(dev), tile_size=572, normalise=False)
     assert np.array_equal(got.cpu().numpy(), want_m)
@@ -287,7 +247,7 @@ def test_bf16_chunks_stay_below_2GiB_tensors(dev, net, math_mode):
     address: segment runs chunks of 11 instead, the same as the pipeline in chunks of 11."""
     import tester
     math_mode(2)
-    img = image(61, 1, 3100, 3100)
+    img = image(61, 1, 3100, 3100, blobs=12)
     assert tester.auto_tile_size(3100, 3100) == 1212 and tester.tile_grid(3100, 3100, 1212)[:2] == (4, 4)
     (want_m, _), _ = pipeline(net, img, 1212, 11)
     got = tester.segment(net, torch.from_numpy(img).to(dev), max_batch=16)
@@ -299,7 +259,7 @@ def test_segment_two_tiles_vs_fp64_c_oracle(dev, net):
     exceeds 10x the forward tolerance (2e-5 of the logit scale), as tests/test_net_gpu.py judges argmax masks."""
     import tester
     from oracle import oracle_c, prng
-    img = image(11, 1, 4, 8)
+    img = image(11, 1, 4, 8, blobs=12)
     m = tester.segment(net, torch.from_numpy(img).to(dev), tile_size=188).cpu().numpy()
     tl = ref.tiles(img, 188, norm=True).astype(np.float64)
     assert tl.shape[0] == 2
@@ -314,7 +274,7 @@ def test_segment_two_tiles_vs_fp64_c_oracle(dev, net):
 def test_chunking_does_not_change_the_result(dev, net):
     """max_batch 1 and 16 on the same 16-tile image: identical masks and probabilities."""
     import tester
-    x = torch.from_numpy(image(21, 1, 1500, 1500)).to(dev)
+    x = torch.from_numpy(image(21, 1, 1500, 1500, blobs=12)).to(dev)
     m1, p1 = tester.segment(net, x, max_batch=1, return_probs=True)
     m16, p16 = tester.segment(net, x, max_batch=16, return_probs=True)
     assert torch.equal(m1, m16)
@@ -323,7 +283,7 @@ def test_chunking_does_not_change_the_result(dev, net):
 
 def test_side_stream_and_repeat_determinism(dev, net):
     import tester
-    x = torch.from_numpy(image(31, 2, 700, 450)).to(dev)
+    x = torch.from_numpy(image(31, 2, 700, 450, blobs=12)).to(dev)
     m0, p0 = tester.segment(net, x, max_batch=3, return_probs=True)
     s = torch.cuda.Stream(device=dev)
     s.wait_stream(torch.cuda.current_stream(dev))
@@ -337,7 +297,7 @@ def test_side_stream_and_repeat_determinism(dev, net):
 
 def test_return_shapes_and_integer_images(dev, net):
     import tester
-    img = np.round(image(41, 2, 90, 130)).clip(0, 255)
+    img = np.round(image(41, 2, 90, 130, blobs=12)).clip(0, 255)
     x = torch.from_numpy(img.astype(np.float32)).to(dev)
     mb = tester.segment(net, x)
     assert mb.shape == (2, 90, 130) and mb.dtype == torch.int64
@@ -350,7 +310,7 @@ def test_return_shapes_and_integer_images(dev, net):
 
 def test_segment_errors(dev, net):
     import tester
-    x = torch.from_numpy(image(51, 1, 60, 60)).to(dev)
+    x = torch.from_numpy(image(51, 1, 60, 60, blobs=12)).to(dev)
     with pytest.raises(RuntimeError, match="HIP device"):
         tester.segment(net, x.cpu())
     with pytest.raises(ValueError):

@@ -13,31 +13,11 @@ import torch
 
 import guarded as gd
 import step_ref
+from gpu_support import hip, nerr, put, rejected, still_poison, strided
 
 pytestmark = pytest.mark.gpu
 
 SPECIAL = np.float32([0.0, -0.0, 1e-8, -1e-8, 17, -17, 88, -88, 104, -104, 1e4, -1e4])
-
-
-@pytest.fixture(scope="module")
-def hip():
-    import _hip
-    _hip.lib()
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    torch.cuda.set_device(0)
-    return _hip
-
-
-def put(mem, a, label=None):
-    return mem.inp(torch.from_numpy(np.ascontiguousarray(a)), label)
-
-
-def still_poison(t):
-    return bool((t.view(torch.uint8) == gd.POISON).all())
-
-
-def nerr(a, r):
-    return float(np.abs(np.asarray(a, np.float64) - r).max() / max(np.abs(r).max(), 1e-300))
 
 
 def logits_and_labels(B, H, W):
@@ -56,15 +36,6 @@ def logits_and_labels(B, H, W):
         if H * W > 2:
             f[0, 0, 1] = -0.0; f[0, 1, 1] = 0.0
     return x, labels
-
-
-def strided(mem, x):
-    """x [B,2,H,W] as a centre-crop view inside a NaN tensor: (pointer of the view, its three strides)."""
-    B, _, H, W = x.shape
-    big = np.full((B, 2, H + 4, W + 6), np.nan, np.float32)
-    big[:, :, 2:2 + H, 3:3 + W] = x
-    d = put(mem, big, "logits inside NaN")
-    return C.c_void_p(mem.address(d) + (2 * (W + 6) + 3) * 4), (2 * (H + 4) * (W + 6), (H + 4) * (W + 6), W + 6)
 
 
 def weight_forms(B, H, W):
@@ -260,10 +231,8 @@ def test_sgd_momentum_table_limits(hip):
     numel = (C.c_size_t * 47)(*[p.numel() for p in case.ps])
     for n in (47, 0):
         rc = L.unet_sgd_momentum(case.ptrs(case.ps), case.ptrs(gs), case.ptrs(case.bufs), numel, n, 0.1, 0.9, 1, hip.stream())
-        assert rc != 0 and L.unet_last_error()
-        torch.cuda.synchronize()
-        case.mem.verify()
-        assert all(torch.equal(p, p0) for p, p0 in zip(case.ps, case.p0)) and all(still_poison(b) for b in case.bufs)
+        rejected(hip, rc, case.mem, *case.bufs)
+        assert all(torch.equal(p, p0) for p, p0 in zip(case.ps, case.p0))
 
 
 @pytest.mark.parametrize("misaligned", [(), (1,)], ids=["vector", "scalar"])

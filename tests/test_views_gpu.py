@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import guarded
+from gpu_support import dev, image, math_mode, net
 
 pytestmark = pytest.mark.gpu
 
@@ -17,53 +18,12 @@ FIRST, LAST = 1, 2
 
 
 @pytest.fixture(scope="module")
-def dev():
-    import _hip
-    _hip.lib()
-    assert torch.cuda.is_available()
-    torch.cuda.set_device(0)
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def net(dev):
-    import network
-    from oracle import prng
-    m = network.Unet()
-    m.load_state_dict({k: torch.from_numpy(v) for k, v in prng.make_params(0).items()})
-    return m.to(dev)
-
-
-@pytest.fixture(scope="module")
 def net3(dev):
     import multiclass_ref
     import network
     m = network.Unet(n_classes=3)
     m.load_state_dict({k: torch.from_numpy(v) for k, v in multiclass_ref.head_params(3).items()})
     return m.to(dev)
-
-
-@pytest.fixture
-def math_mode():
-    import _hip
-    L = _hip.lib()
-    default = L.unet_get_math()
-    yield lambda m: _hip.check(L.unet_set_math(m), "unet_set_math")
-    _hip.check(L.unet_set_math(default), "unet_set_math")
-
-
-def image(seed, B, H, W):
-    """Blobs plus noise, float32 in roughly [0, 255], no symmetry."""
-    rs = np.random.RandomState(seed)
-    yy, xx = np.mgrid[0:H, 0:W]
-    img = np.empty((B, H, W), np.float32)
-    for b in range(B):
-        f = 40 * rs.rand(H, W)
-        for _ in range(8):
-            cy, cx, r = rs.uniform(0, H), rs.uniform(0, W), rs.uniform(2, max(3.0, min(H, W) / 5))
-            f += 200 * np.exp(-((yy - cy) ** 2 + (xx - cx) ** 2) / (2 * r * r))
-        img[b] = f
-    return img
 
 
 def view_grid(H, W, S, v):
@@ -101,7 +61,7 @@ def test_gather_view_is_gather_of_the_materialised_view(dev, B, H, W, S):
     view's 32 x 32 moves, 9 x 14 overhangs its 3 x 4 grid on both axes, 2 x 2 and 37 x 5 reflect several times."""
     import _hip
     ar = guarded.Arena(dev)
-    x = ar.inp(torch.from_numpy(image(H * W + B, B, H, W)))
+    x = ar.inp(torch.from_numpy(image(H * W + B, B, H, W, blobs=8)))
     mm = ar.out((B, 2))
     _hip.run("unet_minmax", dev, ar.ptr(x), B, H * W, ar.ptr(mm))
     for v in D4:
@@ -118,7 +78,7 @@ def test_gather_view_of_a_sub_range_and_through_a_4_byte_aligned_pointer(dev):
     import _hip
     ar = guarded.Arena(dev)
     B, H, W, S = 2, 9, 14, 188
-    x = ar.inp(torch.from_numpy(image(77, B, H, W)))
+    x = ar.inp(torch.from_numpy(image(77, B, H, W, blobs=8)))
     mm = ar.out((B, 2))
     _hip.run("unet_minmax", dev, ar.ptr(x), B, H * W, ar.ptr(mm))
     for v in D4:
@@ -223,7 +183,7 @@ def test_stitch_view_rejects_bad_arguments_without_writing(dev):
     lg = ar.inp(torch.from_numpy(synthetic_logits(5, T, 16, So)))
     prob = ar.out((B, 16, H, W))
     mask = ar.out((B, H, W), torch.int64)
-    x = ar.inp(torch.from_numpy(image(9, B, H, W)))
+    x = ar.inp(torch.from_numpy(image(9, B, H, W, blobs=8)))
     tiles = ar.out((T, 1, S, S))
 
     def stitch(K=2, view=v, grid=(oy0, ox0, ny, nx), phase=3, n_views=1, m=mask):
@@ -270,7 +230,7 @@ def composite(net, x, vs, S, mb):
 
 def check_against_composite(net, dev, B, H, W, S, views, mb, seed):
     import tester
-    x = torch.from_numpy(image(seed, B, H, W)).to(dev)
+    x = torch.from_numpy(image(seed, B, H, W, blobs=8)).to(dev)
     want_p, want_m = composite(net, x, tester.parse_views(views), S, mb)
     m, p = tester.segment(net, x, tile_size=S, max_batch=mb, return_probs=True, views=views)
     assert m.dtype == torch.int64 and p.dtype == torch.float32 and m.shape == (B, H, W) and p.shape == want_p.shape
@@ -304,7 +264,7 @@ def test_segment_views_bf16_same_chunks(dev, net, math_mode):
 
 def test_identity_view_is_the_plain_path(dev, net):
     import tester
-    x = torch.from_numpy(image(12, 2, 40, 30)).to(dev)
+    x = torch.from_numpy(image(12, 2, 40, 30, blobs=8)).to(dev)
     m0, p0 = tester.segment(net, x, tile_size=220, max_batch=3, return_probs=True)
     m1, p1 = tester.segment(net, x, tile_size=220, max_batch=3, return_probs=True, views=(0,))
     assert torch.equal(p0, p1)
@@ -315,7 +275,7 @@ def test_identity_view_is_the_plain_path(dev, net):
 def test_determinism_side_stream_instances_and_shapes(dev, net, net3):
     import tester
     from functions import label_cells
-    x = torch.from_numpy(image(31, 2, 9, 14)).to(dev)
+    x = torch.from_numpy(image(31, 2, 9, 14, blobs=8)).to(dev)
     kw = dict(tile_size=188, max_batch=5, return_probs=True, views="d4")
     m0, p0 = tester.segment(net, x, **kw)
     m1, p1 = tester.segment(net, x, **kw)

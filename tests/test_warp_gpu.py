@@ -10,6 +10,7 @@ from scipy import ndimage
 
 import guarded
 import warp_ref as ref
+from gpu_support import dev
 
 pytestmark = pytest.mark.gpu
 
@@ -17,15 +18,6 @@ pytestmark = pytest.mark.gpu
 SIZES = [(1, 1), (1, 40), (2, 2), (3, 3), (5, 7), (33, 31), (64, 64), (63, 65), (65, 63), (129, 97), (257, 255)]
 CODE = {torch.int64: 0, torch.float32: 1, torch.int32: 2, torch.uint8: 3}
 INTS = ("mismatch", "mismatch_before", "flips")
-
-
-@pytest.fixture(scope="module")
-def dev():
-    import _hip
-    _hip.lib()
-    assert torch.cuda.is_available()
-    torch.cuda.set_device(0)
-    return torch.device("cuda:0")
 
 
 def raw_warp(dev, gt, pred, reach=None, mask=None, connectivity=4, passes=16, launches=8, dtype=torch.uint8):

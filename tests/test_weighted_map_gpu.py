@@ -9,18 +9,10 @@ import torch
 from scipy import ndimage
 
 import weighted_map_ref as ref
+from gpu_support import dev
 from weighted_map_ref import check_against_restatement, golden_cases
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def dev():
-    import _hip
-    _hip.lib()
-    assert torch.cuda.is_available()
-    torch.cuda.set_device(0)
-    return torch.device("cuda:0")
 
 
 def test_weighted_map_matches_reference_golden(dev, golden_dir):

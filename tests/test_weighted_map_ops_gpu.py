@@ -12,21 +12,9 @@ import torch
 
 import guarded as gd
 import weighted_map_ref as ref
+from gpu_support import hip, rejected
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def hip():
-    import _hip
-    _hip.lib()
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    torch.cuda.set_device(0)
-    return _hip
-
-
-def still_poison(t):
-    return bool((t.view(torch.uint8) == gd.POISON).all())
 
 
 class Call:
@@ -80,6 +68,4 @@ def test_weighted_map_rejects_without_touching(hip, sig2, code):
     """sig2 = 0, a reach above 1024 (sig2 = 6000: 1118) and an unknown label type return non-zero; no buffer is touched."""
     lab = ref.param_labels("blobs+far", np.int64)
     c = Call(hip, lab, 20.0, sig2, dtype_code=code)
-    assert c.rc != 0 and hip.lib().unet_last_error()
-    c.mem.verify()
-    assert still_poison(c.w) and still_poison(c.counts) and still_poison(c.nobj) and still_poison(c.scratch)
+    rejected(hip, c.rc, c.mem, c.w, c.counts, c.nobj, c.scratch)

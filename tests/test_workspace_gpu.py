@@ -17,6 +17,7 @@ import pytest
 import torch
 
 import guarded as gd
+from gpu_support import nerr
 
 pytestmark = pytest.mark.gpu
 
@@ -34,11 +35,6 @@ def params_of(base, K):
         import multiclass_ref as ref
         _params[(base, K)] = ref.head_params(K, base=base)
     return _params[(base, K)]
-
-
-def nerr(a, ref):
-    a = np.asarray(a, dtype=np.float64); ref = np.asarray(ref, dtype=np.float64)
-    return np.abs(a - ref).max() / max(np.abs(ref).max(), 1e-300)
 
 
 class Net:
