@@ -99,6 +99,10 @@ _SIGS = {
     "unet_warp_init": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_int, vp, vp, vp, vp]),
     "unet_warp_sweeps": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp]),
     "unet_warp_finish": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]),
+    "unet_geodesic_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "unet_geodesic_init": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]),
+    "unet_geodesic_sweeps": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_int, vp, C.c_int, vp, vp]),
+    "unet_geodesic_finish": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_longlong, vp, vp, vp, vp, vp, vp]),
     "unet_carve_borders":(C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp]),
     "unet_crop_counts_scratch_bytes": (C.c_size_t, [C.c_int] * 5),
     "unet_crop_counts": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),

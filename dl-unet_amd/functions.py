@@ -11,6 +11,8 @@ quote (Ronneberger et al. 2015, Table 1, ISBI 2012): nearest-cell growth of an i
 table of two instance maps on ground-truth foreground (unet_partition_pairs), and the Rand and information scores formed from it.
 warp_labels and warping_error add that table's third column: the topology-preserving warp of a ground-truth mask towards a
 prediction (unet_warp_init / unet_warp_sweeps / unet_warp_finish) and the disagreement it leaves.
+split_cells is the instance post-processing after label_cells: seeds grown back inside a mask along 4-neighbour steps until two
+growths meet (unet_geodesic_init / unet_geodesic_sweeps / unet_geodesic_finish), which splits touching cells.
 """
 import collections
 import fractions
@@ -409,6 +411,80 @@ def warping_error(pred_mask, gt_mask, *, reach=None, mask=None, connectivity=4):
     regions = label_cells(c.mismatch_map)[1].cpu().numpy().astype(np.int64)
     return WarpScores(warping_error=err, mismatch=c.mismatch, mismatch_before=c.mismatch_before, flips=c.flips, sweeps=c.sweeps,
                       error_regions=regions, warping_error_mean=np.float64(err.mean()))
+
+
+SplitInfo = collections.namedtuple("SplitInfo", "seeds_outside unreached max_distance launches")
+
+
+def split_cells(seeds, mask, *, max_steps=None, orphans='drop', return_distance=False, _launches=8):
+    """Seeded geodesic growth inside a mask: split touching cells by growing seeds (confident cores, e.g.
+    label_cells(fg_prob >= high)[0]) back inside the mask until two growths meet.  seeds: int32 / int64 ids [H,W] or [B,H,W] on a
+    HIP device, 0 = no seed, ids in [1, 2^24), not necessarily consecutive or connected; mask: the same shape, of any dtype
+    _int_code takes, the region is mask != 0.  g(p) is the least number of 4-neighbour steps from a seed pixel to p along region
+    pixels (0 on a seed pixel).  A region pixel with g(p) <= max_steps takes the id of the seed pixel at distance g(p), the smallest
+    id among those at that distance (grow_cells' tie rule with the geodesic metric); every other pixel gets 0: pixels outside the
+    region (a seed pixel there is no seed), pixels no seed reaches, pixels beyond max_steps.  max_steps None: unlimited; 0: the
+    seeds restricted to the mask.  orphans='keep': what is left of the mask, the 4-connected components of
+    {mask != 0 and labels == 0}, gets the ids n0[b] + 1, ... in label_cells' raster order per image, n0[b] the largest seed id of
+    image b, so a cell without a seed stays a cell (label_cells and a select; the counts below are taken before it).
+    Returns (labels, SplitInfo) or, with return_distance, (labels, SplitInfo, dist): labels int32 of the input's shape; dist
+    int32, g(p) where the growth gave an id and -1 elsewhere; SplitInfo(seeds_outside, unreached, max_distance, launches):
+    int64 numpy [B], the seed pixels outside the region, the region pixels the growth left 0 and the largest g(p) written, and
+    the launches the growth needed, the final one that changed nothing included.
+    Exact, on the device (unet_geodesic_init / unet_geodesic_sweeps / unet_geodesic_finish): _launches launches are enqueued,
+    their change counts read back in one copy, and the loop ends at the first launch that changed nothing; _launches changes no
+    result.  This is no watershed on intensities, and growth is 4-connected.  Unequal shapes, max_steps < 0, a bad orphans,
+    negative ids and ids >= 2^24 raise ValueError; host tensors raise NotImplementedError (no CPU path)."""
+    if not (torch.is_tensor(seeds) and torch.is_tensor(mask)):
+        raise NotImplementedError("split_cells takes tensors on the HIP device (unet_geodesic_init); there is no CPU implementation")
+    if seeds.shape != mask.shape or seeds.dim() not in (2, 3):
+        raise ValueError("split_cells takes seeds and a mask of equal shape [H,W] or [B,H,W], got %s, %s" % (tuple(seeds.shape), tuple(mask.shape)))
+    if seeds.dtype not in (torch.int32, torch.int64):
+        raise ValueError("split_cells takes int32 or int64 seed ids, got %s" % seeds.dtype)
+    if orphans not in ('drop', 'keep'):
+        raise ValueError("split_cells: orphans must be 'drop' or 'keep', got %r" % (orphans,))
+    if max_steps is None or max_steps == math.inf:
+        steps = -1
+    else:
+        if not max_steps >= 0:
+            raise ValueError("split_cells: max_steps must be None or a number >= 0, got %r" % (max_steps,))
+        steps = min(int(math.floor(max_steps)), 1 << 40)
+    if int(_launches) < 1:
+        raise ValueError("split_cells: _launches must be >= 1")
+    sd, mk = _planes("split_cells", seeds), _planes("split_cells", mask)
+    _device_only("split_cells", "unet_geodesic_init", seeds, mask)
+    import _hip
+    _id_range("split_cells", sd)
+    sd = sd.int()
+    mk, code = _int_code(mk, uint8_ok=True)
+    B, H, W = sd.shape
+    dev = sd.device
+    counts = torch.empty(3, B, dtype=torch.int32, device=dev)          # the library's u32 words: at most H * W < 2^31
+    status = torch.empty(B, dtype=torch.int64, device=dev)
+    scratch = _hip.scratch("unet_geodesic", dev, B, H, W)
+    _hip.run("unet_geodesic_init", dev, _hip.ptr(sd), _hip.ptr(mk), code, B, H, W, _hip.ptr(counts[0]), _hip.ptr(status), _hip.ptr(scratch))
+    launches = 0
+    while True:
+        slots = torch.empty(_launches, B, dtype=torch.int32, device=dev)
+        _hip.run("unet_geodesic_sweeps", dev, B, H, W, steps, _launches, _hip.ptr(slots), 0, _hip.ptr(scratch))
+        idle = ~slots.cpu().numpy().any(axis=1)
+        if idle.any():                                                  # a launch that changed nothing: so did all after it
+            launches += int(np.argmax(idle)) + 1
+            break
+        launches += _launches
+    labels = torch.empty(B, H, W, dtype=torch.int32, device=dev)
+    dist = torch.empty(B, H, W, dtype=torch.int32, device=dev) if return_distance else None
+    _hip.run("unet_geodesic_finish", dev, B, H, W, steps, _hip.ptr(labels), _hip.ptr(dist), _hip.ptr(counts[1]), _hip.ptr(counts[2]),
+             _hip.ptr(scratch))
+    if orphans == 'keep':
+        rest, _ = label_cells((mk != 0) & (labels == 0))
+        n0 = sd.amax(dim=(1, 2)).view(B, 1, 1)
+        labels = torch.where(rest > 0, rest + n0, labels)
+    outside, unreached, far = counts.cpu().numpy().astype(np.int64)
+    single = seeds.dim() == 2
+    info = SplitInfo(seeds_outside=outside, unreached=unreached, max_distance=far, launches=launches)
+    out = (labels[0] if single else labels, info)
+    return out + ((dist[0] if single else dist),) if return_distance else out
 
 
 def class_balance(gt_batch):

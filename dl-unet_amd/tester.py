@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 import _hip
-from functions import evaluation_metrics, label_cells, metrics_from_counts
+from functions import evaluation_metrics, label_cells, metrics_from_counts, split_cells
 import optim as hip_optim
 
 TILE_MARGIN = 92        # context each side of a tile's output that the valid convolutions eat: (S - So) / 2
@@ -197,7 +197,16 @@ def _view_chunks(n_views, Tv, nb):
         yield t0, n, segs
 
 
-def segment(unet, images, tile_size=None, max_batch=16, normalise=True, return_probs=False, return_instances=False, views=None):
+def split_instances(mask, fg_prob, high):
+    """The instance map of a foreground mask with touching cells split: the cores label_cells(fg_prob >= high)[0] are the seeds,
+    functions.split_cells grows them back inside mask != 0 until two growths meet, and a component of the mask without a core
+    stays a cell (orphans='keep').  mask and fg_prob [H,W] or [B,H,W] on a HIP device; returns int32 ids of the same shape."""
+    seeds = label_cells(fg_prob >= high)[0]
+    return split_cells(seeds, mask, orphans='keep')[0]
+
+
+def segment(unet, images, tile_size=None, max_batch=16, normalise=True, return_probs=False, return_instances=False, views=None,
+            split=None):
     """Segment images of any size and shape with the overlap-tile strategy; returns the int64 argmax mask of the same
     shape as `images` (and the float32 foreground probability softmax(logits)[1] with return_probs).  A K-class net
     (Unet(n_classes=K), K > 2) gives the K-way argmax (ties -> the lowest class) and, with return_probs, the softmax of all
@@ -222,6 +231,10 @@ def segment(unet, images, tile_size=None, max_batch=16, normalise=True, return_p
         The sum runs in the order of the codes and is deterministic.  views=(0,) gives the probabilities of views=None bit for
         bit; its mask is prob > 0.5 and not l1 > l0, which differ only where prob == 0.5 exactly (logit differences below
         about 6e-8, where 1 + exp(l0 - l1) rounds to 2).
+    split: None, or a float in (0, 1] (needs return_instances, else ValueError): the instance map becomes
+        split_instances(mask, fg_prob, split), touching cells split by growing the cores fg_prob >= split back inside the mask
+        (functions.split_cells), on the same stream after the last stitch.  fg_prob is the foreground probability of the call:
+        prob for K = 2, 1 - prob[:, 0] for K > 2 (allocated internally without return_probs; the mask does not depend on it).
     Geometry and mirroring: tile_grid."""
     if not images.is_cuda:
         raise RuntimeError("segment: the HIP path needs the images on a HIP device (got %s); there is no CPU fallback - "
@@ -239,6 +252,11 @@ def segment(unet, images, tile_size=None, max_batch=16, normalise=True, return_p
         raise ValueError("segment: empty batch")
     if max_batch < 1:
         raise ValueError("segment: max_batch must be >= 1")
+    if split is not None:
+        if not return_instances:
+            raise ValueError("segment: split needs return_instances=True")
+        if isinstance(split, bool) or not isinstance(split, (int, float)) or not 0 < split <= 1:
+            raise ValueError("segment: split must be None or a number in (0, 1], got %r" % (split,))
     vs = None if views is None else parse_views(views)
     S = auto_tile_size(H, W) if tile_size is None else int(tile_size)
     _check_tile_size(S)
@@ -270,7 +288,7 @@ def segment(unet, images, tile_size=None, max_batch=16, normalise=True, return_p
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         mask = torch.empty(B, H, W, dtype=torch.int64, device=dev)
         prob = None
-        if return_probs or vs is not None:
+        if return_probs or vs is not None or split is not None:
             prob = torch.empty((B, H, W) if K == 2 else (B, K, H, W), dtype=torch.float32, device=dev)
         st = _hip.stream(dev)
         for t0, n, segs in (_view_chunks(len(vs), B * ny * nx, nb) if vs is not None else ()):
@@ -298,7 +316,10 @@ def segment(unet, images, tile_size=None, max_batch=16, normalise=True, return_p
             else:
                 _hip.check(L.unet_tile_stitch_k(_hip.ptr(logits), So, K, oy0, ox0, ny, nx, t0, n, B, H, W, _hip.ptr(mask),
                                                 _hip.ptr(prob), st), "unet_tile_stitch_k")
-        inst = label_cells(mask)[0] if return_instances else None
+        if split is not None:
+            inst = split_instances(mask, prob if K == 2 else 1 - prob[:, 0], float(split))
+        else:
+            inst = label_cells(mask)[0] if return_instances else None
     if single:
         mask = mask[0]
         prob = prob[0] if return_probs else None

@@ -402,6 +402,39 @@ int unet_warp_sweeps(void *state_u8, int B, int H, int W, int passes_per_launch,
                      void *scratch, void *stream);
 int unet_warp_finish(const void *state_u8, int B, int H, int W, int connectivity, void *warped_i32, void *mismatch_map_f32,
                      void *mismatch_u32, void *stream);
+/* Seeded geodesic growth inside a mask: split touching cells by growing confident cores back inside the mask until two growths
+ * meet (functions.split_cells, tester.split_instances; the definition in full: DESIGN.md section 4n).  The region is mask != 0.
+ * g(p) is the least number of 4-neighbour steps from a seed pixel to p along region pixels, 0 on a seed pixel.  A region pixel
+ * with g(p) <= max_steps takes the id of the seed pixel at distance g(p), the smallest id among those at that distance (the tie
+ * rule of unet_grow_labels with the geodesic metric); every other pixel, a seed pixel outside the region included, gets 0.
+ * max_steps < 0: unlimited; 0: the seeds restricted to the region.  Three calls, all on one stream, none of which synchronises:
+ *   unet_geodesic_init    seeds_i32 [B,H,W], 0 = no seed, ids in [1, 2^24); mask [B,H,W] of dtype 0 = int64, 1 = float32,
+ *                         2 = int32, 3 = uint8.  Writes one 64-bit key per pixel into the scratch (distance << 24 | id, or a code
+ *                         for "outside the region" or "region, not reached yet": the mask is not read again).
+ *                         seeds_outside_u32 [B] = the seed pixels outside the region; status_u64 [B] = the pixels whose seed id is
+ *                         outside [0, 2^24): such a value indexes nothing, is no seed and is in neither count above.
+ *   unet_geodesic_sweeps  enqueues n_launches launches.  In each, a workgroup relaxes its 64 x 64 tile, staged with a halo of one
+ *                         pixel, to local convergence and hands off to its neighbours at the kernel boundary (two key planes,
+ *                         ping-pong), so a growth needs about as many launches as its longest shortest path crosses tile borders.
+ *                         changed_out_u32 [slots][B]: launch l of the call first clears, then fills slot first_slot + l:
+ *                         [b] = the pixels of image b whose key that launch lowered; other slots are untouched.  A launch that
+ *                         changes nothing leaves the state as it is, and so does every launch after it: the caller reads the slots
+ *                         back and stops at the first that is all 0.  max_steps >= 0 prunes keys beyond it and changes no key
+ *                         with a distance <= max_steps; pass the same value to unet_geodesic_finish.
+ *   unet_geodesic_finish  out_i32 [B,H,W] = the ids; dist_i32 [B,H,W] (may be NULL) = g(p), -1 where out is 0;
+ *                         unreached_u32 [B] = the region pixels with out = 0; max_dist_u32 [B] = the largest g written, 0 when
+ *                         there is none.
+ * Exact integers throughout: any order of relaxation reaches the same fixed point.  Limits as unet_grow_labels (H * W < 2^31,
+ * H, W, B <= 65535), H != W allowed, down to 1 x 1.
+ * scratch: unet_geodesic_scratch_bytes(B, H, W), the same buffer for the three calls of one growth (the two key planes; 16 bytes
+ * per pixel), initialised by unet_geodesic_init.                                                                            */
+size_t unet_geodesic_scratch_bytes(int B, int H, int W);
+int unet_geodesic_init(const void *seeds_i32, const void *mask, int mask_dtype, int B, int H, int W, void *seeds_outside_u32,
+                       void *status_u64, void *scratch, void *stream);
+int unet_geodesic_sweeps(int B, int H, int W, long long max_steps, int n_launches, void *changed_out_u32, int first_slot, void *scratch,
+                         void *stream);
+int unet_geodesic_finish(int B, int H, int W, long long max_steps, void *out_i32, void *dist_i32, void *unreached_u32, void *max_dist_u32,
+                         void *scratch, void *stream);
 /* Carved training targets from an instance image, replaces preprocess_gt (data.py:195-221: per cell, cv.dilate with a 5 x 5
  * rectangle, iterations=2, and 255 added on the ring the cell gained) and the cv.threshold(gt, 0, 255, THRESH_BINARY) after it
  * (data.py:64, :163).  ids [B,H,W], dtype 0 = int64, 1 = float32 holding integral values, 2 = int32 (what
