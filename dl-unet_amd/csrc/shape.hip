@@ -1,0 +1,397 @@
+// shape.hip — seeds from the shape of a mask alone (functions.distance_map, functions.reconstruct, functions.shape_seeds: the
+// distance map of the region, its h-maxima, and the domes that are left as seeds for functions.split_cells), batched, on the
+// device.  Integers throughout.  DESIGN.md section 4o has the definitions in full.
+//
+// The distance map.  d2(p) is the exact squared Euclidean distance from a region pixel (mask != 0) to the nearest pixel outside
+// the region, 0 outside it.  edge 0 ('ignore'): there is nothing past the image, and an image without a pixel outside the region
+// gets H^2 + W^2 everywhere; edge 1 ('background'): every pixel past the image is outside the region.
+//   1. dm_cols   grow.hip's column pass without ids: a downward and an upward sweep leave g, the row distance to the nearest pixel
+//                of the column outside the region (DM_FAR when the column has none; with edge 1 the pixels above row 0 and below
+//                row H - 1 count).  A sweep is a chain of H dependent steps, so a column is cut into four segments, one wave each:
+//                every thread first finds the first and last outside row of its segment (independent loads), the segments swap
+//                them through LDS, and each sweeps its rows from the distance its neighbours hand it
+//   2. dm_rows   one thread per pixel: d2 = min over x' of g(x')^2 + (x - x')^2, by a scan outwards from x' = x that ends once
+//                dx^2 reaches the running minimum (every column further out offers at least dx^2).  The minimum starts at g(x)^2,
+//                with edge 1 at min(g(x)^2, (x + 1)^2, (W - x)^2), so a pixel at distance d looks at about 2 d columns.  There is
+//                no id and no tie rule here, which is what grow_rows' brute force is for.
+//
+// Grey reconstruction by dilation, 4-connected: R is the least function on the region with R >= min(marker, under), R <= under and
+// R(p) >= min(under(p), R(n)) for every region 4-neighbour n, i.e. the fixed point of
+//      R(p) <- min(under(p), max(R(p), max over the 4-neighbours n of R(n)))        started at R = min(marker, under).
+// Values only rise, every value ever held is a lower bound of the result (it is min(marker(q), under along a real path from q)),
+// and a state that nothing raises satisfies the three conditions, so it is the least such function: any order of relaxation is
+// exact.  Pixels outside the region and past the image hold -1 in both planes: they offer nothing (every region value is >= 0)
+// and take nothing (min(-1, .) = -1), so the relaxation has no case distinction and the mask is read once.
+//   1. rc_init    R = base = min(marker, under) and under, -1 outside the region; counts the values outside [0, 2^30]
+//   2. rc_sweep   geo.hip's sweep with a max in place of its min: a workgroup owns a 64 x 64 tile, stages R and under with a halo of
+//                 one pixel in LDS and relaxes the tile to local convergence, a row phase (a thread owns 16 consecutive pixels of a
+//                 row and sweeps them forward and back in registers) then a column phase, until neither raised a value.  Within a
+//                 phase every thread reads, all wait, then the threads that raised a value store it.  Only the owned tile is
+//                 written, from plane A to plane B; the owned pixels that rose are added to changed[slot][b], one add per wave.
+//   3. rc_finish  R with 0 outside the region, and the pixels with R > base per image
+//
+// The element-wise steps of shape_seeds: sh_heights (q = floor(16 sqrt(d2)) exactly, and q + hq), sh_lower (max(v - c, 0)),
+// sh_maxima (1.0 where r2 < r1 and r1 >= a floor, else 0.0: a mask unet_label_components takes).
+//
+// Coherence (wmap.hip's rule): every kernel reads what an earlier kernel wrote; rc_sweep writes a plane no workgroup of the launch
+// reads; in dm_cols a thread re-reads only its own column.  The counters are only touched by agent-scope adds.
+#include "elem.hpp"
+#include <cmath>
+#include "../../include/unet_hip.h"
+
+namespace unet {
+
+static constexpr int DM_EDGE = 32767;                          // H, W <= DM_EDGE: H^2 + W^2 < 2^31
+static constexpr int DM_FAR = 46340;                           // "no pixel outside the region in this column": DM_FAR^2 is above
+                                                               // every H^2 + W^2 and DM_FAR^2 + dx^2 < 2^32
+static constexpr unsigned DM_FAR2 = (unsigned)DM_FAR * DM_FAR;
+static constexpr int DM_SEGS = 4;                              // row segments of a column, one wave each, in dm_cols
+static constexpr int RC_TILE = 64;                             // owned pixels per side of a workgroup's tile
+static constexpr int RC_SEG = 16;                              // pixels of a row / column one thread owns: 64 lines x 4 segments
+static constexpr int RC_STAGED = RC_TILE + 2;                  // the tile and its halo
+static constexpr int RC_PITCH = RC_STAGED + 1;                 // LDS row pitch in words (67): 32 lanes on 32 rows, no bank twice
+static constexpr int RC_TOP = 1 << 30;                         // values are in [0, RC_TOP]
+
+template <typename T>
+__global__ __launch_bounds__(256) void dm_cols_kernel(const T *__restrict__ mask, int H, int W, int edge, int *__restrict__ g)
+{
+    __shared__ int first[DM_SEGS][64], last[DM_SEGS][64];      // per segment and column: its first and last row outside the region
+    const int lane = threadIdx.x & 63, seg = threadIdx.x >> 6;
+    const int x = blockIdx.x * 64 + lane;
+    const bool live = x < W;
+    const int rows = (H + DM_SEGS - 1) / DM_SEGS, y0 = min(seg * rows, H), y1 = min(y0 + rows, H);
+    const size_t o = (size_t)blockIdx.y * H * W + (live ? x : 0);
+    const T *M = mask + o;
+    int *G = g + o;
+    int lo = -1, hi = -1;
+    if (live) {
+#pragma unroll 8
+        for (int y = y0; y < y1; ++y) {                        // no value depends on the one before: the loads overlap
+            const bool out = M[(size_t)y * W] == 0;
+            lo = out && lo < 0 ? y : lo;
+            hi = out ? y : hi;
+        }
+    }
+    first[seg][lane] = lo;
+    last[seg][lane] = hi;
+    __syncthreads();
+    if (!live) return;
+    int d = edge ? y0 : DM_FAR;                                // the distance in row y0 - 1: edge 1 has row -1 outside the region
+    for (int s = seg - 1; s >= 0; --s)
+        if (last[s][lane] >= 0) { d = y0 - 1 - last[s][lane]; break; }
+#pragma unroll 8
+    for (int y = y0; y < y1; ++y) {                            // downward: the nearest pixel outside the region at or above y
+        d = M[(size_t)y * W] == 0 ? 0 : d >= DM_FAR ? DM_FAR : d + 1;
+        G[(size_t)y * W] = d;
+    }
+    d = edge ? H - y1 : DM_FAR;                                // the distance in row y1: edge 1 has row H outside the region
+    for (int s = seg + 1; s < DM_SEGS; ++s)
+        if (first[s][lane] >= 0) { d = first[s][lane] - y1; break; }
+#pragma unroll 8
+    for (int y = y1 - 1; y >= y0; --y) {                       // upward: the nearest at or below y, merged with the word above
+        const int dn = G[(size_t)y * W];                       // this thread's own store
+        d = dn == 0 ? 0 : d >= DM_FAR ? DM_FAR : d + 1;
+        G[(size_t)y * W] = min(dn, d);
+    }
+}
+
+__global__ __launch_bounds__(256) void dm_rows_kernel(const int *__restrict__ g, int H, int W, int edge, int *__restrict__ d2)
+{
+    const int x = blockIdx.x * 256 + threadIdx.x;
+    if (x >= W) return;
+    const size_t row = ((size_t)blockIdx.z * H + blockIdx.y) * W;
+    const int *G = g + row;
+    const unsigned own = (unsigned)G[x];
+    unsigned best = own * own;
+    if (edge) {                                                // the columns -1 and W
+        const unsigned l = (unsigned)(x + 1), r = (unsigned)(W - x);
+        best = min(best, min(l * l, r * r));
+    }
+    for (int dx = 1; ; ++dx) {
+        const unsigned dd = (unsigned)dx * dx;
+        const int l = x - dx, r = x + dx;
+        if (dd >= best || (l < 0 && r >= W)) break;            // every column further out offers at least dd
+        if (l >= 0) { const unsigned v = (unsigned)G[l]; best = min(best, v * v + dd); }
+        if (r < W) { const unsigned v = (unsigned)G[r]; best = min(best, v * v + dd); }
+    }
+    d2[row + x] = best >= DM_FAR2 ? H * H + W * W : (int)best; // no pixel outside the region in the whole image
+}
+
+__device__ __forceinline__ long long rc_value(const void *p, int dtype, size_t e)
+{
+    return dtype == 0 ? ((const long long *)p)[e] : (long long)((const int *)p)[e];
+}
+
+__global__ __launch_bounds__(256) void rc_init_kernel(const void *__restrict__ marker, int marker_dtype, const void *__restrict__ under,
+                                                      int under_dtype, const void *__restrict__ mask, int mask_dtype, size_t npx,
+                                                      int *__restrict__ r, int *__restrict__ u, int *__restrict__ base,
+                                                      unsigned long long *status)
+{
+    const size_t img = (size_t)blockIdx.y * npx;
+    unsigned bad = 0;
+    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < npx; e += (size_t)gridDim.x * blockDim.x) {
+        long long m = rc_value(marker, marker_dtype, img + e), v = rc_value(under, under_dtype, img + e);
+        const bool m_bad = m < 0 || m > RC_TOP, v_bad = v < 0 || v > RC_TOP;
+        bad += m_bad || v_bad;
+        m = m_bad ? 0 : m;                                     // such a value counts as 0
+        v = v_bad ? 0 : v;
+        const bool region = !mask || mask_on(mask, mask_dtype, img + e);
+        const int start = region ? (int)(m < v ? m : v) : -1;
+        r[img + e] = start;
+        base[img + e] = start;
+        u[img + e] = region ? (int)v : -1;
+    }
+    bad = block_sum256(bad);
+    if (threadIdx.x == 0 && bad)
+        __hip_atomic_fetch_add(&status[blockIdx.y], (unsigned long long)bad, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// the RC_SEG pixels p[k * ALONG] of one line under the ceilings u[k * ALONG], relaxed forward (from the pixel before and the two
+// ACROSS) and backward (from the pixel after) in registers: v[k] is the value after both, bit k of the result says that it rose
+template <int ALONG, int ACROSS>
+__device__ __forceinline__ unsigned rc_relax_line(const int *p, const int *u, int (&v)[RC_SEG])
+{
+    unsigned rose = 0;
+    int top[RC_SEG];
+    int run = p[-ALONG];
+#pragma unroll
+    for (int k = 0; k < RC_SEG; ++k) {
+        const int own = p[k * ALONG], a = p[k * ALONG - ACROSS], b = p[k * ALONG + ACROSS];
+        top[k] = u[k * ALONG];
+        const int c = min(top[k], max(max(a, b), run));
+        rose |= (unsigned)(c > own) << k;
+        run = v[k] = max(own, c);
+    }
+    run = p[RC_SEG * ALONG];
+#pragma unroll
+    for (int k = RC_SEG - 1; k >= 0; --k) {
+        const int c = min(top[k], run);
+        rose |= (unsigned)(c > v[k]) << k;
+        run = v[k] = max(v[k], c);
+    }
+    return rose;
+}
+
+template <int ALONG>
+__device__ __forceinline__ void rc_store_line(int *p, unsigned rose, const int (&v)[RC_SEG])
+{
+#pragma unroll
+    for (int k = 0; k < RC_SEG; ++k)
+        if (rose >> k & 1) p[k * ALONG] = v[k];
+}
+
+__global__ __launch_bounds__(256) void rc_sweep_kernel(const int *__restrict__ src, const int *__restrict__ under, int *__restrict__ dst,
+                                                       int H, int W, unsigned *changed)
+{
+    __shared__ int s[RC_STAGED * RC_PITCH], su[RC_STAGED * RC_PITCH];                // 2 x 17.3 KiB
+    const int t = threadIdx.x, b = blockIdx.z;
+    const int oy = blockIdx.y * RC_TILE, ox = blockIdx.x * RC_TILE;
+    const int OH = min(H, oy + RC_TILE) - oy, OW = min(W, ox + RC_TILE) - ox;
+    const size_t img = (size_t)b * H * W;
+    for (int i = t; i < RC_STAGED * RC_STAGED; i += 256) {                           // the whole staged square: past the image -1,
+        const int ly = i / RC_STAGED, lx = i - ly * RC_STAGED;                       // which never changes
+        const int gy = oy - 1 + ly, gx = ox - 1 + lx;
+        const bool in = gy >= 0 && gy < H && gx >= 0 && gx < W;
+        const size_t e = img + (size_t)gy * W + gx;
+        s[ly * RC_PITCH + lx] = in ? src[e] : -1;
+        su[ly * RC_PITCH + lx] = in ? under[e] : -1;
+    }
+    __syncthreads();
+
+    const int line = t & 63, seg = (t >> 6) * RC_SEG;
+    const int row = (1 + line) * RC_PITCH + 1 + seg, col = (1 + seg) * RC_PITCH + 1 + line;
+    int v[RC_SEG];
+    for (;;) {                                                                       // values only rise, under is a ceiling: it ends
+        const unsigned in_rows = rc_relax_line<1, RC_PITCH>(s + row, su + row, v);
+        __syncthreads();                                                             // every read of the phase is done
+        rc_store_line<1>(s + row, in_rows, v);
+        __syncthreads();
+        const unsigned in_cols = rc_relax_line<RC_PITCH, 1>(s + col, su + col, v);
+        __syncthreads();
+        rc_store_line<RC_PITCH>(s + col, in_cols, v);
+        if (!__syncthreads_or((in_rows | in_cols) != 0)) break;                      // the tile is at its fixed point
+    }
+
+    unsigned n = 0;
+    for (int i = t; i < OH * OW; i += 256) {
+        const int y = i / OW, x = i - y * OW;
+        const size_t e = img + (size_t)(oy + y) * W + ox + x;
+        const int k = s[(1 + y) * RC_PITCH + 1 + x];
+        n += k > src[e];
+        dst[e] = k;
+    }
+    n = wave_sum(n);
+    if ((t & 63) == 0 && n) __hip_atomic_fetch_add(&changed[b], n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__global__ __launch_bounds__(256) void rc_finish_kernel(const int *__restrict__ r, const int *__restrict__ base, size_t npx,
+                                                        int *__restrict__ out, unsigned *raised)
+{
+    const size_t img = (size_t)blockIdx.y * npx;
+    unsigned n = 0;
+    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < npx; e += (size_t)gridDim.x * blockDim.x) {
+        const int v = r[img + e];
+        n += v > base[img + e];
+        out[img + e] = max(v, 0);
+    }
+    n = block_sum256(n);
+    if (threadIdx.x == 0 && n) __hip_atomic_fetch_add(&raised[blockIdx.y], n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// floor(sqrt(256 d2)) = floor(16 sqrt(d2)): 256 d2 < 2^39 is exact in fp64, whose square root is at most one off
+__device__ __forceinline__ int sh_isqrt256(int d2)
+{
+    const long long v = 256ll * d2;
+    long long q = (long long)sqrt((double)v);
+    q -= q * q > v;
+    q += (q + 1) * (q + 1) <= v;
+    return (int)q;
+}
+
+__global__ __launch_bounds__(256) void sh_heights_kernel(const int *__restrict__ d2, size_t n, int hq, int *__restrict__ q,
+                                                         int *__restrict__ lifted)
+{
+    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) {
+        const int v = sh_isqrt256(max(d2[e], 0));
+        q[e] = v;
+        if (lifted) lifted[e] = v + hq;
+    }
+}
+
+__global__ __launch_bounds__(256) void sh_lower_kernel(const int *__restrict__ in, size_t n, int c, int *__restrict__ out)
+{
+    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x)
+        out[e] = max(in[e] - c, 0);
+}
+
+__global__ __launch_bounds__(256) void sh_maxima_kernel(const int *__restrict__ r1, const int *__restrict__ r2, size_t n, int floor_q,
+                                                        float *__restrict__ out)
+{
+    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) {
+        const int v = r1[e];
+        out[e] = r2[e] < v && v >= floor_q ? 1.0f : 0.0f;
+    }
+}
+
+} // namespace unet
+
+using namespace unet;
+
+static size_t sh_plane(int B, int H, int W) { return plane_bytes(B, H, W, sizeof(int)); }
+static bool sh_sizes_ok(int B, int H, int W) { return (size_t)H * W < (1u << 31) && H <= DM_EDGE && W <= DM_EDGE && B <= 65535; }
+#define SH_SIZE_CHECK(name) ARG_CHECK(sh_sizes_ok(B, H, W), name ": image too large (H, W <= 32767, H * W < 2^31, B <= 65535)")
+
+// [g, the column distances]
+size_t unet_distance_map_scratch_bytes(int B, int H, int W)
+{
+    if (B <= 0 || H <= 0 || W <= 0) return 0;
+    return sh_plane(B, H, W);
+}
+
+int unet_distance_map(const void *mask, int mask_dtype, int B, int H, int W, int edge, void *d2_i32, void *scratch, void *stream)
+{
+    ARG_CHECK(mask && d2_i32 && scratch && B > 0 && H > 0 && W > 0, "unet_distance_map: bad argument");
+    ARG_CHECK(mask_dtype >= 0 && mask_dtype <= 3, "unet_distance_map: mask_dtype must be 0 (int64), 1 (float32), 2 (int32) or 3 (uint8)");
+    ARG_CHECK(edge == 0 || edge == 1, "unet_distance_map: edge must be 0 (ignore) or 1 (background)");
+    SH_SIZE_CHECK("unet_distance_map");
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 cols(cdiv(W, 64), B);
+    if (mask_dtype == 0) hipLaunchKernelGGL(dm_cols_kernel<long long>, cols, dim3(256), 0, st, (const long long *)mask, H, W, edge, (int *)scratch);
+    else if (mask_dtype == 1) hipLaunchKernelGGL(dm_cols_kernel<float>, cols, dim3(256), 0, st, (const float *)mask, H, W, edge, (int *)scratch);
+    else if (mask_dtype == 2) hipLaunchKernelGGL(dm_cols_kernel<int>, cols, dim3(256), 0, st, (const int *)mask, H, W, edge, (int *)scratch);
+    else hipLaunchKernelGGL(dm_cols_kernel<unsigned char>, cols, dim3(256), 0, st, (const unsigned char *)mask, H, W, edge, (int *)scratch);
+    hipLaunchKernelGGL(dm_rows_kernel, dim3(cdiv(W, 256), H, B), dim3(256), 0, st, (const int *)scratch, H, W, edge, (int *)d2_i32);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// [R plane 0, the current one between calls | R plane 1 | under | base = min(marker, under)]
+size_t unet_reconstruct_scratch_bytes(int B, int H, int W)
+{
+    if (B <= 0 || H <= 0 || W <= 0) return 0;
+    return 4 * sh_plane(B, H, W);
+}
+
+int unet_reconstruct_init(const void *marker, int marker_dtype, const void *under, int under_dtype, const void *mask, int mask_dtype, int B,
+                          int H, int W, void *status_u64, void *scratch, void *stream)
+{
+    ARG_CHECK(marker && under && status_u64 && scratch && B > 0 && H > 0 && W > 0, "unet_reconstruct_init: bad argument");
+    ARG_CHECK((marker_dtype == 0 || marker_dtype == 2) && (under_dtype == 0 || under_dtype == 2),
+              "unet_reconstruct_init: marker_dtype and under_dtype must be 0 (int64) or 2 (int32)");
+    ARG_CHECK(!mask || (mask_dtype >= 0 && mask_dtype <= 3),
+              "unet_reconstruct_init: mask_dtype must be 0 (int64), 1 (float32), 2 (int32) or 3 (uint8)");
+    SH_SIZE_CHECK("unet_reconstruct_init");
+    hipStream_t st = (hipStream_t)stream;
+    const size_t npx = (size_t)H * W, plane = sh_plane(B, H, W);
+    char *base = (char *)scratch;
+    HIP_TRY(hipMemsetAsync(status_u64, 0, (size_t)B * sizeof(unsigned long long), st));
+    hipLaunchKernelGGL(rc_init_kernel, dim3(grid_for(npx, 256, 2048), B), dim3(256), 0, st, marker, marker_dtype, under, under_dtype, mask,
+                       mask_dtype, npx, (int *)base, (int *)(base + 2 * plane), (int *)(base + 3 * plane), (unsigned long long *)status_u64);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int unet_reconstruct_sweeps(int B, int H, int W, int n_launches, void *changed_out_u32, int first_slot, void *scratch, void *stream)
+{
+    ARG_CHECK(changed_out_u32 && scratch && B > 0 && H > 0 && W > 0 && n_launches > 0 && first_slot >= 0, "unet_reconstruct_sweeps: bad argument");
+    SH_SIZE_CHECK("unet_reconstruct_sweeps");
+    hipStream_t st = (hipStream_t)stream;
+    unsigned *changed = (unsigned *)changed_out_u32 + (size_t)first_slot * B;
+    HIP_TRY(hipMemsetAsync(changed, 0, (size_t)n_launches * B * sizeof(unsigned), st));
+    const size_t bytes = sh_plane(B, H, W);
+    int *plane[2] = {(int *)scratch, (int *)((char *)scratch + bytes)};
+    const int *under = (const int *)((char *)scratch + 2 * bytes);
+    const dim3 grid(cdiv(W, RC_TILE), cdiv(H, RC_TILE), B);
+    for (int l = 0; l < n_launches; ++l)
+        hipLaunchKernelGGL(rc_sweep_kernel, grid, dim3(256), 0, st, (const int *)plane[l & 1], under, plane[~l & 1], H, W,
+                           changed + (size_t)l * B);
+    HIP_TRY(hipGetLastError());
+    if (n_launches & 1) HIP_TRY(hipMemcpyAsync(plane[0], plane[1], (size_t)B * H * W * sizeof(int), hipMemcpyDeviceToDevice, st));
+    return 0;
+}
+
+int unet_reconstruct_finish(int B, int H, int W, void *out_i32, void *raised_u32, void *scratch, void *stream)
+{
+    ARG_CHECK(out_i32 && raised_u32 && scratch && B > 0 && H > 0 && W > 0, "unet_reconstruct_finish: bad argument");
+    SH_SIZE_CHECK("unet_reconstruct_finish");
+    hipStream_t st = (hipStream_t)stream;
+    const size_t npx = (size_t)H * W;
+    HIP_TRY(hipMemsetAsync(raised_u32, 0, (size_t)B * sizeof(unsigned), st));
+    hipLaunchKernelGGL(rc_finish_kernel, dim3(grid_for(npx, 1024, 512), B), dim3(256), 0, st, (const int *)scratch,
+                       (const int *)((char *)scratch + 3 * sh_plane(B, H, W)), npx, (int *)out_i32, (unsigned *)raised_u32);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int unet_shape_heights(const void *d2_i32, int B, int H, int W, int hq, void *q_i32, void *lifted_i32, void *stream)
+{
+    ARG_CHECK(d2_i32 && q_i32 && B > 0 && H > 0 && W > 0, "unet_shape_heights: bad argument");
+    ARG_CHECK(hq >= 0 && hq <= 1 << 28, "unet_shape_heights: hq must be in [0, 2^28]");
+    SH_SIZE_CHECK("unet_shape_heights");
+    const size_t n = (size_t)B * H * W;
+    hipLaunchKernelGGL(sh_heights_kernel, dim3(grid_for(n, 1024)), dim3(256), 0, (hipStream_t)stream, (const int *)d2_i32, n, hq, (int *)q_i32,
+                       (int *)lifted_i32);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int unet_shape_lower(const void *in_i32, int B, int H, int W, int c, void *out_i32, void *stream)
+{
+    ARG_CHECK(in_i32 && out_i32 && B > 0 && H > 0 && W > 0 && c >= 0, "unet_shape_lower: bad argument");
+    SH_SIZE_CHECK("unet_shape_lower");
+    const size_t n = (size_t)B * H * W;
+    hipLaunchKernelGGL(sh_lower_kernel, dim3(grid_for(n, 1024)), dim3(256), 0, (hipStream_t)stream, (const int *)in_i32, n, c, (int *)out_i32);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int unet_shape_maxima(const void *r1_i32, const void *r2_i32, int B, int H, int W, int floor_q, void *out_f32, void *stream)
+{
+    ARG_CHECK(r1_i32 && r2_i32 && out_f32 && B > 0 && H > 0 && W > 0, "unet_shape_maxima: bad argument");
+    SH_SIZE_CHECK("unet_shape_maxima");
+    const size_t n = (size_t)B * H * W;
+    hipLaunchKernelGGL(sh_maxima_kernel, dim3(grid_for(n, 1024)), dim3(256), 0, (hipStream_t)stream, (const int *)r1_i32, (const int *)r2_i32, n,
+                       floor_q, (float *)out_f32);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}

@@ -13,6 +13,9 @@ warp_labels and warping_error add that table's third column: the topology-preser
 prediction (unet_warp_init / unet_warp_sweeps / unet_warp_finish) and the disagreement it leaves.
 split_cells is the instance post-processing after label_cells: seeds grown back inside a mask along 4-neighbour steps until two
 growths meet (unet_geodesic_init / unet_geodesic_sweeps / unet_geodesic_finish), which splits touching cells.
+distance_map, reconstruct and shape_seeds give it seeds from the shape of the mask alone: the exact interior distance map
+(unet_distance_map), grey reconstruction by dilation (unet_reconstruct_init / unet_reconstruct_sweeps / unet_reconstruct_finish),
+and the h-maxima of the distance map with a minimum radius, labelled (unet_shape_heights / unet_shape_lower / unet_shape_maxima).
 """
 import collections
 import fractions
@@ -485,6 +488,140 @@ def split_cells(seeds, mask, *, max_steps=None, orphans='drop', return_distance=
     info = SplitInfo(seeds_outside=outside, unreached=unreached, max_distance=far, launches=launches)
     out = (labels[0] if single else labels, info)
     return out + ((dist[0] if single else dist),) if return_distance else out
+
+
+_EDGES = {'ignore': 0, 'background': 1}
+SHAPE_EDGE = 32767                                                     # H, W of the shape ops: H^2 + W^2 fits int32
+
+
+def _shape_sizes(name, B, H, W):
+    if H > SHAPE_EDGE or W > SHAPE_EDGE or H * W >= 1 << 31 or B > 65535:
+        raise ValueError("%s: H and W are at most %d with H * W < 2^31 (a squared distance is an int32) and B at most 65535, got %s"
+                         % (name, SHAPE_EDGE, (B, H, W)))
+
+
+def distance_map(mask, *, edge='ignore'):
+    """The exact squared Euclidean distance map of the interior of a mask [H,W] or [B,H,W] on a HIP device (the region is
+    mask != 0, of any dtype split_cells takes): int32 of the mask's shape, d2(p) = the squared distance from region pixel p to the
+    nearest pixel outside the region, 0 outside the region.  edge='ignore': pixels beyond the image are nothing
+    (scipy.ndimage.distance_transform_edt's convention), and an image with no pixel outside the region gets H^2 + W^2 everywhere,
+    above every real value (at most (H-1)^2 + (W-1)^2).  edge='background': pixels beyond the image are background, so the pixel in
+    row y, column x is at distance min(x+1, W-x, y+1, H-y) from it.  On the device (unet_distance_map), nothing is read back.
+    H or W above 32767 or H*W >= 2^31 and a bad edge raise ValueError; host tensors raise NotImplementedError (no CPU path)."""
+    if not torch.is_tensor(mask):
+        raise NotImplementedError("distance_map takes a tensor on the HIP device (unet_distance_map); there is no CPU implementation")
+    if edge not in _EDGES:
+        raise ValueError("distance_map: edge must be 'ignore' or 'background', got %r" % (edge,))
+    mk = _planes("distance_map", mask)
+    B, H, W = mk.shape
+    _shape_sizes("distance_map", B, H, W)
+    _device_only("distance_map", "unet_distance_map", mask)
+    import _hip
+    mk, code = _int_code(mk, uint8_ok=True)
+    d2 = torch.empty(B, H, W, dtype=torch.int32, device=mk.device)
+    scratch = _hip.scratch("unet_distance_map", mk.device, B, H, W)
+    _hip.run("unet_distance_map", mk.device, _hip.ptr(mk), code, B, H, W, _EDGES[edge], _hip.ptr(d2), _hip.ptr(scratch))
+    return d2[0] if mask.dim() == 2 else d2
+
+
+ReconInfo = collections.namedtuple("ReconInfo", "launches raised")
+RECON_TOP = 1 << 30
+
+
+def reconstruct(marker, under, *, mask=None, _launches=8):
+    """Grey reconstruction by dilation, 4-connected, on integers: marker and under int32 / int64 [H,W] or [B,H,W] on a HIP device
+    with values in [0, 2^30]; the region is mask != 0 (the same shape, of any dtype split_cells takes), everything when mask is
+    None.  R is the least function on the region with R >= min(marker, under), R <= under and R(p) >= min(under(p), R(n)) for
+    every region 4-neighbour n; equivalently R(p) is the maximum over region pixels q of min(marker(q), the minimum of under along
+    the best 4-path from q to p inside the region).  Outside the region R is 0.  Returns (R, ReconInfo): R int32 of the input's
+    shape; ReconInfo(launches, raised): the launches the reconstruction needed, the final one that raised nothing included
+    (counted as SplitInfo.launches is), and raised int64 numpy [B], the pixels whose final value exceeds min(marker, under).
+    Exact, on the device (unet_reconstruct_init / unet_reconstruct_sweeps / unet_reconstruct_finish): _launches launches are
+    enqueued, their change counts read back in one copy, and the loop ends at the first launch that raised nothing; _launches
+    changes no result.  Unequal shapes, other dtypes, values outside [0, 2^30] (counted by the kernel), H or W above 32767 raise
+    ValueError; host tensors raise NotImplementedError (no CPU path)."""
+    tensors = [marker, under] + ([] if mask is None else [mask])
+    if any(not torch.is_tensor(t) for t in tensors):
+        raise NotImplementedError("reconstruct takes tensors on the HIP device (unet_reconstruct_init); there is no CPU implementation")
+    if any(t.shape != marker.shape for t in tensors) or marker.dim() not in (2, 3):
+        raise ValueError("reconstruct takes marker, under and mask of equal shape [H,W] or [B,H,W], got %s"
+                         % ", ".join(str(tuple(t.shape)) for t in tensors))
+    for t in tensors[:2]:
+        if t.dtype not in (torch.int32, torch.int64):
+            raise ValueError("reconstruct takes int32 or int64 marker and under, got %s" % t.dtype)
+    if int(_launches) < 1:
+        raise ValueError("reconstruct: _launches must be >= 1")
+    planes = [_planes("reconstruct", t) for t in tensors]
+    B, H, W = planes[0].shape
+    _shape_sizes("reconstruct", B, H, W)
+    _device_only("reconstruct", "unet_reconstruct_init", *tensors)
+    import _hip
+    (mr, mr_code), (un, un_code) = _int_code(planes[0]), _int_code(planes[1])
+    mk, mk_code = _int_code(planes[2], uint8_ok=True) if mask is not None else (None, 0)
+    dev = mr.device
+    status = torch.empty(B, dtype=torch.int64, device=dev)
+    raised = torch.empty(B, dtype=torch.int32, device=dev)             # the library's u32 words: at most H * W < 2^31
+    scratch = _hip.scratch("unet_reconstruct", dev, B, H, W)
+    _hip.run("unet_reconstruct_init", dev, _hip.ptr(mr), mr_code, _hip.ptr(un), un_code, _hip.ptr(mk), mk_code, B, H, W, _hip.ptr(status),
+             _hip.ptr(scratch))
+    launches = 0
+    while True:
+        slots = torch.empty(_launches, B, dtype=torch.int32, device=dev)
+        _hip.run("unet_reconstruct_sweeps", dev, B, H, W, _launches, _hip.ptr(slots), 0, _hip.ptr(scratch))
+        if launches == 0:
+            bad = int(status.sum())
+            if bad:
+                raise ValueError("reconstruct: %d pixels hold a marker or under value outside [0, 2^30]" % bad)
+        idle = ~slots.cpu().numpy().any(axis=1)
+        if idle.any():                                                  # a launch that raised nothing: so did all after it
+            launches += int(np.argmax(idle)) + 1
+            break
+        launches += _launches
+    out = torch.empty(B, H, W, dtype=torch.int32, device=dev)
+    _hip.run("unet_reconstruct_finish", dev, B, H, W, _hip.ptr(out), _hip.ptr(raised), _hip.ptr(scratch))
+    info = ReconInfo(launches=launches, raised=raised.cpu().numpy().astype(np.int64))
+    return (out[0] if marker.dim() == 2 else out), info
+
+
+def shape_seeds(mask, h=2.0, *, min_radius=0.0, edge='ignore'):
+    """Seeds for split_cells from the shape of a mask alone: the h-maxima of its distance map.  mask [H,W] or [B,H,W] on a HIP
+    device (the region is mask != 0, of any dtype split_cells takes); returns (seeds, n): seeds int32 of the mask's shape, 0 = no
+    seed, the seeds numbered 1..n[b] in label_cells' raster order; n int32 [B].  Integers throughout: q = isqrt(256 d2) is the
+    floor of distance_map(mask, edge=edge) in 1/16 pixel, hq = round(16 h), rq = ceil(16 min_radius).  R1 is the h-maxima
+    transform of q inside the region, the reconstruction of q - hq under q; its regional maxima are the region pixels where the
+    reconstruction R2 of R1 - 1 under R1 stays below R1; a seed pixel is such a pixel with R1 + hq >= rq (on a maximal plateau
+    R1 + hq is the dome's peak, so a whole dome is kept or dropped); the seeds are label_cells of the seed pixels.  The transform
+    runs on heights lifted by hq (the reconstruction of q under q + hq, which is R1 + hq), so q - hq is never cut off at 0: inside
+    a component with a pixel above hq the cut changes nothing, and a component that lies at or below hq everywhere is one dome
+    and one seed where the cut would leave it flat at 0 and without any.
+    Consequences: two peaks merge iff the saddle between them, by the best 4-path inside the region, is >= the lower peak - h
+    (in 1/16 pixel: lower peak - saddle <= hq); h = 0 gives all regional maxima of q; every region component with max q >= rq
+    gets at least one seed.  The default h = 2: along a diagonal ridge the 4-connected staircase makes spurious maxima less than
+    1 px deep (two discs of r = 12 on a diagonal give 9 seeds at h = 0, 3 at 0.5 and 2 from 1 on).
+    On the device throughout (unet_distance_map, unet_shape_heights / _lower / _maxima, two reconstruct calls,
+    unet_label_components), on the current stream.  h < 0 or above 2^24, min_radius < 0, a bad edge and the shapes distance_map
+    refuses raise ValueError; host tensors raise NotImplementedError (no CPU path)."""
+    if not torch.is_tensor(mask):
+        raise NotImplementedError("shape_seeds takes a tensor on the HIP device (unet_distance_map); there is no CPU implementation")
+    if isinstance(h, bool) or not isinstance(h, (int, float)) or not 0 <= h <= 1 << 24:
+        raise ValueError("shape_seeds: h must be a number in [0, 2^24], got %r" % (h,))
+    if isinstance(min_radius, bool) or not isinstance(min_radius, (int, float)) or not min_radius >= 0:
+        raise ValueError("shape_seeds: min_radius must be a number >= 0, got %r" % (min_radius,))
+    hq, rq = int(round(16 * h)), int(min(math.ceil(16 * min(min_radius, 1 << 26)), 1 << 30))
+    d2 = _planes("shape_seeds", distance_map(mask, edge=edge))
+    import _hip
+    B, H, W = d2.shape
+    dev = d2.device
+    mk = _planes("shape_seeds", mask)
+    q, lifted = torch.empty_like(d2), torch.empty_like(d2)
+    _hip.run("unet_shape_heights", dev, _hip.ptr(d2), B, H, W, hq, _hip.ptr(q), _hip.ptr(lifted))
+    r1 = reconstruct(q, lifted, mask=mk)[0]
+    _hip.run("unet_shape_lower", dev, _hip.ptr(r1), B, H, W, 1, _hip.ptr(q))
+    r2 = reconstruct(q, r1, mask=mk)[0]
+    peaks = torch.empty(B, H, W, dtype=torch.float32, device=dev)
+    _hip.run("unet_shape_maxima", dev, _hip.ptr(r1), _hip.ptr(r2), B, H, W, rq, _hip.ptr(peaks))
+    seeds, n = label_cells(peaks)
+    return (seeds[0] if mask.dim() == 2 else seeds), n
 
 
 def class_balance(gt_batch):

@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 import _hip
-from functions import evaluation_metrics, label_cells, metrics_from_counts, split_cells
+from functions import evaluation_metrics, label_cells, metrics_from_counts, shape_seeds, split_cells
 import optim as hip_optim
 
 TILE_MARGIN = 92        # context each side of a tile's output that the valid convolutions eat: (S - So) / 2
@@ -205,8 +205,28 @@ def split_instances(mask, fg_prob, high):
     return split_cells(seeds, mask, orphans='keep')[0]
 
 
+def split_by_shape(mask, h=2.0, min_radius=0.0, edge='ignore'):
+    """The instance map of a foreground mask with touching cells split by their shape alone, no probabilities needed: the seeds
+    are functions.shape_seeds(mask, h, min_radius=min_radius, edge=edge)[0], the h-maxima of the mask's distance map whose peak
+    reaches min_radius; functions.split_cells grows them back inside mask != 0 until two growths meet, and a component of the mask
+    without a seed stays a cell (orphans='keep').  mask [H,W] or [B,H,W] on a HIP device; returns int32 ids of the same shape."""
+    seeds = shape_seeds(mask, h, min_radius=min_radius, edge=edge)[0]
+    return split_cells(seeds, mask, orphans='keep')[0]
+
+
+def _parse_shape_split(v):
+    """shape_split of segment -> (h, min_radius); ValueError for anything but a number >= 0 or a pair of them."""
+    def number(x):
+        return not isinstance(x, bool) and isinstance(x, (int, float)) and 0 <= x <= 1 << 24
+    if number(v):
+        return float(v), 0.0
+    if isinstance(v, (tuple, list)) and len(v) == 2 and number(v[0]) and number(v[1]):
+        return float(v[0]), float(v[1])
+    raise ValueError("segment: shape_split must be None, a number h >= 0 or a pair (h, min_radius) of numbers >= 0, got %r" % (v,))
+
+
 def segment(unet, images, tile_size=None, max_batch=16, normalise=True, return_probs=False, return_instances=False, views=None,
-            split=None):
+            shape_split=None, split=None):
     """Segment images of any size and shape with the overlap-tile strategy; returns the int64 argmax mask of the same
     shape as `images` (and the float32 foreground probability softmax(logits)[1] with return_probs).  A K-class net
     (Unet(n_classes=K), K > 2) gives the K-way argmax (ties -> the lowest class) and, with return_probs, the softmax of all
@@ -235,6 +255,10 @@ def segment(unet, images, tile_size=None, max_batch=16, normalise=True, return_p
         split_instances(mask, fg_prob, split), touching cells split by growing the cores fg_prob >= split back inside the mask
         (functions.split_cells), on the same stream after the last stitch.  fg_prob is the foreground probability of the call:
         prob for K = 2, 1 - prob[:, 0] for K > 2 (allocated internally without return_probs; the mask does not depend on it).
+    shape_split: None, a number h >= 0 or a pair (h, min_radius) (needs return_instances, not together with split, else
+        ValueError): the instance map becomes split_by_shape(mask, h, min_radius), touching cells split at the h-maxima of the
+        mask's own distance map (functions.shape_seeds, functions.split_cells), on the same stream after the last stitch.  It
+        reads the mask alone, so it works with views= as it does without.
     Geometry and mirroring: tile_grid."""
     if not images.is_cuda:
         raise RuntimeError("segment: the HIP path needs the images on a HIP device (got %s); there is no CPU fallback - "
@@ -257,6 +281,12 @@ def segment(unet, images, tile_size=None, max_batch=16, normalise=True, return_p
             raise ValueError("segment: split needs return_instances=True")
         if isinstance(split, bool) or not isinstance(split, (int, float)) or not 0 < split <= 1:
             raise ValueError("segment: split must be None or a number in (0, 1], got %r" % (split,))
+    if shape_split is not None:
+        if not return_instances:
+            raise ValueError("segment: shape_split needs return_instances=True")
+        if split is not None:
+            raise ValueError("segment: shape_split and split are two ways to seed one growth; give one of them")
+        shape_split = _parse_shape_split(shape_split)
     vs = None if views is None else parse_views(views)
     S = auto_tile_size(H, W) if tile_size is None else int(tile_size)
     _check_tile_size(S)
@@ -318,6 +348,8 @@ def segment(unet, images, tile_size=None, max_batch=16, normalise=True, return_p
                                                 _hip.ptr(prob), st), "unet_tile_stitch_k")
         if split is not None:
             inst = split_instances(mask, prob if K == 2 else 1 - prob[:, 0], float(split))
+        elif shape_split is not None:
+            inst = split_by_shape(mask, *shape_split)
         else:
             inst = label_cells(mask)[0] if return_instances else None
     if single:

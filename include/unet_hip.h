@@ -435,6 +435,53 @@ int unet_geodesic_sweeps(int B, int H, int W, long long max_steps, int n_launche
                          void *stream);
 int unet_geodesic_finish(int B, int H, int W, long long max_steps, void *out_i32, void *dist_i32, void *unreached_u32, void *max_dist_u32,
                          void *scratch, void *stream);
+/* Seeds from the shape of a mask alone: the distance map of the region, its h-maxima, the domes that are left
+ * (functions.distance_map, functions.reconstruct, functions.shape_seeds, tester.split_by_shape; the definitions in full: DESIGN.md
+ * section 4o).  The region is mask != 0; mask [B,H,W] of dtype 0 = int64, 1 = float32, 2 = int32, 3 = uint8.  None of these
+ * calls synchronises; exact integers throughout.  Limits: H, W <= 32767, H * W < 2^31, B <= 65535; H != W allowed, down to 1 x 1.
+ *
+ * unet_distance_map: d2_i32 [B,H,W] = the exact squared Euclidean distance from a region pixel to the nearest pixel outside the
+ * region, 0 outside the region.  edge 0 ("ignore", scipy.ndimage.distance_transform_edt's convention): there is nothing past the
+ * image, and an image without a pixel outside the region gets H^2 + W^2 everywhere, which is above every real value.  edge 1
+ * ("background"): every pixel past the image is outside the region, so the pixel in row y and column x is at most
+ * min(x + 1, W - x, y + 1, H - y) away from one.  A column pass and a row pass whose scan outwards ends once dx^2 reaches the
+ * running minimum.  scratch: unet_distance_map_scratch_bytes(B, H, W) (4 bytes per pixel), initialised by the call.
+ *
+ * Grey reconstruction by dilation, 4-connected: marker and under [B,H,W] of dtype 0 = int64 or 2 = int32 with values in
+ * [0, 2^30]; the region is mask != 0, every pixel when mask is NULL.  R is the least function on the region with
+ * R >= min(marker, under), R <= under and R(p) >= min(under(p), R(n)) for every region 4-neighbour n; equivalently R(p) is the
+ * maximum over region pixels q of min(marker(q), the minimum of under along the best 4-path from q to p inside the region).
+ * Three calls, all on one stream:
+ *   unet_reconstruct_init    writes R = min(marker, under) and under into the scratch, -1 outside the region (the mask is not
+ *                            read again).  status_u64 [B] = the pixels, inside the region or not, where marker or under is outside
+ *                            [0, 2^30]: such a value counts as 0.
+ *   unet_reconstruct_sweeps  enqueues n_launches launches.  In each, a workgroup relaxes its 64 x 64 tile, staged with a halo of
+ *                            one pixel, to local convergence of R <- min(under, max(R, the four neighbours)) and hands off to its
+ *                            neighbours at the kernel boundary (two planes, ping-pong).  changed_out_u32 [slots][B]: launch l of
+ *                            the call first clears, then fills slot first_slot + l: [b] = the pixels of image b that launch
+ *                            raised; other slots are untouched.  A launch that raises nothing leaves the state as it is, and so
+ *                            does every launch after it: the caller reads the slots back and stops at the first that is all 0.
+ *   unet_reconstruct_finish  out_i32 [B,H,W] = R, 0 outside the region; raised_u32 [B] = the pixels with R > min(marker, under).
+ * Values only rise and every value held is a lower bound of R: any order of relaxation reaches the same fixed point.
+ * scratch: unet_reconstruct_scratch_bytes(B, H, W), the same buffer for the three calls of one reconstruction (two planes of R,
+ * under, and min(marker, under); 16 bytes per pixel), initialised by unet_reconstruct_init.
+ *
+ * The element-wise steps of functions.shape_seeds, on int32 [B,H,W]:
+ *   unet_shape_heights  q_i32 = floor(sqrt(256 d2)), the floor of the distance in 1/16 pixel, exactly; lifted_i32 (may be NULL)
+ *                       = q + hq, 0 <= hq <= 2^28
+ *   unet_shape_lower    out_i32 = max(in - c, 0), c >= 0
+ *   unet_shape_maxima   out_f32 = 1.0 where r2 < r1 and r1 >= floor_q, else 0.0 (a mask unet_label_components takes): with
+ *                       r2 = the reconstruction of max(r1 - 1, 0) under r1, the regional maxima of r1 that reach floor_q      */
+size_t unet_distance_map_scratch_bytes(int B, int H, int W);
+int unet_distance_map(const void *mask, int mask_dtype, int B, int H, int W, int edge, void *d2_i32, void *scratch, void *stream);
+size_t unet_reconstruct_scratch_bytes(int B, int H, int W);
+int unet_reconstruct_init(const void *marker, int marker_dtype, const void *under, int under_dtype, const void *mask, int mask_dtype, int B,
+                          int H, int W, void *status_u64, void *scratch, void *stream);
+int unet_reconstruct_sweeps(int B, int H, int W, int n_launches, void *changed_out_u32, int first_slot, void *scratch, void *stream);
+int unet_reconstruct_finish(int B, int H, int W, void *out_i32, void *raised_u32, void *scratch, void *stream);
+int unet_shape_heights(const void *d2_i32, int B, int H, int W, int hq, void *q_i32, void *lifted_i32, void *stream);
+int unet_shape_lower(const void *in_i32, int B, int H, int W, int c, void *out_i32, void *stream);
+int unet_shape_maxima(const void *r1_i32, const void *r2_i32, int B, int H, int W, int floor_q, void *out_f32, void *stream);
 /* Carved training targets from an instance image, replaces preprocess_gt (data.py:195-221: per cell, cv.dilate with a 5 x 5
  * rectangle, iterations=2, and 255 added on the ring the cell gained) and the cv.threshold(gt, 0, 255, THRESH_BINARY) after it
  * (data.py:64, :163).  ids [B,H,W], dtype 0 = int64, 1 = float32 holding integral values, 2 = int32 (what
