@@ -89,6 +89,11 @@ _SIGS = {
     "unet_weighted_map": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, vp, vp, vp, vp, vp]),
     "unet_label_components_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "unet_label_components": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]),
+    "unet_label_components_conn_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "unet_label_components_conn": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]),
+    "unet_clean_mask_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "unet_clean_mask": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_longlong, C.c_int,
+                                  vp, vp, vp, vp, vp]),
     "unet_instance_overlap_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_size_t]),
     "unet_instance_overlap": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, vp, vp, vp, vp, vp, vp, vp]),
     "unet_partition_pairs_scratch_bytes": (C.c_size_t, [C.c_int, C.c_size_t]),

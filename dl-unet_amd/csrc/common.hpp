@@ -218,6 +218,12 @@ static inline int class_pad(int K) { return K <= 2 ? 2 : K <= 4 ? 4 : K <= 8 ? 8
 // (dtype 0: int64, 1: float32); counts[b] = foreground pixels, n_objects[b] = components; parent is an int plane of scratch
 int ccl_labels(const void *mask, int dtype, int B, int H, int W, int *parent, int *label, unsigned long long *counts, int *n_objects,
                hipStream_t st);
+// raster numbering of root labels (instances.hip, passes inst_count / inst_scan / inst_rank / inst_write; shared by
+// unet_label_components and clean.hip): label [B,H,W] holds each pixel's root (the smallest pixel index of its component) or
+// -1 and becomes 1..n in raster order of the roots, 0 where it was -1; ids is an int plane of scratch, chunk_roots
+// inst_chunk_bytes(B, H, W) bytes of it
+size_t inst_chunk_bytes(int B, int H, int W);
+int inst_number(int *label, int *ids, int *chunk_roots, int B, int H, int W, hipStream_t st);
 int maxpool2_fwd(const void *x, void *y, int B, int H, int W, int C, int es, hipStream_t st);
 int maxpool2_bwd(const void *pre, const void *dy, void *dpre, int B, int H, int W, int C, int es, hipStream_t st);
 // drop-out (dropout.hip): x [B,H,W,C] dropped in place (+ its 2x2 max-pool into `pooled`, or null); g[0, n) *= 1 / (1 - p)

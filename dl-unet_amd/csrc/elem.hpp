@@ -1,9 +1,10 @@
 // elem.hpp — what the HBM-bound kernels (direct.hip, multiclass.hip, tile.hip, aux.hip) and the data-path files (wmap.hip,
-// instances.hip, prepare.hip, grow.hip, elastic.hip) share:
+// instances.hip, prepare.hip, grow.hip, elastic.hip, clean.hip) share:
 //   device : 4 consecutive channels of an activation tensor stored as fp32 (16 B) or bf16 (8 B, arithmetic mode 2), read /
 //            written as 4 floats; the sum / min / max of one value per lane over a wave; the min and max of one value per thread
 //            over a block; the sum of one value per thread over a 256-thread block, and (instances.hip, prepare.hip) the
-//            exclusive prefix of one int per thread over it; whether an element of a mask of any of the four dtypes is set
+//            exclusive prefix of one int per thread over it; whether an element of a mask of any of the four dtypes is set;
+//            the union-find of the labellings (wmap.hip, clean.hip) on LDS words and on global words
 //   host   : the grid size of a grid-stride launch, the bytes of a [B,H,W] scratch plane, and the dispatch of a launch on
 //            element size, channel width and padded class count (the launch bracket, profiled(), is common.hpp's)
 #pragma once
@@ -97,6 +98,53 @@ __device__ __forceinline__ int mask_on(const void *mask, int dtype, size_t e)
     if (dtype == 1) return ((const float *)mask)[e] != 0.0f;
     if (dtype == 2) return ((const int *)mask)[e] != 0;
     return ((const unsigned char *)mask)[e] != 0;
+}
+
+// Union-find on a plane of parent words, the smaller index always the parent (wmap.hip, clean.hip).  lds_*: a tile's words in
+// LDS, workgroup scope.  gl_*: the image's words in global memory, where every read and update is an agent-scope atomic
+// read-modify-write (per-XCD L2s are not coherent and a CU's L1 is never refreshed by other CUs' stores).
+__device__ __forceinline__ int lds_find(int *lp, int p)
+{
+    for (;;) {
+        const int q = __hip_atomic_load(&lp[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (q == p) return p;
+        p = q;
+    }
+}
+__device__ __forceinline__ void lds_union(int *lp, int a, int b)
+{
+    for (;;) {
+        a = lds_find(lp, a);
+        b = lds_find(lp, b);
+        if (a == b) return;
+        if (a > b) { const int t = a; a = b; b = t; }
+        int expect = b;                   // link the larger root under the smaller one, only while it is still a root
+        if (__hip_atomic_compare_exchange_strong(&lp[b], &expect, a, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP))
+            return;
+        b = expect;
+    }
+}
+__device__ __forceinline__ int gl_read(int *p) { return __hip_atomic_fetch_or(p, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ int gl_find(int *P, int p)
+{
+    for (;;) {
+        const int q = gl_read(&P[p]);
+        if (q == p) return p;
+        p = q;
+    }
+}
+__device__ __forceinline__ void gl_union(int *P, int a, int b)
+{
+    for (;;) {
+        a = gl_find(P, a);
+        b = gl_find(P, b);
+        if (a == b) return;
+        if (a > b) { const int t = a; a = b; b = t; }
+        int expect = b;
+        if (__hip_atomic_compare_exchange_strong(&P[b], &expect, a, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+            return;
+        b = expect;
+    }
 }
 
 static inline int grid_for(size_t total, int per_block = 256, int cap = 8192)

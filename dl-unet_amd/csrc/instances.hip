@@ -8,7 +8,7 @@
 //   7. inst_write  labels = id[root], 0 on background
 // A component's root is its first pixel in raster order, so the ranks of the roots are the raster numbering of
 // scipy.ndimage.label / cv.connectedComponents(connectivity=4).  Passes 4-7 touch every pixel a fixed number of times: their
-// cost does not depend on how many components there are.
+// cost does not depend on how many components there are.  They are inst_number (common.hpp), which clean.hip calls too.
 //
 // unet_instance_overlap: two id maps -> per-id areas, and for every ground-truth id the one predicted id that covers more than
 // half of it, with the size of that overlap:
@@ -208,13 +208,28 @@ __global__ __launch_bounds__(256) void pairs_compact_kernel(const unsigned long 
     }
 }
 
+static size_t in_chunks(int H, int W) { return ((size_t)H * W + IN_CHUNK - 1) / IN_CHUNK; }
+size_t inst_chunk_bytes(int B, int H, int W) { return align_up((size_t)B * in_chunks(H, W) * sizeof(int), 256); }
+
+// passes 4-7 on st (shared with clean.hip)
+int inst_number(int *label, int *ids, int *chunk_roots, int B, int H, int W, hipStream_t st)
+{
+    const size_t npx = (size_t)H * W;
+    const unsigned nchunk = (unsigned)in_chunks(H, W);
+    hipLaunchKernelGGL(inst_count_kernel, dim3(nchunk, B), dim3(256), 0, st, (const int *)label, npx, chunk_roots);
+    hipLaunchKernelGGL(inst_scan_kernel, dim3(B), dim3(256), 0, st, chunk_roots, (int)nchunk);
+    hipLaunchKernelGGL(inst_rank_kernel, dim3(nchunk, B), dim3(256), 0, st, (const int *)label, npx, (const int *)chunk_roots, ids);
+    hipLaunchKernelGGL(inst_write_kernel, dim3(grid_for(npx, 256, 2048), B), dim3(256), 0, st, label, npx, (const int *)ids);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 } // namespace unet
 
 using namespace unet;
 
 static size_t in_plane(int B, int H, int W) { return plane_bytes(B, H, W, sizeof(int)); }
-static size_t in_chunks(int H, int W) { return ((size_t)H * W + IN_CHUNK - 1) / IN_CHUNK; }
-static size_t in_chunk_bytes(int B, int H, int W) { return align_up((size_t)B * in_chunks(H, W) * sizeof(int), 256); }
+static size_t in_chunk_bytes(int B, int H, int W) { return inst_chunk_bytes(B, H, W); }
 
 size_t unet_label_components_scratch_bytes(int B, int H, int W)
 {
@@ -229,21 +244,13 @@ int unet_label_components(const void *mask, int dtype, int B, int H, int W, void
     ARG_CHECK(dtype == 0 || dtype == 1, "unet_label_components: dtype must be 0 (int64) or 1 (float32)");
     ARG_CHECK((size_t)H * W < (1u << 31) && H <= 65535 && B <= 65535, "unet_label_components: image too large");
     hipStream_t st = (hipStream_t)stream;
-    const size_t npx = (size_t)H * W;
-    const unsigned nchunk = (unsigned)in_chunks(H, W);
     char *s = (char *)scratch;
     int *plane = (int *)s;                                        // the parent words, then (they are dead after ccl_flatten) the ids
     int *chunk_roots = (int *)(s + in_plane(B, H, W));
     unsigned long long *counts = (unsigned long long *)(s + in_plane(B, H, W) + in_chunk_bytes(B, H, W));
     int *label = (int *)labels_i32;
     if (int rc = ccl_labels(mask, dtype, B, H, W, plane, label, counts, (int *)n_objects_i32, st)) return rc;
-    hipLaunchKernelGGL(inst_count_kernel, dim3(nchunk, B), dim3(256), 0, st, (const int *)label, npx, chunk_roots);
-    hipLaunchKernelGGL(inst_scan_kernel, dim3(B), dim3(256), 0, st, chunk_roots, (int)nchunk);
-    hipLaunchKernelGGL(inst_rank_kernel, dim3(nchunk, B), dim3(256), 0, st, (const int *)label, npx, (const int *)chunk_roots, plane);
-    hipLaunchKernelGGL(inst_write_kernel, dim3(grid_for(npx, 256, 2048), B), dim3(256), 0, st, label, npx,
-                       (const int *)plane);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return inst_number(label, plane, chunk_roots, B, H, W, st);
 }
 
 struct OvTable { unsigned long long *keys; unsigned *cnt; };

@@ -32,29 +32,7 @@ __device__ __forceinline__ bool wm_fg(const void *labels, int dtype, size_t e)
     return dtype == 0 ? ((const long long *)labels)[e] != 0 : ((const float *)labels)[e] != 0.f;
 }
 
-// ---- 1. tile-local union-find --------------------------------------------------------------------------
-__device__ __forceinline__ int lds_find(int *lp, int p)
-{
-    for (;;) {
-        const int q = __hip_atomic_load(&lp[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        if (q == p) return p;
-        p = q;
-    }
-}
-__device__ __forceinline__ void lds_union(int *lp, int a, int b)
-{
-    for (;;) {
-        a = lds_find(lp, a);
-        b = lds_find(lp, b);
-        if (a == b) return;
-        if (a > b) { const int t = a; a = b; b = t; }
-        int expect = b;                   // link the larger root under the smaller one, only while it is still a root
-        if (__hip_atomic_compare_exchange_strong(&lp[b], &expect, a, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP))
-            return;
-        b = expect;
-    }
-}
-
+// ---- 1. tile-local union-find (lds_find / lds_union: elem.hpp) ---------------------------------------------
 __global__ __launch_bounds__(256) void ccl_local_kernel(const void *__restrict__ labels, int dtype, int H, int W,
                                                         int *__restrict__ parent, unsigned long long *__restrict__ counts)
 {
@@ -88,30 +66,7 @@ __global__ __launch_bounds__(256) void ccl_local_kernel(const void *__restrict__
     if ((threadIdx.x & 63) == 0 && n1) atomicAdd(&counts[b], n1);
 }
 
-// ---- 2. merge across tile borders: agent-scope atomics only ----------------------------------------------
-__device__ __forceinline__ int gl_read(int *p) { return __hip_atomic_fetch_or(p, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ int gl_find(int *P, int p)
-{
-    for (;;) {
-        const int q = gl_read(&P[p]);
-        if (q == p) return p;
-        p = q;
-    }
-}
-__device__ __forceinline__ void gl_union(int *P, int a, int b)
-{
-    for (;;) {
-        a = gl_find(P, a);
-        b = gl_find(P, b);
-        if (a == b) return;
-        if (a > b) { const int t = a; a = b; b = t; }
-        int expect = b;
-        if (__hip_atomic_compare_exchange_strong(&P[b], &expect, a, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-            return;
-        b = expect;
-    }
-}
-
+// ---- 2. merge across tile borders: agent-scope atomics only (gl_find / gl_union: elem.hpp) ------------------
 // per image: (tiles_x - 1) vertical borders of H pixel pairs, then (tiles_y - 1) horizontal borders of W pairs
 __global__ __launch_bounds__(256) void ccl_merge_kernel(const void *__restrict__ labels, int dtype, int H, int W, int *parent,
                                                         int nv, int total)

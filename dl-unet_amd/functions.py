@@ -16,6 +16,9 @@ growths meet (unet_geodesic_init / unet_geodesic_sweeps / unet_geodesic_finish),
 distance_map, reconstruct and shape_seeds give it seeds from the shape of the mask alone: the exact interior distance map
 (unet_distance_map), grey reconstruction by dilation (unet_reconstruct_init / unet_reconstruct_sweeps / unet_reconstruct_finish),
 and the h-maxima of the distance map with a minimum radius, labelled (unet_shape_heights / unet_shape_lower / unet_shape_maxima).
+clean_mask, fill_holes and remove_small are the clean-up in front of all that, between the argmax and the instance map: holes
+filled, small cells and cells on the frame dropped, with either connectivity (unet_clean_mask); label_cells(connectivity=8) is the
+8-connected labelling that goes with it (unet_label_components_conn).
 """
 import collections
 import fractions
@@ -130,21 +133,99 @@ def weighted_map(gt_batch, *, w0=20, sig2=25, return_objects=False):
     return (w, n_objects) if return_objects else w
 
 
-def label_cells(mask):
+def label_cells(mask, connectivity=4):
     """The cell instances of a foreground mask [H,W] or [B,H,W] on a HIP device (foreground = value != 0; bool / integer masks
     go in as int64, float ones as float32): returns (labels, n_objects), labels int32 of the mask's shape, 0 on background
     and 1..n on the 4-connected components, numbered in raster order of their first pixel like scipy.ndimage.label and
     cv.connectedComponents(connectivity=4) (functions.py:47); n_objects int32 [B] ([1] for a single image) = n.
+    connectivity=8 joins diagonal neighbours too (scipy.ndimage.label with the full 3 x 3 structure, the same numbering;
+    unet_label_components_conn, which reads uint8 and int32 masks as they are); anything but 4 or 8 raises ValueError.
     Host tensors raise NotImplementedError (no CPU path)."""
-    _device_only("label_cells", "unet_label_components", mask)
+    if connectivity not in (4, 8):
+        raise ValueError("label_cells: connectivity must be 4 or 8, got %r" % (connectivity,))
+    entry = "unet_label_components" if connectivity == 4 else "unet_label_components_conn"
+    _device_only("label_cells", entry, mask)
     import _hip
-    m, code = _int_code(_planes("label_cells", mask), int32_ok=False)
+    m, code = _int_code(_planes("label_cells", mask), uint8_ok=connectivity == 8, int32_ok=connectivity == 8)
     B, H, W = m.shape
     labels = torch.empty(B, H, W, dtype=torch.int32, device=m.device)
     n_objects = torch.empty(B, dtype=torch.int32, device=m.device)
-    scratch = _hip.scratch("unet_label_components", m.device, B, H, W)
-    _hip.run("unet_label_components", m.device, _hip.ptr(m), code, B, H, W, _hip.ptr(labels), _hip.ptr(n_objects), _hip.ptr(scratch))
+    scratch = _hip.scratch(entry, m.device, B, H, W)
+    _hip.run(entry, m.device, _hip.ptr(m), code, B, H, W, *((8, 1) if connectivity == 8 else ()), _hip.ptr(labels), _hip.ptr(n_objects),
+             _hip.ptr(scratch))
     return (labels[0] if mask.dim() == 2 else labels), n_objects
+
+
+CleanInfo = collections.namedtuple("CleanInfo", "holes_filled pixels_filled cells_small pixels_small cells_border pixels_border cells_kept")
+
+
+def _area(name, what, v, none_ok=False):
+    if v is None and none_ok:
+        return -1
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0:
+        raise ValueError("%s: %s must be %san integer >= 0, got %r" % (name, what, "None or " if none_ok else "", v))
+    return min(int(v), 1 << 62)
+
+
+def clean_mask(mask, *, fill_holes=True, max_hole_area=None, min_area=0, drop_border=False, connectivity=4, return_info=False,
+               return_action=False):
+    """Clean a foreground mask [H,W] or [B,H,W] on a HIP device between the argmax and the instance map (foreground = value
+    != 0): fill holes, drop small cells and cells on the frame, what scipy.ndimage.binary_fill_holes and skimage's
+    remove_small_holes, remove_small_objects and clear_border do on the host.  connectivity 4 or 8 is the foreground's; the
+    background takes the dual one (8 or 4), as in warp_labels, so no digital curve is both closed and leaky.
+      hole   a component of the background with no pixel in the first or last row or column; its area is its own pixel count
+             (foreground islands inside it do not count: remove_small_holes' convention).  Filled when fill_holes is true and
+             max_hole_area is None or area <= max_hole_area.
+      cell   a component of the mask after filling (an island inside a filled hole is part of the cell round it).  Dropped as
+             small when area < min_area (remove_small_objects' convention: 0 and 1 drop nothing); with drop_border, a cell that
+             is not small and has a pixel in the first or last row or column is dropped too.
+    Returns the cleaned mask of the input's shape and dtype (bool comes back as bool; the other types follow _int_code with
+    uint8 as it is): the input value on a kept foreground pixel, 1 on a filled one, 0 elsewhere.  With return_info it is followed
+    by CleanInfo(holes_filled, pixels_filled, cells_small, pixels_small, cells_border, pixels_border, cells_kept), numpy int64
+    [B] each, read back in one copy; with return_action by the uint8 action plane of the input's shape: 0 background that stays,
+    1 foreground kept, 2 filled, 3 dropped as small, 4 dropped on the border.  Without return_info nothing is read back and
+    nothing waits.  Exact integers on the device (unet_clean_mask: two labellings and two per-pixel passes, whatever the number
+    of holes and cells).  A connectivity other than 4 or 8 and areas that are no integers >= 0 raise ValueError; host tensors
+    raise NotImplementedError (no CPU path)."""
+    if connectivity not in (4, 8):
+        raise ValueError("clean_mask: connectivity must be 4 or 8, got %r" % (connectivity,))
+    hole = _area("clean_mask", "max_hole_area", max_hole_area, none_ok=True)
+    small = _area("clean_mask", "min_area", min_area)
+    if not torch.is_tensor(mask):
+        raise NotImplementedError("clean_mask takes a tensor on the HIP device (unet_clean_mask); there is no CPU implementation")
+    mk = _planes("clean_mask", mask)
+    _device_only("clean_mask", "unet_clean_mask", mask)
+    import _hip
+    m, code = _int_code(mk, uint8_ok=True)
+    B, H, W = m.shape
+    dev = m.device
+    out = torch.empty_like(m)
+    action = torch.empty(B, H, W, dtype=torch.uint8, device=dev) if return_action else None
+    info = torch.empty(B, 7, dtype=torch.int64, device=dev)
+    scratch = _hip.scratch("unet_clean_mask", dev, B, H, W)
+    _hip.run("unet_clean_mask", dev, _hip.ptr(m), code, B, H, W, connectivity, int(bool(fill_holes)), hole, small, int(bool(drop_border)),
+             _hip.ptr(out), _hip.ptr(action), _hip.ptr(info), _hip.ptr(scratch))
+    if out.dtype != mask.dtype:
+        out = out.to(mask.dtype)
+    single = mask.dim() == 2
+    res = (out[0] if single else out,)
+    if return_info:
+        res += (CleanInfo(*info.cpu().numpy().T.copy()),)
+    if return_action:
+        res += (action[0] if single else action,)
+    return res if len(res) > 1 else res[0]
+
+
+def fill_holes(mask, max_area=None, connectivity=4):
+    """clean_mask(mask, max_hole_area=max_area, connectivity=connectivity): the holes of the mask filled, all of them or those
+    of at most max_area pixels; nothing is dropped."""
+    return clean_mask(mask, max_hole_area=max_area, connectivity=connectivity)
+
+
+def remove_small(mask, min_area, connectivity=4):
+    """clean_mask(mask, fill_holes=False, min_area=min_area, connectivity=connectivity): the cells of fewer than min_area
+    pixels dropped; nothing is filled."""
+    return clean_mask(mask, fill_holes=False, min_area=min_area, connectivity=connectivity)
 
 
 SegMeasure = collections.namedtuple("SegMeasure", "seg jaccard_sum n_gt n_matched n_pred per_image jaccard")

@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 import _hip
-from functions import evaluation_metrics, label_cells, metrics_from_counts, shape_seeds, split_cells
+from functions import _area, clean_mask, evaluation_metrics, label_cells, metrics_from_counts, shape_seeds, split_cells
 import optim as hip_optim
 
 TILE_MARGIN = 92        # context each side of a tile's output that the valid convolutions eat: (S - So) / 2
@@ -225,8 +225,32 @@ def _parse_shape_split(v):
     raise ValueError("segment: shape_split must be None, a number h >= 0 or a pair (h, min_radius) of numbers >= 0, got %r" % (v,))
 
 
+_CLEAN_KEYS = ("fill_holes", "max_hole_area", "min_area", "drop_border", "connectivity")
+
+
+def _parse_clean(v, n_classes):
+    """clean of segment -> the keyword arguments of functions.clean_mask, or None; ValueError for anything but None, a bool or a
+    dict of them, for values clean_mask refuses, and for filling holes in a mask of more than two classes."""
+    if v is None or v is False:
+        return None
+    if v is True:
+        kw = {}
+    elif isinstance(v, dict) and all(k in _CLEAN_KEYS for k in v):
+        kw = dict(v)
+    else:
+        raise ValueError("segment: clean must be None, True (fill all holes) or a dict with keys among %s, got %r" % (", ".join(_CLEAN_KEYS), v))
+    if kw.get("connectivity", 4) not in (4, 8):
+        raise ValueError("segment: clean: connectivity must be 4 or 8, got %r" % (kw["connectivity"],))
+    _area("segment: clean", "max_hole_area", kw.get("max_hole_area"), none_ok=True)
+    _area("segment: clean", "min_area", kw.get("min_area", 0))
+    if n_classes > 2 and kw.get("fill_holes", True):
+        raise ValueError("segment: clean with fill_holes on a %d-class net: a filled pixel has no class; pass "
+                         "clean={'fill_holes': False, ...} to drop small or border cells only" % n_classes)
+    return kw
+
+
 def segment(unet, images, tile_size=None, max_batch=16, normalise=True, return_probs=False, return_instances=False, views=None,
-            shape_split=None, split=None):
+            clean=None, shape_split=None, split=None):
     """Segment images of any size and shape with the overlap-tile strategy; returns the int64 argmax mask of the same
     shape as `images` (and the float32 foreground probability softmax(logits)[1] with return_probs).  A K-class net
     (Unet(n_classes=K), K > 2) gives the K-way argmax (ties -> the lowest class) and, with return_probs, the softmax of all
@@ -251,6 +275,13 @@ def segment(unet, images, tile_size=None, max_batch=16, normalise=True, return_p
         The sum runs in the order of the codes and is deterministic.  views=(0,) gives the probabilities of views=None bit for
         bit; its mask is prob > 0.5 and not l1 > l0, which differ only where prob == 0.5 exactly (logit differences below
         about 6e-8, where 1 + exp(l0 - l1) rounds to 2).
+    clean: None, True or a dict of functions.clean_mask's keyword arguments (fill_holes, max_hole_area, min_area, drop_border,
+        connectivity): the mask is cleaned on the device right after the last stitch, on the same stream, before the instance map
+        (label_cells, split or shape_split) is made of it: holes filled, small cells and cells on the frame dropped.  True fills
+        all holes and does nothing else.  The mask returned is the cleaned one; the probabilities are untouched; it does not need
+        return_instances.  A hole in a cell is background to the distance map, so shape_split over-splits a cell that has one.
+        With a K > 2 net a filled pixel would have no class: fill_holes true raises ValueError there, min_area and drop_border
+        alone (fill_holes=False) are allowed and a kept pixel keeps its class.
     split: None, or a float in (0, 1] (needs return_instances, else ValueError): the instance map becomes
         split_instances(mask, fg_prob, split), touching cells split by growing the cores fg_prob >= split back inside the mask
         (functions.split_cells), on the same stream after the last stitch.  fg_prob is the foreground probability of the call:
@@ -287,6 +318,7 @@ def segment(unet, images, tile_size=None, max_batch=16, normalise=True, return_p
         if split is not None:
             raise ValueError("segment: shape_split and split are two ways to seed one growth; give one of them")
         shape_split = _parse_shape_split(shape_split)
+    clean = _parse_clean(clean, getattr(unet, 'n_classes', 2))
     vs = None if views is None else parse_views(views)
     S = auto_tile_size(H, W) if tile_size is None else int(tile_size)
     _check_tile_size(S)
@@ -346,6 +378,8 @@ def segment(unet, images, tile_size=None, max_batch=16, normalise=True, return_p
             else:
                 _hip.check(L.unet_tile_stitch_k(_hip.ptr(logits), So, K, oy0, ox0, ny, nx, t0, n, B, H, W, _hip.ptr(mask),
                                                 _hip.ptr(prob), st), "unet_tile_stitch_k")
+        if clean is not None:
+            mask = clean_mask(mask, **clean)
         if split is not None:
             inst = split_instances(mask, prob if K == 2 else 1 - prob[:, 0], float(split))
         elif shape_split is not None:

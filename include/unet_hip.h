@@ -328,6 +328,38 @@ int unet_weighted_map(const void *labels, int labels_dtype, int B, int H, int W,
 size_t unet_label_components_scratch_bytes(int B, int H, int W);
 int unet_label_components(const void *mask, int dtype, int B, int H, int W, void *labels_i32, void *n_objects_i32, void *scratch,
                           void *stream);
+/* The same numbering for either phase of a mask and either connectivity (clean.hip; functions.label_cells(connectivity=8)):
+ * mask [B,H,W] of dtype 0 = int64, 1 = float32, 2 = int32, 3 = uint8.  phase 1 labels the pixels with mask != 0, phase 0 those
+ * with mask == 0; connectivity 4 (the cross) or 8 (the full 3 x 3 neighbourhood).  labels_i32 [B,H,W]: the number 1..n of the
+ * pixel's component, the components numbered in raster order of their first pixel (scipy.ndimage.label with the matching
+ * structure), 0 on the other phase; n_objects_i32 [B] = n.  For phase 1, connectivity 4 the outputs are those of
+ * unet_label_components bit for bit.  Exact, the cost does not depend on n.  Limits as unet_label_components (H * W < 2^31,
+ * H <= 65535, B <= 65535), H != W allowed, down to 1 x 1.  Another dtype, connectivity or phase, a NULL pointer and a size
+ * over the limit return an error and write nothing.
+ * scratch: unet_label_components_conn_scratch_bytes(B, H, W), initialised by the call.                                        */
+size_t unet_label_components_conn_scratch_bytes(int B, int H, int W);
+int unet_label_components_conn(const void *mask, int dtype, int B, int H, int W, int connectivity, int phase, void *labels_i32,
+                               void *n_objects_i32, void *scratch, void *stream);
+/* Cleaning a foreground mask between the argmax and the instance map (clean.hip; functions.clean_mask; scipy's
+ * binary_fill_holes, skimage's remove_small_holes / remove_small_objects / clear_border): mask [B,H,W] of dtype 0 = int64,
+ * 1 = float32, 2 = int32, 3 = uint8, foreground = value != 0.  connectivity 4 or 8 is the foreground's; the background takes
+ * the dual one (8 or 4).  A hole is a component of the background without a pixel in the first or last row or column; its area
+ * is its own pixel count (foreground islands inside it do not count).  With fill != 0 a hole is filled when max_hole_area is
+ * -1 (no limit) or its area <= max_hole_area.  The cells are the components of the mask after filling: one with area <
+ * min_area is dropped as small (min_area 0 and 1 drop nothing), and with drop_border != 0 one that is not small and has a
+ * pixel in the first or last row or column is dropped too.
+ *   action_u8 [B,H,W] (may be NULL): 0 background that stays, 1 foreground kept, 2 filled, 3 dropped as small, 4 dropped on
+ *                     the border
+ *   out [B,H,W], mask's dtype: the input value where the action is 1, 1 where it is 2, else 0
+ *   info_i64 [B][7]: holes filled, pixels filled, cells dropped as small, their pixels, cells dropped on the border, their
+ *                     pixels, cells kept
+ * A fixed list of launches on the stream for given arguments, no read-back; exact integers, the cost does not depend on the
+ * number of holes or cells.  Limits as unet_label_components.  connectivity other than 4 or 8, max_hole_area < -1,
+ * min_area < 0, another dtype, a NULL pointer (but action_u8) and a size over the limit return an error and write nothing.
+ * scratch: unet_clean_mask_scratch_bytes(B, H, W) (13 bytes per pixel), initialised by the call.                             */
+size_t unet_clean_mask_scratch_bytes(int B, int H, int W);
+int unet_clean_mask(const void *mask, int dtype, int B, int H, int W, int connectivity, int fill, long long max_hole_area,
+                    long long min_area, int drop_border, void *out, void *action_u8, void *info_i64, void *scratch, void *stream);
 /* The integers of the Cell Tracking Challenge SEG measure, the score behind the goals of trainer.py:20-26 (Ronneberger et al.
  * 2015, Table 2): gt_i32, pred_i32 id maps int32 [B,H,W], 0 = background, gt ids anywhere in [0, ng_max] (not necessarily
  * consecutive, an object not necessarily connected), pred ids in [0, np_max]; ng_max, np_max < 2^24.
