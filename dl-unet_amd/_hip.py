@@ -149,6 +149,7 @@ _SIGS = {
     "unet_conv1ch_fwd": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp]),
     "unet_conv1ch_bwd_scratch_bytes": (C.c_size_t, [C.c_int] * 3),
     "unet_conv1ch_bwd": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp]),
+    "unet_conv1ch_dgrad": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
 }
 EXPORTS = tuple(_SIGS.keys())
 

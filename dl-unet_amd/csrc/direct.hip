@@ -776,6 +776,10 @@ int unet_conv1ch_bwd(const void *x, int B, int S, int K, const void *dz, void *d
 {
     return conv1ch_bwd((const float *)x, B, S, K, dz, (float *)dw, (float *)db, (float *)scratch, op_es(), (hipStream_t)stream);
 }
+int unet_conv1ch_dgrad(const void *dz, int B, int S, int K, const void *w, void *dx, void *stream)
+{
+    return conv1ch_dgrad(dz, B, S, K, (const float *)w, (float *)dx, op_es(), (hipStream_t)stream);
+}
 int unet_head1x1_fwd(const void *x, int B, int H, int W, int C, const void *w, const void *bias, void *logits, void *stream)
 {
     return head1x1_fwd(x, B, H, W, C, (const float *)w, (const float *)bias, (float *)logits, op_es(), (hipStream_t)stream);

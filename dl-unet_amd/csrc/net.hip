@@ -1001,6 +1001,8 @@ int unet_conv3x3_fwd(const void *x1, int H1, int W1, int C1, int pad1, const voi
     ARG_CHECK(x2 || (H1 + 2 * pad1 == H && W1 + 2 * pad1 == W), "conv3x3_fwd: single source must match the input extent");
     hipStream_t st = (hipStream_t)stream;
     ARG_CHECK(H == W && H1 == W1, "conv3x3_fwd: square tiles only");
+    // (what launch_igemmb would refuse after the filters have been packed: refused here, before anything is enqueued)
+    ARG_CHECK(t_math != 2 || (C1 % 64 == 0 && (!x2 || C2 % 64 == 0)), "conv3x3_fwd: bf16 tensors need sources of whole 64-channel tiles (C1=%d C2=%d)", C1, x2 ? C2 : 0);
     float *wu = (float *)((char *)scratch + align_up((size_t)K * (C1 + (x2 ? C2 : 0)) * 9 * sizeof(float), 256));
     return conv_fwd_launch((const float *)x1, H1, C1, pad1, (const float *)x2, C2, B, H, (const float *)w_oihw, (float *)scratch,
                            (const float *)bias, K, relu, (float *)y, st, wu);
@@ -1019,7 +1021,14 @@ int unet_conv3x3_bwd(const void *x1, int H1, int W1, int C1, int pad1, const voi
     ARG_CHECK(x1 && w_oihw && dz && scratch, "conv3x3_bwd: null argument");
     MathScope ms(get_math_mode());
     ProfScope ps("op.conv3x3_bwd");
+    ARG_CHECK(x2 || (H1 + 2 * pad1 == H && W1 + 2 * pad1 == W), "conv3x3_bwd: single source must match the input extent");
     ARG_CHECK(H == W && H1 == W1, "conv3x3_bwd: square tiles only");
+    // (what launch_igemmb / launch_wgrad would refuse after the first launches: refused here, before anything is enqueued)
+    if (t_math == 2) {
+        ARG_CHECK(!(dx1 || (x2 && dx2) || dw) || K % 64 == 0, "conv3x3_bwd: bf16 tensors need dz of whole 64-channel tiles (K=%d)", K);
+        ARG_CHECK(!dw || (C1 % 64 == 0 && (!x2 || C2 % 64 == 0)), "conv3x3_bwd: the bf16 weight gradient needs sources of whole 64-channel tiles (C1=%d C2=%d)",
+                  C1, x2 ? C2 : 0);
+    }
     hipStream_t st = (hipStream_t)stream;
     const int C = C1 + (x2 ? C2 : 0);
     const int Ho = H - 2;

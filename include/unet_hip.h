@@ -582,7 +582,10 @@ int unet_normalise01(void *x, int B, size_t n, const void *minmax, void *stream)
 /* nn.Conv2d(3x3, valid)+ReLU, network.py:131-188.  Second source (x2) is the virtual
  * crop_and_concat (network.py:108-127): x1 = skip [B,H1,W1,C1] zero-padded by pad1 per side,
  * x2 = up-conv output [B,H,W,C2]; pass x2=NULL,C2=0,pad1=0 for a plain conv.  H,W = extent of
- * the (virtual) input; y : [B,H-2,W-2,K].  scratch >= unet_conv3x3_scratch_bytes(C1+C2,K).  */
+ * the (virtual) input; y : [B,H-2,W-2,K].  scratch >= unet_conv3x3_scratch_bytes(C1+C2,K).
+ * A single source may carry a signed pad too (x2=NULL, H1 + 2 pad1 == H: zero border for pad1 > 0, crop for pad1 < 0), in
+ * the forward and the backward.  With bf16 tensors (arithmetic mode 2) every source needs whole 64-channel tiles, and so
+ * does dz for dx / dw; a call outside that is refused before anything is enqueued.                                  */
 size_t unet_conv3x3_scratch_bytes(int C, int K);
 int unet_conv3x3_fwd(const void *x1, int H1, int W1, int C1, int pad1, const void *x2, int C2,
                      int B, int H, int W, const void *w_oihw, const void *bias, int K, int relu,
@@ -608,7 +611,8 @@ int unet_maxpool2_bwd(const void *pre, const void *dy, void *dpre, int B, int H,
 int unet_dropout_pool_fwd(void *x_inout, void *pooled_or_null, int B, int H, int W, int C, float p,
                           unsigned long long seed, unsigned long long step, int site, void *stream);
 int unet_dropout_bwd(void *g_inout, size_t n, float p, void *stream);
-/* nn.ConvTranspose2d(k2,s2), network.py:159-183: x [B,H,W,Ci] -> y [B,2H,2W,Co]; w IOHW. */
+/* nn.ConvTranspose2d(k2,s2), network.py:159-183: x [B,H,W,Ci] -> y [B,2H,2W,Co]; w IOHW.
+ * The forward takes H != W; the backward takes square tiles only (H == W, checked).       */
 size_t unet_upconv2_scratch_bytes(int B, int H, int W, int Ci, int Co);
 int unet_upconv2_fwd(const void *x, int B, int H, int W, int Ci, const void *w_iohw,
                      const void *bias, int Co, void *y, void *scratch, void *stream);
@@ -636,6 +640,9 @@ int unet_conv1ch_fwd(const void *x, int B, int S, const void *w, const void *bia
 size_t unet_conv1ch_bwd_scratch_bytes(int B, int S, int K);
 int unet_conv1ch_bwd(const void *x, int B, int S, int K, const void *dz, void *dw, void *db,
                      void *scratch, void *stream);
+/* its input gradient alone (what unet_backward_input runs on the whole net): dz [B,S-2,S-2,K] -> dx [B,S,S] fp32,
+ * dx[b][y][x] = sum_{k,ty,tx} dz[b][y-ty][x-tx][k] w[k][ty][tx] (full correlation with the flipped filter); no scratch. */
+int unet_conv1ch_dgrad(const void *dz, int B, int S, int K, const void *w, void *dx, void *stream);
 
 #ifdef __cplusplus
 }

@@ -180,5 +180,20 @@ def concat_bwd_families(mode, dma, Hs, pad, C1, C2, K):
             wgrad_family(mode, dma, C1, K), wgrad_family(mode, dma, C2, K)]
 
 
+def single_pad_fwd_family(mode, dma, Hs, pad, C1, K):
+    """The one launch of unet_conv3x3_fwd over a single source of extent Hs with a signed pad (x2 = NULL, H = Hs + 2 pad):
+    a positive pad makes taps leave the source, a negative one crops it and none does."""
+    Ho = Hs + 2 * pad - 2
+    return conv_family(mode, dma, Ho, K, [C1], taps_leave(Hs, Ho, 0, pad))
+
+
+def single_pad_bwd_families(mode, dma, Hs, pad, C1, K):
+    """The contraction launches of unet_conv3x3_bwd over that single padded source with every output requested, reduces left
+    out: the dgrad over the source's window of the virtual input, then its weight gradient (the bias gradient does not ride
+    on a launch that misses part of dz: it is the stand-alone bias_grad)."""
+    Ho = Hs + 2 * pad - 2
+    return [conv_family(mode, dma, Hs, C1, [K], taps_leave(Ho, Hs, pad, 2)), wgrad_family(mode, dma, C1, K)]
+
+
 # kernel kinds of the profile (include/unet_hip.h, "measurement")
 K_IGEMM, K_WGRAD, K_REDUCE, K_WINO, K_CONV11C, K_ELEMWISE = 0, 1, 2, 3, 4, 5
