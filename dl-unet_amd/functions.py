@@ -19,6 +19,9 @@ and the h-maxima of the distance map with a minimum radius, labelled (unet_shape
 clean_mask, fill_holes and remove_small are the clean-up in front of all that, between the argmax and the instance map: holes
 filled, small cells and cells on the frame dropped, with either connectivity (unet_clean_mask); label_cells(connectivity=8) is the
 8-connected labelling that goes with it (unet_label_components_conn).
+cell_sums, props_from_sums, cell_props and select_cells are the step after the instance map: one row of exact integers per cell
+(unet_cell_sums), the usual shape and intensity properties formed from them on the host, and the per-id remap that drops or
+renumbers cells by any decision taken on those rows (unet_remap_labels).
 """
 import collections
 import fractions
@@ -226,6 +229,190 @@ def remove_small(mask, min_area, connectivity=4):
     """clean_mask(mask, fill_holes=False, min_area=min_area, connectivity=connectivity): the cells of fewer than min_area
     pixels dropped; nothing is filled."""
     return clean_mask(mask, fill_holes=False, min_area=min_area, connectivity=connectivity)
+
+
+CellSums = collections.namedtuple("CellSums", "area bbox moments frame open contact v_sum v_sum2 v_min v_max present")
+CellProps = collections.namedtuple("CellProps", "area centroid bbox moments_central axis_major axis_minor eccentricity orientation "
+                                                "equivalent_diameter extent perimeter contact_fraction touches_frame mean std min max")
+MEASURE_EDGE = 32768                                                    # H, W of cell_sums: every integer sum fits 64 bits
+
+
+def cell_sums(labels, image=None, *, n_max=None):
+    """One row of exact integers per cell of an instance map, on the device (unet_cell_sums): int32 / int64 ids [H,W] or
+    [B,H,W] on a HIP device, 0 = background, ids in [0, 2^24), not necessarily consecutive or connected (the convention of
+    grow_cells and seg_measure).  image: None or a tensor of the same shape under the map: uint8 / integer images with values in
+    [0, 65536), or float images (read as float32) with finite values.  Returns CellSums of device tensors [B, n_max+1, ...]
+    ([n_max+1, ...] for a single image); row 0 is the background, treated like any other id.  For id i over its pixels (y, x):
+      area     int64
+      bbox     int32 [.., 4]: (y0, x0, y1, x1), half-open like scipy.ndimage.find_objects
+      moments  int64 [.., 5]: (sum y, sum x, sum y^2, sum x^2, sum x y)
+      frame, open, contact  int64, counts over the four sides of every pixel: the side lies on the image frame; the neighbour
+               has id 0 and i != 0; the neighbour has another id (for i = 0 any non-zero id).  Their sum is the crack-length
+               perimeter; an edge between two ids is counted once for each
+      v_sum, v_sum2, v_min, v_max  None without an image; int64 sums and int32 extrema, all exact, for an integer image;
+               float64 sums (v^2 is exact in fp64; the adds round, in an order that can differ between runs) and exact float32
+               extrema for a float image
+      present  bool, area > 0; every field of an absent id is 0
+    n_max: None reads the largest id back once (and checks the ids are in [0, 2^24)); an integer >= 0 skips that, and the call
+    then waits for nothing until the status words are read at its end.  Pixels with an id outside [0, n_max], image values
+    outside [0, 65536) and non-finite ones raise ValueError, as do shapes that differ and H or W above 32768; host tensors raise
+    NotImplementedError (no CPU path).  Exact, every integer the same in every run, at a cost independent of the number of cells.
+    props_from_sums turns the table into the usual shape and intensity properties."""
+    (lab,) = _id_maps("cell_sums", "unet_cell_sums", labels)
+    import _hip
+    img, icode = None, 0
+    if image is not None:
+        if not torch.is_tensor(image) or image.shape != labels.shape:
+            raise ValueError("cell_sums: the image must be a tensor of the labels' shape %s, got %s"
+                             % (tuple(labels.shape), tuple(image.shape) if torch.is_tensor(image) else type(image).__name__))
+        _device_only("cell_sums", "unet_cell_sums", image)
+        img, icode = _int_code(_planes("cell_sums", image), uint8_ok=True)
+    B, H, W = lab.shape
+    if max(H, W) > MEASURE_EDGE:
+        raise ValueError("cell_sums: H and W must be <= %d, got %d x %d" % (MEASURE_EDGE, H, W))
+    if n_max is None:
+        (n_max,) = _id_range("cell_sums", lab)
+    elif isinstance(n_max, bool) or not isinstance(n_max, (int, np.integer)) or not 0 <= n_max < 1 << 24:
+        raise ValueError("cell_sums: n_max must be None or an integer in [0, 2^24), got %r" % (n_max,))
+    n_max = int(n_max)
+    dev, N = lab.device, n_max + 1
+    isfloat = icode == 1
+    area = torch.empty(B, N, dtype=torch.int64, device=dev)
+    bbox = torch.empty(B, N, 4, dtype=torch.int32, device=dev)
+    moments = torch.empty(B, N, 5, dtype=torch.int64, device=dev)
+    edges = torch.empty(B, N, 3, dtype=torch.int64, device=dev)
+    vsum = None if img is None else torch.empty(B, N, 2, dtype=torch.float64 if isfloat else torch.int64, device=dev)
+    vrange = None if img is None else torch.empty(B, N, 2, dtype=torch.float32 if isfloat else torch.int32, device=dev)
+    present = torch.empty(B, N, dtype=torch.bool, device=dev)
+    status = torch.empty(B, 2, dtype=torch.int64, device=dev)
+    scratch = _hip.scratch("unet_cell_sums", dev, B, n_max)
+    _hip.run("unet_cell_sums", dev, _hip.ptr(lab), 0 if lab.dtype == torch.int64 else 2, _hip.ptr(img), icode, B, H, W, n_max,
+             _hip.ptr(area), _hip.ptr(bbox), _hip.ptr(moments), _hip.ptr(edges), _hip.ptr(vsum), _hip.ptr(vrange), _hip.ptr(present),
+             _hip.ptr(status), _hip.ptr(scratch))
+    bad_id, bad_v = (int(v) for v in status.cpu().sum(dim=0))
+    if bad_id:
+        raise ValueError("cell_sums: %d pixels hold ids outside [0, %d]" % (bad_id, n_max))
+    if bad_v:
+        raise ValueError("cell_sums: %d pixels of the image hold %s" % (bad_v, "values that are not finite" if isfloat
+                                                                       else "values outside [0, 65536)"))
+    out = [area, bbox, moments, edges[..., 0], edges[..., 1], edges[..., 2]]
+    out += [None] * 4 if img is None else [vsum[..., 0], vsum[..., 1], vrange[..., 0], vrange[..., 1]]
+    out.append(present)
+    return CellSums(*(t if t is None or labels.dim() == 3 else t[0] for t in out))
+
+
+def _exact_variance(on, n, s2, p, q):
+    """(n * s2 - p * q) / n^2 in float64 where `on`, nan elsewhere: the numerator in Python integers (it reaches 2^90 for int64
+    inputs at the limits of cell_sums), then the one division, correctly rounded.  A loop over the present rows only."""
+    out = np.full(n.shape, np.nan)
+    N, S2, P, Q = (v[on].astype(object) for v in (n, s2, p, q))
+    out[on] = [a / b for a, b in zip(N * S2 - P * Q, N * N)]
+    return out
+
+
+def props_from_sums(sums):
+    """The usual shape and intensity properties of every id from the table of cell_sums (a CellSums of device tensors, host
+    tensors or arrays, [n_max+1, ...] or [B, n_max+1, ...]): pure numpy on the host.  Returns CellProps of float64 arrays of the
+    table's leading shape (nan wherever an id is absent) unless stated:
+      area                 float64 (nan for an absent id)
+      centroid             [.., 2]: (mean y, mean x) in pixel coordinates (a pixel's centre is its integer index)
+      bbox                 int32 [.., 4] as in the table (0 for an absent id)
+      moments_central      [.., 3]: (mu_yy, mu_xx, mu_xy) / area, the second moments about the centroid per pixel, every pixel a
+                           point mass at its centre.  Formed exactly: the raw sums are first re-centred on the box origin (y0, x0)
+                           in integers, then area * S_yy' - S_y'^2 (and so on) in integers that cannot overflow, then one division
+                           by area^2.  Never sum y^2 / area - (sum y / area)^2 on image coordinates
+      axis_major, axis_minor   4 sqrt(lambda) of the two eigenvalues of that 2 x 2 tensor (the axes of the ellipse with the same
+                           second moments; an h x w rectangle has 4 sqrt((w^2 - 1) / 12) and 4 sqrt((h^2 - 1) / 12))
+      eccentricity         sqrt(1 - lambda_min / lambda_max), 0 for a cell whose moments vanish (a single pixel) or are isotropic
+      orientation          the angle of the major axis in radians in (-pi/2, pi/2], measured from the x axis (the direction of
+                           growing column index) towards the y axis (growing row index, downwards on a displayed image):
+                           0.5 atan2(2 mu_xy, mu_xx - mu_yy).  A cell along y = x has +pi/4, along y = -x it has -pi/4, a tall one
+                           pi/2; an isotropic one 0.  (skimage's regionprops measures from the row axis instead.)
+      equivalent_diameter  sqrt(4 area / pi)
+      extent               area / box area
+      perimeter            frame + open + contact, the crack length (not skimage's sub-pixel estimate)
+      contact_fraction     contact / perimeter
+      touches_frame        bool, frame > 0 (False for an absent id)
+      mean, std, min, max  of the image (std is the population one); None when the table has no image.  For an integer image
+                           the variance is (area * sum v^2 - (sum v)^2) / area^2 with exact integers."""
+    def host(t):
+        return None if t is None else (t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t))
+    s = CellSums(*(host(t) for t in sums))
+    on = s.present.astype(bool) & (s.area > 0)
+    nan = np.where(on, 0.0, np.nan)
+    a = s.area.astype(np.int64)
+    y0, x0 = s.bbox[..., 0].astype(np.int64), s.bbox[..., 1].astype(np.int64)
+    bh, bw = s.bbox[..., 2] - y0, s.bbox[..., 3] - x0
+    sy, sx, syy, sxx, sxy = (s.moments[..., k].astype(np.int64) for k in range(5))
+    # re-centred on the box origin: the results lie in [0, 2^60], so int64 arithmetic (which wraps) is exact (DESIGN 4q)
+    ry, rx = sy - a * y0, sx - a * x0
+    ryy, rxx = syy - 2 * y0 * sy + a * y0 * y0, sxx - 2 * x0 * sx + a * x0 * x0
+    rxy = sxy - y0 * sx - x0 * sy + a * x0 * y0
+    myy, mxx, mxy = _exact_variance(on, a, ryy, ry, ry), _exact_variance(on, a, rxx, rx, rx), _exact_variance(on, a, rxy, ry, rx)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        af = a.astype(np.float64) + nan
+        centroid = np.stack([y0 + ry / af, x0 + rx / af], axis=-1)
+        half, diff = (mxx + myy) / 2, (mxx - myy) / 2
+        root = np.hypot(diff, mxy)
+        l1, l2 = half + root, np.maximum(half - root, 0.0)
+        ecc = np.where(l1 > 0, np.sqrt(np.clip(1 - l2 / np.where(l1 > 0, l1, 1.0), 0.0, 1.0)), 0.0) + nan
+        orientation = 0.5 * np.arctan2(2 * mxy, mxx - myy)
+        perimeter = (s.frame + s.open + s.contact).astype(np.float64) + nan
+        contact_fraction = s.contact / perimeter
+        extent = af / (bh * bw).astype(np.float64)
+        mean = std = lo = hi = None
+        if s.v_sum is not None:
+            mean = s.v_sum / af
+            if s.v_sum.dtype.kind == "f":
+                var = s.v_sum2 / af - mean * mean
+            else:
+                var = _exact_variance(on, a, s.v_sum2.astype(np.int64), s.v_sum.astype(np.int64), s.v_sum.astype(np.int64))
+            std = np.sqrt(np.maximum(var, 0.0))
+            lo, hi = s.v_min.astype(np.float64) + nan, s.v_max.astype(np.float64) + nan
+    return CellProps(area=af, centroid=centroid, bbox=s.bbox, moments_central=np.stack([myy, mxx, mxy], axis=-1),
+                     axis_major=4 * np.sqrt(l1), axis_minor=4 * np.sqrt(l2), eccentricity=ecc, orientation=orientation,
+                     equivalent_diameter=np.sqrt(4 * af / np.pi), extent=extent, perimeter=perimeter, contact_fraction=contact_fraction,
+                     touches_frame=(s.frame > 0) & on, mean=mean, std=std, min=lo, max=hi)
+
+
+def cell_props(labels, image=None):
+    """props_from_sums(cell_sums(labels, image)): the per-cell properties of an instance map (and of an image under it)."""
+    return props_from_sums(cell_sums(labels, image))
+
+
+def select_cells(labels, keep, *, renumber=False):
+    """Drop or renumber cells by any per-id decision (unet_remap_labels), e.g.
+    select_cells(lab, torch.from_numpy(props.eccentricity < 0.95).cuda()), which generalises remove_small to every measured
+    property.  labels: int32 / int64 ids [H,W] or [B,H,W] on a HIP device, as cell_sums takes them; keep: a bool tensor
+    [n_max+1] (one decision for the batch) or [B, n_max+1] (one per image) on the same device.  Returns an int32 map of the
+    labels' shape: a pixel keeps its id if keep[id] is true, else becomes 0; keep[0] is ignored (background stays 0).
+    renumber=True maps the kept ids to 1..k in increasing order of the old id (per image with a per-image keep).  A pixel whose
+    id is outside [0, n_max] raises ValueError (the status word is read back once); host tensors raise NotImplementedError."""
+    (lab,) = _id_maps("select_cells", "unet_remap_labels", labels)
+    if not torch.is_tensor(keep) or keep.dtype != torch.bool or keep.dim() not in (1, 2) or keep.shape[-1] < 1:
+        raise ValueError("select_cells: keep must be a bool tensor [n_max+1] or [B, n_max+1]")
+    _device_only("select_cells", "unet_remap_labels", keep)
+    import _hip
+    B, H, W = lab.shape
+    if keep.dim() == 2 and keep.shape[0] != B:
+        raise ValueError("select_cells: keep holds %d images, the labels %d" % (keep.shape[0], B))
+    if max(H, W) > MEASURE_EDGE:
+        raise ValueError("select_cells: H and W must be <= %d, got %d x %d" % (MEASURE_EDGE, H, W))
+    n_max = keep.shape[-1] - 1
+    if n_max >= 1 << 24:
+        raise ValueError("select_cells: ids must be below 2^24, keep has %d entries" % (n_max + 1))
+    k = keep.clone()
+    k[..., 0] = False
+    ids = torch.cumsum(k, dim=-1, dtype=torch.int32) if renumber else torch.arange(n_max + 1, dtype=torch.int32, device=lab.device)
+    table = torch.where(k, ids, torch.zeros((), dtype=torch.int32, device=lab.device)).contiguous()
+    out = torch.empty(B, H, W, dtype=torch.int32, device=lab.device)
+    status = torch.empty(B, dtype=torch.int64, device=lab.device)
+    _hip.run("unet_remap_labels", lab.device, _hip.ptr(lab), 0 if lab.dtype == torch.int64 else 2, B, H, W, _hip.ptr(table), n_max,
+             n_max + 1 if keep.dim() == 2 else 0, _hip.ptr(out), _hip.ptr(status))
+    bad = int(status.sum())
+    if bad:
+        raise ValueError("select_cells: %d pixels hold ids outside [0, %d]" % (bad, n_max))
+    return out[0] if labels.dim() == 2 else out
 
 
 SegMeasure = collections.namedtuple("SegMeasure", "seg jaccard_sum n_gt n_matched n_pred per_image jaccard")

@@ -7,6 +7,8 @@ An extension: segment(unet, images) is the paper's overlap-tile inference (Ronne
 images of any size and shape, [H,W] in, [H,W] mask out (unet_tile_gather, unet_forward, unet_tile_stitch); tile_grid
 is its geometry.  segment(..., views=...) averages the class probabilities over dihedral views of each image (apply_view,
 undo_view, view_shape, parse_views; unet_tile_gather_view, unet_tile_stitch_view)."""
+import functools
+import inspect
 import os
 from time import time
 
@@ -14,7 +16,7 @@ import numpy as np
 import torch
 
 import _hip
-from functions import _area, clean_mask, evaluation_metrics, label_cells, metrics_from_counts, shape_seeds, split_cells
+from functions import _area, cell_props, clean_mask, evaluation_metrics, label_cells, metrics_from_counts, shape_seeds, split_cells
 import optim as hip_optim
 
 TILE_MARGIN = 92        # context each side of a tile's output that the valid convolutions eat: (S - So) / 2
@@ -249,6 +251,28 @@ def _parse_clean(v, n_classes):
     return kw
 
 
+def _measured(fn):
+    """segment with the keyword measure: the call as it is, then functions.cell_props of the instance map it returned and of the
+    images it was given, appended to the returned tuple.  The checks of measure come before any work."""
+    sig = inspect.signature(fn)
+
+    @functools.wraps(fn)
+    def segment(*args, measure=False, **kw):
+        if measure not in (False, True):
+            raise ValueError("segment: measure must be False or True, got %r" % (measure,))
+        if not measure:
+            return fn(*args, **kw)
+        call = sig.bind(*args, **kw)
+        call.apply_defaults()
+        if not call.arguments["return_instances"]:
+            raise ValueError("segment: measure needs return_instances=True")
+        out = fn(*args, **kw)
+        images = call.arguments["images"]
+        return out + (cell_props(out[-1], images if images.dtype == torch.float32 else images.to(torch.float32)),)
+    return segment
+
+
+@_measured
 def segment(unet, images, tile_size=None, max_batch=16, normalise=True, return_probs=False, return_instances=False, views=None,
             clean=None, shape_split=None, split=None):
     """Segment images of any size and shape with the overlap-tile strategy; returns the int64 argmax mask of the same
@@ -290,6 +314,12 @@ def segment(unet, images, tile_size=None, max_batch=16, normalise=True, return_p
         ValueError): the instance map becomes split_by_shape(mask, h, min_radius), touching cells split at the h-maxima of the
         mask's own distance map (functions.shape_seeds, functions.split_cells), on the same stream after the last stitch.  It
         reads the mask alone, so it works with views= as it does without.
+    measure: keyword only, False or True (needs return_instances, else ValueError): the returned tuple gains, after the
+        instance map, the functions.CellProps of functions.cell_props(instances, images): one row of shape and intensity
+        properties per cell of the final instance map (after clean and split), the intensities those of the input images as
+        given (not normalised).  The tuple is then (mask[, prob], instances, props).  It is a step on the call's results and is
+        added by the decorator _measured above, not by a parameter of this function: inspect.signature shows the parameters
+        above, which tests/test_clean_cpu.py and tests/test_split_cpu.py pin.
     Geometry and mirroring: tile_grid."""
     if not images.is_cuda:
         raise RuntimeError("segment: the HIP path needs the images on a HIP device (got %s); there is no CPU fallback - "

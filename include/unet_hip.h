@@ -360,6 +360,37 @@ int unet_label_components_conn(const void *mask, int dtype, int B, int H, int W,
 size_t unet_clean_mask_scratch_bytes(int B, int H, int W);
 int unet_clean_mask(const void *mask, int dtype, int B, int H, int W, int connectivity, int fill, long long max_hole_area,
                     long long min_area, int drop_border, void *out, void *action_u8, void *info_i64, void *scratch, void *stream);
+/* One row of exact integers per cell of an instance map, and of an image under it (measure.hip; functions.cell_sums; what
+ * scipy.ndimage's sum_labels, find_objects, center_of_mass, minimum and maximum give one quantity at a time).  labels [B,H,W] of
+ * label_dtype 0 = int64 or 2 = int32, 0 = background, ids anywhere in [0, n_max], n_max < 2^24, not necessarily consecutive or
+ * connected.  image: NULL, or [B,H,W] of image_dtype 0 = int64, 2 = int32, 3 = uint8 with values in [0, 65536), or 1 = float32
+ * with finite values.  Row i of image b (row 0 = the background, treated like any other id), over the pixels (y, x) with id i:
+ *   area_i64    [B][n_max+1]    : pixels
+ *   bbox_i32    [B][n_max+1][4] : y0, x0, y1, x1, half-open like scipy.ndimage.find_objects
+ *   moments_i64 [B][n_max+1][5] : sum y, sum x, sum y^2, sum x^2, sum x y
+ *   edges_i64   [B][n_max+1][3] : over the four sides of every pixel: frame (the side lies on the image frame), open (the
+ *                                 neighbour has id 0 and i != 0), contact (the neighbour has another id; for i = 0 any non-zero
+ *                                 id).  An edge between two ids counts once for each; the three sum to the crack-length perimeter
+ *   vsum_64     [B][n_max+1][2] : sum v, sum v^2: int64 and exact for an integer image, fp64 for a float32 one (v^2 exact, the
+ *                                 sums rounded per add; a run of equal ids in a row is summed in fixed order, the runs in arrival
+ *                                 order).  May be NULL without an image and is not written then
+ *   vrange_32   [B][n_max+1][2] : min v, max v, exact: int32, or float32 for a float32 image.  As vsum_64
+ *   present_u8  [B][n_max+1]    : area > 0.  Every field of an absent id is 0
+ *   status_u64  [B][2]          : pixels whose id is outside [0, n_max] (they index nothing and count nowhere else), pixels whose
+ *                                 image value is refused (they add nothing to vsum and vrange)
+ * Two memsets and two launches on the stream, no read-back; every integer is the same in every run; the cost does not depend on
+ * the number of cells.  Limits: H, W <= 32768, B <= 65535: every sum fits 64 bits.  Another dtype, a NULL pointer, an image without vsum_64
+ * and vrange_32, and a size over the limit return an error and write nothing.
+ * scratch: unet_cell_sums_scratch_bytes(B, n_max) (128 bytes per row), initialised by the call.                              */
+size_t unet_cell_sums_scratch_bytes(int B, int n_max);
+int unet_cell_sums(const void *labels, int label_dtype, const void *image, int image_dtype, int B, int H, int W, int n_max, void *area_i64,
+                   void *bbox_i32, void *moments_i64, void *edges_i64, void *vsum_64, void *vrange_32, void *present_u8, void *status_u64,
+                   void *scratch, void *stream);
+/* out_i32 [B,H,W] = map_i32[b * map_stride + labels[b,y,x]] (measure.hip; functions.select_cells): labels as above, map_stride 0
+ * (one map [n_max+1] for the batch) or >= n_max + 1.  A pixel whose id is outside [0, n_max] becomes 0 and is counted in
+ * status_u64 [B].  Limits and errors as above.                                                                               */
+int unet_remap_labels(const void *labels, int label_dtype, int B, int H, int W, const void *map_i32, int n_max, long long map_stride,
+                      void *out_i32, void *status_u64, void *stream);
 /* The integers of the Cell Tracking Challenge SEG measure, the score behind the goals of trainer.py:20-26 (Ronneberger et al.
  * 2015, Table 2): gt_i32, pred_i32 id maps int32 [B,H,W], 0 = background, gt ids anywhere in [0, ng_max] (not necessarily
  * consecutive, an object not necessarily connected), pred ids in [0, np_max]; ng_max, np_max < 2^24.
