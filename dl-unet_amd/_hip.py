@@ -111,6 +111,11 @@ _SIGS = {
     "unet_geodesic_init": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]),
     "unet_geodesic_sweeps": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_int, vp, C.c_int, vp, vp]),
     "unet_geodesic_finish": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_longlong, vp, vp, vp, vp, vp, vp]),
+    "unet_flood_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "unet_flood_init": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]),
+    "unet_flood_sweeps": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_int, vp, C.c_int, vp, vp]),
+    "unet_flood_assign": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp]),
+    "unet_flood_finish": (C.c_int, [C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp]),
     "unet_distance_map_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "unet_distance_map": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
     "unet_reconstruct_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),

@@ -13,6 +13,8 @@ warp_labels and warping_error add that table's third column: the topology-preser
 prediction (unet_warp_init / unet_warp_sweeps / unet_warp_finish) and the disagreement it leaves.
 split_cells is the instance post-processing after label_cells: seeds grown back inside a mask along 4-neighbour steps until two
 growths meet (unet_geodesic_init / unet_geodesic_sweeps / unet_geodesic_finish), which splits touching cells.
+watershed is the same growth led by an image: seeded flooding of an intensity landscape, plateaus cut at their geodesic midline
+(unet_flood_init / unet_flood_sweeps / unet_flood_assign / unet_flood_finish).
 distance_map, reconstruct and shape_seeds give it seeds from the shape of the mask alone: the exact interior distance map
 (unet_distance_map), grey reconstruction by dilation (unet_reconstruct_init / unet_reconstruct_sweeps / unet_reconstruct_finish),
 and the h-maxima of the distance map with a minimum radius, labelled (unet_shape_heights / unet_shape_lower / unet_shape_maxima).
@@ -704,7 +706,8 @@ def split_cells(seeds, mask, *, max_steps=None, orphans='drop', return_distance=
     the launches the growth needed, the final one that changed nothing included.
     Exact, on the device (unet_geodesic_init / unet_geodesic_sweeps / unet_geodesic_finish): _launches launches are enqueued,
     their change counts read back in one copy, and the loop ends at the first launch that changed nothing; _launches changes no
-    result.  This is no watershed on intensities, and growth is 4-connected.  Unequal shapes, max_steps < 0, a bad orphans,
+    result.  The growth is blind to any image and 4-connected; watershed (below) is the one that follows an intensity landscape,
+    and equals this on a constant image.  Unequal shapes, max_steps < 0, a bad orphans,
     negative ids and ids >= 2^24 raise ValueError; host tensors raise NotImplementedError (no CPU path)."""
     if not (torch.is_tensor(seeds) and torch.is_tensor(mask)):
         raise NotImplementedError("split_cells takes tensors on the HIP device (unet_geodesic_init); there is no CPU implementation")
@@ -756,6 +759,104 @@ def split_cells(seeds, mask, *, max_steps=None, orphans='drop', return_distance=
     info = SplitInfo(seeds_outside=outside, unreached=unreached, max_distance=far, launches=launches)
     out = (labels[0] if single else labels, info)
     return out + ((dist[0] if single else dist),) if return_distance else out
+
+
+FloodInfo = collections.namedtuple("FloodInfo", "seeds_outside unreached max_level launches")
+FLOOD_LEVELS = 1 << 16                                                 # levels of watershed are in [0, FLOOD_LEVELS)
+
+
+def watershed(seeds, image, *, mask=None, levels=None, max_level=None, return_levels=False, _launches=8):
+    """Seeded watershed: flood an intensity landscape from markers, Vincent-Soille immersion with exact geodesic influence zones
+    on plateaus.  seeds: int32 / int64 ids [H,W] or [B,H,W] on a HIP device, 0 = no seed, ids in [1, 2^24); image: the same
+    shape; mask: optional, the same shape, of any dtype _int_code takes: the region is mask != 0, everything without a mask.
+    Every pixel has an integer level v in [0, 65536): an integer (or bool) image is read as it is (levels must be None), a float
+    image (taken as float32) needs levels in [1, 65536] and gives v = min(levels - 1, max(0, floor(x * levels))), the product in
+    fp32.  A seed pixel in the region is a source with key (L, d) = (0, 0), whatever its own level: the markers are imposed as
+    minima.  A 4-neighbour step onto a region pixel q turns (L, d) into (L, d + 1) if v(q) <= L and into (v(q), 1) otherwise;
+    key(q) is the lexicographic minimum over all region paths from a source: L(q) the pass height at which the flood reaches q,
+    d(q) the steps inside the plateau of that height from the pixels flooded before it.  Neighbour p is a parent of q when its key
+    extends to exactly key(q); a source keeps its seed id and every other reached pixel takes the least id among its parents.
+    Every other pixel gets 0: pixels outside the region (a seed pixel there is no seed), pixels no source reaches, pixels with
+    L > max_level (None: unlimited).  So plateaus are cut at their geodesic midline, ties go to the smaller id, and on a constant
+    image the result is split_cells', bit for bit.  It is not bit-equal to skimage.segmentation.watershed, whose plateau
+    handling depends on the order of its queue.
+    Returns (labels, FloodInfo) or, with return_levels, (labels, FloodInfo, pass_level, dist): labels int32 of the input's
+    shape; pass_level and dist int32, L and d where labels != 0 and -1 elsewhere; FloodInfo(seeds_outside, unreached, max_level,
+    launches): int64 numpy [B], the seed pixels outside the region, the region pixels left 0 and the largest L written, and the
+    pair (launches of stage 1, launches of stage 2), the final one of each that changed nothing included.
+    Exact, on the device (unet_flood_init / unet_flood_sweeps / unet_flood_assign / unet_flood_finish), with split_cells' loop
+    for each stage: _launches launches are enqueued, their change counts read back in one copy, and the loop ends at the first
+    launch that changed nothing; _launches changes no result.  To flood a shape instead of an intensity, pass the inverted
+    distance map as the image: watershed(shape_seeds(mask)[0], d.max() - d, mask=mask) with d = distance_map(mask) scaled into
+    [0, 65536).  Unequal shapes, other seed dtypes, levels or max_level out of range, image values outside [0, 65536) or not
+    finite (counted by the kernel), negative ids and ids >= 2^24 raise ValueError; host tensors raise NotImplementedError (no CPU
+    path)."""
+    tensors = [seeds, image] + ([] if mask is None else [mask])
+    if any(not torch.is_tensor(t) for t in tensors):
+        raise NotImplementedError("watershed takes tensors on the HIP device (unet_flood_init); there is no CPU implementation")
+    if any(t.shape != seeds.shape for t in tensors) or seeds.dim() not in (2, 3):
+        raise ValueError("watershed takes seeds, an image and a mask of equal shape [H,W] or [B,H,W], got %s"
+                         % ", ".join(str(tuple(t.shape)) for t in tensors))
+    if seeds.dtype not in (torch.int32, torch.int64):
+        raise ValueError("watershed takes int32 or int64 seed ids, got %s" % seeds.dtype)
+    if image.is_complex():
+        raise ValueError("watershed takes a real image, got %s" % image.dtype)
+    if image.is_floating_point():
+        if isinstance(levels, bool) or not isinstance(levels, int) or not 1 <= levels <= FLOOD_LEVELS:
+            raise ValueError("watershed: a float image needs levels, an int in [1, %d], got %r" % (FLOOD_LEVELS, levels))
+    elif levels is not None:
+        raise ValueError("watershed: levels is for float images; an integer image is read as it is, got levels=%r for %s" % (levels, image.dtype))
+    if max_level is None or max_level == math.inf:
+        top = -1
+    else:
+        if not max_level >= 0:
+            raise ValueError("watershed: max_level must be None or a number >= 0, got %r" % (max_level,))
+        top = min(int(math.floor(max_level)), FLOOD_LEVELS)
+    if int(_launches) < 1:
+        raise ValueError("watershed: _launches must be >= 1")
+    planes = [_planes("watershed", t) for t in tensors]
+    _device_only("watershed", "unet_flood_init", *tensors)
+    import _hip
+    _id_range("watershed", planes[0])
+    sd = planes[0].int()
+    im, im_code = _int_code(planes[1], uint8_ok=True)
+    mk, mk_code = _int_code(planes[2], uint8_ok=True) if mask is not None else (None, 0)
+    B, H, W = sd.shape
+    dev = sd.device
+    counts = torch.empty(3, B, dtype=torch.int32, device=dev)          # the library's u32 words: at most H * W < 2^31
+    status = torch.empty(2, B, dtype=torch.int64, device=dev)
+    scratch = _hip.scratch("unet_flood", dev, B, H, W)
+    _hip.run("unet_flood_init", dev, _hip.ptr(sd), _hip.ptr(im), im_code, levels or 0, _hip.ptr(mk), mk_code, B, H, W, _hip.ptr(counts[0]),
+             _hip.ptr(status), _hip.ptr(scratch))
+    launches = []
+    for stage in (1, 2):                                               # stage 2 starts after an idle launch of stage 1 was seen
+        n = 0
+        while True:
+            slots = torch.empty(_launches, B, dtype=torch.int32, device=dev)
+            if stage == 1:
+                _hip.run("unet_flood_sweeps", dev, B, H, W, top, _launches, _hip.ptr(slots), 0, _hip.ptr(scratch))
+            else:
+                _hip.run("unet_flood_assign", dev, B, H, W, _launches, _hip.ptr(slots), 0, _hip.ptr(scratch))
+            if stage == 1 and n == 0:                                   # behind the first round: no wait of its own
+                bad = int(status[1].sum())
+                if bad:
+                    raise ValueError("watershed: %d pixels hold an image value that is not finite" % bad if im_code == 1 else
+                                     "watershed: %d pixels hold an image value outside [0, %d)" % (bad, FLOOD_LEVELS))
+            idle = ~slots.cpu().numpy().any(axis=1)
+            if idle.any():                                              # a launch that changed nothing: so did all after it
+                n += int(np.argmax(idle)) + 1
+                break
+            n += _launches
+        launches.append(n)
+    labels = torch.empty(B, H, W, dtype=torch.int32, device=dev)
+    lev, dist = (torch.empty(2, B, H, W, dtype=torch.int32, device=dev) if return_levels else (None, None))
+    _hip.run("unet_flood_finish", dev, B, H, W, _hip.ptr(labels), _hip.ptr(lev), _hip.ptr(dist), _hip.ptr(counts[1]), _hip.ptr(counts[2]),
+             _hip.ptr(scratch))
+    outside, unreached, high = counts.cpu().numpy().astype(np.int64)
+    single = seeds.dim() == 2
+    info = FloodInfo(seeds_outside=outside, unreached=unreached, max_level=high, launches=tuple(launches))
+    out = (labels[0] if single else labels, info)
+    return out + ((lev[0], dist[0]) if single else (lev, dist)) if return_levels else out
 
 
 _EDGES = {'ignore': 0, 'background': 1}

@@ -16,7 +16,8 @@ import numpy as np
 import torch
 
 import _hip
-from functions import _area, cell_props, clean_mask, evaluation_metrics, label_cells, metrics_from_counts, shape_seeds, split_cells
+from functions import (FLOOD_LEVELS, _area, cell_props, clean_mask, evaluation_metrics, label_cells, metrics_from_counts, shape_seeds,
+                       split_cells, watershed)
 import optim as hip_optim
 
 TILE_MARGIN = 92        # context each side of a tile's output that the valid convolutions eat: (S - So) / 2
@@ -216,6 +217,26 @@ def split_by_shape(mask, h=2.0, min_radius=0.0, edge='ignore'):
     return split_cells(seeds, mask, orphans='keep')[0]
 
 
+def split_by_watershed(mask, fg_prob, high, levels=64):
+    """The instance map of a foreground mask with touching cells split where the foreground probability dips: the cores
+    label_cells(fg_prob >= high)[0] are the seeds, functions.watershed floods the landscape 1 - fg_prob (float32, quantised to
+    `levels` levels) from them inside mask != 0, so two growths meet on the ridge of low probability between two cores and not
+    halfway between them as in split_instances; a component of the mask without a core stays a cell, numbered after the seeds
+    as split_cells(orphans='keep') numbers it.  mask and fg_prob [H,W] or [B,H,W] on a HIP device; returns int32 ids of the same
+    shape."""
+    seeds = label_cells(fg_prob >= high)[0]
+    labels = watershed(seeds, 1 - fg_prob.float(), mask=mask, levels=levels)[0]
+    rest = label_cells((mask != 0) & (labels == 0))[0]
+    return torch.where(rest > 0, rest + seeds.amax(dim=(-2, -1), keepdim=True), labels)
+
+
+def _check_split(split, return_instances):
+    if not return_instances:
+        raise ValueError("segment: split needs return_instances=True")
+    if isinstance(split, bool) or not isinstance(split, (int, float)) or not 0 < split <= 1:
+        raise ValueError("segment: split must be None or a number in (0, 1], got %r" % (split,))
+
+
 def _parse_shape_split(v):
     """shape_split of segment -> (h, min_radius); ValueError for anything but a number >= 0 or a pair of them."""
     def number(x):
@@ -251,28 +272,48 @@ def _parse_clean(v, n_classes):
     return kw
 
 
-def _measured(fn):
-    """segment with the keyword measure: the call as it is, then functions.cell_props of the instance map it returned and of the
-    images it was given, appended to the returned tuple.  The checks of measure come before any work."""
+def _with_steps(fn):
+    """segment with the keywords watershed and measure, two steps on the call's results.  watershed: the call without its split
+    (mask and probabilities only), then split_by_watershed of them as the instance map.  measure: functions.cell_props of the
+    final instance map and of the images the call was given, appended to the returned tuple.  The checks of both come before any
+    work."""
     sig = inspect.signature(fn)
 
     @functools.wraps(fn)
-    def segment(*args, measure=False, **kw):
+    def segment(*args, measure=False, watershed=None, **kw):
         if measure not in (False, True):
             raise ValueError("segment: measure must be False or True, got %r" % (measure,))
-        if not measure:
+        if watershed is False:
+            watershed = None
+        if watershed is not None and watershed is not True and not (isinstance(watershed, int) and 1 <= watershed <= FLOOD_LEVELS):
+            raise ValueError("segment: watershed must be None, True (64 levels) or an int in [1, %d], got %r" % (FLOOD_LEVELS, watershed))
+        if not measure and watershed is None:
             return fn(*args, **kw)
         call = sig.bind(*args, **kw)
         call.apply_defaults()
-        if not call.arguments["return_instances"]:
+        given = call.arguments
+        if measure and not given["return_instances"]:
             raise ValueError("segment: measure needs return_instances=True")
-        out = fn(*args, **kw)
-        images = call.arguments["images"]
+        if watershed is None:
+            out = fn(*args, **kw)
+        else:
+            if given["split"] is None:
+                raise ValueError("segment: watershed needs split=high, the cores it floods from")
+            if given["shape_split"] is not None:
+                raise ValueError("segment: watershed floods the probabilities from the cores of split; it does not combine with shape_split")
+            _check_split(given["split"], given["return_instances"])
+            mask, prob = fn(**dict(given, return_probs=True, return_instances=False, split=None))
+            fg = prob if getattr(given["unet"], 'n_classes', 2) == 2 else 1 - prob.select(-3, 0)
+            inst = split_by_watershed(mask, fg, float(given["split"]), 64 if watershed is True else watershed)
+            out = (mask,) + ((prob,) if given["return_probs"] else ()) + (inst,)
+        if not measure:
+            return out
+        images = given["images"]
         return out + (cell_props(out[-1], images if images.dtype == torch.float32 else images.to(torch.float32)),)
     return segment
 
 
-@_measured
+@_with_steps
 def segment(unet, images, tile_size=None, max_batch=16, normalise=True, return_probs=False, return_instances=False, views=None,
             clean=None, shape_split=None, split=None):
     """Segment images of any size and shape with the overlap-tile strategy; returns the int64 argmax mask of the same
@@ -318,8 +359,14 @@ def segment(unet, images, tile_size=None, max_batch=16, normalise=True, return_p
         instance map, the functions.CellProps of functions.cell_props(instances, images): one row of shape and intensity
         properties per cell of the final instance map (after clean and split), the intensities those of the input images as
         given (not normalised).  The tuple is then (mask[, prob], instances, props).  It is a step on the call's results and is
-        added by the decorator _measured above, not by a parameter of this function: inspect.signature shows the parameters
+        added by the decorator _with_steps above, not by a parameter of this function: inspect.signature shows the parameters
         above, which tests/test_clean_cpu.py and tests/test_split_cpu.py pin.
+    watershed: keyword only, None, True (64 levels) or an int in [1, 65536] (needs split, not together with shape_split, else
+        ValueError): the instance map becomes split_by_watershed(mask, fg_prob, split, levels): the cores fg_prob >= split flood
+        the landscape 1 - fg_prob inside the mask (functions.watershed), so the cut between two touching cells follows the dip in
+        foreground probability where split alone puts it halfway between the cores.  clean and measure compose with it as they do
+        with split.  Added by the same decorator.  Flooding the inverted distance map from the seeds of functions.shape_seeds is
+        a composition of functions.watershed and functions.distance_map and has no option here.
     Geometry and mirroring: tile_grid."""
     if not images.is_cuda:
         raise RuntimeError("segment: the HIP path needs the images on a HIP device (got %s); there is no CPU fallback - "
@@ -338,10 +385,7 @@ def segment(unet, images, tile_size=None, max_batch=16, normalise=True, return_p
     if max_batch < 1:
         raise ValueError("segment: max_batch must be >= 1")
     if split is not None:
-        if not return_instances:
-            raise ValueError("segment: split needs return_instances=True")
-        if isinstance(split, bool) or not isinstance(split, (int, float)) or not 0 < split <= 1:
-            raise ValueError("segment: split must be None or a number in (0, 1], got %r" % (split,))
+        _check_split(split, return_instances)
     if shape_split is not None:
         if not return_instances:
             raise ValueError("segment: shape_split needs return_instances=True")

@@ -498,6 +498,49 @@ int unet_geodesic_sweeps(int B, int H, int W, long long max_steps, int n_launche
                          void *stream);
 int unet_geodesic_finish(int B, int H, int W, long long max_steps, void *out_i32, void *dist_i32, void *unreached_u32, void *max_dist_u32,
                          void *scratch, void *stream);
+/* Seeded watershed: flooding of an intensity landscape from markers inside a region (functions.watershed,
+ * tester.split_by_watershed; the definition in full: DESIGN.md section 4r).  The region is mask != 0, or every pixel when mask is
+ * NULL.  Every pixel has a level v in [0, 65536); a seed pixel inside the region is a source with key (L, d) = (0, 0); one
+ * 4-neighbour step onto a region pixel q turns a key (L, d) into (L, d + 1) if v(q) <= L and into (v(q), 1) otherwise.  Stage 1:
+ * key(q) = the lexicographic minimum over all region paths from a source (L the pass height at which the flood reaches q, d the
+ * steps inside the plateau of that height).  Stage 2: neighbour p is a parent of q when its key extends to exactly key(q); a source
+ * keeps its id, every other reached pixel takes the least id among its parents.  Unreached pixels, pixels with L > max_level and
+ * pixels outside the region get 0.  On a constant image this is unet_geodesic_*'s growth bit for bit.  Five calls, all on one
+ * stream, none of which synchronises:
+ *   unet_flood_init    seeds_i32 [B,H,W], 0 = no seed, ids in [1, 2^24); image [B,H,W] of image_dtype 0 = int64, 1 = float32,
+ *                      2 = int32, 3 = uint8; mask [B,H,W] (may be NULL) of mask_dtype with the same codes.  Integer images are
+ *                      read as they are; a float32 image needs levels in [1, 65536] and gives
+ *                      v = min(levels - 1, max(0, floorf(x * (float)levels))), the product in fp32.  Writes the level plane
+ *                      (uint16), the key plane (L << 32 | d, or a code for "outside the region" or "not reached yet") and the id
+ *                      plane into the scratch; neither input is read again.  seeds_outside_u32 [B] = the seed pixels outside the
+ *                      region; status_u64 [2][B]: [0][b] = the pixels whose seed id is outside [0, 2^24) (no seed, in no other
+ *                      count), [1][b] = the pixels whose image value is outside [0, 65536) or not finite (read as level 0).
+ *   unet_flood_sweeps  stage 1, the protocol of unet_geodesic_sweeps: enqueues n_launches launches, in each a workgroup relaxes its
+ *                      64 x 64 tile to local convergence and hands off at the kernel boundary (two key planes, ping-pong);
+ *                      changed_out_u32 [slots][B]: launch l first clears, then fills slot first_slot + l with the pixels whose
+ *                      key it lowered; other slots are untouched.  A launch that changes nothing leaves the state as it is, and
+ *                      so does every launch after it.  max_level < 0: unlimited; else keys with L > max_level are never stored,
+ *                      which changes no key with L <= max_level.
+ *   unet_flood_assign  stage 2, the same protocol over the two id planes (the slots count the ids lowered).  It takes on trust
+ *                      that the keys are final: call it only after the caller has SEEN a launch of unet_flood_sweeps that changed
+ *                      nothing, and call unet_flood_sweeps no more afterwards.  On keys that are not final the ids it leaves are
+ *                      those of no definition.
+ *   unet_flood_finish  call it after a launch of unet_flood_assign that changed nothing.  out_i32 [B,H,W] = the ids;
+ *                      pass_level_i32 and dist_i32 [B,H,W] (each may be NULL) = L and d, -1 where out is 0; unreached_u32 [B] =
+ *                      the region pixels with out = 0; max_level_u32 [B] = the largest L written, 0 when there is none.
+ * Exact integers throughout: any order of relaxation reaches the same fixed point in either stage.  Limits as unet_grow_labels
+ * (H * W < 2^31, H, W, B <= 65535), H != W allowed, down to 1 x 1.
+ * scratch: unet_flood_scratch_bytes(B, H, W), the same buffer for all calls of one flooding: two planes of 64-bit keys, two
+ * planes of 32-bit ids and the plane of 16-bit levels, 26 bytes per pixel (each plane rounded up to 256 bytes), initialised by
+ * unet_flood_init.                                                                                                          */
+size_t unet_flood_scratch_bytes(int B, int H, int W);
+int unet_flood_init(const void *seeds_i32, const void *image, int image_dtype, int levels, const void *mask, int mask_dtype, int B, int H,
+                    int W, void *seeds_outside_u32, void *status_u64, void *scratch, void *stream);
+int unet_flood_sweeps(int B, int H, int W, long long max_level, int n_launches, void *changed_out_u32, int first_slot, void *scratch,
+                      void *stream);
+int unet_flood_assign(int B, int H, int W, int n_launches, void *changed_out_u32, int first_slot, void *scratch, void *stream);
+int unet_flood_finish(int B, int H, int W, void *out_i32, void *pass_level_i32, void *dist_i32, void *unreached_u32, void *max_level_u32,
+                      void *scratch, void *stream);
 /* Seeds from the shape of a mask alone: the distance map of the region, its h-maxima, the domes that are left
  * (functions.distance_map, functions.reconstruct, functions.shape_seeds, tester.split_by_shape; the definitions in full: DESIGN.md
  * section 4o).  The region is mask != 0; mask [B,H,W] of dtype 0 = int64, 1 = float32, 2 = int32, 3 = uint8.  None of these
