@@ -29,15 +29,12 @@
 // counter, a histogram bin or a status word only by an agent-scope add, and n_pairs in pairs_compact likewise; overlap_match,
 // pairs_compact, and every pass of the labelling, reads
 // what an earlier kernel wrote.  No word is handed from one workgroup to another inside a kernel by plain loads and stores.
-#include "elem.hpp"
+#include "ov_table.hpp"
 #include "../../include/unet_hip.h"
 
 namespace unet {
 
 static constexpr int IN_CHUNK = 1024;                        // pixels per workgroup of inst_count / inst_rank: 256 threads x 4
-static constexpr unsigned long long OV_EMPTY = ~0ull;        // never a key: b <= 65534
-static constexpr int OV_ID_BITS = 24;
-static constexpr int OV_ID_MAX = (1 << OV_ID_BITS) - 1;
 
 // roots among this thread's 4 consecutive pixels, as a bit mask
 __device__ __forceinline__ int inst_roots(const int *__restrict__ L, size_t npx, size_t e0)
@@ -93,29 +90,6 @@ __global__ __launch_bounds__(256) void inst_write_kernel(int *__restrict__ label
 }
 
 // ---- overlaps ---------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ unsigned long long ov_hash(unsigned long long x)
-{
-    x ^= x >> 33; x *= 0xff51afd7ed558ccdull;
-    x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ull;
-    return x ^ (x >> 33);
-}
-
-// adds n to the counter of `key`; false when the key is absent and no slot is free
-__device__ __forceinline__ bool ov_insert(unsigned long long *keys, unsigned *cnt, size_t slots, unsigned long long key, unsigned n)
-{
-    size_t h = ov_hash(key) & (slots - 1);
-    for (size_t probe = 0; probe < slots; ++probe) {
-        unsigned long long seen = OV_EMPTY;
-        if (__hip_atomic_compare_exchange_strong(&keys[h], &seen, key, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ||
-            seen == key) {
-            __hip_atomic_fetch_add(&cnt[h], n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            return true;
-        }
-        h = (h + 1) & (slots - 1);
-    }
-    return false;
-}
-
 // FG = false: unet_instance_overlap (both area histograms, pairs with g, p >= 1).  FG = true: unet_partition_pairs (no histogram,
 // pairs with g >= 1 and any p >= 0: the table restricted to ground-truth foreground, "predicted background" being the column 0)
 template <bool FG>
@@ -254,8 +228,6 @@ int unet_label_components(const void *mask, int dtype, int B, int H, int W, void
 }
 
 struct OvTable { unsigned long long *keys; unsigned *cnt; };
-static size_t ov_key_bytes(size_t slots) { return align_up(slots * sizeof(unsigned long long), 256); }
-static size_t ov_scratch_bytes(size_t slots) { return ov_key_bytes(slots) + align_up(slots * sizeof(unsigned), 256); }
 
 // what unet_instance_overlap (FG = false) and unet_partition_pairs (FG = true) share: the checks, the table carved from the
 // scratch, the clears of everything overlap_fill adds to (FG: no histograms, area_gt and area_pred are null) and its launch

@@ -24,6 +24,9 @@ filled, small cells and cells on the frame dropped, with either connectivity (un
 cell_sums, props_from_sums, cell_props and select_cells are the step after the instance map: one row of exact integers per cell
 (unet_cell_sums), the usual shape and intensity properties formed from them on the host, and the per-id remap that drops or
 renumbers cells by any decision taken on those rows (unet_remap_labels).
+link_frames, tracks_from_links and track_cells carry the instance maps of a time-lapse across frames: for every cell the cell of the
+frame before that it overlaps most (unet_link_frames), the tracks, divisions and the Cell Tracking Challenge's res_track.txt table
+formed from those links on the host, and the maps relabelled by track on the device (unet_remap_labels).
 """
 import collections
 import fractions
@@ -513,6 +516,144 @@ def pair_table(pred_labels, gt_labels, *, _table_slots=None):
     order = np.argsort(k)                                   # distinct unsigned keys b << 48 | g << 24 | p: the order of (b, g, p)
     k, c = k[order], c[order]
     return tuple((k >> np.uint64(s) & np.uint64(m)).astype(np.int64) for s, m in ((48, 0xFFFF), (24, 0xFFFFFF), (0, 0xFFFFFF))) + (c,)
+
+
+# ---- linking cells across frames ----------------------------------------------------------------------------------------
+
+MAX_FRAMES = 65535                                                      # T of unet_link_frames: the frame index is the key's top 16 bits
+FrameLinks = collections.namedtuple("FrameLinks", "area pred pred_overlap")
+
+
+def _link_frames(name, labels, reach, slots):
+    """The checks and the device half of link_frames: (int32 labels [T,H,W], n_max, FrameLinks)."""
+    if torch.is_tensor(labels) and labels.dim() != 3:
+        raise ValueError("%s takes a time-lapse of id maps [T,H,W], got %s" % (name, tuple(labels.shape)))
+    if torch.is_tensor(labels) and labels.shape[0] > MAX_FRAMES:
+        raise ValueError("%s: at most %d frames, got %d" % (name, MAX_FRAMES, labels.shape[0]))
+    if reach is not None and not (isinstance(reach, (int, float)) and not isinstance(reach, bool) and reach >= 0):
+        raise ValueError("%s: reach must be None or a number >= 0, got %r" % (name, reach))
+    (lab,) = _id_maps(name, "unet_link_frames", labels)
+    (n_max,) = _id_range(name, lab)
+    import _hip
+    lab = lab.int()
+    src = lab if reach is None else grow_cells(lab, reach)              # grown ids are ids of the frame: still in [0, n_max]
+    T, H, W = lab.shape
+    dev = lab.device
+    out = torch.empty(3, T, n_max + 1, dtype=torch.int32, device=dev)   # the library's u32 words: counts of at most H * W < 2^31
+    status = torch.empty(T, 2, dtype=torch.int64, device=dev)
+    slots = 1 << (min(4 * (T - 1) * n_max, T * H * W) + 1024 - 1).bit_length() if slots is None else int(slots)
+    while True:                                                         # _pair_counts' protocol, one id range for both maps
+        scratch = _hip.scratch("unet_link_frames", dev, T, n_max, slots)
+        _hip.run("unet_link_frames", dev, _hip.ptr(src), _hip.ptr(lab), T, H, W, n_max, slots, _hip.ptr(out[0]), _hip.ptr(out[1]),
+                 _hip.ptr(out[2]), _hip.ptr(status), _hip.ptr(scratch))
+        refused, dropped = (int(v) for v in status.cpu().sum(dim=0))
+        if refused:
+            raise ValueError("%s: %d pixels hold ids outside [0, %d]" % (name, refused, n_max))
+        if not dropped:
+            break
+        slots *= 2                                                      # ends: a table with more slots than pixels cannot fill up
+    return lab, n_max, FrameLinks(*out.cpu().numpy().astype(np.int64))
+
+
+def link_frames(labels, *, reach=None, _table_slots=None):
+    """The overlap links between the consecutive frames of a time-lapse of instance maps, e.g. the instance map of
+    tester.segment(unet, frames, return_instances=True): labels int32 / int64 ids [T,H,W] on a HIP device, 0 = background, ids
+    in [1, 2^24) that mean nothing across frames, not necessarily consecutive or connected.  Returns FrameLinks(area, pred,
+    pred_overlap), int64 numpy arrays [T][n_max+1]: area[t][c] the pixels of id c in frame t (index 0 = background); pred[t][c],
+    for t >= 1 and c >= 1, the id p >= 1 of frame t-1 with the largest |p n c| > 0, the smallest such p on equal overlaps, 0 when
+    no cell of frame t-1 touches c; pred_overlap[t][c] that |p n c|, else 0; row 0 and column 0 are 0.
+    reach=r (a float >= 0): frame t is set against grow_cells(labels, r)[t-1], so a cell that moved up to r px beyond its old
+    outline still finds its predecessor; the areas are those of labels; reach=0 is reach=None.  Exact and on the device
+    (unet_link_frames), the same in every run; the protocol is seg_measure's: the id maximum is read back once, and the pair
+    table is doubled and the call repeated while it reports an overflow.  Negative ids, ids >= 2^24, an input that is not
+    [T,H,W] and T > 65535 raise ValueError; host tensors raise NotImplementedError (no CPU path).
+    tracks_from_links makes tracks of the links; track_cells does both and relabels the maps."""
+    return _link_frames("link_frames", labels, reach, _table_slots)[2]
+
+
+class Tracks(collections.namedtuple("Tracks", "table track_of")):
+    """table: int64 [n,4], one row L B E P per track as in the Cell Tracking Challenge's res_track.txt: label (1..n), first and
+    last frame (counted from 0), label of the parent track or 0.  track_of: int32 [T][n_max+1], track label of id c of frame t,
+    0 for absent ids."""
+    __slots__ = ()
+
+    def ctc_text(self):
+        """The text of res_track.txt: one line `L B E P` per track."""
+        return "".join("%d %d %d %d\n" % tuple(int(v) for v in row) for row in self.table)
+
+
+def _track_rules(name, min_overlap, divisions, max_children):
+    if not (isinstance(min_overlap, (int, float)) and not isinstance(min_overlap, bool) and 0 <= min_overlap <= 1):
+        raise ValueError("%s: min_overlap must be a number in [0, 1], got %r" % (name, min_overlap))
+    if isinstance(max_children, bool) or not isinstance(max_children, (int, np.integer)) or max_children < 1:
+        raise ValueError("%s: max_children must be an int >= 1, got %r" % (name, max_children))
+    if divisions not in (False, True):
+        raise ValueError("%s: divisions must be False or True, got %r" % (name, divisions))
+
+
+def tracks_from_links(links, *, min_overlap=0.0, divisions=True, max_children=2):
+    """Tracks from the FrameLinks of link_frames (or any three integer arrays [T][n_max+1] of that meaning), on the host: the
+    greedy overlap tracker of the U-Net submissions to the Cell Tracking Challenge.  Frames in order, ids in increasing order.
+    The link c -> p = pred[t][c] is accepted iff p > 0 and pred_overlap[t][c] >= min_overlap * area[t][c] (float64).  A cell p
+    of frame t-1 with one accepted claimant is continued by it.  With several, ranked by overlap descending, then id ascending:
+    divisions=True: the first max_children each start a track whose parent is p's track, the rest start tracks with parent 0, and
+    p's track ends at t-1; divisions=False: the first continues p's track and the rest start tracks with parent 0.  A cell
+    nobody claims ends its track; a cell without an accepted link starts a track with parent 0.  Track labels are 1, 2, ... in
+    order of (first frame, cell id).  Returns Tracks(table, track_of)."""
+    _track_rules("tracks_from_links", min_overlap, divisions, max_children)
+    area, pred, over = (np.asarray(a).astype(np.int64) for a in links)
+    if area.ndim != 2 or area.shape[1] < 1 or pred.shape != area.shape or over.shape != area.shape:
+        raise ValueError("tracks_from_links: area, pred and pred_overlap must be three arrays [T][n_max+1] of one shape, got %s"
+                         % ", ".join(str(a.shape) for a in (area, pred, over)))
+    T, N = area.shape
+    track_of = np.zeros((T, N), np.int32)
+    table = []
+    for t in range(T):
+        cells = (np.nonzero(area[t, 1:])[0] + 1).tolist()
+        claimants = {}
+        for c in cells if t else ():
+            p = int(pred[t, c])
+            if p > 0 and float(over[t, c]) >= min_overlap * float(area[t, c]):
+                if p >= N or not track_of[t - 1, p]:
+                    raise ValueError("tracks_from_links: pred[%d][%d] = %d is no cell of frame %d" % (t, c, p, t - 1))
+                claimants.setdefault(p, []).append(c)
+        fate = {}                                                       # c -> (track it continues or 0, parent of the track it starts)
+        for p, cs in claimants.items():
+            mother = int(track_of[t - 1, p])
+            cs.sort(key=lambda c: (-over[t, c], c))
+            if len(cs) == 1 or not divisions:
+                fate[cs[0]] = (mother, 0)
+            else:
+                fate.update((c, (0, mother)) for c in cs[:max_children])
+        for c in cells:
+            goes_on, parent = fate.get(c, (0, 0))
+            if goes_on:
+                table[goes_on - 1][2] = t
+            else:
+                table.append([len(table) + 1, t, t, parent])
+                goes_on = len(table)
+            track_of[t, c] = goes_on
+    return Tracks(np.array(table, np.int64).reshape(-1, 4), track_of)
+
+
+def track_cells(labels, *, reach=None, min_overlap=0.0, divisions=True, max_children=2, _table_slots=None):
+    """A time-lapse of instance maps relabelled so that the same cell keeps the same id: link_frames(labels, reach=reach), then
+    tracks_from_links(links, min_overlap=.., divisions=.., max_children=..), then every pixel's id replaced by its track label on
+    the device (unet_remap_labels with one map per frame); only the [T][n_max+1] rows cross to the host and back.  labels as
+    link_frames takes them, H, W <= 32768.  Returns (track_maps, tracks): track_maps int32 [T,H,W] on the labels' device, 0 where
+    labels is 0; tracks the Tracks, whose ctc_text() is the challenge's res_track.txt for these maps."""
+    if torch.is_tensor(labels) and labels.dim() == 3 and max(labels.shape[1:]) > MEASURE_EDGE:
+        raise ValueError("track_cells: H and W must be <= %d, got %d x %d" % ((MEASURE_EDGE,) + tuple(labels.shape[1:])))
+    _track_rules("track_cells", min_overlap, divisions, max_children)
+    lab, n_max, links = _link_frames("track_cells", labels, reach, _table_slots)
+    tracks = tracks_from_links(links, min_overlap=min_overlap, divisions=divisions, max_children=max_children)
+    import _hip
+    T, H, W = lab.shape
+    table = torch.from_numpy(tracks.track_of).to(lab.device)
+    out = torch.empty(T, H, W, dtype=torch.int32, device=lab.device)
+    status = torch.empty(T, dtype=torch.int64, device=lab.device)
+    _hip.run("unet_remap_labels", lab.device, _hip.ptr(lab), 2, T, H, W, _hip.ptr(table), n_max, n_max + 1, _hip.ptr(out), _hip.ptr(status))
+    return out, tracks
 
 
 RandScores = collections.namedtuple("RandScores", "rand_split rand_merge v_rand rand_error info_split info_merge v_info voi_split "

@@ -6,7 +6,8 @@ written with PIL using torchvision.utils.save_image's conversion (clamp to [0,1]
 An extension: segment(unet, images) is the paper's overlap-tile inference (Ronneberger et al. 2015, Fig. 2) for
 images of any size and shape, [H,W] in, [H,W] mask out (unet_tile_gather, unet_forward, unet_tile_stitch); tile_grid
 is its geometry.  segment(..., views=...) averages the class probabilities over dihedral views of each image (apply_view,
-undo_view, view_shape, parse_views; unet_tile_gather_view, unet_tile_stitch_view)."""
+undo_view, view_shape, parse_views; unet_tile_gather_view, unet_tile_stitch_view).  track(unet, frames) segments a time-lapse
+and links its cells across frames (functions.track_cells; unet_link_frames)."""
 import functools
 import inspect
 import os
@@ -17,7 +18,7 @@ import torch
 
 import _hip
 from functions import (FLOOD_LEVELS, _area, cell_props, clean_mask, evaluation_metrics, label_cells, metrics_from_counts, shape_seeds,
-                       split_cells, watershed)
+                       split_cells, track_cells, watershed)
 import optim as hip_optim
 
 TILE_MARGIN = 92        # context each side of a tile's output that the valid convolutions eat: (S - So) / 2
@@ -466,3 +467,20 @@ def segment(unet, images, tile_size=None, max_batch=16, normalise=True, return_p
         inst = inst[0] if inst is not None else None
     out = (mask,) + ((prob,) if return_probs else ()) + ((inst,) if return_instances else ())
     return out if len(out) > 1 else mask
+
+
+def track(unet, frames, *, reach=None, min_overlap=0.0, divisions=True, max_children=2, **segment_kwargs):
+    """Segment a time-lapse and follow its cells: segment(unet, frames, return_instances=True, **segment_kwargs) on frames
+    [T,H,W], then functions.track_cells(instances, reach=.., min_overlap=.., divisions=.., max_children=..) on the instance map,
+    on the device.  segment_kwargs are segment's own (tile_size, views, clean, split, shape_split, watershed, ...);
+    return_instances, return_probs and measure are not among them.  Returns (mask, track_maps, tracks): the mask of segment;
+    track_maps int32 [T,H,W], 0 where the instance map is 0, else the label of the cell's track, the same from the track's first
+    frame to its last; tracks the functions.Tracks, whose table and ctc_text() are the Cell Tracking Challenge's res_track.txt."""
+    taken = [k for k in ("return_instances", "return_probs", "measure") if k in segment_kwargs]
+    if taken:
+        raise ValueError("track: %s cannot be passed on; track returns (mask, track_maps, tracks)" % ", ".join(taken))
+    if not torch.is_tensor(frames) or frames.dim() != 3:
+        raise ValueError("track: expected frames [T,H,W], got %s" % (tuple(frames.shape) if torch.is_tensor(frames) else type(frames),))
+    mask, instances = segment(unet, frames, return_instances=True, **segment_kwargs)
+    track_maps, tracks = track_cells(instances, reach=reach, min_overlap=min_overlap, divisions=divisions, max_children=max_children)
+    return mask, track_maps, tracks

@@ -422,6 +422,27 @@ size_t unet_partition_pairs_scratch_bytes(int B, size_t table_slots);
 int unet_partition_pairs(const void *gt_i32, const void *pred_i32, int B, int H, int W, int ng_max, int np_max, size_t table_slots,
                          void *pair_keys_u64, void *pair_counts_u32, void *n_pairs_u64, void *status_u64, void *scratch,
                          void *stream);
+/* Linking the cells of consecutive frames by overlap, the greedy tracker of the Cell Tracking Challenge submissions
+ * (track.hip; functions.link_frames, functions.track_cells; the definition in full: DESIGN.md section 4s).  from_i32, to_i32
+ * id maps int32 [T,H,W], 0 = background, ids anywhere in [0, n_max] (not necessarily consecutive or connected), n_max < 2^24;
+ * from_i32 may equal to_i32 (the plain case).  Pair t, 1 <= t < T, sets frame t - 1 of `from` against frame t of `to`.
+ *   area_u32 [T][n_max+1]         : pixels per id of `to` (index 0 = background)
+ *   pred_i32 [T][n_max+1]         : for t >= 1, c >= 1 the id p >= 1 of from[t-1] with the largest |p n c| > 0, the smallest
+ *                                   such p on equal overlaps, 0 when there is none; row 0 and column 0 are 0
+ *   pred_overlap_u32 [T][n_max+1] : that |p n c|, else 0
+ *   status_u64 [T][2]             : {pixels of pair t with to[t] or (t >= 1) from[t-1] outside [0, n_max] (negative included):
+ *                                    used as no index and counted nowhere else, area included;  pixels of pair t dropped because
+ *                                    the pair table was full: if non-zero, row t of pred and pred_overlap is invalid and the
+ *                                    caller repeats the call with a larger table}
+ * table_slots: a power of two, the slots of the open-addressing table of distinct (t, p, c) with p, c >= 1, shared by all frames;
+ * a table with more slots than T*H*W cannot fill up.  Five memsets and three launches on the stream, no read-back; exact integer
+ * atomics and a 64-bit max of overlap << 24 | (2^24 - 1 - p) per (t, c): results are the same in every run.  T = 1 gives the areas
+ * only.  Limits: H * W < 2^31, T <= 65535 (the frame index is the key's top 16 bits).  A NULL pointer, T, H or W < 1, a size over
+ * the limit, n_max outside [0, 2^24) and a table_slots that is no power of two return an error and write nothing.
+ * scratch: unet_link_frames_scratch_bytes(T, n_max, table_slots) (12 bytes per slot, 8 per (t, id)), initialised by the call. */
+size_t unet_link_frames_scratch_bytes(int T, int n_max, size_t table_slots);
+int unet_link_frames(const void *from_i32, const void *to_i32, int T, int H, int W, int n_max, size_t table_slots, void *area_u32,
+                     void *pred_i32, void *pred_overlap_u32, void *status_u64, void *scratch, void *stream);
 /* Nearest-cell growth of an instance map (border thinning; skimage.segmentation.expand_labels with an exact metric and a
  * stated tie rule; functions.grow_cells).  labels_i32, out_i32 int32 [B,H,W], 0 = background, ids in [1, 2^24), not
  * necessarily consecutive or connected; H != W allowed, down to 1 x 1.  A pixel with id != 0 keeps it.  A background pixel takes
