@@ -1,8 +1,9 @@
 // elem.hpp — what the HBM-bound kernels (direct.hip, multiclass.hip, tile.hip, aux.hip) and the data-path files (wmap.hip,
-// instances.hip, prepare.hip, grow.hip, elastic.hip, clean.hip) share:
+// instances.hip, prepare.hip, grow.hip, elastic.hip, clean.hip, and through sweep.hpp geo.hip, shape.hip, flood.hip) share:
 //   device : 4 consecutive channels of an activation tensor stored as fp32 (16 B) or bf16 (8 B, arithmetic mode 2), read /
 //            written as 4 floats; the sum / min / max of one value per lane over a wave; the min and max of one value per thread
-//            over a block; the sum of one value per thread over a 256-thread block, and (instances.hip, prepare.hip) the
+//            over a block; the sum of one value per thread over a 256-thread block, with the max of a second one (the finish
+//            kernels of geo.hip and flood.hip), and (instances.hip, prepare.hip) the
 //            exclusive prefix of one int per thread over it; whether an element of a mask of any of the four dtypes is set;
 //            the union-find of the labellings (wmap.hip, clean.hip) on LDS words and on global words
 //   host   : the grid size of a grid-stride launch, the bytes of a [B,H,W] scratch plane, and the dispatch of a launch on
@@ -68,6 +69,20 @@ __device__ __forceinline__ V block_sum256(V v)
         __syncthreads();
     }
     return red[0];
+}
+// Sum of `add` and max of `top`, one of each per thread, over a 256-thread block, in place; both are valid in thread 0 (geo.hip's
+// and flood.hip's finish kernels)
+__device__ __forceinline__ void block_sum_max256(unsigned &add, unsigned &top)
+{
+    __shared__ unsigned wave_top[4];
+    for (int d = 32; d >= 1; d >>= 1) {
+        const unsigned o = __shfl_xor(top, d, 64);
+        top = o > top ? o : top;
+    }
+    if ((threadIdx.x & 63) == 0) wave_top[threadIdx.x >> 6] = top;
+    add = block_sum256(add);                                // its barriers order the four words above, too
+    if (threadIdx.x == 0)
+        for (int w = 1; w < 4; ++w) top = wave_top[w] > top ? wave_top[w] : top;
 }
 // exclusive prefix of v over the 256 threads of the workgroup, and their sum
 __device__ __forceinline__ int block_scan256(int v, int &total)

@@ -20,29 +20,22 @@
 //
 //   1. flood_init    quantises the image to the u16 level plane, writes the key plane and the id plane (seed ids on sources,
 //                    FL_NONE elsewhere); counts the seed pixels outside the region, the bad ids and the bad image values
-//   2. flood_sweep   geo_sweep with the extension above in the place of + GE_STEP: a workgroup owns a 64 x 64 tile, stages its keys
-//                    with a halo of one pixel and its levels into LDS, relaxes the tile to local convergence with the row and column
-//                    register sweeps (read, wait, store), and writes only its own tile, to the other key plane.  A key with
-//                    L > max_level is never stored: every prefix of a path has a smaller or equal L, so no key below is lost.
-//   3. flood_assign  the same sweeps over ids.  The four parent bits of every owned pixel are formed once, while staging, from the
-//                    keys and levels in global memory, which this kernel only reads; the loop then works on the staged ids
+//   2. flood_sweep   sweep.hpp's tile relaxation over the keys (geo_sweep with the extension above in the place of + GE_STEP); the
+//                    levels are staged beside them.  A key with L > max_level is never stored: every prefix of a path has a
+//                    smaller or equal L, so no key below is lost.
+//   3. flood_assign  the same relaxation over ids.  The four parent bits of every owned pixel are formed once, while staging, from
+//                    the keys and levels in global memory, which this kernel only reads; the loop then works on the staged ids
 //                    and those bits: an id moves along any straight run of parent links in one phase.  Two id planes, ping-pong.
 //   4. flood_finish  ids, pass levels, plateau distances, the unreached region pixels and the largest level reached per image
 //
-// Coherence (wmap.hip's rule, as in geo.hip): a sweep reads plane A, which an earlier kernel wrote, and writes plane B, which no
-// workgroup of the launch reads; the counters are only touched by agent-scope adds.  No word is handed from one workgroup to
-// another inside a kernel, no loop waits on a load.  The local loops end: keys and ids are bounded below and only fall.
-#include "elem.hpp"
+// Monotone and bounded, as sweep.hpp asks: keys and ids are bounded below and only fall.
+#include "sweep.hpp"
 #include "../../include/unet_hip.h"
 
 namespace unet {
 
 typedef unsigned long long fl_key;
 
-static constexpr int FL_TILE = 64;                             // owned pixels per side of a workgroup's tile
-static constexpr int FL_SEG = 16;                              // pixels of a row / column one thread owns: 64 lines x 4 segments
-static constexpr int FL_STAGED = FL_TILE + 2;                  // the tile and its halo
-static constexpr int FL_PITCH = FL_STAGED + 1;                 // LDS row pitch in words (67), as geo.hip's
 static constexpr int FL_L_SHIFT = 32;                          // key = L << 32 | d, d < 2^31 (H * W < 2^31)
 static constexpr int FL_LEVELS = 1 << 16;                      // levels are in [0, FL_LEVELS)
 static constexpr int FL_ID_END = 1 << 24;                      // ids are in [1, FL_ID_END)
@@ -101,15 +94,15 @@ __global__ __launch_bounds__(256) void flood_init_kernel(const int *__restrict__
 
 // ---- stage 1 ------------------------------------------------------------------------------------------------------------------
 
-// geo.hip's ge_relax_line with fl_ext: the FL_SEG pixels p[k * ALONG] of one line and their levels lv[k * ALONG], relaxed forward
+// geo.hip's ge_relax_line with fl_ext: the SW_SEG pixels p[k * ALONG] of one line and their levels lv[k * ALONG], relaxed forward
 // (from the pixel before and the two ACROSS) and backward (from the pixel after) in registers
 template <int ALONG, int ACROSS>
-__device__ __forceinline__ unsigned fl_relax_line(const fl_key *p, const unsigned short *lv, fl_key lim, fl_key (&v)[FL_SEG])
+__device__ __forceinline__ unsigned fl_relax_line(const fl_key *p, const unsigned short *lv, fl_key lim, fl_key (&v)[SW_SEG])
 {
     unsigned fell = 0;
     fl_key run = p[-ALONG];
 #pragma unroll
-    for (int k = 0; k < FL_SEG; ++k) {
+    for (int k = 0; k < SW_SEG; ++k) {
         const fl_key own = p[k * ALONG], a = p[k * ALONG - ACROSS], b = p[k * ALONG + ACROSS];
         fl_key c = a < b ? a : b;
         c = fl_ext(run < c ? run : c, lv[k * ALONG]);
@@ -117,9 +110,9 @@ __device__ __forceinline__ unsigned fl_relax_line(const fl_key *p, const unsigne
         run = v[k] = take ? c : own;
         fell |= (unsigned)take << k;
     }
-    run = p[FL_SEG * ALONG];
+    run = p[SW_SEG * ALONG];
 #pragma unroll
-    for (int k = FL_SEG - 1; k >= 0; --k) {
+    for (int k = SW_SEG - 1; k >= 0; --k) {
         const fl_key c = fl_ext(run, lv[k * ALONG]);
         const bool take = v[k] <= FL_UNREACHED && c < v[k] && c >> FL_L_SHIFT <= lim;
         run = v[k] = take ? c : v[k];
@@ -128,70 +121,33 @@ __device__ __forceinline__ unsigned fl_relax_line(const fl_key *p, const unsigne
     return fell;
 }
 
-template <int ALONG, typename T>
-__device__ __forceinline__ void fl_store_line(T *p, unsigned fell, const T (&v)[FL_SEG])
-{
-#pragma unroll
-    for (int k = 0; k < FL_SEG; ++k)
-        if (fell >> k & 1) p[k * ALONG] = v[k];
-}
-
 __global__ __launch_bounds__(256) void flood_sweep_kernel(const fl_key *__restrict__ src, fl_key *__restrict__ dst,
                                                           const unsigned short *__restrict__ level, int H, int W, fl_key lim,
                                                           unsigned *changed)
 {
-    __shared__ fl_key s[FL_STAGED * FL_PITCH];                                       // 34.5 KiB
-    __shared__ unsigned short sl[FL_STAGED * FL_PITCH];                              // 8.6 KiB
-    const int t = threadIdx.x, b = blockIdx.z;
-    const int oy = blockIdx.y * FL_TILE, ox = blockIdx.x * FL_TILE;
-    const int OH = min(H, oy + FL_TILE) - oy, OW = min(W, ox + FL_TILE) - ox;
-    const size_t img = (size_t)b * H * W;
-    for (int i = t; i < FL_STAGED * FL_STAGED; i += 256) {                           // the whole staged square: past the image,
-        const int ly = i / FL_STAGED, lx = i - ly * FL_STAGED;                       // FL_OUTSIDE, which never changes
-        const int gy = oy - 1 + ly, gx = ox - 1 + lx;
-        const bool in = gy >= 0 && gy < H && gx >= 0 && gx < W;
-        s[ly * FL_PITCH + lx] = in ? src[img + (size_t)gy * W + gx] : FL_OUTSIDE;
-        sl[ly * FL_PITCH + lx] = in ? level[img + (size_t)gy * W + gx] : (unsigned short)0;
-    }
-    __syncthreads();
-
-    const int line = t & 63, seg = (t >> 6) * FL_SEG;
-    const int ro = (1 + line) * FL_PITCH + 1 + seg, co = (1 + seg) * FL_PITCH + 1 + line;
-    fl_key v[FL_SEG];
-    for (;;) {                                                                       // keys only fall: it ends
-        const unsigned in_rows = fl_relax_line<1, FL_PITCH>(s + ro, sl + ro, lim, v);
-        __syncthreads();                                                             // every read of the phase is done
-        fl_store_line<1>(s + ro, in_rows, v);
-        __syncthreads();
-        const unsigned in_cols = fl_relax_line<FL_PITCH, 1>(s + co, sl + co, lim, v);
-        __syncthreads();
-        fl_store_line<FL_PITCH>(s + co, in_cols, v);
-        if (!__syncthreads_or((in_rows | in_cols) != 0)) break;                      // the tile is at its fixed point
-    }
-
-    unsigned n = 0;
-    for (int i = t; i < OH * OW; i += 256) {
-        const int y = i / OW, x = i - y * OW;
-        const size_t e = img + (size_t)(oy + y) * W + ox + x;
-        const fl_key k = s[(1 + y) * FL_PITCH + 1 + x];
-        n += k < src[e];
-        dst[e] = k;
-    }
-    n = wave_sum(n);
-    if ((t & 63) == 0 && n) __hip_atomic_fetch_add(&changed[b], n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __shared__ fl_key s[SW_STAGED * SW_PITCH];                                       // 34.5 KiB
+    __shared__ unsigned short sl[SW_STAGED * SW_PITCH];                              // 8.6 KiB
+    const SweepTile tl = sweep_tile(H, W);
+    sweep_stage(tl, H, W, [&](int i, bool in, size_t e, int, int, int, int) {
+        s[i] = in ? src[e] : FL_OUTSIDE;
+        sl[i] = in ? level[e] : (unsigned short)0;
+    });
+    sweep_converge(s, [&](int o, fl_key (&v)[SW_SEG]) { return fl_relax_line<1, SW_PITCH>(s + o, sl + o, lim, v); },
+                   [&](int o, fl_key (&v)[SW_SEG]) { return fl_relax_line<SW_PITCH, 1>(s + o, sl + o, lim, v); });
+    sweep_write_back(tl, s, src, dst, W, changed, [](fl_key k, fl_key was) { return k < was; });
 }
 
 // ---- stage 2 ------------------------------------------------------------------------------------------------------------------
 
-// the FL_SEG ids p[k * ALONG] of one line and their parent bits: forward, an id takes the least of its own, of the pixel before
+// the SW_SEG ids p[k * ALONG] of one line and their parent bits: forward, an id takes the least of its own, of the pixel before
 // (bit PREV) and of the two ACROSS (bits LO, HI); backward, of the pixel after (bit NEXT)
 template <int ALONG, int ACROSS, int PREV, int NEXT, int LO, int HI>
-__device__ __forceinline__ unsigned fl_assign_line(const unsigned *p, const unsigned char *par, unsigned (&v)[FL_SEG])
+__device__ __forceinline__ unsigned fl_assign_line(const unsigned *p, const unsigned char *par, unsigned (&v)[SW_SEG])
 {
     unsigned fell = 0;
     unsigned run = p[-ALONG];
 #pragma unroll
-    for (int k = 0; k < FL_SEG; ++k) {
+    for (int k = 0; k < SW_SEG; ++k) {
         const unsigned own = p[k * ALONG], a = p[k * ALONG - ACROSS], b = p[k * ALONG + ACROSS], bits = par[k * ALONG];
         unsigned c = own;
         c = (bits & PREV) && run < c ? run : c;
@@ -200,9 +156,9 @@ __device__ __forceinline__ unsigned fl_assign_line(const unsigned *p, const unsi
         fell |= (unsigned)(c < own) << k;
         run = v[k] = c;
     }
-    run = p[FL_SEG * ALONG];
+    run = p[SW_SEG * ALONG];
 #pragma unroll
-    for (int k = FL_SEG - 1; k >= 0; --k) {
+    for (int k = SW_SEG - 1; k >= 0; --k) {
         const bool take = (par[k * ALONG] & NEXT) && run < v[k];
         run = v[k] = take ? run : v[k];
         fell |= (unsigned)take << k;
@@ -214,20 +170,14 @@ __global__ __launch_bounds__(256) void flood_assign_kernel(const fl_key *__restr
                                                            const unsigned *__restrict__ src, unsigned *__restrict__ dst, int H, int W,
                                                            unsigned *changed)
 {
-    __shared__ unsigned s[FL_STAGED * FL_PITCH];                                     // 17.3 KiB
-    __shared__ unsigned char sp[FL_STAGED * FL_PITCH];                               // 4.3 KiB
-    const int t = threadIdx.x, b = blockIdx.z;
-    const int oy = blockIdx.y * FL_TILE, ox = blockIdx.x * FL_TILE;
-    const int OH = min(H, oy + FL_TILE) - oy, OW = min(W, ox + FL_TILE) - ox;
-    const size_t img = (size_t)b * H * W;
-    for (int i = t; i < FL_STAGED * FL_STAGED; i += 256) {                           // past the image: no id and no parent
-        const int ly = i / FL_STAGED, lx = i - ly * FL_STAGED;
-        const int gy = oy - 1 + ly, gx = ox - 1 + lx;
-        const bool in = gy >= 0 && gy < H && gx >= 0 && gx < W;
-        const size_t e = img + (size_t)(in ? gy : 0) * W + (in ? gx : 0);
-        s[ly * FL_PITCH + lx] = in ? src[e] : FL_NONE;
+    __shared__ unsigned s[SW_STAGED * SW_PITCH];                                     // 17.3 KiB
+    __shared__ unsigned char sp[SW_STAGED * SW_PITCH];                               // 4.3 KiB
+    const SweepTile tl = sweep_tile(H, W);
+    sweep_stage(tl, H, W, [&](int i, bool in, size_t, int ly, int lx, int gy, int gx) {      // past the image: no id and no parent
+        const size_t e = tl.img + (size_t)(in ? gy : 0) * W + (in ? gx : 0);
+        s[i] = in ? src[e] : FL_NONE;
         int bits = 0;
-        if (in && ly >= 1 && ly <= FL_TILE && lx >= 1 && lx <= FL_TILE) {            // an owned pixel: which neighbours are parents
+        if (in && ly >= 1 && ly <= SW_TILE && lx >= 1 && lx <= SW_TILE) {            // an owned pixel: which neighbours are parents
             const fl_key k = key[e];
             if (k < FL_UNREACHED) {                                                  // (no extension is 0: a source has none)
                 const unsigned v = level[e];
@@ -237,34 +187,11 @@ __global__ __launch_bounds__(256) void flood_assign_kernel(const fl_key *__restr
                 bits |= gy < H - 1 && fl_ext(key[e + W], v) == k ? FL_DOWN : 0;
             }
         }
-        sp[ly * FL_PITCH + lx] = (unsigned char)bits;
-    }
-    __syncthreads();
-
-    const int line = t & 63, seg = (t >> 6) * FL_SEG;
-    const int ro = (1 + line) * FL_PITCH + 1 + seg, co = (1 + seg) * FL_PITCH + 1 + line;
-    unsigned v[FL_SEG];
-    for (;;) {                                                                       // ids only fall: it ends
-        const unsigned in_rows = fl_assign_line<1, FL_PITCH, FL_LEFT, FL_RIGHT, FL_UP, FL_DOWN>(s + ro, sp + ro, v);
-        __syncthreads();                                                             // every read of the phase is done
-        fl_store_line<1>(s + ro, in_rows, v);
-        __syncthreads();
-        const unsigned in_cols = fl_assign_line<FL_PITCH, 1, FL_UP, FL_DOWN, FL_LEFT, FL_RIGHT>(s + co, sp + co, v);
-        __syncthreads();
-        fl_store_line<FL_PITCH>(s + co, in_cols, v);
-        if (!__syncthreads_or((in_rows | in_cols) != 0)) break;                      // the tile is at its fixed point
-    }
-
-    unsigned n = 0;
-    for (int i = t; i < OH * OW; i += 256) {
-        const int y = i / OW, x = i - y * OW;
-        const size_t e = img + (size_t)(oy + y) * W + ox + x;
-        const unsigned id = s[(1 + y) * FL_PITCH + 1 + x];
-        n += id < src[e];
-        dst[e] = id;
-    }
-    n = wave_sum(n);
-    if ((t & 63) == 0 && n) __hip_atomic_fetch_add(&changed[b], n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        sp[i] = (unsigned char)bits;
+    });
+    sweep_converge(s, [&](int o, unsigned (&v)[SW_SEG]) { return fl_assign_line<1, SW_PITCH, FL_LEFT, FL_RIGHT, FL_UP, FL_DOWN>(s + o, sp + o, v); },
+                   [&](int o, unsigned (&v)[SW_SEG]) { return fl_assign_line<SW_PITCH, 1, FL_UP, FL_DOWN, FL_LEFT, FL_RIGHT>(s + o, sp + o, v); });
+    sweep_write_back(tl, s, src, dst, W, changed, [](unsigned id, unsigned was) { return id < was; });
 }
 
 __global__ __launch_bounds__(256) void flood_finish_kernel(const fl_key *__restrict__ key, const unsigned *__restrict__ ids, size_t npx,
@@ -284,15 +211,8 @@ __global__ __launch_bounds__(256) void flood_finish_kernel(const fl_key *__restr
         open += !got && k <= FL_UNREACHED;
         top = got && L > top ? L : top;
     }
-    __shared__ unsigned wave_top[4];
-    for (int d = 32; d >= 1; d >>= 1) {
-        const unsigned o = __shfl_xor(top, d, 64);
-        top = o > top ? o : top;
-    }
-    if ((threadIdx.x & 63) == 0) wave_top[threadIdx.x >> 6] = top;
-    open = block_sum256(open);                                 // its barriers order the four words above, too
+    block_sum_max256(open, top);
     if (threadIdx.x != 0) return;                              // one add and one max per workgroup: the words are few
-    for (int w = 1; w < 4; ++w) top = wave_top[w] > top ? wave_top[w] : top;
     if (open) __hip_atomic_fetch_add(&unreached[blockIdx.y], open, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (top) __hip_atomic_fetch_max(&max_level[blockIdx.y], top, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -301,7 +221,6 @@ __global__ __launch_bounds__(256) void flood_finish_kernel(const fl_key *__restr
 
 using namespace unet;
 
-static bool fl_sizes_ok(int B, int H, int W) { return (size_t)H * W < (1u << 31) && H <= 65535 && W <= 65535 && B <= 65535; }
 static fl_key fl_limit(long long max_level) { return max_level < 0 || max_level >= FL_LEVELS ? (fl_key)(FL_LEVELS - 1) : (fl_key)max_level; }
 
 // [key plane 0, the current one between calls | key plane 1 | id plane 0, the current one between calls | id plane 1 | levels]
@@ -330,7 +249,7 @@ int unet_flood_init(const void *seeds_i32, const void *image, int image_dtype, i
     ARG_CHECK(image_dtype >= 0 && image_dtype <= 3, "unet_flood_init: image_dtype must be 0 (int64), 1 (float32), 2 (int32) or 3 (uint8)");
     ARG_CHECK(image_dtype != 1 || (levels >= 1 && levels <= FL_LEVELS), "unet_flood_init: a float32 image needs levels in [1, 65536]");
     ARG_CHECK(!mask || (mask_dtype >= 0 && mask_dtype <= 3), "unet_flood_init: mask_dtype must be 0 (int64), 1 (float32), 2 (int32) or 3 (uint8)");
-    ARG_CHECK(fl_sizes_ok(B, H, W), "unet_flood_init: image too large (the limits of unet_grow_labels)");
+    ARG_CHECK(sizes_ok(B, H, W, 65535), "unet_flood_init: image too large (the limits of unet_grow_labels)");
     hipStream_t st = (hipStream_t)stream;
     const size_t npx = (size_t)H * W;
     const FlScratch s = fl_scratch(scratch, B, H, W);
@@ -347,43 +266,36 @@ int unet_flood_sweeps(int B, int H, int W, long long max_level, int n_launches, 
                       void *stream)
 {
     ARG_CHECK(changed_out_u32 && scratch && B > 0 && H > 0 && W > 0 && n_launches > 0 && first_slot >= 0, "unet_flood_sweeps: bad argument");
-    ARG_CHECK(fl_sizes_ok(B, H, W), "unet_flood_sweeps: image too large (the limits of unet_grow_labels)");
+    ARG_CHECK(sizes_ok(B, H, W, 65535), "unet_flood_sweeps: image too large (the limits of unet_grow_labels)");
     hipStream_t st = (hipStream_t)stream;
-    unsigned *changed = (unsigned *)changed_out_u32 + (size_t)first_slot * B;
-    HIP_TRY(hipMemsetAsync(changed, 0, (size_t)n_launches * B * sizeof(unsigned), st));
     const FlScratch s = fl_scratch(scratch, B, H, W);
-    const dim3 grid(cdiv(W, FL_TILE), cdiv(H, FL_TILE), B);
-    for (int l = 0; l < n_launches; ++l)
-        hipLaunchKernelGGL(flood_sweep_kernel, grid, dim3(256), 0, st, (const fl_key *)s.key[l & 1], s.key[~l & 1],
-                           (const unsigned short *)s.level, H, W, fl_limit(max_level), changed + (size_t)l * B);
-    HIP_TRY(hipGetLastError());
-    if (n_launches & 1) HIP_TRY(hipMemcpyAsync(s.key[0], s.key[1], (size_t)B * H * W * sizeof(fl_key), hipMemcpyDeviceToDevice, st));
-    return 0;
+    const fl_key lim = fl_limit(max_level);
+    return sweep_launches(s.key[0], s.key[1], sizeof(fl_key), B, H, W, n_launches, changed_out_u32, first_slot, st,
+                          [&](dim3 grid, void *src, void *dst, unsigned *changed) {
+                              hipLaunchKernelGGL(flood_sweep_kernel, grid, dim3(256), 0, st, (const fl_key *)src, (fl_key *)dst,
+                                                 (const unsigned short *)s.level, H, W, lim, changed);
+                          });
 }
 
 // Takes on trust that the keys are final: a launch of unet_flood_sweeps that changed nothing has been seen by the caller.
 int unet_flood_assign(int B, int H, int W, int n_launches, void *changed_out_u32, int first_slot, void *scratch, void *stream)
 {
     ARG_CHECK(changed_out_u32 && scratch && B > 0 && H > 0 && W > 0 && n_launches > 0 && first_slot >= 0, "unet_flood_assign: bad argument");
-    ARG_CHECK(fl_sizes_ok(B, H, W), "unet_flood_assign: image too large (the limits of unet_grow_labels)");
+    ARG_CHECK(sizes_ok(B, H, W, 65535), "unet_flood_assign: image too large (the limits of unet_grow_labels)");
     hipStream_t st = (hipStream_t)stream;
-    unsigned *changed = (unsigned *)changed_out_u32 + (size_t)first_slot * B;
-    HIP_TRY(hipMemsetAsync(changed, 0, (size_t)n_launches * B * sizeof(unsigned), st));
     const FlScratch s = fl_scratch(scratch, B, H, W);
-    const dim3 grid(cdiv(W, FL_TILE), cdiv(H, FL_TILE), B);
-    for (int l = 0; l < n_launches; ++l)
-        hipLaunchKernelGGL(flood_assign_kernel, grid, dim3(256), 0, st, (const fl_key *)s.key[0], (const unsigned short *)s.level,
-                           (const unsigned *)s.ids[l & 1], s.ids[~l & 1], H, W, changed + (size_t)l * B);
-    HIP_TRY(hipGetLastError());
-    if (n_launches & 1) HIP_TRY(hipMemcpyAsync(s.ids[0], s.ids[1], (size_t)B * H * W * sizeof(unsigned), hipMemcpyDeviceToDevice, st));
-    return 0;
+    return sweep_launches(s.ids[0], s.ids[1], sizeof(unsigned), B, H, W, n_launches, changed_out_u32, first_slot, st,
+                          [&](dim3 grid, void *src, void *dst, unsigned *changed) {
+                              hipLaunchKernelGGL(flood_assign_kernel, grid, dim3(256), 0, st, (const fl_key *)s.key[0],
+                                                 (const unsigned short *)s.level, (const unsigned *)src, (unsigned *)dst, H, W, changed);
+                          });
 }
 
 int unet_flood_finish(int B, int H, int W, void *out_i32, void *pass_level_i32, void *dist_i32, void *unreached_u32, void *max_level_u32,
                       void *scratch, void *stream)
 {
     ARG_CHECK(out_i32 && unreached_u32 && max_level_u32 && scratch && B > 0 && H > 0 && W > 0, "unet_flood_finish: bad argument");
-    ARG_CHECK(fl_sizes_ok(B, H, W), "unet_flood_finish: image too large (the limits of unet_grow_labels)");
+    ARG_CHECK(sizes_ok(B, H, W, 65535), "unet_flood_finish: image too large (the limits of unet_grow_labels)");
     hipStream_t st = (hipStream_t)stream;
     const size_t npx = (size_t)H * W;
     const FlScratch s = fl_scratch(scratch, B, H, W);

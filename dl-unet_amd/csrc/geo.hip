@@ -7,38 +7,21 @@
 // One 64-bit key per pixel:  d << 24 | id  of the best path known so far, GE_UNREACHED for a region pixel no path has reached,
 // GE_OUTSIDE for a pixel that is not in the region (so the mask is read once).  The result is the fixed point of
 //      key(p) <- min(key(p), min over the 4-neighbours q of key(q) + (1 << 24))        for p in the region
-// (a neighbour that is outside or unreached offers a key above GE_UNREACHED, which no region pixel takes).  Every key ever held is
-// the (length, id) of a real path, keys only fall, and the least fixed point is unique: any order of relaxation reaches it.
+// (a neighbour that is outside or unreached offers a key above GE_UNREACHED, which no region pixel takes).  Monotone and bounded,
+// as sweep.hpp asks: every key ever held is the (length, id) of a real path, keys only fall, and the least fixed point is unique.
 //
 //   1. geo_init    the key plane from seeds and mask; counts the seed pixels outside the region and the ids outside [0, 2^24)
-//   2. geo_sweep   a workgroup owns a 64 x 64 tile and stages it with a halo of one pixel (GE_OUTSIDE past the image) into LDS.
-//                  It relaxes the tile to local convergence: a row phase, in which a thread owns 16 consecutive pixels of a row
-//                  and sweeps them left to right (taking the pixel before, above and below) and back right to left in registers,
-//                  then a column phase, the same on 16 consecutive pixels of a column; a key moves along any straight run of the
-//                  tile in one phase.  Within a phase every thread reads, then all wait, then the threads that lowered a key
-//                  store it: no thread reads a word another one may be storing.  The loop ends when both phases lowered nothing.
-//                  Only the owned tile is written, to the other key plane: a neighbour's halo read never sees this launch's
-//                  stores, and the hand-off between tiles is the kernel boundary.  The owned pixels whose key fell are counted
-//                  into changed[slot][b] by agent-scope adds.  With a limit, a key with d > max_steps is never stored: every key
-//                  with d <= max_steps comes from a path whose every prefix has a smaller d, so none of them is lost.
+//   2. geo_sweep   sweep.hpp's tile relaxation over the keys, GE_OUTSIDE past the image.  With a limit, a key with d > max_steps
+//                  is never stored: every key with d <= max_steps comes from a path whose every prefix has a smaller d, so none
+//                  of them is lost.
 //   3. geo_finish  id, distance, the unreached region pixels and the largest distance per image
-//
-// The launches a growth needs are about the tile borders its longest shortest path crosses, not its length.
-//
-// Coherence (wmap.hip's rule): geo_sweep reads plane A, which an earlier kernel wrote, and writes plane B, which no workgroup of
-// the launch reads; the counters are only touched by agent-scope adds.  No word is handed from one workgroup to another inside a
-// kernel, no loop waits on a load.
-#include "elem.hpp"
+#include "sweep.hpp"
 #include "../../include/unet_hip.h"
 
 namespace unet {
 
 typedef unsigned long long ge_key;
 
-static constexpr int GE_TILE = 64;                             // owned pixels per side of a workgroup's tile
-static constexpr int GE_SEG = 16;                              // pixels of a row / column one thread owns: 64 lines x 4 segments
-static constexpr int GE_STAGED = GE_TILE + 2;                  // the tile and its halo
-static constexpr int GE_PITCH = GE_STAGED + 1;                 // LDS row pitch in keys (67): 32 lanes on 32 rows, no bank twice
 static constexpr int GE_ID_BITS = 24;
 static constexpr unsigned GE_ID_MASK = (1u << GE_ID_BITS) - 1;
 static constexpr ge_key GE_STEP = 1ull << GE_ID_BITS;          // one more step, the same id
@@ -66,15 +49,15 @@ __global__ __launch_bounds__(256) void geo_init_kernel(const int *__restrict__ s
         __hip_atomic_fetch_add(&status[blockIdx.y], (unsigned long long)bad, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// the GE_SEG pixels p[k * ALONG] of one line, relaxed forward (from the pixel before and the two ACROSS) and backward (from the
+// the SW_SEG pixels p[k * ALONG] of one line, relaxed forward (from the pixel before and the two ACROSS) and backward (from the
 // pixel after) in registers: v[k] is the key after both, bit k of the result says that it fell
 template <int ALONG, int ACROSS>
-__device__ __forceinline__ unsigned ge_relax_line(const ge_key *p, ge_key lim, ge_key (&v)[GE_SEG])
+__device__ __forceinline__ unsigned ge_relax_line(const ge_key *p, ge_key lim, ge_key (&v)[SW_SEG])
 {
     unsigned fell = 0;
     ge_key run = p[-ALONG];
 #pragma unroll
-    for (int k = 0; k < GE_SEG; ++k) {
+    for (int k = 0; k < SW_SEG; ++k) {
         const ge_key own = p[k * ALONG], a = p[k * ALONG - ACROSS], b = p[k * ALONG + ACROSS];
         ge_key c = a < b ? a : b;
         c = (run < c ? run : c) + GE_STEP;
@@ -82,9 +65,9 @@ __device__ __forceinline__ unsigned ge_relax_line(const ge_key *p, ge_key lim, g
         run = v[k] = take ? c : own;
         fell |= (unsigned)take << k;
     }
-    run = p[GE_SEG * ALONG];
+    run = p[SW_SEG * ALONG];
 #pragma unroll
-    for (int k = GE_SEG - 1; k >= 0; --k) {
+    for (int k = SW_SEG - 1; k >= 0; --k) {
         const ge_key c = run + GE_STEP;
         const bool take = v[k] <= GE_UNREACHED && c < v[k] && c >> GE_ID_BITS <= lim;
         run = v[k] = take ? c : v[k];
@@ -93,53 +76,15 @@ __device__ __forceinline__ unsigned ge_relax_line(const ge_key *p, ge_key lim, g
     return fell;
 }
 
-template <int ALONG>
-__device__ __forceinline__ void ge_store_line(ge_key *p, unsigned fell, const ge_key (&v)[GE_SEG])
-{
-#pragma unroll
-    for (int k = 0; k < GE_SEG; ++k)
-        if (fell >> k & 1) p[k * ALONG] = v[k];
-}
-
 __global__ __launch_bounds__(256) void geo_sweep_kernel(const ge_key *__restrict__ src, ge_key *__restrict__ dst, int H, int W,
                                                         ge_key lim, unsigned *changed)
 {
-    __shared__ ge_key s[GE_STAGED * GE_PITCH];                                       // 34.5 KiB
-    const int t = threadIdx.x, b = blockIdx.z;
-    const int oy = blockIdx.y * GE_TILE, ox = blockIdx.x * GE_TILE;
-    const int OH = min(H, oy + GE_TILE) - oy, OW = min(W, ox + GE_TILE) - ox;
-    const size_t img = (size_t)b * H * W;
-    for (int i = t; i < GE_STAGED * GE_STAGED; i += 256) {                           // the whole staged square: past the image,
-        const int ly = i / GE_STAGED, lx = i - ly * GE_STAGED;                       // GE_OUTSIDE, which never changes
-        const int gy = oy - 1 + ly, gx = ox - 1 + lx;
-        s[ly * GE_PITCH + lx] = gy >= 0 && gy < H && gx >= 0 && gx < W ? src[img + (size_t)gy * W + gx] : GE_OUTSIDE;
-    }
-    __syncthreads();
-
-    const int line = t & 63, seg = (t >> 6) * GE_SEG;
-    ge_key *row = s + (1 + line) * GE_PITCH + 1 + seg, *col = s + (1 + seg) * GE_PITCH + 1 + line;
-    ge_key v[GE_SEG];
-    for (;;) {                                                                       // keys only fall: it ends
-        const unsigned in_rows = ge_relax_line<1, GE_PITCH>(row, lim, v);
-        __syncthreads();                                                             // every read of the phase is done
-        ge_store_line<1>(row, in_rows, v);
-        __syncthreads();
-        const unsigned in_cols = ge_relax_line<GE_PITCH, 1>(col, lim, v);
-        __syncthreads();
-        ge_store_line<GE_PITCH>(col, in_cols, v);
-        if (!__syncthreads_or((in_rows | in_cols) != 0)) break;                      // the tile is at its fixed point
-    }
-
-    unsigned n = 0;
-    for (int i = t; i < OH * OW; i += 256) {
-        const int y = i / OW, x = i - y * OW;
-        const size_t e = img + (size_t)(oy + y) * W + ox + x;
-        const ge_key k = s[(1 + y) * GE_PITCH + 1 + x];
-        n += k < src[e];
-        dst[e] = k;
-    }
-    n = wave_sum(n);
-    if ((t & 63) == 0 && n) __hip_atomic_fetch_add(&changed[b], n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __shared__ ge_key s[SW_STAGED * SW_PITCH];                                       // 34.5 KiB
+    const SweepTile tl = sweep_tile(H, W);
+    sweep_stage(tl, H, W, [&](int i, bool in, size_t e, int, int, int, int) { s[i] = in ? src[e] : GE_OUTSIDE; });
+    sweep_converge(s, [&](int o, ge_key (&v)[SW_SEG]) { return ge_relax_line<1, SW_PITCH>(s + o, lim, v); },
+                   [&](int o, ge_key (&v)[SW_SEG]) { return ge_relax_line<SW_PITCH, 1>(s + o, lim, v); });
+    sweep_write_back(tl, s, src, dst, W, changed, [](ge_key k, ge_key was) { return k < was; });
 }
 
 __global__ __launch_bounds__(256) void geo_finish_kernel(const ge_key *__restrict__ key, size_t npx, ge_key lim, int *__restrict__ out,
@@ -156,15 +101,8 @@ __global__ __launch_bounds__(256) void geo_finish_kernel(const ge_key *__restric
         open += !got && k <= GE_UNREACHED;
         far = got && d > far ? d : far;
     }
-    __shared__ unsigned wave_far[4];
-    for (int d = 32; d >= 1; d >>= 1) {
-        const unsigned o = __shfl_xor(far, d, 64);
-        far = o > far ? o : far;
-    }
-    if ((threadIdx.x & 63) == 0) wave_far[threadIdx.x >> 6] = far;
-    open = block_sum256(open);                                 // its barriers order the four words above, too
+    block_sum_max256(open, far);
     if (threadIdx.x != 0) return;                              // one add and one max per workgroup: the words are few
-    for (int w = 1; w < 4; ++w) far = wave_far[w] > far ? wave_far[w] : far;
     if (open) __hip_atomic_fetch_add(&unreached[blockIdx.y], open, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (far) __hip_atomic_fetch_max(&max_dist[blockIdx.y], far, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -174,7 +112,6 @@ __global__ __launch_bounds__(256) void geo_finish_kernel(const ge_key *__restric
 using namespace unet;
 
 static size_t ge_plane(int B, int H, int W) { return plane_bytes(B, H, W, sizeof(ge_key)); }
-static bool ge_sizes_ok(int B, int H, int W) { return (size_t)H * W < (1u << 31) && H <= 65535 && W <= 65535 && B <= 65535; }
 static ge_key ge_limit(long long max_steps) { return max_steps < 0 || (ge_key)max_steps > GE_UNLIMITED ? GE_UNLIMITED : (ge_key)max_steps; }
 
 // [key plane 0, the current one between calls | key plane 1]
@@ -189,7 +126,7 @@ int unet_geodesic_init(const void *seeds_i32, const void *mask, int mask_dtype, 
 {
     ARG_CHECK(seeds_i32 && mask && seeds_outside_u32 && status_u64 && scratch && B > 0 && H > 0 && W > 0, "unet_geodesic_init: bad argument");
     ARG_CHECK(mask_dtype >= 0 && mask_dtype <= 3, "unet_geodesic_init: mask_dtype must be 0 (int64), 1 (float32), 2 (int32) or 3 (uint8)");
-    ARG_CHECK(ge_sizes_ok(B, H, W), "unet_geodesic_init: image too large (the limits of unet_grow_labels)");
+    ARG_CHECK(sizes_ok(B, H, W, 65535), "unet_geodesic_init: image too large (the limits of unet_grow_labels)");
     hipStream_t st = (hipStream_t)stream;
     const size_t npx = (size_t)H * W;
     HIP_TRY(hipMemsetAsync(seeds_outside_u32, 0, (size_t)B * sizeof(unsigned), st));
@@ -204,25 +141,20 @@ int unet_geodesic_sweeps(int B, int H, int W, long long max_steps, int n_launche
                          void *stream)
 {
     ARG_CHECK(changed_out_u32 && scratch && B > 0 && H > 0 && W > 0 && n_launches > 0 && first_slot >= 0, "unet_geodesic_sweeps: bad argument");
-    ARG_CHECK(ge_sizes_ok(B, H, W), "unet_geodesic_sweeps: image too large (the limits of unet_grow_labels)");
+    ARG_CHECK(sizes_ok(B, H, W, 65535), "unet_geodesic_sweeps: image too large (the limits of unet_grow_labels)");
     hipStream_t st = (hipStream_t)stream;
-    unsigned *changed = (unsigned *)changed_out_u32 + (size_t)first_slot * B;
-    HIP_TRY(hipMemsetAsync(changed, 0, (size_t)n_launches * B * sizeof(unsigned), st));
-    ge_key *plane[2] = {(ge_key *)scratch, (ge_key *)((char *)scratch + ge_plane(B, H, W))};
-    const dim3 grid(cdiv(W, GE_TILE), cdiv(H, GE_TILE), B);
-    for (int l = 0; l < n_launches; ++l)
-        hipLaunchKernelGGL(geo_sweep_kernel, grid, dim3(256), 0, st, (const ge_key *)plane[l & 1], plane[~l & 1], H, W, ge_limit(max_steps),
-                           changed + (size_t)l * B);
-    HIP_TRY(hipGetLastError());
-    if (n_launches & 1) HIP_TRY(hipMemcpyAsync(plane[0], plane[1], (size_t)B * H * W * sizeof(ge_key), hipMemcpyDeviceToDevice, st));
-    return 0;
+    const ge_key lim = ge_limit(max_steps);
+    return sweep_launches(scratch, (char *)scratch + ge_plane(B, H, W), sizeof(ge_key), B, H, W, n_launches, changed_out_u32, first_slot, st,
+                          [&](dim3 grid, void *src, void *dst, unsigned *changed) {
+                              hipLaunchKernelGGL(geo_sweep_kernel, grid, dim3(256), 0, st, (const ge_key *)src, (ge_key *)dst, H, W, lim, changed);
+                          });
 }
 
 int unet_geodesic_finish(int B, int H, int W, long long max_steps, void *out_i32, void *dist_i32, void *unreached_u32, void *max_dist_u32,
                          void *scratch, void *stream)
 {
     ARG_CHECK(out_i32 && unreached_u32 && max_dist_u32 && scratch && B > 0 && H > 0 && W > 0, "unet_geodesic_finish: bad argument");
-    ARG_CHECK(ge_sizes_ok(B, H, W), "unet_geodesic_finish: image too large (the limits of unet_grow_labels)");
+    ARG_CHECK(sizes_ok(B, H, W, 65535), "unet_geodesic_finish: image too large (the limits of unet_grow_labels)");
     hipStream_t st = (hipStream_t)stream;
     const size_t npx = (size_t)H * W;
     HIP_TRY(hipMemsetAsync(unreached_u32, 0, (size_t)B * sizeof(unsigned), st));

@@ -21,21 +21,18 @@
 // Values only rise, every value ever held is a lower bound of the result (it is min(marker(q), under along a real path from q)),
 // and a state that nothing raises satisfies the three conditions, so it is the least such function: any order of relaxation is
 // exact.  Pixels outside the region and past the image hold -1 in both planes: they offer nothing (every region value is >= 0)
-// and take nothing (min(-1, .) = -1), so the relaxation has no case distinction and the mask is read once.
+// and take nothing (min(-1, .) = -1), so the relaxation has no case distinction and the mask is read once.  Monotone and
+// bounded, as sweep.hpp asks: values only rise, and under is a ceiling.
 //   1. rc_init    R = base = min(marker, under) and under, -1 outside the region; counts the values outside [0, 2^30]
-//   2. rc_sweep   geo.hip's sweep with a max in place of its min: a workgroup owns a 64 x 64 tile, stages R and under with a halo of
-//                 one pixel in LDS and relaxes the tile to local convergence, a row phase (a thread owns 16 consecutive pixels of a
-//                 row and sweeps them forward and back in registers) then a column phase, until neither raised a value.  Within a
-//                 phase every thread reads, all wait, then the threads that raised a value store it.  Only the owned tile is
-//                 written, from plane A to plane B; the owned pixels that rose are added to changed[slot][b], one add per wave.
+//   2. rc_sweep   sweep.hpp's tile relaxation over R (geo.hip's sweep with a max in place of its min), under staged beside it
 //   3. rc_finish  R with 0 outside the region, and the pixels with R > base per image
 //
 // The element-wise steps of shape_seeds: sh_heights (q = floor(16 sqrt(d2)) exactly, and q + hq), sh_lower (max(v - c, 0)),
 // sh_maxima (1.0 where r2 < r1 and r1 >= a floor, else 0.0: a mask unet_label_components takes).
 //
-// Coherence (wmap.hip's rule): every kernel reads what an earlier kernel wrote; rc_sweep writes a plane no workgroup of the launch
-// reads; in dm_cols a thread re-reads only its own column.  The counters are only touched by agent-scope adds.
-#include "elem.hpp"
+// Coherence (wmap.hip's rule): every kernel reads what an earlier kernel wrote (rc_sweep: sweep.hpp); in dm_cols a thread re-reads
+// only its own column.  The counters are only touched by agent-scope adds.
+#include "sweep.hpp"
 #include <cmath>
 #include "../../include/unet_hip.h"
 
@@ -46,10 +43,6 @@ static constexpr int DM_FAR = 46340;                           // "no pixel outs
                                                                // every H^2 + W^2 and DM_FAR^2 + dx^2 < 2^32
 static constexpr unsigned DM_FAR2 = (unsigned)DM_FAR * DM_FAR;
 static constexpr int DM_SEGS = 4;                              // row segments of a column, one wave each, in dm_cols
-static constexpr int RC_TILE = 64;                             // owned pixels per side of a workgroup's tile
-static constexpr int RC_SEG = 16;                              // pixels of a row / column one thread owns: 64 lines x 4 segments
-static constexpr int RC_STAGED = RC_TILE + 2;                  // the tile and its halo
-static constexpr int RC_PITCH = RC_STAGED + 1;                 // LDS row pitch in words (67): 32 lanes on 32 rows, no bank twice
 static constexpr int RC_TOP = 1 << 30;                         // values are in [0, RC_TOP]
 
 template <typename T>
@@ -146,25 +139,25 @@ __global__ __launch_bounds__(256) void rc_init_kernel(const void *__restrict__ m
         __hip_atomic_fetch_add(&status[blockIdx.y], (unsigned long long)bad, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// the RC_SEG pixels p[k * ALONG] of one line under the ceilings u[k * ALONG], relaxed forward (from the pixel before and the two
+// the SW_SEG pixels p[k * ALONG] of one line under the ceilings u[k * ALONG], relaxed forward (from the pixel before and the two
 // ACROSS) and backward (from the pixel after) in registers: v[k] is the value after both, bit k of the result says that it rose
 template <int ALONG, int ACROSS>
-__device__ __forceinline__ unsigned rc_relax_line(const int *p, const int *u, int (&v)[RC_SEG])
+__device__ __forceinline__ unsigned rc_relax_line(const int *p, const int *u, int (&v)[SW_SEG])
 {
     unsigned rose = 0;
-    int top[RC_SEG];
+    int top[SW_SEG];
     int run = p[-ALONG];
 #pragma unroll
-    for (int k = 0; k < RC_SEG; ++k) {
+    for (int k = 0; k < SW_SEG; ++k) {
         const int own = p[k * ALONG], a = p[k * ALONG - ACROSS], b = p[k * ALONG + ACROSS];
         top[k] = u[k * ALONG];
         const int c = min(top[k], max(max(a, b), run));
         rose |= (unsigned)(c > own) << k;
         run = v[k] = max(own, c);
     }
-    run = p[RC_SEG * ALONG];
+    run = p[SW_SEG * ALONG];
 #pragma unroll
-    for (int k = RC_SEG - 1; k >= 0; --k) {
+    for (int k = SW_SEG - 1; k >= 0; --k) {
         const int c = min(top[k], run);
         rose |= (unsigned)(c > v[k]) << k;
         run = v[k] = max(v[k], c);
@@ -172,56 +165,18 @@ __device__ __forceinline__ unsigned rc_relax_line(const int *p, const int *u, in
     return rose;
 }
 
-template <int ALONG>
-__device__ __forceinline__ void rc_store_line(int *p, unsigned rose, const int (&v)[RC_SEG])
-{
-#pragma unroll
-    for (int k = 0; k < RC_SEG; ++k)
-        if (rose >> k & 1) p[k * ALONG] = v[k];
-}
-
 __global__ __launch_bounds__(256) void rc_sweep_kernel(const int *__restrict__ src, const int *__restrict__ under, int *__restrict__ dst,
                                                        int H, int W, unsigned *changed)
 {
-    __shared__ int s[RC_STAGED * RC_PITCH], su[RC_STAGED * RC_PITCH];                // 2 x 17.3 KiB
-    const int t = threadIdx.x, b = blockIdx.z;
-    const int oy = blockIdx.y * RC_TILE, ox = blockIdx.x * RC_TILE;
-    const int OH = min(H, oy + RC_TILE) - oy, OW = min(W, ox + RC_TILE) - ox;
-    const size_t img = (size_t)b * H * W;
-    for (int i = t; i < RC_STAGED * RC_STAGED; i += 256) {                           // the whole staged square: past the image -1,
-        const int ly = i / RC_STAGED, lx = i - ly * RC_STAGED;                       // which never changes
-        const int gy = oy - 1 + ly, gx = ox - 1 + lx;
-        const bool in = gy >= 0 && gy < H && gx >= 0 && gx < W;
-        const size_t e = img + (size_t)gy * W + gx;
-        s[ly * RC_PITCH + lx] = in ? src[e] : -1;
-        su[ly * RC_PITCH + lx] = in ? under[e] : -1;
-    }
-    __syncthreads();
-
-    const int line = t & 63, seg = (t >> 6) * RC_SEG;
-    const int row = (1 + line) * RC_PITCH + 1 + seg, col = (1 + seg) * RC_PITCH + 1 + line;
-    int v[RC_SEG];
-    for (;;) {                                                                       // values only rise, under is a ceiling: it ends
-        const unsigned in_rows = rc_relax_line<1, RC_PITCH>(s + row, su + row, v);
-        __syncthreads();                                                             // every read of the phase is done
-        rc_store_line<1>(s + row, in_rows, v);
-        __syncthreads();
-        const unsigned in_cols = rc_relax_line<RC_PITCH, 1>(s + col, su + col, v);
-        __syncthreads();
-        rc_store_line<RC_PITCH>(s + col, in_cols, v);
-        if (!__syncthreads_or((in_rows | in_cols) != 0)) break;                      // the tile is at its fixed point
-    }
-
-    unsigned n = 0;
-    for (int i = t; i < OH * OW; i += 256) {
-        const int y = i / OW, x = i - y * OW;
-        const size_t e = img + (size_t)(oy + y) * W + ox + x;
-        const int k = s[(1 + y) * RC_PITCH + 1 + x];
-        n += k > src[e];
-        dst[e] = k;
-    }
-    n = wave_sum(n);
-    if ((t & 63) == 0 && n) __hip_atomic_fetch_add(&changed[b], n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __shared__ int s[SW_STAGED * SW_PITCH], su[SW_STAGED * SW_PITCH];                // 2 x 17.3 KiB
+    const SweepTile tl = sweep_tile(H, W);
+    sweep_stage(tl, H, W, [&](int i, bool in, size_t e, int, int, int, int) {       // past the image -1, which never changes
+        s[i] = in ? src[e] : -1;
+        su[i] = in ? under[e] : -1;
+    });
+    sweep_converge(s, [&](int o, int (&v)[SW_SEG]) { return rc_relax_line<1, SW_PITCH>(s + o, su + o, v); },
+                   [&](int o, int (&v)[SW_SEG]) { return rc_relax_line<SW_PITCH, 1>(s + o, su + o, v); });
+    sweep_write_back(tl, s, src, dst, W, changed, [](int k, int was) { return k > was; });
 }
 
 __global__ __launch_bounds__(256) void rc_finish_kernel(const int *__restrict__ r, const int *__restrict__ base, size_t npx,
@@ -278,8 +233,7 @@ __global__ __launch_bounds__(256) void sh_maxima_kernel(const int *__restrict__ 
 using namespace unet;
 
 static size_t sh_plane(int B, int H, int W) { return plane_bytes(B, H, W, sizeof(int)); }
-static bool sh_sizes_ok(int B, int H, int W) { return (size_t)H * W < (1u << 31) && H <= DM_EDGE && W <= DM_EDGE && B <= 65535; }
-#define SH_SIZE_CHECK(name) ARG_CHECK(sh_sizes_ok(B, H, W), name ": image too large (H, W <= 32767, H * W < 2^31, B <= 65535)")
+#define SH_SIZE_CHECK(name) ARG_CHECK(sizes_ok(B, H, W, DM_EDGE), name ": image too large (H, W <= 32767, H * W < 2^31, B <= 65535)")
 
 // [g, the column distances]
 size_t unet_distance_map_scratch_bytes(int B, int H, int W)
@@ -336,18 +290,12 @@ int unet_reconstruct_sweeps(int B, int H, int W, int n_launches, void *changed_o
     ARG_CHECK(changed_out_u32 && scratch && B > 0 && H > 0 && W > 0 && n_launches > 0 && first_slot >= 0, "unet_reconstruct_sweeps: bad argument");
     SH_SIZE_CHECK("unet_reconstruct_sweeps");
     hipStream_t st = (hipStream_t)stream;
-    unsigned *changed = (unsigned *)changed_out_u32 + (size_t)first_slot * B;
-    HIP_TRY(hipMemsetAsync(changed, 0, (size_t)n_launches * B * sizeof(unsigned), st));
     const size_t bytes = sh_plane(B, H, W);
-    int *plane[2] = {(int *)scratch, (int *)((char *)scratch + bytes)};
     const int *under = (const int *)((char *)scratch + 2 * bytes);
-    const dim3 grid(cdiv(W, RC_TILE), cdiv(H, RC_TILE), B);
-    for (int l = 0; l < n_launches; ++l)
-        hipLaunchKernelGGL(rc_sweep_kernel, grid, dim3(256), 0, st, (const int *)plane[l & 1], under, plane[~l & 1], H, W,
-                           changed + (size_t)l * B);
-    HIP_TRY(hipGetLastError());
-    if (n_launches & 1) HIP_TRY(hipMemcpyAsync(plane[0], plane[1], (size_t)B * H * W * sizeof(int), hipMemcpyDeviceToDevice, st));
-    return 0;
+    return sweep_launches(scratch, (char *)scratch + bytes, sizeof(int), B, H, W, n_launches, changed_out_u32, first_slot, st,
+                          [&](dim3 grid, void *src, void *dst, unsigned *changed) {
+                              hipLaunchKernelGGL(rc_sweep_kernel, grid, dim3(256), 0, st, (const int *)src, under, (int *)dst, H, W, changed);
+                          });
 }
 
 int unet_reconstruct_finish(int B, int H, int W, void *out_i32, void *raised_u32, void *scratch, void *stream)

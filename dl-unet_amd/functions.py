@@ -827,6 +827,25 @@ def warping_error(pred_mask, gt_mask, *, reach=None, mask=None, connectivity=4):
                       error_regions=regions, warping_error_mean=np.float64(err.mean()))
 
 
+def _sweep_to_idle(entry, dev, B, launches, before, after=(), behind_first=None):
+    """Runs a sweep entry (unet_*_sweeps / unet_flood_assign: ..., n_launches, slots, first_slot, ...) to its first idle launch:
+    `launches` launches are enqueued, their change counts [launches, B] read back in one copy, and the loop ends at the first
+    launch that changed nothing (so did all after it).  Returns the launches needed, that idle one included.  behind_first()
+    runs once, behind the first enqueued round: a read of status words there needs no wait of its own.  (warp_labels keeps its
+    own loop: slots [launches, 4, B], per-sweep flip counts, state updated in place.)"""
+    import _hip
+    n = 0
+    while True:
+        slots = torch.empty(launches, B, dtype=torch.int32, device=dev)
+        _hip.run(entry, dev, *before, launches, _hip.ptr(slots), 0, *after)
+        if n == 0 and behind_first is not None:
+            behind_first()
+        idle = ~slots.cpu().numpy().any(axis=1)
+        if idle.any():
+            return n + int(np.argmax(idle)) + 1
+        n += launches
+
+
 SplitInfo = collections.namedtuple("SplitInfo", "seeds_outside unreached max_distance launches")
 
 
@@ -878,15 +897,7 @@ def split_cells(seeds, mask, *, max_steps=None, orphans='drop', return_distance=
     status = torch.empty(B, dtype=torch.int64, device=dev)
     scratch = _hip.scratch("unet_geodesic", dev, B, H, W)
     _hip.run("unet_geodesic_init", dev, _hip.ptr(sd), _hip.ptr(mk), code, B, H, W, _hip.ptr(counts[0]), _hip.ptr(status), _hip.ptr(scratch))
-    launches = 0
-    while True:
-        slots = torch.empty(_launches, B, dtype=torch.int32, device=dev)
-        _hip.run("unet_geodesic_sweeps", dev, B, H, W, steps, _launches, _hip.ptr(slots), 0, _hip.ptr(scratch))
-        idle = ~slots.cpu().numpy().any(axis=1)
-        if idle.any():                                                  # a launch that changed nothing: so did all after it
-            launches += int(np.argmax(idle)) + 1
-            break
-        launches += _launches
+    launches = _sweep_to_idle("unet_geodesic_sweeps", dev, B, _launches, (B, H, W, steps), (_hip.ptr(scratch),))
     labels = torch.empty(B, H, W, dtype=torch.int32, device=dev)
     dist = torch.empty(B, H, W, dtype=torch.int32, device=dev) if return_distance else None
     _hip.run("unet_geodesic_finish", dev, B, H, W, steps, _hip.ptr(labels), _hip.ptr(dist), _hip.ptr(counts[1]), _hip.ptr(counts[2]),
@@ -969,26 +980,14 @@ def watershed(seeds, image, *, mask=None, levels=None, max_level=None, return_le
     scratch = _hip.scratch("unet_flood", dev, B, H, W)
     _hip.run("unet_flood_init", dev, _hip.ptr(sd), _hip.ptr(im), im_code, levels or 0, _hip.ptr(mk), mk_code, B, H, W, _hip.ptr(counts[0]),
              _hip.ptr(status), _hip.ptr(scratch))
-    launches = []
-    for stage in (1, 2):                                               # stage 2 starts after an idle launch of stage 1 was seen
-        n = 0
-        while True:
-            slots = torch.empty(_launches, B, dtype=torch.int32, device=dev)
-            if stage == 1:
-                _hip.run("unet_flood_sweeps", dev, B, H, W, top, _launches, _hip.ptr(slots), 0, _hip.ptr(scratch))
-            else:
-                _hip.run("unet_flood_assign", dev, B, H, W, _launches, _hip.ptr(slots), 0, _hip.ptr(scratch))
-            if stage == 1 and n == 0:                                   # behind the first round: no wait of its own
-                bad = int(status[1].sum())
-                if bad:
-                    raise ValueError("watershed: %d pixels hold an image value that is not finite" % bad if im_code == 1 else
-                                     "watershed: %d pixels hold an image value outside [0, %d)" % (bad, FLOOD_LEVELS))
-            idle = ~slots.cpu().numpy().any(axis=1)
-            if idle.any():                                              # a launch that changed nothing: so did all after it
-                n += int(np.argmax(idle)) + 1
-                break
-            n += _launches
-        launches.append(n)
+    def values_ok():
+        bad = int(status[1].sum())
+        if bad:
+            raise ValueError("watershed: %d pixels hold an image value that is not finite" % bad if im_code == 1 else
+                             "watershed: %d pixels hold an image value outside [0, %d)" % (bad, FLOOD_LEVELS))
+
+    launches = [_sweep_to_idle("unet_flood_sweeps", dev, B, _launches, (B, H, W, top), (_hip.ptr(scratch),), values_ok),
+                _sweep_to_idle("unet_flood_assign", dev, B, _launches, (B, H, W), (_hip.ptr(scratch),))]   # after an idle stage-1 launch
     labels = torch.empty(B, H, W, dtype=torch.int32, device=dev)
     lev, dist = (torch.empty(2, B, H, W, dtype=torch.int32, device=dev) if return_levels else (None, None))
     _hip.run("unet_flood_finish", dev, B, H, W, _hip.ptr(labels), _hip.ptr(lev), _hip.ptr(dist), _hip.ptr(counts[1]), _hip.ptr(counts[2]),
@@ -1074,19 +1073,12 @@ def reconstruct(marker, under, *, mask=None, _launches=8):
     scratch = _hip.scratch("unet_reconstruct", dev, B, H, W)
     _hip.run("unet_reconstruct_init", dev, _hip.ptr(mr), mr_code, _hip.ptr(un), un_code, _hip.ptr(mk), mk_code, B, H, W, _hip.ptr(status),
              _hip.ptr(scratch))
-    launches = 0
-    while True:
-        slots = torch.empty(_launches, B, dtype=torch.int32, device=dev)
-        _hip.run("unet_reconstruct_sweeps", dev, B, H, W, _launches, _hip.ptr(slots), 0, _hip.ptr(scratch))
-        if launches == 0:
-            bad = int(status.sum())
-            if bad:
-                raise ValueError("reconstruct: %d pixels hold a marker or under value outside [0, 2^30]" % bad)
-        idle = ~slots.cpu().numpy().any(axis=1)
-        if idle.any():                                                  # a launch that raised nothing: so did all after it
-            launches += int(np.argmax(idle)) + 1
-            break
-        launches += _launches
+    def values_ok():
+        bad = int(status.sum())
+        if bad:
+            raise ValueError("reconstruct: %d pixels hold a marker or under value outside [0, 2^30]" % bad)
+
+    launches = _sweep_to_idle("unet_reconstruct_sweeps", dev, B, _launches, (B, H, W), (_hip.ptr(scratch),), values_ok)
     out = torch.empty(B, H, W, dtype=torch.int32, device=dev)
     _hip.run("unet_reconstruct_finish", dev, B, H, W, _hip.ptr(out), _hip.ptr(raised), _hip.ptr(scratch))
     info = ReconInfo(launches=launches, raised=raised.cpu().numpy().astype(np.int64))
