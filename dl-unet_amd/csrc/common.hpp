@@ -213,17 +213,16 @@ static inline int class_pad(int K) { return K <= 2 ? 2 : K <= 4 ? 4 : K <= 8 ? 8
         default: { constexpr int KP_ = 16; LAUNCH; } break;                                                        \
         }                                                                                                          \
     } while (0)
-// exact 4-connected labelling (wmap.hip, passes ccl_local / ccl_merge / ccl_flatten; shared by unet_weighted_map and
-// unet_label_components): label [B,H,W] = the smallest pixel index of the pixel's component in its image, -1 where mask == 0
-// (dtype 0: int64, 1: float32); counts[b] = foreground pixels, n_objects[b] = components; parent is an int plane of scratch
-int ccl_labels(const void *mask, int dtype, int B, int H, int W, int *parent, int *label, unsigned long long *counts, int *n_objects,
-               hipStream_t st);
-// raster numbering of root labels (instances.hip, passes inst_count / inst_scan / inst_rank / inst_write; shared by
-// unet_label_components and clean.hip): label [B,H,W] holds each pixel's root (the smallest pixel index of its component) or
-// -1 and becomes 1..n in raster order of the roots, 0 where it was -1; ids is an int plane of scratch, chunk_roots
-// inst_chunk_bytes(B, H, W) bytes of it
-size_t inst_chunk_bytes(int B, int H, int W);
-int inst_number(int *label, int *ids, int *chunk_roots, int B, int H, int W, hipStream_t st);
+// exact labelling (label.hip, passes label_local / label_merge / label_flatten; unet_label_components[_conn], unet_weighted_map
+// and unet_clean_mask) of the pixels with (mask != 0) == phase (dtype 0: int64, 1: float32, 2: int32, 3: uint8), 4-connected or
+// with conn8 8-connected: parent and label are int planes [B,H,W], attr an unsigned one or null (no attributes); label = the
+// root, the smallest pixel index of the pixel's component in its image, or -1 off the phase; with attr, attr[root] & LB_AREA =
+// the component's area, LB_FRAME = it touches the first or last row or column; n_objects [B] (or null) receives the component
+// counts and fg_counts [B] (or null; null with attr) the pixels in the phase, both zeroed here.  The parent words are dead afterwards.  The
+// caller has checked label_sizes_ok (elem.hpp).
+static constexpr unsigned LB_FRAME = 0x80000000u, LB_AREA = 0x7fffffffu;
+int label_roots(const void *mask, int dtype, int B, int H, int W, int phase, int conn8, int *parent, int *label, unsigned *attr,
+                int *n_objects, unsigned long long *fg_counts, hipStream_t st);
 int maxpool2_fwd(const void *x, void *y, int B, int H, int W, int C, int es, hipStream_t st);
 int maxpool2_bwd(const void *pre, const void *dy, void *dpre, int B, int H, int W, int C, int es, hipStream_t st);
 // drop-out (dropout.hip): x [B,H,W,C] dropped in place (+ its 2x2 max-pool into `pooled`, or null); g[0, n) *= 1 / (1 - p)

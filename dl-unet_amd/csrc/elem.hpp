@@ -1,13 +1,15 @@
-// elem.hpp — what the HBM-bound kernels (direct.hip, multiclass.hip, tile.hip, aux.hip) and the data-path files (wmap.hip,
-// instances.hip, prepare.hip, grow.hip, elastic.hip, clean.hip, and through sweep.hpp geo.hip, shape.hip, flood.hip) share:
+// elem.hpp — what the HBM-bound kernels (direct.hip, multiclass.hip, tile.hip, aux.hip) and the data-path files (label.hip, wmap.hip,
+// instances.hip, prepare.hip, grow.hip, elastic.hip, clean.hip, warp.hip, and through sweep.hpp geo.hip, shape.hip, flood.hip) share:
 //   device : 4 consecutive channels of an activation tensor stored as fp32 (16 B) or bf16 (8 B, arithmetic mode 2), read /
 //            written as 4 floats; the sum / min / max of one value per lane over a wave; the min and max of one value per thread
 //            over a block; the sum of one value per thread over a 256-thread block, with the max of a second one (the finish
-//            kernels of geo.hip and flood.hip), and (instances.hip, prepare.hip) the
-//            exclusive prefix of one int per thread over it; whether an element of a mask of any of the four dtypes is set;
-//            the union-find of the labellings (wmap.hip, clean.hip) on LDS words and on global words
-//   host   : the grid size of a grid-stride launch, the bytes of a [B,H,W] scratch plane, and the dispatch of a launch on
-//            element size, channel width and padded class count (the launch bracket, profiled(), is common.hpp's)
+//            kernels of geo.hip and flood.hip), and (label.hip, prepare.hip) the
+//            exclusive prefix of one int per thread over it; a few counts per thread summed over the workgroup into one
+//            agent-scope add per word (label.hip, clean.hip); whether an element of a mask of any of the four dtypes is set;
+//            the union-find of the labelling (label.hip) on LDS words and on global words
+//   host   : the grid size of a grid-stride launch, the bytes of a [B,H,W] scratch plane, the size limits of the [B,H,W] ops,
+//            and the dispatch of a launch on element size, channel width and padded class count (the launch bracket,
+//            profiled(), is common.hpp's)
 #pragma once
 #include "common.hpp"
 #include <type_traits>
@@ -106,7 +108,24 @@ __device__ __forceinline__ int block_scan256(int v, int &total)
     return before + inc - v;
 }
 
-// is element e of a mask non-zero (prepare.hip, warp.hip; dtype 0: int64, 1: float32, 2: int32, 3: uint8)
+// n[k], summed over the workgroup, is added to words[k] by one agent-scope add per workgroup and word (none where the sum is 0):
+// the adds of a launch meet on a few words per image, so they are reduced in the wave and in LDS first.  Every thread calls it.
+template <int N, typename W>
+__device__ __forceinline__ void block_counts(W *words, const unsigned (&n)[N])
+{
+    __shared__ unsigned tot[N];
+    if (threadIdx.x < N) tot[threadIdx.x] = 0;
+    __syncthreads();
+    for (int k = 0; k < N; ++k) {
+        const unsigned v = wave_sum(n[k]);
+        if ((threadIdx.x & 63) == 0 && v) atomicAdd(&tot[k], v);
+    }
+    __syncthreads();
+    if (threadIdx.x < N && tot[threadIdx.x])
+        __hip_atomic_fetch_add(&words[threadIdx.x], (W)tot[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// is element e of a mask non-zero (label.hip, clean.hip, prepare.hip, warp.hip; dtype 0: int64, 1: float32, 2: int32, 3: uint8)
 __device__ __forceinline__ int mask_on(const void *mask, int dtype, size_t e)
 {
     if (dtype == 0) return ((const long long *)mask)[e] != 0;
@@ -115,7 +134,7 @@ __device__ __forceinline__ int mask_on(const void *mask, int dtype, size_t e)
     return ((const unsigned char *)mask)[e] != 0;
 }
 
-// Union-find on a plane of parent words, the smaller index always the parent (wmap.hip, clean.hip).  lds_*: a tile's words in
+// Union-find on a plane of parent words, the smaller index always the parent (label.hip).  lds_*: a tile's words in
 // LDS, workgroup scope.  gl_*: the image's words in global memory, where every read and update is an agent-scope atomic
 // read-modify-write (per-XCD L2s are not coherent and a CU's L1 is never refreshed by other CUs' stores).
 __device__ __forceinline__ int lds_find(int *lp, int p)
@@ -168,8 +187,16 @@ static inline int grid_for(size_t total, int per_block = 256, int cap = 8192)
     return (int)(g < 1 ? 1 : (g > (size_t)cap ? cap : g));
 }
 
+// workgroups per image of a grid-stride pass that ends in block_counts: about 4096 in all, so that its adds stay few per word
+static inline int count_blocks(size_t npx, int B) { return grid_for(npx, 256, 4096 / B > 1 ? 4096 / B : 1); }
+
 // bytes of a [B,H,W] plane of elem_size-byte words inside a scratch buffer, 256-aligned
 static inline size_t plane_bytes(int B, int H, int W, size_t elem_size) { return align_up((size_t)B * H * W * elem_size, 256); }
+
+// Size limits of the [B,H,W] ops.  sizes_ok: H, W <= edge (65535: a grid dimension; 32767: H^2 + W^2 is an int32).
+// label_sizes_ok: the labelling (label.hip) and what stands on its planes (wmap.hip, clean.hip); W is bounded by H * W alone
+static inline bool sizes_ok(int B, int H, int W, int edge) { return (size_t)H * W < (1u << 31) && H <= edge && W <= edge && B <= 65535; }
+static inline bool label_sizes_ok(int B, int H, int W) { return (size_t)H * W < (1u << 31) && H <= 65535 && B <= 65535; }
 
 // Launch dispatch: f is a generic lambda that receives the storage type as a value of it (es 2: bf16_t, else float), then the
 // channel width (32 or 64; the callers have checked it) and for the K-class head KP = class_pad(K) (4, 8 or 16: K = 2 runs the

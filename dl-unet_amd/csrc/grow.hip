@@ -22,7 +22,7 @@
 // Cost: H * W * min(W, 2 R + 257) key evaluations (one LDS broadcast read, one 64-bit add, one 64-bit minimum each), about
 // 1.4e8 for an unlimited 512 x 512 image, plus 2 H steps per column.  Nothing depends on the number of cells or on their ids.
 //
-// Coherence (wmap.hip's rule): grow_rows reads what grow_cols, an earlier kernel, wrote; in grow_cols a thread re-reads only the
+// Coherence (label.hip's rule): grow_rows reads what grow_cols, an earlier kernel, wrote; in grow_cols a thread re-reads only the
 // words of its own column, which it wrote itself.  No word is handed from one workgroup to another inside a kernel.
 #include "elem.hpp"
 #include <algorithm>

@@ -1,14 +1,5 @@
-// instances.hip — cell instances from a foreground mask, and the per-cell overlaps the Cell Tracking Challenge SEG measure
-// needs (Ronneberger et al. 2015, Table 2), batched, on the device.
-//
-// unet_label_components: ccl_labels (wmap.hip passes 1-3: label = root = the smallest pixel index of the component), then
-//   4. inst_count  one workgroup per 1024 consecutive pixels: how many of them are roots (label[e] == e)
-//   5. inst_scan   one workgroup per image: exclusive scan of those counts
-//   6. inst_rank   the same 1024 pixels again: a root writes 1 + (roots before it in raster order) into the id plane at its index
-//   7. inst_write  labels = id[root], 0 on background
-// A component's root is its first pixel in raster order, so the ranks of the roots are the raster numbering of
-// scipy.ndimage.label / cv.connectedComponents(connectivity=4).  Passes 4-7 touch every pixel a fixed number of times: their
-// cost does not depend on how many components there are.  They are inst_number (common.hpp), which clean.hip calls too.
+// instances.hip — the per-cell overlaps of two instance maps (label.hip makes such maps from a mask) that the Cell Tracking
+// Challenge SEG measure needs (Ronneberger et al. 2015, Table 2), and their contingency table, batched, on the device.
 //
 // unet_instance_overlap: two id maps -> per-id areas, and for every ground-truth id the one predicted id that covers more than
 // half of it, with the size of that overlap:
@@ -25,69 +16,14 @@
 //   2. pairs_compact     a wave reads 64 slots, one agent-scope add on n_pairs gives it a block of the dense (key, count) list
 // The list's order depends on the order of those adds; its content does not.
 //
-// Coherence (wmap.hip's rule): inside overlap_fill a table key is only ever touched by an agent-scope compare-and-swap, a
-// counter, a histogram bin or a status word only by an agent-scope add, and n_pairs in pairs_compact likewise; overlap_match,
-// pairs_compact, and every pass of the labelling, reads
-// what an earlier kernel wrote.  No word is handed from one workgroup to another inside a kernel by plain loads and stores.
+// Coherence (label.hip's rule): inside overlap_fill a table key is only ever touched by an agent-scope compare-and-swap, a
+// counter, a histogram bin or a status word only by an agent-scope add, and n_pairs in pairs_compact likewise; overlap_match
+// and pairs_compact read what an earlier kernel wrote.  No word is handed from one workgroup to another inside a kernel by plain
+// loads and stores.
 #include "ov_table.hpp"
 #include "../../include/unet_hip.h"
 
 namespace unet {
-
-static constexpr int IN_CHUNK = 1024;                        // pixels per workgroup of inst_count / inst_rank: 256 threads x 4
-
-// roots among this thread's 4 consecutive pixels, as a bit mask
-__device__ __forceinline__ int inst_roots(const int *__restrict__ L, size_t npx, size_t e0)
-{
-    int m = 0;
-    for (int k = 0; k < 4; ++k)
-        if (e0 + k < npx && L[e0 + k] == (int)(e0 + k)) m |= 1 << k;
-    return m;
-}
-
-__global__ __launch_bounds__(256) void inst_count_kernel(const int *__restrict__ label, size_t npx, int *__restrict__ chunk_roots)
-{
-    const size_t e0 = (size_t)blockIdx.x * IN_CHUNK + threadIdx.x * 4;
-    int total;
-    block_scan256(__popc(inst_roots(label + (size_t)blockIdx.y * npx, npx, e0)), total);
-    if (threadIdx.x == 0) chunk_roots[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = total;
-}
-
-// in place: chunk_roots[b][c] becomes the number of roots in the chunks before c
-__global__ __launch_bounds__(256) void inst_scan_kernel(int *__restrict__ chunk_roots, int nchunk)
-{
-    int *c = chunk_roots + (size_t)blockIdx.x * nchunk;
-    int carry = 0;
-    for (int base = 0; base < nchunk; base += 256) {
-        const int i = base + threadIdx.x;
-        const int v = i < nchunk ? c[i] : 0;
-        int total;
-        const int before = block_scan256(v, total);
-        if (i < nchunk) c[i] = carry + before;
-        carry += total;
-    }
-}
-
-__global__ __launch_bounds__(256) void inst_rank_kernel(const int *__restrict__ label, size_t npx, const int *__restrict__ chunk_before,
-                                                        int *__restrict__ id)
-{
-    const size_t img = (size_t)blockIdx.y * npx, e0 = (size_t)blockIdx.x * IN_CHUNK + threadIdx.x * 4;
-    const int m = inst_roots(label + img, npx, e0);
-    int total;
-    int rank = chunk_before[(size_t)blockIdx.y * gridDim.x + blockIdx.x] + block_scan256(__popc(m), total);
-    for (int k = 0; k < 4; ++k)
-        if (m >> k & 1) id[img + e0 + k] = ++rank;
-}
-
-// label holds the root (or -1) on entry and the component's number (or 0) on return; each thread rewrites only what it read
-__global__ __launch_bounds__(256) void inst_write_kernel(int *__restrict__ label, size_t npx, const int *__restrict__ id)
-{
-    const size_t img = (size_t)blockIdx.y * npx;
-    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < npx; e += (size_t)gridDim.x * blockDim.x) {
-        const int r = label[img + e];
-        label[img + e] = r >= 0 ? id[img + r] : 0;
-    }
-}
 
 // ---- overlaps ---------------------------------------------------------------------------------------------------------
 // FG = false: unet_instance_overlap (both area histograms, pairs with g, p >= 1).  FG = true: unet_partition_pairs (no histogram,
@@ -182,50 +118,9 @@ __global__ __launch_bounds__(256) void pairs_compact_kernel(const unsigned long 
     }
 }
 
-static size_t in_chunks(int H, int W) { return ((size_t)H * W + IN_CHUNK - 1) / IN_CHUNK; }
-size_t inst_chunk_bytes(int B, int H, int W) { return align_up((size_t)B * in_chunks(H, W) * sizeof(int), 256); }
-
-// passes 4-7 on st (shared with clean.hip)
-int inst_number(int *label, int *ids, int *chunk_roots, int B, int H, int W, hipStream_t st)
-{
-    const size_t npx = (size_t)H * W;
-    const unsigned nchunk = (unsigned)in_chunks(H, W);
-    hipLaunchKernelGGL(inst_count_kernel, dim3(nchunk, B), dim3(256), 0, st, (const int *)label, npx, chunk_roots);
-    hipLaunchKernelGGL(inst_scan_kernel, dim3(B), dim3(256), 0, st, chunk_roots, (int)nchunk);
-    hipLaunchKernelGGL(inst_rank_kernel, dim3(nchunk, B), dim3(256), 0, st, (const int *)label, npx, (const int *)chunk_roots, ids);
-    hipLaunchKernelGGL(inst_write_kernel, dim3(grid_for(npx, 256, 2048), B), dim3(256), 0, st, label, npx, (const int *)ids);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
 } // namespace unet
 
 using namespace unet;
-
-static size_t in_plane(int B, int H, int W) { return plane_bytes(B, H, W, sizeof(int)); }
-static size_t in_chunk_bytes(int B, int H, int W) { return inst_chunk_bytes(B, H, W); }
-
-size_t unet_label_components_scratch_bytes(int B, int H, int W)
-{
-    if (B <= 0 || H <= 0 || W <= 0) return 0;
-    return in_plane(B, H, W) + in_chunk_bytes(B, H, W) + align_up((size_t)B * sizeof(unsigned long long), 256);
-}
-
-int unet_label_components(const void *mask, int dtype, int B, int H, int W, void *labels_i32, void *n_objects_i32, void *scratch,
-                          void *stream)
-{
-    ARG_CHECK(mask && labels_i32 && n_objects_i32 && scratch && B > 0 && H > 0 && W > 0, "unet_label_components: bad argument");
-    ARG_CHECK(dtype == 0 || dtype == 1, "unet_label_components: dtype must be 0 (int64) or 1 (float32)");
-    ARG_CHECK((size_t)H * W < (1u << 31) && H <= 65535 && B <= 65535, "unet_label_components: image too large");
-    hipStream_t st = (hipStream_t)stream;
-    char *s = (char *)scratch;
-    int *plane = (int *)s;                                        // the parent words, then (they are dead after ccl_flatten) the ids
-    int *chunk_roots = (int *)(s + in_plane(B, H, W));
-    unsigned long long *counts = (unsigned long long *)(s + in_plane(B, H, W) + in_chunk_bytes(B, H, W));
-    int *label = (int *)labels_i32;
-    if (int rc = ccl_labels(mask, dtype, B, H, W, plane, label, counts, (int *)n_objects_i32, st)) return rc;
-    return inst_number(label, plane, chunk_roots, B, H, W, st);
-}
 
 struct OvTable { unsigned long long *keys; unsigned *cnt; };
 

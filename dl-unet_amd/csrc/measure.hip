@@ -28,7 +28,7 @@
 // commute, so every integer field is the same in every run, whichever of the two paths a run took; the fp64 sums of a float
 // image are summed in fixed order inside a run and in arrival order across runs.
 //
-// Coherence (wmap.hip's rule): during ms_fill a global record word is touched only by agent-scope atomic read-modify-writes,
+// Coherence (label.hip's rule): during ms_fill a global record word is touched only by agent-scope atomic read-modify-writes,
 // never read or stored plainly; ms_finish is a later kernel of the same stream and reads with plain loads.  The status words
 // likewise.  The LDS table is workgroup-scope and handed over by barriers.
 #include "elem.hpp"

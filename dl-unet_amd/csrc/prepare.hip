@@ -22,7 +22,7 @@
 //   3. crop_colsum   one thread per (b, i, j) sums rowsum[skip i .. skip i + crop)[j]
 //   Every pixel is read once, every prefix word twice at the most: nothing is read once per window.
 //
-// Coherence (wmap.hip's rule): status words are only touched by agent-scope adds; every other word a kernel reads was written
+// Coherence (label.hip's rule): status words are only touched by agent-scope adds; every other word a kernel reads was written
 // by an earlier kernel of the same stream (or by the caller).  No word is handed from one workgroup to another inside a kernel.
 #include "elem.hpp"
 #include <algorithm>

@@ -30,7 +30,7 @@
 // The element-wise steps of shape_seeds: sh_heights (q = floor(16 sqrt(d2)) exactly, and q + hq), sh_lower (max(v - c, 0)),
 // sh_maxima (1.0 where r2 < r1 and r1 >= a floor, else 0.0: a mask unet_label_components takes).
 //
-// Coherence (wmap.hip's rule): every kernel reads what an earlier kernel wrote (rc_sweep: sweep.hpp); in dm_cols a thread re-reads
+// Coherence (label.hip's rule): every kernel reads what an earlier kernel wrote (rc_sweep: sweep.hpp); in dm_cols a thread re-reads
 // only its own column.  The counters are only touched by agent-scope adds.
 #include "sweep.hpp"
 #include <cmath>

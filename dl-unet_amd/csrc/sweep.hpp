@@ -9,7 +9,7 @@
 // reads a word another one may be storing.  The loop ends when both phases moved nothing.  Only the owned tile is written, to the
 // other plane, and the owned pixels whose word moved are counted into changed[b], one agent-scope add per wave.
 //
-// Coherence (wmap.hip's rule): a sweep reads plane A, which an earlier kernel wrote, and writes plane B, which no workgroup of
+// Coherence (label.hip's rule): a sweep reads plane A, which an earlier kernel wrote, and writes plane B, which no workgroup of
 // the launch reads: a neighbour's halo read never sees this launch's stores, and the hand-off between tiles is the kernel
 // boundary.  The counters are only touched by agent-scope adds.  No word is handed from one workgroup to another inside a
 // kernel, no loop waits on a load.
@@ -97,9 +97,6 @@ __device__ __forceinline__ void sweep_write_back(const SweepTile tl, const T *s,
     n = wave_sum(n);
     if ((threadIdx.x & 63) == 0 && n) __hip_atomic_fetch_add(&changed[tl.b], n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-
-// H, W <= edge (65535: a grid dimension; 32767: H^2 + W^2 is an int32)
-static inline bool sizes_ok(int B, int H, int W, int edge) { return (size_t)H * W < (1u << 31) && H <= edge && W <= edge && B <= 65535; }
 
 // n_launches sweeps, launch l from plane[l & 1] to plane[~l & 1] with the counters slots[first_slot + l][B], zeroed here; the
 // result ends in plane0.  launch(grid, src, dst, changed) enqueues one sweep.

@@ -10,7 +10,7 @@
 //   3. link_decode  one thread per (t, c): the word -> pred[t][c], pred_overlap[t][c]; a word nobody touched gives 0, 0
 // Every count is an integer sum and the max is over a total order: the outputs do not depend on the order of the atomics.
 //
-// Coherence (wmap.hip's rule): inside link_fill a table key is only ever touched by an agent-scope compare-and-swap, a counter, an
+// Coherence (label.hip's rule): inside link_fill a table key is only ever touched by an agent-scope compare-and-swap, a counter, an
 // area bin or a status word only by an agent-scope add; inside link_pick a word of `best` only by an agent-scope max; link_pick and
 // link_decode read what an earlier kernel wrote.  No word is handed from one workgroup to another inside a kernel.
 #include "ov_table.hpp"

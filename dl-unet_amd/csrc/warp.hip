@@ -24,7 +24,7 @@
 // The 256-entry table of simple neighbourhoods is built on the host from the component definition (wp_simple) and handed to the
 // kernel by value.
 //
-// Coherence (wmap.hip's rule): warp_sweeps reads plane A, which an earlier kernel wrote, and writes plane B, which no workgroup
+// Coherence (label.hip's rule): warp_sweeps reads plane A, which an earlier kernel wrote, and writes plane B, which no workgroup
 // of the launch reads; the counters are only touched by agent-scope adds.  No word is handed from one workgroup to another inside
 // a kernel.
 #include "elem.hpp"
@@ -250,7 +250,6 @@ using namespace unet;
 
 static size_t wp_state(int B, int H, int W) { return plane_bytes(B, H, W, 1); }
 static size_t wp_ints(int B, int H, int W) { return plane_bytes(B, H, W, sizeof(int)); }
-static bool wp_sizes_ok(int B, int H, int W) { return (size_t)H * W < (1u << 31) && H <= 65535 && W <= 65535 && B <= 65535; }
 static bool wp_dtype_ok(int d) { return d >= 0 && d <= 3; }
 
 // [state plane B | class map | grown map of gt != 0 | grown map of gt == 0 | the scratch of unet_grow_labels]
@@ -267,7 +266,7 @@ int unet_warp_init(const void *gt, int gt_dtype, const void *pred, int pred_dtyp
     ARG_CHECK(wp_dtype_ok(gt_dtype) && wp_dtype_ok(pred_dtype) && (!mask || wp_dtype_ok(mask_dtype)),
               "unet_warp_init: a dtype must be 0 (int64), 1 (float32), 2 (int32) or 3 (uint8)");
     ARG_CHECK(connectivity == 4 || connectivity == 8, "unet_warp_init: connectivity must be 4 or 8");
-    ARG_CHECK(wp_sizes_ok(B, H, W), "unet_warp_init: image too large (the limits of unet_grow_labels)");
+    ARG_CHECK(sizes_ok(B, H, W, 65535), "unet_warp_init: image too large (the limits of unet_grow_labels)");
     hipStream_t st = (hipStream_t)stream;
     const size_t npx = (size_t)H * W;
     const int *near_fg = nullptr, *near_bg = nullptr;
@@ -305,7 +304,7 @@ int unet_warp_sweeps(void *state_u8, int B, int H, int W, int passes_per_launch,
               "unet_warp_sweeps: bad argument");
     ARG_CHECK(passes_per_launch == 4 || passes_per_launch == 8 || passes_per_launch == 16,
               "unet_warp_sweeps: passes_per_launch must be 4, 8 or 16");
-    ARG_CHECK(wp_sizes_ok(B, H, W), "unet_warp_sweeps: image too large (the limits of unet_grow_labels)");
+    ARG_CHECK(sizes_ok(B, H, W, 65535), "unet_warp_sweeps: image too large (the limits of unet_grow_labels)");
     hipStream_t st = (hipStream_t)stream;
     const size_t slot = (size_t)WP_SUB * B;
     unsigned *flips = (unsigned *)flips_out_u32 + (size_t)first_slot * slot;
@@ -330,7 +329,7 @@ int unet_warp_finish(const void *state_u8, int B, int H, int W, int connectivity
 {
     ARG_CHECK(state_u8 && warped_i32 && mismatch_map_f32 && mismatch_u32 && B > 0 && H > 0 && W > 0, "unet_warp_finish: bad argument");
     ARG_CHECK(connectivity == 4 || connectivity == 8, "unet_warp_finish: connectivity must be 4 or 8");
-    ARG_CHECK(wp_sizes_ok(B, H, W), "unet_warp_finish: image too large (the limits of unet_grow_labels)");
+    ARG_CHECK(sizes_ok(B, H, W, 65535), "unet_warp_finish: image too large (the limits of unet_grow_labels)");
     hipStream_t st = (hipStream_t)stream;
     const size_t npx = (size_t)H * W;
     HIP_TRY(hipMemsetAsync(mismatch_u32, 0, (size_t)B * sizeof(unsigned), st));

@@ -2,107 +2,24 @@
 //   w = w_c + w0 * exp(-(d1 + d2)^2 / (2 sig2)) on background,  w = 1 on cells,
 // d1 / d2 = exact Euclidean distance to the nearest / second-nearest distinct 4-connected foreground component.
 //
-//   1. ccl_local   one workgroup per 32x32 tile: union-find in LDS, every pixel -> its tile-local root (image index)
-//   2. ccl_merge   one thread per tile-border pixel pair: union of the two roots with agent-scope atomics
-//   3. ccl_flatten label = root (the smallest pixel index of the component), component count per image
+//   1-3. label_roots (label.hip): label = root (the smallest pixel index of the pixel's component), the component count and the
+//        foreground pixel count per image
 //   4. wmap_cols   per pixel, along its column within +-R: nearest foreground (dist_a, label_a), nearest label != label_a (dist_b)
 //   5. wmap_rows   per pixel, over the column results within +-R in x: d1^2, d2^2, then the weight
-//
-// Passes 1-3 are ccl_labels (common.hpp), which instances.hip calls too.
 //
 // Exactness bound: for s = d1 + d2 > R with R = ceil(sqrt(2 sig2 * 104)), expf(-s^2 / (2 sig2)) underflows (e^-104 < 2^-150),
 // so a component farther than R from a pixel cannot change that pixel's weight; every component within R is found
 // exactly by passes 4-5, whose cost depends on R and not on how many components an image has.
 //
-// Coherence (MI355X: per-XCD L2s are not coherent, a CU's L1 is never refreshed by other CUs' stores): in ccl_merge
-// every read and every update of a parent word is an agent-scope atomic read-modify-write; foreground tests there
-// read the input labels, never the parent words.  Every other hand-off is across a kernel boundary.
+// Coherence (label.hip's rule): passes 4-5 read what earlier kernels wrote; every hand-off is a kernel boundary.
 #include "elem.hpp"
 #include <cmath>
 #include "../../include/unet_hip.h"
 
 namespace unet {
 
-static constexpr int WM_TILE = 32;          // ccl_local tile edge
 static constexpr int WM_ROWS = 256;         // wmap_rows pixels per workgroup
 static constexpr unsigned WM_NONE = 0xffffu;
-
-__device__ __forceinline__ bool wm_fg(const void *labels, int dtype, size_t e)
-{
-    return dtype == 0 ? ((const long long *)labels)[e] != 0 : ((const float *)labels)[e] != 0.f;
-}
-
-// ---- 1. tile-local union-find (lds_find / lds_union: elem.hpp) ---------------------------------------------
-__global__ __launch_bounds__(256) void ccl_local_kernel(const void *__restrict__ labels, int dtype, int H, int W,
-                                                        int *__restrict__ parent, unsigned long long *__restrict__ counts)
-{
-    __shared__ int lp[WM_TILE * WM_TILE];
-    const int b = blockIdx.z, x0 = blockIdx.x * WM_TILE, y0 = blockIdx.y * WM_TILE;
-    const size_t img = (size_t)b * H * W;
-    bool fg[4];
-    unsigned long long n1 = 0;
-    for (int k = 0; k < 4; ++k) {
-        const int i = threadIdx.x + 256 * k, x = x0 + (i & 31), y = y0 + (i >> 5);
-        fg[k] = x < W && y < H && wm_fg(labels, dtype, img + (size_t)y * W + x);
-        lp[i] = fg[k] ? i : -1;
-        n1 += fg[k];
-    }
-    __syncthreads();
-    for (int k = 0; k < 4; ++k) {
-        const int i = threadIdx.x + 256 * k;
-        if (!fg[k]) continue;
-        if ((i & 31) && lp[i - 1] >= 0) lds_union(lp, i - 1, i);        // the sign of a word never changes: plain read
-        if (i >= 32 && lp[i - 32] >= 0) lds_union(lp, i - 32, i);
-    }
-    __syncthreads();
-    for (int k = 0; k < 4; ++k) {
-        const int i = threadIdx.x + 256 * k, x = x0 + (i & 31), y = y0 + (i >> 5);
-        if (x >= W || y >= H) continue;
-        int r = -1;
-        if (fg[k]) { const int l = lds_find(lp, i); r = (y0 + (l >> 5)) * W + x0 + (l & 31); }
-        parent[img + (size_t)y * W + x] = r;
-    }
-    n1 = wave_sum(n1);
-    if ((threadIdx.x & 63) == 0 && n1) atomicAdd(&counts[b], n1);
-}
-
-// ---- 2. merge across tile borders: agent-scope atomics only (gl_find / gl_union: elem.hpp) ------------------
-// per image: (tiles_x - 1) vertical borders of H pixel pairs, then (tiles_y - 1) horizontal borders of W pairs
-__global__ __launch_bounds__(256) void ccl_merge_kernel(const void *__restrict__ labels, int dtype, int H, int W, int *parent,
-                                                        int nv, int total)
-{
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= total) return;
-    const size_t img = (size_t)blockIdx.y * H * W;
-    int a, c;
-    if (e < nv) {
-        const int y = e % H, x = (e / H + 1) * WM_TILE;
-        a = y * W + x - 1; c = y * W + x;
-    } else {
-        const int x = (e - nv) % W, y = ((e - nv) / W + 1) * WM_TILE;
-        a = (y - 1) * W + x; c = y * W + x;
-    }
-    if (wm_fg(labels, dtype, img + a) && wm_fg(labels, dtype, img + c)) gl_union(parent + img, a, c);
-}
-
-// ---- 3. flatten: label = root; a root is a component -------------------------------------------------
-__global__ __launch_bounds__(256) void ccl_flatten_kernel(const int *__restrict__ parent, int *__restrict__ label, size_t npx,
-                                                          int *__restrict__ n_objects)
-{
-    const int b = blockIdx.y;
-    const int *P = parent + (size_t)b * npx;
-    int roots = 0;
-    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < npx; e += (size_t)gridDim.x * blockDim.x) {
-        int p = P[e];
-        if (p >= 0) {
-            while (P[p] != p) p = P[p];
-            roots += p == (int)e;
-        }
-        label[(size_t)b * npx + e] = p;
-    }
-    roots = wave_sum(roots);
-    if ((threadIdx.x & 63) == 0 && roots) atomicAdd(&n_objects[b], roots);
-}
 
 // ---- 4. column pass: nearest foreground (dist_a, label_a) and nearest label != label_a (dist_b) within +-R ------
 __global__ __launch_bounds__(256) void wmap_cols_kernel(const int *__restrict__ label, int H, int W, int R,
@@ -184,25 +101,6 @@ __global__ __launch_bounds__(WM_ROWS) void wmap_rows_kernel(const int *__restric
     w[row + x] = wc + wd;
 }
 
-// passes 1-3 on st (shared with instances.hip): parent and label are int planes [B,H,W]; label = the root, the smallest pixel
-// index of the pixel's component within its image, -1 on background; counts[b] = foreground pixels, n_objects[b] = components
-// (both zeroed here).  The parent words are dead afterwards.  The caller has checked H * W < 2^31, H <= 65535, B <= 65535.
-int ccl_labels(const void *mask, int dtype, int B, int H, int W, int *parent, int *label, unsigned long long *counts, int *n_objects,
-               hipStream_t st)
-{
-    const size_t npx = (size_t)H * W;
-    HIP_TRY(hipMemsetAsync(counts, 0, (size_t)B * sizeof(unsigned long long), st));
-    HIP_TRY(hipMemsetAsync(n_objects, 0, (size_t)B * sizeof(int), st));
-    const int tx = cdiv(W, WM_TILE), ty = cdiv(H, WM_TILE);
-    hipLaunchKernelGGL(ccl_local_kernel, dim3(tx, ty, B), dim3(256), 0, st, mask, dtype, H, W, parent, counts);
-    const int nv = (tx - 1) * H, total = nv + (ty - 1) * W;
-    if (total > 0)
-        hipLaunchKernelGGL(ccl_merge_kernel, dim3(cdiv(total, 256), B), dim3(256), 0, st, mask, dtype, H, W, parent, nv, total);
-    hipLaunchKernelGGL(ccl_flatten_kernel, dim3(grid_for(npx, 256, 1024), B), dim3(256), 0, st, (const int *)parent, label, npx,
-                       n_objects);
-    return 0;
-}
-
 static int wmap_radius(float sig2)
 {
     return (int)std::ceil(std::sqrt(2.0 * (double)sig2 * 104.0));
@@ -224,7 +122,7 @@ int unet_weighted_map(const void *labels, int labels_dtype, int B, int H, int W,
     ARG_CHECK(labels && weights_f32 && counts_u64 && n_objects_i32 && scratch && B > 0 && H > 0 && W > 0,
               "unet_weighted_map: bad argument");
     ARG_CHECK(labels_dtype == 0 || labels_dtype == 1, "unet_weighted_map: labels_dtype must be 0 (int64) or 1 (float32)");
-    ARG_CHECK((size_t)H * W < (1u << 31) && H <= 65535 && B <= 65535, "unet_weighted_map: image too large");
+    ARG_CHECK(label_sizes_ok(B, H, W), "unet_weighted_map: image too large");
     ARG_CHECK(std::isfinite(w0) && std::isfinite(sig2) && sig2 > 0.f, "unet_weighted_map: need finite w0 and sig2 > 0");
     const int R = wmap_radius(sig2);
     ARG_CHECK(R <= 1024, "unet_weighted_map: sig2 %g gives a reach of %d px (at most 1024)", (double)sig2, R);
@@ -233,8 +131,10 @@ int unet_weighted_map(const void *labels, int labels_dtype, int B, int H, int W,
     const size_t plane = plane_bytes(B, H, W, sizeof(int));
     int *parent = (int *)s, *label = (int *)(s + plane);
     unsigned *col_dist = (unsigned *)(s + 2 * plane);
-    int *col_label = parent;                                  // the parent words are dead after ccl_flatten
-    if (int rc = ccl_labels(labels, labels_dtype, B, H, W, parent, label, (unsigned long long *)counts_u64, (int *)n_objects_i32, st)) return rc;
+    int *col_label = parent;                                  // the parent words are dead after label_roots
+    if (int rc = label_roots(labels, labels_dtype, B, H, W, 1, 0, parent, label, nullptr, (int *)n_objects_i32,
+                             (unsigned long long *)counts_u64, st))
+        return rc;
     hipLaunchKernelGGL(wmap_cols_kernel, dim3(cdiv(W, 64), cdiv(H, 4), B), dim3(256), 0, st, (const int *)label, H, W, R,
                        col_label, col_dist);
     const size_t lds = (size_t)(WM_ROWS + 2 * R) * 2 * sizeof(unsigned);

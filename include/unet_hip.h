@@ -323,12 +323,12 @@ int unet_weighted_map(const void *labels, int labels_dtype, int B, int H, int W,
  * cells are carved apart beforehand by preprocess_gt, data.py:195-219): mask [B,H,W], int64 (dtype 0) or float32 (1),
  * foreground = value != 0; H != W allowed, down to 1 x 1.  labels_i32 [B,H,W]: 0 on background, else the number 1..n of the
  * pixel's 4-connected component, the components numbered in raster order of their first pixel (scipy.ndimage.label's and
- * OpenCV's numbering); n_objects_i32 [B] = n.  Exact, and the cost does not depend on n.
+ * OpenCV's numbering); n_objects_i32 [B] = n.  Exact, and the cost does not depend on n (label.hip).
  * scratch: unet_label_components_scratch_bytes(B, H, W), initialised by the call.                                        */
 size_t unet_label_components_scratch_bytes(int B, int H, int W);
 int unet_label_components(const void *mask, int dtype, int B, int H, int W, void *labels_i32, void *n_objects_i32, void *scratch,
                           void *stream);
-/* The same numbering for either phase of a mask and either connectivity (clean.hip; functions.label_cells(connectivity=8)):
+/* The same numbering for either phase of a mask and either connectivity (label.hip; functions.label_cells(connectivity=8)):
  * mask [B,H,W] of dtype 0 = int64, 1 = float32, 2 = int32, 3 = uint8.  phase 1 labels the pixels with mask != 0, phase 0 those
  * with mask == 0; connectivity 4 (the cross) or 8 (the full 3 x 3 neighbourhood).  labels_i32 [B,H,W]: the number 1..n of the
  * pixel's component, the components numbered in raster order of their first pixel (scipy.ndimage.label with the matching

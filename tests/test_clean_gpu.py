@@ -247,6 +247,24 @@ def test_connectivity_4_is_the_existing_op(dev):
             assert np.array_equal(labels, old[0].cpu().numpy()) and np.array_equal(n, old[1].cpu().numpy()), name
 
 
+def test_both_entry_points_give_the_same_labels_and_counts(dev):
+    """unet_label_components and unet_label_components_conn(4, 1) on one float32 mask of 3 images, each on guarded buffers: the
+    same labels and the same n_objects."""
+    import _hip
+    rng = np.random.default_rng(11)
+    for H, W in ((65, 66), (31, 33)):
+        m = (rng.random((3, H, W)) < 0.55).astype(np.float32)
+        a = guarded.Arena(dev)
+        t = a.inp(torch.from_numpy(m), "mask")
+        labels, n = a.out((3, H, W), torch.int32, "labels"), a.out((3,), torch.int32, "n")
+        scratch = a.scratch(_hip.lib().unet_label_components_scratch_bytes(3, H, W), "scratch")
+        _hip.run("unet_label_components", dev, a.ptr(t), CODE[torch.float32], 3, H, W, a.ptr(labels), a.ptr(n), a.ptr(scratch))
+        a.verify(labels, n)
+        labels_conn, n_conn = raw_labels(dev, m, 4, 1, torch.float32)
+        assert np.array_equal(n.cpu().numpy(), n_conn) and np.array_equal(labels.cpu().numpy(), labels_conn), (H, W)
+        assert n_conn.min() > 1                              # the mask is no trivial one
+
+
 def test_without_the_action_plane(dev):
     name, m = cases(129, 127)[3]
     for conn, kw in itertools.product((4, 8), FEW):
