@@ -2,6 +2,7 @@
 // orchestration and the per-op entry points (see include/unet_hip.h for the contract and the
 // reference lines each entry point replaces).
 #include "common.hpp"
+#include "plans.hpp"
 #include "../../include/unet_hip.h"
 
 #include <cstdarg>
@@ -9,8 +10,6 @@
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
-#include <utility>
-#include <vector>
 
 namespace unet {
 
@@ -112,22 +111,9 @@ struct unet_handle {
     // the dgrad chain (they only share dz); the streams re-join at the end of every stage
     hipStream_t aux = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    // plans of the training forwards still awaiting their backward, keyed by workspace pointer
-    std::mutex mu;
-    std::vector<std::pair<void *, Plan>> live;
-    void remember(void *ws, const Plan &pl)
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        for (auto &e : live) if (e.first == ws) { e.second = pl; return; }
-        if (live.size() >= 16) live.erase(live.begin());
-        live.emplace_back(ws, pl);
-    }
-    bool lookup(void *ws, Plan &pl)
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        for (auto &e : live) if (e.first == ws) { pl = e.second; return true; }
-        return false;
-    }
+    // plans of this handle's training forwards, keyed by workspace pointer: pending until their last backward stage has been
+    // enqueued, then finished and evicted oldest first (plans.hpp has the contract)
+    PlanRegistry<Plan> live;
 };
 
 unet_dp **unet_handle_dp_slot(unet_handle *h) { return &h->dp; }
@@ -706,6 +692,10 @@ static int forward_body(unet_handle *h, const void *const *params, const void *x
     ARG_CHECK(((uintptr_t)workspace & 255) == 0, "unet_forward: workspace must be 256-byte aligned");
     const Ctx cx(h, pl, workspace, stream, params, nullptr);
     hipStream_t st = cx.st;
+    // whatever plan this address had is void from here on: this forward overwrites the workspace.  A training forward
+    // registers its own plan once everything is enqueued; an inference forward leaves none, so a backward on this address
+    // is refused (UNET_E_NOTREADY) rather than run over an inference layout.
+    h->live.forget(workspace);
 
     // repack the parameters (reference layout, owned by the caller and updated by its optimizer): the up-convs', level 0 first
     // (the 3x3 layers' weights are packed lazily, only if a launch of the layer takes the implicit-GEMM path: with_wino)
@@ -745,7 +735,7 @@ static int forward_body(unet_handle *h, const void *const *params, const void *x
         }
         }
     }
-    if (training) h->remember(workspace, pl);
+    if (training) h->live.remember(workspace, pl);
     return 0;
 }
 
@@ -901,8 +891,9 @@ int unet_backward_stage(unet_handle *h, int stage, const void *const *params, co
     ARG_CHECK(h && params && grads && workspace, "unet_backward: null argument");
     CHECK_DEVICE(h, "unet_backward");
     Plan pl;
-    if (!h->lookup(workspace, pl)) {
-        set_error("unet_backward: no training forward has been run on this workspace");
+    if (!h->live.lookup(workspace, pl)) {
+        set_error("unet_backward: this handle has no training forward planned on this workspace address (none was run there, "
+                  "or an inference forward has overwritten it since)");
         return UNET_E_NOTREADY;
     }
     ARG_CHECK(workspace_bytes >= pl.total, "unet_backward: workspace too small");
@@ -924,6 +915,9 @@ int unet_backward_stage(unet_handle *h, int stage, const void *const *params, co
         set_error("unet_backward: ordering the weight-gradient stream against the caller's failed: %s", hipGetErrorString(cx.wst.err));
         rc = (int)cx.wst.err;
     }
+    // the forward's backward has been enqueued in full: its plan no longer holds a place among the pending ones (it stays
+    // readable for unet_backward_input and a repeated backward until newer finished plans push it out)
+    if (rc == 0 && stage == N_STAGES - 1) h->live.finish(workspace);
     return rc;
 }
 
@@ -932,8 +926,9 @@ int unet_backward_input(unet_handle *h, const void *const *params, void *dx, voi
     ARG_CHECK(h && params && dx && workspace, "unet_backward_input: null argument");
     CHECK_DEVICE(h, "unet_backward_input");
     Plan pl;
-    if (!h->lookup(workspace, pl)) {
-        set_error("unet_backward_input: no training forward has been run on this workspace");
+    if (!h->live.lookup(workspace, pl)) {
+        set_error("unet_backward_input: this handle has no training forward planned on this workspace address (none was run "
+                  "there, or an inference forward has overwritten it since)");
         return UNET_E_NOTREADY;
     }
     ARG_CHECK(workspace_bytes >= pl.total, "unet_backward_input: workspace too small");

@@ -134,6 +134,10 @@ class _UnetFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dlogits):
+        if ctx.ws is None:
+            raise RuntimeError("Unet: the workspace of this forward was released by its first backward (it held every activation of "
+                               "the forward); a second backward through the same graph, as after backward(retain_graph=True), is "
+                               "not supported - run the forward again")
         params = ctx.saved_tensors
         module = ctx.module
         h = module._get_handle(ctx.dev)

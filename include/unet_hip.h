@@ -37,7 +37,8 @@ extern "C" {
 enum {
     UNET_E_BADSIZE  = -1,         /* S must be 16L+60 with L even >= 8 (network.py:124-127, Q7) */
     UNET_E_BADARG   = -2,
-    UNET_E_NOTREADY = -3,         /* backward without a training forward on this workspace */
+    UNET_E_NOTREADY = -3,         /* backward without a training forward on this workspace: this handle has no plan at that
+                                     address (see "plans a handle keeps" at unet_backward); nothing is enqueued or written */
     UNET_E_UNSUPPORTED = -4,
     UNET_E_COMM     = -5          /* RCCL error (data parallel) */
 };
@@ -130,7 +131,30 @@ int unet_dropout_mask(unsigned long long seed, unsigned long long step, int site
  * Stages let the caller overlap the gradient all-reduce with the rest of the backward:
  * stage s in [0, unet_backward_stages()) must be run in increasing order; after stage s
  * returns, every gradient tensor listed by unet_backward_stage_params(s) is final (in
- * stream order).  unet_backward == all stages.                                              */
+ * stream order).  unet_backward == all stages.
+ *
+ * The plans a handle keeps.  A training forward (unet_forward with training=1, unet_forward_dropout) leaves its plan - shape,
+ * arithmetic mode, drop-out probability, workspace layout - in the handle, keyed by the workspace ADDRESS it was given; the
+ * backward entry points find it by that address and return UNET_E_NOTREADY when the handle has none there (no forward ran
+ * on that address on THIS handle: plans are per handle, and an address inside a workspace is another address).
+ *   - Pending: from the training forward until the last backward stage of that workspace has been enqueued once.  Any number
+ *     of forwards may be pending on one handle at a time, of any mix of shapes, arithmetic modes and drop-out
+ *     probabilities, and their backwards may run in any order; every pending forward needs a live workspace of its own, so
+ *     device memory is what bounds them.  A pending plan is never dropped to make room for another.  The one hard bound is
+ *     1024 pending plans per handle (about 1.5 KB each), against callers that abandon forwards without ever running their
+ *     backward or reusing the address: past it the oldest pending plan is dropped.
+ *   - Finished: after that.  The plan stays for unet_backward_input, and a backward may be REPEATED on the workspace with no
+ *     forward in between: no stage reads a gradient buffer it has not rewritten, so the repeat returns the same bits
+ *     (grad_scale and the knobs below unchanged).  The handle keeps the 16 most recently finished plans; older ones are
+ *     dropped, and a backward on their address returns UNET_E_NOTREADY.
+ *   - A forward on an address replaces the plan at that address.  An inference forward (training=0) leaves none: a backward
+ *     on a workspace that an inference forward has overwritten returns UNET_E_NOTREADY.  The handle sees addresses only: an
+ *     inference forward (or any other write) at a DIFFERENT address inside the same allocation is not detected, and the
+ *     backward of the training forward it damaged computes garbage.
+ *   - Read when the backward runs: unet_set_grad_scale, unet_set_lds_dma, unet_set_overlap (they may change between a forward
+ *     and its backward).  Read when the forward is planned: the arithmetic mode (unet_config::math / unet_set_math); the
+ *     backward of a forward keeps that forward's mode whatever the default is by then.
+ * A workspace_bytes below what the forward's plan needs is UNET_E_BADARG.                       */
 int unet_backward(unet_handle *h, const void *const *params, const void *dlogits,
                   void *const *grads, void *workspace, size_t workspace_bytes, void *stream);
 /* Weight gradients of each backward stage on an auxiliary stream of the handle, next to the dgrad chain (they only share dz);

@@ -146,6 +146,86 @@ def rejected(hip, rc, mem, *outs):
     mem.verify()
 
 
+# ---- the whole net through the C ABI, on buffers the test owns ----------------------------------------------------------------
+_params = {}
+
+
+def params_of(base, K):
+    if (base, K) not in _params:
+        import multiclass_ref as ref
+        _params[(base, K)] = ref.head_params(K, base=base)
+    return _params[(base, K)]
+
+
+class Net:
+    """One handle, guarded parameters, and forward / backward on caller-owned buffers.  mode is the handle's arithmetic
+    (-1: the process default at each forward); params (a state-dict of arrays) defaults to params_of(base, K)."""
+
+    def __init__(self, mode, base, K, params=None):
+        import _hip
+        self.hip, self.L = _hip, _hip.lib()
+        self.K = K
+        self.h = _hip.Handle(base, 0, math=mode, n_classes=K)
+        self.keep = gd.Arena()
+        self.params = params_of(base, K) if params is None else params
+        self.plist = [self.keep.inp(torch.from_numpy(v), k) for k, v in self.params.items()]
+        self.ptab = _hip.ptr_table(self.plist)
+
+    def inputs(self, B, S, seed=0):
+        """Image and dlogits of (B, S); another `seed`, other values."""
+        from oracle import prng
+        x = self.keep.inp(torch.from_numpy(prng.make_input(1 + 10 * seed, B, S)), "x")
+        dl = self.keep.inp(torch.from_numpy(prng.make_cotangent(2 + 10 * seed, (B, self.K, S - 184, S - 184))), "dlogits")
+        return x, dl
+
+    def done(self, A, wsa, outs):
+        torch.cuda.synchronize()
+        A.verify(*outs)
+        wsa.check()
+        self.keep.check()
+        return outs
+
+    def forward(self, A, wsa, ws, nbytes, x, training, dropout=None):
+        """unet_forward, or with dropout = (p, seed, step) unet_forward_dropout, on workspace `ws` of arena `wsa`.  Returns the
+        logits (a device tensor from `A`), fully written, with every guard of `A`, of the workspace and of the inputs intact."""
+        hip, L = self.hip, self.L
+        B, _, S, _ = x.shape
+        logits = A.out((B, self.K, S - 184, S - 184), torch.float32, "logits")
+        wsp = wsa.ptr(ws)
+        if dropout is None:
+            hip.check(L.unet_forward(self.h.h, self.ptab, hip.ptr(x), hip.ptr(logits), B, S, wsp, nbytes, int(training), hip.stream()), "unet_forward")
+        else:
+            assert training
+            p, seed, step = dropout
+            hip.check(L.unet_forward_dropout(self.h.h, self.ptab, hip.ptr(x), hip.ptr(logits), B, S, wsp, nbytes, p, seed, step, hip.stream()),
+                      "unet_forward_dropout")
+        return self.done(A, wsa, [logits])[0]
+
+    def backward(self, A, wsa, ws, nbytes, dl, want_dx=True):
+        """Every backward stage, then (want_dx) unet_backward_input, of the training forward that ran on `ws`.  Returns the 46
+        gradients and, with want_dx, dx, checked like forward()'s logits."""
+        hip, L = self.hip, self.L
+        B, S = dl.shape[0], dl.shape[2] + 184
+        wsp = wsa.ptr(ws)
+        outs = [A.out(p.shape, torch.float32, "grad %s" % k) for k, p in zip(self.params, self.plist)]
+        gtab = hip.ptr_table(outs)
+        for s in range(L.unet_backward_stages()):
+            hip.check(L.unet_backward_stage(self.h.h, s, self.ptab, hip.ptr(dl), gtab, wsp, nbytes, hip.stream()), "unet_backward_stage %d" % s)
+        if want_dx:
+            dx = A.out((B, 1, S, S), torch.float32, "dx")
+            hip.check(L.unet_backward_input(self.h.h, self.ptab, hip.ptr(dx), wsp, nbytes, hip.stream()), "unet_backward_input")
+            outs = outs + [dx]
+        return self.done(A, wsa, outs)
+
+    def step(self, A, wsa, ws, nbytes, x, dl, training):
+        """Training: forward, every backward stage, unet_backward_input.  Inference: the forward.  Returns the outputs
+        (device tensors from `A`), all fully written, with every guard of `A`, of the workspace (arena `wsa`) and of the inputs intact."""
+        outs = [self.forward(A, wsa, ws, nbytes, x, training)]
+        if training:
+            outs += self.backward(A, wsa, ws, nbytes, dl)
+        return outs
+
+
 def strided(mem, x, top=2, left=3, bottom=2, right=3):
     """x [B,K,H,W] as a crop view inside a NaN tensor: (pointer of the view, its batch, class-plane and row strides)."""
     B, K, H, W = x.shape

@@ -17,7 +17,7 @@ import pytest
 import torch
 
 import guarded as gd
-from gpu_support import nerr
+from gpu_support import Net, nerr
 
 pytestmark = pytest.mark.gpu
 
@@ -27,82 +27,31 @@ FWD_TOL = {3: 2e-5, 0: 2e-5, 1: 2e-4, 2: 5e-2}
 OTHER = (1, 188)                    # the plan that leaves stale activations behind: smaller than either plan under test
 PATTERNS = ("0x00", "0xFF", "random", "stale")
 
-_params = {}
 
-
-def params_of(base, K):
-    if (base, K) not in _params:
-        import multiclass_ref as ref
-        _params[(base, K)] = ref.head_params(K, base=base)
-    return _params[(base, K)]
-
-
-class Net:
-    """One handle, guarded parameters, and the step under test on caller-owned buffers."""
-
-    def __init__(self, mode, base, K):
-        import _hip
-        self.hip, self.L = _hip, _hip.lib()
-        self.K = K
-        self.h = _hip.Handle(base, 0, math=mode, n_classes=K)
-        self.keep = gd.Arena()
-        self.params = params_of(base, K)
-        self.plist = [self.keep.inp(torch.from_numpy(v), k) for k, v in self.params.items()]
-        self.ptab = _hip.ptr_table(self.plist)
-
-    def inputs(self, B, S):
-        from oracle import prng
-        x = self.keep.inp(torch.from_numpy(prng.make_input(1, B, S)), "x")
-        dl = self.keep.inp(torch.from_numpy(prng.make_cotangent(2, (B, self.K, S - 184, S - 184))), "dlogits")
-        return x, dl
-
-    def step(self, A, wsa, ws, nbytes, x, dl, training):
-        """Training: forward, every backward stage, unet_backward_input.  Inference: the forward.  Returns the outputs
-        (device tensors from `A`), all fully written, with every guard of `A`, of the workspace (arena `wsa`) and of the inputs intact."""
-        hip, L = self.hip, self.L
-        B, _, S, _ = x.shape
-        logits = A.out((B, self.K, S - 184, S - 184), torch.float32, "logits")
-        wsp = wsa.ptr(ws)
-        hip.check(L.unet_forward(self.h.h, self.ptab, hip.ptr(x), hip.ptr(logits), B, S, wsp, nbytes, int(training), hip.stream()), "unet_forward")
-        outs = [logits]
-        if training:
-            grads = [A.out(p.shape, torch.float32, "grad %s" % k) for k, p in zip(self.params, self.plist)]
-            gtab = hip.ptr_table(grads)
-            for s in range(L.unet_backward_stages()):
-                hip.check(L.unet_backward_stage(self.h.h, s, self.ptab, hip.ptr(dl), gtab, wsp, nbytes, hip.stream()), "unet_backward_stage %d" % s)
-            dx = A.out((B, 1, S, S), torch.float32, "dx")
-            hip.check(L.unet_backward_input(self.h.h, self.ptab, hip.ptr(dx), wsp, nbytes, hip.stream()), "unet_backward_input")
-            outs += grads + [dx]
-        torch.cuda.synchronize()
-        A.verify(*outs)
-        wsa.check()
-        self.keep.check()
-        return outs
-
-    def four_runs(self, B, S, training):
-        """The step with the workspace preset four ways; returns {pattern: [cpu tensors]}."""
-        nbytes = self.h.workspace_bytes(B, S, training)
-        ob, os_ = OTHER
-        assert self.h.workspace_bytes(ob, os_, training) <= nbytes
-        wsa = gd.Arena()
-        ws = wsa.scratch(nbytes, "workspace of exactly unet_workspace_bytes(%d, %d, %d)" % (B, S, training))
-        assert wsa.address(ws) % 256 == 0
-        x, dl = self.inputs(B, S)
-        xo, dlo = self.inputs(ob, os_)
-        res = {}
-        for pat in PATTERNS:
-            if pat == "0x00":
-                ws.zero_()
-            elif pat == "0xFF":
-                ws.fill_(0xFF)
-            elif pat == "random":
-                g = torch.Generator(device="cuda"); g.manual_seed(20240607)
-                ws.random_(0, 256, generator=g)
-            else:                                   # what a step of another plan leaves in the same allocation
-                self.step(gd.Arena(), wsa, ws, nbytes, xo, dlo, training)
-            outs = self.step(gd.Arena(), wsa, ws, nbytes, x, dl, training)
-            res[pat] = [t.cpu() for t in outs]
-        return res
+def four_runs(net, B, S, training):
+    """The step with the workspace preset four ways; returns {pattern: [cpu tensors]}."""
+    nbytes = net.h.workspace_bytes(B, S, training)
+    ob, os_ = OTHER
+    assert net.h.workspace_bytes(ob, os_, training) <= nbytes
+    wsa = gd.Arena()
+    ws = wsa.scratch(nbytes, "workspace of exactly unet_workspace_bytes(%d, %d, %d)" % (B, S, training))
+    assert wsa.address(ws) % 256 == 0
+    x, dl = net.inputs(B, S)
+    xo, dlo = net.inputs(ob, os_)
+    res = {}
+    for pat in PATTERNS:
+        if pat == "0x00":
+            ws.zero_()
+        elif pat == "0xFF":
+            ws.fill_(0xFF)
+        elif pat == "random":
+            g = torch.Generator(device="cuda"); g.manual_seed(20240607)
+            ws.random_(0, 256, generator=g)
+        else:                                   # what a step of another plan leaves in the same allocation
+            net.step(gd.Arena(), wsa, ws, nbytes, xo, dlo, training)
+        outs = net.step(gd.Arena(), wsa, ws, nbytes, x, dl, training)
+        res[pat] = [t.cpu() for t in outs]
+    return res
 
 
 def names_of(net, training):
@@ -119,7 +68,7 @@ def test_results_do_not_depend_on_workspace_contents(golden_dir, mode, base, K, 
         want = torch_ref.unet_forward(torch_ref.params_to_torch(net.params, dtype=torch.float64),
                                       torch.from_numpy(prng.make_input(1, B, S)).double()).numpy()
     for training in (1, 0):
-        res = net.four_runs(B, S, training)
+        res = four_runs(net, B, S, training)
         names = names_of(net, training)
         for pat in PATTERNS:
             for n, t in zip(names, res[pat]):
