@@ -112,17 +112,21 @@ _SIGS = {
     "unet_geodesic_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "unet_geodesic_init": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]),
     "unet_geodesic_sweeps": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_int, vp, C.c_int, vp, vp]),
+    "unet_geodesic_sweeps_conn": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, vp, C.c_int, vp, vp]),
     "unet_geodesic_finish": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_longlong, vp, vp, vp, vp, vp, vp]),
     "unet_flood_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "unet_flood_init": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]),
     "unet_flood_sweeps": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_int, vp, C.c_int, vp, vp]),
+    "unet_flood_sweeps_conn": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, vp, C.c_int, vp, vp]),
     "unet_flood_assign": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp]),
+    "unet_flood_assign_conn": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp]),
     "unet_flood_finish": (C.c_int, [C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp]),
     "unet_distance_map_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "unet_distance_map": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
     "unet_reconstruct_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "unet_reconstruct_init": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
     "unet_reconstruct_sweeps": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp]),
+    "unet_reconstruct_sweeps_conn": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp]),
     "unet_reconstruct_finish": (C.c_int, [C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]),
     "unet_shape_heights": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
     "unet_shape_lower": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),

@@ -26,9 +26,16 @@
 //   3. flood_assign  the same relaxation over ids.  The four parent bits of every owned pixel are formed once, while staging, from
 //                    the keys and levels in global memory, which this kernel only reads; the loop then works on the staged ids
 //                    and those bits: an id moves along any straight run of parent links in one phase.  Two id planes, ping-pong.
+//                    (Eight bits and the diagonal ids with connectivity 8, below.)
 //   4. flood_finish  ids, pass levels, plateau distances, the unreached region pixels and the largest level reached per image
 //
 // Monotone and bounded, as sweep.hpp asks: keys and ids are bounded below and only fall.
+//
+// Connectivity 8 (unet_flood_sweeps_conn, unet_flood_assign_conn): the same ext; a step goes to any of the eight neighbours in
+// the region, whatever the two pixels beside a diagonal step are, the minimum of stage 1 runs over eight neighbours and a parent
+// in stage 2 is any of the eight whose key extends to exactly key(q).  Neither argument above uses which pixels are neighbours:
+// ext is as isotone, a parent's key as strictly smaller.  The eight parent bits fill the staged byte; the diagonal tests carry
+// their own bounds, so past the image there is no parent.  Both stages of one flood take the same connectivity.
 #include "sweep.hpp"
 #include "../../include/unet_hip.h"
 
@@ -43,6 +50,7 @@ static constexpr unsigned FL_NONE = 1u << 30;                  // id plane: no i
 static constexpr fl_key FL_UNREACHED = 1ull << 60;             // above every key (L < 2^16: a key < 2^48)
 static constexpr fl_key FL_OUTSIDE = 1ull << 61;               // not in the region; its extension does not wrap
 static constexpr int FL_LEFT = 1, FL_RIGHT = 2, FL_UP = 4, FL_DOWN = 8;     // parent bits
+static constexpr int FL_UP_LEFT = 16, FL_UP_RIGHT = 32, FL_DOWN_LEFT = 64, FL_DOWN_RIGHT = 128;      // connectivity 8: the byte is full
 
 // one step from a pixel with key k onto a pixel of level v
 __device__ __forceinline__ fl_key fl_ext(fl_key k, unsigned v)
@@ -96,7 +104,7 @@ __global__ __launch_bounds__(256) void flood_init_kernel(const int *__restrict__
 
 // geo.hip's ge_relax_line with fl_ext: the SW_SEG pixels p[k * ALONG] of one line and their levels lv[k * ALONG], relaxed forward
 // (from the pixel before and the two ACROSS) and backward (from the pixel after) in registers
-template <int ALONG, int ACROSS>
+template <int ALONG, int ACROSS, int CONN>
 __device__ __forceinline__ unsigned fl_relax_line(const fl_key *p, const unsigned short *lv, fl_key lim, fl_key (&v)[SW_SEG])
 {
     unsigned fell = 0;
@@ -105,6 +113,13 @@ __device__ __forceinline__ unsigned fl_relax_line(const fl_key *p, const unsigne
     for (int k = 0; k < SW_SEG; ++k) {
         const fl_key own = p[k * ALONG], a = p[k * ALONG - ACROSS], b = p[k * ALONG + ACROSS];
         fl_key c = a < b ? a : b;
+        if constexpr (CONN == 8) {
+            const fl_key d0 = p[(k - 1) * ALONG - ACROSS], d1 = p[(k - 1) * ALONG + ACROSS];
+            const fl_key d2 = p[(k + 1) * ALONG - ACROSS], d3 = p[(k + 1) * ALONG + ACROSS];
+            const fl_key e = d0 < d1 ? d0 : d1, f = d2 < d3 ? d2 : d3;
+            c = e < c ? e : c;
+            c = f < c ? f : c;
+        }
         c = fl_ext(run < c ? run : c, lv[k * ALONG]);
         const bool take = own <= FL_UNREACHED && c < own && c >> FL_L_SHIFT <= lim;
         run = v[k] = take ? c : own;
@@ -121,6 +136,7 @@ __device__ __forceinline__ unsigned fl_relax_line(const fl_key *p, const unsigne
     return fell;
 }
 
+template <int CONN>
 __global__ __launch_bounds__(256) void flood_sweep_kernel(const fl_key *__restrict__ src, fl_key *__restrict__ dst,
                                                           const unsigned short *__restrict__ level, int H, int W, fl_key lim,
                                                           unsigned *changed)
@@ -132,16 +148,17 @@ __global__ __launch_bounds__(256) void flood_sweep_kernel(const fl_key *__restri
         s[i] = in ? src[e] : FL_OUTSIDE;
         sl[i] = in ? level[e] : (unsigned short)0;
     });
-    sweep_converge(s, [&](int o, fl_key (&v)[SW_SEG]) { return fl_relax_line<1, SW_PITCH>(s + o, sl + o, lim, v); },
-                   [&](int o, fl_key (&v)[SW_SEG]) { return fl_relax_line<SW_PITCH, 1>(s + o, sl + o, lim, v); });
+    sweep_converge(s, [&](int o, fl_key (&v)[SW_SEG]) { return fl_relax_line<1, SW_PITCH, CONN>(s + o, sl + o, lim, v); },
+                   [&](int o, fl_key (&v)[SW_SEG]) { return fl_relax_line<SW_PITCH, 1, CONN>(s + o, sl + o, lim, v); });
     sweep_write_back(tl, s, src, dst, W, changed, [](fl_key k, fl_key was) { return k < was; });
 }
 
 // ---- stage 2 ------------------------------------------------------------------------------------------------------------------
 
 // the SW_SEG ids p[k * ALONG] of one line and their parent bits: forward, an id takes the least of its own, of the pixel before
-// (bit PREV) and of the two ACROSS (bits LO, HI); backward, of the pixel after (bit NEXT)
-template <int ALONG, int ACROSS, int PREV, int NEXT, int LO, int HI>
+// (bit PREV) and of the two ACROSS (bits LO, HI); backward, of the pixel after (bit NEXT).  With CONN == 8 the forward pass also
+// takes the four diagonal ids p[(k -+ 1) * ALONG -+ ACROSS] under their bits: PREV_LO, PREV_HI before the pixel, NEXT_LO, NEXT_HI after
+template <int ALONG, int ACROSS, int PREV, int NEXT, int LO, int HI, int CONN, int PREV_LO = 0, int PREV_HI = 0, int NEXT_LO = 0, int NEXT_HI = 0>
 __device__ __forceinline__ unsigned fl_assign_line(const unsigned *p, const unsigned char *par, unsigned (&v)[SW_SEG])
 {
     unsigned fell = 0;
@@ -153,6 +170,14 @@ __device__ __forceinline__ unsigned fl_assign_line(const unsigned *p, const unsi
         c = (bits & PREV) && run < c ? run : c;
         c = (bits & LO) && a < c ? a : c;
         c = (bits & HI) && b < c ? b : c;
+        if constexpr (CONN == 8) {
+            const unsigned d0 = p[(k - 1) * ALONG - ACROSS], d1 = p[(k - 1) * ALONG + ACROSS];
+            const unsigned d2 = p[(k + 1) * ALONG - ACROSS], d3 = p[(k + 1) * ALONG + ACROSS];
+            c = (bits & PREV_LO) && d0 < c ? d0 : c;
+            c = (bits & PREV_HI) && d1 < c ? d1 : c;
+            c = (bits & NEXT_LO) && d2 < c ? d2 : c;
+            c = (bits & NEXT_HI) && d3 < c ? d3 : c;
+        }
         fell |= (unsigned)(c < own) << k;
         run = v[k] = c;
     }
@@ -166,6 +191,7 @@ __device__ __forceinline__ unsigned fl_assign_line(const unsigned *p, const unsi
     return fell;
 }
 
+template <int CONN>
 __global__ __launch_bounds__(256) void flood_assign_kernel(const fl_key *__restrict__ key, const unsigned short *__restrict__ level,
                                                            const unsigned *__restrict__ src, unsigned *__restrict__ dst, int H, int W,
                                                            unsigned *changed)
@@ -185,12 +211,25 @@ __global__ __launch_bounds__(256) void flood_assign_kernel(const fl_key *__restr
                 bits |= gx < W - 1 && fl_ext(key[e + 1], v) == k ? FL_RIGHT : 0;
                 bits |= gy > 0 && fl_ext(key[e - W], v) == k ? FL_UP : 0;
                 bits |= gy < H - 1 && fl_ext(key[e + W], v) == k ? FL_DOWN : 0;
+                if constexpr (CONN == 8) {                                           // past the image there is no parent
+                    bits |= gy > 0 && gx > 0 && fl_ext(key[e - W - 1], v) == k ? FL_UP_LEFT : 0;
+                    bits |= gy > 0 && gx < W - 1 && fl_ext(key[e - W + 1], v) == k ? FL_UP_RIGHT : 0;
+                    bits |= gy < H - 1 && gx > 0 && fl_ext(key[e + W - 1], v) == k ? FL_DOWN_LEFT : 0;
+                    bits |= gy < H - 1 && gx < W - 1 && fl_ext(key[e + W + 1], v) == k ? FL_DOWN_RIGHT : 0;
+                }
             }
         }
         sp[i] = (unsigned char)bits;
     });
-    sweep_converge(s, [&](int o, unsigned (&v)[SW_SEG]) { return fl_assign_line<1, SW_PITCH, FL_LEFT, FL_RIGHT, FL_UP, FL_DOWN>(s + o, sp + o, v); },
-                   [&](int o, unsigned (&v)[SW_SEG]) { return fl_assign_line<SW_PITCH, 1, FL_UP, FL_DOWN, FL_LEFT, FL_RIGHT>(s + o, sp + o, v); });
+    sweep_converge(s,
+                   [&](int o, unsigned (&v)[SW_SEG]) {
+                       return fl_assign_line<1, SW_PITCH, FL_LEFT, FL_RIGHT, FL_UP, FL_DOWN, CONN, FL_UP_LEFT, FL_DOWN_LEFT, FL_UP_RIGHT,
+                                             FL_DOWN_RIGHT>(s + o, sp + o, v);
+                   },
+                   [&](int o, unsigned (&v)[SW_SEG]) {
+                       return fl_assign_line<SW_PITCH, 1, FL_UP, FL_DOWN, FL_LEFT, FL_RIGHT, CONN, FL_UP_LEFT, FL_UP_RIGHT,
+                                             FL_DOWN_LEFT, FL_DOWN_RIGHT>(s + o, sp + o, v);
+                   });
     sweep_write_back(tl, s, src, dst, W, changed, [](unsigned id, unsigned was) { return id < was; });
 }
 
@@ -262,33 +301,50 @@ int unet_flood_init(const void *seeds_i32, const void *image, int image_dtype, i
     return 0;
 }
 
-int unet_flood_sweeps(int B, int H, int W, long long max_level, int n_launches, void *changed_out_u32, int first_slot, void *scratch,
-                      void *stream)
+int unet_flood_sweeps_conn(int B, int H, int W, long long max_level, int connectivity, int n_launches, void *changed_out_u32, int first_slot,
+                           void *scratch, void *stream)
 {
     ARG_CHECK(changed_out_u32 && scratch && B > 0 && H > 0 && W > 0 && n_launches > 0 && first_slot >= 0, "unet_flood_sweeps: bad argument");
+    SW_CONN_CHECK("unet_flood_sweeps_conn");
     ARG_CHECK(sizes_ok(B, H, W, 65535), "unet_flood_sweeps: image too large (the limits of unet_grow_labels)");
     hipStream_t st = (hipStream_t)stream;
     const FlScratch s = fl_scratch(scratch, B, H, W);
     const fl_key lim = fl_limit(max_level);
+    const auto kernel = connectivity == 8 ? flood_sweep_kernel<8> : flood_sweep_kernel<4>;
     return sweep_launches(s.key[0], s.key[1], sizeof(fl_key), B, H, W, n_launches, changed_out_u32, first_slot, st,
                           [&](dim3 grid, void *src, void *dst, unsigned *changed) {
-                              hipLaunchKernelGGL(flood_sweep_kernel, grid, dim3(256), 0, st, (const fl_key *)src, (fl_key *)dst,
+                              hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, (const fl_key *)src, (fl_key *)dst,
                                                  (const unsigned short *)s.level, H, W, lim, changed);
                           });
 }
 
-// Takes on trust that the keys are final: a launch of unet_flood_sweeps that changed nothing has been seen by the caller.
-int unet_flood_assign(int B, int H, int W, int n_launches, void *changed_out_u32, int first_slot, void *scratch, void *stream)
+int unet_flood_sweeps(int B, int H, int W, long long max_level, int n_launches, void *changed_out_u32, int first_slot, void *scratch,
+                      void *stream)
+{
+    return unet_flood_sweeps_conn(B, H, W, max_level, 4, n_launches, changed_out_u32, first_slot, scratch, stream);
+}
+
+// Takes on trust that the keys are final: a launch of unet_flood_sweeps_conn with the same connectivity that changed nothing has
+// been seen by the caller.
+int unet_flood_assign_conn(int B, int H, int W, int connectivity, int n_launches, void *changed_out_u32, int first_slot, void *scratch,
+                           void *stream)
 {
     ARG_CHECK(changed_out_u32 && scratch && B > 0 && H > 0 && W > 0 && n_launches > 0 && first_slot >= 0, "unet_flood_assign: bad argument");
+    SW_CONN_CHECK("unet_flood_assign_conn");
     ARG_CHECK(sizes_ok(B, H, W, 65535), "unet_flood_assign: image too large (the limits of unet_grow_labels)");
     hipStream_t st = (hipStream_t)stream;
     const FlScratch s = fl_scratch(scratch, B, H, W);
+    const auto kernel = connectivity == 8 ? flood_assign_kernel<8> : flood_assign_kernel<4>;
     return sweep_launches(s.ids[0], s.ids[1], sizeof(unsigned), B, H, W, n_launches, changed_out_u32, first_slot, st,
                           [&](dim3 grid, void *src, void *dst, unsigned *changed) {
-                              hipLaunchKernelGGL(flood_assign_kernel, grid, dim3(256), 0, st, (const fl_key *)s.key[0],
-                                                 (const unsigned short *)s.level, (const unsigned *)src, (unsigned *)dst, H, W, changed);
+                              hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, (const fl_key *)s.key[0], (const unsigned short *)s.level,
+                                                 (const unsigned *)src, (unsigned *)dst, H, W, changed);
                           });
+}
+
+int unet_flood_assign(int B, int H, int W, int n_launches, void *changed_out_u32, int first_slot, void *scratch, void *stream)
+{
+    return unet_flood_assign_conn(B, H, W, 4, n_launches, changed_out_u32, first_slot, scratch, stream);
 }
 
 int unet_flood_finish(int B, int H, int W, void *out_i32, void *pass_level_i32, void *dist_i32, void *unreached_u32, void *max_level_u32,

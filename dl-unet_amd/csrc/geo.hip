@@ -9,6 +9,9 @@
 //      key(p) <- min(key(p), min over the 4-neighbours q of key(q) + (1 << 24))        for p in the region
 // (a neighbour that is outside or unreached offers a key above GE_UNREACHED, which no region pixel takes).  Monotone and bounded,
 // as sweep.hpp asks: every key ever held is the (length, id) of a real path, keys only fall, and the least fixed point is unique.
+// With connectivity 8 (unet_geodesic_sweeps_conn) the minimum runs over the eight neighbours and a step is one to any of them that
+// lies in the region, whatever the two pixels beside a diagonal step are.  The argument does not look at which pixels count as
+// neighbours: a key is still the (length, id) of a real path, now of 8-neighbour steps, keys only fall, and the bound is the same.
 //
 //   1. geo_init    the key plane from seeds and mask; counts the seed pixels outside the region and the ids outside [0, 2^24)
 //   2. geo_sweep   sweep.hpp's tile relaxation over the keys, GE_OUTSIDE past the image.  With a limit, a key with d > max_steps
@@ -49,9 +52,10 @@ __global__ __launch_bounds__(256) void geo_init_kernel(const int *__restrict__ s
         __hip_atomic_fetch_add(&status[blockIdx.y], (unsigned long long)bad, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// the SW_SEG pixels p[k * ALONG] of one line, relaxed forward (from the pixel before and the two ACROSS) and backward (from the
-// pixel after) in registers: v[k] is the key after both, bit k of the result says that it fell
-template <int ALONG, int ACROSS>
+// the SW_SEG pixels p[k * ALONG] of one line, relaxed forward (from the pixel before and the two ACROSS; with CONN == 8 from the
+// four diagonal ones p[(k +- 1) * ALONG +- ACROSS] too) and backward (from the pixel after) in registers: v[k] is the key after
+// both, bit k of the result says that it fell
+template <int ALONG, int ACROSS, int CONN>
 __device__ __forceinline__ unsigned ge_relax_line(const ge_key *p, ge_key lim, ge_key (&v)[SW_SEG])
 {
     unsigned fell = 0;
@@ -60,6 +64,13 @@ __device__ __forceinline__ unsigned ge_relax_line(const ge_key *p, ge_key lim, g
     for (int k = 0; k < SW_SEG; ++k) {
         const ge_key own = p[k * ALONG], a = p[k * ALONG - ACROSS], b = p[k * ALONG + ACROSS];
         ge_key c = a < b ? a : b;
+        if constexpr (CONN == 8) {
+            const ge_key d0 = p[(k - 1) * ALONG - ACROSS], d1 = p[(k - 1) * ALONG + ACROSS];
+            const ge_key d2 = p[(k + 1) * ALONG - ACROSS], d3 = p[(k + 1) * ALONG + ACROSS];
+            const ge_key e = d0 < d1 ? d0 : d1, f = d2 < d3 ? d2 : d3;
+            c = e < c ? e : c;
+            c = f < c ? f : c;
+        }
         c = (run < c ? run : c) + GE_STEP;
         const bool take = own <= GE_UNREACHED && c < own && c >> GE_ID_BITS <= lim;
         run = v[k] = take ? c : own;
@@ -76,14 +87,15 @@ __device__ __forceinline__ unsigned ge_relax_line(const ge_key *p, ge_key lim, g
     return fell;
 }
 
+template <int CONN>
 __global__ __launch_bounds__(256) void geo_sweep_kernel(const ge_key *__restrict__ src, ge_key *__restrict__ dst, int H, int W,
                                                         ge_key lim, unsigned *changed)
 {
     __shared__ ge_key s[SW_STAGED * SW_PITCH];                                       // 34.5 KiB
     const SweepTile tl = sweep_tile(H, W);
     sweep_stage(tl, H, W, [&](int i, bool in, size_t e, int, int, int, int) { s[i] = in ? src[e] : GE_OUTSIDE; });
-    sweep_converge(s, [&](int o, ge_key (&v)[SW_SEG]) { return ge_relax_line<1, SW_PITCH>(s + o, lim, v); },
-                   [&](int o, ge_key (&v)[SW_SEG]) { return ge_relax_line<SW_PITCH, 1>(s + o, lim, v); });
+    sweep_converge(s, [&](int o, ge_key (&v)[SW_SEG]) { return ge_relax_line<1, SW_PITCH, CONN>(s + o, lim, v); },
+                   [&](int o, ge_key (&v)[SW_SEG]) { return ge_relax_line<SW_PITCH, 1, CONN>(s + o, lim, v); });
     sweep_write_back(tl, s, src, dst, W, changed, [](ge_key k, ge_key was) { return k < was; });
 }
 
@@ -137,17 +149,25 @@ int unet_geodesic_init(const void *seeds_i32, const void *mask, int mask_dtype, 
     return 0;
 }
 
-int unet_geodesic_sweeps(int B, int H, int W, long long max_steps, int n_launches, void *changed_out_u32, int first_slot, void *scratch,
-                         void *stream)
+int unet_geodesic_sweeps_conn(int B, int H, int W, long long max_steps, int connectivity, int n_launches, void *changed_out_u32,
+                              int first_slot, void *scratch, void *stream)
 {
     ARG_CHECK(changed_out_u32 && scratch && B > 0 && H > 0 && W > 0 && n_launches > 0 && first_slot >= 0, "unet_geodesic_sweeps: bad argument");
+    SW_CONN_CHECK("unet_geodesic_sweeps_conn");
     ARG_CHECK(sizes_ok(B, H, W, 65535), "unet_geodesic_sweeps: image too large (the limits of unet_grow_labels)");
     hipStream_t st = (hipStream_t)stream;
     const ge_key lim = ge_limit(max_steps);
+    const auto kernel = connectivity == 8 ? geo_sweep_kernel<8> : geo_sweep_kernel<4>;
     return sweep_launches(scratch, (char *)scratch + ge_plane(B, H, W), sizeof(ge_key), B, H, W, n_launches, changed_out_u32, first_slot, st,
                           [&](dim3 grid, void *src, void *dst, unsigned *changed) {
-                              hipLaunchKernelGGL(geo_sweep_kernel, grid, dim3(256), 0, st, (const ge_key *)src, (ge_key *)dst, H, W, lim, changed);
+                              hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, (const ge_key *)src, (ge_key *)dst, H, W, lim, changed);
                           });
+}
+
+int unet_geodesic_sweeps(int B, int H, int W, long long max_steps, int n_launches, void *changed_out_u32, int first_slot, void *scratch,
+                         void *stream)
+{
+    return unet_geodesic_sweeps_conn(B, H, W, max_steps, 4, n_launches, changed_out_u32, first_slot, scratch, stream);
 }
 
 int unet_geodesic_finish(int B, int H, int W, long long max_steps, void *out_i32, void *dist_i32, void *unreached_u32, void *max_dist_u32,

@@ -22,7 +22,9 @@
 // and a state that nothing raises satisfies the three conditions, so it is the least such function: any order of relaxation is
 // exact.  Pixels outside the region and past the image hold -1 in both planes: they offer nothing (every region value is >= 0)
 // and take nothing (min(-1, .) = -1), so the relaxation has no case distinction and the mask is read once.  Monotone and
-// bounded, as sweep.hpp asks: values only rise, and under is a ceiling.
+// bounded, as sweep.hpp asks: values only rise, and under is a ceiling.  With connectivity 8 (unet_reconstruct_sweeps_conn) "4-"
+// reads "8-" in all of the above, a diagonal neighbour counting whatever the two pixels beside the step are; the argument never
+// uses which pixels are neighbours, only that the path behind a value is real.
 //   1. rc_init    R = base = min(marker, under) and under, -1 outside the region; counts the values outside [0, 2^30]
 //   2. rc_sweep   sweep.hpp's tile relaxation over R (geo.hip's sweep with a max in place of its min), under staged beside it
 //   3. rc_finish  R with 0 outside the region, and the pixels with R > base per image
@@ -140,8 +142,9 @@ __global__ __launch_bounds__(256) void rc_init_kernel(const void *__restrict__ m
 }
 
 // the SW_SEG pixels p[k * ALONG] of one line under the ceilings u[k * ALONG], relaxed forward (from the pixel before and the two
-// ACROSS) and backward (from the pixel after) in registers: v[k] is the value after both, bit k of the result says that it rose
-template <int ALONG, int ACROSS>
+// ACROSS; with CONN == 8 from the four diagonal ones too) and backward (from the pixel after) in registers: v[k] is the value
+// after both, bit k of the result says that it rose
+template <int ALONG, int ACROSS, int CONN>
 __device__ __forceinline__ unsigned rc_relax_line(const int *p, const int *u, int (&v)[SW_SEG])
 {
     unsigned rose = 0;
@@ -151,7 +154,11 @@ __device__ __forceinline__ unsigned rc_relax_line(const int *p, const int *u, in
     for (int k = 0; k < SW_SEG; ++k) {
         const int own = p[k * ALONG], a = p[k * ALONG - ACROSS], b = p[k * ALONG + ACROSS];
         top[k] = u[k * ALONG];
-        const int c = min(top[k], max(max(a, b), run));
+        int n = max(a, b);
+        if constexpr (CONN == 8)
+            n = max(max(n, max(p[(k - 1) * ALONG - ACROSS], p[(k - 1) * ALONG + ACROSS])),
+                    max(p[(k + 1) * ALONG - ACROSS], p[(k + 1) * ALONG + ACROSS]));
+        const int c = min(top[k], max(n, run));
         rose |= (unsigned)(c > own) << k;
         run = v[k] = max(own, c);
     }
@@ -165,6 +172,7 @@ __device__ __forceinline__ unsigned rc_relax_line(const int *p, const int *u, in
     return rose;
 }
 
+template <int CONN>
 __global__ __launch_bounds__(256) void rc_sweep_kernel(const int *__restrict__ src, const int *__restrict__ under, int *__restrict__ dst,
                                                        int H, int W, unsigned *changed)
 {
@@ -174,8 +182,8 @@ __global__ __launch_bounds__(256) void rc_sweep_kernel(const int *__restrict__ s
         s[i] = in ? src[e] : -1;
         su[i] = in ? under[e] : -1;
     });
-    sweep_converge(s, [&](int o, int (&v)[SW_SEG]) { return rc_relax_line<1, SW_PITCH>(s + o, su + o, v); },
-                   [&](int o, int (&v)[SW_SEG]) { return rc_relax_line<SW_PITCH, 1>(s + o, su + o, v); });
+    sweep_converge(s, [&](int o, int (&v)[SW_SEG]) { return rc_relax_line<1, SW_PITCH, CONN>(s + o, su + o, v); },
+                   [&](int o, int (&v)[SW_SEG]) { return rc_relax_line<SW_PITCH, 1, CONN>(s + o, su + o, v); });
     sweep_write_back(tl, s, src, dst, W, changed, [](int k, int was) { return k > was; });
 }
 
@@ -285,17 +293,25 @@ int unet_reconstruct_init(const void *marker, int marker_dtype, const void *unde
     return 0;
 }
 
-int unet_reconstruct_sweeps(int B, int H, int W, int n_launches, void *changed_out_u32, int first_slot, void *scratch, void *stream)
+int unet_reconstruct_sweeps_conn(int B, int H, int W, int connectivity, int n_launches, void *changed_out_u32, int first_slot, void *scratch,
+                                 void *stream)
 {
     ARG_CHECK(changed_out_u32 && scratch && B > 0 && H > 0 && W > 0 && n_launches > 0 && first_slot >= 0, "unet_reconstruct_sweeps: bad argument");
+    SW_CONN_CHECK("unet_reconstruct_sweeps_conn");
     SH_SIZE_CHECK("unet_reconstruct_sweeps");
     hipStream_t st = (hipStream_t)stream;
     const size_t bytes = sh_plane(B, H, W);
     const int *under = (const int *)((char *)scratch + 2 * bytes);
+    const auto kernel = connectivity == 8 ? rc_sweep_kernel<8> : rc_sweep_kernel<4>;
     return sweep_launches(scratch, (char *)scratch + bytes, sizeof(int), B, H, W, n_launches, changed_out_u32, first_slot, st,
                           [&](dim3 grid, void *src, void *dst, unsigned *changed) {
-                              hipLaunchKernelGGL(rc_sweep_kernel, grid, dim3(256), 0, st, (const int *)src, under, (int *)dst, H, W, changed);
+                              hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, (const int *)src, under, (int *)dst, H, W, changed);
                           });
+}
+
+int unet_reconstruct_sweeps(int B, int H, int W, int n_launches, void *changed_out_u32, int first_slot, void *scratch, void *stream)
+{
+    return unet_reconstruct_sweeps_conn(B, H, W, 4, n_launches, changed_out_u32, first_slot, scratch, stream);
 }
 
 int unet_reconstruct_finish(int B, int H, int W, void *out_i32, void *raised_u32, void *scratch, void *stream)

@@ -9,6 +9,15 @@
 // reads a word another one may be storing.  The loop ends when both phases moved nothing.  Only the owned tile is written, to the
 // other plane, and the owned pixels whose word moved are counted into changed[b], one agent-scope add per wave.
 //
+// Connectivity (the template parameter CONN of the relax-line functions and of the sweep kernels, 4 or 8).  With CONN == 8 the
+// forward pass of a line also takes the four diagonal words p[(k +- 1) * ALONG +- ACROSS].  All of them lie in the staged square,
+// the four halo corners included, for k = 0, for k = SW_SEG - 1 and across a tile corner: nothing more is staged and nothing is
+// bounds-checked.  The loop ends only when neither phase moved a word, so "moved nothing" has to mean "stable against all eight
+// neighbours": each phase takes all eight offers (before, after, two across, four diagonal).  The row phase alone would be enough
+// for that; the column phase takes the diagonals as well because it is faster so, a diagonal run of words then moving in either
+// phase (DESIGN.md section 4t has both timings).  The phase discipline above is untouched: the diagonal reads come before the
+// phase's barrier like every other read.
+//
 // Coherence (label.hip's rule): a sweep reads plane A, which an earlier kernel wrote, and writes plane B, which no workgroup of
 // the launch reads: a neighbour's halo read never sees this launch's stores, and the hand-off between tiles is the kernel
 // boundary.  The counters are only touched by agent-scope adds.  No word is handed from one workgroup to another inside a
@@ -113,5 +122,7 @@ static inline int sweep_launches(void *plane0, void *plane1, size_t elem_size, i
     if (n_launches & 1) HIP_TRY(hipMemcpyAsync(plane0, plane1, (size_t)B * H * W * elem_size, hipMemcpyDeviceToDevice, st));
     return 0;
 }
+
+#define SW_CONN_CHECK(name) ARG_CHECK(connectivity == 4 || connectivity == 8, name ": connectivity must be 4 or 8, got %d", connectivity)
 
 }  // namespace unet

@@ -13,6 +13,7 @@ warp_labels and warping_error add that table's third column: the topology-preser
 prediction (unet_warp_init / unet_warp_sweeps / unet_warp_finish) and the disagreement it leaves.
 split_cells is the instance post-processing after label_cells: seeds grown back inside a mask along 4-neighbour steps until two
 growths meet (unet_geodesic_init / unet_geodesic_sweeps / unet_geodesic_finish), which splits touching cells.
+split_cells, watershed, reconstruct and shape_seeds take connectivity=8 as label_cells does: 8-neighbour steps (the _conn entries).
 watershed is the same growth led by an image: seeded flooding of an intensity landscape, plateaus cut at their geodesic midline
 (unet_flood_init / unet_flood_sweeps / unet_flood_assign / unet_flood_finish).
 distance_map, reconstruct and shape_seeds give it seeds from the shape of the mask alone: the exact interior distance map
@@ -30,6 +31,8 @@ formed from those links on the host, and the maps relabelled by track on the dev
 """
 import collections
 import fractions
+import functools
+import inspect
 import math
 
 import numpy as np
@@ -846,10 +849,30 @@ def _sweep_to_idle(entry, dev, B, launches, before, after=(), behind_first=None)
         n += launches
 
 
+def _check_connectivity(name, connectivity):
+    if isinstance(connectivity, bool) or connectivity not in (4, 8):
+        raise ValueError("%s: connectivity must be 4 or 8, got %r" % (name, connectivity))
+
+
+def _with_connectivity(fn):
+    """fn with the keyword connectivity=4, checked here before anything else and handed to fn as its last parameter
+    _connectivity, which the signature inspect reports leaves out: the parameter lists of split_cells and watershed are pinned by
+    tests/test_split_cpu.py and tests/test_flood_cpu.py, as segment's is (tester._with_steps)."""
+    sig = inspect.signature(fn)
+
+    @functools.wraps(fn)
+    def call(*args, connectivity=4, **kw):
+        _check_connectivity(fn.__name__, connectivity)
+        return fn(*args, _connectivity=connectivity, **kw)
+    call.__signature__ = sig.replace(parameters=[p for p in sig.parameters.values() if p.name != "_connectivity"])
+    return call
+
+
 SplitInfo = collections.namedtuple("SplitInfo", "seeds_outside unreached max_distance launches")
 
 
-def split_cells(seeds, mask, *, max_steps=None, orphans='drop', return_distance=False, _launches=8):
+@_with_connectivity
+def split_cells(seeds, mask, *, max_steps=None, orphans='drop', return_distance=False, _launches=8, _connectivity=4):
     """Seeded geodesic growth inside a mask: split touching cells by growing seeds (confident cores, e.g.
     label_cells(fg_prob >= high)[0]) back inside the mask until two growths meet.  seeds: int32 / int64 ids [H,W] or [B,H,W] on a
     HIP device, 0 = no seed, ids in [1, 2^24), not necessarily consecutive or connected; mask: the same shape, of any dtype
@@ -867,7 +890,13 @@ def split_cells(seeds, mask, *, max_steps=None, orphans='drop', return_distance=
     Exact, on the device (unet_geodesic_init / unet_geodesic_sweeps / unet_geodesic_finish): _launches launches are enqueued,
     their change counts read back in one copy, and the loop ends at the first launch that changed nothing; _launches changes no
     result.  The growth is blind to any image and 4-connected; watershed (below) is the one that follows an intensity landscape,
-    and equals this on a constant image.  Unequal shapes, max_steps < 0, a bad orphans,
+    and equals this on a constant image.
+    connectivity: keyword only, 4 (the default, all of the above) or 8.  With 8 a step goes to any of the eight neighbours that
+    lies in the region, whatever the two pixels beside a diagonal step are, so a one-pixel-thick diagonal wall does not separate.
+    g(p) is the least number of 8-neighbour steps, max_steps counts those, the id rule is the same, and orphans='keep' labels
+    the rest with label_cells(..., connectivity=8) (unet_geodesic_sweeps_conn).  It is added by the decorator _with_connectivity
+    above, not by a parameter of this function: inspect.signature shows the parameters above, which tests/test_split_cpu.py pins.
+    A connectivity other than 4 or 8 (checked first), unequal shapes, max_steps < 0, a bad orphans,
     negative ids and ids >= 2^24 raise ValueError; host tensors raise NotImplementedError (no CPU path)."""
     if not (torch.is_tensor(seeds) and torch.is_tensor(mask)):
         raise NotImplementedError("split_cells takes tensors on the HIP device (unet_geodesic_init); there is no CPU implementation")
@@ -897,13 +926,13 @@ def split_cells(seeds, mask, *, max_steps=None, orphans='drop', return_distance=
     status = torch.empty(B, dtype=torch.int64, device=dev)
     scratch = _hip.scratch("unet_geodesic", dev, B, H, W)
     _hip.run("unet_geodesic_init", dev, _hip.ptr(sd), _hip.ptr(mk), code, B, H, W, _hip.ptr(counts[0]), _hip.ptr(status), _hip.ptr(scratch))
-    launches = _sweep_to_idle("unet_geodesic_sweeps", dev, B, _launches, (B, H, W, steps), (_hip.ptr(scratch),))
+    launches = _sweep_to_idle("unet_geodesic_sweeps_conn", dev, B, _launches, (B, H, W, steps, _connectivity), (_hip.ptr(scratch),))
     labels = torch.empty(B, H, W, dtype=torch.int32, device=dev)
     dist = torch.empty(B, H, W, dtype=torch.int32, device=dev) if return_distance else None
     _hip.run("unet_geodesic_finish", dev, B, H, W, steps, _hip.ptr(labels), _hip.ptr(dist), _hip.ptr(counts[1]), _hip.ptr(counts[2]),
              _hip.ptr(scratch))
     if orphans == 'keep':
-        rest, _ = label_cells((mk != 0) & (labels == 0))
+        rest, _ = label_cells((mk != 0) & (labels == 0), connectivity=_connectivity)
         n0 = sd.amax(dim=(1, 2)).view(B, 1, 1)
         labels = torch.where(rest > 0, rest + n0, labels)
     outside, unreached, far = counts.cpu().numpy().astype(np.int64)
@@ -917,7 +946,8 @@ FloodInfo = collections.namedtuple("FloodInfo", "seeds_outside unreached max_lev
 FLOOD_LEVELS = 1 << 16                                                 # levels of watershed are in [0, FLOOD_LEVELS)
 
 
-def watershed(seeds, image, *, mask=None, levels=None, max_level=None, return_levels=False, _launches=8):
+@_with_connectivity
+def watershed(seeds, image, *, mask=None, levels=None, max_level=None, return_levels=False, _launches=8, _connectivity=4):
     """Seeded watershed: flood an intensity landscape from markers, Vincent-Soille immersion with exact geodesic influence zones
     on plateaus.  seeds: int32 / int64 ids [H,W] or [B,H,W] on a HIP device, 0 = no seed, ids in [1, 2^24); image: the same
     shape; mask: optional, the same shape, of any dtype _int_code takes: the region is mask != 0, everything without a mask.
@@ -940,7 +970,14 @@ def watershed(seeds, image, *, mask=None, levels=None, max_level=None, return_le
     for each stage: _launches launches are enqueued, their change counts read back in one copy, and the loop ends at the first
     launch that changed nothing; _launches changes no result.  To flood a shape instead of an intensity, pass the inverted
     distance map as the image: watershed(shape_seeds(mask)[0], d.max() - d, mask=mask) with d = distance_map(mask) scaled into
-    [0, 65536).  Unequal shapes, other seed dtypes, levels or max_level out of range, image values outside [0, 65536) or not
+    [0, 65536).
+    connectivity: keyword only, 4 (the default, all of the above) or 8.  With 8 a step goes to any of the eight neighbours that
+    lies in the region, whatever the two pixels beside a diagonal step are, so a one-pixel-thick diagonal wall does not separate.
+    The extension of a key is the same, the minimum runs over eight neighbours, a parent is any of the eight whose key extends
+    to exactly key(q), and on a constant image the result is split_cells(connectivity=8)'s, bit for bit (unet_flood_sweeps_conn,
+    unet_flood_assign_conn).  Added by the decorator _with_connectivity: inspect.signature shows the parameters above, which
+    tests/test_flood_cpu.py pins.
+    A connectivity other than 4 or 8 (checked first), unequal shapes, other seed dtypes, levels or max_level out of range, image values outside [0, 65536) or not
     finite (counted by the kernel), negative ids and ids >= 2^24 raise ValueError; host tensors raise NotImplementedError (no CPU
     path)."""
     tensors = [seeds, image] + ([] if mask is None else [mask])
@@ -986,8 +1023,8 @@ def watershed(seeds, image, *, mask=None, levels=None, max_level=None, return_le
             raise ValueError("watershed: %d pixels hold an image value that is not finite" % bad if im_code == 1 else
                              "watershed: %d pixels hold an image value outside [0, %d)" % (bad, FLOOD_LEVELS))
 
-    launches = [_sweep_to_idle("unet_flood_sweeps", dev, B, _launches, (B, H, W, top), (_hip.ptr(scratch),), values_ok),
-                _sweep_to_idle("unet_flood_assign", dev, B, _launches, (B, H, W), (_hip.ptr(scratch),))]   # after an idle stage-1 launch
+    launches = [_sweep_to_idle("unet_flood_sweeps_conn", dev, B, _launches, (B, H, W, top, _connectivity), (_hip.ptr(scratch),), values_ok),
+                _sweep_to_idle("unet_flood_assign_conn", dev, B, _launches, (B, H, W, _connectivity), (_hip.ptr(scratch),))]   # after an idle stage-1 launch
     labels = torch.empty(B, H, W, dtype=torch.int32, device=dev)
     lev, dist = (torch.empty(2, B, H, W, dtype=torch.int32, device=dev) if return_levels else (None, None))
     _hip.run("unet_flood_finish", dev, B, H, W, _hip.ptr(labels), _hip.ptr(lev), _hip.ptr(dist), _hip.ptr(counts[1]), _hip.ptr(counts[2]),
@@ -1037,18 +1074,21 @@ ReconInfo = collections.namedtuple("ReconInfo", "launches raised")
 RECON_TOP = 1 << 30
 
 
-def reconstruct(marker, under, *, mask=None, _launches=8):
-    """Grey reconstruction by dilation, 4-connected, on integers: marker and under int32 / int64 [H,W] or [B,H,W] on a HIP device
+def reconstruct(marker, under, *, mask=None, connectivity=4, _launches=8):
+    """Grey reconstruction by dilation, 4-connected (8-connected with connectivity=8), on integers: marker and under int32 / int64 [H,W] or [B,H,W] on a HIP device
     with values in [0, 2^30]; the region is mask != 0 (the same shape, of any dtype split_cells takes), everything when mask is
     None.  R is the least function on the region with R >= min(marker, under), R <= under and R(p) >= min(under(p), R(n)) for
     every region 4-neighbour n; equivalently R(p) is the maximum over region pixels q of min(marker(q), the minimum of under along
-    the best 4-path from q to p inside the region).  Outside the region R is 0.  Returns (R, ReconInfo): R int32 of the input's
+    the best 4-path from q to p inside the region).  With connectivity=8 the neighbours are the eight and the paths 8-paths, a
+    diagonal step allowed whatever the two pixels beside it are (skimage.morphology.reconstruction's default footprint;
+    unet_reconstruct_sweeps_conn).  Outside the region R is 0.  Returns (R, ReconInfo): R int32 of the input's
     shape; ReconInfo(launches, raised): the launches the reconstruction needed, the final one that raised nothing included
     (counted as SplitInfo.launches is), and raised int64 numpy [B], the pixels whose final value exceeds min(marker, under).
     Exact, on the device (unet_reconstruct_init / unet_reconstruct_sweeps / unet_reconstruct_finish): _launches launches are
     enqueued, their change counts read back in one copy, and the loop ends at the first launch that raised nothing; _launches
-    changes no result.  Unequal shapes, other dtypes, values outside [0, 2^30] (counted by the kernel), H or W above 32767 raise
-    ValueError; host tensors raise NotImplementedError (no CPU path)."""
+    changes no result.  A connectivity other than 4 or 8 (checked first), unequal shapes, other dtypes, values outside [0, 2^30]
+    (counted by the kernel), H or W above 32767 raise ValueError; host tensors raise NotImplementedError (no CPU path)."""
+    _check_connectivity("reconstruct", connectivity)
     tensors = [marker, under] + ([] if mask is None else [mask])
     if any(not torch.is_tensor(t) for t in tensors):
         raise NotImplementedError("reconstruct takes tensors on the HIP device (unet_reconstruct_init); there is no CPU implementation")
@@ -1078,14 +1118,14 @@ def reconstruct(marker, under, *, mask=None, _launches=8):
         if bad:
             raise ValueError("reconstruct: %d pixels hold a marker or under value outside [0, 2^30]" % bad)
 
-    launches = _sweep_to_idle("unet_reconstruct_sweeps", dev, B, _launches, (B, H, W), (_hip.ptr(scratch),), values_ok)
+    launches = _sweep_to_idle("unet_reconstruct_sweeps_conn", dev, B, _launches, (B, H, W, connectivity), (_hip.ptr(scratch),), values_ok)
     out = torch.empty(B, H, W, dtype=torch.int32, device=dev)
     _hip.run("unet_reconstruct_finish", dev, B, H, W, _hip.ptr(out), _hip.ptr(raised), _hip.ptr(scratch))
     info = ReconInfo(launches=launches, raised=raised.cpu().numpy().astype(np.int64))
     return (out[0] if marker.dim() == 2 else out), info
 
 
-def shape_seeds(mask, h=2.0, *, min_radius=0.0, edge='ignore'):
+def shape_seeds(mask, h=2.0, *, min_radius=0.0, edge='ignore', connectivity=4):
     """Seeds for split_cells from the shape of a mask alone: the h-maxima of its distance map.  mask [H,W] or [B,H,W] on a HIP
     device (the region is mask != 0, of any dtype split_cells takes); returns (seeds, n): seeds int32 of the mask's shape, 0 = no
     seed, the seeds numbered 1..n[b] in label_cells' raster order; n int32 [B].  Integers throughout: q = isqrt(256 d2) is the
@@ -1100,9 +1140,14 @@ def shape_seeds(mask, h=2.0, *, min_radius=0.0, edge='ignore'):
     (in 1/16 pixel: lower peak - saddle <= hq); h = 0 gives all regional maxima of q; every region component with max q >= rq
     gets at least one seed.  The default h = 2: along a diagonal ridge the 4-connected staircase makes spurious maxima less than
     1 px deep (two discs of r = 12 on a diagonal give 9 seeds at h = 0, 3 at 0.5 and 2 from 1 on).
+    connectivity=8: both reconstructions are 8-connected ("4-path" above reads "8-path") and the seed pixels are labelled with
+    label_cells(..., connectivity=8); the distance map is Euclidean and does not change.  A diagonal ridge is then no staircase
+    and has no spurious maxima: the same two discs give 2 seeds at every h >= 0, as skimage.morphology.h_maxima's default
+    footprint does.
     On the device throughout (unet_distance_map, unet_shape_heights / _lower / _maxima, two reconstruct calls,
-    unet_label_components), on the current stream.  h < 0 or above 2^24, min_radius < 0, a bad edge and the shapes distance_map
-    refuses raise ValueError; host tensors raise NotImplementedError (no CPU path)."""
+    unet_label_components), on the current stream.  A connectivity other than 4 or 8 (checked first), h < 0 or above 2^24,
+    min_radius < 0, a bad edge and the shapes distance_map refuses raise ValueError; host tensors raise NotImplementedError (no CPU path)."""
+    _check_connectivity("shape_seeds", connectivity)
     if not torch.is_tensor(mask):
         raise NotImplementedError("shape_seeds takes a tensor on the HIP device (unet_distance_map); there is no CPU implementation")
     if isinstance(h, bool) or not isinstance(h, (int, float)) or not 0 <= h <= 1 << 24:
@@ -1117,12 +1162,12 @@ def shape_seeds(mask, h=2.0, *, min_radius=0.0, edge='ignore'):
     mk = _planes("shape_seeds", mask)
     q, lifted = torch.empty_like(d2), torch.empty_like(d2)
     _hip.run("unet_shape_heights", dev, _hip.ptr(d2), B, H, W, hq, _hip.ptr(q), _hip.ptr(lifted))
-    r1 = reconstruct(q, lifted, mask=mk)[0]
+    r1 = reconstruct(q, lifted, mask=mk, connectivity=connectivity)[0]
     _hip.run("unet_shape_lower", dev, _hip.ptr(r1), B, H, W, 1, _hip.ptr(q))
-    r2 = reconstruct(q, r1, mask=mk)[0]
+    r2 = reconstruct(q, r1, mask=mk, connectivity=connectivity)[0]
     peaks = torch.empty(B, H, W, dtype=torch.float32, device=dev)
     _hip.run("unet_shape_maxima", dev, _hip.ptr(r1), _hip.ptr(r2), B, H, W, rq, _hip.ptr(peaks))
-    seeds, n = label_cells(peaks)
+    seeds, n = label_cells(peaks, connectivity=connectivity)
     return (seeds[0] if mask.dim() == 2 else seeds), n
 
 

@@ -17,8 +17,8 @@ import numpy as np
 import torch
 
 import _hip
-from functions import (FLOOD_LEVELS, _area, cell_props, clean_mask, evaluation_metrics, label_cells, metrics_from_counts, shape_seeds,
-                       split_cells, track_cells, watershed)
+from functions import (FLOOD_LEVELS, _area, _check_connectivity, _with_connectivity, cell_props, clean_mask, evaluation_metrics, label_cells,
+                       metrics_from_counts, shape_seeds, split_cells, track_cells, watershed)
 import optim as hip_optim
 
 TILE_MARGIN = 92        # context each side of a tile's output that the valid convolutions eat: (S - So) / 2
@@ -201,33 +201,39 @@ def _view_chunks(n_views, Tv, nb):
         yield t0, n, segs
 
 
-def split_instances(mask, fg_prob, high):
+@_with_connectivity
+def split_instances(mask, fg_prob, high, _connectivity=4):
     """The instance map of a foreground mask with touching cells split: the cores label_cells(fg_prob >= high)[0] are the seeds,
     functions.split_cells grows them back inside mask != 0 until two growths meet, and a component of the mask without a core
-    stays a cell (orphans='keep').  mask and fg_prob [H,W] or [B,H,W] on a HIP device; returns int32 ids of the same shape."""
-    seeds = label_cells(fg_prob >= high)[0]
-    return split_cells(seeds, mask, orphans='keep')[0]
+    stays a cell (orphans='keep').  mask and fg_prob [H,W] or [B,H,W] on a HIP device; returns int32 ids of the same shape.
+    connectivity: keyword only, 4 or 8 (else ValueError), for the cores' labelling, the growth and the orphans alike; added by
+    functions._with_connectivity, so inspect.signature shows the three parameters tests/test_split_cpu.py pins."""
+    seeds = label_cells(fg_prob >= high, connectivity=_connectivity)[0]
+    return split_cells(seeds, mask, orphans='keep', connectivity=_connectivity)[0]
 
 
-def split_by_shape(mask, h=2.0, min_radius=0.0, edge='ignore'):
+def split_by_shape(mask, h=2.0, min_radius=0.0, edge='ignore', *, connectivity=4):
     """The instance map of a foreground mask with touching cells split by their shape alone, no probabilities needed: the seeds
     are functions.shape_seeds(mask, h, min_radius=min_radius, edge=edge)[0], the h-maxima of the mask's distance map whose peak
     reaches min_radius; functions.split_cells grows them back inside mask != 0 until two growths meet, and a component of the mask
-    without a seed stays a cell (orphans='keep').  mask [H,W] or [B,H,W] on a HIP device; returns int32 ids of the same shape."""
-    seeds = shape_seeds(mask, h, min_radius=min_radius, edge=edge)[0]
-    return split_cells(seeds, mask, orphans='keep')[0]
+    without a seed stays a cell (orphans='keep').  mask [H,W] or [B,H,W] on a HIP device; returns int32 ids of the same shape.
+    connectivity: 4 or 8 (else ValueError), for the seeds (shape_seeds), the growth and the orphans alike."""
+    seeds = shape_seeds(mask, h, min_radius=min_radius, edge=edge, connectivity=connectivity)[0]
+    return split_cells(seeds, mask, orphans='keep', connectivity=connectivity)[0]
 
 
-def split_by_watershed(mask, fg_prob, high, levels=64):
+@_with_connectivity
+def split_by_watershed(mask, fg_prob, high, levels=64, _connectivity=4):
     """The instance map of a foreground mask with touching cells split where the foreground probability dips: the cores
     label_cells(fg_prob >= high)[0] are the seeds, functions.watershed floods the landscape 1 - fg_prob (float32, quantised to
     `levels` levels) from them inside mask != 0, so two growths meet on the ridge of low probability between two cores and not
     halfway between them as in split_instances; a component of the mask without a core stays a cell, numbered after the seeds
     as split_cells(orphans='keep') numbers it.  mask and fg_prob [H,W] or [B,H,W] on a HIP device; returns int32 ids of the same
-    shape."""
-    seeds = label_cells(fg_prob >= high)[0]
-    labels = watershed(seeds, 1 - fg_prob.float(), mask=mask, levels=levels)[0]
-    rest = label_cells((mask != 0) & (labels == 0))[0]
+    shape.  connectivity: keyword only, 4 or 8 (else ValueError), for the cores' labelling, the flood and the orphans alike; added
+    by functions._with_connectivity, so inspect.signature shows the four parameters tests/test_flood_cpu.py pins."""
+    seeds = label_cells(fg_prob >= high, connectivity=_connectivity)[0]
+    labels = watershed(seeds, 1 - fg_prob.float(), mask=mask, levels=levels, connectivity=_connectivity)[0]
+    rest = label_cells((mask != 0) & (labels == 0), connectivity=_connectivity)[0]
     return torch.where(rest > 0, rest + seeds.amax(dim=(-2, -1), keepdim=True), labels)
 
 
@@ -274,29 +280,54 @@ def _parse_clean(v, n_classes):
 
 
 def _with_steps(fn):
-    """segment with the keywords watershed and measure, two steps on the call's results.  watershed: the call without its split
-    (mask and probabilities only), then split_by_watershed of them as the instance map.  measure: functions.cell_props of the
-    final instance map and of the images the call was given, appended to the returned tuple.  The checks of both come before any
-    work."""
+    """segment with the keywords watershed, connectivity and measure, three steps on the call's results.  watershed: the call
+    without its split (mask and probabilities only), then split_by_watershed of them as the instance map.  connectivity=8: the
+    call without instances (mask and probabilities only), then the instance map formed here, 8-connected throughout: label_cells,
+    split_instances, split_by_shape or split_by_watershed of them.  measure: functions.cell_props of the final instance map and
+    of the images the call was given, appended to the returned tuple.  The checks of all three come before any work."""
     sig = inspect.signature(fn)
 
     @functools.wraps(fn)
-    def segment(*args, measure=False, watershed=None, **kw):
+    def segment(*args, measure=False, watershed=None, connectivity=None, **kw):
+        if connectivity is not None:
+            _check_connectivity("segment", connectivity)
         if measure not in (False, True):
             raise ValueError("segment: measure must be False or True, got %r" % (measure,))
         if watershed is False:
             watershed = None
         if watershed is not None and watershed is not True and not (isinstance(watershed, int) and 1 <= watershed <= FLOOD_LEVELS):
             raise ValueError("segment: watershed must be None, True (64 levels) or an int in [1, %d], got %r" % (FLOOD_LEVELS, watershed))
-        if not measure and watershed is None:
+        if not measure and watershed is None and connectivity is None:
             return fn(*args, **kw)
         call = sig.bind(*args, **kw)
         call.apply_defaults()
         given = call.arguments
         if measure and not given["return_instances"]:
             raise ValueError("segment: measure needs return_instances=True")
-        if watershed is None:
+        if connectivity is not None and not given["return_instances"]:
+            raise ValueError("segment: connectivity is the instance map's; it needs return_instances=True")
+        conn = 4 if connectivity is None else connectivity
+        if watershed is None and conn == 4:
             out = fn(*args, **kw)
+        elif watershed is None:
+            split, shape_split = given["split"], given["shape_split"]
+            if split is not None:
+                _check_split(split, True)
+            if shape_split is not None:
+                if split is not None:
+                    raise ValueError("segment: shape_split and split are two ways to seed one growth; give one of them")
+                shape_split = _parse_shape_split(shape_split)
+            need_prob = given["return_probs"] or split is not None
+            got = fn(**dict(given, return_probs=need_prob, return_instances=False, split=None, shape_split=None))
+            mask, prob = got if need_prob else (got, None)
+            if split is not None:
+                fg = prob if getattr(given["unet"], 'n_classes', 2) == 2 else 1 - prob.select(-3, 0)
+                inst = split_instances(mask, fg, float(split), connectivity=8)
+            elif shape_split is not None:
+                inst = split_by_shape(mask, *shape_split, connectivity=8)
+            else:
+                inst = label_cells(mask, connectivity=8)[0]
+            out = (mask,) + ((prob,) if given["return_probs"] else ()) + (inst,)
         else:
             if given["split"] is None:
                 raise ValueError("segment: watershed needs split=high, the cores it floods from")
@@ -305,7 +336,7 @@ def _with_steps(fn):
             _check_split(given["split"], given["return_instances"])
             mask, prob = fn(**dict(given, return_probs=True, return_instances=False, split=None))
             fg = prob if getattr(given["unet"], 'n_classes', 2) == 2 else 1 - prob.select(-3, 0)
-            inst = split_by_watershed(mask, fg, float(given["split"]), 64 if watershed is True else watershed)
+            inst = split_by_watershed(mask, fg, float(given["split"]), 64 if watershed is True else watershed, connectivity=conn)
             out = (mask,) + ((prob,) if given["return_probs"] else ()) + (inst,)
         if not measure:
             return out
@@ -368,6 +399,12 @@ def segment(unet, images, tile_size=None, max_batch=16, normalise=True, return_p
         foreground probability where split alone puts it halfway between the cores.  clean and measure compose with it as they do
         with split.  Added by the same decorator.  Flooding the inverted distance map from the seeds of functions.shape_seeds is
         a composition of functions.watershed and functions.distance_map and has no option here.
+    connectivity: keyword only, 4 or 8 (needs return_instances, else ValueError; anything else raises ValueError before any
+        work): the connectivity of the instance map.  With 8 it is made 8-connected throughout: label_cells(mask, connectivity=8),
+        or with split, shape_split or split + watershed, split_instances, split_by_shape or split_by_watershed with
+        connectivity=8 (cores or seeds, growth or flood, and orphans alike).  The mask and the probabilities are those of the call
+        without it; clean keeps its own connectivity key.  Added by the same decorator: mask and probabilities come from the
+        inner call without instances and the instance map is formed from them.
     Geometry and mirroring: tile_grid."""
     if not images.is_cuda:
         raise RuntimeError("segment: the HIP path needs the images on a HIP device (got %s); there is no CPU fallback - "

@@ -541,6 +541,22 @@ int unet_geodesic_init(const void *seeds_i32, const void *mask, int mask_dtype, 
                        void *status_u64, void *scratch, void *stream);
 int unet_geodesic_sweeps(int B, int H, int W, long long max_steps, int n_launches, void *changed_out_u32, int first_slot, void *scratch,
                          void *stream);
+/* The four sweep entries with a connectivity, 4 or 8 (after unet_label_components_conn): unet_geodesic_sweeps_conn,
+ * unet_flood_sweeps_conn, unet_flood_assign_conn and unet_reconstruct_sweeps_conn are the entries without _conn with
+ * `int connectivity` directly before n_launches, and the entries without _conn are these with 4.  With 8 a step goes to any of
+ * the eight neighbours that lies in the region, whatever the two pixels beside a diagonal step are (a one-pixel-thick diagonal
+ * wall does not separate): g(p) counts 8-neighbour steps, the flood's minimum runs over eight neighbours and a parent is any of
+ * the eight whose key extends to exactly key(q), and R(p) >= min(under(p), R(n)) holds for every region 8-neighbour n.  init,
+ * finish and the scratch sizes do not depend on it; both stages of one flood take the same value.  Anything but 4 or 8 returns -2
+ * with a unet_last_error() that names it, and enqueues nothing.                                                              */
+int unet_geodesic_sweeps_conn(int B, int H, int W, long long max_steps, int connectivity, int n_launches, void *changed_out_u32,
+                              int first_slot, void *scratch, void *stream);
+int unet_flood_sweeps_conn(int B, int H, int W, long long max_level, int connectivity, int n_launches, void *changed_out_u32, int first_slot,
+                           void *scratch, void *stream);
+int unet_flood_assign_conn(int B, int H, int W, int connectivity, int n_launches, void *changed_out_u32, int first_slot, void *scratch,
+                           void *stream);
+int unet_reconstruct_sweeps_conn(int B, int H, int W, int connectivity, int n_launches, void *changed_out_u32, int first_slot, void *scratch,
+                                 void *stream);
 int unet_geodesic_finish(int B, int H, int W, long long max_steps, void *out_i32, void *dist_i32, void *unreached_u32, void *max_dist_u32,
                          void *scratch, void *stream);
 /* Seeded watershed: flooding of an intensity landscape from markers inside a region (functions.watershed,

@@ -5,9 +5,10 @@ are seeded cell images (tests/instances_ref.cells_case, the prediction's foregro
 'ignore'.  The geodesic growth timed is split_cells' own on the seeds shape_seeds returns.
 Events around the library call alone (buffers preallocated, no host sync inside), 3 warm-ups, median, minimum and maximum of --reps;
 the plane a sweep changes is restored in front of every repetition, outside the timed region.  functions.shape_seeds and
-tester.split_by_shape as wall time of the whole Python call (read-backs included).
+tester.split_by_shape as wall time of the whole Python call (read-backs included).  --connectivity 8 times the 8-connected
+reconstructions, labelling and growth (the _conn entries; 4 goes through the same entries).
 
-    timeout -k 10 600 python tools/shape_time.py [--reps 50] [--json out.json]
+    timeout -k 10 600 python tools/shape_time.py [--reps 50] [--connectivity {4,8}] [--json out.json]
 """
 import argparse
 import json
@@ -29,11 +30,11 @@ from instances_time import event_median, wall_median  # noqa: E402
 from warp_time import event_median_after  # noqa: E402
 
 
-def time_reconstruction(dev, marker, under, mask, reps):
+def time_reconstruction(dev, marker, under, mask, reps, conn=4):
     """(init ms, sweeps ms, launches, pixels raised, finish ms, R) of one reconstruction of int32 planes inside a uint8 mask."""
     L = _hip.lib()
     B, H, W = marker.shape
-    out, info = functions.reconstruct(marker, under, mask=mask)
+    out, info = functions.reconstruct(marker, under, mask=mask, connectivity=conn)
     status = torch.empty(B, dtype=torch.int64, device=dev)
     raised = torch.empty(B, dtype=torch.int32, device=dev)
     scratch = torch.empty(L.unet_reconstruct_scratch_bytes(B, H, W), dtype=torch.uint8, device=dev)
@@ -44,7 +45,7 @@ def time_reconstruction(dev, marker, under, mask, reps):
     plane0 = plane.clone()
     n = info.launches
     slots = torch.empty(n, B, dtype=torch.int32, device=dev)
-    sweeps = lambda: _hip.run("unet_reconstruct_sweeps", dev, B, H, W, n, _hip.ptr(slots), 0, _hip.ptr(scratch))
+    sweeps = lambda: _hip.run("unet_reconstruct_sweeps_conn", dev, B, H, W, conn, n, _hip.ptr(slots), 0, _hip.ptr(scratch))
     sweeps_ms = event_median_after(lambda: plane.copy_(plane0), sweeps, reps)
     assert bool(slots[:-1].any(dim=1).all()) and not bool(slots[-1].any())
     res = torch.empty(B, H, W, dtype=torch.int32, device=dev)
@@ -53,22 +54,22 @@ def time_reconstruction(dev, marker, under, mask, reps):
     return init_ms, sweeps_ms, n, int(info.raised.sum()), finish_ms, out
 
 
-def time_case(dev, B, H, W, cells, reps, h=2.0):
+def time_case(dev, B, H, W, cells, reps, h=2.0, conn=4):
     L = _hip.lib()
     mask = torch.from_numpy(np.stack([instances_ref.cells_case(100 + b % 6, cells, H, W)[1] > 0 for b in range(B)]).astype(np.uint8)).to(dev)
-    r = {"B": B, "H": H, "W": W, "cells": cells, "h": h, "components": int(functions.label_cells(mask)[1].sum())}
+    r = {"B": B, "H": H, "W": W, "cells": cells, "h": h, "connectivity": conn, "components": int(functions.label_cells(mask)[1].sum())}
     labels = torch.empty(B, H, W, dtype=torch.int32, device=dev)
     nobj = torch.empty(B, dtype=torch.int32, device=dev)
     lscr = torch.empty(L.unet_label_components_scratch_bytes(B, H, W), dtype=torch.uint8, device=dev)
     mask64 = mask.long()
     r["label_ms"] = event_median(lambda: _hip.run("unet_label_components", dev, _hip.ptr(mask64), 0, B, H, W, _hip.ptr(labels), _hip.ptr(nobj),
                                                   _hip.ptr(lscr)), reps)
-    seeds, n_seeds = functions.shape_seeds(mask, h)
+    seeds, n_seeds = functions.shape_seeds(mask, h, connectivity=conn)
     r["seeds"] = int(n_seeds.sum())
     gscr = torch.empty(L.unet_grow_labels_scratch_bytes(B, H, W), dtype=torch.uint8, device=dev)
     r["grow_ms"] = event_median(lambda: _hip.run("unet_grow_labels", dev, _hip.ptr(seeds), B, H, W, -1, _hip.ptr(labels), _hip.ptr(gscr)), reps)
 
-    out, info = functions.split_cells(seeds, mask)                                # the growth these seeds are for
+    out, info = functions.split_cells(seeds, mask, connectivity=conn)                                # the growth these seeds are for
     r["geodesic_launches"], r["cells_after"] = info.launches, int(sum(len(np.unique(o)) - 1 for o in out.cpu().numpy()))
     counts = torch.empty(B, dtype=torch.int32, device=dev)
     status = torch.empty(B, dtype=torch.int64, device=dev)
@@ -77,7 +78,7 @@ def time_case(dev, B, H, W, cells, reps, h=2.0):
     keys = escr[:B * H * W * 8]
     keys0 = keys.clone()
     gslots = torch.empty(info.launches, B, dtype=torch.int32, device=dev)
-    r["geodesic_ms"] = event_median_after(lambda: keys.copy_(keys0), lambda: _hip.run("unet_geodesic_sweeps", dev, B, H, W, -1, info.launches,
+    r["geodesic_ms"] = event_median_after(lambda: keys.copy_(keys0), lambda: _hip.run("unet_geodesic_sweeps_conn", dev, B, H, W, -1, conn, info.launches,
                                                                                       _hip.ptr(gslots), 0, _hip.ptr(escr)), reps)
 
     d2 = torch.empty(B, H, W, dtype=torch.int32, device=dev)
@@ -89,14 +90,14 @@ def time_case(dev, B, H, W, cells, reps, h=2.0):
     hq = int(round(16 * h))
     q, lifted, lowered = torch.empty_like(d2), torch.empty_like(d2), torch.empty_like(d2)
     r["heights_ms"] = event_median(lambda: _hip.run("unet_shape_heights", dev, _hip.ptr(d2), B, H, W, hq, _hip.ptr(q), _hip.ptr(lifted)), reps)
-    r["r1_init_ms"], r["r1_sweeps_ms"], r["r1_launches"], r["r1_raised"], r["r1_finish_ms"], r1 = time_reconstruction(dev, q, lifted, mask, reps)
+    r["r1_init_ms"], r["r1_sweeps_ms"], r["r1_launches"], r["r1_raised"], r["r1_finish_ms"], r1 = time_reconstruction(dev, q, lifted, mask, reps, conn)
     r["lower_ms"] = event_median(lambda: _hip.run("unet_shape_lower", dev, _hip.ptr(r1), B, H, W, 1, _hip.ptr(lowered)), reps)
-    r["r2_init_ms"], r["r2_sweeps_ms"], r["r2_launches"], r["r2_raised"], r["r2_finish_ms"], r2 = time_reconstruction(dev, lowered, r1, mask, reps)
+    r["r2_init_ms"], r["r2_sweeps_ms"], r["r2_launches"], r["r2_raised"], r["r2_finish_ms"], r2 = time_reconstruction(dev, lowered, r1, mask, reps, conn)
     peaks = torch.empty(B, H, W, dtype=torch.float32, device=dev)
     r["maxima_ms"] = event_median(lambda: _hip.run("unet_shape_maxima", dev, _hip.ptr(r1), _hip.ptr(r2), B, H, W, 0, _hip.ptr(peaks)), reps)
-    assert torch.equal(functions.label_cells(peaks)[0], seeds)
-    r["shape_seeds_wall_ms"] = wall_median(lambda: functions.shape_seeds(mask, h), max(3, reps // 5))
-    r["split_by_shape_wall_ms"] = wall_median(lambda: tester.split_by_shape(mask, h), max(3, reps // 5))
+    assert torch.equal(functions.label_cells(peaks, connectivity=conn)[0], seeds)
+    r["shape_seeds_wall_ms"] = wall_median(lambda: functions.shape_seeds(mask, h, connectivity=conn), max(3, reps // 5))
+    r["split_by_shape_wall_ms"] = wall_median(lambda: tester.split_by_shape(mask, h, connectivity=conn), max(3, reps // 5))
     r["device_ms"] = sum(r[k][0] for k in ("distance_ms", "heights_ms", "r1_init_ms", "r1_sweeps_ms", "r1_finish_ms", "lower_ms", "r2_init_ms",
                                            "r2_sweeps_ms", "r2_finish_ms", "maxima_ms", "label_ms"))
     for other in ("label_ms", "geodesic_ms", "grow_ms"):
@@ -109,19 +110,20 @@ def time_case(dev, B, H, W, cells, reps, h=2.0):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=50)
+    ap.add_argument("--connectivity", type=int, choices=(4, 8), default=4)
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     torch.cuda.set_device(dev)
     res = []
     for B, H, W, cells in ((30, 512, 512, 170), (8, 388, 388, 99)):
-        r = time_case(dev, B, H, W, cells, a.reps)
+        r = time_case(dev, B, H, W, cells, a.reps, conn=a.connectivity)
         res.append(r)
-        print("B %d, %d x %d: %d components -> %d seeds -> %d cells, largest distance %.1f | label %.3f ms | geodesic sweeps %.3f ms (%d launches) | "
+        print("connectivity %d | B %d, %d x %d: %d components -> %d seeds -> %d cells, largest distance %.1f | label %.3f ms | geodesic sweeps %.3f ms (%d launches) | "
               "grow_labels %.3f ms | distance_map %.3f ms (background %.3f) | heights %.3f ms | R1: init %.3f, sweeps %.3f (%d launches, %d raised), "
               "finish %.3f ms | lower %.3f ms | R2: init %.3f, sweeps %.3f (%d launches, %d raised), finish %.3f ms | maxima %.3f ms | "
               "device total with the labelling %.3f ms | shape_seeds %.2f ms wall | split_by_shape %.2f ms wall"
-              % (B, H, W, r["components"], r["seeds"], r["cells_after"], r["max_distance"], r["label_ms"][0], r["geodesic_ms"][0],
+              % (a.connectivity, B, H, W, r["components"], r["seeds"], r["cells_after"], r["max_distance"], r["label_ms"][0], r["geodesic_ms"][0],
                  r["geodesic_launches"], r["grow_ms"][0], r["distance_ms"][0], r["distance_background_ms"][0], r["heights_ms"][0],
                  r["r1_init_ms"][0], r["r1_sweeps_ms"][0], r["r1_launches"], r["r1_raised"], r["r1_finish_ms"][0], r["lower_ms"][0],
                  r["r2_init_ms"][0], r["r2_sweeps_ms"][0], r["r2_launches"], r["r2_raised"], r["r2_finish_ms"][0], r["maxima_ms"][0],

@@ -6,9 +6,10 @@ labelled.  One call of unet_geodesic_sweeps enqueues every launch the growth nee
 first; the final launch that changes nothing included), the key plane restored in front of every repetition outside the timed
 region; and two launches on the converged state.
 Events around the library call alone (buffers preallocated, no host sync inside), 3 warm-ups, median, minimum and maximum of --reps.
-functions.split_cells as wall time of the whole Python call (read-backs included).
+functions.split_cells as wall time of the whole Python call (read-backs included).  --connectivity 8 times the 8-connected growth
+(unet_geodesic_sweeps_conn; 4 goes through the same entry).
 
-    timeout -k 10 600 python tools/split_time.py [--reps 50] [--json out.json]
+    timeout -k 10 600 python tools/split_time.py [--reps 50] [--connectivity {4,8}] [--json out.json]
 """
 import argparse
 import json
@@ -29,12 +30,12 @@ from instances_time import event_median, wall_median  # noqa: E402
 from warp_time import event_median_after  # noqa: E402
 
 
-def time_case(dev, B, H, W, cells, reps, erode=5):
+def time_case(dev, B, H, W, cells, reps, erode=5, conn=4):
     L = _hip.lib()
     mask = torch.from_numpy(np.stack([instances_ref.cells_case(100 + b % 6, cells, H, W)[1] > 0 for b in range(B)]).astype(np.uint8)).to(dev)
     near_bg = functions.grow_cells((mask == 0).int(), erode)
     seeds, n_seeds = functions.label_cells((mask != 0) & (near_bg == 0))
-    r = {"B": B, "H": H, "W": W, "cells": cells, "erode": erode, "seeds": int(n_seeds.sum()),
+    r = {"B": B, "H": H, "W": W, "cells": cells, "erode": erode, "connectivity": conn, "seeds": int(n_seeds.sum()),
          "components": int(functions.label_cells(mask)[1].sum())}
     labels = torch.empty(B, H, W, dtype=torch.int32, device=dev)
     nobj = torch.empty(B, dtype=torch.int32, device=dev)
@@ -46,7 +47,7 @@ def time_case(dev, B, H, W, cells, reps, erode=5):
     for name, d2 in (("grow_unlimited_ms", -1), ("grow_reach5_ms", 25)):
         r[name] = event_median(lambda: _hip.run("unet_grow_labels", dev, _hip.ptr(seeds), B, H, W, d2, _hip.ptr(labels), _hip.ptr(gscr)), reps)
 
-    out, info = functions.split_cells(seeds, mask)
+    out, info = functions.split_cells(seeds, mask, connectivity=conn)
     r["launches"], r["unreached"], r["max_distance"] = info.launches, int(info.unreached.sum()), int(info.max_distance.max())
     r["cells_after"] = int(sum(len(np.unique(o)) - 1 for o in out.cpu().numpy()))
     counts = torch.empty(3, B, dtype=torch.int32, device=dev)
@@ -59,7 +60,7 @@ def time_case(dev, B, H, W, cells, reps, erode=5):
     plane0 = plane.clone()
     n = info.launches
     slots = torch.empty(n, B, dtype=torch.int32, device=dev)
-    sweeps = lambda k=n: _hip.run("unet_geodesic_sweeps", dev, B, H, W, -1, k, _hip.ptr(slots), 0, _hip.ptr(scratch))
+    sweeps = lambda k=n: _hip.run("unet_geodesic_sweeps_conn", dev, B, H, W, -1, conn, k, _hip.ptr(slots), 0, _hip.ptr(scratch))
     r["sweeps_ms"] = event_median_after(lambda: plane.copy_(plane0), sweeps, reps)
     assert bool(slots[:-1].any(dim=1).all()) and not bool(slots[-1].any())
     r["lowered"] = int(slots.sum())
@@ -69,7 +70,7 @@ def time_case(dev, B, H, W, cells, reps, erode=5):
     r["finish_ms"] = event_median(lambda: _hip.run("unet_geodesic_finish", dev, B, H, W, -1, _hip.ptr(labels), _hip.ptr(dist), _hip.ptr(counts[1]),
                                                    _hip.ptr(counts[2]), _hip.ptr(scratch)), reps)
     assert torch.equal(labels, out)
-    r["split_cells_wall_ms"] = wall_median(lambda: functions.split_cells(seeds, mask), max(3, reps // 5))
+    r["split_cells_wall_ms"] = wall_median(lambda: functions.split_cells(seeds, mask, connectivity=conn), max(3, reps // 5))
     r["sweeps_over_label"] = r["sweeps_ms"][0] / r["label_ms"][0]
     return r
 
@@ -77,18 +78,19 @@ def time_case(dev, B, H, W, cells, reps, erode=5):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=50)
+    ap.add_argument("--connectivity", type=int, choices=(4, 8), default=4)
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     torch.cuda.set_device(dev)
     res = []
     for B, H, W, cells in ((30, 512, 512, 170), (8, 388, 388, 99)):
-        r = time_case(dev, B, H, W, cells, a.reps)
+        r = time_case(dev, B, H, W, cells, a.reps, conn=a.connectivity)
         res.append(r)
-        print("B %d, %d x %d: %d components, %d seeds -> %d cells, %d unreached, largest distance %d | label %.3f ms | grow_labels %.3f ms "
+        print("connectivity %d | B %d, %d x %d: %d components, %d seeds -> %d cells, %d unreached, largest distance %d | label %.3f ms | grow_labels %.3f ms "
               "(reach 5: %.3f) | init %.3f ms | sweeps to convergence %.3f ms (%d launches, %d keys lowered) = %.2f x label | "
               "two idle launches %.4f ms | finish %.3f ms | split_cells %.2f ms wall"
-              % (B, H, W, r["components"], r["seeds"], r["cells_after"], r["unreached"], r["max_distance"], r["label_ms"][0],
+              % (a.connectivity, B, H, W, r["components"], r["seeds"], r["cells_after"], r["unreached"], r["max_distance"], r["label_ms"][0],
                  r["grow_unlimited_ms"][0], r["grow_reach5_ms"][0], r["init_ms"][0], r["sweeps_ms"][0], r["launches"], r["lowered"],
                  r["sweeps_over_label"], r["idle_launches_ms"][0], r["finish_ms"][0], r["split_cells_wall_ms"]), flush=True)
     if a.json:
