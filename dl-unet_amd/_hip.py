@@ -97,6 +97,10 @@ _SIGS = {
     "unet_cell_sums_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "unet_cell_sums": (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "unet_remap_labels": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_longlong, vp, vp, vp]),
+    "unet_cell_hulls_scratch_bytes": (C.c_size_t, [C.c_longlong]),
+    "unet_cell_hulls": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_longlong, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "unet_cell_contacts_scratch_bytes": (C.c_size_t, [C.c_int, C.c_size_t]),
+    "unet_cell_contacts": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, vp, vp, vp, vp, vp, vp]),
     "unet_instance_overlap_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_size_t]),
     "unet_instance_overlap": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, vp, vp, vp, vp, vp, vp, vp]),
     "unet_partition_pairs_scratch_bytes": (C.c_size_t, [C.c_int, C.c_size_t]),

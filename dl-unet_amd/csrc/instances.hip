@@ -16,7 +16,12 @@
 //   2. pairs_compact     a wave reads 64 slots, one agent-scope add on n_pairs gives it a block of the dense (key, count) list
 // The list's order depends on the order of those adds; its content does not.
 //
-// Coherence (label.hip's rule): inside overlap_fill a table key is only ever touched by an agent-scope compare-and-swap, a
+// unet_cell_contacts: the same table and compaction for one id map against itself, shifted: for every pair of ids i < j the unit
+// pixel sides at which they are 4-adjacent (functions.cell_neighbours):
+//   1. contact_fill      every pixel looks right (one insert per side) and down (one insert per run of equal (id, id below) pairs)
+//   2. pairs_compact     as above
+//
+// Coherence (label.hip's rule): inside overlap_fill and contact_fill a table key is only ever touched by an agent-scope compare-and-swap, a
 // counter, a histogram bin or a status word only by an agent-scope add, and n_pairs in pairs_compact likewise; overlap_match
 // and pairs_compact read what an earlier kernel wrote.  No word is handed from one workgroup to another inside a kernel by plain
 // loads and stores.
@@ -118,6 +123,50 @@ __global__ __launch_bounds__(256) void pairs_compact_kernel(const unsigned long 
     }
 }
 
+// ---- contacts ---------------------------------------------------------------------------------------------------------
+// unet_cell_contacts: for every unordered pair of ids 1 <= i < j of image b = blockIdx.y, the unit pixel sides at which a pixel of
+// i is 4-adjacent to a pixel of j.  Every pixel looks right and down, so each side is counted once.  A side to the right is one
+// insert; the sides below are merged per run of equal (id, id below) pairs along a row with one ballot, as overlap_fill merges
+// its pairs.  A pixel with an id outside [0, n_max] is counted in status[b][0] and is nobody's neighbour.
+template <typename LT>
+__global__ __launch_bounds__(256) void contact_fill_kernel(const LT *__restrict__ labels, int H, int W, int n_max, unsigned long long *keys,
+                                                           unsigned *cnt, size_t slots, unsigned long long *status)
+{
+    const int b = blockIdx.y, lane = threadIdx.x & 63;
+    const size_t npx = (size_t)H * W;
+    const LT *M = labels + (size_t)b * npx;
+    auto id_at = [&](size_t e) { const LT v = M[e]; return (v < 0 || v > (LT)n_max) ? -1 : (int)v; };
+    auto key_of = [&](int i, int j) {
+        return (unsigned long long)b << (2 * OV_ID_BITS) | (unsigned long long)min(i, j) << OV_ID_BITS | (unsigned)max(i, j);
+    };
+    unsigned long long bad = 0, dropped = 0;                      // this lane's share of status[b][0..1]
+    bool full = false;                                            // the table only fills up: after one failed probe, stop probing
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t base = (size_t)blockIdx.x * blockDim.x + (threadIdx.x & ~63); base < npx; base += stride) {   // wave-uniform
+        const size_t e = base + lane;
+        const bool in = e < npx;
+        const int y = in ? (int)(e / W) : 0, x = in ? (int)(e - (size_t)y * W) : 0;
+        const int a = in ? id_at(e) : -2;
+        const int right = in && x + 1 < W ? id_at(e + 1) : 0;
+        int down = in && y + 1 < H ? id_at(e + W) : 0;
+        bad += a == -1;
+        if (a < 1 || down < 1 || down == a) down = 0;             // no contact below: such pixels form runs too, and add nothing
+        const int al = __shfl_up(a, 1, 64), dl = __shfl_up(down, 1, 64);
+        const bool head = lane == 0 || a != al || down != dl || x == 0;
+        const unsigned long long heads = __ballot(head);
+        const unsigned long long above = lane == 63 ? 0ull : heads >> (lane + 1);
+        const unsigned n = above ? (unsigned)__ffsll(above) : (unsigned)(64 - lane);   // run length: up to the next head
+        if (a >= 1 && right >= 1 && right != a && (full || !ov_insert(keys, cnt, slots, key_of(a, right), 1u))) { ++dropped; full = true; }
+        if (head && down && (full || !ov_insert(keys, cnt, slots, key_of(a, down), n))) { dropped += n; full = true; }
+        full = __any(full);
+    }
+    bad = wave_sum(bad); dropped = wave_sum(dropped);
+    if (lane == 0) {
+        if (bad) __hip_atomic_fetch_add(&status[2 * b], bad, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (dropped) __hip_atomic_fetch_add(&status[2 * b + 1], dropped, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
 } // namespace unet
 
 using namespace unet;
@@ -196,6 +245,42 @@ int unet_partition_pairs(const void *gt_i32, const void *pred_i32, int B, int H,
     hipLaunchKernelGGL(pairs_compact_kernel, dim3(grid_for(table_slots, 256, 2048)), dim3(256), 0, st,
                        (const unsigned long long *)t.keys, (const unsigned *)t.cnt, table_slots, (unsigned long long *)pair_keys_u64,
                        (unsigned *)pair_counts_u32, (unsigned long long *)n_pairs_u64);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+size_t unet_cell_contacts_scratch_bytes(int B, size_t table_slots)
+{
+    if (B <= 0 || table_slots == 0) return 0;
+    return ov_scratch_bytes(table_slots);
+}
+
+int unet_cell_contacts(const void *labels, int label_dtype, int B, int H, int W, int n_max, size_t table_slots, void *pair_keys_u64,
+                       void *pair_counts_u32, void *n_pairs_u64, void *status_u64, void *scratch, void *stream)
+{
+    ARG_CHECK(labels && pair_keys_u64 && pair_counts_u32 && n_pairs_u64 && status_u64 && scratch && B > 0 && H > 0 && W > 0,
+              "unet_cell_contacts: bad argument");
+    ARG_CHECK(label_dtype == 0 || label_dtype == 2, "unet_cell_contacts: label dtype must be 0 (int64) or 2 (int32)");
+    ARG_CHECK(H <= 32768 && W <= 32768 && B <= 65535 && n_max >= 0 && n_max <= OV_ID_MAX,
+              "unet_cell_contacts: H, W must be <= 32768, B <= 65535 and n_max in [0, 2^24)");
+    ARG_CHECK(table_slots > 0 && (table_slots & (table_slots - 1)) == 0, "unet_cell_contacts: table_slots must be a power of two");
+    hipStream_t st = (hipStream_t)stream;
+    unsigned long long *keys = (unsigned long long *)scratch;
+    unsigned *cnt = (unsigned *)((char *)scratch + ov_key_bytes(table_slots));
+    HIP_TRY(hipMemsetAsync(keys, 0xFF, table_slots * sizeof(unsigned long long), st));          // OV_EMPTY
+    HIP_TRY(hipMemsetAsync(cnt, 0, table_slots * sizeof(unsigned), st));
+    HIP_TRY(hipMemsetAsync(status_u64, 0, (size_t)B * 2 * sizeof(unsigned long long), st));
+    HIP_TRY(hipMemsetAsync(n_pairs_u64, 0, sizeof(unsigned long long), st));
+    const dim3 grid(grid_for((size_t)H * W, 256, 2048), B);
+    if (label_dtype == 0)
+        hipLaunchKernelGGL(contact_fill_kernel<long long>, grid, dim3(256), 0, st, (const long long *)labels, H, W, n_max, keys, cnt,
+                           table_slots, (unsigned long long *)status_u64);
+    else
+        hipLaunchKernelGGL(contact_fill_kernel<int>, grid, dim3(256), 0, st, (const int *)labels, H, W, n_max, keys, cnt, table_slots,
+                           (unsigned long long *)status_u64);
+    hipLaunchKernelGGL(pairs_compact_kernel, dim3(grid_for(table_slots, 256, 2048)), dim3(256), 0, st, (const unsigned long long *)keys,
+                       (const unsigned *)cnt, table_slots, (unsigned long long *)pair_keys_u64, (unsigned *)pair_counts_u32,
+                       (unsigned long long *)n_pairs_u64);
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -25,6 +25,9 @@ filled, small cells and cells on the frame dropped, with either connectivity (un
 cell_sums, props_from_sums, cell_props and select_cells are the step after the instance map: one row of exact integers per cell
 (unet_cell_sums), the usual shape and intensity properties formed from them on the host, and the per-id remap that drops or
 renumbers cells by any decision taken on those rows (unet_remap_labels).
+cell_hulls, hull_props, cell_neighbours and neighbour_counts measure what that table cannot see: the convex hull of every cell
+with its area and calliper widths as exact integers (unet_cell_hulls), solidity and the Feret diameters formed from them on the
+host, and the list of touching pairs of cells with the length of their common border (unet_cell_contacts).
 link_frames, tracks_from_links and track_cells carry the instance maps of a time-lapse across frames: for every cell the cell of the
 frame before that it overlaps most (unet_link_frames), the tracks, divisions and the Cell Tracking Challenge's res_track.txt table
 formed from those links on the host, and the maps relabelled by track on the device (unet_remap_labels).
@@ -421,6 +424,149 @@ def select_cells(labels, keep, *, renumber=False):
     if bad:
         raise ValueError("select_cells: %d pixels hold ids outside [0, %d]" % (bad, n_max))
     return out[0] if labels.dim() == 2 else out
+
+
+# ---- convex hulls and neighbours of the cells ---------------------------------------------------------------------------
+
+CellHulls = collections.namedtuple("CellHulls", "n_vertices area2 feret_max2 width_cross width_len2 offset vertices")
+HullProps = collections.namedtuple("HullProps", "convex_area solidity feret_max feret_min convex_perimeter n_vertices")
+Neighbours = collections.namedtuple("Neighbours", "b i j sides")
+
+
+def cell_hulls(labels, sums=None, *, n_max=None):
+    """The convex hull of every cell of an instance map and the exact integers measured on it, on the device (unet_cell_hulls):
+    labels as cell_sums takes them.  A pixel (y, x) is the closed unit square [x, x+1] x [y, y+1] in corner coordinates; the hull
+    of id i >= 1 is the convex hull of the union of its pixels' squares.  Ids need not be connected; id 0 is skipped and its row
+    is 0, as is the row of every absent id.  sums: the CellSums of cell_sums(labels, ..., n_max=n_max) (its boxes are used), or
+    None to form it here.  Returns CellHulls of device tensors [B, n_max+1] ([n_max+1] for a single image) unless stated:
+      n_vertices   int32, the vertices of the hull, collinear points dropped
+      area2        int64, twice the hull's area
+      feret_max2   int64, the largest squared distance between two vertices
+      width_cross, width_len2   int64 (c, l2) of the hull edge with the smallest width c / sqrt(l2): c = the largest |cross| of a
+                   vertex against the edge, l2 = the edge's squared length; the smaller l2 among edges of equal width
+      offset       int64 [B (n_max+1) + 1] ([n_max+2]): row r owns vertices[2 offset[r] : 2 offset[r+1]]
+      vertices     int32 [2 L, 2], (x, y): the row's n_vertices vertices, down the left side from the top and up the right side
+                   from the bottom, then zeros
+    The offsets are a cumulative sum on the device and their total L is read back once to size the tables; the status words are
+    read at the end.  Pixels with an id outside [0, n_max] and boxes that do not hold their id's pixels raise ValueError; host
+    tensors raise NotImplementedError (no CPU path).  hull_props turns the table into areas, solidity and Feret diameters."""
+    (lab,) = _id_maps("cell_hulls", "unet_cell_hulls", labels)
+    import _hip
+    B, H, W = lab.shape
+    if max(H, W) > MEASURE_EDGE:
+        raise ValueError("cell_hulls: H and W must be <= %d, got %d x %d" % (MEASURE_EDGE, H, W))
+    if sums is None:
+        sums = cell_sums(labels, n_max=n_max)
+    bbox, present = sums.bbox, sums.present
+    if not (torch.is_tensor(bbox) and torch.is_tensor(present)) or bbox.dtype != torch.int32 or bbox.dim() != labels.dim() \
+            or bbox.shape[-1] != 4 or present.shape != bbox.shape[:-1] or (labels.dim() == 3 and bbox.shape[0] != B):
+        raise ValueError("cell_hulls: sums must be the CellSums of cell_sums(labels) (bbox int32 [.., n_max+1, 4])")
+    _device_only("cell_hulls", "unet_cell_hulls", bbox, present)
+    N = bbox.shape[-2]
+    if n_max is not None and (isinstance(n_max, bool) or not isinstance(n_max, (int, np.integer)) or int(n_max) + 1 != N):
+        raise ValueError("cell_hulls: n_max = %r does not match the %d rows of sums" % (n_max, N))
+    n_max, dev = N - 1, lab.device
+    bbox, present = bbox.reshape(B, N, 4).contiguous(), present.reshape(B, N).bool()
+    levels = torch.where(present, (bbox[..., 2] - bbox[..., 0] + 1).long(), torch.zeros((), dtype=torch.int64, device=dev))
+    levels[:, 0] = 0
+    offset = torch.zeros(B * N + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(levels.flatten(), dim=0, out=offset[1:])
+    L = int(offset[-1])
+    n_vertices = torch.empty(B, N, dtype=torch.int32, device=dev)
+    area2 = torch.empty(B, N, dtype=torch.int64, device=dev)
+    feret_max2 = torch.empty(B, N, dtype=torch.int64, device=dev)
+    width = torch.empty(B, N, 2, dtype=torch.int64, device=dev)
+    vertices = torch.empty(2 * L, 2, dtype=torch.int32, device=dev)
+    status = torch.empty(B, 2, dtype=torch.int64, device=dev)
+    scratch = _hip.scratch("unet_cell_hulls", dev, L)
+    _hip.run("unet_cell_hulls", dev, _hip.ptr(lab), 0 if lab.dtype == torch.int64 else 2, B, H, W, n_max, _hip.ptr(bbox), _hip.ptr(offset), L,
+             _hip.ptr(n_vertices), _hip.ptr(area2), _hip.ptr(feret_max2), _hip.ptr(width), _hip.ptr(vertices) if L else None, _hip.ptr(status),
+             _hip.ptr(scratch) if L else None)
+    bad_id, outside = (int(v) for v in status.cpu().sum(dim=0))
+    if bad_id:
+        raise ValueError("cell_hulls: %d pixels hold ids outside [0, %d]" % (bad_id, n_max))
+    if outside:
+        raise ValueError("cell_hulls: %d pixels lie outside the box that sums gives for their id" % outside)
+    out = [n_vertices, area2, feret_max2, width[..., 0], width[..., 1]]
+    return CellHulls(*(t if labels.dim() == 3 else t[0] for t in out), offset, vertices)
+
+
+def hull_props(hulls, sums):
+    """The hull-based shape properties of every id from the tables of cell_hulls and cell_sums (device tensors, host tensors or
+    arrays): pure numpy on the host.  Returns HullProps of float64 arrays of the tables' leading shape, nan wherever an id is
+    absent (row 0 included):
+      convex_area       area2 / 2
+      solidity          area / convex area = 2 area / area2, at most 1 and exactly 1 for a rectangle; a cell with a concavity
+                        (two touching discs under one id) falls well below a convex one
+      feret_max         sqrt(feret_max2), the largest calliper width
+      feret_min         c / sqrt(l2), the smallest calliper width
+      convex_perimeter  the sum of the vertex-to-vertex lengths around the hull
+      n_vertices        int32 as in the table (0 for an absent id)"""
+    def host(t):
+        return t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+    h = CellHulls(*(host(t) for t in hulls))
+    k = h.n_vertices.astype(np.int64)
+    on = k > 0
+    nan = np.where(on, 0.0, np.nan)
+    area = host(sums.area).astype(np.float64)
+    if area.shape != k.shape:
+        raise ValueError("hull_props: hulls %s and sums %s do not belong together" % (k.shape, area.shape))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        a2 = h.area2.astype(np.float64) + nan
+        feret_min = h.width_cross.astype(np.float64) / np.sqrt(h.width_len2.astype(np.float64)) + nan
+    kf = k.ravel()
+    row = np.repeat(np.arange(kf.size), kf)                             # one entry per vertex: its row, its place in the row
+    pos = np.arange(row.size) - np.repeat(np.cumsum(kf) - kf, kf)
+    start = 2 * h.offset.astype(np.int64)[row]
+    v = h.vertices.astype(np.float64)
+    p, q = v[start + pos], v[start + (pos + 1) % np.maximum(kf[row], 1)]
+    perimeter = np.bincount(row, weights=np.hypot(q[:, 0] - p[:, 0], q[:, 1] - p[:, 1]), minlength=kf.size).reshape(k.shape) + nan
+    return HullProps(convex_area=a2 / 2, solidity=2 * area / a2, feret_max=np.sqrt(h.feret_max2.astype(np.float64)) + nan,
+                     feret_min=feret_min, convex_perimeter=perimeter, n_vertices=h.n_vertices)
+
+
+def cell_neighbours(labels, *, _table_slots=None):
+    """Who touches whom in an instance map, and along how much border (unet_cell_contacts): labels as cell_sums takes them.
+    Returns Neighbours(b, i, j, sides) of int64 numpy arrays sorted by (b, i, j): one entry per image b and unordered pair of ids
+    1 <= i < j with at least one unit pixel side at which a pixel of i is 4-adjacent to a pixel of j, and the number of such sides.
+    Summed over the pairs that hold an id they give CellSums.contact of that id.  The counting is exact and on the device; the
+    protocol is pair_table's: the largest id is read back once, and the table is doubled and the call repeated while it reports
+    an overflow.  Negative ids and ids >= 2^24 raise ValueError; host tensors raise NotImplementedError (no CPU path)."""
+    (lab,) = _id_maps("cell_neighbours", "unet_cell_contacts", labels)
+    import _hip
+    B, H, W = lab.shape
+    if max(H, W) > MEASURE_EDGE:
+        raise ValueError("cell_neighbours: H and W must be <= %d, got %d x %d" % (MEASURE_EDGE, H, W))
+    (n_max,) = _id_range("cell_neighbours", lab)
+    dev = lab.device
+    n_pairs = torch.empty(1, dtype=torch.int64, device=dev)
+    status = torch.empty(B, 2, dtype=torch.int64, device=dev)
+    slots = 1 << (8 * n_max + 1024 - 1).bit_length() if _table_slots is None else int(_table_slots)
+    while True:
+        keys, counts = torch.empty(slots, dtype=torch.int64, device=dev), torch.empty(slots, dtype=torch.int32, device=dev)
+        scratch = _hip.scratch("unet_cell_contacts", dev, B, slots)
+        _hip.run("unet_cell_contacts", dev, _hip.ptr(lab), 0 if lab.dtype == torch.int64 else 2, B, H, W, n_max, slots, _hip.ptr(keys),
+                 _hip.ptr(counts), _hip.ptr(n_pairs), _hip.ptr(status), _hip.ptr(scratch))
+        refused, dropped = (int(v) for v in status.cpu().sum(dim=0))
+        if refused:
+            raise ValueError("cell_neighbours: %d pixels hold ids outside [0, %d]" % (refused, n_max))
+        if not dropped:
+            break
+        slots *= 2
+    n = int(n_pairs.item())
+    k, c = keys[:n].cpu().numpy().view(np.uint64), counts[:n].cpu().numpy().astype(np.int64)
+    order = np.argsort(k)                                   # distinct unsigned keys b << 48 | i << 24 | j: the order of (b, i, j)
+    k, c = k[order], c[order]
+    return Neighbours(*((k >> np.uint64(s) & np.uint64(m)).astype(np.int64) for s, m in ((48, 0xFFFF), (24, 0xFFFFFF), (0, 0xFFFFFF))), c)
+
+
+def neighbour_counts(neigh, B, n_max):
+    """int64 [B, n_max+1]: the number of distinct neighbours of every cell, from the list of cell_neighbours."""
+    out = np.zeros((int(B), int(n_max) + 1), np.int64)
+    b = np.asarray(neigh.b, np.int64)
+    np.add.at(out, (b, np.asarray(neigh.i, np.int64)), 1)
+    np.add.at(out, (b, np.asarray(neigh.j, np.int64)), 1)
+    return out
 
 
 SegMeasure = collections.namedtuple("SegMeasure", "seg jaccard_sum n_gt n_matched n_pred per_image jaccard")

@@ -415,6 +415,33 @@ int unet_cell_sums(const void *labels, int label_dtype, const void *image, int i
  * status_u64 [B].  Limits and errors as above.                                                                               */
 int unet_remap_labels(const void *labels, int label_dtype, int B, int H, int W, const void *map_i32, int n_max, long long map_stride,
                       void *out_i32, void *status_u64, void *stream);
+/* The convex hull of every cell of an instance map, and the exact integers measured on it (hull.hip; functions.cell_hulls,
+ * functions.hull_props; the definition in full: DESIGN.md section 4u; what a loop over cells with scipy.spatial.ConvexHull gives).
+ * A pixel (y, x) is the closed unit square [x, x+1] x [y, y+1]; the hull of id i >= 1 of image b is the convex hull of the union
+ * of its pixels' squares, i.e. of their integer corner points.  Ids need not be connected; id 0 is skipped.  labels, label_dtype,
+ * n_max as unet_cell_sums; bbox_i32 [B][n_max+1][4] is unet_cell_sums's.  Row r = b (n_max + 1) + i has y1 - y0 + 1 levels if
+ * i >= 1 and the id is present, else 0; level_offset_i64 [B (n_max+1) + 1] is the exclusive prefix sum of those counts and
+ * n_levels = L their total.
+ *   n_vertices_i32 [B][n_max+1]    : k, the vertices of the hull (collinear points dropped; >= 4 for a present id)
+ *   area2_i64      [B][n_max+1]    : twice the area of the hull (shoelace sum)
+ *   feret_max2_i64 [B][n_max+1]    : the largest squared distance between two vertices
+ *   width_i64      [B][n_max+1][2] : (c, l2) of the hull edge (p, q) with the smallest c^2 / l2, the smaller l2 on equal ratios,
+ *                                    where c = max over the vertices v of |cross(q - p, v - p)| and l2 = |q - p|^2: the minimum
+ *                                    Feret diameter is c / sqrt(l2).  Compared in 128-bit integers, no division
+ *   vertices_i32   [2 L][2]        : (x, y) in corner coordinates; row r owns [2 off[r], 2 off[r+1]): its k vertices, the left
+ *                                    chain from (lo_0, y0) down to (lo_h, y1), then the right chain from (hi_h, y1) up to
+ *                                    (hi_0, y0); the rest of the slice is 0
+ *   status_u64     [B][2]          : pixels whose id is outside [0, n_max]; pixels outside the box given for their id, or whose
+ *                                    id's level count does not fit its box or the tables.  Neither kind writes anything
+ * Every output of row 0, of an absent id and of a row with an inconsistent box or level count is 0.  n_levels = 0 is legal:
+ * vertices_i32 and scratch may be NULL then.  Three memsets and two launches on the stream, no read-back; every output is the same
+ * in every run.  Limits as unet_cell_sums; another dtype, a NULL pointer, n_levels < 0 and a size over the limit return an error
+ * and write nothing.
+ * scratch: unet_cell_hulls_scratch_bytes(n_levels) (8 bytes per level: two 32-bit tables), initialised by the call.           */
+size_t unet_cell_hulls_scratch_bytes(long long n_levels);
+int unet_cell_hulls(const void *labels, int label_dtype, int B, int H, int W, int n_max, const void *bbox_i32, const void *level_offset_i64,
+                    long long n_levels, void *n_vertices_i32, void *area2_i64, void *feret_max2_i64, void *width_i64, void *vertices_i32,
+                    void *status_u64, void *scratch, void *stream);
 /* The integers of the Cell Tracking Challenge SEG measure, the score behind the goals of trainer.py:20-26 (Ronneberger et al.
  * 2015, Table 2): gt_i32, pred_i32 id maps int32 [B,H,W], 0 = background, gt ids anywhere in [0, ng_max] (not necessarily
  * consecutive, an object not necessarily connected), pred ids in [0, np_max]; ng_max, np_max < 2^24.
@@ -446,6 +473,18 @@ size_t unet_partition_pairs_scratch_bytes(int B, size_t table_slots);
 int unet_partition_pairs(const void *gt_i32, const void *pred_i32, int B, int H, int W, int ng_max, int np_max, size_t table_slots,
                          void *pair_keys_u64, void *pair_counts_u32, void *n_pairs_u64, void *status_u64, void *scratch,
                          void *stream);
+/* Who touches whom in an instance map, and along how much border (instances.hip; functions.cell_neighbours): for every unordered
+ * pair of ids 1 <= i < j of image b, the unit pixel sides at which a pixel of i is 4-adjacent to a pixel of j.  labels,
+ * label_dtype, n_max and the limits as unet_cell_sums; outputs, table_slots and the protocol as unet_partition_pairs:
+ *   pair_keys_u64 [table_slots]   : the distinct (b, i, j) packed b << 48 | i << 24 | j, in unspecified order
+ *   pair_counts_u32 [table_slots] : the sides of each; summed over the pairs that hold i they give unet_cell_sums's contact of i
+ *   n_pairs_u64 [1]               : how many entries of the two lists are written; the rest is left untouched
+ *   status_u64 [B][2]             : {pixels whose id is outside [0, n_max] (nobody's neighbour);  sides dropped because the table
+ *                                    was full: if non-zero the caller repeats the call with a larger table}
+ * scratch: unet_cell_contacts_scratch_bytes(B, table_slots), initialised by the call.                                      */
+size_t unet_cell_contacts_scratch_bytes(int B, size_t table_slots);
+int unet_cell_contacts(const void *labels, int label_dtype, int B, int H, int W, int n_max, size_t table_slots, void *pair_keys_u64,
+                       void *pair_counts_u32, void *n_pairs_u64, void *status_u64, void *scratch, void *stream);
 /* Linking the cells of consecutive frames by overlap, the greedy tracker of the Cell Tracking Challenge submissions
  * (track.hip; functions.link_frames, functions.track_cells; the definition in full: DESIGN.md section 4s).  from_i32, to_i32
  * id maps int32 [T,H,W], 0 = background, ids anywhere in [0, n_max] (not necessarily consecutive or connected), n_max < 2^24;
