@@ -68,6 +68,9 @@ _SIGS = {
     "unet_softmax_ce_scratch_bytes": (C.c_size_t, [C.c_size_t]),
     "unet_softmax_ce_step": (C.c_int, [vp, C.c_long, C.c_long, C.c_long, C.c_int, vp, vp, C.c_long, C.c_long, C.c_long, C.c_int, C.c_int,
                                        C.c_int, vp, vp, C.c_float, vp, vp, vp, vp]),
+    "unet_dice_scratch_bytes": (C.c_size_t, [C.c_int] * 4),
+    "unet_dice_step": (C.c_int, [vp, C.c_long, C.c_long, C.c_long, C.c_int, vp, vp, C.c_long, C.c_long, C.c_long, C.c_int, C.c_int, C.c_int,
+                                 C.c_float, C.c_float, C.c_float, C.c_int, vp, vp, vp, C.c_float, vp, vp, vp, vp]),
     "unet_argmaxk": (C.c_int, [vp, C.c_long, C.c_long, C.c_long, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp]),
     "unet_sgd_momentum": (C.c_int, [vp, vp, vp, C.POINTER(C.c_size_t), C.c_int, C.c_float, C.c_float, C.c_int, vp]),
     "unet_minmax": (C.c_int, [vp, C.c_int, C.c_size_t, vp, vp]),

@@ -1397,6 +1397,17 @@ def metrics_from_confusion(conf_b):
     return out
 
 
+def dice_from_confusion(conf):
+    """The hard per-class Dice 2 TP / (2 TP + FP + FN) from K x K confusion counts (optim.crop_argmax_confusion, conf[..., i, j] =
+    pixels labelled i predicted j; any leading axes, e.g. [B,K,K]): float64 [..., K], NaN for a class that is absent from
+    both the labels and the prediction."""
+    conf = np.asarray(conf.cpu() if hasattr(conf, 'cpu') else conf, dtype=np.int64)
+    tp = np.diagonal(conf, axis1=-2, axis2=-1).astype(np.float64)
+    denom = (conf.sum(axis=-1) + conf.sum(axis=-2)).astype(np.float64)        # (TP + FN) + (TP + FP)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        return np.where(denom > 0, 2.0 * tp / denom, np.nan)
+
+
 def evaluation_metrics(pred, label):
     """[[IoU],[pixel error]] as a (2,1) array (functions.py:150-170)."""
     out = np.empty([2, 1])

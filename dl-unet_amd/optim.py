@@ -3,8 +3,11 @@
   bce_with_logits  — nn.BCEWithLogitsLoss(weight=w)(preds, ll) + backward   (trainer.py:63-77)
   argmax2          — preds.argmax(dim=1) for the 2-class head               (trainer.py:82, tester.py:30)
   SGD              — optim.SGD(lr, momentum).step()                          (trainer.py:30,78)
+  softmax_ce_step  — the paper's eq. 1 for K classes; dice_step — soft Dice, alone or added to it (no counterpart in the reference)
 """
+import collections
 import ctypes as C
+import math
 
 import torch
 
@@ -253,6 +256,93 @@ def softmax_ce_step(preds, labels, weight=None, grad_scale=1.0, want_mask=True, 
         if n:
             raise ValueError("softmax_ce_step: %d label(s) outside [0, %d)" % (n, preds.shape[1]))
     return loss, (mask if want_mask else None)
+
+
+DICE_BATCH = 1                  # UNET_DICE_BATCH
+DICE_SKIP_BACKGROUND = 2        # UNET_DICE_SKIP_BACKGROUND
+
+
+class DiceParts(collections.namedtuple("DiceParts", "ce dice per_class")):
+    """The parts of dice_step's loss: ce and dice are 0-d fp32 tensors (L_ce and L_dice, unweighted), per_class the soft Dice
+    coefficients, fp32 [B,K] ([1,K] with batch=True), of every class whether it is counted in the mean or not."""
+
+
+class _DiceFn(torch.autograd.Function):
+    """unet_dice_step: the loss and its parts, the gradient, the argmax mask and the invalid-label count in one call."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, weight, wstrides, ce_weight, dice_weight, smooth, flags, grad_scale, want_mask):
+        B, K, H, W = logits.shape
+        need_grad = ctx.needs_input_grad[0]
+        if logits.stride(3) != 1:
+            logits = logits.contiguous()
+        labels = labels.to(logits.device).reshape(B, H, W)
+        if labels.dtype != torch.int64:
+            labels = labels.long()
+        labels = labels.contiguous()
+        dev = logits.device
+        losses = torch.empty(3, dtype=torch.float32, device=dev)
+        coeffs = torch.empty(1 if flags & DICE_BATCH else B, K, dtype=torch.float32, device=dev)
+        invalid = torch.empty((), dtype=torch.int64, device=dev)
+        dl = torch.empty(B, K, H, W, dtype=torch.float32, device=dev) if need_grad else None
+        mask = torch.empty(B, H, W, dtype=torch.int64, device=dev) if want_mask else torch.empty(0, dtype=torch.int64, device=dev)
+        sc = _hip.scratch("unet_dice", dev, B, K, H, W)
+        ws = wstrides if weight is not None else (0, 0, 0)
+        _hip.run("unet_dice_step", dev, _hip.ptr(logits), logits.stride(0), logits.stride(1), logits.stride(2), K, _hip.ptr(labels),
+                 _hip.ptr(weight), ws[0], ws[1], ws[2], B, H, W, float(ce_weight), float(dice_weight), float(smooth), int(flags),
+                 _hip.ptr(losses), _hip.ptr(coeffs), _hip.ptr(dl), float(grad_scale), _hip.ptr(mask) if want_mask else None,
+                 _hip.ptr(invalid), _hip.ptr(sc))
+        if need_grad:
+            ctx.save_for_backward(dl)
+        loss, ce, dice = losses[0], losses[1], losses[2]
+        ctx.mark_non_differentiable(ce, dice, coeffs, mask, invalid)
+        return loss, ce, dice, coeffs, mask, invalid
+
+    @staticmethod
+    def backward(ctx, g, *_unused):
+        (dl,) = ctx.saved_tensors
+        return (dl * g,) + (None,) * 9
+
+
+def dice_step(preds, labels, weight=None, *, ce_weight=0.0, dice_weight=1.0, smooth=1.0, batch=False, include_background=True,
+              grad_scale=1.0, want_mask=True, validate=True, return_parts=False):
+    """The soft Dice loss (Milletari et al. 2016) over the K-class soft-max, alone or added to the weighted cross-entropy of
+    softmax_ce_step (nnU-Net's CE + Dice), with its gradient and the argmax mask, in one library call (unet_dice_step).  With
+    p = softmax(preds) over the classes and v = the pixels whose label lies in [0, K):
+         I[b,k] = sum_v p_k [y = k]     P[b,k] = sum_v p_k     Y[b,k] = sum_v [y = k]
+         dice[b,k] = (2 I + smooth) / (P + Y + smooth)         L_dice = 1 - mean of dice over the (b,k) counted
+         loss = ce_weight * L_ce + dice_weight * L_dice        L_ce = softmax_ce_step's loss, `weight` included
+    batch=True sums I, P and Y over the batch before the ratio (nnU-Net's batch dice: one term per class);
+    include_background=False leaves class 0 out of the mean.  smooth must be positive: it keeps 0 / 0 out of a class that is
+    absent and unpredicted.  preds, labels, weight (a PER-PIXEL map; it multiplies the CE term only), grad_scale, want_mask and
+    validate are softmax_ce_step's; labels outside [0, K) add nothing to any sum and no gradient.
+    Returns (loss, mask | None), and with return_parts=True a third value DiceParts(ce, dice, per_class); loss.backward()
+    feeds the gradient the same call produced (x grad_scale).  The result is bit-identical on every run and stream.
+    Raises ValueError for smooth <= 0, a negative weight, both weights 0, and a weight map with ce_weight == 0 (it would be
+    silently unused)."""
+    if preds.dim() != 4 or preds.shape[1] < 2:
+        raise ValueError("dice_step: expected preds [B,K,H,W] with K >= 2, got %s" % (tuple(preds.shape),))
+    ce_weight, dice_weight, smooth = float(ce_weight), float(dice_weight), float(smooth)
+    if not (smooth > 0.0 and math.isfinite(smooth)):
+        raise ValueError("dice_step: smooth must be positive and finite, got %r" % smooth)
+    if not (ce_weight >= 0.0 and dice_weight >= 0.0 and math.isfinite(ce_weight + dice_weight)):
+        raise ValueError("dice_step: ce_weight and dice_weight must be >= 0, got %r and %r" % (ce_weight, dice_weight))
+    if ce_weight == 0.0 and dice_weight == 0.0:
+        raise ValueError("dice_step: ce_weight and dice_weight are both 0")
+    if weight is not None and ce_weight == 0.0:
+        raise ValueError("dice_step: a weight map multiplies the cross-entropy term only; with ce_weight = 0 it would be unused")
+    wstrides = None
+    if weight is not None:
+        weight, wstrides = _pixel_weight_strides(weight, preds)
+    flags = (DICE_BATCH if batch else 0) | (0 if include_background else DICE_SKIP_BACKGROUND)
+    loss, ce, dice, coeffs, mask, invalid = _DiceFn.apply(preds, labels, weight, wstrides, ce_weight, dice_weight, smooth, flags,
+                                                          grad_scale, want_mask)
+    if validate:
+        n = int(invalid.item())
+        if n:
+            raise ValueError("dice_step: %d label(s) outside [0, %d)" % (n, preds.shape[1]))
+    out = (loss, mask if want_mask else None)
+    return out + (DiceParts(ce, dice, coeffs),) if return_parts else out
 
 
 def argmaxk(preds):

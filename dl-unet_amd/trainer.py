@@ -9,6 +9,7 @@
     weight map (N3)    class_balance(labels)               -> unet_class_balance
     (loss_weights='border') weighted_map(labels)                -> unet_weighted_map
     (loss='softmax_ce')     the paper's eq. 1 for K classes       -> unet_softmax_ce_step, unet_eval_confusion
+    (loss='dice' | 'ce_dice') soft Dice, alone or added to eq. 1  -> unet_dice_step
 
 Reference behaviours kept on purpose: Q3 the dataset-name comparisons are IDENTITY tests
 against string literals in the reference (trainer.py:18-27,68,110): a name arriving from argv never
@@ -71,16 +72,40 @@ def _goal_for(DATASET):
 
 
 _LOSS_WEIGHTS = {'class_balance': class_balance, 'border': weighted_map, 'none': None}
-_LOSSES = ('bce', 'softmax_ce')
+_LOSSES = ('bce', 'softmax_ce', 'dice', 'ce_dice')
+_DICE_DEFAULTS = {'dice': dict(ce_weight=0.0, dice_weight=1.0), 'ce_dice': dict(ce_weight=1.0, dice_weight=1.0)}
+_DICE_OPTIONS = ('smooth', 'batch', 'include_background', 'ce_weight', 'dice_weight')
 
 
-def _step_loss(unet, images, labels, device, train, weight_fn=class_balance, loss_kind='bce', validate=False):
+def dice_step_options(loss, dice_options=None):
+    """The keyword arguments optim.dice_step gets for loss = 'dice' | 'ce_dice': the loss's default weights ((0, 1) and (1, 1))
+    overridden by `dice_options`; None for the other losses.  Raises ValueError for an unknown key, and for dice_options
+    given with a loss that does not use them."""
+    if loss not in _DICE_DEFAULTS:
+        if dice_options:
+            raise ValueError("dice_options are for loss='dice' and loss='ce_dice', got loss=%r" % (loss,))
+        return None
+    opts = dict(_DICE_DEFAULTS[loss])
+    if dice_options is not None:
+        unknown = sorted(set(dice_options) - set(_DICE_OPTIONS))
+        if unknown:
+            raise ValueError("unknown dice_options %s (known: %s)" % (unknown, list(_DICE_OPTIONS)))
+        opts.update(dice_options)
+    if loss == 'dice' and float(opts['ce_weight']) != 0.0:
+        raise ValueError("loss='dice' has no cross-entropy term (ce_weight=%r); loss='ce_dice' is the sum" % (opts['ce_weight'],))
+    return opts
+
+
+def _step_loss(unet, images, labels, device, train, weight_fn=class_balance, loss_kind='bce', validate=False, dice_kw=None):
     preds = unet(images.to(device))
     labels = labels.to(device)                                  # everything below stays on the device
     pad = int((preds.shape[-1] - labels.shape[-1]) / 2)
     preds = preds[:, :, pad:labels.shape[-1] + pad, pad:labels.shape[-1] + pad]
     weight_maps = weight_fn(labels.squeeze(1)) if weight_fn is not None else None   # [B,H,W] (trainer.py:72 / :70)
-    if loss_kind == 'softmax_ce':
+    if dice_kw is not None:
+        # soft Dice (+ eq. 1): the weight map, if any, multiplies the cross-entropy term only
+        loss, _ = hip_optim.dice_step(preds, labels, weight=weight_maps, want_mask=False, validate=validate, **dice_kw)
+    elif loss_kind == 'softmax_ce':
         # eq. 1: the weight map multiplies each pixel's cross-entropy (per pixel, not Q4's class-axis alignment)
         loss, _ = hip_optim.softmax_ce_step(preds, labels, weight=weight_maps, want_mask=False, validate=validate)
     else:
@@ -106,6 +131,9 @@ def check_loss_options(n_classes, loss, loss_weights):
         raise ValueError("loss must be one of %s, got %r" % (list(_LOSSES), loss))
     if loss_weights not in _LOSS_WEIGHTS:
         raise ValueError("loss_weights must be one of %s, got %r" % (sorted(_LOSS_WEIGHTS), loss_weights))
+    if loss == 'dice' and loss_weights != 'none':
+        raise ValueError("loss='dice' has no cross-entropy term for loss_weights=%r to weight; it takes loss_weights='none' "
+                         "(loss='ce_dice' weights its cross-entropy term)" % (loss_weights,))
     if n_classes != 2:
         if loss == 'bce':
             raise ValueError("loss='bce' is the reference's two-class loss; a %d-class net trains with loss='softmax_ce'" % n_classes)
@@ -115,7 +143,7 @@ def check_loss_options(n_classes, loss, loss_weights):
 
 
 def training(unet, train_loader, val_loader, epochs, batch_size, device, fold_dir, DATASET, *, resume_from=None,
-             save_optimizer=False, loss_weights='class_balance', loss='bce'):
+             save_optimizer=False, loss_weights='class_balance', loss='bce', dice_options=None):
     """Reference signature (trainer.py:15) plus keyword-only extensions, all off by default so that the files
     written are exactly the reference's: resume_from = a checkpoint made by checkpoint.py (weights + SGD momentum +
     scheduler + epoch), save_optimizer = also write models/checkpoint_latest.pth every epoch (both SURVEY N4);
@@ -128,9 +156,17 @@ def training(unet, train_loader, val_loader, epochs, batch_size, device, fold_di
     both losses take all three loss_weights: loss='bce' with loss_weights='none' is the reference's BCE without a weight map
     (uniform), 'softmax_ce' with 'class_balance' / 'border' weights each pixel's cross-entropy by the map.  Labels are validated (an error if any is outside [0, K)) on the first
     training step of every epoch only: the check reads a count back to the host, and a sync on every step would add host gap
-    to every step; labels outside [0, K) in the other steps add no loss and no gradient."""
+    to every step; labels outside [0, K) in the other steps add no loss and no gradient.
+    loss = 'dice' trains with the soft Dice loss over the soft-max (optim.dice_step), loss = 'ce_dice' with its sum with eq. 1
+    (nnU-Net's default); both are valid for every K >= 2.  'ce_dice' follows 'softmax_ce' for loss_weights (all three at K = 2,
+    weighting the cross-entropy term; 'none' at K > 2); 'dice' has no term to weight and takes loss_weights='none' only.
+    dice_options = a dict of smooth, batch, include_background, ce_weight, dice_weight (dice_step's; unknown keys raise); the
+    weights default to (0, 1) for 'dice' and (1, 1) for 'ce_dice'.  Under dp.DataParallel every rank forms the Dice
+    coefficients on its own shard of the batch, then the gradients are averaged: batch=True means the rank's batch, not the
+    global one."""
     n_classes = getattr(unet, 'n_classes', 2)
     check_loss_options(n_classes, loss, loss_weights)
+    dice_kw = dice_step_options(loss, dice_options)
     weight_fn = _LOSS_WEIGHTS[loss_weights]
     loss_kind = loss
     when_to_stop, goal = _goal_for(DATASET)
@@ -173,7 +209,7 @@ def training(unet, train_loader, val_loader, epochs, batch_size, device, fold_di
 
         for step, (images, labels) in enumerate(train_loader):
             optimizer.zero_grad()
-            preds, loss, labels = _step_loss(unet, images, labels, device, True, weight_fn, loss_kind, step == 0)
+            preds, loss, labels = _step_loss(unet, images, labels, device, True, weight_fn, loss_kind, step == 0, dice_kw)
             loss.backward()
             optimizer.step()
             total_loss += loss.detach()
@@ -183,7 +219,7 @@ def training(unet, train_loader, val_loader, epochs, batch_size, device, fold_di
 
         with torch.no_grad():
             for images, labels in val_loader:
-                preds, loss, labels = _step_loss(unet, images, labels, device, False, weight_fn, loss_kind)
+                preds, loss, labels = _step_loss(unet, images, labels, device, False, weight_fn, loss_kind, dice_kw=dice_kw)
                 total_loss_val += loss
                 if val_eval is None:
                     val_eval = _first_sample_metrics(preds, labels)

@@ -261,6 +261,27 @@ size_t unet_softmax_ce_scratch_bytes(size_t npix);
 int unet_softmax_ce_step(const void *logits, long xsB, long xsC, long xsH, int K, const void *labels_i64, const void *weight,
                          long wsB, long wsH, long wsW, int B, int H, int W, void *loss_out, void *dlogits, float grad_scale,
                          void *mask_i64, void *invalid_u64, void *scratch, void *stream);
+/* L1 + L2 with an overlap loss: the soft Dice loss (Milletari et al. 2016) over the K-class soft-max, alone or added to the
+ * cross-entropy above (nnU-Net's CE + Dice).  Logits, labels, weight, mask_i64, invalid_u64 and grad_scale as in
+ * unet_softmax_ce_step; the weight map multiplies the CE term only.  With p = softmax(l) and v = the pixels whose label is in [0, K):
+ *   I[b,k] = sum_v p_k [y = k]   P[b,k] = sum_v p_k   Y[b,k] = sum_v [y = k]   dice[b,k] = (2 I + s) / (P + Y + s),  s = smooth > 0
+ *   L_dice = 1 - mean of dice over the counted (b,k);   L = ce_weight * L_ce + dice_weight * L_dice   (both weights >= 0, not both 0)
+ *   flags    : UNET_DICE_BATCH sums I, P, Y over the batch before the ratio (one term per class); UNET_DICE_SKIP_BACKGROUND
+ *              leaves class 0 out of the mean
+ *   loss_out : 3 fp32 = L, L_ce, L_dice (partials in double, fixed order: bit-identical on every run and stream)
+ *   dice_out : NULL or [B,K] fp32 ([1,K] with UNET_DICE_BATCH) = dice, of every class, counted or not
+ *   dlogits  : NULL or dense [B,K,H,W] = grad_scale * (ce_weight * dL_ce/dl + dice_weight * dL_dice/dl),
+ *              dL_dice/dl_j = p_j (g_j - sum_k g_k p_k), g_k = -(2 [y = k] / D - (2 I + s) / D^2) / terms at valid pixels, D = P + Y + s;
+ *              0 on every plane of a pixel whose label is outside [0, K)
+ * Three launches (sums, finish, gradient; the last only with dlogits), no host sync.  B <= 65535.
+ * scratch: >= unet_dice_scratch_bytes(B, K, H, W) (0 for an empty shape). */
+#define UNET_DICE_BATCH 1
+#define UNET_DICE_SKIP_BACKGROUND 2
+size_t unet_dice_scratch_bytes(int B, int K, int H, int W);
+int unet_dice_step(const void *logits, long xsB, long xsC, long xsH, int K, const void *labels_i64, const void *weight,
+                   long wsB, long wsH, long wsW, int B, int H, int W, float ce_weight, float dice_weight, float smooth, int flags,
+                   void *loss_out, void *dice_out, void *dlogits, float grad_scale, void *mask_i64, void *invalid_u64,
+                   void *scratch, void *stream);
 
 /* L2 replaces preds.argmax(dim=1) (trainer.py:82, tester.py:30): [B,2,H,W] fp32 with row
  * stride ld (elements) and plane stride ps -> [B,H,W] int64; ties -> class 0.               */
