@@ -73,6 +73,12 @@ _SIGS = {
                                  C.c_float, C.c_float, C.c_float, C.c_int, vp, vp, vp, C.c_float, vp, vp, vp, vp]),
     "unet_argmaxk": (C.c_int, [vp, C.c_long, C.c_long, C.c_long, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp]),
     "unet_sgd_momentum": (C.c_int, [vp, vp, vp, C.POINTER(C.c_size_t), C.c_int, C.c_float, C.c_float, C.c_int, vp]),
+    "unet_adam_step": (C.c_int, [vp, vp, vp, vp, C.POINTER(C.c_size_t), C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
+                                 C.c_int, C.c_long, vp, vp]),
+    "unet_grad_sumsq_partials": (C.c_size_t, [C.POINTER(C.c_size_t), C.c_int]),
+    "unet_grad_sumsq": (C.c_int, [vp, C.POINTER(C.c_size_t), C.c_int, vp, C.c_size_t, vp]),
+    "unet_grad_norm_finish": (C.c_int, [vp, C.c_size_t, C.c_float, vp, vp]),
+    "unet_grads_scale": (C.c_int, [vp, C.POINTER(C.c_size_t), C.c_int, vp, vp]),
     "unet_minmax": (C.c_int, [vp, C.c_int, C.c_size_t, vp, vp]),
     "unet_mirror_pad": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
     "unet_tile_gather": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_long,

@@ -3,6 +3,8 @@
   bce_with_logits  — nn.BCEWithLogitsLoss(weight=w)(preds, ll) + backward   (trainer.py:63-77)
   argmax2          — preds.argmax(dim=1) for the 2-class head               (trainer.py:82, tester.py:30)
   SGD              — optim.SGD(lr, momentum).step()                          (trainer.py:30,78)
+  Adam, AdamW      — torch.optim.Adam / AdamW (no amsgrad / maximize) by one multi-tensor HIP kernel (no counterpart in the reference)
+  clip_grad_norm_  — nn.utils.clip_grad_norm_ on the device, without a host sync
   softmax_ce_step  — the paper's eq. 1 for K classes; dice_step — soft Dice, alone or added to it (no counterpart in the reference)
 """
 import collections
@@ -153,6 +155,126 @@ class SGD(torch.optim.Optimizer):
                     numel = (C.c_size_t * len(chunk))(*[p.numel() for p in chunk])
                     _hip.run("unet_sgd_momentum", chunk[0].device, _hip.ptr_table(chunk), _hip.ptr_table(grads), _hip.ptr_table(bufs),
                              numel, len(chunk), float(group["lr"]), float(group["momentum"]), is_first)
+
+
+def check_adam_options(lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+    """Raises ValueError for hyper-parameters unet_adam_step does not take: lr < 0, a beta outside [0, 1), eps <= 0,
+    weight_decay < 0 (non-finite values included).  No device is touched."""
+    try:
+        b1, b2 = betas
+    except (TypeError, ValueError):
+        raise ValueError("Adam: betas must be a pair (beta1, beta2), got %r" % (betas,))
+    if not (float(lr) >= 0.0 and math.isfinite(float(lr))):
+        raise ValueError("Adam: lr must be >= 0, got %r" % (lr,))
+    for i, b in enumerate((b1, b2)):
+        if not 0.0 <= float(b) < 1.0:
+            raise ValueError("Adam: beta%d must lie in [0, 1), got %r" % (i + 1, b))
+    if not (float(eps) > 0.0 and math.isfinite(float(eps))):
+        raise ValueError("Adam: eps must be positive, got %r" % (eps,))
+    if not (float(weight_decay) >= 0.0 and math.isfinite(float(weight_decay))):
+        raise ValueError("Adam: weight_decay must be >= 0, got %r" % (weight_decay,))
+
+
+def _numel_table(tensors):
+    return (C.c_size_t * len(tensors))(*[t.numel() for t in tensors])
+
+
+class Adam(torch.optim.Optimizer):
+    """torch.optim.Adam(params, lr, betas, eps, weight_decay) without amsgrad / maximize, the update done by one multi-tensor HIP
+    kernel per <= 46 tensors (unet_adam_step; the statement order is in include/unet_hip.h).  decoupled=False adds weight_decay * p
+    to the gradient (L2), decoupled=True shrinks p by lr * weight_decay before the update (AdamW).  param_groups and state keep
+    torch's shape (state: step, a Python int, exp_avg, exp_avg_sq), so lr schedulers and checkpoint.py work unchanged.
+    step(grad_scale=c), c a 1-element fp32 device tensor such as clip_grad_norm_(..., scale=False)'s coefficient, multiplies
+    every gradient by c inside the same pass; the stored gradients are left as they are.  Parameters without a gradient are
+    skipped; host tensors raise (there is no CPU fallback)."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decoupled=False):
+        check_adam_options(lr, betas, eps, weight_decay)
+        super().__init__(params, dict(lr=lr, betas=(float(betas[0]), float(betas[1])), eps=eps, weight_decay=weight_decay,
+                                      decoupled=bool(decoupled)))
+
+    @torch.no_grad()
+    def step(self, closure=None, *, grad_scale=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        if grad_scale is not None and (grad_scale.numel() != 1 or grad_scale.dtype != torch.float32):
+            raise ValueError("Adam.step: grad_scale must be a 1-element float32 device tensor, got %s %s"
+                             % (tuple(grad_scale.shape), grad_scale.dtype))
+        for group in self.param_groups:
+            by_step = {}                                       # tensors that have taken the same number of updates share a launch
+            for p in group["params"]:
+                if p.grad is None:
+                    continue
+                st = self.state[p]
+                if "step" not in st:
+                    _hip.ptr(p)                                 # a host tensor raises before any state is made
+                    st["step"] = 0
+                    st["exp_avg"] = torch.empty_like(p)         # written, never read, by the first update
+                    st["exp_avg_sq"] = torch.empty_like(p)
+                by_step.setdefault(int(st["step"]), []).append(p)
+            b1, b2 = group["betas"]
+            for done, ps in by_step.items():
+                for i in range(0, len(ps), _hip.N_PARAMS):
+                    chunk = ps[i:i + _hip.N_PARAMS]
+                    grads = [p.grad.contiguous() for p in chunk]
+                    _hip.run("unet_adam_step", chunk[0].device, _hip.ptr_table(chunk), _hip.ptr_table(grads),
+                             _hip.ptr_table([self.state[p]["exp_avg"] for p in chunk]),
+                             _hip.ptr_table([self.state[p]["exp_avg_sq"] for p in chunk]), _numel_table(chunk), len(chunk),
+                             float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]),
+                             int(bool(group["decoupled"])), done + 1, _hip.ptr(grad_scale))
+                    for p in chunk:
+                        self.state[p]["step"] = done + 1
+        return loss
+
+
+class AdamW(Adam):
+    """Adam with decoupled weight decay (Loshchilov & Hutter 2019): Adam(decoupled=True), weight_decay 1e-2 by default."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, decoupled=True)
+
+
+def clip_grad_norm_(parameters, max_norm, *, scale=True):
+    """torch.nn.utils.clip_grad_norm_(parameters, max_norm) (2-norm) on the device, without a host sync: one sum-of-squares
+    launch per <= 46 gradients (fp64 partials in a fixed order, unet_grad_sumsq), one finishing workgroup, and with scale=True
+    one launch per <= 46 gradients that multiplies them in place by the coefficient.  scale=False leaves the gradients alone:
+    hand `coef` to Adam.step(grad_scale=coef), which saves that read-and-write pass.
+    Returns (total_norm, coef), 0-dim fp32 device tensors (views of one [2] buffer): coef = min(1, max_norm / (total_norm + 1e-6)).
+    Non-finite gradients are not treated specially: a NaN norm gives a NaN coefficient.  Parameters without a gradient are
+    skipped; gradients must be contiguous fp32 device tensors."""
+    if isinstance(parameters, torch.Tensor):
+        parameters = [parameters]
+    max_norm = float(max_norm)
+    if not max_norm > 0.0:
+        raise ValueError("clip_grad_norm_: max_norm must be positive, got %r" % max_norm)
+    grads = [p.grad for p in parameters if p.grad is not None]
+    if not grads:
+        raise ValueError("clip_grad_norm_: no parameter has a gradient")
+    for g in grads:
+        if g.dtype != torch.float32 or not g.is_contiguous():
+            raise ValueError("clip_grad_norm_: gradients must be contiguous float32 tensors, got %s with strides %s" % (g.dtype, g.stride()))
+    dev = grads[0].device
+    L = _hip.lib()
+    calls = []
+    for i in range(0, len(grads), _hip.N_PARAMS):
+        chunk = grads[i:i + _hip.N_PARAMS]
+        numel = _numel_table(chunk)
+        calls.append((_hip.ptr_table(chunk), numel, len(chunk), L.unet_grad_sumsq_partials(numel, len(chunk))))
+    n_partials = sum(c[3] for c in calls)
+    partials = torch.empty(n_partials, dtype=torch.float64, device=dev)
+    out2 = torch.empty(2, dtype=torch.float32, device=dev)
+    offset = 0
+    for table, numel, n, count in calls:
+        _hip.run("unet_grad_sumsq", dev, table, numel, n, _hip.ptr(partials), offset)
+        offset += count
+    _hip.run("unet_grad_norm_finish", dev, _hip.ptr(partials), n_partials, max_norm, _hip.ptr(out2))
+    if scale:
+        coef = _hip.ptr(out2[1:])
+        for table, numel, n, _ in calls:
+            _hip.run("unet_grads_scale", dev, table, numel, n, coef)
+    return out2[0], out2[1]
 
 
 def crop_argmax_metrics(preds, labels=None):

@@ -5,6 +5,8 @@
     loss (L1)          BCEWithLogitsLoss(weight=class map)  -> unet_bce_step (target from labels, fwd + grad in one pass)
     backward           loss.backward()                     -> unet_backward_stage x6 (+ RCCL all-reduce if DP)
     update (L3)        SGD(lr=1e-4, momentum=0.99)          -> unet_sgd_momentum
+    (optimizer='adam' | 'adamw')  Adam / AdamW                   -> unet_adam_step
+    (clip_grad_norm=max_norm)     clip_grad_norm_                -> unet_grad_sumsq, unet_grad_norm_finish (+ unet_grads_scale for SGD)
     prediction (L2)    preds.argmax(dim=1) + IoU/PE        -> unet_eval_masks (fused crop+argmax+counts)
     weight map (N3)    class_balance(labels)               -> unet_class_balance
     (loss_weights='border') weighted_map(labels)                -> unet_weighted_map
@@ -142,8 +144,41 @@ def check_loss_options(n_classes, loss, loss_weights):
                              % (loss_weights, n_classes))
 
 
+_OPTIMIZERS = {'sgd': (hip_optim.SGD, ('lr', 'momentum'), dict(lr=0.0001, momentum=0.99)),
+               'adam': (hip_optim.Adam, ('lr', 'betas', 'eps', 'weight_decay'), dict(lr=0.0001)),
+               'adamw': (hip_optim.AdamW, ('lr', 'betas', 'eps', 'weight_decay'), dict(lr=0.0001))}
+
+
+def check_optimizer_options(optimizer='sgd', optimizer_options=None, clip_grad_norm=None):
+    """The keyword arguments the optimiser of training(optimizer=...) is built with: lr = 1e-4 for all three (momentum = 0.99
+    for 'sgd'; the other defaults are optim.Adam's and optim.AdamW's) overridden by `optimizer_options`.  Raises ValueError,
+    before any device work, for an unknown optimizer, an unknown key (known: lr, momentum for 'sgd'; lr, betas, eps,
+    weight_decay for 'adam' and 'adamw'), a value the optimiser does not take, and a clip_grad_norm that is neither None nor a
+    positive number."""
+    if optimizer not in _OPTIMIZERS:
+        raise ValueError("optimizer must be one of %s, got %r" % (sorted(_OPTIMIZERS), optimizer))
+    _, known, defaults = _OPTIMIZERS[optimizer]
+    opts = dict(defaults)
+    if optimizer_options is not None:
+        unknown = sorted(set(optimizer_options) - set(known))
+        if unknown:
+            raise ValueError("unknown optimizer_options %s for optimizer=%r (known: %s)" % (unknown, optimizer, list(known)))
+        opts.update(optimizer_options)
+    if optimizer == 'sgd':
+        for k in ('lr', 'momentum'):
+            if not (float(opts[k]) >= 0.0 and np.isfinite(float(opts[k]))):
+                raise ValueError("optimizer_options: %s must be >= 0, got %r" % (k, opts[k]))
+    else:
+        hip_optim.check_adam_options(**opts)
+    if clip_grad_norm is not None and not (isinstance(clip_grad_norm, (int, float)) and float(clip_grad_norm) > 0.0
+                                           and np.isfinite(float(clip_grad_norm))):
+        raise ValueError("clip_grad_norm must be None or a positive number, got %r" % (clip_grad_norm,))
+    return opts
+
+
 def training(unet, train_loader, val_loader, epochs, batch_size, device, fold_dir, DATASET, *, resume_from=None,
-             save_optimizer=False, loss_weights='class_balance', loss='bce', dice_options=None):
+             save_optimizer=False, loss_weights='class_balance', loss='bce', dice_options=None, optimizer='sgd',
+             optimizer_options=None, clip_grad_norm=None):
     """Reference signature (trainer.py:15) plus keyword-only extensions, all off by default so that the files
     written are exactly the reference's: resume_from = a checkpoint made by checkpoint.py (weights + SGD momentum +
     scheduler + epoch), save_optimizer = also write models/checkpoint_latest.pth every epoch (both SURVEY N4);
@@ -163,15 +198,26 @@ def training(unet, train_loader, val_loader, epochs, batch_size, device, fold_di
     dice_options = a dict of smooth, batch, include_background, ce_weight, dice_weight (dice_step's; unknown keys raise); the
     weights default to (0, 1) for 'dice' and (1, 1) for 'ce_dice'.  Under dp.DataParallel every rank forms the Dice
     coefficients on its own shard of the batch, then the gradients are averaged: batch=True means the rank's batch, not the
-    global one."""
+    global one.
+    optimizer = 'sgd' (the reference's SGD with momentum 0.99, the default), 'adam' or 'adamw' (optim.Adam / optim.AdamW, one
+    unet_adam_step launch per step); optimizer_options = a dict of lr, momentum ('sgd') or lr, betas, eps, weight_decay ('adam',
+    'adamw'); unknown keys raise.  lr defaults to 1e-4 for all three: a choice, not a tuned value; the scheduler is the same.
+    clip_grad_norm = None, or max_norm > 0: the global 2-norm of the gradients is formed on the device after backward
+    (optim.clip_grad_norm_, no host sync) and the gradients are scaled by min(1, max_norm / (norm + 1e-6)): inside the Adam
+    pass for 'adam' / 'adamw', in place before the update for 'sgd'.  Under dp.DataParallel the norm is that of the reduced
+    gradients, the same bits on every rank.  resume_from a checkpoint written with another kind of optimiser raises
+    ValueError (checkpoint.load_checkpoint); with save_optimizer the Adam state (step, exp_avg, exp_avg_sq) is saved and a
+    resumed run is the interrupted one, as for SGD."""
     n_classes = getattr(unet, 'n_classes', 2)
     check_loss_options(n_classes, loss, loss_weights)
     dice_kw = dice_step_options(loss, dice_options)
+    optimizer_kw = check_optimizer_options(optimizer, optimizer_options, clip_grad_norm)
+    fused_clip = optimizer != 'sgd'                             # Adam takes the clipping coefficient inside its own pass
     weight_fn = _LOSS_WEIGHTS[loss_weights]
     loss_kind = loss
     when_to_stop, goal = _goal_for(DATASET)
 
-    optimizer = hip_optim.SGD(unet.parameters(), lr=0.0001, momentum=0.99)
+    optimizer = _OPTIMIZERS[optimizer][0](unet.parameters(), **optimizer_kw)
     scheduler = torch.optim.lr_scheduler.ReduceLROnPlateau(optimizer, mode='min', factor=0.1, patience=30,
                                                            threshold=1e-3, threshold_mode='rel', eps=1e-7)
     my_patience = 0
@@ -211,7 +257,14 @@ def training(unet, train_loader, val_loader, epochs, batch_size, device, fold_di
             optimizer.zero_grad()
             preds, loss, labels = _step_loss(unet, images, labels, device, True, weight_fn, loss_kind, step == 0, dice_kw)
             loss.backward()
-            optimizer.step()
+            if clip_grad_norm is None:
+                optimizer.step()
+            else:
+                _, coef = hip_optim.clip_grad_norm_(unet.parameters(), clip_grad_norm, scale=not fused_clip)
+                if fused_clip:
+                    optimizer.step(grad_scale=coef)
+                else:
+                    optimizer.step()
             total_loss += loss.detach()
             if train_eval is None:                              # Q5: first sample of the epoch only
                 train_eval = _first_sample_metrics(preds, labels)

@@ -297,6 +297,38 @@ int unet_sgd_momentum(void *const *params, const void *const *grads, void *const
                       const size_t *numel, int n, float lr, float mu, int first_step,
                       void *stream);
 
+/* L3 with an adaptive update (adam.hip): Adam (decoupled = 0, L2 decay) and AdamW (decoupled = 1) over n <= UNET_N_PARAMS fp32
+ * tensors, torch.optim.Adam / AdamW without amsgrad and maximize.  Pointer tables and numel are HOST arrays; step >= 1 counts
+ * this update, eps > 0, 0 <= beta < 1.  Per element, every operation rounded once to fp32, in this order:
+ *    1  g = g * c                        only if grad_scale_dev != NULL: c = the one device float it points to
+ *    2  g = g + wd * p                   decoupled = 0 and wd != 0
+ *       p = p * decay                    decoupled = 1 and wd != 0;  decay = 1 - lr wd
+ *    3  m = m + om1 * (g - m)            om1 = 1 - beta1
+ *    4  v = beta2 * v + om2 * (g * g)    om2 = 1 - beta2
+ *    5  d = sqrt(v) * rbc2 + eps         rbc2 = 1 / sqrt(1 - beta2^step)
+ *    6  p = p - step_size * (m / d)      step_size = lr / (1 - beta1^step)
+ * om1, om2, decay, rbc2 and step_size are formed on the host in double from the fp32 arguments and rounded to fp32 once each.
+ * With step == 1, m and v count as 0 and exp_avg / exp_avg_sq are written, never read (as unet_sgd_momentum's first_step).
+ * Subnormals are kept; sqrt and the division are correctly rounded.  The gradients are not written.  16 B read and 12 B
+ * written per element (8 B read at step 1).  Non-finite values propagate as IEEE has them. */
+int unet_adam_step(void *const *params, const void *const *grads, void *const *exp_avg, void *const *exp_avg_sq,
+                   const size_t *numel, int n, float lr, float beta1, float beta2, float eps, float weight_decay,
+                   int decoupled, long step, const void *grad_scale_dev, void *stream);
+/* The global gradient norm and torch.nn.utils.clip_grad_norm_'s coefficient, without a host sync and without float atomics.
+ *   unet_grad_sumsq_partials : host only: the number of 4096-element chunks of the n tensors (each tensor's last one may be
+ *                      short; a zero-size tensor has none) = the fp64 partials unet_grad_sumsq writes for them.
+ *   unet_grad_sumsq  : partials[partial_offset + c] = the sum of g^2 over chunk c of the call (fp64; exact squares, a fixed
+ *                      order per lane, then wave, then block).  Several calls at increasing offsets cover more than
+ *                      UNET_N_PARAMS tensors.
+ *   unet_grad_norm_finish : one workgroup adds the n_partials partials in a fixed order in fp64 and writes two fp32:
+ *                      out2[0] = (float)sqrt(sum), out2[1] = min(1, max_norm / (out2[0] + 1e-6)) in fp32; max_norm > 0.
+ *                      A NaN norm gives a NaN coefficient, an infinite one 0.
+ *   unet_grads_scale : g = g * c in place, c = the device float at scale_dev (for updates that do not take it themselves). */
+size_t unet_grad_sumsq_partials(const size_t *numel, int n);
+int unet_grad_sumsq(const void *const *grads, const size_t *numel, int n, void *partials, size_t partial_offset, void *stream);
+int unet_grad_norm_finish(const void *partials, size_t n_partials, float max_norm, void *out2, void *stream);
+int unet_grads_scale(void *const *grads, const size_t *numel, int n, const void *scale_dev, void *stream);
+
 /* ---- callers either side of the path; fp32 images [B,H,W], int64 labels ----------
  * N2 overlap-tile front end, replaces mirror_transform + the [0,1] normalisation (data.py:184-188,
  * :249-277): out[b,0,Y,X] = x[b, r(Y), r(X)] with the reference's asymmetric reflection (top/left band
