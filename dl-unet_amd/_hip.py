@@ -154,6 +154,10 @@ _SIGS = {
     "unet_elastic_grid": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_double, vp, vp]),
     "unet_elastic_grid_sample": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]),
     "unet_normalise01": (C.c_int, [vp, C.c_int, C.c_size_t, vp, vp]),
+    "unet_grey_scratch_bytes": (C.c_size_t, [C.c_int, C.c_size_t]),
+    "unet_grey_vary": (C.c_int, [vp, vp, C.c_int, C.c_size_t, C.c_longlong, C.POINTER(C.c_double), vp, C.c_ulonglong, C.c_ulonglong,
+                                 C.c_int, vp, vp]),
+    "unet_grey_normals": (C.c_int, [C.c_ulonglong, C.c_ulonglong, C.c_longlong, C.c_size_t, C.c_size_t, vp, vp]),
     "unet_conv3x3_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "unet_conv3x3_fwd": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int,
                                    vp, vp, C.c_int, C.c_int, vp, vp, vp]),

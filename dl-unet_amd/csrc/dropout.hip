@@ -9,6 +9,7 @@
 //                         element is exactly 0: the drop is already in their masks - DESIGN.md section 4k)
 //   dropout_mask_kernel   the keep flags as bytes (tests)
 #include "elem.hpp"
+#include "philox.hpp"
 #include "../../include/unet_hip.h"
 
 namespace unet {
@@ -33,20 +34,11 @@ static DropKey drop_key(float p, unsigned long long seed, unsigned long long ste
     return k;
 }
 
-// Philox4x32-10 (Salmon et al., SC'11) of counter (g, step | site) under key seed: the four words decide the four elements
+// Philox4x32-10 (philox.hpp) of counter (g, step | site) under key seed: the four words decide the four elements
 // 4g .. 4g+3, i.e. four consecutive channels of one pixel
-struct u32x4 { unsigned v[4]; };
 __device__ __forceinline__ u32x4 philox4x32_10(unsigned long long g, const DropKey &k)
 {
-    unsigned c0 = (unsigned)g, c1 = (unsigned)(g >> 32), c2 = k.c2, c3 = k.c3, k0 = k.k0, k1 = k.k1;
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned long long p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
-        const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1;
-        c1 = (unsigned)p1; c3 = (unsigned)p0; c0 = n0; c2 = n2;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    return u32x4{{c0, c1, c2, c3}};
+    return philox4x32_10((unsigned)g, (unsigned)(g >> 32), k.c2, k.c3, k.k0, k.k1);
 }
 
 // the four channels at element index idx (a multiple of 4), dropped: one fp32 multiply per kept element

@@ -8,6 +8,8 @@
   grid_displacements(rs, B, G, s)    -                 the paper's random displacement vectors on a coarse G x G grid
   elastic_grid(images, disp, a)      -                 the paper's elastic deformation: that grid, bicubic, bilinear warp
   reflect_rotate_crop(images, deg)   data.py:106-125   reflect pad + cubic-spline rotation + centre crop, fused (N1)
+  grey_parameters(rs, B, ...)        -                 the random gamma, contrast, brightness, noise level, inversion per sample
+  grey_variation(images, params)     -                 the paper's grey-value variation: those, applied in one fused pass
   augment(image, target, ...)        data.py:97-135    ImageDataset.__getitem__ after the file reads, on the device
   preprocess_gt(img)                 data.py:195-221   borders carved between touching cells of an instance image
   binary_target(img)                 data.py:63-64     preprocess_gt + cv.threshold(gt, 0, 255): the {0,255} training target
@@ -195,9 +197,126 @@ def reflect_rotate_crop(images, angles_deg, input_size=None, levels=255):
     return out[0] if single else out
 
 
-def _grid_stage(both, crop, disp, a, levels):
+MAX_GREY_SAMPLES = 64      # UNET_GREY_MAX_SAMPLES
+GREY_NO_CLIP = 1           # UNET_GREY_NO_CLIP
+GREY_IDENTITY = (1.0, 1.0, 0.0, 0.0, 0.0)      # gamma, contrast, brightness, sigma, invert: every stage skipped
+
+
+def grey_parameters(random_state, B, *, gamma=(0.7, 1.5), contrast=(0.75, 1.25), brightness=(-0.1, 0.1), noise=(0.0, 0.05), p_invert=0.0):
+    """The random input of grey_variation: float64 [B,5], row b = (gamma, contrast, brightness, sigma, invert) of sample b,
+    drawn from random_state (a numpy RandomState).  The draw order is the contract: sample after sample, and for one sample
+        gamma      = exp(random_state.uniform(log(gamma[0]), log(gamma[1])))     log-uniform: 0.7 and 1 / 0.7 are equally likely
+        contrast   = random_state.uniform(contrast[0], contrast[1])
+        brightness = random_state.uniform(brightness[0], brightness[1])
+        sigma      = random_state.uniform(noise[0], noise[1])
+        invert     = 1.0 if random_state.uniform(0.0, 1.0) < p_invert else 0.0
+    - five uniform draws per sample and nothing else, whatever the ranges are: a degenerate range (v, v) still consumes its
+    draw (and gives v), so the generator's state after B samples does not depend on the ranges."""
+    if random_state is None:
+        raise ValueError("grey_parameters draws from a numpy RandomState; got None")
+    ranges = {"gamma": gamma, "contrast": contrast, "brightness": brightness, "noise": noise}
+    for name, r in ranges.items():
+        if len(r) != 2 or not np.all(np.isfinite(r)) or r[0] > r[1]:
+            raise ValueError("grey_parameters: %s must be a finite range (lo, hi) with lo <= hi, got %r" % (name, r))
+    if gamma[0] <= 0 or contrast[0] < 0 or noise[0] < 0 or not 0.0 <= p_invert <= 1.0:
+        raise ValueError("grey_parameters: need gamma > 0, contrast >= 0, noise >= 0 and 0 <= p_invert <= 1")
+    out = np.empty((int(B), 5), np.float64)
+    for b in range(int(B)):
+        out[b, 0] = np.exp(random_state.uniform(np.log(gamma[0]), np.log(gamma[1])))
+        out[b, 1] = random_state.uniform(contrast[0], contrast[1])
+        out[b, 2] = random_state.uniform(brightness[0], brightness[1])
+        out[b, 3] = random_state.uniform(noise[0], noise[1])
+        out[b, 4] = 1.0 if random_state.uniform(0.0, 1.0) < p_invert else 0.0
+    return out
+
+
+def _grey_rows(params, B, name):
+    """params [B,5] (or [5] for one sample), numpy or tensor -> checked float64 numpy [B,5]"""
+    p = params.detach().cpu().numpy() if torch.is_tensor(params) else np.asarray(params)
+    p = np.ascontiguousarray(p, dtype=np.float64)
+    if p.ndim == 1 and B == 1:
+        p = p[None]
+    if p.shape != (B, 5):
+        raise ValueError("%s: params must be [%d,5] (gamma, contrast, brightness, sigma, invert per sample), got %s" % (name, B, p.shape))
+    if not np.isfinite(p).all():
+        raise ValueError("%s: a parameter is not finite" % name)
+    if (p[:, 0] <= 0).any() or (p[:, 1] < 0).any() or (p[:, 3] < 0).any() or not np.isin(p[:, 4], (0.0, 1.0)).all():
+        raise ValueError("%s: need gamma > 0, contrast >= 0, sigma >= 0 and invert 0 or 1" % name)
+    return p
+
+
+def _grey_run(x, out, rows, seed, step, first_sample, clip, mm):
+    """unet_grey_vary on contiguous device fp32 x, out [B, ...] (out may be x) in chunks of 64 samples; mm [B,2] or None"""
+    B = x.shape[0]
+    n = x[0].numel()
+    if int(first_sample) < 0 or int(first_sample) + B > 2 ** 32 or not 0 <= int(seed) < 2 ** 64 or not 0 <= int(step) < 2 ** 64:
+        raise ValueError("grey variation: seed and step are unsigned 64-bit numbers, the sample index first_sample + b an unsigned 32-bit one")
+    for lo in range(0, B, MAX_GREY_SAMPLES):
+        b = min(MAX_GREY_SAMPLES, B - lo)
+        sc = _hip.scratch("unet_grey", x.device, b, n)
+        arr = (_C.c_double * (5 * b))(*rows[lo:lo + b].ravel().tolist())
+        _hip.run("unet_grey_vary", x.device, _hip.ptr(x[lo:lo + b]), _hip.ptr(out[lo:lo + b]), b, n, int(first_sample) + lo, arr,
+                 None if mm is None else _hip.ptr(mm[lo:lo + b]), int(seed), int(step), 0 if clip else GREY_NO_CLIP, _hip.ptr(sc))
+
+
+def grey_variation(images, params, *, seed=0, step=0, first_sample=0, clip=True, minmax=None, out=None):
+    """Grey-value variation (Ronneberger et al. 3.1; unet_grey_vary in include/unet_hip.h states the arithmetic) of
+    device float32 images [H,W], [B,H,W] or [B,1,H,W], meant for images in [0,1].  params: [B,5] ([5] for one image), row b =
+    (gamma, contrast, brightness, sigma, invert) of sample b, as grey_parameters draws them.  Per sample, in fp64: contrast
+    about the sample's own mean plus brightness, clamped to [0,1]; u^gamma (1 - (1 - u)^gamma with invert); + sigma * z with z
+    standard normal from Philox4x32-10 of (seed, step, first_sample + b, pixel) - no generator state, so equal arguments give
+    equal bits on every run and stream; the clip to [0,1] unless clip=False.  A stage with identity parameters (contrast 1
+    and brightness 0; gamma 1; sigma 0) is skipped.  minmax: device float32 [B,2] = (lo, hi) per sample; (x - lo) / (hi - lo)
+    then runs first, in the same pass.  out: None (a new tensor), or a contiguous tensor of images' shape, which may be images
+    itself.  A NaN pixel stays NaN, and a NaN anywhere in a sample whose contrast or brightness is not the identity makes that
+    whole sample NaN (its mean is).  ValueError on host tensors, other dtypes, and parameters outside gamma > 0, contrast >= 0,
+    sigma >= 0, invert in {0, 1} or not finite; there is no CPU implementation."""
+    if not torch.is_tensor(images) or not images.is_cuda:
+        raise ValueError("grey_variation runs on the HIP device only (unet_grey_vary): move the images to the device first")
+    if images.dtype != torch.float32:
+        raise ValueError("grey_variation takes float32 images, got %s" % images.dtype)
+    if images.dim() not in (2, 3, 4) or (images.dim() == 4 and images.shape[1] != 1) or images.numel() == 0:
+        raise ValueError("grey_variation takes images [H,W], [B,H,W] or [B,1,H,W], got %s" % (tuple(images.shape),))
+    B = 1 if images.dim() == 2 else images.shape[0]
+    rows = _grey_rows(params, B, "grey_variation")
+    if out is None:
+        out = torch.empty(images.shape, dtype=torch.float32, device=images.device)
+    elif (not torch.is_tensor(out) or out.device != images.device or out.dtype != torch.float32 or out.shape != images.shape
+          or not out.is_contiguous()):
+        raise ValueError("grey_variation: out must be a contiguous float32 tensor of the images' shape on their device")
+    if out is images and not images.is_contiguous():
+        raise ValueError("grey_variation: in place needs contiguous images")
+    mm = None
+    if minmax is not None:
+        if not torch.is_tensor(minmax) or minmax.device != images.device or minmax.dtype != torch.float32 or tuple(minmax.shape) != (B, 2):
+            raise ValueError("grey_variation: minmax must be a float32 [%d,2] tensor on the images' device" % B)
+        mm = minmax.contiguous()
+    x = images if out is images else images.contiguous()
+    _grey_run(x.reshape(B, -1), out.reshape(B, -1), rows, seed, step, first_sample, clip, mm)
+    return out
+
+
+def _grey_of(grey, random_state, B, name):
+    """augment's grey argument -> checked [B,5] rows: given, or drawn from random_state by a dict of grey_parameters' ranges"""
+    if isinstance(grey, dict):
+        if random_state is None:
+            raise ValueError("%s(grey={...}) draws the parameters from random_state (a numpy RandomState): pass one, or pass the "
+                             "parameters [B,5]" % name)
+        _grey_ranges(grey, name)
+        grey = grey_parameters(random_state, B, **grey)
+    return _grey_rows(grey, B, name)
+
+
+def _grey_ranges(grey, name):
+    unknown = set(grey) - {"gamma", "contrast", "brightness", "noise", "p_invert"}
+    if unknown:
+        raise ValueError("%s: grey takes the ranges gamma, contrast, brightness, noise and p_invert, got %s" % (name, sorted(unknown)))
+
+
+def _grid_stage(both, crop, disp, a, levels, grey=None):
     """augment's elastic='grid' stage: both [2B,S,S] = the rotated images, then the rotated masks -> (inp [B,S,S] in [0,1],
-    gt [B,crop,crop] int64).  One small upload (the nodes) and the library's two calls; no ATen arithmetic."""
+    gt [B,crop,crop] int64).  One small upload (the nodes) and the library's two calls; no ATen arithmetic.  grey = (rows [B,5],
+    seed, step): unet_grey_vary with the min / max table takes unet_normalise01's place."""
     B, S = both.shape[0] // 2, both.shape[-1]
     dev = both.device
     pad = int((S - crop) / 2)
@@ -207,12 +326,16 @@ def _grid_stage(both, crop, disp, a, levels):
     mm = torch.empty(B, 2, dtype=torch.float32, device=dev)
     _hip.run("unet_elastic_grid_sample", dev, _hip.ptr(both[:B]), _hip.ptr(both[B:]), B, S, _hip.ptr(d), d.shape[2], float(a),
              int(levels), pad, int(crop), _hip.ptr(inp), _hip.ptr(gt), _hip.ptr(mm))
-    _hip.run("unet_normalise01", dev, _hip.ptr(inp), B, S * S, _hip.ptr(mm))
+    if grey is None:
+        _hip.run("unet_normalise01", dev, _hip.ptr(inp), B, S * S, _hip.ptr(mm))
+    else:
+        rows, seed, step = grey
+        _grey_run(inp.reshape(B, -1), inp.reshape(B, -1), rows, seed, step, 0, True, mm)
     return inp, gt
 
 
 def augment(image, target, crop_xy, crop, rot_deg, alpha, sigma, random_state=None, fields=None, levels=255, elastic='field', grid=3,
-            disp=None, a=-0.5):
+            disp=None, a=-0.5, grey=None, grey_seed=0, grey_step=0):
     """What ImageDataset.__getitem__ does to one sample after reading it (data.py:97-135), on the device.  The random draws
     stay with the caller (crop origin from the weighted distribution + jitter, rot_deg from np.arange(0,360,30), the elastic
     fields), so the host RNG sequence can follow the reference's:  crop -> reflect pad + rotate + centre crop -> the same
@@ -225,12 +348,20 @@ def augment(image, target, crop_xy, crop, rot_deg, alpha, sigma, random_state=No
     ignored.  The node displacements are disp ([B,2,G,G], or [2,G,G] for one sample) or, when disp is None,
     grid_displacements(random_state, B, grid, sigma): random_state must then be given, the device generator is not used.
     After the rotation the grid path is two kernels: unet_elastic_grid_sample (warp of image and mask, rounding, crop and
-    threshold of the mask, per-sample min / max) and unet_normalise01."""
+    threshold of the mask, per-sample min / max) and unet_normalise01.
+    grey=None (default) ends there.  grey = parameters [B,5] ([5] for one sample), or a dict of grey_parameters' ranges (e.g.
+    {} for its defaults), adds the grey-value variation of grey_variation as the last stage, with seed grey_seed, step
+    grey_step and the sample's position in the batch as its sample index.  With a dict the parameters are drawn from
+    random_state (required then) after this call's elastic draws.  On the grid path the stage takes unet_normalise01's place
+    (unet_grey_vary normalises in the same pass); on the field path it runs after the normalisation."""
     if elastic not in ('field', 'grid'):
         raise ValueError("augment: elastic is 'field' or 'grid', got %r" % (elastic,))
     if elastic == 'grid' and disp is None and random_state is None:
         raise ValueError("augment(elastic='grid') draws the node displacements from random_state (a numpy RandomState): "
                          "pass one, or pass disp")
+    if isinstance(grey, dict) and random_state is None:
+        raise ValueError("augment(grey={...}) draws the parameters from random_state (a numpy RandomState): pass one, or pass "
+                         "the parameters [B,5]")
     batched = image.dim() == 3
     imgs = image if batched else image[None]
     tgts = target if batched else target[None]
@@ -244,7 +375,9 @@ def augment(image, target, crop_xy, crop, rot_deg, alpha, sigma, random_state=No
     _, S, _ = input_size_compute(img)
     both = reflect_rotate_crop(torch.cat((img, tgt)), angles + angles, S, levels=levels)            # [2B,S,S]: images, then masks
     if elastic == 'grid':
-        inp, gt = _grid_stage(both, crop, grid_displacements(random_state, B, grid, sigma) if disp is None else disp, a, levels)
+        disp = grid_displacements(random_state, B, grid, sigma) if disp is None else disp
+        rows = None if grey is None else (_grey_of(grey, random_state, B, "augment"), grey_seed, grey_step)
+        inp, gt = _grid_stage(both, crop, disp, a, levels, rows)
         if batched:
             return inp[:, None], gt[:, None]
         return inp[0][None], gt[0][None]
@@ -258,6 +391,9 @@ def augment(image, target, crop_xy, crop, rot_deg, alpha, sigma, random_state=No
     gt = (gt[:, pad:crop + pad, pad:crop + pad] > 127).long()
     lo, hi = inp.amin(dim=(1, 2), keepdim=True), inp.amax(dim=(1, 2), keepdim=True)
     inp = (inp - lo) / (hi - lo)
+    if grey is not None:
+        inp = inp.contiguous()
+        _grey_run(inp.reshape(B, -1), inp.reshape(B, -1), _grey_of(grey, random_state, B, "augment"), grey_seed, grey_step, 0, True, None)
     if batched:
         return inp[:, None], gt[:, None]
     return inp[0][None], gt[0][None]
@@ -373,17 +509,28 @@ class CropDataset:
     gt [B,1,crop,crop] int64) on the device - usable as train_loader / val_loader of trainer.training as it is.  The elastic
     fields come from random_state (a numpy RandomState, drawn as the reference's elastic_transform draws them), or from the
     device generator when it is None.  elastic='grid' deforms with the paper's grid x grid displacement grid instead
-    (augment(elastic='grid'): sigma is the nodes' standard deviation in pixels, alpha is ignored, random_state is required)."""
+    (augment(elastic='grid'): sigma is the nodes' standard deviation in pixels, alpha is ignored, random_state is required).
+    grey = a dict of grey_parameters' ranges ({} for its defaults) adds the grey-value variation as augment's last stage: each
+    batch's parameters are drawn from random_state (required) after that batch's elastic draws - rng's sequence is untouched -
+    and its noise is that of (grey_seed, grey_step, position in the batch).  grey_step is a public integer that starts at 0 and
+    advances by one per batch; a resumed run sets it.  grey=None (default) is the reference's pipeline."""
 
     def __init__(self, images, instances, alpha, sigma, crop, batch_size, rng, levels=255, *, random_state=None, skip=10, device=None,
-                 elastic='field', grid=3):
+                 elastic='field', grid=3, grey=None, grey_seed=0):
         if elastic not in ('field', 'grid'):
             raise ValueError("CropDataset: elastic is 'field' or 'grid', got %r" % (elastic,))
         if elastic == 'grid' and random_state is None:
             raise ValueError("CropDataset(elastic='grid') draws the node displacements from random_state (a numpy RandomState)")
         if elastic == 'grid' and int(grid) < 2:
             raise ValueError("CropDataset: a grid of %d nodes per side, need at least 2" % int(grid))
+        if grey is not None:
+            if not isinstance(grey, dict):
+                raise ValueError("CropDataset: grey is None or a dict of grey_parameters' ranges, got %r" % (grey,))
+            if random_state is None:
+                raise ValueError("CropDataset(grey={...}) draws the parameters from random_state (a numpy RandomState)")
+            _grey_ranges(grey, "CropDataset")
         self.elastic, self.grid = elastic, int(grid)
+        self.grey, self.grey_seed, self.grey_step = grey, int(grey_seed), 0
         if device is None:
             device = images.device if torch.is_tensor(images) and images.is_cuda else torch.device("cuda", torch.cuda.current_device())
         self.device = torch.device(device)
@@ -412,5 +559,9 @@ class CropDataset:
         for lo in range(0, N, self.batch_size):
             idx = list(range(lo, min(N, lo + self.batch_size)))
             draws = [self.draw(i) for i in idx]
+            step = self.grey_step
+            if self.grey is not None:
+                self.grey_step += 1
             yield augment(self.image[idx], self.target[idx], [d[0] for d in draws], self.crop, [d[1] for d in draws], self.alpha,
-                          self.sigma, random_state=self.random_state, levels=self.levels, elastic=self.elastic, grid=self.grid)
+                          self.sigma, random_state=self.random_state, levels=self.levels, elastic=self.elastic, grid=self.grid,
+                          grey=self.grey, grey_seed=self.grey_seed, grey_step=step)

@@ -803,6 +803,38 @@ int unet_elastic_grid(const void *planes, int P, int B, int H, int W, const void
 int unet_elastic_grid_sample(const void *img, const void *mask, int B, int S, const void *grid_f64, int G, double a, int levels,
                              int pad, int crop, void *out_img, void *out_gt_i64, void *minmax, void *stream);
 int unet_normalise01(void *x, int B, size_t n, const void *minmax, void *stream);
+/* Grey-value variation of training samples (Ronneberger et al. §3.1 names it beside shift, rotation and deformation; the
+ * reference has none).  x fp32 [B][n] -> out fp32 [B][n], out == x (in place) or disjoint from x.  Sample b has five
+ * HOST parameters params_host[5 b ..]: gamma > 0, contrast >= 0, brightness, sigma >= 0, invert (0 or 1), all finite.  Per
+ * pixel i of sample b, the stages in this order; everything after the normalisation is fp64, narrowed to fp32 once at the store:
+ *   normalise  only with minmax (DEVICE fp32 [B][2], as unet_elastic_grid_sample leaves it): x <- (x - lo) / (hi - lo) in
+ *              fp32 with true division, bit-equal to calling unet_normalise01 first
+ *   mean       m = (sum_i x[i]) / n, an fp64 sum in a fixed order (per-workgroup partials combined in index order, no
+ *              floating-point atomics); formed only for a sample whose affine stage runs
+ *   affine     u = (x - m) * contrast + m + brightness, then u = min(max(u, 0), 1): contrast about the sample's own mean
+ *   gamma      u = u^gamma, or 1 - (1 - u)^gamma with invert; meant for u in [0,1] (pow of a negative base is NaN)
+ *   noise      u += sigma * z, z standard normal by Box-Muller from Philox4x32-10:
+ *                counter = (i >> 2, first_sample + b, step lo, step hi),  key = (seed lo, seed hi ^ 0x47524559)
+ *                words 0, 1 -> pixels 4g (r cos t) and 4g+1 (r sin t), words 2, 3 -> 4g+2 and 4g+3, with
+ *                u1 = (w + 0.5) 2^-32 of the first word, u2 likewise of the second, r = sqrt(-2 log u1), t = 2 pi u2
+ *   clip       y = min(max(u, 0), 1) unless flags has UNET_GREY_NO_CLIP
+ * A stage whose parameters are the identity is skipped for that sample, not computed: contrast == 1 && brightness == 0,
+ * gamma == 1, sigma == 0.  Identity parameters on a [0,1] image return it bit for bit, and a sample without noise never runs
+ * Philox.  A NaN is no special case: min and max here keep it, 0/0 of a constant sample's normalisation stays NaN, and a NaN
+ * mean makes every pixel of that sample's affine stage NaN.
+ * At most UNET_GREY_MAX_SAMPLES samples per call; first_sample is the global index of sample 0, so a batch done in chunks
+ * equals one call.  Two launches when any sample needs its mean (partial sums, then the stages), one otherwise; no host sync,
+ * bit-identical on every run and stream.  The parameters are checked on the host before anything is enqueued.  1 <= n < 2^31,
+ * first_sample + B <= 2^32.  scratch >= unet_grey_scratch_bytes(B, n); it may be NULL when no sample's affine stage runs.
+ *   unet_grey_normals : out_f64 DEVICE fp64 [n] = z of pixels [first, first + n) of global sample `sample` (tests).            */
+#define UNET_GREY_MAX_SAMPLES 64
+#define UNET_GREY_NO_CLIP 1
+size_t unet_grey_scratch_bytes(int B, size_t n);
+int unet_grey_vary(const void *x, void *out, int B, size_t n, long long first_sample, const double *params_host,
+                   const void *minmax_or_null, unsigned long long seed, unsigned long long step, int flags, void *scratch,
+                   void *stream);
+int unet_grey_normals(unsigned long long seed, unsigned long long step, long long sample, size_t first, size_t n, void *out_f64,
+                      void *stream);
 
 /* ---- per-op entry points (NHWC fp32), used by the unit tests ---------------------------------
  * Each replaces the ATen op dispatched at the cited line.  w_* are in reference layout.    */
