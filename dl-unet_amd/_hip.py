@@ -110,6 +110,10 @@ _SIGS = {
     "unet_cell_hulls": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_longlong, vp, vp, vp, vp, vp, vp, vp, vp]),
     "unet_cell_contacts_scratch_bytes": (C.c_size_t, [C.c_int, C.c_size_t]),
     "unet_cell_contacts": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, vp, vp, vp, vp, vp, vp]),
+    "unet_mask_boundary": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
+    "unet_surface_sums_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "unet_surface_sums": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong,
+                                    C.c_longlong, C.POINTER(C.c_int), C.c_int, vp, vp, vp, vp, vp]),
     "unet_instance_overlap_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_size_t]),
     "unet_instance_overlap": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, vp, vp, vp, vp, vp, vp, vp]),
     "unet_partition_pairs_scratch_bytes": (C.c_size_t, [C.c_int, C.c_size_t]),

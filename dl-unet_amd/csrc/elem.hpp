@@ -1,5 +1,6 @@
 // elem.hpp — what the HBM-bound kernels (direct.hip, multiclass.hip, dice.hip, tile.hip, aux.hip) and the data-path files (label.hip, wmap.hip,
-// instances.hip, prepare.hip, grow.hip, elastic.hip, clean.hip, warp.hip, and through sweep.hpp geo.hip, shape.hip, flood.hip) share:
+// instances.hip, prepare.hip, grow.hip, elastic.hip, clean.hip, warp.hip, through sweep.hpp geo.hip, shape.hip, flood.hip, and
+// through dm.hpp shape.hip and boundary.hip) share:
 //   device : 4 consecutive channels of an activation tensor stored as fp32 (16 B) or bf16 (8 B, arithmetic mode 2), read /
 //            written as 4 floats; the sum / min / max of one value per lane over a wave; the min and max of one value per thread
 //            over a block; the sum of one value per thread over a 256-thread block, with the max of a second one (the finish

@@ -5,15 +5,12 @@
 // The distance map.  d2(p) is the exact squared Euclidean distance from a region pixel (mask != 0) to the nearest pixel outside
 // the region, 0 outside it.  edge 0 ('ignore'): there is nothing past the image, and an image without a pixel outside the region
 // gets H^2 + W^2 everywhere; edge 1 ('background'): every pixel past the image is outside the region.
-//   1. dm_cols   grow.hip's column pass without ids: a downward and an upward sweep leave g, the row distance to the nearest pixel
-//                of the column outside the region (DM_FAR when the column has none; with edge 1 the pixels above row 0 and below
-//                row H - 1 count).  A sweep is a chain of H dependent steps, so a column is cut into four segments, one wave each:
-//                every thread first finds the first and last outside row of its segment (independent loads), the segments swap
-//                them through LDS, and each sweeps its rows from the distance its neighbours hand it
-//   2. dm_rows   one thread per pixel: d2 = min over x' of g(x')^2 + (x - x')^2, by a scan outwards from x' = x that ends once
-//                dx^2 reaches the running minimum (every column further out offers at least dx^2).  The minimum starts at g(x)^2,
-//                with edge 1 at min(g(x)^2, (x + 1)^2, (W - x)^2), so a pixel at distance d looks at about 2 d columns.  There is
-//                no id and no tie rule here, which is what grow_rows' brute force is for.
+//   1. dm_cols   dm.hpp's column pass (grow.hip's without ids; boundary.hip runs the same code on contours), the sites being the
+//                pixels outside the region: g is the row distance to the nearest of them in the column (DM_FAR when the column
+//                has none; with edge 1 the pixels above row 0 and below row H - 1 count)
+//   2. dm_rows   one thread per pixel: d2 = min over x' of g(x')^2 + (x - x')^2, by dm.hpp's scan outwards from x' = x.  The
+//                minimum starts at g(x)^2, with edge 1 at min(g(x)^2, (x + 1)^2, (W - x)^2), so a pixel at distance d looks at
+//                about 2 d columns.  There is no id and no tie rule here, which is what grow_rows' brute force is for.
 //
 // Grey reconstruction by dilation, 4-connected: R is the least function on the region with R >= min(marker, under), R <= under and
 // R(p) >= min(under(p), R(n)) for every region 4-neighbour n, i.e. the fixed point of
@@ -35,60 +32,20 @@
 // Coherence (label.hip's rule): every kernel reads what an earlier kernel wrote (rc_sweep: sweep.hpp); in dm_cols a thread re-reads
 // only its own column.  The counters are only touched by agent-scope adds.
 #include "sweep.hpp"
+#include "dm.hpp"
 #include <cmath>
 #include "../../include/unet_hip.h"
 
 namespace unet {
 
-static constexpr int DM_EDGE = 32767;                          // H, W <= DM_EDGE: H^2 + W^2 < 2^31
-static constexpr int DM_FAR = 46340;                           // "no pixel outside the region in this column": DM_FAR^2 is above
-                                                               // every H^2 + W^2 and DM_FAR^2 + dx^2 < 2^32
-static constexpr unsigned DM_FAR2 = (unsigned)DM_FAR * DM_FAR;
-static constexpr int DM_SEGS = 4;                              // row segments of a column, one wave each, in dm_cols
 static constexpr int RC_TOP = 1 << 30;                         // values are in [0, RC_TOP]
 
+// dm.hpp's site test of the distance map: a pixel outside the region
 template <typename T>
-__global__ __launch_bounds__(256) void dm_cols_kernel(const T *__restrict__ mask, int H, int W, int edge, int *__restrict__ g)
-{
-    __shared__ int first[DM_SEGS][64], last[DM_SEGS][64];      // per segment and column: its first and last row outside the region
-    const int lane = threadIdx.x & 63, seg = threadIdx.x >> 6;
-    const int x = blockIdx.x * 64 + lane;
-    const bool live = x < W;
-    const int rows = (H + DM_SEGS - 1) / DM_SEGS, y0 = min(seg * rows, H), y1 = min(y0 + rows, H);
-    const size_t o = (size_t)blockIdx.y * H * W + (live ? x : 0);
-    const T *M = mask + o;
-    int *G = g + o;
-    int lo = -1, hi = -1;
-    if (live) {
-#pragma unroll 8
-        for (int y = y0; y < y1; ++y) {                        // no value depends on the one before: the loads overlap
-            const bool out = M[(size_t)y * W] == 0;
-            lo = out && lo < 0 ? y : lo;
-            hi = out ? y : hi;
-        }
-    }
-    first[seg][lane] = lo;
-    last[seg][lane] = hi;
-    __syncthreads();
-    if (!live) return;
-    int d = edge ? y0 : DM_FAR;                                // the distance in row y0 - 1: edge 1 has row -1 outside the region
-    for (int s = seg - 1; s >= 0; --s)
-        if (last[s][lane] >= 0) { d = y0 - 1 - last[s][lane]; break; }
-#pragma unroll 8
-    for (int y = y0; y < y1; ++y) {                            // downward: the nearest pixel outside the region at or above y
-        d = M[(size_t)y * W] == 0 ? 0 : d >= DM_FAR ? DM_FAR : d + 1;
-        G[(size_t)y * W] = d;
-    }
-    d = edge ? H - y1 : DM_FAR;                                // the distance in row y1: edge 1 has row H outside the region
-    for (int s = seg + 1; s < DM_SEGS; ++s)
-        if (first[s][lane] >= 0) { d = first[s][lane] - y1; break; }
-#pragma unroll 8
-    for (int y = y1 - 1; y >= y0; --y) {                       // upward: the nearest at or below y, merged with the word above
-        const int dn = G[(size_t)y * W];                       // this thread's own store
-        d = dn == 0 ? 0 : d >= DM_FAR ? DM_FAR : d + 1;
-        G[(size_t)y * W] = min(dn, d);
-    }
-}
+struct DmOutside {
+    const T *mask;
+    __device__ __forceinline__ bool operator()(size_t e) const { return mask[e] == 0; }
+};
 
 __global__ __launch_bounds__(256) void dm_rows_kernel(const int *__restrict__ g, int H, int W, int edge, int *__restrict__ d2)
 {
@@ -102,13 +59,7 @@ __global__ __launch_bounds__(256) void dm_rows_kernel(const int *__restrict__ g,
         const unsigned l = (unsigned)(x + 1), r = (unsigned)(W - x);
         best = min(best, min(l * l, r * r));
     }
-    for (int dx = 1; ; ++dx) {
-        const unsigned dd = (unsigned)dx * dx;
-        const int l = x - dx, r = x + dx;
-        if (dd >= best || (l < 0 && r >= W)) break;            // every column further out offers at least dd
-        if (l >= 0) { const unsigned v = (unsigned)G[l]; best = min(best, v * v + dd); }
-        if (r < W) { const unsigned v = (unsigned)G[r]; best = min(best, v * v + dd); }
-    }
+    best = dm_row_best(G, x, W, best);
     d2[row + x] = best >= DM_FAR2 ? H * H + W * W : (int)best; // no pixel outside the region in the whole image
 }
 
@@ -258,10 +209,10 @@ int unet_distance_map(const void *mask, int mask_dtype, int B, int H, int W, int
     SH_SIZE_CHECK("unet_distance_map");
     hipStream_t st = (hipStream_t)stream;
     const dim3 cols(cdiv(W, 64), B);
-    if (mask_dtype == 0) hipLaunchKernelGGL(dm_cols_kernel<long long>, cols, dim3(256), 0, st, (const long long *)mask, H, W, edge, (int *)scratch);
-    else if (mask_dtype == 1) hipLaunchKernelGGL(dm_cols_kernel<float>, cols, dim3(256), 0, st, (const float *)mask, H, W, edge, (int *)scratch);
-    else if (mask_dtype == 2) hipLaunchKernelGGL(dm_cols_kernel<int>, cols, dim3(256), 0, st, (const int *)mask, H, W, edge, (int *)scratch);
-    else hipLaunchKernelGGL(dm_cols_kernel<unsigned char>, cols, dim3(256), 0, st, (const unsigned char *)mask, H, W, edge, (int *)scratch);
+    if (mask_dtype == 0) hipLaunchKernelGGL(dm_cols_kernel<DmOutside<long long>>, cols, dim3(256), 0, st, DmOutside<long long>{(const long long *)mask}, H, W, edge, (int *)scratch);
+    else if (mask_dtype == 1) hipLaunchKernelGGL(dm_cols_kernel<DmOutside<float>>, cols, dim3(256), 0, st, DmOutside<float>{(const float *)mask}, H, W, edge, (int *)scratch);
+    else if (mask_dtype == 2) hipLaunchKernelGGL(dm_cols_kernel<DmOutside<int>>, cols, dim3(256), 0, st, DmOutside<int>{(const int *)mask}, H, W, edge, (int *)scratch);
+    else hipLaunchKernelGGL(dm_cols_kernel<DmOutside<unsigned char>>, cols, dim3(256), 0, st, DmOutside<unsigned char>{(const unsigned char *)mask}, H, W, edge, (int *)scratch);
     hipLaunchKernelGGL(dm_rows_kernel, dim3(cdiv(W, 256), H, B), dim3(256), 0, st, (const int *)scratch, H, W, edge, (int *)d2_i32);
     HIP_TRY(hipGetLastError());
     return 0;

@@ -28,6 +28,10 @@ renumbers cells by any decision taken on those rows (unet_remap_labels).
 cell_hulls, hull_props, cell_neighbours and neighbour_counts measure what that table cannot see: the convex hull of every cell
 with its area and calliper widths as exact integers (unet_cell_hulls), solidity and the Feret diameters formed from them on the
 host, and the list of touching pairs of cells with the length of their common border (unet_cell_contacts).
+mask_boundary, surface_sums, scores_from_surface and boundary_scores score a mask by where its contour lies: the contour of a
+region (unet_mask_boundary), per image and direction the exact integers and the fp64 sum of the distances from one contour to the
+other (unet_surface_sums), and the Hausdorff distance, its percentile, the average symmetric surface distance and the normalised
+surface Dice formed from them on the host.
 link_frames, tracks_from_links and track_cells carry the instance maps of a time-lapse across frames: for every cell the cell of the
 frame before that it overlaps most (unet_link_frames), the tracks, divisions and the Cell Tracking Challenge's res_track.txt table
 formed from those links on the host, and the maps relabelled by track on the device (unet_remap_labels).
@@ -1315,6 +1319,176 @@ def shape_seeds(mask, h=2.0, *, min_radius=0.0, edge='ignore', connectivity=4):
     _hip.run("unet_shape_maxima", dev, _hip.ptr(r1), _hip.ptr(r2), B, H, W, rq, _hip.ptr(peaks))
     seeds, n = label_cells(peaks, connectivity=connectivity)
     return (seeds[0] if mask.dim() == 2 else seeds), n
+
+
+# ---- boundary scores: Hausdorff, its percentile, surface distance, surface Dice -------------------------------------------
+
+SurfaceSums = collections.namedtuple("SurfaceSums", "record d2_pred d2_gt t2 q_num q_den")
+BoundaryScores = collections.namedtuple("BoundaryScores", "hausdorff hd_percentile assd nsd precision recall boundary_f1 n_pred n_gt")
+SURFACE_TOLERANCES = 4                                                 # thresholds of one unet_surface_sums call
+SURFACE_Q_DEN = 1 << 20                                                # its percentile is q_num / q_den with q_den below this
+
+
+def _boundary_rules(name, select, connectivity, edge):
+    _check_connectivity(name, connectivity)
+    if edge not in _EDGES:
+        raise ValueError("%s: edge must be 'ignore' or 'background', got %r" % (name, edge))
+    if select is None:
+        return -1
+    if isinstance(select, bool) or not isinstance(select, (int, np.integer)) or not 0 <= select < 1 << 31:
+        raise ValueError("%s: select must be None or a class index in [0, 2^31), got %r" % (name, select))
+    return int(select)
+
+
+def _boundary_masks(name, entry, *masks):
+    """The checks of the boundary ops on one or two masks: tensors (NotImplementedError), rank, dtype, equal shapes, sizes
+    (ValueError, on any device), then the device (NotImplementedError).  Returns [(contiguous [B,H,W], dtype code)]."""
+    if not all(torch.is_tensor(m) for m in masks):
+        raise NotImplementedError("%s takes tensors on the HIP device (%s); there is no CPU implementation" % (name, entry))
+    for m in masks:
+        if m.is_complex():
+            raise ValueError("%s takes masks of a real dtype, got %s" % (name, m.dtype))
+    if any(m.shape != masks[0].shape for m in masks):
+        raise ValueError("%s takes masks of equal shape, got %s" % (name, ", ".join(str(tuple(m.shape)) for m in masks)))
+    planes = [_planes(name, m) for m in masks]
+    _shape_sizes(name, *planes[0].shape)
+    _device_only(name, entry, *masks)
+    return [_int_code(p, uint8_ok=True) for p in planes]
+
+
+def mask_boundary(mask, *, select=None, connectivity=4, edge='background'):
+    """The contour of a mask [H,W] or [B,H,W] on a HIP device (unet_mask_boundary): uint8 of the mask's shape, 1 on the region
+    pixels that have a neighbour outside the region, 0 elsewhere.  The region is mask != 0, with select=k it is mask == k (the
+    class-k region of a label map).  connectivity 4 or 8: which neighbours count.  edge='background' (the default; what
+    scipy.ndimage.binary_erosion(border_value=0) and MONAI's get_mask_edges do): pixels past the image are outside the region, so
+    region pixels on the frame are contour; edge='ignore': pixels past the image are nothing.  Nothing is read back.  A bad
+    connectivity, edge, select, rank or size raise ValueError; host tensors raise NotImplementedError (no CPU path)."""
+    k = _boundary_rules("mask_boundary", select, connectivity, edge)
+    ((mk, code),) = _boundary_masks("mask_boundary", "unet_mask_boundary", mask)
+    import _hip
+    B, H, W = mk.shape
+    out = torch.empty(B, H, W, dtype=torch.uint8, device=mk.device)
+    _hip.run("unet_mask_boundary", mk.device, _hip.ptr(mk), code, k, B, H, W, connectivity, _EDGES[edge], _hip.ptr(out))
+    return out[0] if mask.dim() == 2 else out
+
+
+def _surface_fraction(name, what, v):
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating, fractions.Fraction)) or not math.isfinite(v):
+        raise ValueError("%s: %s must be a finite number, got %r" % (name, what, v))
+    return fractions.Fraction(v.item() if isinstance(v, np.generic) else v)
+
+
+def _percentile_fraction(name, percentile):
+    """percentile in [0, 100] -> q = q_num / q_den exactly; a float whose binary value needs q_den >= 2^20 (99.9) is read by its
+    shortest decimal form (999 / 1000), and only past that rounded to the nearest fraction with a smaller denominator."""
+    p = _surface_fraction(name, "percentile", percentile)
+    if not 0 <= p <= 100:
+        raise ValueError("%s: percentile must be in [0, 100], got %r" % (name, percentile))
+    q = p / 100
+    if q.denominator >= SURFACE_Q_DEN and isinstance(percentile, (float, np.floating)):
+        q = fractions.Fraction(repr(float(percentile))) / 100
+    if q.denominator >= SURFACE_Q_DEN:
+        q = q.limit_denominator(SURFACE_Q_DEN - 1)
+    return q.numerator, q.denominator
+
+
+def surface_sums(pred, gt, *, tolerances=(1.0,), percentile=95, select=None, connectivity=4, edge='background', return_maps=False):
+    """What the boundary scores of a predicted mask against the ground truth are formed from, on the device (unet_surface_sums):
+    pred, gt [H,W] or [B,H,W] of equal shape, of any dtype split_cells takes.  Region, contour, connectivity, edge and select as
+    mask_boundary (select applies to both masks).  For both directions, pred -> gt (index 0) and gt -> pred (index 1), with d2(p) the
+    exact squared Euclidean distance from contour pixel p to the nearest pixel of the other contour:
+      record   int64 [B, 2, 10] ([2, 10] for a single image): n = the contour's pixels, max d2, lo, hi, rem (the two order statistics
+               of d2 around the percentile and the numerator of the interpolation weight), the pixels with d2 <= T2[i] for up to 4
+               tolerances (T2 = floor(tolerance^2), exactly), and, as the bits of word 9, the fp64 sum of sqrt(d2)
+      d2_pred, d2_gt   with return_maps: int32 of the masks' shape, d2 on the contour of pred (gt), -1 elsewhere; else None
+      t2, q_num, q_den   the squared tolerances and the percentile as the exact fraction the device used (host values)
+    tolerances are in pixels.  percentile is a number in [0, 100].  Nothing is read back; every word is the same in every run.
+    scores_from_surface forms the scores.  More than 4 tolerances, a negative or non-finite one, a percentile outside [0, 100], a
+    bad connectivity, edge or select, shapes that differ and sizes distance_map refuses raise ValueError; host tensors raise
+    NotImplementedError (no CPU path)."""
+    k = _boundary_rules("surface_sums", select, connectivity, edge)
+    tol = tuple(tolerances)
+    if len(tol) > SURFACE_TOLERANCES:
+        raise ValueError("surface_sums: at most %d tolerances, got %d" % (SURFACE_TOLERANCES, len(tol)))
+    t2 = []
+    for t in tol:
+        f = _surface_fraction("surface_sums", "a tolerance", t)
+        if f < 0:
+            raise ValueError("surface_sums: a tolerance must not be negative, got %r" % (t,))
+        t2.append(min(math.floor(f * f), (1 << 31) - 1))               # no d2 is above 2^31 - 1
+    q_num, q_den = _percentile_fraction("surface_sums", percentile)
+    (p, pcode), (g, gcode) = _boundary_masks("surface_sums", "unet_surface_sums", pred, gt)
+    import ctypes
+    import _hip
+    B, H, W = p.shape
+    dev = p.device
+    record = torch.empty(B, 2, 10, dtype=torch.int64, device=dev)
+    maps = [torch.empty(B, H, W, dtype=torch.int32, device=dev) if return_maps else None for _ in range(2)]
+    scratch = _hip.scratch("unet_surface_sums", dev, B, H, W)
+    _hip.run("unet_surface_sums", dev, _hip.ptr(p), pcode, k, _hip.ptr(g), gcode, k, B, H, W, connectivity, _EDGES[edge], q_num, q_den,
+             (ctypes.c_int * 4)(*(t2 + [0] * (4 - len(t2)))), len(t2), _hip.ptr(record), _hip.ptr(maps[0]), _hip.ptr(maps[1]), _hip.ptr(scratch))
+    single = pred.dim() == 2
+    return SurfaceSums(record[0] if single else record, *((m[0] if single and m is not None else m) for m in maps), tuple(t2), q_num, q_den)
+
+
+def scores_from_surface(sums, *, spacing=1.0):
+    """The boundary scores of every image from the record of surface_sums (a device tensor, a host tensor or an array): pure numpy
+    on the host.  Returns BoundaryScores of float64 arrays [B] (scalars for a single image), nsd, precision, recall and boundary_f1
+    [B, tolerances]:
+      hausdorff      sqrt(the larger of the two max d2)
+      hd_percentile  the larger of the two directed percentiles of the distances, each numpy.percentile(d, p, method='linear'):
+                     MONAI's convention, not medpy's percentile of the pooled distances
+      assd           the average symmetric surface distance: (sum pred -> gt + sum gt -> pred) / (n_pred + n_gt)
+      nsd            the normalised surface Dice at each tolerance: the contour pixels of both masks within it / (n_pred + n_gt)
+      precision, recall, boundary_f1   the share of pred's contour within the tolerance of gt's, the reverse, their harmonic mean
+      n_pred, n_gt   int64, the pixels of the two contours
+    spacing, the size of a pixel, multiplies the distances; the tolerances were given to surface_sums in pixels (boundary_scores
+    divides them).  Both contours empty: the distances are 0, nsd and boundary_f1 are 1; exactly one empty: inf and 0; precision
+    (recall) is nan where pred's (gt's) contour is empty."""
+    if isinstance(spacing, bool) or not isinstance(spacing, (int, float, np.integer, np.floating)) or not (math.isfinite(spacing) and spacing > 0):
+        raise ValueError("scores_from_surface: spacing must be a positive finite number, got %r" % (spacing,))
+    rec = sums.record
+    rec = rec.detach().cpu().numpy() if torch.is_tensor(rec) else np.asarray(rec)
+    if rec.dtype != np.int64 or rec.ndim not in (2, 3) or rec.shape[-2:] != (2, 10):
+        raise ValueError("scores_from_surface: record must be int64 [B, 2, 10] or [2, 10], got %s %s" % (rec.dtype, rec.shape))
+    single = rec.ndim == 2
+    rec = np.ascontiguousarray(rec.reshape(-1, 2, 10))
+    k, spacing = len(sums.t2), float(spacing)
+    n = rec[:, :, 0]
+    both, none = (n > 0).all(axis=1), (n == 0).all(axis=1)
+    total = n.sum(axis=1).astype(np.float64)
+
+    def distance(v):                                                   # v: per image, valid where both contours exist
+        return np.where(both, v, np.where(none, 0.0, np.inf)) * spacing
+    lo, hi = np.sqrt(rec[:, :, 2].astype(np.float64)), np.sqrt(rec[:, :, 3].astype(np.float64))
+    directed = lo + rec[:, :, 4].astype(np.float64) / float(sums.q_den) * (hi - lo)
+    dsum = rec[:, :, 9].copy().view(np.float64)
+    within = rec[:, :, 5:5 + k].astype(np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        assd = dsum.sum(axis=1) / total
+        share = np.where(both[:, None], within.sum(axis=1) / total[:, None], np.where(none[:, None], 1.0, 0.0))
+        precision, recall = within[:, 0] / n[:, 0, None], within[:, 1] / n[:, 1, None]          # 0 / 0 = nan: an empty side
+        f1 = np.where(both[:, None], np.where(precision + recall > 0, 2 * precision * recall / (precision + recall), 0.0),
+                      np.where(none[:, None], 1.0, 0.0))
+    out = BoundaryScores(hausdorff=distance(np.sqrt(rec[:, :, 1].max(axis=1).astype(np.float64))), hd_percentile=distance(directed.max(axis=1)),
+                         assd=distance(assd), nsd=share, precision=precision, recall=recall, boundary_f1=f1, n_pred=n[:, 0].copy(),
+                         n_gt=n[:, 1].copy())
+    return BoundaryScores(*(t[0] for t in out)) if single else out
+
+
+def boundary_scores(pred, gt, *, tolerances=(1.0,), percentile=95, spacing=1.0, select=None, connectivity=4, edge='background'):
+    """scores_from_surface(surface_sums(pred, gt, ...), spacing=spacing): the Hausdorff distance, its percentile, the average
+    symmetric surface distance and the normalised surface Dice of a predicted mask against the ground truth, one read-back.
+    tolerances are in the unit of spacing: they are divided by it, exactly, before they are squared."""
+    if isinstance(spacing, bool) or not isinstance(spacing, (int, float, np.integer, np.floating)) or not (math.isfinite(spacing) and spacing > 0):
+        raise ValueError("boundary_scores: spacing must be a positive finite number, got %r" % (spacing,))
+    s = _surface_fraction("boundary_scores", "spacing", spacing)
+    tol = tuple(tolerances)
+    for t in tol:
+        _surface_fraction("boundary_scores", "a tolerance", t)
+    sums = surface_sums(pred, gt, tolerances=[fractions.Fraction(t.item() if isinstance(t, np.generic) else t) / s for t in tol],
+                        percentile=percentile, select=select, connectivity=connectivity, edge=edge)
+    return scores_from_surface(sums, spacing=spacing)
 
 
 def class_balance(gt_batch):

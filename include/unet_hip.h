@@ -495,6 +495,44 @@ size_t unet_cell_hulls_scratch_bytes(long long n_levels);
 int unet_cell_hulls(const void *labels, int label_dtype, int B, int H, int W, int n_max, const void *bbox_i32, const void *level_offset_i64,
                     long long n_levels, void *n_vertices_i32, void *area2_i64, void *feret_max2_i64, void *width_i64, void *vertices_i32,
                     void *status_u64, void *scratch, void *stream);
+/* Boundary scores: where the contour of a predicted mask lies against the contour of the ground truth (boundary.hip;
+ * functions.mask_boundary, functions.surface_sums, functions.scores_from_surface, functions.boundary_scores).
+ * The device gives exact integers and one fp64 sum per image and direction; the Hausdorff distance, its percentile, the average
+ * symmetric surface distance and the normalised surface Dice are formed from them on the host.
+ *   Region    mask != 0; with select = k >= 0 it is mask == k (the class-k region of a K-class label map; a float32 mask is compared
+ *             with (float)k).  select = -1 means none.  Masks [B,H,W] of dtype 0 = int64, 1 = float32, 2 = int32, 3 = uint8.
+ *   Contour   dA = the pixels of A that have a neighbour outside A: the 4-neighbours with connectivity 4, all eight with 8.
+ *   Edge      edge 1 ("background", what scipy.ndimage.binary_erosion(border_value=0) and MONAI's get_mask_edges do): a pixel
+ *             past the image is outside A, so region pixels on the frame are contour.  edge 0 ("ignore"): pixels past the image
+ *             are nothing.
+ *   Distance  for p in dA, d2(p) = the exact squared Euclidean distance (int32) to the nearest pixel of dB; defined only when dB is
+ *             not empty.
+ * unet_mask_boundary: out_u8 [B,H,W] = 1 on the contour of the mask's region, 0 elsewhere.  One launch, no scratch.
+ * unet_surface_sums: both directions, P -> G (dir 0: d2 of the pixels of dP to dG) and G -> P (dir 1), in one call that never
+ * synchronises.  record [B][2 dir] of 10 64-bit words each:
+ *   [0] int64 n       = |dA|, also when dB is empty
+ *   [1] int64 max_d2  = the largest d2
+ *   [2] int64 lo, [3] int64 hi, [4] int64 rem : with j = floor((n - 1) q_num / q_den) and rem = (n - 1) q_num mod q_den, the j-th and
+ *                       the min(j + 1, n - 1)-th smallest d2 (0-based): sqrt(lo) + rem / q_den (sqrt(hi) - sqrt(lo)) is
+ *                       numpy.percentile(d, 100 q_num / q_den, method='linear').  0 <= q_num <= q_den, 1 <= q_den < 2^20
+ *   [5..8] int64 within[i] = the pixels with d2 <= t2_i32[i], i < n_t2 (0 <= n_t2 <= 4; t2_i32 is a host array, read during the
+ *                       call, every entry >= 0); 0 for i >= n_t2
+ *   [9] fp64 sum      = the sum of sqrt(d2)
+ * If dA or dB is empty, every word but n is 0 (the fp64 sum +0.0) and the d2 plane of that direction is -1 everywhere: the caller
+ * tells "both empty" from "one empty" by the two n.  d2_pg_i32, d2_gp_i32 [B,H,W] (each may be NULL): d2 on dP (dG), -1 elsewhere.
+ * Exact order statistics by a radix select on the device (digits of 11, 10 and 10 bits); every count is an integer atomic or a
+ * fixed-order reduce, the fp64 sum is reduced per workgroup in a fixed order, written to the workgroup's own slot and added in slot
+ * order by one workgroup: every output is bit-identical in every run and on every stream.  One memset and 11 launches.
+ * Limits as unet_distance_map: H, W <= 32767, H * W < 2^31, B <= 65535; H != W allowed, down to 1 x 1.  A NULL pointer, another
+ * dtype, connectivity, edge, a select below -1, a bad percentile or tolerance and a size over the limit return an error and write
+ * nothing.
+ * scratch: unet_surface_sums_scratch_bytes(B, H, W) (17 bytes per pixel, 32 per 256 pixels of a row and direction, and 32 KiB of
+ * histograms per image), initialised by the call.                                                                              */
+int unet_mask_boundary(const void *mask, int mask_dtype, int select, int B, int H, int W, int connectivity, int edge, void *out_u8, void *stream);
+size_t unet_surface_sums_scratch_bytes(int B, int H, int W);
+int unet_surface_sums(const void *pred, int pred_dtype, int pred_select, const void *gt, int gt_dtype, int gt_select, int B, int H, int W,
+                      int connectivity, int edge, long long q_num, long long q_den, const int *t2_i32, int n_t2, void *record,
+                      void *d2_pg_i32, void *d2_gp_i32, void *scratch, void *stream);
 /* The integers of the Cell Tracking Challenge SEG measure, the score behind the goals of trainer.py:20-26 (Ronneberger et al.
  * 2015, Table 2): gt_i32, pred_i32 id maps int32 [B,H,W], 0 = background, gt ids anywhere in [0, ng_max] (not necessarily
  * consecutive, an object not necessarily connected), pred ids in [0, np_max]; ng_max, np_max < 2^24.
