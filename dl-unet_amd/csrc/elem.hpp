@@ -1,6 +1,6 @@
 // elem.hpp — what the HBM-bound kernels (direct.hip, multiclass.hip, dice.hip, tile.hip, aux.hip) and the data-path files (label.hip, wmap.hip,
-// instances.hip, prepare.hip, grow.hip, elastic.hip, clean.hip, warp.hip, through sweep.hpp geo.hip, shape.hip, flood.hip, and
-// through dm.hpp shape.hip and boundary.hip) share:
+// prepare.hip, grow.hip, elastic.hip, clean.hip, warp.hip, measure.hip, hull.hip, through ov_table.hpp instances.hip and track.hip,
+// through sweep.hpp geo.hip, shape.hip, flood.hip, and through dm.hpp shape.hip and boundary.hip) share:
 //   device : 4 consecutive channels of an activation tensor stored as fp32 (16 B) or bf16 (8 B, arithmetic mode 2), read /
 //            written as 4 floats; the sum / min / max of one value per lane over a wave; the min and max of one value per thread
 //            over a block; the sum of one value per thread over a 256-thread block, with the max of a second one (the finish
@@ -8,7 +8,7 @@
 //            exclusive prefix of one int per thread over it; a few counts per thread summed over the workgroup into one
 //            agent-scope add per word (label.hip, clean.hip); whether an element of a mask of any of the four dtypes is set;
 //            the union-find of the labelling (label.hip) on LDS words and on global words
-//   host   : the grid size of a grid-stride launch, the bytes of a [B,H,W] scratch plane, the size limits of the [B,H,W] ops,
+//   host   : the grid size of a grid-stride launch, the bytes of a [B,H,W] scratch plane, the size and id limits of the [B,H,W] ops,
 //            and the dispatch of a launch on element size, channel width and padded class count (the launch bracket,
 //            profiled(), is common.hpp's)
 #pragma once
@@ -198,6 +198,16 @@ static inline size_t plane_bytes(int B, int H, int W, size_t elem_size) { return
 // label_sizes_ok: the labelling (label.hip) and what stands on its planes (wmap.hip, clean.hip); W is bounded by H * W alone
 static inline bool sizes_ok(int B, int H, int W, int edge) { return (size_t)H * W < (1u << 31) && H <= edge && W <= edge && B <= 65535; }
 static inline bool label_sizes_ok(int B, int H, int W) { return (size_t)H * W < (1u << 31) && H <= 65535 && B <= 65535; }
+
+// The ops on instance maps (instances.hip, track.hip, measure.hip, hull.hip) take ids in [0, ID_MAX]: two ids and an image index
+// fill a 64-bit key (ov_table.hpp).  The measurement family (measure.hip, hull.hip, unet_cell_contacts) takes H, W <=
+// MEASURE_EDGE: every coordinate sum of a cell fits 64 bits
+static constexpr int ID_BITS = 24, ID_MAX = (1 << ID_BITS) - 1;
+static constexpr int MEASURE_EDGE = 32768;
+static inline bool measure_sizes_ok(int B, int H, int W, int n_max)
+{
+    return H <= MEASURE_EDGE && W <= MEASURE_EDGE && B <= 65535 && n_max >= 0 && n_max <= ID_MAX;
+}
 
 // Launch dispatch: f is a generic lambda that receives the storage type as a value of it (es 2: bf16_t, else float), then the
 // channel width (32 or 64; the callers have checked it) and for the K-class head KP = class_pad(K) (4, 8 or 16: K = 2 runs the

@@ -37,9 +37,6 @@ namespace unet {
 typedef unsigned long long u64;
 typedef unsigned __int128 u128;
 
-static constexpr int HU_EDGE = 32768;                          // H, W <= HU_EDGE, as unet_cell_sums
-static constexpr int HU_ID_MAX = (1 << 24) - 1;
-
 // where the levels of row r = b * (n_max + 1) + i lie: false for id 0, an empty or impossible box, and a level count that is
 // not y1 - y0 + 1 or does not fit the tables [0, L)
 struct HullRow { int y0, x0, y1, x1; long long base; };
@@ -179,8 +176,7 @@ int unet_cell_hulls(const void *labels, int label_dtype, int B, int H, int W, in
               H > 0 && W > 0 && n_levels >= 0, "unet_cell_hulls: bad argument");
     ARG_CHECK(n_levels == 0 || (vertices_i32 && scratch), "unet_cell_hulls: n_levels > 0 needs vertices_i32 and scratch");
     ARG_CHECK(label_dtype == 0 || label_dtype == 2, "unet_cell_hulls: label dtype must be 0 (int64) or 2 (int32)");
-    ARG_CHECK(H <= HU_EDGE && W <= HU_EDGE && B <= 65535 && n_max >= 0 && n_max <= HU_ID_MAX,
-              "unet_cell_hulls: H, W must be <= 32768, B <= 65535 and n_max in [0, 2^24)");
+    ARG_CHECK(measure_sizes_ok(B, H, W, n_max), "unet_cell_hulls: H, W must be <= 32768, B <= 65535 and n_max in [0, 2^24)");
     hipStream_t st = (hipStream_t)stream;
     const size_t rows = (size_t)B * ((size_t)n_max + 1), L = (size_t)n_levels;
     unsigned *lo_tab = (unsigned *)scratch, *hi_tab = lo_tab + L;

@@ -3,16 +3,15 @@
 //
 // unet_instance_overlap: two id maps -> per-id areas, and for every ground-truth id the one predicted id that covers more than
 // half of it, with the size of that overlap:
-//   1. overlap_fill   a wave reads 64 consecutive pixels, merges the runs of equal (gt, pred) pairs among them with one ballot,
-//                     and the first lane of a run adds the run's length to both area histograms and, for gt, pred >= 1, to the
-//                     pair's counter in an open-addressing table (64-bit key (b, gt, pred), claimed by compare-and-swap)
+//   1. overlap_fill   ov_table.hpp's pair fill on (gt, pred): the first lane of a run of equal pairs adds the run's length to both
+//                     area histograms and, for gt, pred >= 1, to the counter of the key (b, gt, pred) in the pair table
 //   2. overlap_match  one thread per table slot: 2 * count > area_gt[g] -> match[g] = p, inter[g] = count (at most one p per g)
 // Every count is an integer sum: the outputs do not depend on the order of the atomics.  Which slot a key lands in does, and
 // nothing reads that.
 //
 // unet_partition_pairs: the contingency table of two id maps restricted to ground-truth foreground, which the Rand and information
 // scores of the ISBI 2012 challenge (Ronneberger et al. 2015, Table 1) are sums over:
-//   1. overlap_fill<FG>  the same wave loop and table, for every pixel with gt >= 1 and any pred >= 0; no histograms
+//   1. overlap_fill<FG>  the same pair fill and table, for every pixel with gt >= 1 and any pred >= 0; no histograms
 //   2. pairs_compact     a wave reads 64 slots, one agent-scope add on n_pairs gives it a block of the dense (key, count) list
 // The list's order depends on the order of those adds; its content does not.
 //
@@ -21,66 +20,28 @@
 //   1. contact_fill      every pixel looks right (one insert per side) and down (one insert per run of equal (id, id below) pairs)
 //   2. pairs_compact     as above
 //
-// Coherence (label.hip's rule): inside overlap_fill and contact_fill a table key is only ever touched by an agent-scope compare-and-swap, a
-// counter, a histogram bin or a status word only by an agent-scope add, and n_pairs in pairs_compact likewise; overlap_match
-// and pairs_compact read what an earlier kernel wrote.  No word is handed from one workgroup to another inside a kernel by plain
-// loads and stores.
+// Coherence: ov_table.hpp's rule for overlap_fill and contact_fill; n_pairs in pairs_compact is likewise touched by agent-scope
+// adds only; overlap_match and pairs_compact read what an earlier kernel wrote.
 #include "ov_table.hpp"
 #include "../../include/unet_hip.h"
 
 namespace unet {
 
 // ---- overlaps ---------------------------------------------------------------------------------------------------------
-// FG = false: unet_instance_overlap (both area histograms, pairs with g, p >= 1).  FG = true: unet_partition_pairs (no histogram,
-// pairs with g >= 1 and any p >= 0: the table restricted to ground-truth foreground, "predicted background" being the column 0)
+// overlap_fill = pair_fill_kernel (ov_table.hpp) on image b of gt and pred, key (b, g, p).  FG = false: unet_instance_overlap
+// (both area histograms, pairs with g, p >= 1).  FG = true: unet_partition_pairs (no histogram, pairs with g >= 1 and any p >= 0:
+// the table restricted to ground-truth foreground, "predicted background" being the column 0)
 template <bool FG>
-__global__ __launch_bounds__(256) void overlap_fill_kernel(const int *__restrict__ gt, const int *__restrict__ pred, size_t npx,
-                                                           int ng_max, int np_max, unsigned long long *keys, unsigned *cnt,
-                                                           size_t slots, unsigned *area_gt, unsigned *area_pred,
-                                                           unsigned long long *status)
-{
-    const int b = blockIdx.y, lane = threadIdx.x & 63;
-    const int *G = gt + (size_t)b * npx, *P = pred + (size_t)b * npx;
-    unsigned *ag = FG ? nullptr : area_gt + (size_t)b * (ng_max + 1), *ap = FG ? nullptr : area_pred + (size_t)b * (np_max + 1);
-    unsigned long long bad = 0, dropped = 0, g0 = 0, p0 = 0;      // this lane's share of status[b][0..1] and of the two bins 0
-    bool full = false;                                            // the table only fills up: after one failed probe, stop probing
-    const size_t stride = (size_t)gridDim.x * blockDim.x;
-    for (size_t base = (size_t)blockIdx.x * blockDim.x + (threadIdx.x & ~63); base < npx; base += stride) {   // wave-uniform
-        const size_t e = base + lane;
-        const bool in = e < npx;
-        int g = in ? G[e] : -1, p = in ? P[e] : -1;
-        const bool ok = in && (unsigned)g <= (unsigned)ng_max && (unsigned)p <= (unsigned)np_max;
-        if (!ok) g = p = in ? -1 : -2;                            // out-of-range pixels form runs of their own; so does the tail past the image
-        const int gl = __shfl_up(g, 1, 64), pl = __shfl_up(p, 1, 64);
-        const bool head = lane == 0 || g != gl || p != pl;
-        const unsigned long long heads = __ballot(head);
-        const unsigned long long above = lane == 63 ? 0ull : heads >> (lane + 1);
-        const unsigned n = above ? (unsigned)__ffsll(above) : (unsigned)(64 - lane);   // run length: up to the next head
-        if (head && in) {
-            if (!ok) bad += n;
-            else {
-                if constexpr (!FG) {
-                    if (g) __hip_atomic_fetch_add(&ag[g], n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); else g0 += n;
-                    if (p) __hip_atomic_fetch_add(&ap[p], n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); else p0 += n;
-                }
-                if (g && (FG || p)) {
-                    const unsigned long long key = (unsigned long long)b << (2 * OV_ID_BITS) | (unsigned long long)g << OV_ID_BITS | (unsigned)p;
-                    if (full || !ov_insert(keys, cnt, slots, key, n)) { dropped += n; full = true; }
-                }
-            }
-        }
-        full = __any(full);
+struct OverlapFill {
+    const int *gt, *pred; size_t npx; int ng_max, np_max; OvTable tab; unsigned *area_gt, *area_pred; unsigned long long *status;
+    static constexpr bool J_MAY_BE_NULL = false, AREA_I = !FG, AREA_J = !FG, KEEP_J0 = FG;
+    __device__ unsigned long long key(unsigned long long b, int g, int p) const { return ov_key(b, g, p); }
+    __device__ PairMaps maps(int b) const
+    {
+        return {gt + (size_t)b * npx, pred + (size_t)b * npx, ng_max, np_max, FG ? nullptr : area_gt + (size_t)b * (ng_max + 1),
+                FG ? nullptr : area_pred + (size_t)b * (np_max + 1)};
     }
-    bad = wave_sum(bad); dropped = wave_sum(dropped); g0 = wave_sum(g0); p0 = wave_sum(p0);
-    if (lane == 0) {
-        if (bad) __hip_atomic_fetch_add(&status[2 * b], bad, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (dropped) __hip_atomic_fetch_add(&status[2 * b + 1], dropped, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if constexpr (!FG) {
-            if (g0) __hip_atomic_fetch_add(&ag[0], (unsigned)g0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (p0) __hip_atomic_fetch_add(&ap[0], (unsigned)p0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
-}
+};
 
 __global__ __launch_bounds__(256) void overlap_match_kernel(const unsigned long long *__restrict__ keys, const unsigned *__restrict__ cnt,
                                                             size_t slots, int ng_max, const unsigned *__restrict__ area_gt,
@@ -89,8 +50,8 @@ __global__ __launch_bounds__(256) void overlap_match_kernel(const unsigned long 
     for (size_t s = (size_t)blockIdx.x * blockDim.x + threadIdx.x; s < slots; s += (size_t)gridDim.x * blockDim.x) {
         const unsigned long long key = keys[s];
         if (key == OV_EMPTY) continue;
-        const size_t b = key >> (2 * OV_ID_BITS);
-        const int g = (int)(key >> OV_ID_BITS) & OV_ID_MAX, p = (int)key & OV_ID_MAX;
+        const size_t b = ov_key_b(key);
+        const int g = ov_key_i(key), p = ov_key_j(key);
         const size_t o = b * (ng_max + 1) + g;
         const unsigned c = cnt[s];
         if (2ull * c > area_gt[o]) { match[o] = p; inter[o] = c; }      // strict: no two p can both hold more than half of g
@@ -129,18 +90,16 @@ __global__ __launch_bounds__(256) void pairs_compact_kernel(const unsigned long 
 // insert; the sides below are merged per run of equal (id, id below) pairs along a row with one ballot, as overlap_fill merges
 // its pairs.  A pixel with an id outside [0, n_max] is counted in status[b][0] and is nobody's neighbour.
 template <typename LT>
-__global__ __launch_bounds__(256) void contact_fill_kernel(const LT *__restrict__ labels, int H, int W, int n_max, unsigned long long *keys,
-                                                           unsigned *cnt, size_t slots, unsigned long long *status)
+__global__ __launch_bounds__(256) void contact_fill_kernel(const LT *__restrict__ labels, int H, int W, int n_max, const OvTable tab,
+                                                           unsigned long long *status)
 {
     const int b = blockIdx.y, lane = threadIdx.x & 63;
     const size_t npx = (size_t)H * W;
     const LT *M = labels + (size_t)b * npx;
     auto id_at = [&](size_t e) { const LT v = M[e]; return (v < 0 || v > (LT)n_max) ? -1 : (int)v; };
-    auto key_of = [&](int i, int j) {
-        return (unsigned long long)b << (2 * OV_ID_BITS) | (unsigned long long)min(i, j) << OV_ID_BITS | (unsigned)max(i, j);
-    };
+    auto key_of = [&](int i, int j) { return ov_key(b, min(i, j), max(i, j)); };
     unsigned long long bad = 0, dropped = 0;                      // this lane's share of status[b][0..1]
-    bool full = false;                                            // the table only fills up: after one failed probe, stop probing
+    bool full = false;
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     for (size_t base = (size_t)blockIdx.x * blockDim.x + (threadIdx.x & ~63); base < npx; base += stride) {   // wave-uniform
         const size_t e = base + lane;
@@ -153,50 +112,36 @@ __global__ __launch_bounds__(256) void contact_fill_kernel(const LT *__restrict_
         if (a < 1 || down < 1 || down == a) down = 0;             // no contact below: such pixels form runs too, and add nothing
         const int al = __shfl_up(a, 1, 64), dl = __shfl_up(down, 1, 64);
         const bool head = lane == 0 || a != al || down != dl || x == 0;
-        const unsigned long long heads = __ballot(head);
-        const unsigned long long above = lane == 63 ? 0ull : heads >> (lane + 1);
-        const unsigned n = above ? (unsigned)__ffsll(above) : (unsigned)(64 - lane);   // run length: up to the next head
-        if (a >= 1 && right >= 1 && right != a && (full || !ov_insert(keys, cnt, slots, key_of(a, right), 1u))) { ++dropped; full = true; }
-        if (head && down && (full || !ov_insert(keys, cnt, slots, key_of(a, down), n))) { dropped += n; full = true; }
+        const unsigned n = wave_run_length(head, lane);
+        OV_ADD_IF(a >= 1 && right >= 1 && right != a, tab, key_of(a, right), 1u, full, dropped);
+        OV_ADD_IF(head && down, tab, key_of(a, down), n, full, dropped);
         full = __any(full);
     }
-    bad = wave_sum(bad); dropped = wave_sum(dropped);
-    if (lane == 0) {
-        if (bad) __hip_atomic_fetch_add(&status[2 * b], bad, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (dropped) __hip_atomic_fetch_add(&status[2 * b + 1], dropped, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    ov_flush(status, b, lane, bad, dropped);
 }
 
 } // namespace unet
 
 using namespace unet;
 
-struct OvTable { unsigned long long *keys; unsigned *cnt; };
-
-// what unet_instance_overlap (FG = false) and unet_partition_pairs (FG = true) share: the checks, the table carved from the
-// scratch, the clears of everything overlap_fill adds to (FG: no histograms, area_gt and area_pred are null) and its launch
+// what unet_instance_overlap (FG = false) and unet_partition_pairs (FG = true) share: the checks, the open table, the clears of
+// the histograms overlap_fill adds to (FG: there are none, area_gt and area_pred are null) and its launch
 template <bool FG>
 static int ov_fill(const char *who, const void *gt_i32, const void *pred_i32, int B, int H, int W, int ng_max, int np_max,
                    size_t table_slots, void *area_gt_u32, void *area_pred_u32, void *status_u64, void *scratch, hipStream_t st, OvTable &t)
 {
     ARG_CHECK(gt_i32 && pred_i32 && status_u64 && scratch && B > 0 && H > 0 && W > 0, "%s: bad argument", who);
     ARG_CHECK((size_t)H * W < (1u << 31) && B <= 65535, "%s: image too large", who);
-    ARG_CHECK(ng_max >= 0 && np_max >= 0 && ng_max <= OV_ID_MAX && np_max <= OV_ID_MAX, "%s: ng_max and np_max must be in [0, %d]", who,
-              OV_ID_MAX);
-    ARG_CHECK(table_slots > 0 && (table_slots & (table_slots - 1)) == 0, "%s: table_slots must be a power of two", who);
+    ARG_CHECK(ng_max >= 0 && np_max >= 0 && ng_max <= ID_MAX && np_max <= ID_MAX, "%s: ng_max and np_max must be in [0, %d]", who, ID_MAX);
+    if (int rc = ov_open(who, scratch, table_slots, status_u64, B, st, t)) return rc;
     const size_t npx = (size_t)H * W;
-    t.keys = (unsigned long long *)scratch;
-    t.cnt = (unsigned *)((char *)scratch + ov_key_bytes(table_slots));
-    HIP_TRY(hipMemsetAsync(t.keys, 0xFF, table_slots * sizeof(unsigned long long), st));        // OV_EMPTY
-    HIP_TRY(hipMemsetAsync(t.cnt, 0, table_slots * sizeof(unsigned), st));
     if (!FG) {
         HIP_TRY(hipMemsetAsync(area_gt_u32, 0, B * ((size_t)ng_max + 1) * sizeof(unsigned), st));
         HIP_TRY(hipMemsetAsync(area_pred_u32, 0, B * ((size_t)np_max + 1) * sizeof(unsigned), st));
     }
-    HIP_TRY(hipMemsetAsync(status_u64, 0, (size_t)B * 2 * sizeof(unsigned long long), st));
-    hipLaunchKernelGGL(overlap_fill_kernel<FG>, dim3(grid_for(npx, 256, 2048), B), dim3(256), 0, st, (const int *)gt_i32,
-                       (const int *)pred_i32, npx, ng_max, np_max, t.keys, t.cnt, table_slots, (unsigned *)area_gt_u32,
-                       (unsigned *)area_pred_u32, (unsigned long long *)status_u64);
+    const OverlapFill<FG> src{(const int *)gt_i32, (const int *)pred_i32, npx, ng_max, np_max, t, (unsigned *)area_gt_u32,
+                              (unsigned *)area_pred_u32, (unsigned long long *)status_u64};
+    hipLaunchKernelGGL(pair_fill_kernel<OverlapFill<FG>>, dim3(grid_for(npx, 256, 2048), B), dim3(256), 0, st, src);
     return 0;
 }
 
@@ -261,25 +206,20 @@ int unet_cell_contacts(const void *labels, int label_dtype, int B, int H, int W,
     ARG_CHECK(labels && pair_keys_u64 && pair_counts_u32 && n_pairs_u64 && status_u64 && scratch && B > 0 && H > 0 && W > 0,
               "unet_cell_contacts: bad argument");
     ARG_CHECK(label_dtype == 0 || label_dtype == 2, "unet_cell_contacts: label dtype must be 0 (int64) or 2 (int32)");
-    ARG_CHECK(H <= 32768 && W <= 32768 && B <= 65535 && n_max >= 0 && n_max <= OV_ID_MAX,
-              "unet_cell_contacts: H, W must be <= 32768, B <= 65535 and n_max in [0, 2^24)");
-    ARG_CHECK(table_slots > 0 && (table_slots & (table_slots - 1)) == 0, "unet_cell_contacts: table_slots must be a power of two");
+    ARG_CHECK(measure_sizes_ok(B, H, W, n_max), "unet_cell_contacts: H, W must be <= 32768, B <= 65535 and n_max in [0, 2^24)");
     hipStream_t st = (hipStream_t)stream;
-    unsigned long long *keys = (unsigned long long *)scratch;
-    unsigned *cnt = (unsigned *)((char *)scratch + ov_key_bytes(table_slots));
-    HIP_TRY(hipMemsetAsync(keys, 0xFF, table_slots * sizeof(unsigned long long), st));          // OV_EMPTY
-    HIP_TRY(hipMemsetAsync(cnt, 0, table_slots * sizeof(unsigned), st));
-    HIP_TRY(hipMemsetAsync(status_u64, 0, (size_t)B * 2 * sizeof(unsigned long long), st));
+    OvTable t;
+    if (int rc = ov_open("unet_cell_contacts", scratch, table_slots, status_u64, B, st, t)) return rc;
     HIP_TRY(hipMemsetAsync(n_pairs_u64, 0, sizeof(unsigned long long), st));
     const dim3 grid(grid_for((size_t)H * W, 256, 2048), B);
     if (label_dtype == 0)
-        hipLaunchKernelGGL(contact_fill_kernel<long long>, grid, dim3(256), 0, st, (const long long *)labels, H, W, n_max, keys, cnt,
-                           table_slots, (unsigned long long *)status_u64);
-    else
-        hipLaunchKernelGGL(contact_fill_kernel<int>, grid, dim3(256), 0, st, (const int *)labels, H, W, n_max, keys, cnt, table_slots,
+        hipLaunchKernelGGL(contact_fill_kernel<long long>, grid, dim3(256), 0, st, (const long long *)labels, H, W, n_max, t,
                            (unsigned long long *)status_u64);
-    hipLaunchKernelGGL(pairs_compact_kernel, dim3(grid_for(table_slots, 256, 2048)), dim3(256), 0, st, (const unsigned long long *)keys,
-                       (const unsigned *)cnt, table_slots, (unsigned long long *)pair_keys_u64, (unsigned *)pair_counts_u32,
+    else
+        hipLaunchKernelGGL(contact_fill_kernel<int>, grid, dim3(256), 0, st, (const int *)labels, H, W, n_max, t,
+                           (unsigned long long *)status_u64);
+    hipLaunchKernelGGL(pairs_compact_kernel, dim3(grid_for(table_slots, 256, 2048)), dim3(256), 0, st, (const unsigned long long *)t.keys,
+                       (const unsigned *)t.cnt, table_slots, (unsigned long long *)pair_keys_u64, (unsigned *)pair_counts_u32,
                        (unsigned long long *)n_pairs_u64);
     HIP_TRY(hipGetLastError());
     return 0;

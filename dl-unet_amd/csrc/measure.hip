@@ -42,8 +42,6 @@ static constexpr int MS_WORDS = 16;
 static constexpr int MS_TW = 64, MS_TH = 16;                   // tile: one wave-row wide, four rows per wave
 static constexpr int MS_SLOTS = 128, MS_SLOT_BITS = 7;         // 128 records of 128 B = 16 KiB of LDS
 static constexpr int MS_PROBES = 8;
-static constexpr int MS_EDGE = 32768;                          // H, W <= MS_EDGE: every sum fits 64 bits
-static constexpr int MS_ID_MAX = (1 << 24) - 1;
 static constexpr int MS_OUTSIDE = -1, MS_BAD = -2, MS_EMPTY = -1;
 enum { MW_AREA = 0, MW_SY = 1, MW_SX = 2, MW_SYY = 3, MW_SXX = 4, MW_SXY = 5, MW_OPEN = 6, MW_CONTACT = 7, MW_SV = 8, MW_SVV = 9,
        MW_Y0 = 10, MW_X0 = 11, MW_Y1 = 12, MW_X1 = 13, MW_VMIN = 14, MW_VMAX = 15 };
@@ -265,11 +263,9 @@ __global__ __launch_bounds__(256) void ms_remap_kernel(const LT *__restrict__ la
 
 using namespace unet;
 
-static bool ms_sizes_ok(int B, int H, int W, int n_max) { return H <= MS_EDGE && W <= MS_EDGE && B <= 65535 && n_max >= 0 && n_max <= MS_ID_MAX; }
-
 size_t unet_cell_sums_scratch_bytes(int B, int n_max)
 {
-    if (B <= 0 || n_max < 0 || n_max > MS_ID_MAX) return 0;
+    if (B <= 0 || n_max < 0 || n_max > ID_MAX) return 0;
     return (size_t)B * ((size_t)n_max + 1) * MS_WORDS * sizeof(u64);
 }
 
@@ -282,7 +278,7 @@ int unet_cell_sums(const void *labels, int label_dtype, const void *image, int i
     ARG_CHECK(label_dtype == 0 || label_dtype == 2, "unet_cell_sums: label dtype must be 0 (int64) or 2 (int32)");
     ARG_CHECK(!image || (image_dtype >= 0 && image_dtype <= 3), "unet_cell_sums: image dtype must be 0 (int64), 1 (float32), 2 (int32) or 3 (uint8)");
     ARG_CHECK(!image || (vsum_64 && vrange_32), "unet_cell_sums: an image needs vsum_64 and vrange_32");
-    ARG_CHECK(ms_sizes_ok(B, H, W, n_max), "unet_cell_sums: H, W must be <= 32768, B <= 65535 and n_max in [0, 2^24)");
+    ARG_CHECK(measure_sizes_ok(B, H, W, n_max), "unet_cell_sums: H, W must be <= 32768, B <= 65535 and n_max in [0, 2^24)");
     hipStream_t st = (hipStream_t)stream;
     u64 *records = (u64 *)scratch;
     const int kind = !image ? IMG_NONE : image_dtype == 1 ? IMG_FLOAT : IMG_INT;
@@ -313,7 +309,7 @@ int unet_remap_labels(const void *labels, int label_dtype, int B, int H, int W, 
 {
     ARG_CHECK(labels && map_i32 && out_i32 && status_u64 && B > 0 && H > 0 && W > 0, "unet_remap_labels: bad argument");
     ARG_CHECK(label_dtype == 0 || label_dtype == 2, "unet_remap_labels: label dtype must be 0 (int64) or 2 (int32)");
-    ARG_CHECK(ms_sizes_ok(B, H, W, n_max), "unet_remap_labels: H, W must be <= 32768, B <= 65535 and n_max in [0, 2^24)");
+    ARG_CHECK(measure_sizes_ok(B, H, W, n_max), "unet_remap_labels: H, W must be <= 32768, B <= 65535 and n_max in [0, 2^24)");
     ARG_CHECK(map_stride == 0 || map_stride >= (long long)n_max + 1, "unet_remap_labels: map_stride must be 0 (one map for the batch) or >= n_max + 1");
     hipStream_t st = (hipStream_t)stream;
     const size_t npx = (size_t)H * W;

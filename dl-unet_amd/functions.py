@@ -102,27 +102,42 @@ def _id_range(name, *maps):
     return vals[1:]
 
 
-def _pair_counts(entry, gt, pred, ng_max, np_max, slots, scratch_dims, outputs, bad):
-    """The table protocol of unet_instance_overlap and unet_partition_pairs on int32 maps [B,H,W]: allocate the scratch
-    (scratch_dims(slots)) and the entry's outputs (outputs(slots)), call it, read the status words back once; status[:, 0], the
-    pixels whose ids the entry refuses, raises ValueError(bad % (count, ng_max, np_max)); status[:, 1], the pixels a full table
-    dropped, doubles the table and repeats, which ends: a table with more slots than pixels cannot fill up.  Returns the outputs."""
+def _table_call(entry, dev, n, head, slots, room, scratch_dims, outputs, bad, limits):
+    """The protocol of the entries that count into the pair table (csrc/ov_table.hpp), from slots (None: the power of two with
+    room + 1024 slots): allocate the entry's outputs (outputs(slots)) and scratch (scratch_dims(slots)), call entry(*head, slots,
+    *outputs, status, scratch), read the [n, 2] status words back once; status[:, 0], the pixels whose ids the entry refuses,
+    raises ValueError(bad % ((count,) + limits)); status[:, 1], the pixels a full table dropped, doubles the table and repeats,
+    which ends: a table with more slots than pixels cannot fill up.  Returns (outputs, slots)."""
     import _hip
-    B, H, W = gt.shape
-    dev = gt.device
-    status = torch.empty(B, 2, dtype=torch.int64, device=dev)
-    slots = 1 << (4 * (ng_max + np_max) + 1024 - 1).bit_length() if slots is None else int(slots)
+    status = torch.empty(n, 2, dtype=torch.int64, device=dev)
+    slots = 1 << (room + 1024 - 1).bit_length() if slots is None else int(slots)
     while True:
         outs = outputs(slots)
         scratch = _hip.scratch(entry, dev, *scratch_dims(slots))
-        _hip.run(entry, dev, _hip.ptr(gt), _hip.ptr(pred), B, H, W, ng_max, np_max, slots, *[_hip.ptr(o) for o in outs],
-                 _hip.ptr(status), _hip.ptr(scratch))
+        _hip.run(entry, dev, *head, slots, *[_hip.ptr(o) for o in outs], _hip.ptr(status), _hip.ptr(scratch))
         refused, dropped = (int(v) for v in status.cpu().sum(dim=0))
         if refused:
-            raise ValueError(bad % (refused, ng_max, np_max))
+            raise ValueError(bad % ((refused,) + limits))
         if not dropped:
-            return outs
+            return outs, slots
         slots *= 2
+
+
+def _overlap_call(entry, gt, pred, ng_max, np_max, slots, scratch_dims, outputs, bad):
+    """_table_call for unet_instance_overlap and unet_partition_pairs on int32 maps [B,H,W]; returns the outputs."""
+    import _hip
+    head = (_hip.ptr(gt), _hip.ptr(pred)) + tuple(gt.shape) + (ng_max, np_max)
+    return _table_call(entry, gt.device, len(gt), head, slots, 4 * (ng_max + np_max), scratch_dims, outputs, bad, (ng_max, np_max))[0]
+
+
+def _sorted_pairs(keys, counts, n_pairs):
+    """The compacted (key, count) list of unet_partition_pairs or unet_cell_contacts as int64 numpy arrays (b, i, j, n), sorted by
+    (b, i, j): the keys are distinct and unsigned, b << 48 | i << 24 | j, so their order is that of the triples."""
+    n = int(n_pairs.item())
+    k, c = keys[:n].cpu().numpy().view(np.uint64), counts[:n].cpu().numpy().astype(np.int64)
+    order = np.argsort(k)
+    k, c = k[order], c[order]
+    return tuple((k >> np.uint64(s) & np.uint64(m)).astype(np.int64) for s, m in ((48, 0xFFFF), (24, 0xFFFFFF), (0, 0xFFFFFF))) + (c,)
 
 
 def weighted_map(gt_batch, *, w0=20, sig2=25, return_objects=False):
@@ -544,24 +559,11 @@ def cell_neighbours(labels, *, _table_slots=None):
     (n_max,) = _id_range("cell_neighbours", lab)
     dev = lab.device
     n_pairs = torch.empty(1, dtype=torch.int64, device=dev)
-    status = torch.empty(B, 2, dtype=torch.int64, device=dev)
-    slots = 1 << (8 * n_max + 1024 - 1).bit_length() if _table_slots is None else int(_table_slots)
-    while True:
-        keys, counts = torch.empty(slots, dtype=torch.int64, device=dev), torch.empty(slots, dtype=torch.int32, device=dev)
-        scratch = _hip.scratch("unet_cell_contacts", dev, B, slots)
-        _hip.run("unet_cell_contacts", dev, _hip.ptr(lab), 0 if lab.dtype == torch.int64 else 2, B, H, W, n_max, slots, _hip.ptr(keys),
-                 _hip.ptr(counts), _hip.ptr(n_pairs), _hip.ptr(status), _hip.ptr(scratch))
-        refused, dropped = (int(v) for v in status.cpu().sum(dim=0))
-        if refused:
-            raise ValueError("cell_neighbours: %d pixels hold ids outside [0, %d]" % (refused, n_max))
-        if not dropped:
-            break
-        slots *= 2
-    n = int(n_pairs.item())
-    k, c = keys[:n].cpu().numpy().view(np.uint64), counts[:n].cpu().numpy().astype(np.int64)
-    order = np.argsort(k)                                   # distinct unsigned keys b << 48 | i << 24 | j: the order of (b, i, j)
-    k, c = k[order], c[order]
-    return Neighbours(*((k >> np.uint64(s) & np.uint64(m)).astype(np.int64) for s, m in ((48, 0xFFFF), (24, 0xFFFFFF), (0, 0xFFFFFF))), c)
+    (keys, counts, _), _ = _table_call(
+        "unet_cell_contacts", dev, B, (_hip.ptr(lab), 0 if lab.dtype == torch.int64 else 2, B, H, W, n_max), _table_slots, 8 * n_max, lambda slots: (B, slots),
+        lambda slots: (torch.empty(slots, dtype=torch.int64, device=dev), torch.empty(slots, dtype=torch.int32, device=dev), n_pairs),
+        "cell_neighbours: %d pixels hold ids outside [0, %d]", (n_max,))
+    return Neighbours(*_sorted_pairs(keys, counts, n_pairs))
 
 
 def neighbour_counts(neigh, B, n_max):
@@ -614,8 +616,8 @@ def seg_measure(pred_labels, gt_labels, *, _table_slots=None):
     area_pred = torch.empty(B, np_max + 1, dtype=torch.int32, device=dev)       # most H * W < 2^31, so the signed views agree
     match = torch.empty(B, ng_max + 1, dtype=torch.int32, device=dev)
     inter = torch.empty(B, ng_max + 1, dtype=torch.int32, device=dev)
-    _pair_counts("unet_instance_overlap", gt.int(), pred.int(), ng_max, np_max, _table_slots, lambda slots: (B, ng_max, np_max, slots),
-                 lambda slots: (area_gt, area_pred, match, inter), "seg_measure: %d pixels hold ids outside [0, %d] / [0, %d]")
+    _overlap_call("unet_instance_overlap", gt.int(), pred.int(), ng_max, np_max, _table_slots, lambda slots: (B, ng_max, np_max, slots),
+                  lambda slots: (area_gt, area_pred, match, inter), "seg_measure: %d pixels hold ids outside [0, %d] / [0, %d]")
     return seg_from_counts(area_gt.cpu().numpy(), area_pred.cpu().numpy(), match.cpu().numpy(), inter.cpu().numpy())
 
 
@@ -660,15 +662,11 @@ def pair_table(pred_labels, gt_labels, *, _table_slots=None):
     if max(ng_max, np_max) >= 1 << 24:
         raise ValueError("pair_table: ids must be below 2^24, got up to %d" % max(ng_max, np_max))
     n_pairs = torch.empty(1, dtype=torch.int64, device=dev)
-    keys, counts, _ = _pair_counts(
+    keys, counts, _ = _overlap_call(
         "unet_partition_pairs", gt.int(), pred.int(), ng_max, np_max, _table_slots, lambda slots: (B, slots),
         lambda slots: (torch.empty(slots, dtype=torch.int64, device=dev), torch.empty(slots, dtype=torch.int32, device=dev), n_pairs),
         "pair_table: %d pixels hold negative ids (outside [0, %d] / [0, %d])")
-    n = int(n_pairs.item())
-    k, c = keys[:n].cpu().numpy().view(np.uint64), counts[:n].cpu().numpy().astype(np.int64)
-    order = np.argsort(k)                                   # distinct unsigned keys b << 48 | g << 24 | p: the order of (b, g, p)
-    k, c = k[order], c[order]
-    return tuple((k >> np.uint64(s) & np.uint64(m)).astype(np.int64) for s, m in ((48, 0xFFFF), (24, 0xFFFFFF), (0, 0xFFFFFF))) + (c,)
+    return _sorted_pairs(keys, counts, n_pairs)
 
 
 # ---- linking cells across frames ----------------------------------------------------------------------------------------
@@ -693,18 +691,8 @@ def _link_frames(name, labels, reach, slots):
     T, H, W = lab.shape
     dev = lab.device
     out = torch.empty(3, T, n_max + 1, dtype=torch.int32, device=dev)   # the library's u32 words: counts of at most H * W < 2^31
-    status = torch.empty(T, 2, dtype=torch.int64, device=dev)
-    slots = 1 << (min(4 * (T - 1) * n_max, T * H * W) + 1024 - 1).bit_length() if slots is None else int(slots)
-    while True:                                                         # _pair_counts' protocol, one id range for both maps
-        scratch = _hip.scratch("unet_link_frames", dev, T, n_max, slots)
-        _hip.run("unet_link_frames", dev, _hip.ptr(src), _hip.ptr(lab), T, H, W, n_max, slots, _hip.ptr(out[0]), _hip.ptr(out[1]),
-                 _hip.ptr(out[2]), _hip.ptr(status), _hip.ptr(scratch))
-        refused, dropped = (int(v) for v in status.cpu().sum(dim=0))
-        if refused:
-            raise ValueError("%s: %d pixels hold ids outside [0, %d]" % (name, refused, n_max))
-        if not dropped:
-            break
-        slots *= 2                                                      # ends: a table with more slots than pixels cannot fill up
+    _table_call("unet_link_frames", dev, T, (_hip.ptr(src), _hip.ptr(lab), T, H, W, n_max), slots, min(4 * (T - 1) * n_max, T * H * W),
+                lambda slots: (T, n_max, slots), lambda slots: tuple(out), name + ": %d pixels hold ids outside [0, %d]", (n_max,))
     return lab, n_max, FrameLinks(*out.cpu().numpy().astype(np.int64))
 
 

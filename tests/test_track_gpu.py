@@ -231,3 +231,45 @@ def test_tester_track(dev):
     assert maps.shape == (3, 200, 260) and maps.dtype == torch.int32 and torch.equal(maps != 0, inst != 0)
     ref.check_structure(tracks.table, tracks.track_of, functions.link_frames(inst).area)
 
+
+
+@pytest.mark.parametrize("slots", [None, 4])
+@pytest.mark.parametrize("T,H,W", [(3, 5, 17), (3, 67, 130)])
+def test_the_three_pair_fills_agree(dev, T, H, W, slots):
+    """unet_partition_pairs, unet_link_frames and unet_instance_overlap fill their tables with one kernel: on the same maps the
+    contingency table of frame t-1 (pred) against frame t (gt), cut down to p >= 1, must hold per c the link (largest count, the
+    smallest p among equals) and per c the match (the p with 2 n > area).  slots = 4 makes every table overflow and double."""
+    import _hip
+    import functions
+    m = ref.random_frames(2, T, H, W)
+    m[m == 5] = 70001                                                  # one id above 16 bits
+    n_max = int(m.max())
+    assert n_max == 70001 and len(np.unique(m)) > 12
+    t = torch.from_numpy(m).to(dev)
+    gt, pred = t[1:].contiguous(), t[:-1].contiguous()
+    pairs = functions.pair_table(pred, gt, _table_slots=slots)
+    b, c, p, n = (x[pairs[2] >= 1] for x in pairs)
+    assert len(n) > T and (n > 1).any()
+    links = functions.link_frames(t, _table_slots=slots)
+    # the table is sorted by (b, c, p): a stable sort by count descending keeps the smallest p first among equal counts
+    order = np.lexsort((p, -n, c, b))
+    first = np.ones(len(order), bool)
+    first[1:] = (b[order][1:] != b[order][:-1]) | (c[order][1:] != c[order][:-1])
+    best = order[first]
+    want_pred, want_over = np.zeros((T, n_max + 1), np.int64), np.zeros((T, n_max + 1), np.int64)
+    want_pred[b[best] + 1, c[best]], want_over[b[best] + 1, c[best]] = p[best], n[best]
+    assert np.array_equal(links.pred, want_pred) and np.array_equal(links.pred_overlap, want_over)
+    area = links.area[1:]
+    half = 2 * n > area[b, c]
+    want_match, want_inter = np.zeros((T - 1, n_max + 1), np.int64), np.zeros((T - 1, n_max + 1), np.int64)
+    want_match[b[half], c[half]], want_inter[b[half], c[half]] = p[half], n[half]
+    outs = [torch.empty(T - 1, n_max + 1, dtype=torch.int32, device=dev) for _ in range(4)]
+    status = torch.empty(T - 1, 2, dtype=torch.int64, device=dev)
+    table = slots_for(len(n))
+    _hip.run("unet_instance_overlap", dev, _hip.ptr(gt), _hip.ptr(pred), T - 1, H, W, n_max, n_max, table, *(_hip.ptr(o) for o in outs),
+             _hip.ptr(status), _hip.ptr(_hip.scratch("unet_instance_overlap", dev, T - 1, n_max, n_max, table)))
+    area_gt, area_pred, match, inter = (o.cpu().numpy().astype(np.int64) for o in outs)
+    assert not status.cpu().numpy().any()
+    assert np.array_equal(area_gt, area) and np.array_equal(area_pred, links.area[:-1])
+    assert np.array_equal(match, want_match) and np.array_equal(inter, want_inter) and (match > 0).sum() > T
+    assert functions.seg_measure(pred, gt, _table_slots=slots).n_matched == (want_match[:, 1:] > 0).sum()
