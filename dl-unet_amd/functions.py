@@ -63,30 +63,115 @@ def _planes(name, t):
     return (t[None] if t.dim() == 2 else t).contiguous()
 
 
+_CODES = {torch.int64: 0, torch.float32: 1, torch.int32: 2, torch.uint8: 3}      # the dtype codes of the library's entry points
+
+
 def _int_code(x, uint8_ok=False, int32_ok=True):
     """The tensor in one of the widths the library reads, and its dtype code: float -> float32 (1), int64 and the unsigned
     types int32 cannot hold -> int64 (0), uint8 stays where the entry point takes it (3), every other integer type (uint16
     from a numpy-born image included) and bool -> int32 (2), or int64 (0) where the entry point reads only that and float32."""
     if x.is_floating_point():
-        return x.float(), 1
-    if x.dtype == torch.uint8 and uint8_ok:
-        return x, 3
-    if not int32_ok or x.dtype in (torch.int64, torch.uint32, torch.uint64):
-        return x.to(torch.int64), 0
-    return x.to(torch.int32), 2
+        x = x.float()
+    elif x.dtype == torch.uint8 and uint8_ok:
+        pass
+    elif not int32_ok or x.dtype in (torch.int64, torch.uint32, torch.uint64):
+        x = x.to(torch.int64)
+    else:
+        x = x.to(torch.int32)
+    return x, _CODES[x.dtype]
+
+
+def _id_code(lab):
+    """The dtype code of an id map, which _id_maps has held to int32 or int64 and which goes in as it is."""
+    return _CODES[lab.dtype]
+
+
+def _unbatch(like, *ts):
+    """ts ([B,H,W] tensors or tables [B, ...], None passes through) without the batch axis that _planes gave an input `like` of
+    [H,W]: one value for one t, else a tuple."""
+    if like.dim() == 2:
+        ts = tuple(t if t is None else t[0] for t in ts)
+    return ts[0] if len(ts) == 1 else ts
+
+
+# The checks that the ops on two or three planes of one shape open with, in the order every one of them keeps: _all_tensors,
+# _same_shape, the dtype rules (_need_ids, ...), then _device_planes.  An op's checks of its other arguments sit between them.
+
+def _all_tensors(name, entry, tensors):
+    for t in tensors:
+        if not torch.is_tensor(t):
+            raise NotImplementedError("%s takes tensors on the HIP device (%s); there is no CPU implementation" % (name, entry))
+
+
+def _same_shape(name, what, tensors, ranked=True):
+    """One shape (and, if ranked, [H,W] or [B,H,W]), else ValueError("<name> takes <what>, got <the shapes>")."""
+    shape = tensors[0].shape
+    for t in tensors:
+        if t.shape != shape or (ranked and len(shape) not in (2, 3)):
+            raise ValueError("%s takes %s, got %s" % (name, what, ", ".join(str(tuple(t.shape)) for t in tensors)))
+
+
+def _need_ids(name, what, *tensors):
+    for t in tensors:
+        if t.dtype not in (torch.int32, torch.int64):
+            raise ValueError("%s takes int32 or int64 %s, got %s" % (name, what, t.dtype))
+
+
+def _device_planes(name, entry, tensors, sizes=None):
+    """The tensors as contiguous [B,H,W] (_planes, then sizes(name, B, H, W): ValueError on any device), then the device
+    (NotImplementedError)."""
+    planes = [_planes(name, t) for t in tensors]
+    if sizes is not None:
+        sizes(name, *planes[0].shape)
+    _device_only(name, entry, *tensors)
+    return planes
 
 
 def _id_maps(name, entry, *maps):
     """The checks of the ops that take one or two id maps: equal shape, rank, dtype, size (ValueError, on any device), then the
     device (NotImplementedError); returns them as contiguous [B,H,W]."""
-    if any(t.shape != maps[0].shape for t in maps) or maps[0].dim() not in (2, 3):
-        raise ValueError("%s takes id maps of equal shape [H,W] or [B,H,W], got %s" % (name, ", ".join(str(tuple(t.shape)) for t in maps)))
-    for t in maps:
-        if t.dtype not in (torch.int32, torch.int64):
-            raise ValueError("%s takes int32 or int64 id maps, got %s" % (name, t.dtype))
-    planes = [_planes(name, t) for t in maps]
-    _device_only(name, entry, *maps)
-    return planes
+    _same_shape(name, "id maps of equal shape [H,W] or [B,H,W]", maps)
+    _need_ids(name, "id maps", *maps)
+    return _device_planes(name, entry, maps)
+
+
+# ---- the checks of the other arguments: one statement of each rule, the message is the caller's ----------------------------
+
+_INTEGERS = (int, np.integer)
+
+
+def _int_in(v, lo, hi, message, types=_INTEGERS):
+    """v if it is one of `types`, no bool, with lo <= v < hi; else ValueError(message % (v,))."""
+    if isinstance(v, bool) or not isinstance(v, types) or not lo <= v < hi:
+        raise ValueError(message % (v,))
+    return v
+
+
+def _real_in(v, lo, hi, message, types=(int, float)):
+    """v if it is one of `types`, no bool, with lo <= v <= hi (which refuses nan); else ValueError(message % (v,))."""
+    if isinstance(v, bool) or not isinstance(v, types) or not lo <= v <= hi:
+        raise ValueError(message % (v,))
+    return v
+
+
+def _limit(name, what, v, cap=1 << 40, square=False):
+    """An optional limit as the library takes it: None and inf -> -1 (none), else min(floor(v) or floor(v^2), cap); anything
+    that is not >= 0, nan included, raises ValueError."""
+    if v is None or v == math.inf:
+        return -1
+    if not v >= 0:
+        raise ValueError("%s: %s must be None or a number >= 0, got %r" % (name, what, v))
+    return min(int(math.floor(float(v) ** 2 if square else v)), cap)
+
+
+def _host(t):
+    """A device tensor, host tensor or array as a numpy array."""
+    return t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+
+
+def _status_words(status):
+    """The status words [B] or [B, k] of a call summed over its images, read back in one copy: k Python ints."""
+    return status.cpu().numpy().reshape(len(status), -1).sum(axis=0).tolist()
 
 
 def _id_range(name, *maps):
@@ -115,7 +200,7 @@ def _table_call(entry, dev, n, head, slots, room, scratch_dims, outputs, bad, li
         outs = outputs(slots)
         scratch = _hip.scratch(entry, dev, *scratch_dims(slots))
         _hip.run(entry, dev, *head, slots, *[_hip.ptr(o) for o in outs], _hip.ptr(status), _hip.ptr(scratch))
-        refused, dropped = (int(v) for v in status.cpu().sum(dim=0))
+        refused, dropped = _status_words(status)
         if refused:
             raise ValueError(bad % ((refused,) + limits))
         if not dropped:
@@ -174,8 +259,7 @@ def label_cells(mask, connectivity=4):
     connectivity=8 joins diagonal neighbours too (scipy.ndimage.label with the full 3 x 3 structure, the same numbering;
     unet_label_components_conn, which reads uint8 and int32 masks as they are); anything but 4 or 8 raises ValueError.
     Host tensors raise NotImplementedError (no CPU path)."""
-    if connectivity not in (4, 8):
-        raise ValueError("label_cells: connectivity must be 4 or 8, got %r" % (connectivity,))
+    _check_connectivity("label_cells", connectivity)
     entry = "unet_label_components" if connectivity == 4 else "unet_label_components_conn"
     _device_only("label_cells", entry, mask)
     import _hip
@@ -186,7 +270,7 @@ def label_cells(mask, connectivity=4):
     scratch = _hip.scratch(entry, m.device, B, H, W)
     _hip.run(entry, m.device, _hip.ptr(m), code, B, H, W, *((8, 1) if connectivity == 8 else ()), _hip.ptr(labels), _hip.ptr(n_objects),
              _hip.ptr(scratch))
-    return (labels[0] if mask.dim() == 2 else labels), n_objects
+    return _unbatch(mask, labels), n_objects
 
 
 CleanInfo = collections.namedtuple("CleanInfo", "holes_filled pixels_filled cells_small pixels_small cells_border pixels_border cells_kept")
@@ -195,9 +279,7 @@ CleanInfo = collections.namedtuple("CleanInfo", "holes_filled pixels_filled cell
 def _area(name, what, v, none_ok=False):
     if v is None and none_ok:
         return -1
-    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0:
-        raise ValueError("%s: %s must be %san integer >= 0, got %r" % (name, what, "None or " if none_ok else "", v))
-    return min(int(v), 1 << 62)
+    return min(int(_int_in(v, 0, math.inf, "%s: %s must be %san integer >= 0, got %%r" % (name, what, "None or " if none_ok else ""))), 1 << 62)
 
 
 def clean_mask(mask, *, fill_holes=True, max_hole_area=None, min_area=0, drop_border=False, connectivity=4, return_info=False,
@@ -220,14 +302,12 @@ def clean_mask(mask, *, fill_holes=True, max_hole_area=None, min_area=0, drop_bo
     nothing waits.  Exact integers on the device (unet_clean_mask: two labellings and two per-pixel passes, whatever the number
     of holes and cells).  A connectivity other than 4 or 8 and areas that are no integers >= 0 raise ValueError; host tensors
     raise NotImplementedError (no CPU path)."""
-    if connectivity not in (4, 8):
-        raise ValueError("clean_mask: connectivity must be 4 or 8, got %r" % (connectivity,))
+    _check_connectivity("clean_mask", connectivity)
     hole = _area("clean_mask", "max_hole_area", max_hole_area, none_ok=True)
     small = _area("clean_mask", "min_area", min_area)
     if not torch.is_tensor(mask):
         raise NotImplementedError("clean_mask takes a tensor on the HIP device (unet_clean_mask); there is no CPU implementation")
-    mk = _planes("clean_mask", mask)
-    _device_only("clean_mask", "unet_clean_mask", mask)
+    (mk,) = _device_planes("clean_mask", "unet_clean_mask", [mask])
     import _hip
     m, code = _int_code(mk, uint8_ok=True)
     B, H, W = m.shape
@@ -240,12 +320,11 @@ def clean_mask(mask, *, fill_holes=True, max_hole_area=None, min_area=0, drop_bo
              _hip.ptr(out), _hip.ptr(action), _hip.ptr(info), _hip.ptr(scratch))
     if out.dtype != mask.dtype:
         out = out.to(mask.dtype)
-    single = mask.dim() == 2
-    res = (out[0] if single else out,)
+    res = (_unbatch(mask, out),)
     if return_info:
         res += (CleanInfo(*info.cpu().numpy().T.copy()),)
     if return_action:
-        res += (action[0] if single else action,)
+        res += (_unbatch(mask, action),)
     return res if len(res) > 1 else res[0]
 
 
@@ -265,6 +344,11 @@ CellSums = collections.namedtuple("CellSums", "area bbox moments frame open cont
 CellProps = collections.namedtuple("CellProps", "area centroid bbox moments_central axis_major axis_minor eccentricity orientation "
                                                 "equivalent_diameter extent perimeter contact_fraction touches_frame mean std min max")
 MEASURE_EDGE = 32768                                                    # H, W of cell_sums: every integer sum fits 64 bits
+
+
+def _measure_sizes(name, B, H, W):
+    if max(H, W) > MEASURE_EDGE:
+        raise ValueError("%s: H and W must be <= %d, got %d x %d" % (name, MEASURE_EDGE, H, W))
 
 
 def cell_sums(labels, image=None, *, n_max=None):
@@ -298,13 +382,10 @@ def cell_sums(labels, image=None, *, n_max=None):
         _device_only("cell_sums", "unet_cell_sums", image)
         img, icode = _int_code(_planes("cell_sums", image), uint8_ok=True)
     B, H, W = lab.shape
-    if max(H, W) > MEASURE_EDGE:
-        raise ValueError("cell_sums: H and W must be <= %d, got %d x %d" % (MEASURE_EDGE, H, W))
+    _measure_sizes("cell_sums", B, H, W)
     if n_max is None:
         (n_max,) = _id_range("cell_sums", lab)
-    elif isinstance(n_max, bool) or not isinstance(n_max, (int, np.integer)) or not 0 <= n_max < 1 << 24:
-        raise ValueError("cell_sums: n_max must be None or an integer in [0, 2^24), got %r" % (n_max,))
-    n_max = int(n_max)
+    n_max = int(_int_in(n_max, 0, 1 << 24, "cell_sums: n_max must be None or an integer in [0, 2^24), got %r"))
     dev, N = lab.device, n_max + 1
     isfloat = icode == 1
     area = torch.empty(B, N, dtype=torch.int64, device=dev)
@@ -316,10 +397,9 @@ def cell_sums(labels, image=None, *, n_max=None):
     present = torch.empty(B, N, dtype=torch.bool, device=dev)
     status = torch.empty(B, 2, dtype=torch.int64, device=dev)
     scratch = _hip.scratch("unet_cell_sums", dev, B, n_max)
-    _hip.run("unet_cell_sums", dev, _hip.ptr(lab), 0 if lab.dtype == torch.int64 else 2, _hip.ptr(img), icode, B, H, W, n_max,
-             _hip.ptr(area), _hip.ptr(bbox), _hip.ptr(moments), _hip.ptr(edges), _hip.ptr(vsum), _hip.ptr(vrange), _hip.ptr(present),
-             _hip.ptr(status), _hip.ptr(scratch))
-    bad_id, bad_v = (int(v) for v in status.cpu().sum(dim=0))
+    _hip.run("unet_cell_sums", dev, _hip.ptr(lab), _id_code(lab), _hip.ptr(img), icode, B, H, W, n_max, _hip.ptr(area), _hip.ptr(bbox),
+             _hip.ptr(moments), _hip.ptr(edges), _hip.ptr(vsum), _hip.ptr(vrange), _hip.ptr(present), _hip.ptr(status), _hip.ptr(scratch))
+    bad_id, bad_v = _status_words(status)
     if bad_id:
         raise ValueError("cell_sums: %d pixels hold ids outside [0, %d]" % (bad_id, n_max))
     if bad_v:
@@ -328,7 +408,7 @@ def cell_sums(labels, image=None, *, n_max=None):
     out = [area, bbox, moments, edges[..., 0], edges[..., 1], edges[..., 2]]
     out += [None] * 4 if img is None else [vsum[..., 0], vsum[..., 1], vrange[..., 0], vrange[..., 1]]
     out.append(present)
-    return CellSums(*(t if t is None or labels.dim() == 3 else t[0] for t in out))
+    return CellSums(*_unbatch(labels, *out))
 
 
 def _exact_variance(on, n, s2, p, q):
@@ -365,9 +445,7 @@ def props_from_sums(sums):
       touches_frame        bool, frame > 0 (False for an absent id)
       mean, std, min, max  of the image (std is the population one); None when the table has no image.  For an integer image
                            the variance is (area * sum v^2 - (sum v)^2) / area^2 with exact integers."""
-    def host(t):
-        return None if t is None else (t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t))
-    s = CellSums(*(host(t) for t in sums))
+    s = CellSums(*(None if t is None else _host(t) for t in sums))
     on = s.present.astype(bool) & (s.area > 0)
     nan = np.where(on, 0.0, np.nan)
     a = s.area.astype(np.int64)
@@ -426,8 +504,7 @@ def select_cells(labels, keep, *, renumber=False):
     B, H, W = lab.shape
     if keep.dim() == 2 and keep.shape[0] != B:
         raise ValueError("select_cells: keep holds %d images, the labels %d" % (keep.shape[0], B))
-    if max(H, W) > MEASURE_EDGE:
-        raise ValueError("select_cells: H and W must be <= %d, got %d x %d" % (MEASURE_EDGE, H, W))
+    _measure_sizes("select_cells", B, H, W)
     n_max = keep.shape[-1] - 1
     if n_max >= 1 << 24:
         raise ValueError("select_cells: ids must be below 2^24, keep has %d entries" % (n_max + 1))
@@ -437,12 +514,12 @@ def select_cells(labels, keep, *, renumber=False):
     table = torch.where(k, ids, torch.zeros((), dtype=torch.int32, device=lab.device)).contiguous()
     out = torch.empty(B, H, W, dtype=torch.int32, device=lab.device)
     status = torch.empty(B, dtype=torch.int64, device=lab.device)
-    _hip.run("unet_remap_labels", lab.device, _hip.ptr(lab), 0 if lab.dtype == torch.int64 else 2, B, H, W, _hip.ptr(table), n_max,
-             n_max + 1 if keep.dim() == 2 else 0, _hip.ptr(out), _hip.ptr(status))
-    bad = int(status.sum())
+    _hip.run("unet_remap_labels", lab.device, _hip.ptr(lab), _id_code(lab), B, H, W, _hip.ptr(table), n_max, n_max + 1 if keep.dim() == 2 else 0,
+             _hip.ptr(out), _hip.ptr(status))
+    (bad,) = _status_words(status)
     if bad:
         raise ValueError("select_cells: %d pixels hold ids outside [0, %d]" % (bad, n_max))
-    return out[0] if labels.dim() == 2 else out
+    return _unbatch(labels, out)
 
 
 # ---- convex hulls and neighbours of the cells ---------------------------------------------------------------------------
@@ -472,8 +549,7 @@ def cell_hulls(labels, sums=None, *, n_max=None):
     (lab,) = _id_maps("cell_hulls", "unet_cell_hulls", labels)
     import _hip
     B, H, W = lab.shape
-    if max(H, W) > MEASURE_EDGE:
-        raise ValueError("cell_hulls: H and W must be <= %d, got %d x %d" % (MEASURE_EDGE, H, W))
+    _measure_sizes("cell_hulls", B, H, W)
     if sums is None:
         sums = cell_sums(labels, n_max=n_max)
     bbox, present = sums.bbox, sums.present
@@ -482,8 +558,8 @@ def cell_hulls(labels, sums=None, *, n_max=None):
         raise ValueError("cell_hulls: sums must be the CellSums of cell_sums(labels) (bbox int32 [.., n_max+1, 4])")
     _device_only("cell_hulls", "unet_cell_hulls", bbox, present)
     N = bbox.shape[-2]
-    if n_max is not None and (isinstance(n_max, bool) or not isinstance(n_max, (int, np.integer)) or int(n_max) + 1 != N):
-        raise ValueError("cell_hulls: n_max = %r does not match the %d rows of sums" % (n_max, N))
+    if n_max is not None:
+        _int_in(n_max, N - 1, N, "cell_hulls: n_max = %%r does not match the %d rows of sums" % N)
     n_max, dev = N - 1, lab.device
     bbox, present = bbox.reshape(B, N, 4).contiguous(), present.reshape(B, N).bool()
     levels = torch.where(present, (bbox[..., 2] - bbox[..., 0] + 1).long(), torch.zeros((), dtype=torch.int64, device=dev))
@@ -498,16 +574,16 @@ def cell_hulls(labels, sums=None, *, n_max=None):
     vertices = torch.empty(2 * L, 2, dtype=torch.int32, device=dev)
     status = torch.empty(B, 2, dtype=torch.int64, device=dev)
     scratch = _hip.scratch("unet_cell_hulls", dev, L)
-    _hip.run("unet_cell_hulls", dev, _hip.ptr(lab), 0 if lab.dtype == torch.int64 else 2, B, H, W, n_max, _hip.ptr(bbox), _hip.ptr(offset), L,
-             _hip.ptr(n_vertices), _hip.ptr(area2), _hip.ptr(feret_max2), _hip.ptr(width), _hip.ptr(vertices) if L else None, _hip.ptr(status),
+    _hip.run("unet_cell_hulls", dev, _hip.ptr(lab), _id_code(lab), B, H, W, n_max, _hip.ptr(bbox), _hip.ptr(offset), L, _hip.ptr(n_vertices),
+             _hip.ptr(area2), _hip.ptr(feret_max2), _hip.ptr(width), _hip.ptr(vertices) if L else None, _hip.ptr(status),
              _hip.ptr(scratch) if L else None)
-    bad_id, outside = (int(v) for v in status.cpu().sum(dim=0))
+    bad_id, outside = _status_words(status)
     if bad_id:
         raise ValueError("cell_hulls: %d pixels hold ids outside [0, %d]" % (bad_id, n_max))
     if outside:
         raise ValueError("cell_hulls: %d pixels lie outside the box that sums gives for their id" % outside)
     out = [n_vertices, area2, feret_max2, width[..., 0], width[..., 1]]
-    return CellHulls(*(t if labels.dim() == 3 else t[0] for t in out), offset, vertices)
+    return CellHulls(*_unbatch(labels, *out), offset, vertices)
 
 
 def hull_props(hulls, sums):
@@ -521,13 +597,11 @@ def hull_props(hulls, sums):
       feret_min         c / sqrt(l2), the smallest calliper width
       convex_perimeter  the sum of the vertex-to-vertex lengths around the hull
       n_vertices        int32 as in the table (0 for an absent id)"""
-    def host(t):
-        return t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
-    h = CellHulls(*(host(t) for t in hulls))
+    h = CellHulls(*(_host(t) for t in hulls))
     k = h.n_vertices.astype(np.int64)
     on = k > 0
     nan = np.where(on, 0.0, np.nan)
-    area = host(sums.area).astype(np.float64)
+    area = _host(sums.area).astype(np.float64)
     if area.shape != k.shape:
         raise ValueError("hull_props: hulls %s and sums %s do not belong together" % (k.shape, area.shape))
     with np.errstate(invalid="ignore", divide="ignore"):
@@ -554,13 +628,12 @@ def cell_neighbours(labels, *, _table_slots=None):
     (lab,) = _id_maps("cell_neighbours", "unet_cell_contacts", labels)
     import _hip
     B, H, W = lab.shape
-    if max(H, W) > MEASURE_EDGE:
-        raise ValueError("cell_neighbours: H and W must be <= %d, got %d x %d" % (MEASURE_EDGE, H, W))
+    _measure_sizes("cell_neighbours", B, H, W)
     (n_max,) = _id_range("cell_neighbours", lab)
     dev = lab.device
     n_pairs = torch.empty(1, dtype=torch.int64, device=dev)
     (keys, counts, _), _ = _table_call(
-        "unet_cell_contacts", dev, B, (_hip.ptr(lab), 0 if lab.dtype == torch.int64 else 2, B, H, W, n_max), _table_slots, 8 * n_max, lambda slots: (B, slots),
+        "unet_cell_contacts", dev, B, (_hip.ptr(lab), _id_code(lab), B, H, W, n_max), _table_slots, 8 * n_max, lambda slots: (B, slots),
         lambda slots: (torch.empty(slots, dtype=torch.int64, device=dev), torch.empty(slots, dtype=torch.int32, device=dev), n_pairs),
         "cell_neighbours: %d pixels hold ids outside [0, %d]", (n_max,))
     return Neighbours(*_sorted_pairs(keys, counts, n_pairs))
@@ -633,19 +706,14 @@ def grow_cells(labels, max_distance=None):
     Negative ids and ids >= 2^24 raise ValueError; host tensors raise NotImplementedError (no CPU path)."""
     (lab,) = _id_maps("grow_cells", "unet_grow_labels", labels)
     import _hip
-    if max_distance is None or max_distance == math.inf:
-        max_dist2 = -1
-    else:
-        if not max_distance >= 0:
-            raise ValueError("grow_cells: max_distance must be None or a number >= 0, got %r" % (max_distance,))
-        max_dist2 = min(int(math.floor(float(max_distance) ** 2)), 1 << 40)
+    max_dist2 = _limit("grow_cells", "max_distance", max_distance, square=True)
     _id_range("grow_cells", lab)
     lab = lab.int()
     B, H, W = lab.shape
     out = torch.empty_like(lab)
     scratch = _hip.scratch("unet_grow_labels", lab.device, B, H, W)
     _hip.run("unet_grow_labels", lab.device, _hip.ptr(lab), B, H, W, max_dist2, _hip.ptr(out), _hip.ptr(scratch))
-    return out[0] if labels.dim() == 2 else out
+    return _unbatch(labels, out)
 
 
 def pair_table(pred_labels, gt_labels, *, _table_slots=None):
@@ -681,8 +749,8 @@ def _link_frames(name, labels, reach, slots):
         raise ValueError("%s takes a time-lapse of id maps [T,H,W], got %s" % (name, tuple(labels.shape)))
     if torch.is_tensor(labels) and labels.shape[0] > MAX_FRAMES:
         raise ValueError("%s: at most %d frames, got %d" % (name, MAX_FRAMES, labels.shape[0]))
-    if reach is not None and not (isinstance(reach, (int, float)) and not isinstance(reach, bool) and reach >= 0):
-        raise ValueError("%s: reach must be None or a number >= 0, got %r" % (name, reach))
+    if reach is not None:
+        _real_in(reach, 0, math.inf, name + ": reach must be None or a number >= 0, got %r")
     (lab,) = _id_maps(name, "unet_link_frames", labels)
     (n_max,) = _id_range(name, lab)
     import _hip
@@ -724,10 +792,8 @@ class Tracks(collections.namedtuple("Tracks", "table track_of")):
 
 
 def _track_rules(name, min_overlap, divisions, max_children):
-    if not (isinstance(min_overlap, (int, float)) and not isinstance(min_overlap, bool) and 0 <= min_overlap <= 1):
-        raise ValueError("%s: min_overlap must be a number in [0, 1], got %r" % (name, min_overlap))
-    if isinstance(max_children, bool) or not isinstance(max_children, (int, np.integer)) or max_children < 1:
-        raise ValueError("%s: max_children must be an int >= 1, got %r" % (name, max_children))
+    _real_in(min_overlap, 0, 1, name + ": min_overlap must be a number in [0, 1], got %r")
+    _int_in(max_children, 1, math.inf, name + ": max_children must be an int >= 1, got %r")
     if divisions not in (False, True):
         raise ValueError("%s: divisions must be False or True, got %r" % (name, divisions))
 
@@ -783,8 +849,8 @@ def track_cells(labels, *, reach=None, min_overlap=0.0, divisions=True, max_chil
     the device (unet_remap_labels with one map per frame); only the [T][n_max+1] rows cross to the host and back.  labels as
     link_frames takes them, H, W <= 32768.  Returns (track_maps, tracks): track_maps int32 [T,H,W] on the labels' device, 0 where
     labels is 0; tracks the Tracks, whose ctc_text() is the challenge's res_track.txt for these maps."""
-    if torch.is_tensor(labels) and labels.dim() == 3 and max(labels.shape[1:]) > MEASURE_EDGE:
-        raise ValueError("track_cells: H and W must be <= %d, got %d x %d" % ((MEASURE_EDGE,) + tuple(labels.shape[1:])))
+    if torch.is_tensor(labels) and labels.dim() == 3:
+        _measure_sizes("track_cells", *labels.shape)
     _track_rules("track_cells", min_overlap, divisions, max_children)
     lab, n_max, links = _link_frames("track_cells", labels, reach, _table_slots)
     tracks = tracks_from_links(links, min_overlap=min_overlap, divisions=divisions, max_children=max_children)
@@ -908,22 +974,12 @@ def warp_labels(gt_mask, pred_mask, *, reach=None, mask=None, connectivity=4, _p
     changes any result.  Unequal shapes, a bad connectivity and reach < 0 raise ValueError; host tensors raise
     NotImplementedError (no CPU path)."""
     tensors = [gt_mask, pred_mask] + ([] if mask is None else [mask])
-    if any(not torch.is_tensor(t) for t in tensors):
-        raise NotImplementedError("warp_labels takes tensors on the HIP device (unet_warp_init); there is no CPU implementation")
-    if any(t.shape != gt_mask.shape for t in tensors):
-        raise ValueError("warp_labels takes masks of equal shape, got %s" % ", ".join(str(tuple(t.shape)) for t in tensors))
-    if connectivity not in (4, 8):
-        raise ValueError("warp_labels: connectivity must be 4 or 8, got %r" % (connectivity,))
-    if reach is None or reach == math.inf:
-        max_dist2 = -1
-    else:
-        if not reach >= 0:
-            raise ValueError("warp_labels: reach must be None or a number >= 0, got %r" % (reach,))
-        max_dist2 = min(int(math.floor(float(reach) ** 2)), 1 << 40)
-    planes = [_planes("warp_labels", t) for t in tensors]
-    _device_only("warp_labels", "unet_warp_init", *tensors)
+    _all_tensors("warp_labels", "unet_warp_init", tensors)
+    _same_shape("warp_labels", "masks of equal shape", tensors, ranked=False)
+    _check_connectivity("warp_labels", connectivity)
+    max_dist2 = _limit("warp_labels", "reach", reach, square=True)
+    coded = [_int_code(t, uint8_ok=True) for t in _device_planes("warp_labels", "unet_warp_init", tensors)]
     import _hip
-    coded = [_int_code(t, uint8_ok=True) for t in planes]
     (gt, gt_code), (pred, pred_code) = coded[:2]
     user, user_code = coded[2] if mask is not None else (None, 0)
     B, H, W = gt.shape
@@ -946,10 +1002,9 @@ def warp_labels(gt_mask, pred_mask, *, reach=None, mask=None, connectivity=4, _p
     mismatch_map = torch.empty(B, H, W, dtype=torch.float32, device=dev)
     _hip.run("unet_warp_finish", dev, _hip.ptr(state), B, H, W, connectivity, _hip.ptr(warped), _hip.ptr(mismatch_map), _hip.ptr(counts[1]))
     before, after = counts.cpu().numpy().astype(np.int64)
-    single = gt_mask.dim() == 2
-    return (warped[0] if single else warped), WarpCounts(
-        mismatch=after, mismatch_before=before, flips=per_sweep.sum(axis=0), sweeps=int(np.argmin(per_sweep.any(axis=1))) + 1,
-        mismatch_map=mismatch_map[0] if single else mismatch_map)
+    warped, mismatch_map = _unbatch(gt_mask, warped, mismatch_map)
+    return warped, WarpCounts(mismatch=after, mismatch_before=before, flips=per_sweep.sum(axis=0),
+                              sweeps=int(np.argmin(per_sweep.any(axis=1))) + 1, mismatch_map=mismatch_map)
 
 
 def warping_error(pred_mask, gt_mask, *, reach=None, mask=None, connectivity=4):
@@ -1036,24 +1091,15 @@ def split_cells(seeds, mask, *, max_steps=None, orphans='drop', return_distance=
     above, not by a parameter of this function: inspect.signature shows the parameters above, which tests/test_split_cpu.py pins.
     A connectivity other than 4 or 8 (checked first), unequal shapes, max_steps < 0, a bad orphans,
     negative ids and ids >= 2^24 raise ValueError; host tensors raise NotImplementedError (no CPU path)."""
-    if not (torch.is_tensor(seeds) and torch.is_tensor(mask)):
-        raise NotImplementedError("split_cells takes tensors on the HIP device (unet_geodesic_init); there is no CPU implementation")
-    if seeds.shape != mask.shape or seeds.dim() not in (2, 3):
-        raise ValueError("split_cells takes seeds and a mask of equal shape [H,W] or [B,H,W], got %s, %s" % (tuple(seeds.shape), tuple(mask.shape)))
-    if seeds.dtype not in (torch.int32, torch.int64):
-        raise ValueError("split_cells takes int32 or int64 seed ids, got %s" % seeds.dtype)
+    _all_tensors("split_cells", "unet_geodesic_init", (seeds, mask))
+    _same_shape("split_cells", "seeds and a mask of equal shape [H,W] or [B,H,W]", (seeds, mask))
+    _need_ids("split_cells", "seed ids", seeds)
     if orphans not in ('drop', 'keep'):
         raise ValueError("split_cells: orphans must be 'drop' or 'keep', got %r" % (orphans,))
-    if max_steps is None or max_steps == math.inf:
-        steps = -1
-    else:
-        if not max_steps >= 0:
-            raise ValueError("split_cells: max_steps must be None or a number >= 0, got %r" % (max_steps,))
-        steps = min(int(math.floor(max_steps)), 1 << 40)
+    steps = _limit("split_cells", "max_steps", max_steps)
     if int(_launches) < 1:
         raise ValueError("split_cells: _launches must be >= 1")
-    sd, mk = _planes("split_cells", seeds), _planes("split_cells", mask)
-    _device_only("split_cells", "unet_geodesic_init", seeds, mask)
+    sd, mk = _device_planes("split_cells", "unet_geodesic_init", (seeds, mask))
     import _hip
     _id_range("split_cells", sd)
     sd = sd.int()
@@ -1074,10 +1120,8 @@ def split_cells(seeds, mask, *, max_steps=None, orphans='drop', return_distance=
         n0 = sd.amax(dim=(1, 2)).view(B, 1, 1)
         labels = torch.where(rest > 0, rest + n0, labels)
     outside, unreached, far = counts.cpu().numpy().astype(np.int64)
-    single = seeds.dim() == 2
-    info = SplitInfo(seeds_outside=outside, unreached=unreached, max_distance=far, launches=launches)
-    out = (labels[0] if single else labels, info)
-    return out + ((dist[0] if single else dist),) if return_distance else out
+    out = (_unbatch(seeds, labels), SplitInfo(seeds_outside=outside, unreached=unreached, max_distance=far, launches=launches))
+    return out + (_unbatch(seeds, dist),) if return_distance else out
 
 
 FloodInfo = collections.namedtuple("FloodInfo", "seeds_outside unreached max_level launches")
@@ -1119,30 +1163,19 @@ def watershed(seeds, image, *, mask=None, levels=None, max_level=None, return_le
     finite (counted by the kernel), negative ids and ids >= 2^24 raise ValueError; host tensors raise NotImplementedError (no CPU
     path)."""
     tensors = [seeds, image] + ([] if mask is None else [mask])
-    if any(not torch.is_tensor(t) for t in tensors):
-        raise NotImplementedError("watershed takes tensors on the HIP device (unet_flood_init); there is no CPU implementation")
-    if any(t.shape != seeds.shape for t in tensors) or seeds.dim() not in (2, 3):
-        raise ValueError("watershed takes seeds, an image and a mask of equal shape [H,W] or [B,H,W], got %s"
-                         % ", ".join(str(tuple(t.shape)) for t in tensors))
-    if seeds.dtype not in (torch.int32, torch.int64):
-        raise ValueError("watershed takes int32 or int64 seed ids, got %s" % seeds.dtype)
+    _all_tensors("watershed", "unet_flood_init", tensors)
+    _same_shape("watershed", "seeds, an image and a mask of equal shape [H,W] or [B,H,W]", tensors)
+    _need_ids("watershed", "seed ids", seeds)
     if image.is_complex():
         raise ValueError("watershed takes a real image, got %s" % image.dtype)
     if image.is_floating_point():
-        if isinstance(levels, bool) or not isinstance(levels, int) or not 1 <= levels <= FLOOD_LEVELS:
-            raise ValueError("watershed: a float image needs levels, an int in [1, %d], got %r" % (FLOOD_LEVELS, levels))
+        _int_in(levels, 1, FLOOD_LEVELS + 1, "watershed: a float image needs levels, an int in [1, %d], got %%r" % FLOOD_LEVELS, (int,))
     elif levels is not None:
         raise ValueError("watershed: levels is for float images; an integer image is read as it is, got levels=%r for %s" % (levels, image.dtype))
-    if max_level is None or max_level == math.inf:
-        top = -1
-    else:
-        if not max_level >= 0:
-            raise ValueError("watershed: max_level must be None or a number >= 0, got %r" % (max_level,))
-        top = min(int(math.floor(max_level)), FLOOD_LEVELS)
+    top = _limit("watershed", "max_level", max_level, cap=FLOOD_LEVELS)
     if int(_launches) < 1:
         raise ValueError("watershed: _launches must be >= 1")
-    planes = [_planes("watershed", t) for t in tensors]
-    _device_only("watershed", "unet_flood_init", *tensors)
+    planes = _device_planes("watershed", "unet_flood_init", tensors)
     import _hip
     _id_range("watershed", planes[0])
     sd = planes[0].int()
@@ -1168,10 +1201,8 @@ def watershed(seeds, image, *, mask=None, levels=None, max_level=None, return_le
     _hip.run("unet_flood_finish", dev, B, H, W, _hip.ptr(labels), _hip.ptr(lev), _hip.ptr(dist), _hip.ptr(counts[1]), _hip.ptr(counts[2]),
              _hip.ptr(scratch))
     outside, unreached, high = counts.cpu().numpy().astype(np.int64)
-    single = seeds.dim() == 2
-    info = FloodInfo(seeds_outside=outside, unreached=unreached, max_level=high, launches=tuple(launches))
-    out = (labels[0] if single else labels, info)
-    return out + ((lev[0], dist[0]) if single else (lev, dist)) if return_levels else out
+    out = (_unbatch(seeds, labels), FloodInfo(seeds_outside=outside, unreached=unreached, max_level=high, launches=tuple(launches)))
+    return out + _unbatch(seeds, lev, dist) if return_levels else out
 
 
 _EDGES = {'ignore': 0, 'background': 1}
@@ -1196,16 +1227,13 @@ def distance_map(mask, *, edge='ignore'):
         raise NotImplementedError("distance_map takes a tensor on the HIP device (unet_distance_map); there is no CPU implementation")
     if edge not in _EDGES:
         raise ValueError("distance_map: edge must be 'ignore' or 'background', got %r" % (edge,))
-    mk = _planes("distance_map", mask)
-    B, H, W = mk.shape
-    _shape_sizes("distance_map", B, H, W)
-    _device_only("distance_map", "unet_distance_map", mask)
+    mk, code = _int_code(*_device_planes("distance_map", "unet_distance_map", [mask], _shape_sizes), uint8_ok=True)
     import _hip
-    mk, code = _int_code(mk, uint8_ok=True)
+    B, H, W = mk.shape
     d2 = torch.empty(B, H, W, dtype=torch.int32, device=mk.device)
     scratch = _hip.scratch("unet_distance_map", mk.device, B, H, W)
     _hip.run("unet_distance_map", mk.device, _hip.ptr(mk), code, B, H, W, _EDGES[edge], _hip.ptr(d2), _hip.ptr(scratch))
-    return d2[0] if mask.dim() == 2 else d2
+    return _unbatch(mask, d2)
 
 
 ReconInfo = collections.namedtuple("ReconInfo", "launches raised")
@@ -1228,21 +1256,14 @@ def reconstruct(marker, under, *, mask=None, connectivity=4, _launches=8):
     (counted by the kernel), H or W above 32767 raise ValueError; host tensors raise NotImplementedError (no CPU path)."""
     _check_connectivity("reconstruct", connectivity)
     tensors = [marker, under] + ([] if mask is None else [mask])
-    if any(not torch.is_tensor(t) for t in tensors):
-        raise NotImplementedError("reconstruct takes tensors on the HIP device (unet_reconstruct_init); there is no CPU implementation")
-    if any(t.shape != marker.shape for t in tensors) or marker.dim() not in (2, 3):
-        raise ValueError("reconstruct takes marker, under and mask of equal shape [H,W] or [B,H,W], got %s"
-                         % ", ".join(str(tuple(t.shape)) for t in tensors))
-    for t in tensors[:2]:
-        if t.dtype not in (torch.int32, torch.int64):
-            raise ValueError("reconstruct takes int32 or int64 marker and under, got %s" % t.dtype)
+    _all_tensors("reconstruct", "unet_reconstruct_init", tensors)
+    _same_shape("reconstruct", "marker, under and mask of equal shape [H,W] or [B,H,W]", tensors)
+    _need_ids("reconstruct", "marker and under", marker, under)
     if int(_launches) < 1:
         raise ValueError("reconstruct: _launches must be >= 1")
-    planes = [_planes("reconstruct", t) for t in tensors]
-    B, H, W = planes[0].shape
-    _shape_sizes("reconstruct", B, H, W)
-    _device_only("reconstruct", "unet_reconstruct_init", *tensors)
+    planes = _device_planes("reconstruct", "unet_reconstruct_init", tensors, _shape_sizes)
     import _hip
+    B, H, W = planes[0].shape
     (mr, mr_code), (un, un_code) = _int_code(planes[0]), _int_code(planes[1])
     mk, mk_code = _int_code(planes[2], uint8_ok=True) if mask is not None else (None, 0)
     dev = mr.device
@@ -1259,8 +1280,7 @@ def reconstruct(marker, under, *, mask=None, connectivity=4, _launches=8):
     launches = _sweep_to_idle("unet_reconstruct_sweeps_conn", dev, B, _launches, (B, H, W, connectivity), (_hip.ptr(scratch),), values_ok)
     out = torch.empty(B, H, W, dtype=torch.int32, device=dev)
     _hip.run("unet_reconstruct_finish", dev, B, H, W, _hip.ptr(out), _hip.ptr(raised), _hip.ptr(scratch))
-    info = ReconInfo(launches=launches, raised=raised.cpu().numpy().astype(np.int64))
-    return (out[0] if marker.dim() == 2 else out), info
+    return _unbatch(marker, out), ReconInfo(launches=launches, raised=raised.cpu().numpy().astype(np.int64))
 
 
 def shape_seeds(mask, h=2.0, *, min_radius=0.0, edge='ignore', connectivity=4):
@@ -1288,10 +1308,8 @@ def shape_seeds(mask, h=2.0, *, min_radius=0.0, edge='ignore', connectivity=4):
     _check_connectivity("shape_seeds", connectivity)
     if not torch.is_tensor(mask):
         raise NotImplementedError("shape_seeds takes a tensor on the HIP device (unet_distance_map); there is no CPU implementation")
-    if isinstance(h, bool) or not isinstance(h, (int, float)) or not 0 <= h <= 1 << 24:
-        raise ValueError("shape_seeds: h must be a number in [0, 2^24], got %r" % (h,))
-    if isinstance(min_radius, bool) or not isinstance(min_radius, (int, float)) or not min_radius >= 0:
-        raise ValueError("shape_seeds: min_radius must be a number >= 0, got %r" % (min_radius,))
+    _real_in(h, 0, 1 << 24, "shape_seeds: h must be a number in [0, 2^24], got %r")
+    _real_in(min_radius, 0, math.inf, "shape_seeds: min_radius must be a number >= 0, got %r")
     hq, rq = int(round(16 * h)), int(min(math.ceil(16 * min(min_radius, 1 << 26)), 1 << 30))
     d2 = _planes("shape_seeds", distance_map(mask, edge=edge))
     import _hip
@@ -1306,7 +1324,7 @@ def shape_seeds(mask, h=2.0, *, min_radius=0.0, edge='ignore', connectivity=4):
     peaks = torch.empty(B, H, W, dtype=torch.float32, device=dev)
     _hip.run("unet_shape_maxima", dev, _hip.ptr(r1), _hip.ptr(r2), B, H, W, rq, _hip.ptr(peaks))
     seeds, n = label_cells(peaks, connectivity=connectivity)
-    return (seeds[0] if mask.dim() == 2 else seeds), n
+    return _unbatch(mask, seeds), n
 
 
 # ---- boundary scores: Hausdorff, its percentile, surface distance, surface Dice -------------------------------------------
@@ -1323,25 +1341,18 @@ def _boundary_rules(name, select, connectivity, edge):
         raise ValueError("%s: edge must be 'ignore' or 'background', got %r" % (name, edge))
     if select is None:
         return -1
-    if isinstance(select, bool) or not isinstance(select, (int, np.integer)) or not 0 <= select < 1 << 31:
-        raise ValueError("%s: select must be None or a class index in [0, 2^31), got %r" % (name, select))
-    return int(select)
+    return int(_int_in(select, 0, 1 << 31, name + ": select must be None or a class index in [0, 2^31), got %r"))
 
 
 def _boundary_masks(name, entry, *masks):
     """The checks of the boundary ops on one or two masks: tensors (NotImplementedError), rank, dtype, equal shapes, sizes
     (ValueError, on any device), then the device (NotImplementedError).  Returns [(contiguous [B,H,W], dtype code)]."""
-    if not all(torch.is_tensor(m) for m in masks):
-        raise NotImplementedError("%s takes tensors on the HIP device (%s); there is no CPU implementation" % (name, entry))
+    _all_tensors(name, entry, masks)
     for m in masks:
         if m.is_complex():
             raise ValueError("%s takes masks of a real dtype, got %s" % (name, m.dtype))
-    if any(m.shape != masks[0].shape for m in masks):
-        raise ValueError("%s takes masks of equal shape, got %s" % (name, ", ".join(str(tuple(m.shape)) for m in masks)))
-    planes = [_planes(name, m) for m in masks]
-    _shape_sizes(name, *planes[0].shape)
-    _device_only(name, entry, *masks)
-    return [_int_code(p, uint8_ok=True) for p in planes]
+    _same_shape(name, "masks of equal shape", masks, ranked=False)
+    return [_int_code(p, uint8_ok=True) for p in _device_planes(name, entry, masks, _shape_sizes)]
 
 
 def mask_boundary(mask, *, select=None, connectivity=4, edge='background'):
@@ -1357,7 +1368,7 @@ def mask_boundary(mask, *, select=None, connectivity=4, edge='background'):
     B, H, W = mk.shape
     out = torch.empty(B, H, W, dtype=torch.uint8, device=mk.device)
     _hip.run("unet_mask_boundary", mk.device, _hip.ptr(mk), code, k, B, H, W, connectivity, _EDGES[edge], _hip.ptr(out))
-    return out[0] if mask.dim() == 2 else out
+    return _unbatch(mask, out)
 
 
 def _surface_fraction(name, what, v):
@@ -1415,8 +1426,12 @@ def surface_sums(pred, gt, *, tolerances=(1.0,), percentile=95, select=None, con
     scratch = _hip.scratch("unet_surface_sums", dev, B, H, W)
     _hip.run("unet_surface_sums", dev, _hip.ptr(p), pcode, k, _hip.ptr(g), gcode, k, B, H, W, connectivity, _EDGES[edge], q_num, q_den,
              (ctypes.c_int * 4)(*(t2 + [0] * (4 - len(t2)))), len(t2), _hip.ptr(record), _hip.ptr(maps[0]), _hip.ptr(maps[1]), _hip.ptr(scratch))
-    single = pred.dim() == 2
-    return SurfaceSums(record[0] if single else record, *((m[0] if single and m is not None else m) for m in maps), tuple(t2), q_num, q_den)
+    return SurfaceSums(*_unbatch(pred, record, *maps), tuple(t2), q_num, q_den)
+
+
+def _check_spacing(name, spacing):
+    if isinstance(spacing, bool) or not isinstance(spacing, (int, float, np.integer, np.floating)) or not (math.isfinite(spacing) and spacing > 0):
+        raise ValueError("%s: spacing must be a positive finite number, got %r" % (name, spacing))
 
 
 def scores_from_surface(sums, *, spacing=1.0):
@@ -1433,10 +1448,8 @@ def scores_from_surface(sums, *, spacing=1.0):
     spacing, the size of a pixel, multiplies the distances; the tolerances were given to surface_sums in pixels (boundary_scores
     divides them).  Both contours empty: the distances are 0, nsd and boundary_f1 are 1; exactly one empty: inf and 0; precision
     (recall) is nan where pred's (gt's) contour is empty."""
-    if isinstance(spacing, bool) or not isinstance(spacing, (int, float, np.integer, np.floating)) or not (math.isfinite(spacing) and spacing > 0):
-        raise ValueError("scores_from_surface: spacing must be a positive finite number, got %r" % (spacing,))
-    rec = sums.record
-    rec = rec.detach().cpu().numpy() if torch.is_tensor(rec) else np.asarray(rec)
+    _check_spacing("scores_from_surface", spacing)
+    rec = _host(sums.record)
     if rec.dtype != np.int64 or rec.ndim not in (2, 3) or rec.shape[-2:] != (2, 10):
         raise ValueError("scores_from_surface: record must be int64 [B, 2, 10] or [2, 10], got %s %s" % (rec.dtype, rec.shape))
     single = rec.ndim == 2
@@ -1468,8 +1481,7 @@ def boundary_scores(pred, gt, *, tolerances=(1.0,), percentile=95, spacing=1.0, 
     """scores_from_surface(surface_sums(pred, gt, ...), spacing=spacing): the Hausdorff distance, its percentile, the average
     symmetric surface distance and the normalised surface Dice of a predicted mask against the ground truth, one read-back.
     tolerances are in the unit of spacing: they are divided by it, exactly, before they are squared."""
-    if isinstance(spacing, bool) or not isinstance(spacing, (int, float, np.integer, np.floating)) or not (math.isfinite(spacing) and spacing > 0):
-        raise ValueError("boundary_scores: spacing must be a positive finite number, got %r" % (spacing,))
+    _check_spacing("boundary_scores", spacing)
     s = _surface_fraction("boundary_scores", "spacing", spacing)
     tol = tuple(tolerances)
     for t in tol:
