@@ -38,8 +38,6 @@ formed from those links on the host, and the maps relabelled by track on the dev
 """
 import collections
 import fractions
-import functools
-import inspect
 import math
 
 import numpy as np
@@ -1047,25 +1045,10 @@ def _check_connectivity(name, connectivity):
         raise ValueError("%s: connectivity must be 4 or 8, got %r" % (name, connectivity))
 
 
-def _with_connectivity(fn):
-    """fn with the keyword connectivity=4, checked here before anything else and handed to fn as its last parameter
-    _connectivity, which the signature inspect reports leaves out: the parameter lists of split_cells and watershed are pinned by
-    tests/test_split_cpu.py and tests/test_flood_cpu.py, as segment's is (tester._with_steps)."""
-    sig = inspect.signature(fn)
-
-    @functools.wraps(fn)
-    def call(*args, connectivity=4, **kw):
-        _check_connectivity(fn.__name__, connectivity)
-        return fn(*args, _connectivity=connectivity, **kw)
-    call.__signature__ = sig.replace(parameters=[p for p in sig.parameters.values() if p.name != "_connectivity"])
-    return call
-
-
 SplitInfo = collections.namedtuple("SplitInfo", "seeds_outside unreached max_distance launches")
 
 
-@_with_connectivity
-def split_cells(seeds, mask, *, max_steps=None, orphans='drop', return_distance=False, _launches=8, _connectivity=4):
+def split_cells(seeds, mask, *, max_steps=None, orphans='drop', return_distance=False, _launches=8, connectivity=4):
     """Seeded geodesic growth inside a mask: split touching cells by growing seeds (confident cores, e.g.
     label_cells(fg_prob >= high)[0]) back inside the mask until two growths meet.  seeds: int32 / int64 ids [H,W] or [B,H,W] on a
     HIP device, 0 = no seed, ids in [1, 2^24), not necessarily consecutive or connected; mask: the same shape, of any dtype
@@ -1087,10 +1070,10 @@ def split_cells(seeds, mask, *, max_steps=None, orphans='drop', return_distance=
     connectivity: keyword only, 4 (the default, all of the above) or 8.  With 8 a step goes to any of the eight neighbours that
     lies in the region, whatever the two pixels beside a diagonal step are, so a one-pixel-thick diagonal wall does not separate.
     g(p) is the least number of 8-neighbour steps, max_steps counts those, the id rule is the same, and orphans='keep' labels
-    the rest with label_cells(..., connectivity=8) (unet_geodesic_sweeps_conn).  It is added by the decorator _with_connectivity
-    above, not by a parameter of this function: inspect.signature shows the parameters above, which tests/test_split_cpu.py pins.
+    the rest with label_cells(..., connectivity=8) (unet_geodesic_sweeps_conn).
     A connectivity other than 4 or 8 (checked first), unequal shapes, max_steps < 0, a bad orphans,
     negative ids and ids >= 2^24 raise ValueError; host tensors raise NotImplementedError (no CPU path)."""
+    _check_connectivity("split_cells", connectivity)
     _all_tensors("split_cells", "unet_geodesic_init", (seeds, mask))
     _same_shape("split_cells", "seeds and a mask of equal shape [H,W] or [B,H,W]", (seeds, mask))
     _need_ids("split_cells", "seed ids", seeds)
@@ -1110,13 +1093,13 @@ def split_cells(seeds, mask, *, max_steps=None, orphans='drop', return_distance=
     status = torch.empty(B, dtype=torch.int64, device=dev)
     scratch = _hip.scratch("unet_geodesic", dev, B, H, W)
     _hip.run("unet_geodesic_init", dev, _hip.ptr(sd), _hip.ptr(mk), code, B, H, W, _hip.ptr(counts[0]), _hip.ptr(status), _hip.ptr(scratch))
-    launches = _sweep_to_idle("unet_geodesic_sweeps_conn", dev, B, _launches, (B, H, W, steps, _connectivity), (_hip.ptr(scratch),))
+    launches = _sweep_to_idle("unet_geodesic_sweeps_conn", dev, B, _launches, (B, H, W, steps, connectivity), (_hip.ptr(scratch),))
     labels = torch.empty(B, H, W, dtype=torch.int32, device=dev)
     dist = torch.empty(B, H, W, dtype=torch.int32, device=dev) if return_distance else None
     _hip.run("unet_geodesic_finish", dev, B, H, W, steps, _hip.ptr(labels), _hip.ptr(dist), _hip.ptr(counts[1]), _hip.ptr(counts[2]),
              _hip.ptr(scratch))
     if orphans == 'keep':
-        rest, _ = label_cells((mk != 0) & (labels == 0), connectivity=_connectivity)
+        rest, _ = label_cells((mk != 0) & (labels == 0), connectivity=connectivity)
         n0 = sd.amax(dim=(1, 2)).view(B, 1, 1)
         labels = torch.where(rest > 0, rest + n0, labels)
     outside, unreached, far = counts.cpu().numpy().astype(np.int64)
@@ -1128,8 +1111,7 @@ FloodInfo = collections.namedtuple("FloodInfo", "seeds_outside unreached max_lev
 FLOOD_LEVELS = 1 << 16                                                 # levels of watershed are in [0, FLOOD_LEVELS)
 
 
-@_with_connectivity
-def watershed(seeds, image, *, mask=None, levels=None, max_level=None, return_levels=False, _launches=8, _connectivity=4):
+def watershed(seeds, image, *, mask=None, levels=None, max_level=None, return_levels=False, _launches=8, connectivity=4):
     """Seeded watershed: flood an intensity landscape from markers, Vincent-Soille immersion with exact geodesic influence zones
     on plateaus.  seeds: int32 / int64 ids [H,W] or [B,H,W] on a HIP device, 0 = no seed, ids in [1, 2^24); image: the same
     shape; mask: optional, the same shape, of any dtype _int_code takes: the region is mask != 0, everything without a mask.
@@ -1157,11 +1139,11 @@ def watershed(seeds, image, *, mask=None, levels=None, max_level=None, return_le
     lies in the region, whatever the two pixels beside a diagonal step are, so a one-pixel-thick diagonal wall does not separate.
     The extension of a key is the same, the minimum runs over eight neighbours, a parent is any of the eight whose key extends
     to exactly key(q), and on a constant image the result is split_cells(connectivity=8)'s, bit for bit (unet_flood_sweeps_conn,
-    unet_flood_assign_conn).  Added by the decorator _with_connectivity: inspect.signature shows the parameters above, which
-    tests/test_flood_cpu.py pins.
+    unet_flood_assign_conn).
     A connectivity other than 4 or 8 (checked first), unequal shapes, other seed dtypes, levels or max_level out of range, image values outside [0, 65536) or not
     finite (counted by the kernel), negative ids and ids >= 2^24 raise ValueError; host tensors raise NotImplementedError (no CPU
     path)."""
+    _check_connectivity("watershed", connectivity)
     tensors = [seeds, image] + ([] if mask is None else [mask])
     _all_tensors("watershed", "unet_flood_init", tensors)
     _same_shape("watershed", "seeds, an image and a mask of equal shape [H,W] or [B,H,W]", tensors)
@@ -1194,8 +1176,8 @@ def watershed(seeds, image, *, mask=None, levels=None, max_level=None, return_le
             raise ValueError("watershed: %d pixels hold an image value that is not finite" % bad if im_code == 1 else
                              "watershed: %d pixels hold an image value outside [0, %d)" % (bad, FLOOD_LEVELS))
 
-    launches = [_sweep_to_idle("unet_flood_sweeps_conn", dev, B, _launches, (B, H, W, top, _connectivity), (_hip.ptr(scratch),), values_ok),
-                _sweep_to_idle("unet_flood_assign_conn", dev, B, _launches, (B, H, W, _connectivity), (_hip.ptr(scratch),))]   # after an idle stage-1 launch
+    launches = [_sweep_to_idle("unet_flood_sweeps_conn", dev, B, _launches, (B, H, W, top, connectivity), (_hip.ptr(scratch),), values_ok),
+                _sweep_to_idle("unet_flood_assign_conn", dev, B, _launches, (B, H, W, connectivity), (_hip.ptr(scratch),))]   # after an idle stage-1 launch
     labels = torch.empty(B, H, W, dtype=torch.int32, device=dev)
     lev, dist = (torch.empty(2, B, H, W, dtype=torch.int32, device=dev) if return_levels else (None, None))
     _hip.run("unet_flood_finish", dev, B, H, W, _hip.ptr(labels), _hip.ptr(lev), _hip.ptr(dist), _hip.ptr(counts[1]), _hip.ptr(counts[2]),

@@ -8,8 +8,6 @@ images of any size and shape, [H,W] in, [H,W] mask out (unet_tile_gather, unet_f
 is its geometry.  segment(..., views=...) averages the class probabilities over dihedral views of each image (apply_view,
 undo_view, view_shape, parse_views; unet_tile_gather_view, unet_tile_stitch_view).  track(unet, frames) segments a time-lapse
 and links its cells across frames (functions.track_cells; unet_link_frames)."""
-import functools
-import inspect
 import os
 from time import time
 
@@ -17,7 +15,7 @@ import numpy as np
 import torch
 
 import _hip
-from functions import (FLOOD_LEVELS, _area, _check_connectivity, _with_connectivity, cell_props, clean_mask, evaluation_metrics, label_cells,
+from functions import (FLOOD_LEVELS, _area, _check_connectivity, cell_props, clean_mask, evaluation_metrics, label_cells,
                        metrics_from_counts, shape_seeds, split_cells, track_cells, watershed)
 import optim as hip_optim
 
@@ -188,7 +186,8 @@ VIEW_FIRST, VIEW_LAST = 1, 2        # unet_tile_stitch_view's phase bits: store 
 
 def _view_chunks(n_views, Tv, nb):
     """The tile list of n_views views of Tv tiles each, cut into chunks of at most nb: yields (t0, n, segments), a segment
-    being (index of the view in the list, first tile within that view, number of tiles, offset in the chunk)."""
+    being (index of the view in the list, first tile within that view, number of tiles, offset in the chunk).  One view: every
+    chunk is the one segment (0, t0, n, 0)."""
     T = n_views * Tv
     for t0 in range(0, T, nb):
         n = min(nb, T - t0)
@@ -201,15 +200,14 @@ def _view_chunks(n_views, Tv, nb):
         yield t0, n, segs
 
 
-@_with_connectivity
-def split_instances(mask, fg_prob, high, _connectivity=4):
+def split_instances(mask, fg_prob, high, *, connectivity=4):
     """The instance map of a foreground mask with touching cells split: the cores label_cells(fg_prob >= high)[0] are the seeds,
     functions.split_cells grows them back inside mask != 0 until two growths meet, and a component of the mask without a core
     stays a cell (orphans='keep').  mask and fg_prob [H,W] or [B,H,W] on a HIP device; returns int32 ids of the same shape.
-    connectivity: keyword only, 4 or 8 (else ValueError), for the cores' labelling, the growth and the orphans alike; added by
-    functions._with_connectivity, so inspect.signature shows the three parameters tests/test_split_cpu.py pins."""
-    seeds = label_cells(fg_prob >= high, connectivity=_connectivity)[0]
-    return split_cells(seeds, mask, orphans='keep', connectivity=_connectivity)[0]
+    connectivity: 4 or 8 (else ValueError, checked first), for the cores' labelling, the growth and the orphans alike."""
+    _check_connectivity("split_instances", connectivity)
+    seeds = label_cells(fg_prob >= high, connectivity=connectivity)[0]
+    return split_cells(seeds, mask, orphans='keep', connectivity=connectivity)[0]
 
 
 def split_by_shape(mask, h=2.0, min_radius=0.0, edge='ignore', *, connectivity=4):
@@ -222,26 +220,18 @@ def split_by_shape(mask, h=2.0, min_radius=0.0, edge='ignore', *, connectivity=4
     return split_cells(seeds, mask, orphans='keep', connectivity=connectivity)[0]
 
 
-@_with_connectivity
-def split_by_watershed(mask, fg_prob, high, levels=64, _connectivity=4):
+def split_by_watershed(mask, fg_prob, high, levels=64, *, connectivity=4):
     """The instance map of a foreground mask with touching cells split where the foreground probability dips: the cores
     label_cells(fg_prob >= high)[0] are the seeds, functions.watershed floods the landscape 1 - fg_prob (float32, quantised to
     `levels` levels) from them inside mask != 0, so two growths meet on the ridge of low probability between two cores and not
     halfway between them as in split_instances; a component of the mask without a core stays a cell, numbered after the seeds
     as split_cells(orphans='keep') numbers it.  mask and fg_prob [H,W] or [B,H,W] on a HIP device; returns int32 ids of the same
-    shape.  connectivity: keyword only, 4 or 8 (else ValueError), for the cores' labelling, the flood and the orphans alike; added
-    by functions._with_connectivity, so inspect.signature shows the four parameters tests/test_flood_cpu.py pins."""
-    seeds = label_cells(fg_prob >= high, connectivity=_connectivity)[0]
-    labels = watershed(seeds, 1 - fg_prob.float(), mask=mask, levels=levels, connectivity=_connectivity)[0]
-    rest = label_cells((mask != 0) & (labels == 0), connectivity=_connectivity)[0]
+    shape.  connectivity: 4 or 8 (else ValueError, checked first), for the cores' labelling, the flood and the orphans alike."""
+    _check_connectivity("split_by_watershed", connectivity)
+    seeds = label_cells(fg_prob >= high, connectivity=connectivity)[0]
+    labels = watershed(seeds, 1 - fg_prob.float(), mask=mask, levels=levels, connectivity=connectivity)[0]
+    rest = label_cells((mask != 0) & (labels == 0), connectivity=connectivity)[0]
     return torch.where(rest > 0, rest + seeds.amax(dim=(-2, -1), keepdim=True), labels)
-
-
-def _check_split(split, return_instances):
-    if not return_instances:
-        raise ValueError("segment: split needs return_instances=True")
-    if isinstance(split, bool) or not isinstance(split, (int, float)) or not 0 < split <= 1:
-        raise ValueError("segment: split must be None or a number in (0, 1], got %r" % (split,))
 
 
 def _parse_shape_split(v):
@@ -279,75 +269,53 @@ def _parse_clean(v, n_classes):
     return kw
 
 
-def _with_steps(fn):
-    """segment with the keywords watershed, connectivity and measure, three steps on the call's results.  watershed: the call
-    without its split (mask and probabilities only), then split_by_watershed of them as the instance map.  connectivity=8: the
-    call without instances (mask and probabilities only), then the instance map formed here, 8-connected throughout: label_cells,
-    split_instances, split_by_shape or split_by_watershed of them.  measure: functions.cell_props of the final instance map and
-    of the images the call was given, appended to the returned tuple.  The checks of all three come before any work."""
-    sig = inspect.signature(fn)
-
-    @functools.wraps(fn)
-    def segment(*args, measure=False, watershed=None, connectivity=None, **kw):
-        if connectivity is not None:
-            _check_connectivity("segment", connectivity)
-        if measure not in (False, True):
-            raise ValueError("segment: measure must be False or True, got %r" % (measure,))
-        if watershed is False:
-            watershed = None
-        if watershed is not None and watershed is not True and not (isinstance(watershed, int) and 1 <= watershed <= FLOOD_LEVELS):
-            raise ValueError("segment: watershed must be None, True (64 levels) or an int in [1, %d], got %r" % (FLOOD_LEVELS, watershed))
-        if not measure and watershed is None and connectivity is None:
-            return fn(*args, **kw)
-        call = sig.bind(*args, **kw)
-        call.apply_defaults()
-        given = call.arguments
-        if measure and not given["return_instances"]:
-            raise ValueError("segment: measure needs return_instances=True")
-        if connectivity is not None and not given["return_instances"]:
-            raise ValueError("segment: connectivity is the instance map's; it needs return_instances=True")
-        conn = 4 if connectivity is None else connectivity
-        if watershed is None and conn == 4:
-            out = fn(*args, **kw)
-        elif watershed is None:
-            split, shape_split = given["split"], given["shape_split"]
-            if split is not None:
-                _check_split(split, True)
-            if shape_split is not None:
-                if split is not None:
-                    raise ValueError("segment: shape_split and split are two ways to seed one growth; give one of them")
-                shape_split = _parse_shape_split(shape_split)
-            need_prob = given["return_probs"] or split is not None
-            got = fn(**dict(given, return_probs=need_prob, return_instances=False, split=None, shape_split=None))
-            mask, prob = got if need_prob else (got, None)
-            if split is not None:
-                fg = prob if getattr(given["unet"], 'n_classes', 2) == 2 else 1 - prob.select(-3, 0)
-                inst = split_instances(mask, fg, float(split), connectivity=8)
-            elif shape_split is not None:
-                inst = split_by_shape(mask, *shape_split, connectivity=8)
-            else:
-                inst = label_cells(mask, connectivity=8)[0]
-            out = (mask,) + ((prob,) if given["return_probs"] else ()) + (inst,)
-        else:
-            if given["split"] is None:
-                raise ValueError("segment: watershed needs split=high, the cores it floods from")
-            if given["shape_split"] is not None:
-                raise ValueError("segment: watershed floods the probabilities from the cores of split; it does not combine with shape_split")
-            _check_split(given["split"], given["return_instances"])
-            mask, prob = fn(**dict(given, return_probs=True, return_instances=False, split=None))
-            fg = prob if getattr(given["unet"], 'n_classes', 2) == 2 else 1 - prob.select(-3, 0)
-            inst = split_by_watershed(mask, fg, float(given["split"]), 64 if watershed is True else watershed, connectivity=conn)
-            out = (mask,) + ((prob,) if given["return_probs"] else ()) + (inst,)
-        if not measure:
-            return out
-        images = given["images"]
-        return out + (cell_props(out[-1], images if images.dtype == torch.float32 else images.to(torch.float32)),)
-    return segment
+def _check_keywords(return_instances, shape_split, split, measure, watershed, connectivity):
+    """The rules of segment's keywords that need no device, each stated once and checked in this order whatever else is given;
+    ValueError for the first one broken.  Returns (shape_split as (h, min_radius) or None, watershed as its levels or None)."""
+    if connectivity is not None:
+        _check_connectivity("segment", connectivity)
+    if measure not in (False, True):
+        raise ValueError("segment: measure must be False or True, got %r" % (measure,))
+    if watershed is False:
+        watershed = None
+    if watershed is not None and watershed is not True and not (isinstance(watershed, int) and 1 <= watershed <= FLOOD_LEVELS):
+        raise ValueError("segment: watershed must be None, True (64 levels) or an int in [1, %d], got %r" % (FLOOD_LEVELS, watershed))
+    if measure and not return_instances:
+        raise ValueError("segment: measure needs return_instances=True")
+    if connectivity is not None and not return_instances:
+        raise ValueError("segment: connectivity is the instance map's; it needs return_instances=True")
+    if watershed is not None and split is None:
+        raise ValueError("segment: watershed needs split=high, the cores it floods from")
+    if watershed is not None and shape_split is not None:
+        raise ValueError("segment: watershed floods the probabilities from the cores of split; it does not combine with shape_split")
+    if split is not None:
+        if not return_instances:
+            raise ValueError("segment: split needs return_instances=True")
+        if isinstance(split, bool) or not isinstance(split, (int, float)) or not 0 < split <= 1:
+            raise ValueError("segment: split must be None or a number in (0, 1], got %r" % (split,))
+    if shape_split is not None:
+        if not return_instances:
+            raise ValueError("segment: shape_split needs return_instances=True")
+        if split is not None:
+            raise ValueError("segment: shape_split and split are two ways to seed one growth; give one of them")
+        shape_split = _parse_shape_split(shape_split)
+    return shape_split, 64 if watershed is True else watershed
 
 
-@_with_steps
+def _instance_map(mask, fg_prob, split, shape_split, watershed, connectivity):
+    """The instance map segment returns, of the (cleaned) mask: split, shape_split and watershed as _check_keywords left them;
+    fg_prob is read only with split."""
+    if watershed is not None:
+        return split_by_watershed(mask, fg_prob, float(split), watershed, connectivity=connectivity)
+    if split is not None:
+        return split_instances(mask, fg_prob, float(split), connectivity=connectivity)
+    if shape_split is not None:
+        return split_by_shape(mask, *shape_split, connectivity=connectivity)
+    return label_cells(mask, connectivity=connectivity)[0]
+
+
 def segment(unet, images, tile_size=None, max_batch=16, normalise=True, return_probs=False, return_instances=False, views=None,
-            clean=None, shape_split=None, split=None):
+            clean=None, shape_split=None, split=None, *, measure=False, watershed=None, connectivity=None):
     """Segment images of any size and shape with the overlap-tile strategy; returns the int64 argmax mask of the same
     shape as `images` (and the float32 foreground probability softmax(logits)[1] with return_probs).  A K-class net
     (Unet(n_classes=K), K > 2) gives the K-way argmax (ties -> the lowest class) and, with return_probs, the softmax of all
@@ -374,11 +342,11 @@ def segment(unet, images, tile_size=None, max_batch=16, normalise=True, return_p
         about 6e-8, where 1 + exp(l0 - l1) rounds to 2).
     clean: None, True or a dict of functions.clean_mask's keyword arguments (fill_holes, max_hole_area, min_area, drop_border,
         connectivity): the mask is cleaned on the device right after the last stitch, on the same stream, before the instance map
-        (label_cells, split or shape_split) is made of it: holes filled, small cells and cells on the frame dropped.  True fills
-        all holes and does nothing else.  The mask returned is the cleaned one; the probabilities are untouched; it does not need
-        return_instances.  A hole in a cell is background to the distance map, so shape_split over-splits a cell that has one.
-        With a K > 2 net a filled pixel would have no class: fill_holes true raises ValueError there, min_area and drop_border
-        alone (fill_holes=False) are allowed and a kept pixel keeps its class.
+        is made of it: holes filled, small cells and cells on the frame dropped.  True fills all holes and does nothing else.
+        The mask returned is the cleaned one; the probabilities are untouched; it does not need return_instances.  A hole in a
+        cell is background to the distance map, so shape_split over-splits a cell that has one.  With a K > 2 net a filled
+        pixel would have no class: fill_holes true raises ValueError there, min_area and drop_border alone (fill_holes=False)
+        are allowed and a kept pixel keeps its class.
     split: None, or a float in (0, 1] (needs return_instances, else ValueError): the instance map becomes
         split_instances(mask, fg_prob, split), touching cells split by growing the cores fg_prob >= split back inside the mask
         (functions.split_cells), on the same stream after the last stitch.  fg_prob is the foreground probability of the call:
@@ -387,25 +355,25 @@ def segment(unet, images, tile_size=None, max_batch=16, normalise=True, return_p
         ValueError): the instance map becomes split_by_shape(mask, h, min_radius), touching cells split at the h-maxima of the
         mask's own distance map (functions.shape_seeds, functions.split_cells), on the same stream after the last stitch.  It
         reads the mask alone, so it works with views= as it does without.
-    measure: keyword only, False or True (needs return_instances, else ValueError): the returned tuple gains, after the
-        instance map, the functions.CellProps of functions.cell_props(instances, images): one row of shape and intensity
-        properties per cell of the final instance map (after clean and split), the intensities those of the input images as
-        given (not normalised).  The tuple is then (mask[, prob], instances, props).  It is a step on the call's results and is
-        added by the decorator _with_steps above, not by a parameter of this function: inspect.signature shows the parameters
-        above, which tests/test_clean_cpu.py and tests/test_split_cpu.py pin.
-    watershed: keyword only, None, True (64 levels) or an int in [1, 65536] (needs split, not together with shape_split, else
-        ValueError): the instance map becomes split_by_watershed(mask, fg_prob, split, levels): the cores fg_prob >= split flood
-        the landscape 1 - fg_prob inside the mask (functions.watershed), so the cut between two touching cells follows the dip in
-        foreground probability where split alone puts it halfway between the cores.  clean and measure compose with it as they do
-        with split.  Added by the same decorator.  Flooding the inverted distance map from the seeds of functions.shape_seeds is
-        a composition of functions.watershed and functions.distance_map and has no option here.
-    connectivity: keyword only, 4 or 8 (needs return_instances, else ValueError; anything else raises ValueError before any
-        work): the connectivity of the instance map.  With 8 it is made 8-connected throughout: label_cells(mask, connectivity=8),
-        or with split, shape_split or split + watershed, split_instances, split_by_shape or split_by_watershed with
-        connectivity=8 (cores or seeds, growth or flood, and orphans alike).  The mask and the probabilities are those of the call
-        without it; clean keeps its own connectivity key.  Added by the same decorator: mask and probabilities come from the
-        inner call without instances and the instance map is formed from them.
+    measure: False or True (needs return_instances, else ValueError): the returned tuple gains, after the instance map, the
+        functions.CellProps of functions.cell_props(instances, images): one row of shape and intensity properties per cell of
+        the instance map as returned (after clean and split), the intensities those of the input images as given (not
+        normalised).  The tuple is then (mask[, prob], instances, props).
+    watershed: None, True (64 levels) or an int in [1, 65536] (needs split, not together with shape_split, else ValueError):
+        the instance map becomes split_by_watershed(mask, fg_prob, split, levels): the cores fg_prob >= split flood the
+        landscape 1 - fg_prob inside the mask (functions.watershed), so the cut between two touching cells follows the dip in
+        foreground probability where split alone puts it halfway between the cores.  clean and measure compose with it as they
+        do with split.  Flooding the inverted distance map from the seeds of functions.shape_seeds is a composition of
+        functions.watershed and functions.distance_map and has no option here.
+    connectivity: None (not given: 4), 4 or 8 (given, it needs return_instances, else ValueError): the connectivity of the
+        instance map, throughout: label_cells(mask, connectivity=c), or with split, shape_split or split + watershed,
+        split_instances, split_by_shape or split_by_watershed with connectivity=c (cores or seeds, growth or flood, and orphans
+        alike).  The mask and the probabilities do not depend on it; clean keeps its own connectivity key.
+    The keywords are checked before anything else, in one order (_check_keywords): the values of connectivity, measure and
+    watershed, what each of them needs, then split and shape_split; then the images, device first; then max_batch, clean, views
+    and the tile size.
     Geometry and mirroring: tile_grid."""
+    shape_split, watershed = _check_keywords(return_instances, shape_split, split, measure, watershed, connectivity)
     if not images.is_cuda:
         raise RuntimeError("segment: the HIP path needs the images on a HIP device (got %s); there is no CPU fallback - "
                            "use unet.to('cuda:0') and images.to('cuda:0')" % images.device)
@@ -422,22 +390,17 @@ def segment(unet, images, tile_size=None, max_batch=16, normalise=True, return_p
         raise ValueError("segment: empty batch")
     if max_batch < 1:
         raise ValueError("segment: max_batch must be >= 1")
-    if split is not None:
-        _check_split(split, return_instances)
-    if shape_split is not None:
-        if not return_instances:
-            raise ValueError("segment: shape_split needs return_instances=True")
-        if split is not None:
-            raise ValueError("segment: shape_split and split are two ways to seed one growth; give one of them")
-        shape_split = _parse_shape_split(shape_split)
-    clean = _parse_clean(clean, getattr(unet, 'n_classes', 2))
+    K = getattr(unet, 'n_classes', 2)
+    clean = _parse_clean(clean, K)
     vs = None if views is None else parse_views(views)
+
     S = auto_tile_size(H, W) if tile_size is None else int(tile_size)
     _check_tile_size(S)
     So = S - 2 * TILE_MARGIN
-    ny, nx, oy0, ox0 = tile_grid(H, W, S)
-    T = B * ny * nx * (1 if vs is None else len(vs))        # a transposed view has as many tiles: its grid is (nx, ny)
-    nb = min(max_batch, T)
+    # one tile grid per view, whose tiles form one list; a transposed view has as many tiles: its grid is (nx, ny)
+    grids = [tile_grid(*view_shape(H, W, v), S) for v in ((0,) if vs is None else vs)]
+    Tv = B * grids[0][0] * grids[0][1]
+    nb = min(max_batch, len(grids) * Tv)
     dev = x.device
     h = unet._get_handle(dev.index)
     L = _hip.lib()
@@ -456,7 +419,6 @@ def segment(unet, images, tile_size=None, max_batch=16, normalise=True, return_p
             if flat:
                 raise ValueError("segment: image(s) %s are constant; normalise=True would divide by zero" % flat)
         tiles = torch.empty(nb, 1, S, S, dtype=torch.float32, device=dev)
-        K = getattr(unet, 'n_classes', 2)
         logits = torch.empty(nb, K, So, So, dtype=torch.float32, device=dev)
         nbytes = h.workspace_bytes(nb, S, False)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
@@ -465,44 +427,46 @@ def segment(unet, images, tile_size=None, max_batch=16, normalise=True, return_p
         if return_probs or vs is not None or split is not None:
             prob = torch.empty((B, H, W) if K == 2 else (B, K, H, W), dtype=torch.float32, device=dev)
         st = _hip.stream(dev)
-        for t0, n, segs in (_view_chunks(len(vs), B * ny * nx, nb) if vs is not None else ()):
-            grids = {k: tile_grid(*view_shape(H, W, vs[k]), S) for k, _, _, _ in segs}
+
+        # without views a chunk is one segment (0, t0, n, 0) of the one grid: the plain entries, the mask from l1 > l0
+        for _, n, segs in _view_chunks(len(grids), Tv, nb):
             for k, a, m, off in segs:
                 gy, gx, y0, x0 = grids[k]
-                _hip.check(L.unet_tile_gather_view(_hip.ptr(x), B, H, W, _hip.ptr(mm), S, vs[k], y0, x0, gy, gx, a, m,
-                                                   _hip.ptr(tiles[off:]), st), "unet_tile_gather_view")
+                if vs is None:
+                    _hip.check(L.unet_tile_gather(_hip.ptr(x), B, H, W, _hip.ptr(mm), S, y0, x0, gy, gx, a, m, _hip.ptr(tiles[off:]), st),
+                               "unet_tile_gather")
+                else:
+                    _hip.check(L.unet_tile_gather_view(_hip.ptr(x), B, H, W, _hip.ptr(mm), S, vs[k], y0, x0, gy, gx, a, m,
+                                                       _hip.ptr(tiles[off:]), st), "unet_tile_gather_view")
             _hip.check(L.unet_forward(h.h, ptab, _hip.ptr(tiles), _hip.ptr(logits), n, S, _hip.ptr(ws), nbytes, 0, st),
                        "unet_forward")
             for k, a, m, off in segs:
                 gy, gx, y0, x0 = grids[k]
-                phase = (VIEW_FIRST if k == 0 else 0) | (VIEW_LAST if k == len(vs) - 1 else 0)
-                _hip.check(L.unet_tile_stitch_view(_hip.ptr(logits[off:]), So, K, vs[k], y0, x0, gy, gx, a, m, B, H, W, phase,
-                                                   len(vs), _hip.ptr(prob), _hip.ptr(mask), st), "unet_tile_stitch_view")
-        for t0 in range(0, T, nb) if vs is None else ():
-            n = min(nb, T - t0)
-            _hip.check(L.unet_tile_gather(_hip.ptr(x), B, H, W, _hip.ptr(mm), S, oy0, ox0, ny, nx, t0, n, _hip.ptr(tiles), st),
-                       "unet_tile_gather")
-            _hip.check(L.unet_forward(h.h, ptab, _hip.ptr(tiles), _hip.ptr(logits), n, S, _hip.ptr(ws), nbytes, 0, st),
-                       "unet_forward")
-            if K == 2:
-                _hip.check(L.unet_tile_stitch(_hip.ptr(logits), So, oy0, ox0, ny, nx, t0, n, B, H, W, _hip.ptr(mask),
-                                              _hip.ptr(prob), st), "unet_tile_stitch")
-            else:
-                _hip.check(L.unet_tile_stitch_k(_hip.ptr(logits), So, K, oy0, ox0, ny, nx, t0, n, B, H, W, _hip.ptr(mask),
-                                                _hip.ptr(prob), st), "unet_tile_stitch_k")
+                if vs is not None:
+                    phase = (VIEW_FIRST if k == 0 else 0) | (VIEW_LAST if k == len(vs) - 1 else 0)
+                    _hip.check(L.unet_tile_stitch_view(_hip.ptr(logits[off:]), So, K, vs[k], y0, x0, gy, gx, a, m, B, H, W, phase,
+                                                       len(vs), _hip.ptr(prob), _hip.ptr(mask), st), "unet_tile_stitch_view")
+                elif K == 2:
+                    _hip.check(L.unet_tile_stitch(_hip.ptr(logits[off:]), So, y0, x0, gy, gx, a, m, B, H, W, _hip.ptr(mask),
+                                                  _hip.ptr(prob), st), "unet_tile_stitch")
+                else:
+                    _hip.check(L.unet_tile_stitch_k(_hip.ptr(logits[off:]), So, K, y0, x0, gy, gx, a, m, B, H, W, _hip.ptr(mask),
+                                                    _hip.ptr(prob), st), "unet_tile_stitch_k")
+
         if clean is not None:
             mask = clean_mask(mask, **clean)
-        if split is not None:
-            inst = split_instances(mask, prob if K == 2 else 1 - prob[:, 0], float(split))
-        elif shape_split is not None:
-            inst = split_by_shape(mask, *shape_split)
-        else:
-            inst = label_cells(mask)[0] if return_instances else None
+        inst = None
+        if return_instances:
+            fg = None if split is None else prob if K == 2 else 1 - prob[:, 0]
+            inst = _instance_map(mask, fg, split, shape_split, watershed, 4 if connectivity is None else connectivity)
+
     if single:
         mask = mask[0]
         prob = prob[0] if return_probs else None
-        inst = inst[0] if inst is not None else None
+        inst = inst[0] if return_instances else None
     out = (mask,) + ((prob,) if return_probs else ()) + ((inst,) if return_instances else ())
+    if measure:
+        out += (cell_props(inst, images if images.dtype == torch.float32 else images.to(torch.float32)),)
     return out if len(out) > 1 else mask
 
 

@@ -89,7 +89,11 @@ def test_python_surface():
     assert list(sig.parameters) == ["mask", "min_area", "connectivity"] and sig.parameters["connectivity"].default == 4
     seg = list(inspect.signature(tester.segment).parameters)
     assert seg[:7] == ["unet", "images", "tile_size", "max_batch", "normalise", "return_probs", "return_instances"]
-    assert seg[7:] == ["views", "clean", "shape_split", "split"]
+    assert seg[7:] == ["views", "clean", "shape_split", "split", "measure", "watershed", "connectivity"]
+    P = inspect.Parameter
+    assert [p.kind for p in inspect.signature(tester.segment).parameters.values()] == [P.POSITIONAL_OR_KEYWORD] * 11 + [P.KEYWORD_ONLY] * 3
+    assert [p.default for p in inspect.signature(tester.segment).parameters.values()] == [
+        P.empty, P.empty, None, 16, True, False, False, None, None, None, None, False, None, None]
     assert inspect.signature(tester.segment).parameters["clean"].default is None
 
     m = torch.zeros(2, 5, 7, dtype=torch.uint8)

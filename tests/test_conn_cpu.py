@@ -254,13 +254,22 @@ def test_python_surface():
     import torch
     import functions
     import tester
-    names = lambda f: list(inspect.signature(f).parameters)
-    assert names(functions.split_cells) == ["seeds", "mask", "max_steps", "orphans", "return_distance", "_launches"]
-    assert names(functions.watershed) == ["seeds", "image", "mask", "levels", "max_level", "return_levels", "_launches"]
-    assert names(tester.split_instances) == ["mask", "fg_prob", "high"]
-    assert names(tester.split_by_watershed) == ["mask", "fg_prob", "high", "levels"]
-    assert names(tester.segment)[-1] == "split" and "connectivity" not in names(tester.segment)
-    for f in (functions.reconstruct, functions.shape_seeds, tester.split_by_shape):
+    # the whole signature as text: every name, what is before the * (positional or keyword) and after it (keyword only), every default
+    sig = lambda f: str(inspect.signature(f))
+    assert sig(functions.split_cells) == "(seeds, mask, *, max_steps=None, orphans='drop', return_distance=False, _launches=8, connectivity=4)"
+    assert sig(functions.watershed) == ("(seeds, image, *, mask=None, levels=None, max_level=None, return_levels=False, _launches=8, "
+                                        "connectivity=4)")
+    assert sig(tester.split_instances) == "(mask, fg_prob, high, *, connectivity=4)"
+    assert sig(tester.split_by_watershed) == "(mask, fg_prob, high, levels=64, *, connectivity=4)"
+    assert sig(tester.segment) == ("(unet, images, tile_size=None, max_batch=16, normalise=True, return_probs=False, return_instances=False, "
+                                   "views=None, clean=None, shape_split=None, split=None, *, measure=False, watershed=None, connectivity=None)")
+    seg = list(inspect.signature(tester.segment).parameters.values())
+    P = inspect.Parameter
+    assert [p.name for p in seg if p.kind is P.POSITIONAL_OR_KEYWORD][-1] == "split"        # the last one a positional caller reaches
+    assert [(p.name, p.kind, p.default) for p in seg[-3:]] == [("measure", P.KEYWORD_ONLY, False), ("watershed", P.KEYWORD_ONLY, None),
+                                                               ("connectivity", P.KEYWORD_ONLY, None)]
+    for f in (functions.split_cells, functions.watershed, tester.split_instances, tester.split_by_watershed,
+              functions.reconstruct, functions.shape_seeds, tester.split_by_shape):
         p = inspect.signature(f).parameters["connectivity"]
         assert p.kind is inspect.Parameter.KEYWORD_ONLY and p.default == 4
     for f in (functions.split_cells, functions.watershed, tester.split_instances, tester.split_by_watershed, tester.segment):
@@ -289,3 +298,40 @@ def test_python_surface():
             functions.shape_seeds(s, connectivity=conn)
         with pytest.raises(ValueError, match="return_instances"):
             tester.segment(None, p, connectivity=conn)
+
+
+def test_segment_checks_fire_in_one_order():
+    """segment's argument checks fire in one fixed order, whichever keywords are present: the values of connectivity, measure and
+    watershed; what measure, connectivity and watershed need; split; shape_split; the device; then everything else.  A host
+    tensor stands in for "wrong in something checked later": no device is needed."""
+    import torch
+    import tester
+    V, R = ValueError, RuntimeError
+    table = [(dict(connectivity=5, measure="yes", watershed="x"), V, "connectivity must be 4 or 8"),
+             (dict(measure="yes", watershed="x"), V, "measure must be"),
+             (dict(watershed="x", measure=True), V, "watershed must be"),
+             (dict(measure=True), V, "measure needs"),
+             (dict(measure=True, connectivity=8), V, "measure needs"),
+             (dict(connectivity=8), V, "return_instances"),
+             (dict(connectivity=4), V, "return_instances"),
+             (dict(connectivity=8, return_instances=True, split=2), V, "split must be"),
+             (dict(connectivity=8, return_instances=True, split=0.5, shape_split=1.0), V, "two ways"),
+             (dict(connectivity=8, return_instances=True, shape_split=-1), V, "shape_split must be"),
+             (dict(connectivity=8, return_instances=True, clean=3), R, "HIP device"),
+             (dict(connectivity=8, return_instances=True, views="rot3"), R, "HIP device"),
+             (dict(watershed=16), V, "needs split"),
+             (dict(watershed=16, return_instances=True, split=0.5, shape_split=2.0), V, "does not combine"),
+             (dict(watershed=16, split=0.5), V, "split needs return_instances"),
+             (dict(watershed=16, split=2, return_instances=True), V, "split must be"),
+             (dict(clean=3), R, "HIP device"),
+             (dict(views="rot3"), R, "HIP device"),
+             (dict(tile_size=600), R, "HIP device"),
+             (dict(max_batch=0), R, "HIP device"),
+             (dict(measure=True, return_instances=True), R, "HIP device"),
+             # the two rows that changed when the checks got one order: a bad split or shape_split used to be reported after the
+             # device (RuntimeError "HIP device") unless measure, watershed or connectivity was given as well
+             (dict(split=2), V, "split needs return_instances"),
+             (dict(shape_split=2.0), V, "shape_split needs return_instances")]
+    for kw, error, word in table:
+        with pytest.raises(error, match=word):
+            tester.segment(None, torch.zeros(2, 5, 7), **kw)

@@ -454,3 +454,54 @@ def test_segment_with_connectivity(dev, net):
     assert torch.equal(i3, tester.split_by_shape(m0, 1.0, connectivity=8))
     m5, i5 = tester.segment(net, x, tile_size=188, max_batch=64, return_instances=True, split=high, watershed=True, connectivity=8)
     assert torch.equal(i5, tester.split_by_watershed(m0, p0, high, connectivity=8))
+
+
+def test_segment_steps_compose(dev, net):
+    """The same image and tiles: connectivity, measure, clean, split, watershed and views in the combinations no other test makes,
+    each equal, bit for bit, to the composition of the plain call's mask and probabilities with the step's own function.  The
+    one exception: the mean and std of measure=True, whose fp64 sums are not the same in two runs, are held to their rounding."""
+    import functions
+    import tester
+    x = torch.from_numpy(image(30, 1, 100, 130, blobs=9)[0]).to(dev)
+    kw = dict(tile_size=188, max_batch=64, return_probs=True, return_instances=True)
+    m0, p0, i0 = tester.segment(net, x, **kw)
+    assert bool((m0 != 0).any()) and bool((m0 == 0).any())   # foreground and background: nothing below is vacuous
+    high = float(p0[m0 != 0].median())
+
+    out = tester.segment(net, x, connectivity=8, measure=True, **kw)
+    assert len(out) == 4
+    m, p, inst, props = out
+    assert torch.equal(m, m0) and torch.equal(p, p0) and torch.equal(inst, functions.label_cells(m0, connectivity=8)[0])
+    want = functions.cell_props(inst, x)
+    assert isinstance(props, functions.CellProps)
+    for name in props._fields:
+        if name not in ("mean", "std"):
+            assert np.array_equal(getattr(props, name), getattr(want, name), equal_nan=True), name
+    # mean and std of a float image are formed from fp64 sums whose adds round in an order that differs between two runs
+    # (functions.cell_sums), so two calls on the same input need not agree in the last bits.  n values of magnitude <= v: each
+    # run's sum is within n 2^-53 of sum |v| <= n v, so the means of two runs differ by at most n 2^-52 v (+ the division's
+    # 2^-52 v) <= 2^-51 n v; likewise sum v^2 / n by (n + 1) 2^-52 v^2, mean^2 by 2 v 2^-51 n v + 2^-52 v^2, the subtraction adds
+    # 2^-52 v^2: the variances differ by at most 2^-49 n v^2, and the square root and squaring it again stay within 2^-48 n v^2
+    on = ~np.isnan(want.area)
+    n, v = want.area[on], np.maximum(np.abs(want.min[on]), np.abs(want.max[on]))
+    for name in ("mean", "std"):
+        assert np.array_equal(np.isnan(getattr(props, name)), ~on) and np.array_equal(np.isnan(getattr(want, name)), ~on), name
+    assert (np.abs(props.mean[on] - want.mean[on]) <= 2.0 ** -51 * n * v).all()
+    assert (np.abs(props.std[on] ** 2 - want.std[on] ** 2) <= 2.0 ** -48 * n * v * v).all()
+
+    clean = {"fill_holes": False, "min_area": 4}
+    m, p, inst = tester.segment(net, x, connectivity=8, clean=clean, split=high, **kw)
+    mc = functions.clean_mask(m0, fill_holes=False, min_area=4)
+    assert torch.equal(m, mc) and torch.equal(p, p0)
+    assert torch.equal(inst, tester.split_instances(mc, p0, high, connectivity=8))
+
+    ny, nx, _, _ = tester.tile_grid(100, 130, 188)
+    assert (ny * nx) % 64 != 0                               # so a chunk of 64 holds tiles of two views
+    mv, pv, iv = tester.segment(net, x, views="flips", **kw)
+    m, p, inst = tester.segment(net, x, views="flips", split=high, watershed=16, connectivity=8, **kw)
+    assert torch.equal(m, mv) and torch.equal(p, pv)
+    assert torch.equal(inst, tester.split_by_watershed(mv, pv, high, 16, connectivity=8))
+
+    m, p, i4 = tester.segment(net, x, shape_split=1.0, connectivity=4, **kw)
+    m, p, inst = tester.segment(net, x, shape_split=1.0, **kw)
+    assert torch.equal(i4, inst)

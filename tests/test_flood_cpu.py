@@ -78,12 +78,16 @@ def test_python_surface():
     import tester
     import torch
     sig = inspect.signature(functions.watershed)
-    assert list(sig.parameters) == ["seeds", "image", "mask", "levels", "max_level", "return_levels", "_launches"]
-    assert [sig.parameters[k].default for k in list(sig.parameters)[2:]] == [None, None, None, False, 8]
-    assert all(sig.parameters[k].kind is inspect.Parameter.KEYWORD_ONLY for k in list(sig.parameters)[2:])
+    P = inspect.Parameter
+    assert list(sig.parameters) == ["seeds", "image", "mask", "levels", "max_level", "return_levels", "_launches", "connectivity"]
+    assert [sig.parameters[k].default for k in list(sig.parameters)[2:]] == [None, None, None, False, 8, 4]
+    assert all(sig.parameters[k].kind is P.KEYWORD_ONLY for k in list(sig.parameters)[2:])
+    assert all(sig.parameters[k].kind is P.POSITIONAL_OR_KEYWORD and sig.parameters[k].default is P.empty for k in ("seeds", "image"))
     assert functions.FloodInfo._fields == ("seeds_outside", "unreached", "max_level", "launches")
     sig = inspect.signature(tester.split_by_watershed)
-    assert list(sig.parameters) == ["mask", "fg_prob", "high", "levels"] and sig.parameters["levels"].default == 64
+    assert list(sig.parameters) == ["mask", "fg_prob", "high", "levels", "connectivity"] and sig.parameters["levels"].default == 64
+    assert [p.kind for p in sig.parameters.values()] == [P.POSITIONAL_OR_KEYWORD] * 4 + [P.KEYWORD_ONLY]
+    assert [p.default for p in sig.parameters.values()] == [P.empty] * 3 + [64, 4]
     s = torch.zeros(2, 5, 7, dtype=torch.int32)
     with pytest.raises(NotImplementedError):
         functions.watershed(s, s)

@@ -67,13 +67,17 @@ def test_python_surface():
     import functions
     import tester
     sig = inspect.signature(functions.split_cells)
-    assert list(sig.parameters) == ["seeds", "mask", "max_steps", "orphans", "return_distance", "_launches"]
-    assert [sig.parameters[k].default for k in list(sig.parameters)[2:]] == [None, "drop", False, 8]
-    assert all(sig.parameters[k].kind is inspect.Parameter.KEYWORD_ONLY for k in list(sig.parameters)[2:])
+    P = inspect.Parameter
+    assert list(sig.parameters) == ["seeds", "mask", "max_steps", "orphans", "return_distance", "_launches", "connectivity"]
+    assert [sig.parameters[k].default for k in list(sig.parameters)[2:]] == [None, "drop", False, 8, 4]
+    assert all(sig.parameters[k].kind is P.KEYWORD_ONLY for k in list(sig.parameters)[2:])
+    assert all(sig.parameters[k].kind is P.POSITIONAL_OR_KEYWORD and sig.parameters[k].default is P.empty for k in ("seeds", "mask"))
     assert functions.SplitInfo._fields == ("seeds_outside", "unreached", "max_distance", "launches")
-    assert list(inspect.signature(tester.split_instances).parameters) == ["mask", "fg_prob", "high"]
+    assert str(inspect.signature(tester.split_instances)) == "(mask, fg_prob, high, *, connectivity=4)"
     seg = inspect.signature(tester.segment)
-    assert list(seg.parameters)[-1] == "split" and seg.parameters["split"].default is None
+    assert [k for k, p in seg.parameters.items() if p.kind is P.POSITIONAL_OR_KEYWORD][-1] == "split" and seg.parameters["split"].default is None
+    assert [(k, p.kind, p.default) for k, p in list(seg.parameters.items())[-3:]] == [
+        ("measure", P.KEYWORD_ONLY, False), ("watershed", P.KEYWORD_ONLY, None), ("connectivity", P.KEYWORD_ONLY, None)]
     import torch
     s = torch.zeros(2, 5, 7, dtype=torch.int32)
     with pytest.raises(NotImplementedError):
