@@ -250,7 +250,8 @@ static int launch_cfg(const IgemmP &p, hipStream_t st)
     q.mtiles = cdiv(p.M, BM);
     q.ntiles = cdiv(p.Nn, BN);
     char tag[96];
-    snprintf(tag, sizeof(tag), "igemm<%d;%d;%d> M=%d N=%d Kd=%d T=%d s=%d nsrc=%d", BM, BN, (int)PAD, p.M, p.Nn, p.Kd, p.T, p.stride, p.nsrc);
+    // (buf: the staging variant, a field and not part of the family like wgrad's - 1 = buffer descriptors, 0 = global_load_lds)
+    snprintf(tag, sizeof(tag), "igemm<%d;%d;%d> M=%d N=%d Kd=%d T=%d s=%d nsrc=%d buf=%d", BM, BN, (int)PAD, p.M, p.Nn, p.Kd, p.T, p.stride, p.nsrc, (int)BUF);
     return launch_profiled<igemm_f32_kernel<BM, BN, PAD, BUF>>(q.mtiles * q.ntiles, 256, LDS, st, PK_IGEMM, tag, igemm_alg_flops(p),
                                                                2.0 * q.mtiles * BM * (double)q.ntiles * BN * p.Kd, igemm_alg_bytes(p), q);
 }

@@ -985,6 +985,23 @@ static size_t wino_scratch_bytes(int C, int K)
     const size_t fwd = wino_u_floats(C, K), bwd = wino_u_floats(K, C) + wino_u_floats(K, 64);
     return align_up((fwd > bwd ? fwd : bwd) * sizeof(float), 256);
 }
+// The one size rule (common.hpp) for one tensor of a per-op 3x3 call, checked before anything is enqueued (what launch_igemm /
+// launch_igemmb / launch_wgrad would refuse after the filters have been packed): fewer than 2^31 - 1 elements, and a bf16
+// tensor that a kernel stages (`staged`: the bf16 kernels have buffer-descriptor staging only) fewer than 2^31 - 1 bytes.
+// The launchers keep their own checks (the net's path goes through them alone); this one only moves the refusal in front of
+// the first enqueue.  `staged` at the call sites follows who reads the tensor as a source:
+//   forward   x1, x2: launch_igemmb (igemm_source_bytes);  y: a destination, never staged
+//   backward  dz: launch_igemmb for each dgrad that runs (dx1, dx2) and launch_wgrad_b (its Y) when dw is asked for;
+//             x1, x2: launch_wgrad_b (its X), so only with dw;  the stand-alone bias_grad takes dz at any size
+static int op_tensor_ok(const char *op, const char *name, int B, int H, int W, int C, bool staged)
+{
+    const size_t n = tensor_elems(B, H, W, C);
+    ARG_CHECK(n < LIMIT_31BIT, "%s: %s [%d,%d,%d,%d] has %zu elements, the limit is 2^31 - 1 = %zu (31-bit element offsets)", op, name, B, H, W, C, n, LIMIT_31BIT);
+    ARG_CHECK(!(staged && t_math == 2) || fits_buffer(n * 2), "%s: bf16 %s [%d,%d,%d,%d] has %zu bytes, the limit is 2^31 - 1 = %zu (2 GiB: buffer-descriptor staging)",
+              op, name, B, H, W, C, n * 2, LIMIT_31BIT);
+    return 0;
+}
+
 size_t unet_conv3x3_scratch_bytes(int C, int K) { return align_up((size_t)K * C * 9 * sizeof(float), 256) + wino_scratch_bytes(C, K); }
 
 int unet_conv3x3_fwd(const void *x1, int H1, int W1, int C1, int pad1, const void *x2, int C2, int B, int H, int W,
@@ -998,6 +1015,10 @@ int unet_conv3x3_fwd(const void *x1, int H1, int W1, int C1, int pad1, const voi
     ARG_CHECK(H == W && H1 == W1, "conv3x3_fwd: square tiles only");
     // (what launch_igemmb would refuse after the filters have been packed: refused here, before anything is enqueued)
     ARG_CHECK(t_math != 2 || (C1 % 64 == 0 && (!x2 || C2 % 64 == 0)), "conv3x3_fwd: bf16 tensors need sources of whole 64-channel tiles (C1=%d C2=%d)", C1, x2 ? C2 : 0);
+    int rc;
+    if ((rc = op_tensor_ok("conv3x3_fwd", "x1", B, H1, W1, C1, true))) return rc;
+    if (x2 && (rc = op_tensor_ok("conv3x3_fwd", "x2", B, H, W, C2, true))) return rc;
+    if ((rc = op_tensor_ok("conv3x3_fwd", "y", B, H - 2, W - 2, K, false))) return rc;
     float *wu = (float *)((char *)scratch + align_up((size_t)K * (C1 + (x2 ? C2 : 0)) * 9 * sizeof(float), 256));
     return conv_fwd_launch((const float *)x1, H1, C1, pad1, (const float *)x2, C2, B, H, (const float *)w_oihw, (float *)scratch,
                            (const float *)bias, K, relu, (float *)y, st, wu);
@@ -1024,6 +1045,10 @@ int unet_conv3x3_bwd(const void *x1, int H1, int W1, int C1, int pad1, const voi
         ARG_CHECK(!dw || (C1 % 64 == 0 && (!x2 || C2 % 64 == 0)), "conv3x3_bwd: the bf16 weight gradient needs sources of whole 64-channel tiles (C1=%d C2=%d)",
                   C1, x2 ? C2 : 0);
     }
+    int rc;
+    if ((rc = op_tensor_ok("conv3x3_bwd", "x1", B, H1, W1, C1, dw != nullptr))) return rc;
+    if (x2 && (rc = op_tensor_ok("conv3x3_bwd", "x2", B, H, W, C2, dw != nullptr))) return rc;
+    if ((rc = op_tensor_ok("conv3x3_bwd", "dz", B, H - 2, W - 2, K, dx1 || (x2 && dx2) || dw))) return rc;
     hipStream_t st = (hipStream_t)stream;
     const int C = C1 + (x2 ? C2 : 0);
     const int Ho = H - 2;
@@ -1033,7 +1058,6 @@ int unet_conv3x3_bwd(const void *x1, int H1, int W1, int C1, int pad1, const voi
     float *slab = (float *)((char *)scratch + wt_bytes);
     float *small = (float *)((char *)scratch + wt_bytes + slab_bytes);
     float *wu = (float *)((char *)scratch + wt_bytes + slab_bytes + align_up(bias_grad_scratch_bytes((size_t)B * Ho * Ho, K), 256));
-    int rc;
     if ((rc = conv_dgrad_launch((const float *)dz, Ho, K, B, (const float *)w_oihw, wt, wu, H1, C1, pad1, (float *)dx1, (const float *)mask1,
                                 (const float *)add1, H, C - C1, x2 ? (float *)dx2 : nullptr, (const float *)mask2, st))) return rc;
     bool db_done = false;

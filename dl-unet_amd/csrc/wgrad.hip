@@ -967,7 +967,8 @@ int launch_wgrad(WgradP p, hipStream_t st)
     ARG_CHECK(p.XC % 4 == 0 && p.YC % 4 == 0 && p.xc0 % 4 == 0 && p.yc0 % 4 == 0, "wgrad: channel pitch/offset must be multiples of 4");
     if (p.math == 2) ARG_CHECK(p.XC % 8 == 0 && p.YC % 8 == 0 && p.xc0 % 8 == 0 && p.yc0 % 8 == 0, "wgrad (bf16): channel pitch/offset must be multiples of 8");
     ARG_CHECK(p.ywin0 >= 0 && p.ywin1 <= p.YH && p.xwin0 >= 0 && p.xwin1 <= p.YW && p.ywin0 < p.ywin1 && p.xwin0 < p.xwin1, "wgrad: bad window");
-    ARG_CHECK(tensor_elems(p.NB, p.XH, p.XW, p.XC) < LIMIT_31BIT * 2 && tensor_elems(p.NB, p.YH, p.YW, p.YC) < LIMIT_31BIT * 2, "wgrad: tensor too large");
+    ARG_CHECK(tensor_elems(p.NB, p.XH, p.XW, p.XC) < LIMIT_31BIT && tensor_elems(p.NB, p.YH, p.YW, p.YC) < LIMIT_31BIT,
+              "wgrad: tensor exceeds 31-bit element offsets (the limit is 2^31 - 1 elements)");
     p.zeros = zero_page();
     if (!p.zeros) return -2;
     ARG_CHECK(p.math >= 0 && p.math <= 3, "wgrad: bad arithmetic mode %d", p.math);

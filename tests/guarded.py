@@ -38,6 +38,7 @@ import torch
 POISON = 0xFF
 ALIGN = 256
 G = 196608
+CHUNK = 1 << 28
 
 
 class _Buf:
@@ -47,10 +48,12 @@ class _Buf:
 class Arena:
     """One per test.  Keeps every allocation alive until the test ends (raw pointers are in flight)."""
 
-    def __init__(self, device="cuda", guard=G):
+    def __init__(self, device="cuda", guard=G, chunk=CHUNK):
         assert guard % ALIGN == 0 and guard >= G, "the guard is a multiple of 256 bytes and at least G"
+        assert chunk > 0
         self.device = torch.device(device)
         self.guard = guard
+        self.chunk = chunk          # bytes assert_written looks at in one piece (the result does not depend on it)
         self.bufs = []
 
     # ---- allocation ----------------------------------------------------------------------------------------------------
@@ -134,17 +137,31 @@ class Arena:
             if b.nbytes == 0:
                 continue
             es = t.element_size()
-            left = (b.raw[b.start:b.start + b.nbytes].view(-1, es) == POISON).all(dim=1)
-            n = int(left.sum())
+            # in pieces of at most self.chunk bytes: the comparison's mask is as large as what it looks at, and a tensor may
+            # be gigabytes.  One device-side count per piece, one host read-back for the whole buffer.
+            step = max(self.chunk // es, 1) * es
+
+            def left(o):
+                return (b.raw[b.start + o:b.start + min(o + step, b.nbytes)].view(-1, es) == POISON).all(dim=1)
+
+            count = torch.zeros((), dtype=torch.int64, device=b.raw.device)
+            for o in range(0, b.nbytes, step):
+                count += left(o).sum()
+            n = int(count)
             if n == 0:
                 continue
-            idx = left.nonzero().flatten()
-            first = np.unravel_index(int(idx[0]), b.shape)
-            last = np.unravel_index(int(idx[-1]), b.shape)
+            first = last = None                       # only to word the failure: element indices of the first and last poison
+            for o in range(0, b.nbytes, step):
+                idx = left(o).nonzero().flatten()
+                if len(idx):
+                    first = o // es + int(idx[0]) if first is None else first
+                    last = o // es + int(idx[-1])
+            first = np.unravel_index(first, b.shape)
+            last = np.unravel_index(last, b.shape)
             names = "(n, h, w, c) = " if len(b.shape) == 4 else "index "
             raise AssertionError("%s %s: %d of %d elements still hold poison (never written, or a NaN that kept the payload of poison "
                                  "that was read); first at %s%s, last at %s"
-                                 % (b.label, b.shape, n, left.numel(), names, tuple(int(i) for i in first), tuple(int(i) for i in last)))
+                                 % (b.label, b.shape, n, b.nbytes // es, names, tuple(int(i) for i in first), tuple(int(i) for i in last)))
 
     def verify(self, *outputs):
         """assert_written on each requested output (None = not requested), then check()."""

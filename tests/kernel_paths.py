@@ -107,17 +107,38 @@ def cdiv(a, b):
     return -(-a // b)
 
 
+# ---- the one size rule (csrc/common.hpp) ------------------------------------------------------------------------------------
+LIMIT_31BIT = 0x7FFFFFFF
+
+
+def tensor_bytes(B, H, W, C, es=4):
+    return B * H * W * C * es
+
+
+def fits_buffer(nbytes):
+    """common.hpp fits_buffer: a tensor is staged through a buffer descriptor only while its bytes stay below 2^31 - 1."""
+    return nbytes < LIMIT_31BIT
+
+
+def staging(dma, nbytes=()):
+    """The effective staging variant of an MFMA launch (the <1> / <0> of wino32 and wgradw, the buf= field of igemm and wgrad):
+    the unet_set_lds_dma knob AND every tensor the launch stages fitting a buffer descriptor.  nbytes: the bytes of those
+    tensors (the sources of a forward or dgrad, x and dz of a weight gradient); empty = all small, the knob alone decides."""
+    return int(bool(dma) and all(fits_buffer(b) for b in nbytes))
+
+
 def wino_applicable(OW, Nn, nchs, OH=None):
     """wino.hip wino_applicable for the per-op shapes (square tiles, linear store)."""
     OH = OW if OH is None else OH
     return Nn % 32 == 0 and cdiv(OW, 2) >= 9 and cdiv(OH, 2) >= 7 and all(c % 8 == 0 for c in nchs)
 
 
-def fp32_conv_family(mode, dma, OW, Nn, nchs, pad=False):
-    """The family an fp32-mode (0 / 3) single 3x3 launch reaches: Winograd (staging variant = the lds_dma knob) in mode 3
-    where wino_applicable holds, else the implicit GEMM tile chosen by Nn % 128."""
+def fp32_conv_family(mode, dma, OW, Nn, nchs, pad=False, nbytes=()):
+    """The family an fp32-mode (0 / 3) single 3x3 launch reaches: Winograd (staging variant = the lds_dma knob AND the sources'
+    bytes, staging()) in mode 3 where wino_applicable holds, else the implicit GEMM tile chosen by Nn % 128 (its staging
+    variant is the tag's buf= field: conv_spec)."""
     if mode == 3 and wino_applicable(OW, Nn, nchs):
-        return "wino32<%d>" % dma
+        return "wino32<%d>" % staging(dma, nbytes)
     return "igemm<%s;%d>" % ("128;128" if Nn % 128 == 0 else "256;64", int(pad))
 
 
@@ -132,13 +153,19 @@ def bf16_conv_family(OW, Nn, nchs, pad):
     return "igemmb<%s;%d>" % ("128;128" if Nn % 128 == 0 else "256;64", int(pad))
 
 
-def conv_family(mode, dma, OW, Nn, nchs, pad):
+def conv_family(mode, dma, OW, Nn, nchs, pad, nbytes=()):
     """The family of one 3x3 launch in any mode: fp32 (0 / 3), bf16x3 (1) or bf16 tensors (2)."""
     if mode == 2:
         return bf16_conv_family(OW, Nn, nchs, pad)
     if mode == 1:
         return "igemmx<%s;%d;split3>" % ("128;128" if Nn % 128 == 0 else "256;64", int(pad))
-    return fp32_conv_family(mode, dma, OW, Nn, nchs, pad)
+    return fp32_conv_family(mode, dma, OW, Nn, nchs, pad, nbytes)
+
+
+def conv_spec(mode, dma, OW, Nn, nchs, pad=False, nbytes=()):
+    """conv_family as a spec for Record.reached: an fp32 implicit GEMM also carries its staging variant (buf=)."""
+    fam = conv_family(mode, dma, OW, Nn, nchs, pad, nbytes)
+    return fam + " buf=%d" % staging(dma, nbytes) if fam.startswith("igemm<") else fam
 
 
 def taps_leave(src_H, OH, o0, src_pad):
@@ -160,15 +187,36 @@ def concat_fwd_families(mode, dma, Hs, pad, C1, C2, K, split_thr=0.85):
             conv_family(mode, dma, w1 - w0, K, [C1], taps_leave(Hs, w1 - w0, w0, pad))]
 
 
-def wgrad_family(mode, dma, Ci, Cj):
-    """The 3x3 weight-gradient kernel of a source with Ci channels against dz with Cj channels."""
+def wgrad_family(mode, dma, Ci, Cj, nbytes=()):
+    """The 3x3 weight-gradient kernel of a source with Ci channels against dz with Cj channels (nbytes: the bytes of both)."""
     if mode == 2:
         return "wgradb<3;3;1>"
     if mode == 1:
         return "wgrad<3;3;1;split3>"
     if mode == 3 and Ci % 64 == 0 and Cj % 64 == 0:
-        return "wgradw<%d>" % dma
+        return "wgradw<%d>" % staging(dma, nbytes)
     return "wgrad<3;3;1;split0>"
+
+
+def wgrad_spec(mode, dma, Ci, Cj, nbytes=()):
+    """wgrad_family as a spec for Record.reached: the row-walking kernels carry their staging variant as buf= (the exact fp32
+    3x3 instantiation has the global_load_lds form only, wgrad.hip CAN_BUF; the bf16 one the buffer form only)."""
+    fam = wgrad_family(mode, dma, Ci, Cj, nbytes)
+    if fam == "wgrad<3;3;1;split0>":
+        return fam + " buf=0"
+    if fam == "wgrad<3;3;1;split3>":
+        return fam + " buf=%d" % staging(dma, nbytes)
+    return fam + (" buf=1" if mode == 2 else "")
+
+
+def upconv_wgrad_spec(mode, dma, nbytes=()):
+    """The up-conv weight gradient (wgrad.hip up_applicable): the pixel-linear kernel for bf16 tensors and, while both tensors
+    fit a buffer descriptor and the knob is on, for exact fp32; else the row-walking 2x2 stride-2 kernel."""
+    if mode == 2:
+        return "wgrad_up<bf16>"
+    if mode != 1 and staging(dma, nbytes):
+        return "wgrad_up<f32>"
+    return "wgrad<2;2;2;split%d> buf=%d" % (3 if mode == 1 else 0, staging(dma, nbytes))
 
 
 def concat_bwd_families(mode, dma, Hs, pad, C1, C2, K):

@@ -160,3 +160,25 @@ def test_accumulating_into_uncleared_scratch_turns_nan():
     scale_rows(A, xd, y, sc, clear=False)
     A.verify(y)
     assert (y.double() - ref).abs().max() < 1e-5
+
+
+@pytest.mark.parametrize("chunk", [4, 20, 100, 1919, 1920, 4096])
+def test_assert_written_in_pieces_means_the_same(chunk):
+    """assert_written looks at a buffer in pieces of Arena.chunk bytes (the tensors of tests/test_large_tensors_gpu.py are
+    gigabytes): whatever the piece size - one element, pieces that end inside the tensor's last row, exactly the tensor, more
+    than it - a fully written tensor passes and a gap is reported with the same count, first and last element."""
+    A = gd.Arena("cpu", chunk=chunk)
+    y = A.out((B, H, W, C), torch.float32, "y")
+    assert y.numel() * 4 == 1920
+    y.zero_()
+    A.verify(y)
+    flat = raw(A, y).view(np.uint32)
+    flat[[7, 8, 250, 479]] = 0xFFFFFFFF
+    with pytest.raises(AssertionError, match=r"y \(2, 5, 6, 8\): 4 of 480 elements still hold poison.*first at \(n, h, w, c\) = \(0, 0, 0, 7\), "
+                                             r"last at \(1, 4, 5, 7\)"):
+        A.assert_written(y)
+    h = A.out((3, 5), torch.bfloat16, "h")      # two-byte elements: a piece never cuts one in two
+    h.zero_()
+    raw(A, h, dtype=np.uint16)[14] = 0xFFFF
+    with pytest.raises(AssertionError, match=r"h \(3, 5\): 1 of 15 elements still hold poison.*first at index \(2, 4\), last at \(2, 4\)"):
+        A.assert_written(h)

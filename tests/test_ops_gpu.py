@@ -30,7 +30,8 @@ ConvMode = collections.namedtuple("ConvMode", "mode dma")
 def conv_mode(hip, request):
     """The 3x3 layers have two fp32 evaluations: the direct fmaf chain (math mode 0) and Winograd F(2x2,3x3) (mode 3);
     each stages its operands either by buffer-descriptor LDS-DMA (default) or by global_load_lds — the instantiation
-    tensors >= 2 GiB take (BASELINE config #5 at batch 16), forced here with unet_set_lds_dma(0)."""
+    tensors >= 2 GiB take (BASELINE config #5 at batch 16), forced here with unet_set_lds_dma(0);
+    tests/test_large_tensors_gpu.py reaches it by size, with the knob at its default."""
     mode, dma = request.param
     with library_state(math=mode, lds_dma=dma):
         yield ConvMode(mode, dma)
