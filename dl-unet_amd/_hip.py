@@ -120,6 +120,8 @@ _SIGS = {
     "unet_partition_pairs": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, vp, vp, vp, vp, vp, vp]),
     "unet_link_frames_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_size_t]),
     "unet_link_frames": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, vp, vp, vp, vp, vp, vp]),
+    "unet_aogm_counts_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "unet_aogm_counts": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "unet_grow_labels_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "unet_grow_labels": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_longlong, vp, vp, vp]),
     "unet_warp_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),

@@ -597,6 +597,38 @@ int unet_cell_contacts(const void *labels, int label_dtype, int B, int H, int W,
 size_t unet_link_frames_scratch_bytes(int T, int n_max, size_t table_slots);
 int unet_link_frames(const void *from_i32, const void *to_i32, int T, int H, int W, int n_max, size_t table_slots, void *area_u32,
                      void *pred_i32, void *pred_overlap_u32, void *status_u64, void *scratch, void *stream);
+/* The graph stage of the Cell Tracking Challenge's DET and TRA measures (AOGM: Matula et al. 2015; aogm.hip; ctc.aogm_counts;
+ * the definition in full: DESIGN.md section 4s-ter).  Two time-lapses of id maps labelled by track, the reference ("gt") and the
+ * result ("res"), reach this entry as the outputs of one unet_instance_overlap call with B = T on (gt, res): area_gt_u32
+ * [T][ng_max+1], area_res_u32 [T][nr_max+1], match_i32 [T][ng_max+1].  No pixel is read here: O(T * (ng_max + nr_max)) work.
+ * rows_gt_i32 [ng_max+1][3], rows_res_i32 [nr_max+1][3] (each may be NULL: no table, every label accepted, no parent links):
+ * the row (B, E, P) of label L of the challenge's track table, frames counted from 0, P = 0 for "no parent"; B = -1: no row.
+ * One side's graph: a vertex is (t, L), L >= 1, with area[t][L] != 0.  Its in-edge comes from L's latest presence before t (kind
+ * "track"; it spans the frames in which L is absent), else, at L's first presence with P > 0, from the last presence of P (kind
+ * "parent"), else there is none.  A vertex is bad if its label has no row although a table was given, if t is outside [B, E],
+ * or if at a first presence with P > 0 the parent is never present (P > n_max included) or its last presence is not before t;
+ * a bad parent link gives no in-edge.  Reference vertex g of frame t is matched by m = match[t][g] if m is in [1, nr_max].
+ *   claims_u32 [T][nr_max+1]      : the reference vertices of frame t matched by result label s; s is TP iff that is 1
+ *   claimant_i32 [T][nr_max+1]    : the largest such reference label (an integer max, so defined for claims > 1 too), 0 if none
+ *   inedge_gt_i32 [T][ng_max+1][2], inedge_res_i32 [T][nr_max+1][2] : (frame, label) of the in-edge's source, (-1, 0) if none
+ *   flags_gt_u8 [T][ng_max+1], flags_res_u8 [T][nr_max+1] : one byte per (t, L), 0 where there is no vertex.  Both sides:
+ *       1 = present, 2 = has an in-edge, 4 = that edge is of kind parent, 8 = bad.  Reference: 16 = matched, 32 = EA (has an
+ *       in-edge u -> v that is not reproduced: match(v) = s and match(u) = r both TP and the in-edge of s comes from r), 64 = EC
+ *       (reproduced, but the two kinds differ).  Result: 16 = TP, 32 = FP (claims = 0), 64 = ED (has an in-edge r -> s, s and r
+ *       both TP, and the in-edge of s's partner does not come from r's partner)
+ *   counts_u64 [T][12]            : per frame {n_ref, n_res, e_ref, e_res, TP, FN, FP, NS, EA, ED, EC, bad}: vertices and
+ *       in-edges (booked to the frame of their head) of either side, TP result vertices, reference vertices without a match,
+ *       result vertices with claims = 0, the sum of claims - 1 over result vertices with claims > 1, the three edge flags, and
+ *       the bad vertices of both sides
+ * Three launches on the stream, no memset, no read-back; integer atomics only: every output is the same in every run.
+ * Limits: 1 <= T <= 65535, ng_max and nr_max in [0, 2^24).  A NULL pointer (the two row arrays apart) or a broken limit returns
+ * an error and writes nothing.  Whatever the input words hold, nothing outside the buffers is touched.
+ * scratch: unet_aogm_counts_scratch_bytes(T, ng_max, nr_max) (4 bytes per (t, L) and 4 per L of either side), initialised by the
+ * call; 0 on a size outside the limits.                                                                                     */
+size_t unet_aogm_counts_scratch_bytes(int T, int ng_max, int nr_max);
+int unet_aogm_counts(const void *area_gt_u32, const void *area_res_u32, const void *match_i32, const void *rows_gt_i32,
+                     const void *rows_res_i32, int T, int ng_max, int nr_max, void *claims_u32, void *claimant_i32, void *inedge_gt_i32,
+                     void *inedge_res_i32, void *flags_gt_u8, void *flags_res_u8, void *counts_u64, void *scratch, void *stream);
 /* Nearest-cell growth of an instance map (border thinning; skimage.segmentation.expand_labels with an exact metric and a
  * stated tie rule; functions.grow_cells).  labels_i32, out_i32 int32 [B,H,W], 0 = background, ids in [1, 2^24), not
  * necessarily consecutive or connected; H != W allowed, down to 1 x 1.  A pixel with id != 0 keeps it.  A background pixel takes
