@@ -1,6 +1,5 @@
-// aux.hip — the callers and data formats either side of the hot path, all HBM-bound:
+// aux.hip — the callers and data formats either side of the hot path (N2's back end is loss.hip's), all HBM-bound:
 //   N2 overlap-tile front end : per-image min/max + mirror-pad + normalise     (data.py:184-188, :249-277)
-//   N2 back end               : centre-crop + argmax + IoU / pixel-error counts (tester.py:29-42, functions.py:174-213)
 //   N3 class-balance maps     : per-image class counts -> weight map            (functions.py:82-117)
 //   N1 elastic deformation    : separable Gaussian of a uniform field, bilinear warp (data.py:225-245)
 #include "common.hpp"
@@ -40,32 +39,6 @@ __global__ __launch_bounds__(256) void mirror_pad_kernel(const float *__restrict
         float v = x[((size_t)b * n + mirror_index(Y, P, n)) * n + mirror_index(X, P, n)];
         if (minmax) { const float lo = minmax[2 * b], hi = minmax[2 * b + 1]; v = (v - lo) / (hi - lo); }
         out[e] = v;
-    }
-}
-
-// ---- crop + argmax + metric counts: stats[b] = {sum(pred&label), sum(pred|label), sum|pred-label|} ----
-__global__ __launch_bounds__(256) void eval_masks_kernel(const float *__restrict__ logits, long bs, long ps, long rs, int pad,
-                                                         const long long *__restrict__ labels, long long *__restrict__ mask,
-                                                         int n, unsigned long long *__restrict__ stats)
-{
-    const int b = blockIdx.y;
-    const size_t npx = (size_t)n * n;
-    unsigned long long inter = 0, uni = 0, diff = 0;
-    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < npx; e += (size_t)gridDim.x * blockDim.x) {
-        const int xx = (int)(e % n), yy = (int)(e / n);
-        const float *p = logits + b * bs + (size_t)(yy + pad) * rs + xx + pad;
-        const long long pr = p[ps] > p[0] ? 1 : 0;                       // first maximum on ties -> class 0
-        mask[(size_t)b * npx + e] = pr;
-        if (labels) {
-            const long long lb = labels[(size_t)b * npx + e];
-            inter += (pr != 0 && lb != 0); uni += (pr != 0 || lb != 0);
-            diff += (unsigned long long)(pr > lb ? pr - lb : lb - pr);
-        }
-    }
-    if (!labels) return;
-    inter = wave_sum(inter); uni = wave_sum(uni); diff = wave_sum(diff);
-    if ((threadIdx.x & 63) == 0) {       // integer atomics: order-independent, exact
-        atomicAdd(&stats[3 * b], inter); atomicAdd(&stats[3 * b + 1], uni); atomicAdd(&stats[3 * b + 2], diff);
     }
 }
 
@@ -259,20 +232,6 @@ int unet_mirror_pad(const void *x, int B, int n, int S, const void *minmax, void
     const size_t total = (size_t)B * S * S;
     hipLaunchKernelGGL(mirror_pad_kernel, dim3(grid_for(total, 256, 16384)), dim3(256), 0, (hipStream_t)stream, (const float *)x, (float *)out, n, S, (S - n) / 2,
                        (const float *)minmax, total);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-int unet_eval_masks(const void *logits, long batch_stride, long plane_stride, long row_stride, int pad, const void *labels_i64,
-                    void *mask_i64, int B, int n, void *stats_u64, void *stream)
-{
-    ARG_CHECK(logits && mask_i64 && B > 0 && n > 0 && pad >= 0, "unet_eval_masks: bad argument");
-    ARG_CHECK(!labels_i64 || stats_u64, "unet_eval_masks: stats buffer needed with labels");
-    hipStream_t st = (hipStream_t)stream;
-    if (labels_i64) HIP_TRY(hipMemsetAsync(stats_u64, 0, (size_t)B * 3 * sizeof(unsigned long long), st));
-    int gx = grid_for((size_t)n * n, 256, 256);
-    hipLaunchKernelGGL(eval_masks_kernel, dim3(gx, B), dim3(256), 0, st, (const float *)logits, batch_stride, plane_stride, row_stride, pad,
-                       (const long long *)labels_i64, (long long *)mask_i64, n, (unsigned long long *)stats_u64);
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -201,7 +201,7 @@ int headk_fwd(const void *x, int B, int H, int W, int C, int K, const float *w, 
 int headk_bwd(const void *x, int B, int H, int W, int C, int K, const float *w, const float *dlogits, float dl_scale, void *dz, float *dw,
               float *db, float *scratch, int es, hipStream_t st);
 size_t headk_bwd_scratch_bytes(int B, int H, int W, int C, int K);
-// K classes padded to the kernels' template width: 2, 4, 8 or 16 (multiclass.hip, tile.hip)
+// K classes padded to the kernels' template width: 2, 4, 8 or 16 (multiclass.hip, loss.hip, dice.hip, tile.hip)
 static inline int class_pad(int K) { return K <= 2 ? 2 : K <= 4 ? 4 : K <= 8 ? 8 : 16; }
 // LAUNCH with KP_ = class_pad(K) as a compile-time constant
 #define CLASS_DISPATCH(K, LAUNCH)                                                                                      \

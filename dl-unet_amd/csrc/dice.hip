@@ -1,14 +1,15 @@
 // dice.hip — the soft Dice loss (Milletari et al. 2016) and the CE + Dice sum over the K-class soft-max, one training-step op
 // (unet_dice_step), HBM-bound, three launches, no host sync, no floating-point atomics:
 //   sums    : a thread owns a pixel (all K planes), a workgroup DICE_PX_PER_BLOCK pixels of ONE image (grid: blocks per image x
-//             B); p as softmax_ce_kernel forms it; per block the CE partial, the invalid count, the I / P partials (double) and
-//             the label counts Y (integers); the argmax mask
+//             B); p by softmax.hpp's pixel_exps, softmax_ce_kernel's statements; per block the CE partial, the invalid count,
+//             the I / P partials (double) and the label counts Y (integers); the argmax mask
 //   finish  : one workgroup sums the partials in a fixed order per (image, class) or per class (batch Dice), forms the Dice
 //             coefficients, the three losses and the coefficient table (a, c) the gradient reads
 //   grad    : re-reads the logits, recomputes p, writes the dense gradient (CE term included)
 // Every sum has one fixed order, so a result does not depend on the run or on the stream.  See DESIGN §4v.
 #include "common.hpp"
 #include "elem.hpp"
+#include "softmax.hpp"
 #include <cmath>
 #include "../../include/unet_hip.h"
 
@@ -21,29 +22,6 @@ constexpr int DICE_PX_PER_THREAD = DICE_PX_PER_BLOCK / DICE_THREADS;      // sum
 constexpr int DICE_FIN_THREADS = 256;        // the finisher: one workgroup ...
 constexpr int DICE_FIN_GROUP = 16;           // ... of 16-lane groups, a group per (image, class) term, its lanes stride the partials
 constexpr int DICE_FIN_GROUPS = DICE_FIN_THREADS / DICE_FIN_GROUP;
-
-// exp(l_k - max l) of one pixel, their sum, the first maximum and (m - l_label) as softmax_ce_kernel forms them
-template <int KP>
-__device__ __forceinline__ void pixel_exps(const float *__restrict__ px, long xsC, int K, long long lab, float (&ex)[KP], float &se,
-                                           float &m_ll, int &am)
-{
-    float l[KP];
-#pragma unroll
-    for (int k = 0; k < KP; ++k) l[k] = k < K ? px[k * xsC] : 0.f;
-    float m = l[0];
-    am = 0;
-#pragma unroll
-    for (int k = 1; k < KP; ++k) if (k < K && l[k] > m) { m = l[k]; am = k; }          // first maximum: torch.argmax's tie rule
-    float ll = m;
-    se = 0.f;
-#pragma unroll
-    for (int k = 0; k < KP; ++k) {
-        ex[k] = k < K ? expf(l[k] - m) : 0.f;
-        se += ex[k];
-        if (k == lab) ll = l[k];
-    }
-    m_ll = m - ll;
-}
 
 // ---- launch 1: sums -----------------------------------------------------------------------------------------------------------
 // Partials of block (b, blockIdx.x) sit at slot = b * gridDim.x + blockIdx.x: ce_part[slot], bad_part[slot], and per class

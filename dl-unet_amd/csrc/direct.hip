@@ -1,7 +1,7 @@
 // direct.hip — the HBM-bound kernels of the path (no dense contraction worth a matrix core):
 //   conv11c (1 -> K stencil) fwd / weight-grad, 1x1 head fwd / bwd, 2x2 max-pool fwd / bwd,
-//   conv11c input gradient, weight packers, bias gradients, and the step-side kernels
-//   (BCE-with-logits alone and fused with the argmax mask, one-hot, argmax, SGD-momentum).
+//   conv11c input gradient, weight packers, bias gradients, and the SGD-momentum update (the losses and masks of the step
+//   side are loss.hip's).
 // All are written for 16 B (fp32) / 8 B (bf16) per lane coalesced NHWC traffic, templated on the storage type.  Element
 // access, the block sum, grid_for and the dispatch on (element size, width) are elem.hpp's; the launch bracket is common.hpp's.
 #include "common.hpp"
@@ -452,118 +452,6 @@ int bias_grad(const void *dz, size_t M, int K, float *db, float *scratch, int es
     });
 }
 
-// ============================================================================================
-// Step-side kernels (L1-L3)
-// ============================================================================================
-constexpr int BCE_PER_BLOCK = 4096;
-__global__ __launch_bounds__(256) void bce_logits_kernel(const float *__restrict__ x, const float *__restrict__ z,
-                                                         const float *__restrict__ w, long wsB, long wsC, long wsH, long wsW,
-                                                         int H, int W, size_t n, float *__restrict__ dx, float gscale,
-                                                         double *__restrict__ partial)
-{
-    const size_t b0 = (size_t)blockIdx.x * BCE_PER_BLOCK;
-    double acc = 0.0;
-    const float inv_n = (float)(1.0 / (double)n);
-    for (int i = threadIdx.x; i < BCE_PER_BLOCK; i += 256) {
-        const size_t e = b0 + i;
-        if (e >= n) break;
-        const float xv = x[e], zv = z[e];
-        float wv = 1.f;
-        if (w) {
-            size_t r = e;
-            const int xx = (int)(r % W); r /= W;
-            const int yy = (int)(r % H); r /= H;
-            const int cc = (int)(r % 2);
-            const long bb = (long)(r / 2);
-            wv = w[bb * wsB + cc * wsC + yy * wsH + xx * wsW];
-        }
-        const float ax = fabsf(xv);
-        const float l = fmaxf(xv, 0.f) - xv * zv + log1pf(expf(-ax));
-        acc += (double)(wv * l);
-        if (dx) {
-            const float ex = expf(-ax);
-            const float sg = xv >= 0.f ? 1.f / (1.f + ex) : ex / (1.f + ex);
-            dx[e] = wv * (sg - zv) * inv_n * gscale;
-        }
-    }
-    acc = block_sum256(acc);
-    if (threadIdx.x == 0) partial[blockIdx.x] = acc;
-}
-__global__ __launch_bounds__(256) void bce_final_kernel(const double *__restrict__ partial, int nb, size_t n, float *loss)
-{
-    double a = 0.0;
-    for (int i = threadIdx.x; i < nb; i += 256) a += partial[i];
-    a = block_sum256(a);
-    if (threadIdx.x == 0) *loss = (float)(a / (double)n);
-}
-
-// L1 + L2 in one pass over the logits (trainer.py:60-82): the one-hot target [1-y, y] is never materialised, the loss
-// gradient and the argmax mask come out of the same read.  A thread owns a pixel (both class planes): 2 x 4 B logits + 8 B
-// label in, 2 x 4 B dlogits + 8 B mask out.  Logits / weight are addressed through strides (the trainer's centre crop of
-// preds is a view); dlogits and the mask are dense.  Loss partials per block in double, fixed-order finish in bce_final_kernel.
-constexpr int BCE_PX_PER_BLOCK = 2048;
-__global__ __launch_bounds__(256) void bce_step_kernel(const float *__restrict__ x, long xsB, long xsC, long xsH,
-                                                       const long long *__restrict__ labels,
-                                                       const float *__restrict__ w, long wsB, long wsC, long wsH, long wsW,
-                                                       int H, int W, size_t npix, float *__restrict__ dx, float gscale,
-                                                       long long *__restrict__ mask, double *__restrict__ partial)
-{
-    const size_t b0 = (size_t)blockIdx.x * BCE_PX_PER_BLOCK;
-    double acc = 0.0;
-    const float inv_n = (float)(1.0 / (double)(2 * npix));
-    const size_t HW = (size_t)H * W;
-    for (int i = threadIdx.x; i < BCE_PX_PER_BLOCK; i += 256) {
-        const size_t e = b0 + i;
-        if (e >= npix) break;
-        const size_t bb = e / HW, rem = e - bb * HW;
-        const int yy = (int)(rem / W), xx = (int)(rem - (size_t)yy * W);
-        const float *px = x + bb * xsB + (long)yy * xsH + xx;
-        const float x0 = px[0], x1 = px[xsC];
-        const float y = (float)labels[e];
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-            const float xv = c ? x1 : x0, zv = c ? y : 1.f - y;
-            const float wv = w ? w[bb * wsB + c * wsC + yy * wsH + xx * wsW] : 1.f;
-            const float ax = fabsf(xv);
-            const float ex = expf(-ax);
-            const float l = fmaxf(xv, 0.f) - xv * zv + log1pf(ex);
-            acc += (double)(wv * l);
-            if (dx) {
-                const float sg = xv >= 0.f ? 1.f / (1.f + ex) : ex / (1.f + ex);
-                dx[(bb * 2 + c) * HW + rem] = wv * (sg - zv) * inv_n * gscale;
-            }
-        }
-        if (mask) mask[e] = x1 > x0 ? 1 : 0;              // first maximum wins on ties -> class 0
-    }
-    acc = block_sum256(acc);
-    if (threadIdx.x == 0) partial[blockIdx.x] = acc;
-}
-
-__global__ void onehot2_kernel(const long long *__restrict__ labels, float *__restrict__ t, int B, size_t HW)
-{
-    const size_t total = (size_t)B * HW;
-    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
-        const size_t img = e / HW, rem = e - img * HW;
-        const float y = (float)labels[e];
-        t[(img * 2) * HW + rem] = 1.f - y;
-        t[(img * 2 + 1) * HW + rem] = y;
-    }
-}
-
-__global__ void argmax2_kernel(const float *__restrict__ x, long bs, long ps, long rs, long long *__restrict__ out,
-                               int B, int H, int W)
-{
-    const size_t total = (size_t)B * H * W;
-    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
-        size_t r = e;
-        const int xx = (int)(r % W); r /= W;
-        const int yy = (int)(r % H);
-        const long b = (long)(r / H);
-        const float *p = x + b * bs + yy * rs + xx;
-        out[e] = p[ps] > p[0] ? 1 : 0;            // first maximum wins on ties -> class 0
-    }
-}
-
 // L3: buf = first ? g : mu*buf + g ; p -= lr*buf over <= 46 tensors in one launch.  HBM-bound (3 reads + 2 writes per
 // element): a workgroup takes 4096-element chunks of one tensor (16 B per lane per access; the tensors' tails and any
 // tensor whose pointers are not 16-byte aligned take 4-byte accesses).  The multiply and the add are rounded separately,
@@ -799,56 +687,6 @@ int unet_maxpool2_bwd(const void *pre, const void *dy, void *dpre, int B, int H,
     return maxpool2_bwd(pre, dy, dpre, B, H, W, C, op_es(), (hipStream_t)stream);
 }
 
-size_t unet_bce_scratch_bytes(size_t numel) { return ((numel + BCE_PER_BLOCK - 1) / BCE_PER_BLOCK) * sizeof(double); }
-int unet_bce_logits(const void *logits, const void *target, const void *weight, long wsB, long wsC, long wsH, long wsW,
-                    int B, int H, int W, void *loss_out, void *dlogits, float grad_scale, void *scratch, void *stream)
-{
-    const size_t n = (size_t)B * 2 * H * W;
-    ARG_CHECK(n > 0 && loss_out && scratch, "bce: bad arguments");
-    const int nb = (int)((n + BCE_PER_BLOCK - 1) / BCE_PER_BLOCK);
-    hipStream_t st = (hipStream_t)stream;
-    ProfScope ps("L1.bce");
-    return profiled(PK_ELEMWISE, "bce_logits", st, 0.0, 0.0, 4.0 * (double)n * (2 + (weight ? 1 : 0) + (dlogits ? 1 : 0)), [&] {
-        hipLaunchKernelGGL(bce_logits_kernel, dim3(nb), dim3(256), 0, st, (const float *)logits, (const float *)target, (const float *)weight,
-                           wsB, wsC, wsH, wsW, H, W, n, (float *)dlogits, grad_scale, (double *)scratch);
-        hipLaunchKernelGGL(bce_final_kernel, dim3(1), dim3(256), 0, st, (const double *)scratch, nb, n, (float *)loss_out);
-    });
-}
-size_t unet_bce_step_scratch_bytes(size_t npix) { return ((npix + BCE_PX_PER_BLOCK - 1) / BCE_PX_PER_BLOCK) * sizeof(double); }
-int unet_bce_step(const void *logits, long xsB, long xsC, long xsH, const void *labels_i64, const void *weight, long wsB, long wsC,
-                  long wsH, long wsW, int B, int H, int W, void *loss_out, void *dlogits, float grad_scale, void *mask_i64, void *scratch,
-                  void *stream)
-{
-    const size_t npix = (size_t)B * H * W;
-    ARG_CHECK(npix > 0 && logits && labels_i64 && loss_out && scratch, "bce_step: bad arguments");
-    const int nb = (int)((npix + BCE_PX_PER_BLOCK - 1) / BCE_PX_PER_BLOCK);
-    hipStream_t st = (hipStream_t)stream;
-    ProfScope ps("L1.bce+L2.argmax");
-    // logits 8 B + label 8 B in, dlogits 8 B + mask 8 B out per pixel
-    return profiled(PK_ELEMWISE, "bce_step", st, 24.0 * npix, 0.0,
-                    (double)npix * (16.0 + (dlogits ? 8.0 : 0.0) + (mask_i64 ? 8.0 : 0.0) + (weight ? 8.0 : 0.0)), [&] {
-        hipLaunchKernelGGL(bce_step_kernel, dim3(nb), dim3(256), 0, st, (const float *)logits, xsB, xsC, xsH, (const long long *)labels_i64,
-                           (const float *)weight, wsB, wsC, wsH, wsW, H, W, npix, (float *)dlogits, grad_scale, (long long *)mask_i64, (double *)scratch);
-        hipLaunchKernelGGL(bce_final_kernel, dim3(1), dim3(256), 0, st, (const double *)scratch, nb, 2 * npix, (float *)loss_out);
-    });
-}
-
-int unet_onehot2(const void *labels_i64, void *target, int B, int H, int W, void *stream)
-{
-    hipStream_t st = (hipStream_t)stream;
-    ProfScope ps("L1.onehot");
-    return profiled(PK_ELEMWISE, "onehot2", st, 0.0, 0.0, 16.0 * (double)B * H * W, [&] {
-        hipLaunchKernelGGL(onehot2_kernel, dim3(grid_for((size_t)B * H * W)), dim3(256), 0, st, (const long long *)labels_i64, (float *)target, B, (size_t)H * W);
-    });
-}
-int unet_argmax2(const void *logits, long batch_stride, long plane_stride, long row_stride, void *out_i64, int B, int H, int W, void *stream)
-{
-    hipStream_t st = (hipStream_t)stream;
-    ProfScope ps("L2.argmax");
-    return profiled(PK_ELEMWISE, "argmax2", st, 0.0, 0.0, 16.0 * (double)B * H * W, [&] {
-        hipLaunchKernelGGL(argmax2_kernel, dim3(grid_for((size_t)B * H * W)), dim3(256), 0, st, (const float *)logits, batch_stride, plane_stride, row_stride, (long long *)out_i64, B, H, W);
-    });
-}
 int unet_sgd_momentum(void *const *params, const void *const *grads, void *const *bufs, const size_t *numel, int n,
                       float lr, float mu, int first_step, void *stream)
 {

@@ -1,4 +1,4 @@
-// elem.hpp — what the HBM-bound kernels (direct.hip, multiclass.hip, dice.hip, tile.hip, aux.hip) and the data-path files (label.hip, wmap.hip,
+// elem.hpp — what the HBM-bound kernels (direct.hip, loss.hip, multiclass.hip, dice.hip, tile.hip, aux.hip) and the data-path files (label.hip, wmap.hip,
 // prepare.hip, grow.hip, elastic.hip, clean.hip, warp.hip, measure.hip, hull.hip, through ov_table.hpp instances.hip and track.hip,
 // through sweep.hpp geo.hip, shape.hip, flood.hip, and through dm.hpp shape.hip and boundary.hip) share:
 //   device : 4 consecutive channels of an activation tensor stored as fp32 (16 B) or bf16 (8 B, arithmetic mode 2), read /

@@ -1,12 +1,9 @@
-// multiclass.hip — the K-class end of the net (2 <= K <= 16; the head at K = 2 stays direct.hip's head1x1), all HBM-bound:
-//   head   : finalconv 1x1, C -> K, NHWC in, NCHW logits out, and its backward (dz, dw [K,C], db [K])
-//   step   : pixel-wise softmax cross-entropy (Ronneberger et al. 2015, eq. 1) + its gradient + the argmax mask, one pass
-//   argmax : K-way argmax of a strided [B,K,H,W] view; crop + argmax + per-image K x K confusion counts
-// Kernels are templated on KP, the class count padded to 4, 8 or 16; the true K is a runtime bound (padded classes carry zero
-// weights and are never written).  See DESIGN §4f.
+// multiclass.hip — the K-class head of the net (2 < K <= 16; the head at K = 2 stays direct.hip's head1x1), HBM-bound: finalconv
+// 1x1, C -> K, NHWC in, NCHW logits out, and its backward (dz, dw [K,C], db [K]).  The kernels are templated on KP, the class
+// count padded to 4, 8 or 16; the true K is a runtime bound (padded classes carry zero weights and are never written).  The
+// K-class loss, argmax and confusion counts are loss.hip's.  See DESIGN §4f.
 #include "common.hpp"
 #include "elem.hpp"
-#include <cmath>
 #include "../../include/unet_hip.h"
 
 namespace unet {
@@ -194,147 +191,6 @@ __global__ __launch_bounds__(256) void headk_bwd_reduce_kernel(const float *__re
     if (lane == 0) { if (e < K * C) { if (dw) dw[e] = s; } else if (db) db[e - K * C] = s; }
 }
 
-// ---- softmax cross-entropy step (eq. 1): a thread owns a pixel (all K planes) -------------------------------------------
-// loss_px = w * (logsumexp(l) - l_label) formed as (m - l_label) + log(sum exp(l - m)), m = max l: both terms >= 0, so the
-// per-pixel value keeps full relative precision.  Partials per block in double, fixed-order finish.
-constexpr int CE_PX_PER_BLOCK = 2048;
-template <int KP>
-__global__ __launch_bounds__(256) void softmax_ce_kernel(const float *__restrict__ x, long xsB, long xsC, long xsH,
-                                                         const long long *__restrict__ labels, const float *__restrict__ w,
-                                                         long wsB, long wsH, long wsW, int K, int H, int W, size_t npix,
-                                                         float *__restrict__ dx, float gscale, long long *__restrict__ mask,
-                                                         double *__restrict__ partial, unsigned long long *__restrict__ bad_partial)
-{
-    const size_t b0 = (size_t)blockIdx.x * CE_PX_PER_BLOCK;
-    double acc = 0.0;
-    unsigned bad = 0;
-    const float inv_n = (float)(1.0 / (double)npix);
-    const unsigned HW = (unsigned)H * (unsigned)W;         // < 2^31 (checked on the host)
-    // (image, pixel-in-image) of this thread's first pixel by one 64-bit division, then stepped by 256 pixels per trip
-    size_t bb = (b0 + threadIdx.x) / HW;
-    unsigned rem = (unsigned)(b0 + threadIdx.x - bb * HW);
-    for (int i = threadIdx.x; i < CE_PX_PER_BLOCK; i += 256) {
-        const size_t e = b0 + i;
-        if (e >= npix) break;
-        const int yy = (int)(rem / (unsigned)W), xx = (int)(rem - (unsigned)yy * W);
-        const float *px = x + bb * xsB + (long)yy * xsH + xx;
-        float l[KP];
-#pragma unroll
-        for (int k = 0; k < KP; ++k) l[k] = k < K ? px[k * xsC] : 0.f;
-        float m = l[0];
-        int am = 0;
-#pragma unroll
-        for (int k = 1; k < KP; ++k) if (k < K && l[k] > m) { m = l[k]; am = k; }      // first maximum: torch.argmax's tie rule
-        const long long lab = labels[e];
-        const bool ok = lab >= 0 && lab < (long long)K;
-        float se = 0.f, ll = m, ex[KP];
-#pragma unroll
-        for (int k = 0; k < KP; ++k) {
-            ex[k] = k < K ? expf(l[k] - m) : 0.f;
-            se += ex[k];
-            if (k == lab) ll = l[k];
-        }
-        const float wv = w ? w[bb * wsB + (long)yy * wsH + (long)xx * wsW] : 1.f;
-        if (ok) acc += (double)wv * ((double)(m - ll) + (double)logf(se));
-        else ++bad;
-        if (dx) {
-            const float inv_se = 1.f / se;
-            const float sc = ok ? wv * inv_n * gscale : 0.f;
-#pragma unroll
-            for (int k = 0; k < KP; ++k)
-                if (k < K) dx[(bb * K + k) * HW + rem] = sc * (ex[k] * inv_se - (k == lab ? 1.f : 0.f));
-        }
-        if (mask) mask[e] = am;
-        rem += 256;
-        while (rem >= HW) { rem -= HW; ++bb; }
-    }
-    __shared__ double red[256];
-    __shared__ unsigned redb[256];
-    red[threadIdx.x] = acc;
-    redb[threadIdx.x] = bad;
-    __syncthreads();
-    for (int s2 = 128; s2 > 0; s2 >>= 1) {
-        if (threadIdx.x < s2) { red[threadIdx.x] += red[threadIdx.x + s2]; redb[threadIdx.x] += redb[threadIdx.x + s2]; }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) { partial[blockIdx.x] = red[0]; bad_partial[blockIdx.x] = redb[0]; }
-}
-
-__global__ __launch_bounds__(256) void softmax_ce_final_kernel(const double *__restrict__ partial, const unsigned long long *__restrict__ bad_partial,
-                                                               int nb, size_t n, float *loss, unsigned long long *invalid)
-{
-    __shared__ double red[256];
-    __shared__ unsigned long long redb[256];
-    double a = 0.0;
-    unsigned long long c = 0;
-    for (int i = threadIdx.x; i < nb; i += 256) { a += partial[i]; c += bad_partial[i]; }
-    red[threadIdx.x] = a;
-    redb[threadIdx.x] = c;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (threadIdx.x < s) { red[threadIdx.x] += red[threadIdx.x + s]; redb[threadIdx.x] += redb[threadIdx.x + s]; }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        *loss = (float)(red[0] / (double)n);
-        if (invalid) *invalid = redb[0];
-    }
-}
-
-// ---- K-way argmax of a strided view -------------------------------------------------------------------------------------
-template <int KP>
-__global__ __launch_bounds__(256) void argmaxk_kernel(const float *__restrict__ x, long bs, long ps, long rs, int K,
-                                                      long long *__restrict__ out, int H, int W, size_t total)
-{
-    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
-        size_t r = e;
-        const int xx = (int)(r % W); r /= W;
-        const int yy = (int)(r % H);
-        const long b = (long)(r / H);
-        const float *p = x + b * bs + yy * rs + xx;
-        float m = p[0];
-        int am = 0;
-#pragma unroll
-        for (int k = 1; k < KP; ++k) if (k < K) { const float v = p[k * ps]; if (v > m) { m = v; am = k; } }
-        out[e] = am;
-    }
-}
-
-// ---- crop + argmax + confusion counts: conf[b][label][pred], labels outside [0, K) go to invalid[b] -------------------------
-// Per block an LDS histogram (32-bit, a block sees < 2^32 pixels), then one integer atomic per nonzero bin: exact, deterministic.
-template <int KP>
-__global__ __launch_bounds__(256) void eval_confusion_kernel(const float *__restrict__ logits, long bs, long ps, long rs, int pad, int K,
-                                                             const long long *__restrict__ labels, long long *__restrict__ mask, int n,
-                                                             unsigned long long *__restrict__ conf, unsigned long long *__restrict__ invalid)
-{
-    __shared__ unsigned hist[KP * KP + 1];
-    const int b = blockIdx.y;
-    const size_t npx = (size_t)n * n;
-    if (labels) {
-        for (int i = threadIdx.x; i < KP * KP + 1; i += blockDim.x) hist[i] = 0;
-        __syncthreads();
-    }
-    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < npx; e += (size_t)gridDim.x * blockDim.x) {
-        const int xx = (int)(e % n), yy = (int)(e / n);
-        const float *p = logits + b * bs + (size_t)(yy + pad) * rs + xx + pad;
-        float m = p[0];
-        int am = 0;
-#pragma unroll
-        for (int k = 1; k < KP; ++k) if (k < K) { const float v = p[k * ps]; if (v > m) { m = v; am = k; } }
-        mask[(size_t)b * npx + e] = am;
-        if (labels) {
-            const long long lb = labels[(size_t)b * npx + e];
-            const int bin = (lb >= 0 && lb < (long long)K) ? (int)lb * K + am : KP * KP;
-            atomicAdd(&hist[bin], 1u);
-        }
-    }
-    if (!labels) return;
-    __syncthreads();
-    for (int i = threadIdx.x; i < K * K; i += blockDim.x)
-        if (hist[i]) atomicAdd(&conf[(size_t)b * K * K + i], (unsigned long long)hist[i]);
-    if (threadIdx.x == 0 && hist[KP * KP]) atomicAdd(&invalid[b], (unsigned long long)hist[KP * KP]);
-}
-
 }  // namespace mc
 
 // one block per HK_PPB-pixel chunk up to 4096 blocks (a 572^2 batch of 8 is 2353 chunks: no block takes two)
@@ -384,7 +240,6 @@ int headk_bwd(const void *x, int B, int H, int W, int C, int K, const float *w, 
 }  // namespace unet
 
 using namespace unet;
-using namespace unet::mc;
 
 extern "C" {
 
@@ -400,64 +255,6 @@ int unet_head1xk_bwd(const void *x, int B, int H, int W, int C, int K, const voi
     ARG_CHECK(x && w && dlogits && dz && scratch && B > 0 && H > 0 && W > 0, "unet_head1xk_bwd: bad argument");
     return headk_bwd(x, B, H, W, C, K, (const float *)w, (const float *)dlogits, 1.0f, dz, (float *)dw, (float *)db, (float *)scratch,
                      op_es(), (hipStream_t)stream);
-}
-
-size_t unet_softmax_ce_scratch_bytes(size_t npix) { return ((npix + CE_PX_PER_BLOCK - 1) / CE_PX_PER_BLOCK) * 2 * sizeof(double); }
-int unet_softmax_ce_step(const void *logits, long xsB, long xsC, long xsH, int K, const void *labels_i64, const void *weight, long wsB,
-                         long wsH, long wsW, int B, int H, int W, void *loss_out, void *dlogits, float grad_scale, void *mask_i64,
-                         void *invalid_u64, void *scratch, void *stream)
-{
-    const size_t npix = (size_t)B * H * W;
-    ARG_CHECK(B > 0 && H > 0 && W > 0 && logits && labels_i64 && loss_out && scratch, "unet_softmax_ce_step: bad arguments");
-    ARG_CHECK(K >= 2 && K <= UNET_MAX_CLASSES, "unet_softmax_ce_step: K=%d unsupported (2..%d)", K, UNET_MAX_CLASSES);
-    ARG_CHECK((size_t)H * W < ((size_t)1 << 31), "unet_softmax_ce_step: %d x %d pixels per image (must be < 2^31)", H, W);
-    const int nb = (int)((npix + CE_PX_PER_BLOCK - 1) / CE_PX_PER_BLOCK);
-    hipStream_t st = (hipStream_t)stream;
-    double *part = (double *)scratch;
-    unsigned long long *bad = (unsigned long long *)(part + nb);
-    ProfScope ps("L1.softmax_ce+L2.argmax");
-    // K logits + label (+ weight) in, K dlogits + mask out per pixel
-    return profiled(PK_ELEMWISE, "softmax_ce_step", st, 8.0 * K * npix, 0.0,
-                    (double)npix * (4.0 * K + 8.0 + (dlogits ? 4.0 * K : 0.0) + (mask_i64 ? 8.0 : 0.0) + (weight ? 4.0 : 0.0)), [&] {
-        CLASS_DISPATCH(K, hipLaunchKernelGGL(softmax_ce_kernel<KP_>, dim3(nb), dim3(256), 0, st, (const float *)logits, xsB, xsC, xsH,
-                                          (const long long *)labels_i64, (const float *)weight, wsB, wsH, wsW, K, H, W, npix,
-                                          (float *)dlogits, grad_scale, (long long *)mask_i64, part, bad));
-        hipLaunchKernelGGL(softmax_ce_final_kernel, dim3(1), dim3(256), 0, st, (const double *)part, (const unsigned long long *)bad, nb, npix,
-                           (float *)loss_out, (unsigned long long *)invalid_u64);
-    });
-}
-
-int unet_argmaxk(const void *logits, long batch_stride, long plane_stride, long row_stride, int K, void *out_i64, int B, int H, int W,
-                 void *stream)
-{
-    ARG_CHECK(logits && out_i64 && B > 0 && H > 0 && W > 0, "unet_argmaxk: bad argument");
-    ARG_CHECK(K >= 2 && K <= UNET_MAX_CLASSES, "unet_argmaxk: K=%d unsupported (2..%d)", K, UNET_MAX_CLASSES);
-    hipStream_t st = (hipStream_t)stream;
-    const size_t total = (size_t)B * H * W;
-    ProfScope ps("L2.argmax");
-    return profiled(PK_ELEMWISE, "argmaxk", st, 0.0, 0.0, (4.0 * K + 8.0) * (double)total, [&] {
-        CLASS_DISPATCH(K, hipLaunchKernelGGL(argmaxk_kernel<KP_>, dim3(grid_for(total)), dim3(256), 0, st, (const float *)logits, batch_stride,
-                                          plane_stride, row_stride, K, (long long *)out_i64, H, W, total));
-    });
-}
-
-int unet_eval_confusion(const void *logits, long batch_stride, long plane_stride, long row_stride, int pad, int K, const void *labels_i64,
-                        void *mask_i64, int B, int n, void *conf_u64, void *invalid_u64, void *stream)
-{
-    ARG_CHECK(logits && mask_i64 && B > 0 && n > 0 && pad >= 0, "unet_eval_confusion: bad argument");
-    ARG_CHECK(K >= 2 && K <= UNET_MAX_CLASSES, "unet_eval_confusion: K=%d unsupported (2..%d)", K, UNET_MAX_CLASSES);
-    ARG_CHECK(!labels_i64 || (conf_u64 && invalid_u64), "unet_eval_confusion: conf and invalid buffers needed with labels");
-    hipStream_t st = (hipStream_t)stream;
-    if (labels_i64) {
-        HIP_TRY(hipMemsetAsync(conf_u64, 0, (size_t)B * K * K * sizeof(unsigned long long), st));
-        HIP_TRY(hipMemsetAsync(invalid_u64, 0, (size_t)B * sizeof(unsigned long long), st));
-    }
-    const int gx = grid_for((size_t)n * n, 256, 256);
-    CLASS_DISPATCH(K, hipLaunchKernelGGL(eval_confusion_kernel<KP_>, dim3(gx, B), dim3(256), 0, st, (const float *)logits, batch_stride,
-                                      plane_stride, row_stride, pad, K, (const long long *)labels_i64, (long long *)mask_i64, n,
-                                      (unsigned long long *)conf_u64, (unsigned long long *)invalid_u64));
-    HIP_TRY(hipGetLastError());
-    return 0;
 }
 
 }  // extern "C"

@@ -9,6 +9,7 @@
 // output rows [oy0 + i*So, +So), columns [ox0 + j*So, +So), clipped to the image; the output rectangles partition it.
 #include "common.hpp"
 #include "elem.hpp"
+#include "softmax.hpp"
 #include "../../include/unet_hip.h"
 
 namespace unet {
@@ -111,7 +112,7 @@ __device__ __forceinline__ void load_logits4(const float *p, bool on, float (&l)
 }
 
 // one pixel's class probabilities.  BIN (K = 2): one plane, class 1 of the softmax of the two logits, p[0] = 1 / (1 + e^(l0 - l1));
-// else the softmax of all K classes as exp(l_k - max) / sum_j exp(l_j - max), the sum in increasing j
+// else the softmax of all K classes as exp(l_k - max) / sum_j exp(l_j - max), the sum in increasing j (softmax.hpp, as the losses)
 template <int KP, bool BIN>
 __device__ __forceinline__ void class_probs(const float (&l)[KP], int K, float (&p)[KP])
 {
@@ -119,14 +120,11 @@ __device__ __forceinline__ void class_probs(const float (&l)[KP], int K, float (
         p[0] = 1.f / (1.f + expf(l[0] - l[1]));
         return;
     }
-    float m = l[0];
+    int am;
+    float ex[KP];
+    const float se = class_exps<KP>(l, K, first_max<KP>([&](int k) { return l[k]; }, K, am), ex);
 #pragma unroll
-    for (int k = 1; k < KP; ++k) if (k < K && l[k] > m) m = l[k];
-    float ex[KP], se = 0.f;
-#pragma unroll
-    for (int k = 0; k < KP; ++k) { ex[k] = k < K ? expf(l[k] - m) : 0.f; se += ex[k]; }
-#pragma unroll
-    for (int k = 0; k < KP; ++k) p[k] = ex[k] / se;
+    for (int k = 0; k < KP; ++k) p[k] = ex[k] / se;         // true division (the loss kernels multiply by 1.f / se)
 }
 
 // one lane = 4 consecutive columns of one tile's output row (So % 4 == 0); rows and columns outside the image are skipped,

@@ -16,78 +16,96 @@ import torch
 import _hip
 
 
-class _BCEFn(torch.autograd.Function):
+class _LossFn(torch.autograd.Function):
+    """The autograd shell of the loss ops: the forward's device pass has written dlogits already, so backward is dl * g for the
+    logits (input 0) and None for every other input.  A forward saves dl unless the logits need no gradient (dl is then None)."""
+
     @staticmethod
-    def forward(ctx, logits, target, weight, wstrides, grad_scale):
+    def backward(ctx, g, *_unused):
+        (dl,) = ctx.saved_tensors
+        return (dl * g,) + (None,) * (len(ctx.needs_input_grad) - 1)       # one entry per input of forward
+
+
+def _step_inputs(ctx, logits, labels, want_mask, loss_shape=()):
+    """What the label-driven steps share: logits [B,K,H,W] with unit last stride, labels as contiguous int64 [B,H,W] on their
+    device, that device, and the outputs: loss (fp32, loss_shape), dl [B,K,H,W] (None unless the logits need a gradient) and
+    mask int64 [B,H,W] (None unless wanted)."""
+    B, K, H, W = logits.shape
+    # (read before any copy: forward runs with grad mode off, so a contiguous() copy never requires grad)
+    need_grad = ctx.needs_input_grad[0]
+    if logits.stride(3) != 1:
+        logits = logits.contiguous()
+    dev = logits.device
+    labels = labels.to(dev).reshape(B, H, W)
+    if labels.dtype != torch.int64:
+        labels = labels.long()
+    loss = torch.empty(loss_shape, dtype=torch.float32, device=dev)
+    dl = torch.empty(B, K, H, W, dtype=torch.float32, device=dev) if need_grad else None
+    mask = torch.empty(B, H, W, dtype=torch.int64, device=dev) if want_mask else None
+    return logits, labels.contiguous(), dev, loss, dl, mask
+
+
+def _no_mask(dev):
+    """What a forward returns in the mask's place when none was asked for (autograd wants a tensor)."""
+    return torch.empty(0, dtype=torch.int64, device=dev)
+
+
+def _broadcast_strides(weight, target, mismatch):
+    """The element strides with which `weight`, right-aligned, broadcasts against the shape `target`: 0 on every axis along
+    which it does not vary.  An axis that is neither 1 nor the target's raises mismatch(axis, size)."""
+    pad = len(target) - weight.dim()
+    shape = (1,) * pad + tuple(weight.shape)
+    st = (0,) * pad + tuple(weight.stride())
+    for d, n in enumerate(target):
+        if shape[d] not in (n, 1):
+            raise mismatch(d, shape[d])
+    return [st[d] if shape[d] > 1 else 0 for d in range(len(target))]
+
+
+def _weight_strides(weight, logits):
+    """torch broadcasting of `weight` against [B,2,H,W] as four element strides (0 on broadcast axes); like the reference
+    (trainer.py:72-75), a [B,H,W] map is right-aligned: its first axis meets the CLASS axis (quirk Q4), other sizes raise.
+    No weight: (None, zeros)."""
+    if weight is None:
+        return None, (0, 0, 0, 0)
+    weight = weight.to(logits.device, torch.float32).contiguous()
+    return weight, _broadcast_strides(weight, logits.shape, lambda d, size: RuntimeError(
+        "The size of tensor a (%d) must match the size of tensor b (%d) at non-singleton dimension %d" % (logits.shape[d], size, d)))
+
+
+class _BCEFn(_LossFn):
+    @staticmethod
+    def forward(ctx, logits, target, weight, ws, grad_scale):
         B, two, H, W = logits.shape
         assert two == 2
         logits = logits.contiguous()
         target = target.contiguous()
         loss = torch.empty((), dtype=torch.float32, device=logits.device)
         dl = torch.empty_like(logits)
-        sc = torch.empty(_hip.lib().unet_bce_scratch_bytes(logits.numel()), dtype=torch.uint8, device=logits.device)
-        ws = wstrides if weight is not None else (0, 0, 0, 0)
+        sc = _hip.scratch("unet_bce", logits.device, logits.numel())
         _hip.run("unet_bce_logits", logits.device, _hip.ptr(logits), _hip.ptr(target), _hip.ptr(weight), ws[0], ws[1], ws[2], ws[3],
                  B, H, W, _hip.ptr(loss), _hip.ptr(dl), float(grad_scale), _hip.ptr(sc))
         ctx.save_for_backward(dl)
         return loss
 
-    @staticmethod
-    def backward(ctx, g):
-        (dl,) = ctx.saved_tensors
-        return dl * g, None, None, None, None
 
-
-def _weight_strides(weight, logits):
-    """torch broadcasting of `weight` against [B,2,H,W] as four element strides (0 on broadcast axes); like the reference
-    (trainer.py:72-75), a [B,H,W] map is right-aligned: its first axis meets the CLASS axis (quirk Q4), other sizes raise."""
-    weight = weight.to(logits.device, torch.float32).contiguous()
-    shape = (1,) * (4 - weight.dim()) + tuple(weight.shape)
-    st = (0,) * (4 - weight.dim()) + tuple(weight.stride())
-    wstrides = []
-    for d in range(4):
-        if shape[d] == logits.shape[d]:
-            wstrides.append(st[d])
-        elif shape[d] == 1:
-            wstrides.append(0)
-        else:
-            raise RuntimeError("The size of tensor a (%d) must match the size of tensor b (%d) at non-singleton "
-                               "dimension %d" % (logits.shape[d], shape[d], d))
-    return weight, wstrides
-
-
-class _BCEStepFn(torch.autograd.Function):
+class _BCEStepFn(_LossFn):
     """unet_bce_step: loss (+ its gradient) and the argmax mask from logits and integer labels in one device pass."""
 
     @staticmethod
-    def forward(ctx, logits, labels, weight, wstrides, grad_scale, want_mask):
+    def forward(ctx, logits, labels, weight, ws, grad_scale, want_mask):
         B, two, H, W = logits.shape
         assert two == 2
-        # (read before any copy: forward runs with grad mode off, so a contiguous() copy never requires grad)
-        need_grad = ctx.needs_input_grad[0]
-        if logits.stride(3) != 1:
-            logits = logits.contiguous()
-        labels = labels.to(logits.device).reshape(B, H, W).contiguous()
-        if labels.dtype != torch.int64:
-            labels = labels.long()
-        loss = torch.empty((), dtype=torch.float32, device=logits.device)
-        dl = torch.empty(B, 2, H, W, dtype=torch.float32, device=logits.device) if need_grad else None
-        mask = torch.empty(B, H, W, dtype=torch.int64, device=logits.device) if want_mask else None
-        sc = torch.empty(_hip.lib().unet_bce_step_scratch_bytes(B * H * W), dtype=torch.uint8, device=logits.device)
-        ws = wstrides if weight is not None else (0, 0, 0, 0)
-        _hip.run("unet_bce_step", logits.device, _hip.ptr(logits), logits.stride(0), logits.stride(1), logits.stride(2), _hip.ptr(labels),
+        logits, labels, dev, loss, dl, mask = _step_inputs(ctx, logits, labels, want_mask)
+        sc = _hip.scratch("unet_bce_step", dev, B * H * W)
+        _hip.run("unet_bce_step", dev, _hip.ptr(logits), logits.stride(0), logits.stride(1), logits.stride(2), _hip.ptr(labels),
                  _hip.ptr(weight), ws[0], ws[1], ws[2], ws[3], B, H, W, _hip.ptr(loss), _hip.ptr(dl), float(grad_scale), _hip.ptr(mask), _hip.ptr(sc))
-        if need_grad:
+        if dl is not None:
             ctx.save_for_backward(dl)
-        if mask is not None:
-            ctx.mark_non_differentiable(mask)
-            return loss, mask
-        return loss, torch.empty(0, dtype=torch.int64, device=logits.device)
-
-    @staticmethod
-    def backward(ctx, g, _gmask):
-        (dl,) = ctx.saved_tensors
-        return dl * g, None, None, None, None, None
+        if mask is None:
+            return loss, _no_mask(dev)
+        ctx.mark_non_differentiable(mask)
+        return loss, mask
 
 
 def bce_argmax_step(preds, labels, weight=None, grad_scale=1.0, want_mask=True):
@@ -95,9 +113,7 @@ def bce_argmax_step(preds, labels, weight=None, grad_scale=1.0, want_mask=True):
          loss = BCEWithLogitsLoss(weight)(preds, [1 - y, y])      mask = preds.argmax(dim=1)
     preds [B,2,H,W] (any view with unit last stride, e.g. the trainer's centre crop), labels int64 [B,1,H,W] or [B,H,W].
     Returns (loss, mask | None); loss.backward() feeds the gradient the same pass produced."""
-    wstrides = None
-    if weight is not None:
-        weight, wstrides = _weight_strides(weight, preds)
+    weight, wstrides = _weight_strides(weight, preds)
     loss, mask = _BCEStepFn.apply(preds, labels, weight, wstrides, grad_scale, want_mask)
     return loss, (mask if want_mask else None)
 
@@ -106,9 +122,7 @@ def bce_with_logits(logits, target, weight=None, grad_scale=1.0):
     """mean(weight * bce(logits, target)).  `weight` follows torch broadcasting against
     [B,2,H,W]: like the reference (trainer.py:72-75), a [B,H,W] map is right-aligned, i.e. its
     first axis meets the CLASS axis and must be 1 or 2 (quirk Q4) — other sizes raise."""
-    wstrides = None
-    if weight is not None:
-        weight, wstrides = _weight_strides(weight, logits)
+    weight, wstrides = _weight_strides(weight, logits)
     return _BCEFn.apply(logits, target, weight, wstrides, grad_scale)
 
 
@@ -277,19 +291,25 @@ def clip_grad_norm_(parameters, max_norm, *, scale=True):
     return out2[0], out2[1]
 
 
+def _crop_to_labels(preds, labels):
+    """The centre crop of the two back ends below: `preds` [B,K,So,So] (unit last stride) is cropped to the labels' size n (So
+    without labels).  Returns labels as contiguous [B,n,n] on preds' device (or None), the empty mask int64 [B,n,n], n and the pad."""
+    B, So = preds.shape[0], preds.shape[2]
+    assert preds.stride(3) == 1
+    n = So
+    if labels is not None:
+        labels = labels.to(preds.device).reshape(B, labels.shape[-2], labels.shape[-1]).contiguous()
+        n = labels.shape[-1]
+    return labels, torch.empty(B, n, n, dtype=torch.int64, device=preds.device), n, int((So - n) / 2)
+
+
 def crop_argmax_metrics(preds, labels=None):
     """Fused back end of the test/validation step (tester.py:29-42): centre-crop `preds` [B,2,So,So] to the
     label size, argmax over the two classes, and (with int64 labels [B,1,n,n] or [B,n,n]) count
     sum(pred&label), sum(pred|label), sum|pred-label| per image.  Returns (mask int64 [B,n,n], stats int64 [B,3] | None)."""
-    B, two, So, _ = preds.shape
-    assert two == 2 and preds.stride(3) == 1
-    if labels is not None:
-        labels = labels.to(preds.device).reshape(B, labels.shape[-2], labels.shape[-1]).contiguous()
-        n = labels.shape[-1]
-    else:
-        n = So
-    pad = int((So - n) / 2)
-    mask = torch.empty(B, n, n, dtype=torch.int64, device=preds.device)
+    B, two = preds.shape[:2]
+    assert two == 2
+    labels, mask, n, pad = _crop_to_labels(preds, labels)
     stats = torch.empty(B, 3, dtype=torch.int64, device=preds.device) if labels is not None else None
     _hip.run("unet_eval_masks", preds.device, _hip.ptr(preds), preds.stride(0), preds.stride(1), preds.stride(2), pad, _hip.ptr(labels),
              _hip.ptr(mask), B, n, _hip.ptr(stats))
@@ -301,60 +321,45 @@ def crop_argmax_metrics(preds, labels=None):
 def _pixel_weight_strides(weight, preds):
     """A per-pixel weight [B,H,W] / [H,W] / [1,H,W] (or anything that broadcasts to [B,H,W]) as three element strides
     (batch, row, column; 0 on broadcast axes).  Unlike the BCE path's right-alignment against [B,2,H,W] (quirk Q4), the map
-    is aligned with the PIXELS: weight[b, y, x] multiplies pixel (b, y, x) of every class."""
+    is aligned with the PIXELS: weight[b, y, x] multiplies pixel (b, y, x) of every class.  No weight: (None, zeros)."""
+    if weight is None:
+        return None, (0, 0, 0)
     B, _, H, W = preds.shape
     weight = weight.to(preds.device, torch.float32)
     if weight.dim() == 4 and weight.shape[1] == 1:
         weight = weight[:, 0]
+    error = ValueError("softmax_ce_step: weight must broadcast to [B,H,W] = %s, got %s" % ((B, H, W), tuple(weight.shape)))
     if weight.dim() > 3:
-        raise ValueError("softmax_ce_step: weight must broadcast to [B,H,W] = %s, got %s" % ((B, H, W), tuple(weight.shape)))
-    shape = (1,) * (3 - weight.dim()) + tuple(weight.shape)
-    st = (0,) * (3 - weight.dim()) + tuple(weight.stride())
-    out = []
-    for d, n in enumerate((B, H, W)):
-        if shape[d] == n:
-            out.append(st[d] if n > 1 else 0)
-        elif shape[d] == 1:
-            out.append(0)
-        else:
-            raise ValueError("softmax_ce_step: weight must broadcast to [B,H,W] = %s, got %s" % ((B, H, W), tuple(weight.shape)))
-    return weight, out
+        raise error
+    return weight, _broadcast_strides(weight, (B, H, W), lambda d, size: error)
 
 
-class _SoftmaxCEFn(torch.autograd.Function):
+def _raise_invalid(name, invalid, K):
+    """validate=True of the K-class steps: reads the kernel's count of labels outside [0, K) back (8 bytes, one host sync)."""
+    n = int(invalid.item())
+    if n:
+        raise ValueError("%s: %d label(s) outside [0, %d)" % (name, n, K))
+
+
+class _SoftmaxCEFn(_LossFn):
     """unet_softmax_ce_step: loss (+ its gradient), the argmax mask and the invalid-label count in one device pass."""
 
     @staticmethod
-    def forward(ctx, logits, labels, weight, wstrides, grad_scale, want_mask):
+    def forward(ctx, logits, labels, weight, ws, grad_scale, want_mask):
         B, K, H, W = logits.shape
-        need_grad = ctx.needs_input_grad[0]
-        if logits.stride(3) != 1:
-            logits = logits.contiguous()
-        labels = labels.to(logits.device).reshape(B, H, W)
-        if labels.dtype != torch.int64:
-            labels = labels.long()
-        labels = labels.contiguous()
-        loss = torch.empty((), dtype=torch.float32, device=logits.device)
-        invalid = torch.empty((), dtype=torch.int64, device=logits.device)
-        dl = torch.empty(B, K, H, W, dtype=torch.float32, device=logits.device) if need_grad else None
-        mask = torch.empty(B, H, W, dtype=torch.int64, device=logits.device) if want_mask else None
-        sc = torch.empty(_hip.lib().unet_softmax_ce_scratch_bytes(B * H * W), dtype=torch.uint8, device=logits.device)
-        ws = wstrides if weight is not None else (0, 0, 0)
-        _hip.run("unet_softmax_ce_step", logits.device, _hip.ptr(logits), logits.stride(0), logits.stride(1), logits.stride(2), K,
+        logits, labels, dev, loss, dl, mask = _step_inputs(ctx, logits, labels, want_mask)
+        invalid = torch.empty((), dtype=torch.int64, device=dev)
+        sc = _hip.scratch("unet_softmax_ce", dev, B * H * W)
+        _hip.run("unet_softmax_ce_step", dev, _hip.ptr(logits), logits.stride(0), logits.stride(1), logits.stride(2), K,
                  _hip.ptr(labels), _hip.ptr(weight), ws[0], ws[1], ws[2], B, H, W, _hip.ptr(loss), _hip.ptr(dl), float(grad_scale),
                  _hip.ptr(mask), _hip.ptr(invalid), _hip.ptr(sc))
-        if need_grad:
+        if dl is not None:
             ctx.save_for_backward(dl)
         ctx.mark_non_differentiable(invalid)
-        if mask is not None:
-            ctx.mark_non_differentiable(mask)
-            return loss, mask, invalid
-        return loss, torch.empty(0, dtype=torch.int64, device=logits.device), invalid
-
-    @staticmethod
-    def backward(ctx, g, _gmask, _ginvalid):
-        (dl,) = ctx.saved_tensors
-        return dl * g, None, None, None, None, None
+        if mask is None:
+            return loss, _no_mask(dev), invalid
+        ctx.mark_non_differentiable(mask)
+        return loss, mask, invalid
 
 
 def softmax_ce_step(preds, labels, weight=None, grad_scale=1.0, want_mask=True, validate=True):
@@ -369,14 +374,10 @@ def softmax_ce_step(preds, labels, weight=None, grad_scale=1.0, want_mask=True, 
     the same pass produced (x grad_scale), as bce_argmax_step does."""
     if preds.dim() != 4 or preds.shape[1] < 2:
         raise ValueError("softmax_ce_step: expected preds [B,K,H,W] with K >= 2, got %s" % (tuple(preds.shape),))
-    wstrides = None
-    if weight is not None:
-        weight, wstrides = _pixel_weight_strides(weight, preds)
+    weight, wstrides = _pixel_weight_strides(weight, preds)
     loss, mask, invalid = _SoftmaxCEFn.apply(preds, labels, weight, wstrides, grad_scale, want_mask)
     if validate:
-        n = int(invalid.item())
-        if n:
-            raise ValueError("softmax_ce_step: %d label(s) outside [0, %d)" % (n, preds.shape[1]))
+        _raise_invalid("softmax_ce_step", invalid, preds.shape[1])
     return loss, (mask if want_mask else None)
 
 
@@ -389,41 +390,26 @@ class DiceParts(collections.namedtuple("DiceParts", "ce dice per_class")):
     coefficients, fp32 [B,K] ([1,K] with batch=True), of every class whether it is counted in the mean or not."""
 
 
-class _DiceFn(torch.autograd.Function):
+class _DiceFn(_LossFn):
     """unet_dice_step: the loss and its parts, the gradient, the argmax mask and the invalid-label count in one call."""
 
     @staticmethod
-    def forward(ctx, logits, labels, weight, wstrides, ce_weight, dice_weight, smooth, flags, grad_scale, want_mask):
+    def forward(ctx, logits, labels, weight, ws, ce_weight, dice_weight, smooth, flags, grad_scale, want_mask):
         B, K, H, W = logits.shape
-        need_grad = ctx.needs_input_grad[0]
-        if logits.stride(3) != 1:
-            logits = logits.contiguous()
-        labels = labels.to(logits.device).reshape(B, H, W)
-        if labels.dtype != torch.int64:
-            labels = labels.long()
-        labels = labels.contiguous()
-        dev = logits.device
-        losses = torch.empty(3, dtype=torch.float32, device=dev)
+        logits, labels, dev, losses, dl, mask = _step_inputs(ctx, logits, labels, want_mask, loss_shape=(3,))
         coeffs = torch.empty(1 if flags & DICE_BATCH else B, K, dtype=torch.float32, device=dev)
         invalid = torch.empty((), dtype=torch.int64, device=dev)
-        dl = torch.empty(B, K, H, W, dtype=torch.float32, device=dev) if need_grad else None
-        mask = torch.empty(B, H, W, dtype=torch.int64, device=dev) if want_mask else torch.empty(0, dtype=torch.int64, device=dev)
         sc = _hip.scratch("unet_dice", dev, B, K, H, W)
-        ws = wstrides if weight is not None else (0, 0, 0)
         _hip.run("unet_dice_step", dev, _hip.ptr(logits), logits.stride(0), logits.stride(1), logits.stride(2), K, _hip.ptr(labels),
                  _hip.ptr(weight), ws[0], ws[1], ws[2], B, H, W, float(ce_weight), float(dice_weight), float(smooth), int(flags),
-                 _hip.ptr(losses), _hip.ptr(coeffs), _hip.ptr(dl), float(grad_scale), _hip.ptr(mask) if want_mask else None,
-                 _hip.ptr(invalid), _hip.ptr(sc))
-        if need_grad:
+                 _hip.ptr(losses), _hip.ptr(coeffs), _hip.ptr(dl), float(grad_scale), _hip.ptr(mask), _hip.ptr(invalid), _hip.ptr(sc))
+        if dl is not None:
             ctx.save_for_backward(dl)
+        if mask is None:
+            mask = _no_mask(dev)
         loss, ce, dice = losses[0], losses[1], losses[2]
         ctx.mark_non_differentiable(ce, dice, coeffs, mask, invalid)
         return loss, ce, dice, coeffs, mask, invalid
-
-    @staticmethod
-    def backward(ctx, g, *_unused):
-        (dl,) = ctx.saved_tensors
-        return (dl * g,) + (None,) * 9
 
 
 def dice_step(preds, labels, weight=None, *, ce_weight=0.0, dice_weight=1.0, smooth=1.0, batch=False, include_background=True,
@@ -453,16 +439,12 @@ def dice_step(preds, labels, weight=None, *, ce_weight=0.0, dice_weight=1.0, smo
         raise ValueError("dice_step: ce_weight and dice_weight are both 0")
     if weight is not None and ce_weight == 0.0:
         raise ValueError("dice_step: a weight map multiplies the cross-entropy term only; with ce_weight = 0 it would be unused")
-    wstrides = None
-    if weight is not None:
-        weight, wstrides = _pixel_weight_strides(weight, preds)
+    weight, wstrides = _pixel_weight_strides(weight, preds)
     flags = (DICE_BATCH if batch else 0) | (0 if include_background else DICE_SKIP_BACKGROUND)
     loss, ce, dice, coeffs, mask, invalid = _DiceFn.apply(preds, labels, weight, wstrides, ce_weight, dice_weight, smooth, flags,
                                                           grad_scale, want_mask)
     if validate:
-        n = int(invalid.item())
-        if n:
-            raise ValueError("dice_step: %d label(s) outside [0, %d)" % (n, preds.shape[1]))
+        _raise_invalid("dice_step", invalid, preds.shape[1])
     out = (loss, mask if want_mask else None)
     return out + (DiceParts(ce, dice, coeffs),) if return_parts else out
 
@@ -481,15 +463,8 @@ def crop_argmax_confusion(preds, labels=None, return_invalid=False):
     [B,1,n,n] or [B,n,n], the per-image confusion counts conf[b, i, j] = pixels labelled i predicted j (unet_eval_confusion).
     Labels outside [0, K) fall in no bin; return_invalid=True also returns their per-image count.
     Returns (mask int64 [B,n,n], conf int64 [B,K,K] | None) (+ invalid int64 [B] | None)."""
-    B, K, So, _ = preds.shape
-    assert preds.stride(3) == 1
-    if labels is not None:
-        labels = labels.to(preds.device).reshape(B, labels.shape[-2], labels.shape[-1]).contiguous()
-        n = labels.shape[-1]
-    else:
-        n = So
-    pad = int((So - n) / 2)
-    mask = torch.empty(B, n, n, dtype=torch.int64, device=preds.device)
+    B, K = preds.shape[:2]
+    labels, mask, n, pad = _crop_to_labels(preds, labels)
     conf = torch.empty(B, K, K, dtype=torch.int64, device=preds.device) if labels is not None else None
     invalid = torch.empty(B, dtype=torch.int64, device=preds.device) if labels is not None else None
     _hip.run("unet_eval_confusion", preds.device, _hip.ptr(preds), preds.stride(0), preds.stride(1), preds.stride(2), pad, K,

@@ -1,4 +1,4 @@
-"""fp64 numpy / scipy references and the fixed inputs of the per-op tests of aux.hip (tests/test_aux_ops_gpu.py), pinned to
+"""fp64 numpy / scipy references and the fixed inputs of the per-op tests of aux.hip and unet_eval_masks (tests/test_aux_ops_gpu.py), pinned to
 scipy and to oracle/aux_ref.py by tests/test_aux_ops_cpu.py.  Imported like the other *_ref.py files.
 
 The inputs are part of the reference: they are built so that every comparison is well-posed before a GPU is involved

@@ -1,8 +1,8 @@
 """Plain numpy restatements of the K-class end of the net (Unet(n_classes=K)): the paper's softmax cross-entropy (eq. 1) and
 its gradient, the K-way argmax, the per-image confusion counts and the K-class overlap-tile stitch.
 tests/test_multiclass_cpu.py pins them to torch (F.cross_entropy, torch.argmax, torch.bincount) in fp64.
-Also the seeded inputs, the shape lists and the error bounds that tests/test_multiclass_ops_gpu.py holds the kernels of
-multiclass.hip to; tests/test_multiclass_cpu.py proves those inputs well-posed without a device."""
+Also the seeded inputs, the shape lists and the error bounds that tests/test_multiclass_ops_gpu.py holds the K-class
+kernels of loss.hip and multiclass.hip to; tests/test_multiclass_cpu.py proves those inputs well-posed without a device."""
 import math
 
 

@@ -1,4 +1,4 @@
-"""fp64 references of the step-side kernels of direct.hip (bce_logits, bce_step, onehot2, argmax2, sgd_momentum), shared by
+"""fp64 references of the step-side kernels of loss.hip (bce_logits, bce_step, onehot2, argmax2) and direct.hip (sgd_momentum), shared by
 tests/test_ops_gpu.py and tests/test_step_ops_gpu.py.  Imported like the other *_ref.py files."""
 import ctypes as C
 

@@ -1,4 +1,4 @@
-"""Per-op tests of aux.hip through the C ABI: every entry point either side of the hot path against the fp64 references of
+"""Per-op tests of aux.hip (and loss.hip's unet_eval_masks) through the C ABI: every entry point either side of the hot path against the fp64 references of
 tests/aux_ops_ref.py (pinned to scipy and oracle/aux_ref.py, and their inputs shown well-posed, by tests/test_aux_ops_cpu.py)
 at small adversarial shapes: H != W, pad != S, odd sizes, more than one block, the grid-stride loops behind the grid caps,
 windows and pads longer than the image.  Every pointer handed to the library comes from a guarded.Arena (tests/guarded.py):

@@ -183,6 +183,7 @@ def test_ce_shape_and_class_lists():
     assert [b * h * w for b, h, w in ref.CE_SHAPES] == [1, 2047, 2048, 2049, 2100, 255, 525312]
     assert 300 * 1 * 7 == 2100 and 1 * 7 < 256                        # a thread's next pixel lies 256 / 7 = 36 images on
     assert -(-525312 // 2048) == 257                                   # partials: one more than the finisher's 256 threads
+    assert (3, 1, 683) in ref.CE_SMALL_SHAPES and 683 < 2048 < 3 * 683  # one block over three images
     small = [c for c in ref.CE_CASES if c[0] != ref.CE_LARGE_SHAPE]
     assert [c for c in ref.CE_CASES if c[0] == ref.CE_LARGE_SHAPE] == [(ref.CE_LARGE_SHAPE, 3)]
     assert len(set(small)) == len(small)

@@ -1,4 +1,4 @@
-"""Per-op tests of multiclass.hip (unet_softmax_ce_step, unet_argmaxk, unet_eval_confusion, unet_head1xk_fwd / _bwd) through
+"""Per-op tests of the K-class kernels of loss.hip (unet_softmax_ce_step, unet_argmaxk, unet_eval_confusion) and multiclass.hip (unet_head1xk_fwd / _bwd) through
 the C ABI against the fp64 references of tests/multiclass_ref.py, at the shapes where the kernels change path: pixel counts
 either side of a block's quantum, images smaller than a block's stride, more partials than the finisher has threads, more
 pixels than a capped grid has threads, every class padding (KP = 4, 8, 16, full and padded), logits at which expf underflows

@@ -1,6 +1,6 @@
-"""Per-op tests of the step-side kernels of direct.hip (bce_logits, bce_step, onehot2, argmax2, sgd_momentum) through the
-C ABI against the fp64 references of tests/step_ref.py: logits large enough for the log1pf(expf(-|x|)) and ex / (1 + ex)
-branches, element counts either side of BCE_PER_BLOCK (4096), BCE_PX_PER_BLOCK (2048) and SGD_CHUNK (4096), H != W, every
+"""Per-op tests of the 2-class step-side kernels of loss.hip (bce_logits, bce_step, onehot2, argmax2) and of direct.hip's
+sgd_momentum through the C ABI against the fp64 references of tests/step_ref.py: logits large enough for the
+log1pf(expf(-|x|)) and ex / (1 + ex) branches, element counts either side of BCE_PER_BLOCK (4096), BCE_PX_PER_BLOCK (2048) and SGD_CHUNK (4096), H != W, every
 weight broadcast, strided logits inside NaN.  Every pointer handed to the library comes from a guarded.Arena
 (tests/guarded.py); mem.verify(outputs...) after every call = every element written, every guard intact.
 Tolerances are those of test_ops_gpu.py::test_step_side_kernels: 1e-5 relative on the loss, 1e-5 normalised on the gradient;
@@ -53,8 +53,9 @@ def weight_forms(B, H, W):
 
 
 # 1, 2047, 2048, 2049 and 3 * 2048 + 5 pixels (bce_step's 2048 per block) = 2, 4094, 4096, 4098 and 3 * 4096 + 10 elements
-# (bce_logits' 4096 per block), with H != W
-SHAPES = [(1, 1, 1), (1, 23, 89), (2, 16, 64), (3, 1, 683), (11, 13, 43)]
+# (bce_logits' 4096 per block), with H != W; 3 x 683: a block over three images; then 257 blocks of either kernel: the second trip
+# of the finisher's 256 threads over the partials (the loop it shares with the soft-max CE and Dice finishers)
+SHAPES = [(1, 1, 1), (1, 23, 89), (2, 16, 64), (3, 1, 683), (11, 13, 43), (2, 513, 512)]
 
 
 @pytest.mark.parametrize("B,H,W", SHAPES)
@@ -65,7 +66,8 @@ def test_bce_step_and_bce_logits(hip, B, H, W):
     onehot2 + bce_logits + argmax2 on the same data: gradient bit-equal, loss within the tolerance."""
     L = hip.lib()
     npix = B * H * W
-    assert [b * h * w for b, h, w in SHAPES] == [1, 2047, 2048, 2049, 3 * 2048 + 5] and (H != W or npix == 1)
+    assert [b * h * w for b, h, w in SHAPES] == [1, 2047, 2048, 2049, 3 * 2048 + 5, 256 * 2048 + 1024] and (H != W or npix == 1)
+    assert -(-SHAPES[-1][0] * 513 * 512 // 2048) == 257 == -(-2 * SHAPES[-1][0] * 513 * 512 // 4096) and 683 < 2048 < 3 * 683
     x, labels = logits_and_labels(B, H, W)
     z = step_ref.onehot2(labels)
     mask_ref = step_ref.argmax2(x)

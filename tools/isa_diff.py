@@ -7,7 +7,8 @@ change code: run it on a CPU-only machine, hipcc cross-compiles).
 Each file of both trees is compiled with  hipcc -O3 -std=c++17 --offload-arch=gfx950 --cuda-device-only -S;  comments,
 .file / .ident / .loc / .cfi lines and the __hip_cuid_* symbol are dropped, a kernel's own symbol and the function
 numbers in local labels are normalised, and per kernel the instruction stream, the .amdhsa_* lines and the metadata
-resource lines (VGPRs, SGPRs, LDS, scratch, kernarg size) are compared.  Kernels are paired by mangled name; kernels left
+resource lines (VGPRs, SGPRs, LDS, scratch, kernarg size) are compared.  Kernels are paired by mangled name, per file; a kernel
+that has left its file is looked up by that name in the other *.hip of NEW (it moved: same check, no --allow); kernels left
 over on both sides (a template parameter was removed: the symbol changes) are paired when their normalised code is equal.
 Exit status 0 iff every kernel of the parent has an identical partner or matches --allow REGEX (kernels that are meant to
 change, their resource lines are printed, or to go: an instantiation nothing launches); -v prints a unified diff of those
@@ -88,10 +89,17 @@ def main():
     demangle = lambda s: subprocess.run(["c++filt", s], capture_output=True, text=True).stdout.strip() or s
     bad = 0
     with tempfile.TemporaryDirectory() as tmp, ThreadPoolExecutor(max_workers=min(12, os.cpu_count() or 1)) as ex:
+        new_files = sorted(set(a.files) | {f for f in os.listdir(a.new) if f.endswith(".hip")})
         jobs = {(side, f): ex.submit(compile_s, a.hipcc, os.path.join(os.path.abspath(d), f), os.path.join(tmp, side + "_" + f + ".s"))
-                for side, d in (("a", a.parent), ("b", a.new)) for f in a.files}
+                for side, d, fs in (("a", a.parent, a.files), ("b", a.new, new_files)) for f in fs}
+        new = {f: kernels(jobs[("b", f)].result()) for f in new_files}
         for f in a.files:
-            ka, kb = kernels(jobs[("a", f)].result()), kernels(jobs[("b", f)].result())
+            ka, kb = kernels(jobs[("a", f)].result()), dict(new[f])
+            for n in [n for n in ka if n not in kb]:      # a kernel that left this file: its new home, by mangled name
+                home = next((g for g in new_files if n in new[g]), None)
+                if home:
+                    kb[n] = new[home][n]
+                    print("%s: %s is now in %s" % (f, demangle(n), home))
             pairs = [(n, n) for n in ka if n in kb]
             left_a, left_b = [n for n in ka if n not in kb], [n for n in kb if n not in ka]
             for n in list(left_a):                       # renamed symbols: pair by equal code, else in order of appearance
